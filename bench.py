@@ -9,8 +9,12 @@ A "step" is one pass of the tick pipeline over one batch of independent C2 scena
 primitives, 8 dynamic opponents with a 0.2 s prediction each = 16 obstacle positions, sample zone) whose inputs are already
 resident in HBM (ltpl_batch_upload). Every rank owns one GPU and its own shard of scenarios (weak scaling, no data-path
 collective: scenarios are independent); torch.distributed (RCCL) is only used for the barrier and the
-max-over-ranks of the timed region. The timed region is the K-step block repeated until it lasts >= 2 s (`timed_steps` in the
-line; `ms_per_step` and `value` are per step), bracketed by barrier + synchronize on both sides.
+max-over-ranks of the timed region. The timed region is exactly K steps (`timed_steps` in the line; `ms_per_step` and `value`
+are per step), bracketed by barrier + synchronize on both sides.
+
+  --dump-outputs DIR   after the timed steps, write what the last step computed (the arrays ltpl_batch_download hands the caller)
+                  as DIR/<name>.npy, float64: see dump_outputs(). The inputs are seeded, so two builds run with the same arguments
+                  can be compared output for output.
 
 The JSON line also carries
   roofline        ALGORITHMIC bytes per launch (graphbasedlocaltrajectoryplanner_amd/roofline.py) of the
@@ -51,7 +55,9 @@ from graphbasedlocaltrajectoryplanner_amd.roofline import algorithmic_bytes  # n
 from graphbasedlocaltrajectoryplanner_amd.scenario_gen import c2_scenarios   # noqa: E402
 
 HBM_PEAK_GBPS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s (spec)
-MIN_TIMED_S = 2.0
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: all files together
+DUMP_MAX_SCEN = 1024
+DUMP_SEED = 2024
 TARGET_TICKS_PER_S = 10000.0    # BASELINE.json north_star / BASELINE.md section 3: C2 target on one MI355X
 W_LAST = [0.0, 0.5, 0.8]        # params/ltpl_config_online.ini:71
 
@@ -202,6 +208,52 @@ def parity_check(res, vres, ref, idx):
                 "integer_outputs_compared_bit_exact": sorted(ints.keys()), "integer_mismatches": bad_ints,
                 "scales": "x, y, coeff_a0: extent of the path; coeff_a1..a3: largest magnitude of that order; kappa: floor 1e-4 1/m; "
                           "psi: pi; vx: floor 1 m/s; ax: max(v^2 / 2, 5 m/s^2)"}
+
+
+def dump_sample(n_scen, bytes_per_scen):
+    """Scenario indices written by --dump-outputs: all of them when they fit, else a fixed seeded sample (sorted) of at most DUMP_MAX_SCEN
+    scenarios that keeps the files under DUMP_MAX_BYTES."""
+    n = min(n_scen, DUMP_MAX_SCEN, max(1, DUMP_MAX_BYTES // max(bytes_per_scen, 1)))
+    if n == n_scen:
+        return np.arange(n_scen, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_scen, size=n, replace=False))
+
+
+def dump_outputs(out_dir, res, vres):
+    """--dump-outputs: the path and velocity results of the last timed step as float64 .npy files (integers are exact in float64),
+    one file per output array, first axis = the scenarios of `scenario_index.npy`. Entries the ABI leaves unspecified (behind n_actions,
+    behind n_nodes / n_pts of a valid path, every per-path entry of an invalid action) are written as 0 so that files of two builds
+    compare element by element."""
+    per_scen = {"end_layer": res.end_layer, "closest_obj_index": res.closest_obj_index, "closest_obj_node": res.closest_obj_node,
+                "n_actions": res.n_actions}
+    per_action = {"action_id": res.action_id, "valid": res.valid, "reduced": res.reduced, "goal_layer": res.goal_layer}
+    per_path = {"n_nodes": res.n_nodes, "n_pts": res.n_pts, "n_ties": res.n_ties, "vel_bound": vres.vel_bound, "too_close": vres.too_close}
+    by_node = {"nodes": res.nodes, "node_idx": res.node_idx, "coeff": res.coeff}
+    by_pt = {"path_param": res.path_param, "vx": vres.vx, "ax": vres.ax}
+    arrays = dict(per_scen, **per_action, **per_path, **by_node, **by_pt)
+    n_scen = int(res.n_actions.shape[0])
+    idx = dump_sample(n_scen, sum(8 * a[0].size for a in arrays.values()) + 8)
+    out = {k: np.asarray(a)[idx].astype(np.float64) for k, a in arrays.items()}
+    n_act = out["n_actions"].astype(np.int64)
+    act = np.arange(res.action_id.shape[1])[None, :] < n_act[:, None]              # [sample, action]: inside n_actions
+    live = act & (out["valid"] != 0)                                                  # ... and a valid path
+    for k in per_action:
+        out[k][~act] = 0.0
+    for k in per_path:
+        out[k][~live] = 0.0
+    n_nodes = np.where(live, out["n_nodes"], 0).astype(np.int64)
+    n_pts = np.where(live, out["n_pts"], 0).astype(np.int64)
+    for k in by_node:
+        used = n_nodes - 1 if k == "coeff" else n_nodes                               # coeff: one row per segment
+        out[k][np.arange(out[k].shape[2])[None, None, :] >= used[:, :, None]] = 0.0
+    for k in by_pt:
+        out[k][np.arange(out[k].shape[2])[None, None, :] >= n_pts[:, :, None]] = 0.0
+    out["scenario_index"] = idx.astype(np.float64)
+    assert sum(a.nbytes for a in out.values()) <= DUMP_MAX_BYTES
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return out
 
 
 def library_stamp(hip):
@@ -739,16 +791,13 @@ def worker(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    # warm-up (untimed), then one untimed K-step block to size the timed region (>= MIN_TIMED_S; agreed over the ranks)
+    # warm-up (untimed): --warmup single steps and one K-step block; then exactly K = --steps timed steps
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     for _ in range(args.warmup):
         hip.batch_run(reps=1, timed=False)
-    barrier()
-    t0 = time.perf_counter()
     hip.batch_run(reps=args.steps, timed=False)
-    barrier()
-    block_s = max_over_ranks(time.perf_counter() - t0)
-    inner = max(1, int(math.ceil(MIN_TIMED_S / max(block_s, 1e-6)))) if not args.exact_steps else 1
-    timed_steps = args.steps * inner
+    timed_steps = args.steps
     barrier()
     t0 = time.perf_counter()
     ms_kernel = hip.batch_run(reps=timed_steps, timed=True)     # HIP events on the library's stream + wait
@@ -756,7 +805,9 @@ def worker(args):
     paths_ms_live = hip.batch_last_paths_ms()                    # path kernel inside the timed region (events per launch)
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0)
-    res, vres = hip.batch_download()
+    res, vres = hip.batch_download()                             # the outputs of the last timed step
+    if getattr(args, "dump_outputs", None) and rank == 0:
+        dump_outputs(args.dump_outputs, res, vres)
 
     def gather_over_ranks(x):
         if dist is None:
@@ -1007,7 +1058,10 @@ def main():
     ap.add_argument("--c5-ticks", type=int, default=400, help="extra.c5: ticks per horizon")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-extra", action="store_true")
-    ap.add_argument("--exact-steps", action="store_true", help="time exactly --steps steps (no repetition up to 2 s)")
+    ap.add_argument("--exact-steps", action="store_true", help="accepted for older scripts: --steps is always the number of timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float64, a seeded sample of at most %d scenarios, "
+                         "<= 64 MB in all; rank 0's shard)" % DUMP_MAX_SCEN)
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak (default, the driver's scaling run): --batch scenarios per GPU; strong: a fixed batch of --batch-total scenarios "
                          "block-partitioned over the ranks (BASELINE config C4: 1024 scenarios over 8 GPUs)")

@@ -265,6 +265,38 @@ def test_flags_that_drop_legs(monkeypatch, capsys):
     assert "tick_batch" not in hip.calls
 
 
+def test_steps_sets_the_timed_steps_and_outputs_are_dumped(monkeypatch, capsys, tmp_path):
+    """--steps is the number of timed steps (no repetition up to a minimum duration); --dump-outputs writes the last step's results as
+    float64 .npy files, padding zeroed, the same files for the same arguments."""
+    import os
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("d%d" % k)
+        out, hip = run_worker(monkeypatch, capsys, steps=5, warmup=2, exact_steps=False, no_cpu=True, no_extra=True, latency_ticks=0,
+                              dump_outputs=str(d))
+        assert out["steps"] == 5 and out["timed_steps"] == 5 and out["ms_per_step"] > 0
+        assert abs(out["value"] * out["ms_per_step"] * 1e-3 - 64.0) < 1e-6
+        files = sorted(os.listdir(d))
+        assert {"scenario_index.npy", "n_actions.npy", "nodes.npy", "path_param.npy", "vx.npy", "ax.npy"} <= set(files)
+        arrs = {f[:-4]: np.load(d / f) for f in files}
+        assert all(a.dtype == np.float64 for a in arrs.values()) and sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        dumps.append(arrs)
+    assert dumps[0].keys() == dumps[1].keys() and all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
+    a = dumps[0]
+    assert np.array_equal(a["scenario_index"], np.arange(64))                 # the whole dry-run batch fits
+    res, vres = hip.batch_download()
+    s, act = 3, int(res.n_actions[3])
+    for q in range(act):
+        if res.valid[s, q]:
+            n = int(res.n_pts[s, q])
+            assert np.array_equal(a["vx"][s, q, :n], vres.vx[s, q, :n]) and not a["vx"][s, q, n:].any()
+            assert np.array_equal(a["path_param"][s, q, :n], res.path_param[s, q, :n]) and not a["path_param"][s, q, n:].any()
+    assert not a["action_id"][s, act:].any()
+    # a batch that does not fit: a fixed sample within the budget
+    idx = bench.dump_sample(32768, 100000)
+    assert len(idx) * 100000 <= 64 << 20 and np.array_equal(idx, bench.dump_sample(32768, 100000)) and np.all(np.diff(idx) > 0)
+
+
 def test_refuses_to_run_without_a_gpu(monkeypatch):
     import torch
     monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
