@@ -133,7 +133,8 @@ inline std::string err_text(int planner, int err)
         "velocity job longer than max_path_pts + 64 points",
         "local_gg rows of a path do not match its coordinates (OTH.py:641-646)",
         "emergency profile: the friction rows of the first path do not match the first trajectory (a backup plan): the reference raises "
-        "RuntimeError 'Length of loc_gg and kappa must be equal!' (OTH.py:1031, calc_brake_emergency.py:31)"};
+        "RuntimeError 'Length of loc_gg and kappa must be equal!' (OTH.py:1031, calc_brake_emergency.py:31)",
+        "closed-loop simulation: no action of the preference list is a key of the last trajectory set (KeyError in the example driver's loop)"};
     const int site = (err >> 8) & 0xff;
     return "fleet: planner " + std::to_string(planner) + ": " + (site > 0 && site < (int)(sizeof(sites) / sizeof(sites[0])) ? sites[site] : "error");
 }

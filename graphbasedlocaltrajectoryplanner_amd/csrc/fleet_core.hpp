@@ -42,7 +42,7 @@ FLT_FN double inf() { return HUGE_VAL; }
 // error sites (S.err = LTPL_ERR_* | site << 8)
 enum Site { E_BACKUP_KEY = 1, E_NO_START, E_CAP_ROWS, E_CAP_NODES, E_CUT_LAYER, E_BRAKE_PREFIX, E_FOLLOW_EMPTY, E_NO_NODES, E_END_NONE,
             E_FOLLOW_SHORT, E_VX_SHORT, E_ROW5, E_BACKUP_CUT, E_BACKUP_SHORT, E_BACKUP_LEN, E_EMERG_EMPTY, E_CALC_BUF, E_GG_DICT, E_CAP_JOBS, E_NO_RANGE, E_CAP_VEL,
-            E_GG_ROWS, E_EMERG_GG };
+            E_GG_ROWS, E_EMERG_GG, E_SIM_ACTION };
 
 // ---------------------------------------------------------------------------------------------------------------------
 // plain-data state

@@ -72,7 +72,7 @@ __device__ __forceinline__ void fleet_load(const WaveX& x, const fleet::Block& B
 #define FLEET_AXM_ROWS 512          // machine-table rows of one call, all tables together (the lane kernel keeps them in LDS)
 #define FLEET_ERR_SHIFT 13
 #define FLEET_ERR_MASK 0x1fff
-static_assert((fleet::E_EMERG_GG << 8 | 0xff) <= FLEET_ERR_MASK, "error word: site bits");
+static_assert((fleet::E_SIM_ACTION << 8 | 0xff) <= FLEET_ERR_MASK, "error word: site bits");
 __device__ __forceinline__ void fleet_store(const WaveX& x, const fleet::Block& B, const fleet::PlannerS* S, int p, int* err_word)
 {
     x.sync();
@@ -134,13 +134,13 @@ __global__ __launch_bounds__(64) void k_fleet_ref_idx(FleetArgs F, const double*
 //   per id k: [8 + 7 K + 2 k ..] key id, id value
 // -- the quantities the tick recordings hold for every tick (tick_replay.check_trajectories). One wave per planner, read only.
 #define LTPL_FLEET_DIGEST (8 + 9 * LTPL_PLANNER_MAX_KEYS)
-__global__ __launch_bounds__(64) void k_fleet_digest(FleetArgs F, double* out)
+__global__ __launch_bounds__(64) void k_fleet_digest(FleetArgs F, double* out, int stride /* doubles between two planners' rows */)
 {
     const int p = blockIdx.x; const WaveX x{(int)threadIdx.x};
     const fleet::Block B{F.state + F.D.stride * (size_t)p, F.D, F.gg ? F.gg + F.D.gg_stride * (size_t)p : nullptr};
     __shared__ fleet::PlannerS S;
     fleet_load(x, B, &S);
-    double* o = out + (size_t)p * LTPL_FLEET_DIGEST;
+    double* o = out + (size_t)p * (size_t)stride;
     constexpr int K = LTPL_PLANNER_MAX_KEYS;
     for (int i = x.lane(); i < LTPL_FLEET_DIGEST; i += 64) o[i] = 0.0;
     x.sync();
@@ -352,6 +352,9 @@ struct FleetTickIn {
     bool has_paths = false, has_vel = false;
 };
 
+struct FleetSim;                                   // closed-loop simulation state (fleet_sim.hpp, ltpl_fleet_sim_*)
+static void fleet_sim_free(FleetSim* s);
+
 struct ltpl_fleet {
     ltpl_handle* h = nullptr;
     std::string err;
@@ -378,9 +381,11 @@ struct ltpl_fleet {
     bool seen_gg = false;
     size_t vel_lds = 0, vel_lds_lite = 0, vel_lds_gg = 0, vel_lds_lite_gg = 0;
     bool tape_fuse = !(getenv("LTPL_FLEET_NO_FUSE") && atoi(getenv("LTPL_FLEET_NO_FUSE")) != 0);     // tape runs with fused stage kernels (results identical)
+    FleetSim* sim = nullptr;                          // ltpl_fleet_sim_setup
     ~ltpl_fleet()
     {
         if (h) { (void)hipSetDevice(h->device); (void)hipStreamSynchronize(h->stream); --h->n_planners; }
+        fleet_sim_free(sim);
         if (stream2) { (void)hipStreamSynchronize(stream2); (void)hipStreamDestroy(stream2); }
         if (ev_a) (void)hipEventDestroy(ev_a);
         if (ev_b) (void)hipEventDestroy(ev_b);
@@ -949,7 +954,7 @@ try {
         if (rc) return rc;
     }
     double* d = f->d_digest;
-    hipLaunchKernelGGL(k_fleet_digest, dim3(f->D.N), dim3(64), 0, f->h->stream, f->args, d);
+    hipLaunchKernelGGL(k_fleet_digest, dim3(f->D.N), dim3(64), 0, f->h->stream, f->args, d, (int)LTPL_FLEET_DIGEST);
     FLEET_TRY(f, hipGetLastError());
     FLEET_TRY(f, hipMemcpyAsync(out, d, sizeof(double) * n, hipMemcpyDeviceToHost, f->h->stream));
     FLEET_TRY(f, hipStreamSynchronize(f->h->stream));

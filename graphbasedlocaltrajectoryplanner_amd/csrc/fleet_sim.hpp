@@ -1,0 +1,449 @@
+// fleet_sim.hpp -- closed-loop simulation of the fleet on the device (ltpl_fleet_sim_*, include/ltpl_hip.h): the example driver's loop
+// (main_std_example.py:98-135) around every planner -- opponents on the race line (ObjectlistDummy, objectlist_dummy.py:148-170), object
+// ingestion (ObjectListInterface.py:75-153, the device code of ltpl_process_objects), the ideal ego tracker (vdc_dummy.py:5-58) -- in
+// front of the fleet's own tick (fleet_dev.hpp), with no host work per tick. Per tick:
+//   k_fleet_sim_step     one wave64 per planner: clock, action choice, opponents (one lane each), ingestion (one lane per object, ballot
+//                        compaction inside the planner's range), ego tracker (trajectory staged in LDS, two-nearest search across the wave,
+//                        the 1 ms loop on lane 0)
+//   k_fleet_sim_offsets  exclusive scan of the on-track counts -> veh_off (one workgroup)
+//   k_fleet_sim_compact  survivors into the fleet's object layout (one lane per planner)
+//   then paths_pre | path kernel | paths_post (+ vel_a) | velocity stages as in ltpl_fleet_tape_run. Tick k + 1's inputs depend on tick k's
+//   trajectories, so the tape's "next paths_pre inside the last kernel" fusion does not apply: paths_pre is launched on its own.
+// The host mirrors of the same arithmetic are graphbasedlocaltrajectoryplanner_amd/sim.py.
+#pragma once
+
+namespace fleet {
+
+// np.interp (numpy's arr_interp) for a scalar x on segment j = the largest index with xp[j] <= x (-1 below xp[0]; n - 1 at or above
+// xp[n - 1]): clamping at both ends, fp[j] on a knot, slope * (x - xp[j]) + fp[j], the right end of the segment when that is NaN.
+// `fp(i)` yields the table value of row i (the opponents' scaled speeds are formed there: vel_rl[i] * vel_scale, objectlist_dummy.py:121).
+template <class FP>
+__device__ __forceinline__ double sim_interp(double x, const double* xp, int n, int j, FP fp)
+{
+    if (isnan(x)) return x;
+    if (j < 0) return fp(0);
+    if (j >= n - 1) return fp(n - 1);
+    const double xj = xp[j], f0 = fp(j);
+    if (xj == x) return f0;
+    const double f1 = fp(j + 1);
+    const double slope = (f1 - f0) / (xp[j + 1] - xj);
+    double r = slope * (x - xj) + f0;
+    if (isnan(r)) {
+        r = slope * (x - xp[j + 1]) + f1;
+        if (isnan(r) && f0 == f1) r = f0;
+    }
+    return r;
+}
+// segment of x by bisection (the same index numpy's binary_search_with_guess finds: the largest j with xp[j] <= x)
+__device__ __forceinline__ int sim_segment(double x, const double* xp, int n)
+{
+    if (!(x >= xp[0])) return -1;
+    int lo = 0, hi = n;                 // xp[lo] <= x; hi == n or xp[hi] > x
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (xp[mid] <= x) lo = mid; else hi = mid; }
+    return lo;
+}
+// the same from a segment valid for a smaller x: s only grows between two wraps, so the integration loops walk forward
+__device__ __forceinline__ int sim_advance(double x, const double* xp, int n, int j)
+{
+    while (j + 1 < n && xp[j + 1] <= x) ++j;
+    return j;
+}
+
+}  // namespace fleet
+
+#define SIM_OBJ_CAP MAX_VEH                // objects (opponents + static) per planner
+#define SIM_DT_STEP 0.001                  // integration step of both simulators (objectlist_dummy.py:149, vdc_dummy.py:46)
+
+struct SimDev {
+    int n_rl; const double* race;          // [5][n_rl] column-major: s_rl, x, y, psi, vel_rl
+    const int* opp_off; double* opp_s; double* opp_tic; const double* opp_scale; const double* opp_len;
+    const int* st_off; const double* st_x; const double* st_y; const double* st_th; const double* st_v; const double* st_len;
+    const int* pref_off; const int* pref;
+    double dt; int n_export;
+    double* now; int* sel; int* started; double* pos_x; double* pos_y; double* vel;
+    int* cnt;                              // [N] on-track objects of the tick
+    double* g_x; double* g_y; double* g_px; double* g_py; double* g_r; double* g_v;   // survivors, planner p's from opp_off[p] + st_off[p] on
+    int* prev_action; double* t_now; int* veh_off; double* o_r; double* o_v; double* o_px; double* o_py;   // the tick's fleet::FObj arrays
+};
+
+struct SimBest { double d; int i; };
+__device__ __forceinline__ SimBest sim_better(SimBest a, SimBest b) { return (b.d < a.d || (b.d == a.d && b.i < a.i)) ? b : a; }
+__device__ __forceinline__ SimBest sim_wave_min(SimBest v)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) { SimBest o; o.d = __shfl_xor(v.d, m); o.i = __shfl_xor(v.i, m); v = sim_better(v, o); }
+    return v;
+}
+
+__global__ __launch_bounds__(64) void k_fleet_sim_step(FleetArgs F, DevLat lat, SimDev sd, double* trace /* this tick's records or null */)
+{
+    const int p = blockIdx.x, lane = threadIdx.x; const WaveX x{lane};
+    const fleet::Block B{F.state + F.D.stride * (size_t)p, F.D, nullptr};
+    __shared__ fleet::PlannerS S;
+    __shared__ double ts[LTPL_FLEET_SIM_MAX_EXPORT], tx[LTPL_FLEET_SIM_MAX_EXPORT], ty[LTPL_FLEET_SIM_MAX_EXPORT], tv[LTPL_FLEET_SIM_MAX_EXPORT];
+    __shared__ double ox[SIM_OBJ_CAP], oy[SIM_OBJ_CAP], oth[SIM_OBJ_CAP], ov[SIM_OBJ_CAP], ol[SIM_OBJ_CAP];
+    __shared__ double first_xy[2];
+    fleet_load(x, B, &S);
+    double now = sd.now[p], pos_x = sd.pos_x[p], pos_y = sd.pos_y[p], vel = sd.vel[p];
+    int sel = sd.sel[p], cnt = 0;
+    bool failed = false;
+    if (lane == 0) { first_xy[0] = NAN; first_xy[1] = NAN; }
+    if (!S.err) {
+        now += sd.dt;
+        // action choice (run_loop: the first preferred key of the previous exported set; before the first tick {'straight': None})
+        const int started = sd.started[p];
+        int slot = -1;
+        bool found = false;
+        for (int i = sd.pref_off[p]; i < sd.pref_off[p + 1] && !found; ++i) {
+            sel = sd.pref[i];
+            if (!started) found = sel == LTPL_ACT_STRAIGHT;
+            else for (int k = 0; k < S.n_bp && !found; ++k) if (S.bp_id[k] == sel) { found = true; slot = k; }
+        }
+        if (!found) {
+            fleet::fail(S, LTPL_ERR_INVALID_ARG, fleet::E_SIM_ACTION);
+            failed = true;
+        } else {
+            const int o0 = sd.opp_off[p], no = sd.opp_off[p + 1] - o0, s0 = sd.st_off[p], ns = sd.st_off[p + 1] - s0;
+            const int n_rl = sd.n_rl;
+            const double* s_rl = sd.race;
+            // opponents: one lane each (objectlist_dummy.py:148-170)
+            for (int q = lane; q < no; q += 64) {
+                const double scale = sd.opp_scale[o0 + q];
+                const double* vrl = s_rl + (size_t)4 * n_rl;
+                auto vel_s = [&](int i) { return vrl[i] * scale; };
+                double s = sd.opp_s[o0 + q];
+                const double toc = now - sd.opp_tic[o0 + q];
+                double t = 0.0;
+                int j = fleet::sim_segment(s, s_rl, n_rl);
+                while (t < toc) {
+                    s += fleet::sim_interp(s, s_rl, n_rl, j, vel_s) * SIM_DT_STEP;
+                    t += SIM_DT_STEP;
+                    if (s >= s_rl[n_rl - 1]) { s = 0.0; j = fleet::sim_segment(s, s_rl, n_rl); }
+                    else j = fleet::sim_advance(s, s_rl, n_rl, j);
+                }
+                sd.opp_s[o0 + q] = s; sd.opp_tic[o0 + q] = now;
+                const double* cx = s_rl + n_rl; const double* cy = cx + n_rl; const double* cpsi = cy + n_rl;
+                ox[q] = fleet::sim_interp(s, s_rl, n_rl, j, [&](int i) { return cx[i]; });
+                oy[q] = fleet::sim_interp(s, s_rl, n_rl, j, [&](int i) { return cy[i]; });
+                double psi = fleet::sim_interp(s, s_rl, n_rl, j, [&](int i) { return cpsi[i]; });
+                if (psi > fleet::kPi) psi -= 2 * fleet::kPi;
+                oth[q] = psi; ov[q] = fleet::sim_interp(s, s_rl, n_rl, j, vel_s); ol[q] = sd.opp_len[o0 + q];
+            }
+            for (int q = lane; q < ns; q += 64) {
+                ox[no + q] = sd.st_x[s0 + q]; oy[no + q] = sd.st_y[s0 + q]; oth[no + q] = sd.st_th[s0 + q]; ov[no + q] = sd.st_v[s0 + q];
+                ol[no + q] = sd.st_len[s0 + q];
+            }
+            __syncthreads();
+            // ingestion: survivors in list order (ballot + prefix count), staged from the planner's first object slot on
+            const int base = o0 + s0, nobj = no + ns;
+            for (int b0 = 0; b0 < nobj; b0 += 64) {
+                const int k = b0 + lane;
+                ObjIngest r{0, 0.0, 0.0, 0.0};
+                if (k < nobj) r = process_object_dev(lat, 0.2, ox[k], oy[k], oth[k], ov[k], ol[k]);     // ObjectListInterface.py:121
+                const bool keep = k < nobj && r.on_track;
+                const unsigned long long m = __ballot(keep);
+                const int idx = cnt + __popcll(m & ((1ull << lane) - 1ull));
+                if (keep) {
+                    sd.g_x[base + idx] = ox[k]; sd.g_y[base + idx] = oy[k]; sd.g_px[base + idx] = r.pred_x; sd.g_py[base + idx] = r.pred_y;
+                    sd.g_r[base + idx] = r.radius; sd.g_v[base + idx] = ov[k];
+                    if (idx == 0) { first_xy[0] = ox[k]; first_xy[1] = oy[k]; }
+                }
+                cnt += __popcll(m);
+            }
+            // ego tracker on the previous trajectory of the selected action (vdc_dummy.py:5-58), trimmed to the exported rows
+            if (started) {
+                const fleet::Rows tr = B.bp(S.bp_slot[slot]);
+                const int n = S.bp_rows[slot] < sd.n_export ? S.bp_rows[slot] : sd.n_export;
+                for (int i = lane; i < n; i += 64) { ts[i] = tr.at(i, 0); tx[i] = tr.at(i, 1); ty[i] = tr.at(i, 2); tv[i] = tr.at(i, 5); }
+                __syncthreads();
+                if (n <= 2) {
+                    vel = n > 0 ? tv[0] : vel;
+                } else {
+                    const double ex = pos_x, ey = pos_y;
+                    SimBest b1{INFINITY, 0x7fffffff};
+                    for (int i = lane; i < n; i += 64) b1 = sim_better(b1, SimBest{(tx[i] - ex) * (tx[i] - ex) + (ty[i] - ey) * (ty[i] - ey), i});
+                    b1 = sim_wave_min(b1);
+                    SimBest b2{INFINITY, 0x7fffffff};
+                    for (int i = lane; i < n; i += 64)
+                        if (i != b1.i) b2 = sim_better(b2, SimBest{(tx[i] - ex) * (tx[i] - ex) + (ty[i] - ey) * (ty[i] - ey), i});
+                    b2 = sim_wave_min(b2);
+                    int i0 = b1.i < b2.i ? b1.i : b2.i;
+                    if (i0 < 0 || i0 >= n) i0 = 0;               // (NaN distances only)
+                    if (lane == 0) {
+                        const double dx = tx[i0] - ex, dy = ty[i0] - ey;
+                        double s = sqrt(dx * dx + dy * dy) + ts[i0];
+                        auto vx = [&](int i) { return tv[i]; };
+                        int j = fleet::sim_segment(s, ts, n);
+                        double t = 0.0;
+                        while (t < sd.dt) {
+                            const double step = fleet::sim_interp(s, ts, n, j, vx) * SIM_DT_STEP;
+                            s += 0.0001 > step ? 0.0001 : step;      // Python's max(step, 0.0001): the second only where it is larger (NaN stays)
+                            t += SIM_DT_STEP;
+                            j = fleet::sim_advance(s, ts, n, j);
+                        }
+                        pos_x = fleet::sim_interp(s, ts, n, j, [&](int i) { return tx[i]; });
+                        pos_y = fleet::sim_interp(s, ts, n, j, [&](int i) { return ty[i]; });
+                        vel = fleet::sim_interp(s, ts, n, j, vx);
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (lane == 0) {
+        if (!failed && !S.err) {
+            sd.now[p] = now; sd.sel[p] = sel; sd.started[p] = 1; sd.pos_x[p] = pos_x; sd.pos_y[p] = pos_y; sd.vel[p] = vel;
+        }
+        sd.cnt[p] = cnt; sd.prev_action[p] = sd.sel[p]; sd.t_now[p] = sd.now[p];
+        if (trace) {
+            double* o = trace + (size_t)p * LTPL_FLEET_SIM_TRACE_DOUBLES;
+            o[0] = (double)sel; o[1] = now; o[2] = pos_x; o[3] = pos_y; o[4] = vel; o[5] = (double)cnt; o[6] = first_xy[0]; o[7] = first_xy[1];
+        }
+    }
+    if (failed) fleet_store(x, B, &S, p, F.err_word);
+}
+
+// exclusive scan of the on-track counts (one workgroup; a few hundred thousand planners at most)
+__global__ __launch_bounds__(1024) void k_fleet_sim_offsets(const int* cnt, int n, int* veh_off)
+{
+    __shared__ int part[1024];
+    const int t = threadIdx.x, per = (n + 1023) / 1024;
+    const int a = t * per, b = a + per < n ? a + per : n;
+    int sum = 0;
+    for (int i = a; i < b; ++i) sum += cnt[i];
+    part[t] = sum;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {
+        const int v = t >= d ? part[t - d] : 0;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    int run = part[t] - sum;
+    for (int i = a; i < b; ++i) { veh_off[i] = run; run += cnt[i]; }
+    if (t == 1023) veh_off[n] = part[1023];
+}
+
+// survivors into the fleet's object layout: own position, then the prediction (pos_off[v] = 2 v, written at setup)
+__global__ __launch_bounds__(64) void k_fleet_sim_compact(SimDev sd, int n)
+{
+    const int p = blockIdx.x * 64 + threadIdx.x;
+    if (p >= n) return;
+    const int base = sd.opp_off[p] + sd.st_off[p], o = sd.veh_off[p], c = sd.cnt[p];
+    for (int i = 0; i < c; ++i) {
+        const int v = o + i, g = base + i;
+        sd.o_r[v] = sd.g_r[g]; sd.o_v[v] = sd.g_v[g];
+        sd.o_px[2 * v] = sd.g_x[g]; sd.o_py[2 * v] = sd.g_y[g]; sd.o_px[2 * v + 1] = sd.g_px[g]; sd.o_py[2 * v + 1] = sd.g_py[g];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------------------------------
+struct FleetSim {
+    std::vector<void*> allocs;
+    SimDev sd{};
+    fleet::FObj ob{}; const int* zone_off = nullptr; const int* zone_gid = nullptr;
+    FleetTickIn velt;                       // velocity arguments of ltpl_fleet_sim_vel (its own arena)
+    bool has_vel = false;
+    int n_opp = 0, n_obj = 0;
+};
+static void fleet_sim_free(FleetSim* s)
+{
+    if (!s) return;
+    for (void* p : s->allocs) (void)hipFree(p);
+    if (s->velt.d_buf) (void)hipFree(s->velt.d_buf);
+    delete s;
+}
+
+template <class T>
+static int sim_upload(ltpl_fleet* f, FleetSim* s, const T* src, size_t n, T** out)
+{
+    void* p = nullptr;
+    FLEET_TRY(f, hipMalloc(&p, (n ? n : 1) * sizeof(T)));
+    s->allocs.push_back(p);
+    if (src && n) FLEET_TRY(f, hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice));
+    else FLEET_TRY(f, hipMemset(p, 0, (n ? n : 1) * sizeof(T)));
+    *out = static_cast<T*>(p);
+    return LTPL_OK;
+}
+
+static int sim_check_csr(ltpl_fleet* f, const int32_t* off, int N, const char* what, int* total)
+{
+    if (!off) { f->err = std::string("fleet sim: ") + what + " offsets missing"; return LTPL_ERR_INVALID_ARG; }
+    if (off[0] != 0) { f->err = std::string("fleet sim: ") + what + " offsets must start at 0"; return LTPL_ERR_INVALID_ARG; }
+    for (int p = 0; p < N; ++p) if (off[p + 1] < off[p]) { f->err = std::string("fleet sim: ") + what + " offsets must not decrease"; return LTPL_ERR_INVALID_ARG; }
+    *total = off[N];
+    return LTPL_OK;
+}
+
+// every argument is checked before the first HIP call
+static int sim_check_in(ltpl_fleet* f, const ltpl_fleet_sim_in* in, int* n_opp, int* n_st, int* n_pref, int* n_zone)
+{
+    const int N = f->D.N;
+    auto bad = [&](const char* why, int code = LTPL_ERR_INVALID_ARG) { f->err = std::string("fleet sim: ") + why; return code; };
+    if (in->n_rl < 2 || !in->race) return bad("race-line table with fewer than 2 rows");
+    for (int i = 0; i + 1 < in->n_rl; ++i) if (!(in->race[(size_t)5 * (i + 1)] >= in->race[(size_t)5 * i])) return bad("s_rl must not decrease");
+    int rc;
+    if ((rc = sim_check_csr(f, in->opp_off, N, "opponent", n_opp))) return rc;
+    if ((rc = sim_check_csr(f, in->static_off, N, "static object", n_st))) return rc;
+    if ((rc = sim_check_csr(f, in->pref_off, N, "preference", n_pref))) return rc;
+    if ((rc = sim_check_csr(f, in->zone_off, N, "zone", n_zone))) return rc;
+    if (*n_opp > 0 && (!in->opp_s0 || !in->opp_vel_scale || !in->opp_length)) return bad("opponent arrays missing");
+    if (*n_st > 0 && (!in->static_x || !in->static_y || !in->static_theta || !in->static_v || !in->static_length)) return bad("static object arrays missing");
+    for (int p = 0; p < N; ++p) {
+        if ((in->opp_off[p + 1] - in->opp_off[p]) + (in->static_off[p + 1] - in->static_off[p]) > SIM_OBJ_CAP)
+            return bad("more than 96 objects for one planner", LTPL_ERR_CAPACITY);
+        const int np_ = in->pref_off[p + 1] - in->pref_off[p];
+        if (np_ < 1 || np_ > LTPL_FLEET_SIM_MAX_PREF) return bad("a preference list needs 1 .. 5 entries");
+    }
+    if (!in->pref_action) return bad("preference actions missing");
+    for (int i = 0; i < *n_pref; ++i) if (in->pref_action[i] < LTPL_ACT_STRAIGHT || in->pref_action[i] > LTPL_ACT_EMERGENCY) return bad("unknown action in a preference list");
+    if (*n_zone > 0 && !in->zone_gid) return bad("zone node ids missing");
+    for (int i = 0; i < *n_zone; ++i) if (in->zone_gid[i] < 0 || in->zone_gid[i] >= f->h->lat.V) return bad("zone node id out of range");
+    if (!(in->dt > 0.0) || !std::isfinite(in->dt) || !std::isfinite(in->t0) || !std::isfinite(in->tic0)) return bad("dt must be positive, t0 / tic0 finite");
+    if (in->n_export < 1 || in->n_export > LTPL_FLEET_SIM_MAX_EXPORT) return bad("n_export must be 1 .. 256", LTPL_ERR_CAPACITY);
+    if (!in->pos_est_x || !in->pos_est_y || !in->vel_est) return bad("initial pose estimate missing");
+    return LTPL_OK;
+}
+
+extern "C" int ltpl_fleet_sim_setup(ltpl_fleet* f, const ltpl_fleet_sim_in* in)
+try {
+    if (!f || !in) return LTPL_ERR_INVALID_ARG;
+    int n_opp = 0, n_st = 0, n_pref = 0, n_zone = 0;
+    int rc = sim_check_in(f, in, &n_opp, &n_st, &n_pref, &n_zone);
+    if (rc) return rc;
+    if ((rc = fleet_enter(f))) return rc;
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    fleet_sim_free(f->sim); f->sim = nullptr;
+    std::unique_ptr<FleetSim, void (*)(FleetSim*)> s(new FleetSim(), fleet_sim_free);
+    const int N = f->D.N, n_obj = n_opp + n_st;
+    s->n_opp = n_opp; s->n_obj = n_obj;
+    SimDev& d = s->sd;
+    d.n_rl = in->n_rl; d.dt = in->dt; d.n_export = in->n_export;
+    {
+        std::vector<double> race((size_t)5 * in->n_rl);             // column-major on the device
+        for (int i = 0; i < in->n_rl; ++i) for (int c = 0; c < 5; ++c) race[(size_t)c * in->n_rl + i] = in->race[(size_t)5 * i + c];
+        double* p = nullptr;
+        if ((rc = sim_upload(f, s.get(), race.data(), race.size(), &p))) return rc;
+        d.race = p;
+    }
+    const std::vector<double> tic(n_opp, in->tic0), now(N, in->t0);
+    const std::vector<int> sel(N, LTPL_ACT_NONE);
+    std::vector<int> pos_off((size_t)n_obj + 1);
+    for (int v = 0; v <= n_obj; ++v) pos_off[(size_t)v] = 2 * v;
+    int* pi = nullptr; double* pd = nullptr; int* po = nullptr;
+#define SIM_UP(dst, src, n) do { if ((rc = sim_upload(f, s.get(), src, (size_t)(n), &dst))) return rc; } while (0)
+    SIM_UP(pi, in->opp_off, N + 1); d.opp_off = pi;
+    SIM_UP(d.opp_s, in->opp_s0, n_opp); SIM_UP(d.opp_tic, tic.data(), n_opp);
+    SIM_UP(pd, in->opp_vel_scale, n_opp); d.opp_scale = pd; SIM_UP(pd, in->opp_length, n_opp); d.opp_len = pd;
+    SIM_UP(pi, in->static_off, N + 1); d.st_off = pi;
+    SIM_UP(pd, in->static_x, n_st); d.st_x = pd; SIM_UP(pd, in->static_y, n_st); d.st_y = pd; SIM_UP(pd, in->static_theta, n_st); d.st_th = pd;
+    SIM_UP(pd, in->static_v, n_st); d.st_v = pd; SIM_UP(pd, in->static_length, n_st); d.st_len = pd;
+    SIM_UP(pi, in->pref_off, N + 1); d.pref_off = pi; SIM_UP(pi, in->pref_action, n_pref); d.pref = pi;
+    SIM_UP(d.now, now.data(), N); SIM_UP(d.sel, sel.data(), N); SIM_UP(d.started, (const int*)nullptr, N);
+    SIM_UP(d.pos_x, in->pos_est_x, N); SIM_UP(d.pos_y, in->pos_est_y, N); SIM_UP(d.vel, in->vel_est, N);
+    SIM_UP(d.cnt, (const int*)nullptr, N);
+    SIM_UP(d.g_x, (const double*)nullptr, n_obj); SIM_UP(d.g_y, (const double*)nullptr, n_obj); SIM_UP(d.g_px, (const double*)nullptr, n_obj);
+    SIM_UP(d.g_py, (const double*)nullptr, n_obj); SIM_UP(d.g_r, (const double*)nullptr, n_obj); SIM_UP(d.g_v, (const double*)nullptr, n_obj);
+    SIM_UP(d.prev_action, sel.data(), N); SIM_UP(d.t_now, now.data(), N); SIM_UP(d.veh_off, (const int*)nullptr, N + 1);
+    SIM_UP(po, pos_off.data(), n_obj + 1);
+    SIM_UP(d.o_r, (const double*)nullptr, n_obj); SIM_UP(d.o_v, (const double*)nullptr, n_obj);
+    SIM_UP(d.o_px, (const double*)nullptr, 2 * n_obj); SIM_UP(d.o_py, (const double*)nullptr, 2 * n_obj);
+    int* zo = nullptr; int* zg = nullptr;
+    SIM_UP(zo, in->zone_off, N + 1); SIM_UP(zg, in->zone_gid, n_zone);
+#undef SIM_UP
+    s->ob = fleet::FObj{d.prev_action, d.t_now, d.veh_off, po, d.o_r, d.o_v, d.o_px, d.o_py};
+    s->zone_off = zo; s->zone_gid = zg;
+    f->sim = s.release();
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+extern "C" int ltpl_fleet_sim_vel(ltpl_fleet* f, const ltpl_planner_vel_in* in)
+try {
+    if (!f || !in) return LTPL_ERR_INVALID_ARG;
+    if (!f->sim) { f->err = "fleet sim: ltpl_fleet_sim_setup first"; return LTPL_ERR_INVALID_ARG; }
+    if (in->gg_row_off || in->gg_rows) { f->err = "fleet sim: local_gg as a dict depends on the tick's own paths (not supported by the simulation)"; return LTPL_ERR_UNSUPPORTED; }
+    int rc = fleet_enter(f);
+    if (rc) return rc;
+    // pos_est / vel_est come from the simulation: stand-ins for the checks of the packer
+    const std::vector<double> zero((size_t)f->D.N, 0.0);
+    ltpl_planner_vel_in v = *in;
+    v.pos_est_x = v.pos_est_y = v.vel_est = zero.data();
+    f->sim->has_vel = false;
+    if ((rc = fleet_pack_inputs(f, &f->sim->velt, nullptr, &v, false))) return rc;
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    f->sim->has_vel = true;
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+extern "C" int ltpl_fleet_sim_run(ltpl_fleet* f, int32_t n_ticks, double* trace, int32_t doubles_per_tick_planner, float* ms_total)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    if (n_ticks < 1) { f->err = "fleet sim: n_ticks must be positive"; return LTPL_ERR_INVALID_ARG; }
+    if (trace && doubles_per_tick_planner != LTPL_FLEET_SIM_TRACE_DOUBLES) { f->err = "fleet sim: trace record size mismatch"; return LTPL_ERR_INVALID_ARG; }
+    if (!f->sim || !f->sim->has_vel) { f->err = "fleet sim: ltpl_fleet_sim_setup and ltpl_fleet_sim_vel first"; return LTPL_ERR_INVALID_ARG; }
+    int rc = fleet_enter(f);
+    if (rc) return rc;
+    FleetSim& s = *f->sim;
+    const int N = f->D.N;
+    const size_t rec = (size_t)N * LTPL_FLEET_SIM_TRACE_DOUBLES;
+    double* d_trace = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    struct Guard { double** t; hipEvent_t* a; hipEvent_t* b; ~Guard() { if (*t) (void)hipFree(*t); if (*a) (void)hipEventDestroy(*a); if (*b) (void)hipEventDestroy(*b); } } g{&d_trace, &e0, &e1};
+    if (trace) FLEET_TRY(f, hipMalloc(reinterpret_cast<void**>(&d_trace), sizeof(double) * rec * (size_t)n_ticks));
+    FLEET_TRY(f, hipEventCreate(&e0)); FLEET_TRY(f, hipEventCreate(&e1));
+    FleetTickIn t = s.velt;
+    t.ob = s.ob; t.zone_off = s.zone_off; t.zone_gid = s.zone_gid;
+    t.vin.pos_x = s.sd.pos_x; t.vin.pos_y = s.sd.pos_y; t.vin.vel_est = s.sd.vel;
+    t.has_paths = true;
+    hipStream_t st = f->h->stream;
+    FLEET_TRY(f, hipStreamSynchronize(st));
+    FLEET_TRY(f, hipEventRecord(e0, st));
+    for (int k = 0; k < n_ticks; ++k) {
+        double* tr = d_trace ? d_trace + rec * (size_t)k : nullptr;
+        hipLaunchKernelGGL(k_fleet_sim_step, dim3(N), dim3(64), 0, st, f->args, f->h->lat, s.sd, tr);
+        FLEET_TRY(f, hipGetLastError());
+        hipLaunchKernelGGL(k_fleet_sim_offsets, dim3(1), dim3(1024), 0, st, (const int*)s.sd.cnt, N, s.sd.veh_off);
+        FLEET_TRY(f, hipGetLastError());
+        hipLaunchKernelGGL(k_fleet_sim_compact, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, st, s.sd, N);
+        FLEET_TRY(f, hipGetLastError());
+        if (f->tape_fuse) {
+            fleet::FPathsOut po{};
+            if ((rc = fleet_launch_paths(f, t, true, true, false, &po))) return rc;
+            if ((rc = fleet_launch_vel(f, t, &po))) return rc;
+        } else {
+            if ((rc = fleet_launch_paths(f, t, true, true))) return rc;
+            if ((rc = fleet_launch_vel(f, t))) return rc;
+        }
+        if (tr) {
+            hipLaunchKernelGGL(k_fleet_digest, dim3(N), dim3(64), 0, st, f->args, tr + 8, (int)LTPL_FLEET_SIM_TRACE_DOUBLES);
+            FLEET_TRY(f, hipGetLastError());
+        }
+    }
+    FLEET_TRY(f, hipEventRecord(e1, st));
+    FLEET_TRY(f, hipEventSynchronize(e1));
+    if (ms_total) FLEET_TRY(f, hipEventElapsedTime(ms_total, e0, e1));
+    if (trace) FLEET_TRY(f, hipMemcpy(trace, d_trace, sizeof(double) * rec * (size_t)n_ticks, hipMemcpyDeviceToHost));
+    f->cur.has_paths = false;           // (the objects of the last tick live in the simulation: a per-call calc_vel_profile needs its own calc_paths first)
+    return fleet_check(f);
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+extern "C" int ltpl_fleet_sim_state(ltpl_fleet* f, double* pos_est_x, double* pos_est_y, double* vel_est, int32_t* sel_action, double* now,
+                                    double* opp_s, double* opp_tic)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    if (!f->sim) { f->err = "fleet sim: ltpl_fleet_sim_setup first"; return LTPL_ERR_INVALID_ARG; }
+    FLEET_TRY(f, hipSetDevice(f->h->device));
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    const SimDev& d = f->sim->sd;
+    const size_t n = (size_t)f->D.N, no = (size_t)f->sim->n_opp;
+    if (pos_est_x) FLEET_TRY(f, hipMemcpy(pos_est_x, d.pos_x, 8 * n, hipMemcpyDeviceToHost));
+    if (pos_est_y) FLEET_TRY(f, hipMemcpy(pos_est_y, d.pos_y, 8 * n, hipMemcpyDeviceToHost));
+    if (vel_est) FLEET_TRY(f, hipMemcpy(vel_est, d.vel, 8 * n, hipMemcpyDeviceToHost));
+    if (sel_action) FLEET_TRY(f, hipMemcpy(sel_action, d.sel, 4 * n, hipMemcpyDeviceToHost));
+    if (now) FLEET_TRY(f, hipMemcpy(now, d.now, 8 * n, hipMemcpyDeviceToHost));
+    if (opp_s && no) FLEET_TRY(f, hipMemcpy(opp_s, d.opp_s, 8 * no, hipMemcpyDeviceToHost));
+    if (opp_tic && no) FLEET_TRY(f, hipMemcpy(opp_tic, d.opp_tic, 8 * no, hipMemcpyDeviceToHost));
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))

@@ -2485,13 +2485,10 @@ __global__ __launch_bounds__(64) void k_compact_rows(DevPathsOut out, DevTickVel
 // (get_s_coord.py:34-47,93-96 with closed = True), closest of the 50 np.linspace points between the two bracketing
 // points, comparison of the squared distances to the interpolated bounds with the squared track width
 // (check_inside_bounds.py:26-56); constant-velocity prediction and radius (ObjectListInterface.py:117-133).
-__global__ __launch_bounds__(64) void k_process_objects(DevLat lat, int n_obj, double dt, const double* ox, const double* oy,
-                                                        const double* oth, const double* ov, const double* olen,
-                                                        int* on_track, double* pred_x, double* pred_y, double* radius)
+// The per-object body is shared with the fleet's closed-loop simulation (fleet_sim.hpp, k_fleet_sim_step).
+struct ObjIngest { int on_track; double pred_x, pred_y, radius; };
+__device__ __forceinline__ ObjIngest process_object_dev(const DevLat& lat, double dt, double px, double py, double th, double v, double len)
 {
-    const int k = blockIdx.x * 64 + threadIdx.x;
-    if (k >= n_obj) return;
-    const double px = ox[k], py = oy[k];
     const int L = lat.L;
     int nb = 0; double best = INFINITY;
     for (int l = 0; l < L; ++l) {
@@ -2520,10 +2517,22 @@ __global__ __launch_bounds__(64) void k_process_objects(DevLat lat, int n_obj, d
     const double d_track_2 = (l1x - l2x) * (l1x - l2x) + (l1y - l2y) * (l1y - l2y);
     const double d_b1_2 = (l1x - px) * (l1x - px) + (l1y - py) * (l1y - py);
     const double d_b2_2 = (l2x - px) * (l2x - px) + (l2y - py) * (l2y - py);
-    on_track[k] = !(d_b1_2 > d_track_2 || d_b2_2 > d_track_2) ? 1 : 0;
-    pred_x[k] = px - sin(oth[k]) * ov[k] * dt;
-    pred_y[k] = py + cos(oth[k]) * ov[k] * dt;
-    radius[k] = olen[k] / 2.0;
+    ObjIngest r;
+    r.on_track = !(d_b1_2 > d_track_2 || d_b2_2 > d_track_2) ? 1 : 0;
+    r.pred_x = px - sin(th) * v * dt;
+    r.pred_y = py + cos(th) * v * dt;
+    r.radius = len / 2.0;
+    return r;
+}
+
+__global__ __launch_bounds__(64) void k_process_objects(DevLat lat, int n_obj, double dt, const double* ox, const double* oy,
+                                                        const double* oth, const double* ov, const double* olen,
+                                                        int* on_track, double* pred_x, double* pred_y, double* radius)
+{
+    const int k = blockIdx.x * 64 + threadIdx.x;
+    if (k >= n_obj) return;
+    const ObjIngest r = process_object_dev(lat, dt, ox[k], oy[k], oth[k], ov[k], olen[k]);
+    on_track[k] = r.on_track; pred_x[k] = r.pred_x; pred_y[k] = r.pred_y; radius[k] = r.radius;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -4772,3 +4781,4 @@ try {
 // fleet (ABI v5): planners with device-resident state
 // ---------------------------------------------------------------------------------------------------------------------
 #include "fleet_dev.hpp"
+#include "fleet_sim.hpp"

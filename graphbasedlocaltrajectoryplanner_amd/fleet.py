@@ -16,6 +16,20 @@ from . import _capi
 from .planner import KEY_IDS, Planner, PlannerPathsIn, PlannerVelIn
 
 
+class SimIn(C.Structure):                 # ltpl_fleet_sim_in (pointer members as plain addresses)
+    _fields_ = [("n_rl", C.c_int32), ("race", C.c_void_p),
+                ("opp_off", C.c_void_p), ("opp_s0", C.c_void_p), ("opp_vel_scale", C.c_void_p), ("opp_length", C.c_void_p),
+                ("static_off", C.c_void_p), ("static_x", C.c_void_p), ("static_y", C.c_void_p), ("static_theta", C.c_void_p),
+                ("static_v", C.c_void_p), ("static_length", C.c_void_p),
+                ("t0", C.c_double), ("tic0", C.c_double), ("dt", C.c_double), ("n_export", C.c_int32),
+                ("pref_off", C.c_void_p), ("pref_action", C.c_void_p),
+                ("pos_est_x", C.c_void_p), ("pos_est_y", C.c_void_p), ("vel_est", C.c_void_p),
+                ("zone_off", C.c_void_p), ("zone_gid", C.c_void_p)]
+
+
+SIM_TRACE_DOUBLES = 8 + 8 + 9 * _capi.PLANNER_MAX_KEYS     # LTPL_FLEET_SIM_TRACE_DOUBLES
+
+
 class Fleet(Planner):
     def __init__(self, backend, n_planners, **config):
         Planner.__init__(self, backend, n_scen=n_planners, prefix="ltpl_fleet_", **config)
@@ -30,6 +44,11 @@ class Fleet(Planner):
         f("tape_run").argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_float)]
         if hasattr(self.lib, "ltpl_fleet_digest"):
             f("digest").argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32]
+        if hasattr(self.lib, "ltpl_fleet_sim_run"):
+            f("sim_setup").argtypes = [C.c_void_p, C.POINTER(SimIn)]
+            f("sim_vel").argtypes = [C.c_void_p, C.POINTER(PlannerVelIn)]
+            f("sim_run").argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_float)]
+            f("sim_state").argtypes = [C.c_void_p] + [C.c_void_p] * 7
 
     def set_start_range(self, first, past_last, pos, heading, vel=0.0, max_heading_offset=math.pi / 4):
         """``set_start`` with the same pose for the planners [first, past_last) in one call (ltpl_fleet_set_start_range)."""
@@ -219,3 +238,69 @@ class Fleet(Planner):
         ms = C.c_float(0.0)
         self._check(self._fn("tape_run")(self.handle, int(first), int(count), C.byref(ms)))
         return float(ms.value)
+
+    # ---- closed-loop simulation on the device -------------------------------------------------------------------------------------
+    def sim_setup(self, race, planners, t0=1.0e6, tic0=None, dt=0.05, n_export=115):
+        """The example driver's loop around every planner (ltpl_fleet_sim_setup). ``race``: ``sim.RaceLineTable`` (or its [n, 5] rows).
+        ``planners``: one dict per planner -- ``opponents`` [(s0, vel_scale, length)], ``static`` [(x, y, theta, v, length)],
+        ``pref`` action names in order of preference (1 .. 5, 'emergency' allowed), ``pos_est`` (x, y), ``vel_est``, ``zone_gids``.
+        The opponents' previous call is at ``tic0`` (default ``t0``)."""
+        if len(planners) != self.n_scen:
+            raise ValueError("sim_setup: one entry per planner expected")
+        f64, i32 = np.float64, np.int32
+        rows = np.ascontiguousarray(np.asarray(race.rows() if hasattr(race, "rows") else race, f64).reshape(-1, 5))
+
+        def csr(lists):
+            return np.ascontiguousarray(np.concatenate(([0], np.cumsum([len(x) for x in lists]))).astype(i32))
+
+        def col(lists, c, dt_=f64):
+            a = np.array([row[c] for x in lists for row in x], dt_)
+            return np.ascontiguousarray(a if a.size else np.zeros(1, dt_))
+        opp = [list(p.get("opponents", ())) for p in planners]
+        sta = [list(p.get("static", ())) for p in planners]
+        pref = [[KEY_IDS[a] if isinstance(a, str) else int(a) for a in p["pref"]] for p in planners]
+        zones = [sorted(set(int(g) for g in (p.get("zone_gids") or ()))) for p in planners]
+        arrs = dict(race=rows, opp_off=csr(opp), opp_s0=col(opp, 0), opp_vel_scale=col(opp, 1), opp_length=col(opp, 2),
+                    static_off=csr(sta), static_x=col(sta, 0), static_y=col(sta, 1), static_theta=col(sta, 2), static_v=col(sta, 3),
+                    static_length=col(sta, 4), pref_off=csr(pref),
+                    pref_action=np.ascontiguousarray(np.array([a for x in pref for a in x] or [0], i32)),
+                    pos_est_x=np.ascontiguousarray(np.array([float(p["pos_est"][0]) for p in planners], f64)),
+                    pos_est_y=np.ascontiguousarray(np.array([float(p["pos_est"][1]) for p in planners], f64)),
+                    vel_est=np.ascontiguousarray(np.array([float(p.get("vel_est", 0.0)) for p in planners], f64)),
+                    zone_off=csr(zones), zone_gid=np.ascontiguousarray(np.array([g for z in zones for g in z] or [0], i32)))
+        si = SimIn()
+        for k, a in arrs.items():
+            setattr(si, k, a.ctypes.data)
+        si.n_rl, si.t0, si.tic0, si.dt, si.n_export = rows.shape[0], float(t0), float(t0 if tic0 is None else tic0), float(dt), int(n_export)
+        self._check(self._fn("sim_setup")(self.handle, C.byref(si)))
+        self._sim_opp = int(arrs["opp_off"][-1])
+
+    def sim_vel(self, ax_tables=None, ax_table_idx=None, **vel_kwargs):
+        """Velocity arguments of the following ``sim_run`` calls (keywords of ``calc_vel_profile`` without pos_est / vel_est, scalars or one
+        value per planner; ``ax_tables`` + ``ax_table_idx``: a machine table per planner). local_gg as a dict is not supported."""
+        vi, keep = self._pack_vel_in([(0.0, 0.0)] * self.n_scen, 0.0, **vel_kwargs)
+        if ax_tables is not None:
+            keep = [keep]
+            Fleet._machine_tables(vi, ax_tables, ax_table_idx, keep)
+        self._check(self._fn("sim_vel")(self.handle, C.byref(vi)))
+
+    def sim_run(self, n_ticks, trace=True):
+        """``n_ticks`` closed-loop ticks back to back on the device (ltpl_fleet_sim_run). Returns (trace, ms): trace [n_ticks, n_planners,
+        SIM_TRACE_DOUBLES] -- sel action, t_now, pos_est x / y, vel_est, on-track vehicles, first vehicle X / Y, then the tick's digest row
+        (``digest``) -- or None with ``trace=False``. A failing planner raises BackendError after the run (``last_trace`` keeps the trace)."""
+        out = np.zeros((int(n_ticks), self.n_scen, SIM_TRACE_DOUBLES), np.float64) if trace else None
+        ms = C.c_float(0.0)
+        rc = self._fn("sim_run")(self.handle, int(n_ticks), None if out is None else out.ctypes.data, SIM_TRACE_DOUBLES, C.byref(ms))
+        self.last_trace, self.last_ms = out, float(ms.value)
+        self._check(rc)
+        return out, float(ms.value)
+
+    def sim_state(self):
+        """Simulation state: dict of pos_est [n, 2], vel_est, sel_action (ids), now, opponent s / tic (all opponents in planner order)."""
+        n, no = self.n_scen, getattr(self, "_sim_opp", 0)
+        px, py, v, now = (np.zeros(n, np.float64) for _ in range(4))
+        sel = np.zeros(n, np.int32)
+        os_, ot = np.zeros(max(no, 1), np.float64), np.zeros(max(no, 1), np.float64)
+        self._check(self._fn("sim_state")(self.handle, px.ctypes.data, py.ctypes.data, v.ctypes.data, sel.ctypes.data, now.ctypes.data,
+                                          os_.ctypes.data, ot.ctypes.data))
+        return dict(pos_est=np.column_stack((px, py)), vel_est=v, sel_action=sel, now=now, opp_s=os_[:no], opp_tic=ot[:no])

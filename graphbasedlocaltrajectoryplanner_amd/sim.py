@@ -1,0 +1,131 @@
+"""
+Closed-loop simulation of the example driver (``main_std_example.py:98-135``) for the fleet's device loop (``ltpl_fleet_sim_*``,
+include/ltpl_hip.h; csrc/fleet_sim.hpp): the race-line table the opponents drive on and scalar host mirrors of the two simulators the
+driver runs around the planner on every tick --
+
+  ``opponent_step``  one ``ObjectlistDummy.get_objectlist`` call (graph_ltpl/testing_tools/src/objectlist_dummy.py:148-170): the
+                     opponent's arc length integrated in 1 ms steps over the time since its last call, then position, heading and speed
+                     interpolated on the race line;
+  ``vdc_step``       one ``vdc_dummy`` call (graph_ltpl/testing_tools/src/vdc_dummy.py:5-58): the ideal tracker that moves the ego
+                     along its last trajectory for one tick.
+
+Both restate ``np.interp`` (numpy's ``arr_interp``) in the operation order of the device functions (``interp_at`` here,
+``fleet::sim_interp`` there), so that host and device give the same bits as the reference.
+"""
+import bisect
+import math
+
+import numpy as np
+
+from .offline_build import _closed_line_heading
+
+OPP_DT = 0.001        # integration step of both simulators (objectlist_dummy.py:149, vdc_dummy.py:46)
+VDC_MIN_STEP = 0.0001  # vdc_dummy.py:49
+
+
+def interp_at(x, xp, fp, j):
+    """``np.interp(x, xp, fp)`` for a scalar ``x`` once the segment is known: ``j`` = the largest index with ``xp[j] <= x`` (-1 below
+    ``xp[0]``, ``len(xp)`` above ``xp[-1]``). numpy's arr_interp: clamps at both ends, ``fp[j]`` on a knot, slope times offset plus
+    ``fp[j]`` inside a segment, and the same from the right end of the segment when that gives NaN."""
+    n = len(xp)
+    if j < 0:
+        return float(fp[0])
+    if j >= n - 1:
+        return float(fp[n - 1])
+    if xp[j] == x:
+        return float(fp[j])
+    slope = (fp[j + 1] - fp[j]) / (xp[j + 1] - xp[j])
+    r = slope * (x - xp[j]) + fp[j]
+    if math.isnan(r):
+        r = slope * (x - xp[j + 1]) + fp[j + 1]
+        if math.isnan(r) and fp[j] == fp[j + 1]:
+            r = fp[j]
+    return float(r)
+
+
+def segment(x, xp):
+    """Segment index of ``interp_at`` (``xp`` a Python list, non-decreasing)."""
+    if x < xp[0]:
+        return -1
+    if x > xp[-1]:
+        return len(xp)
+    return bisect.bisect_right(xp, x) - 1
+
+
+def interp(x, xp, fp):
+    """``np.interp`` for a scalar (``xp`` / ``fp`` Python lists)."""
+    if math.isnan(x):
+        return x
+    return interp_at(x, xp, fp, segment(x, xp))
+
+
+class RaceLineTable(object):
+    """The race line an ``ObjectlistDummy`` drives on (objectlist_dummy.py:112-127): ``refline + normvec * alpha``, ``s_rl =
+    cumsum(length_rl)`` (it does NOT start at 0), the heading of ``calc_head_curv_num(is_closed=True)`` shifted into [0, 2 pi) and the
+    race-line speed. ``rows()`` is the [n, 5] table [s_rl, x, y, psi, vel_rl] of ``ltpl_fleet_sim_in``."""
+
+    def __init__(self, s_rl, x, y, psi, vel_rl):
+        self.s_rl, self.x, self.y, self.psi, self.vel_rl = (np.ascontiguousarray(np.asarray(a, dtype=np.float64)) for a in
+                                                            (s_rl, x, y, psi, vel_rl))
+
+    @classmethod
+    def from_track(cls, track):
+        """``track``: mapping with refline [n, 2], normvec [n, 2], alpha, length_rl, vel_rl (the track npz / the reference's csv)."""
+        refline = np.asarray(track['refline'], dtype=float)
+        normvec = np.asarray(track['normvec'], dtype=float)
+        alpha = np.asarray(track['alpha'], dtype=float)
+        length_rl = np.asarray(track['length_rl'], dtype=float)
+        raceline = refline + normvec * alpha[:, np.newaxis]
+        psi = _closed_line_heading(raceline, length_rl)
+        psi = np.where(psi < 0.0, psi + np.pi * 2, psi)
+        return cls(np.cumsum(length_rl), raceline[:, 0], raceline[:, 1], psi, np.asarray(track['vel_rl'], dtype=float))
+
+    def rows(self):
+        return np.ascontiguousarray(np.column_stack((self.s_rl, self.x, self.y, self.psi, self.vel_rl)))
+
+    def lists(self):
+        return [a.tolist() for a in (self.s_rl, self.x, self.y, self.psi, self.vel_rl)]
+
+
+def opponent_step(tab, s, tic, now, vel_scale, lists=None):
+    """One ``ObjectlistDummy.get_objectlist`` call at clock value ``now``: returns (s, tic, x, y, psi, v). ``lists``: ``tab.lists()``
+    (pass it in a loop: the conversion is the expensive part)."""
+    s_rl, xs, ys, psis, vel = lists if lists is not None else tab.lists()
+    vel_s = [v * vel_scale for v in vel]              # the scaled table is formed first (objectlist_dummy.py:121)
+    toc = now - tic
+    tic = now
+    t = 0.0
+    while t < toc:
+        s += interp(s, s_rl, vel_s) * OPP_DT
+        t += OPP_DT
+        if s >= s_rl[-1]:
+            s = 0.0
+    j = segment(s, s_rl)
+    x, y = interp_at(s, s_rl, xs, j), interp_at(s, s_rl, ys, j)
+    psi = interp_at(s, s_rl, psis, j)
+    if psi > np.pi:
+        psi -= 2 * np.pi
+    return s, tic, x, y, psi, interp_at(s, s_rl, vel_s, j)
+
+
+def vdc_step(pos_est, traj, iter_time):
+    """One ``vdc_dummy`` call: ``traj`` = the exported trajectory (rows [s, x, y, psi, kappa, vx, ax], already trimmed to the exported
+    rows). Returns (pos_out [x, y], vel_est). Exact ties of the two-nearest search take the lower index (numpy leaves their order
+    open)."""
+    traj = np.asarray(traj, dtype=float)
+    sc, px, py, vx = (traj[:, c].tolist() for c in (0, 1, 2, 5))
+    n = len(sc)
+    if n <= 2:
+        return [float(pos_est[0]), float(pos_est[1])], float(vx[0])
+    ex, ey = float(pos_est[0]), float(pos_est[1])
+    d2 = [(px[i] - ex) * (px[i] - ex) + (py[i] - ey) * (py[i] - ey) for i in range(n)]
+    i1 = min(range(n), key=lambda i: (d2[i], i))
+    i2 = min((i for i in range(n) if i != i1), key=lambda i: (d2[i], i))
+    i = min(i1, i2)
+    s = math.sqrt(d2[i]) + sc[i]
+    t = 0.0
+    while t < iter_time:
+        s += max(interp(s, sc, vx) * OPP_DT, VDC_MIN_STEP)
+        t += OPP_DT
+    j = segment(s, sc)
+    return [interp_at(s, sc, px, j), interp_at(s, sc, py, j)], interp_at(s, sc, vx, j)

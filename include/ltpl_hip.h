@@ -647,6 +647,69 @@ int ltpl_fleet_tape_clear(ltpl_fleet* fleet);
 int ltpl_fleet_tape_append(ltpl_fleet* fleet, const ltpl_planner_paths_in* paths_in, const ltpl_planner_vel_in* vel_in);
 int ltpl_fleet_tape_run(ltpl_fleet* fleet, int32_t first, int32_t count, float* ms_total /* may be NULL */);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Additive to ABI v9 -- CLOSED-LOOP SIMULATION of the fleet on the device: the example driver's loop (main_std_example.py:98-135)
+ * around every planner, with no host work per tick. Tick k of planner p (csrc/fleet_sim.hpp, one wave64 per planner):
+ *   1. now += dt (fp64 accumulation, t_now of the tick = now);
+ *   2. the action: the first entry of the planner's preference list that is a key of the previous tick's exported trajectory set (before
+ *      the first tick: {'straight': None}); none -> the planner's error word is set (the driver's KeyError) and the planner stops;
+ *   3. the opponents (ObjectlistDummy, objectlist_dummy.py:148-170): toc = now - tic, tic = now, 1 ms steps of
+ *      s += interp(s, s_rl, vel_rl * vel_scale) * 0.001 while t < toc (s = 0 at s >= s_rl[-1]), then x, y, psi (psi > pi -> - 2 pi), v
+ *      interpolated on the race line; the planner's static objects follow in list order;
+ *   4. object ingestion (on-track test, 0.2 s constant-velocity prediction, radius = length / 2: ltpl_process_objects' device code);
+ *      objects off the track are dropped, the others compacted into the fleet's object layout (count, exclusive scan, write);
+ *   5. the ego tracker (vdc_dummy.py:5-58, iter_time = dt) on the previous tick's trajectory of the selected action, trimmed to n_export
+ *      rows: the two nearest rows (exact ties: the LOWER indices; numpy leaves their order open), s = distance + s of the lower one,
+ *      1 ms steps of max(interp(s) * 0.001, 0.0001), then x, y, vx interpolated; <= 2 rows: the pose stays, vel_est = vx[0];
+ *   6. the fleet's tick on these inputs (paths_pre, path kernel, paths_post, velocity stages), zones constant per planner.
+ * np.interp is replayed in numpy's operation order (clamping at both ends, fp[j] on a knot, the NaN fallback). Opponent poses depend on
+ * the clock and the race line alone and are bit-identical to the reference's.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define LTPL_FLEET_SIM_MAX_PREF     5     /* entries of a preference list (LTPL_ACT_*, emergency allowed)              */
+#define LTPL_FLEET_SIM_MAX_EXPORT 256     /* n_export cap (the reference's nmbr_export_points: 115, Graph_LTPL.py:400-406) */
+/* trace record per tick and planner: [0] sel action, [1] t_now, [2] pos_est x, [3] pos_est y, [4] vel_est, [5] on-track vehicles,
+ * [6] / [7] X / Y of the first vehicle (NaN without one), then the tick's ltpl_fleet_digest row */
+#define LTPL_FLEET_SIM_TRACE_DOUBLES (8 + LTPL_FLEET_DIGEST_DOUBLES)
+
+typedef struct {
+    int32_t n_rl;                   /* rows of the race-line table, >= 2                                          */
+    const double*  race;            /* [n_rl * 5] rows [s_rl, x, y, psi, vel_rl], s_rl non-decreasing (shared by the fleet)  */
+    const int32_t* opp_off;         /* [n + 1] opponents of planner p: opp_off[p] .. opp_off[p + 1]               */
+    const double*  opp_s0;          /* [n_opp] initial arc length                                                 */
+    const double*  opp_vel_scale;   /* [n_opp] factor on vel_rl                                                   */
+    const double*  opp_length;      /* [n_opp] object length (radius = length / 2)                                */
+    const int32_t* static_off;      /* [n + 1] static objects of planner p, behind its opponents in the object list */
+    const double*  static_x;        /* [n_static] ...                                                             */
+    const double*  static_y;
+    const double*  static_theta;
+    const double*  static_v;
+    const double*  static_length;
+    double  t0;                     /* clock before the first tick                                                */
+    double  tic0;                   /* time of every opponent's previous call                                      */
+    double  dt;                     /* clock step per tick (also vdc_dummy's iter_time), > 0                       */
+    int32_t n_export;               /* exported trajectory rows, 1 .. LTPL_FLEET_SIM_MAX_EXPORT                     */
+    const int32_t* pref_off;        /* [n + 1] preference list of planner p: 1 .. LTPL_FLEET_SIM_MAX_PREF entries    */
+    const int32_t* pref_action;     /* LTPL_ACT_* in order of preference                                           */
+    const double*  pos_est_x;       /* [n] initial pose estimate / velocity                                        */
+    const double*  pos_est_y;
+    const double*  vel_est;
+    const int32_t* zone_off;        /* [n + 1] node ids the "overtaking_zones" filter removes (constant per run)   */
+    const int32_t* zone_gid;
+} ltpl_fleet_sim_in;
+
+/* (re)initialises the simulation of every planner; the planners' own memory (ltpl_fleet_set_start) is not touched */
+int ltpl_fleet_sim_setup(ltpl_fleet* fleet, const ltpl_fleet_sim_in* in);
+/* velocity arguments of the following runs (pos_est / vel_est members ignored; gg_row_off / gg_rows: LTPL_ERR_UNSUPPORTED) */
+int ltpl_fleet_sim_vel(ltpl_fleet* fleet, const ltpl_planner_vel_in* in);
+/* n_ticks ticks back to back on the handle's stream; trace (may be NULL): [n_ticks][n][doubles_per_tick_planner] with
+ * doubles_per_tick_planner == LTPL_FLEET_SIM_TRACE_DOUBLES, copied out once at the end; ms_total (may be NULL): device time of the run.
+ * Returns the status of the first failing planner like ltpl_fleet_tape_run; the trace is written either way. */
+int ltpl_fleet_sim_run(ltpl_fleet* fleet, int32_t n_ticks, double* trace, int32_t doubles_per_tick_planner, float* ms_total);
+/* copy-out of the simulation state (every pointer may be NULL): [n] pose estimate, velocity, last selected action, clock;
+ * [n_opp] opponent arc length and time of its last call */
+int ltpl_fleet_sim_state(ltpl_fleet* fleet, double* pos_est_x, double* pos_est_y, double* vel_est, int32_t* sel_action, double* now,
+                         double* opp_s, double* opp_tic);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,77 @@
+"""Closed-loop SIMULATION rate of a fleet (ltpl_fleet_sim_*): N planners, each with its own eight C2-style race-line opponents (SURVEY.md
+section 8d: s0_k = 250 + 280 k, vel_scale_k = 0.30 + 0.05 (k mod 4), here staggered by 10 m (p mod 16) per planner), run the example
+driver's loop on the device for T ticks without host work per tick.   tools/sim_rate.py [--planners 32768] [--ticks 200] [--no-tape]
+Prints planner-ticks per second of sim_run (device time of the run) next to tape_run on the C2 tape (recorded inputs, tools/fleet_rate.py)."""
+import argparse
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np                                                            # noqa: E402
+import planner_replay as pr                                                   # noqa: E402
+from graphbasedlocaltrajectoryplanner_amd import _capi                        # noqa: E402
+from graphbasedlocaltrajectoryplanner_amd.fleet import Fleet                  # noqa: E402
+from graphbasedlocaltrajectoryplanner_amd.lattice import Lattice              # noqa: E402
+from graphbasedlocaltrajectoryplanner_amd.sim import RaceLineTable            # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--planners", type=int, default=32768)
+    ap.add_argument("--ticks", type=int, default=200)
+    ap.add_argument("--reps", type=int, default=2)
+    ap.add_argument("--no-tape", action="store_true", help="skip the tape_run comparison on the C2 recording")
+    a = ap.parse_args()
+    lat = Lattice.load(os.path.join(ROOT, "tests", "golden", "monteblanco_lattice.npz"))
+    race = RaceLineTable.from_track(np.load(os.path.join(ROOT, "tests", "golden", "monteblanco_track.npz")))
+    hip = _capi.HipBackend(lat)
+    ticks = pr.load_ticks("c2")
+    st, va = ticks[0]['start'], ticks[0]['vel_args']
+    zones = pr.zone_gids_of_tick(lat, ticks[0])
+    n = a.planners
+    entries = [dict(opponents=[(250.0 + 280.0 * k + 10.0 * (p % 16), 0.30 + 0.05 * (k % 4), 5.0) for k in range(8)],
+                    pref=("right", "left", "straight", "follow"), pos_est=st['pos'], vel_est=0.0, zone_gids=zones) for p in range(n)]
+    best = None
+    for rep in range(a.reps):
+        fleet = Fleet(hip, n)
+        fleet.set_start_range(0, n, st['pos'], st['heading'], st['vel'], st['max_heading_offset'])
+        fleet.sim_setup(race, entries)
+        fleet.sim_vel(vel_max=va['vel_max'], gg_scale=va['gg_scale'], local_gg=tuple(va['local_gg']), safety_d=va['safety_d'],
+                      ax_max_machines=va['ax_max_machines'])
+        t0 = time.perf_counter()
+        failed = 0
+        try:
+            _, ms = fleet.sim_run(a.ticks, trace=False)
+        except _capi.BackendError as e:
+            ms = fleet.last_ms
+            failed = int(np.count_nonzero(fleet.digest()[:, 0]))
+            print("  (%d planners stopped with an error: %s)" % (failed, str(e)[:160]))
+        wall = time.perf_counter() - t0
+        best = ms if best is None else min(best, ms)
+        print("rep %d: sim_run %d planners x %d ticks: device %.1f ms (wall %.1f ms) = %.3f M planner-ticks/s; %.3f ms per tick of the fleet" % (
+            rep, n, a.ticks, ms, wall * 1e3, n * a.ticks / ms / 1e3, ms / a.ticks))
+        if failed == 0:
+            sel = np.bincount(fleet.sim_state()['sel_action'] + 1, minlength=6)
+            print("  last selected actions (none, straight, follow, left, right, emergency): %s" % sel.tolist())
+        fleet.close()
+    print("closed_loop_sim_ticks_per_s %.0f" % (n * a.ticks / best * 1e3))
+    if a.no_tape:
+        return
+    fleet = Fleet(hip, n)
+    for k in range(a.ticks):
+        t, v = ticks[k], ticks[k]['vel_args']
+        fleet.tape_append_groups([(n, dict(prev_action=t['action_id_sel'], t_now=t['t'], vehicles=pr.vehicles_of_tick(t), zone_gids=zones,
+                                           pos_est=t['pos_est'], vel_est=v['vel_est'], vel_max=v['vel_max'], gg_scale=v['gg_scale'],
+                                           local_gg=tuple(v['local_gg']), safety_d=v['safety_d'], incl_emerg_traj=v['incl_emerg_traj']))],
+                                 ax_max_machines=v['ax_max_machines'])
+    fleet.set_start_range(0, n, st['pos'], st['heading'], st['vel'], st['max_heading_offset'])
+    ms = fleet.tape_run(0, a.ticks)
+    print("tape_run (C2 recording) %d planners x %d ticks: device %.1f ms = %.3f M planner-ticks/s" % (n, a.ticks, ms, n * a.ticks / ms / 1e3))
+    print("closed_loop_device_ticks_per_s %.0f" % (n * a.ticks / ms * 1e3))
+
+
+if __name__ == "__main__":
+    main()
