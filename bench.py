@@ -16,7 +16,13 @@ are per step), bracketed by barrier + synchronize on both sides.
                   as DIR/<name>.npy, float64: see dump_outputs(). The inputs are seeded, so two builds run with the same arguments
                   can be compared output for output.
 
-The JSON line also carries
+A plain run does only what the headline needs: set up, warm up, time the K steps, dump if asked, print the line (metric, value, unit,
+ms_per_step, higher_is_better, dtype, the step counts, per-rank times and the config). Every other leg runs only with
+
+  --full          the line also carries the fields below (and, at N > 1, the sharded fleet leg); --no-cpu, --no-extra and
+                  --latency-ticks 0 drop legs of a full run as before.
+
+The JSON line of a --full run also carries
   roofline        ALGORITHMIC bytes per launch (graphbasedlocaltrajectoryplanner_amd/roofline.py) of the
                   dominant kernel (path kernel: mask + sweeps + spline) divided by its average duration measured with HIP
                   events on the library's own stream inside the timed region, against the 8 TB/s HBM peak; `traffic` = HBM
@@ -805,8 +811,10 @@ def worker(args):
     paths_ms_live = hip.batch_last_paths_ms()                    # path kernel inside the timed region (events per launch)
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0)
-    res, vres = hip.batch_download()                             # the outputs of the last timed step
-    if getattr(args, "dump_outputs", None) and rank == 0:
+    dump = getattr(args, "dump_outputs", None) and rank == 0
+    if args.full or dump:
+        res, vres = hip.batch_download()                         # the outputs of the last timed step
+    if dump:
         dump_outputs(args.dump_outputs, res, vres)
 
     def gather_over_ranks(x):
@@ -817,6 +825,45 @@ def worker(args):
         dist.all_gather(outl, t)
         return [float(o.item()) for o in outl]
     per_rank_ms = [v / timed_steps * 1e3 for v in gather_over_ranks(own_s)]
+    # units of one step over ALL ranks (weak: every rank owns --batch scenarios; strong: the fixed --batch-total)
+    total_units = args.batch_total if strong else world * args.batch
+    headline = {
+        "metric": "planning ticks/s (all action primitives), " + ("Monteblanco lattice" if args.workload == "c2" else "synthetic C3 lattice"),
+        "value": total_units * timed_steps / elapsed,
+        "unit": "ticks/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "timed_steps": timed_steps,
+        "ms_per_step": elapsed / timed_steps * 1e3,
+        # every rank's own time per step for ITS shard (the line's ms_per_step is the max-over-ranks region incl. the closing barrier);
+        # scaling efficiency is the driver's to compute from the per-N lines -- the field is a placeholder it may fill
+        "per_rank_ms_per_step": per_rank_ms, "efficiency_vs_n1": None,
+        "higher_is_better": True, "scaling": "strong" if strong else "weak",
+        # BASELINE.md holds no published number for this metric (the reference publishes none): null, as the contract asks. The ratio to
+        # BASELINE.json's stated TARGET (>= 10 000 ticks/s per GPU on C2) is `vs_target`; the measured CPU baseline is in `cpu_baseline`
+        # (--full)
+        "vs_baseline": None,
+        "vs_target": (total_units * timed_steps / elapsed) / (TARGET_TICKS_PER_S * world) if args.workload == "c2" else None,
+        "vs_target_basis": "BASELINE.json target: >= 10 000 ticks/s per GPU on C2 (no published reference number exists)",
+        # the path kernel (mask, sweeps, spline) computes in fp64 throughout; the lane kernels of the velocity stage read |kappa| and the
+        # element length as an fp32 pair and take 1 / |kappa| from v_rcp_f32 -- their profile state and every output are fp64
+        "dtype": "f64", "data": "synthetic",
+        "config": {"workload": (("C2: Monteblanco lattice (%d layers / %d nodes / %d edges), 4 action primitives, 8 dynamic "
+                                 "opponents (16 obstacle positions), sample zone" if args.workload == "c2" else
+                                 "C3: synthetic oval lattice (%d layers / %d nodes / %d edges), 4 action primitives, 32 static "
+                                 "obstacles (64 obstacle positions)") % (lat.num_layers, lat.num_nodes, lat.num_edges))
+                               + ("; a fixed batch of %d independent scenarios per step block-partitioned over the ranks (C4), tick pipeline "
+                                  "(paths + velocity)" % total_units if strong else
+                                  "; %d independent scenarios per GPU per step, tick pipeline (paths + velocity)" % args.batch),
+                   "batch_per_gpu": args.batch, "batch_total": total_units,
+                   "parallelism": "scenario-sharded x%d (no collective; results stay on the ranks)" % world},
+    }
+    if not args.full:
+        # a plain run ends here: the headline needs nothing else (every other leg is behind --full)
+        if rank == 0:
+            print(json.dumps(headline))
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # N > 1: the state-carrying fleet sharded like the scenario batches -- every rank owns a block of the vehicles (sharding.fleet_shard),
     # no communication between the fleets; a short tape of the recorded C2 loop per rank, rates summed over the ranks
     fleet_sharded = None
@@ -833,8 +880,6 @@ def worker(args):
 
     # per-kernel durations of the pipeline (HIP events between the launches on the library's stream), outside the timed region
     prof_ms = hip.batch_run_profile(reps=20)
-    # units of one step over ALL ranks (weak: every rank owns --batch scenarios; strong: the fixed --batch-total)
-    total_units = args.batch_total if strong else world * args.batch
     if rank == 0:
         ab = algorithmic_bytes(lat, batch, res)
         kern_ms = ms_kernel / timed_steps
@@ -940,34 +985,7 @@ def worker(args):
         # contract's HBM figure
         binding = binding_of(issue)
         out = {
-            "metric": "planning ticks/s (all action primitives), " + ("Monteblanco lattice" if args.workload == "c2" else "synthetic C3 lattice"),
-            "value": total_units * timed_steps / elapsed,
-            "unit": "ticks/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "timed_steps": timed_steps,
-            "ms_per_step": elapsed / timed_steps * 1e3,
-            # every rank's own time per step for ITS shard (the line's ms_per_step is the max-over-ranks region incl. the closing barrier);
-            # scaling efficiency is the driver's to compute from the per-N lines -- the field is a placeholder it may fill
-            "per_rank_ms_per_step": per_rank_ms, "efficiency_vs_n1": None,
-            "higher_is_better": True, "scaling": "strong" if strong else "weak",
-            # BASELINE.md holds no published number for this metric (the reference publishes none); the only figure it states for this
-            # config is BASELINE.json's target of >= 10 000 planning ticks/s on one GPU -- the ratio below is against that TARGET
-            # BASELINE.md holds no published number for this metric (the reference publishes none): null, as the contract asks. The ratio to
-            # BASELINE.json's stated TARGET (>= 10 000 ticks/s per GPU on C2) is `vs_target`; the measured CPU baseline is in `cpu_baseline`
-            "vs_baseline": None,
-            "vs_target": (total_units * timed_steps / elapsed) / (TARGET_TICKS_PER_S * world) if args.workload == "c2" else None,
-            "vs_target_basis": "BASELINE.json target: >= 10 000 ticks/s per GPU on C2 (no published reference number exists)",
-            # the path kernel (mask, sweeps, spline) computes in fp64 throughout; the lane kernels of the velocity stage read |kappa| and the
-            # element length as an fp32 pair and take 1 / |kappa| from v_rcp_f32 -- their profile state and every output are fp64
-            "dtype": "f64", "data": "synthetic",
-            "config": {"workload": (("C2: Monteblanco lattice (%d layers / %d nodes / %d edges), 4 action primitives, 8 dynamic "
-                                     "opponents (16 obstacle positions), sample zone" if args.workload == "c2" else
-                                     "C3: synthetic oval lattice (%d layers / %d nodes / %d edges), 4 action primitives, 32 static "
-                                     "obstacles (64 obstacle positions)") % (lat.num_layers, lat.num_nodes, lat.num_edges))
-                                   + ("; a fixed batch of %d independent scenarios per step block-partitioned over the ranks (C4), tick pipeline "
-                                      "(paths + velocity)" % total_units if strong else
-                                      "; %d independent scenarios per GPU per step, tick pipeline (paths + velocity)" % args.batch),
-                       "batch_per_gpu": args.batch, "batch_total": total_units,
-                       "parallelism": "scenario-sharded x%d (no collective; results stay on the ranks)" % world},
+            **headline,
             # the library this line was measured on (LTPL_HIP_LIB can redirect it) and the digest the counter passes are matched against
             "library": stamp,
             # `bound`: what binds the kernel (the same word as `binding.bound`: latency-bound, its busiest pipe named); `contract_bound`: the
@@ -1056,6 +1074,9 @@ def main():
     ap.add_argument("--fleet-ticks", type=int, default=200, help="extra.closed_loop_device: consecutive ticks")
     ap.add_argument("--c3-batch", type=int, default=32768, help="extra.c3: scenarios per step (one size for builder and driver since round 5: the headline's)")
     ap.add_argument("--c5-ticks", type=int, default=400, help="extra.c5: ticks per horizon")
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg besides the headline: roofline and per-kernel figures, CPU baseline and parity, latency, the extra "
+                         "configurations (C3, C4, C5, fleet); a plain run only times the steps")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-extra", action="store_true")
     ap.add_argument("--exact-steps", action="store_true", help="accepted for older scripts: --steps is always the number of timed steps")

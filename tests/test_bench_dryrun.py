@@ -118,9 +118,11 @@ class StandInBackend(object):
         return 0.8
 
     def batch_run_profile(self, reps=10):
+        self.calls.append("batch_run_profile")
         return [0.8, 0.07, 0.15]
 
     def batch_download(self):
+        self.calls.append("batch_download")
         return self.orc.tick_batch(*self._resident)
 
     def close(self):
@@ -145,7 +147,7 @@ def run_worker(monkeypatch, capsys, **over):
     monkeypatch.setattr(torch.cuda, "synchronize", lambda *a: None)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         monkeypatch.delenv(k, raising=False)
-    args = dict(gpus=1, steps=3, warmup=1, batch=64, cpu_sample=8, latency_ticks=4, dropin_ticks=40, no_cpu=False,
+    args = dict(gpus=1, steps=3, warmup=1, batch=64, cpu_sample=8, latency_ticks=4, dropin_ticks=40, full=False, no_cpu=False,
                 no_extra=False, exact_steps=True, workload="c2", fleet_planners=4, fleet_ticks=40, c3_batch=6, c5_ticks=2)
     args.update(over)
     bench.worker(argparse.Namespace(**args))
@@ -155,7 +157,7 @@ def run_worker(monkeypatch, capsys, **over):
 
 
 def test_the_line_carries_the_drivers_contract(monkeypatch, capsys):
-    out, hip = run_worker(monkeypatch, capsys)
+    out, hip = run_worker(monkeypatch, capsys, full=True)
     for key, typ in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int),
                      ("ms_per_step", float), ("higher_is_better", bool), ("scaling", str), ("dtype", str), ("data", str),
                      ("config", dict), ("roofline", dict), ("cpu_baseline", dict)):
@@ -249,7 +251,7 @@ def test_counter_passes_are_tied_to_the_build(monkeypatch, capsys, tmp_path):
         for name, d in (("pmc_issue.json", issue), ("pmc_traffic.json", traffic)):
             with open(tmp_path / name, "w") as fh:
                 json.dump(dict(d, build=build) if build else d, fh)
-        out, _ = run_worker(monkeypatch, capsys, no_cpu=True, no_extra=True, latency_ticks=0)
+        out, _ = run_worker(monkeypatch, capsys, full=True, no_cpu=True, no_extra=True, latency_ticks=0)
         r = out["roofline"]
         assert r["issue"]["build_matches"] is expect and r["traffic_build_matches"] is expect
         assert r["traffic"] == 1.4e6 and r["issue"]["valu_insts_per_scenario"] == pytest.approx(5.0e5 / 64)
@@ -259,10 +261,24 @@ def test_counter_passes_are_tied_to_the_build(monkeypatch, capsys, tmp_path):
 
 
 def test_flags_that_drop_legs(monkeypatch, capsys):
-    out, hip = run_worker(monkeypatch, capsys, no_cpu=True, no_extra=True, latency_ticks=0)
+    out, hip = run_worker(monkeypatch, capsys, full=True, no_cpu=True, no_extra=True, latency_ticks=0)
     assert "cpu_baseline" not in out and "parity_checked" not in out and out["extra"] == {}
     assert out["latency_us"]["p50"] is None and out["latency_us"]["dropin_p50"] is None and out["latency_us"]["ticks"] == 0
     assert "tick_batch" not in hip.calls
+
+
+def test_a_plain_run_only_times_the_steps(monkeypatch, capsys):
+    """Without --full the line carries the headline and nothing that needs a leg of its own: one backend, one upload, the warm-up and timed
+    runs; no profile pass, no download (nothing is dumped), no CPU baseline, latency or extra configuration."""
+    out, hip = run_worker(monkeypatch, capsys, steps=4, warmup=2)
+    assert set(out) == {"metric", "value", "unit", "n_gpus", "steps", "warmup", "timed_steps", "ms_per_step", "per_rank_ms_per_step",
+                        "efficiency_vs_n1", "higher_is_better", "scaling", "vs_baseline", "vs_target", "vs_target_basis", "dtype", "data",
+                        "config"}
+    assert out["unit"] == "ticks/s" and out["higher_is_better"] is True and out["dtype"] == "f64" and "ticks/s" in out["metric"]
+    assert out["steps"] == 4 and out["warmup"] == 2 and out["timed_steps"] == 4 and out["ms_per_step"] > 0
+    assert abs(out["value"] * out["ms_per_step"] * 1e-3 - 64.0) < 1e-6
+    assert out["config"]["batch_per_gpu"] == 64 and out["vs_target"] == pytest.approx(out["value"] / 10000.0)
+    assert hip.calls == ["batch_upload"] + ["batch_run"] * 4                  # 2 warm-up steps, the untimed K-step block, the timed steps
 
 
 def test_steps_sets_the_timed_steps_and_outputs_are_dumped(monkeypatch, capsys, tmp_path):
@@ -317,7 +333,7 @@ def _rank_main(rank, port, out_dir, strong=False):
     torch.cuda.is_available = lambda: True
     torch.cuda.set_device = lambda d: None
     torch.cuda.synchronize = lambda *a: None
-    args = argparse.Namespace(gpus=2, steps=2, warmup=1, batch=64, cpu_sample=8, latency_ticks=0, dropin_ticks=0, no_cpu=False,
+    args = argparse.Namespace(gpus=2, steps=2, warmup=1, batch=64, cpu_sample=8, latency_ticks=0, dropin_ticks=0, full=True, no_cpu=False,
                               no_extra=True, exact_steps=True, workload="c2", scaling="strong" if strong else "weak", batch_total=100)
     with open(os.path.join(out_dir, "rank%d.out" % rank), "w") as fh, contextlib.redirect_stdout(fh):
         bench.worker(args)

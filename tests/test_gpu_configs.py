@@ -308,7 +308,7 @@ def test_bench_two_ranks_strong_scaling_on_one_gpu():
     import subprocess
     import sys
     env = dict(os.environ, LTPL_BENCH_SHARE_GPU="1")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "3", "--scaling", "strong",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "3", "--full", "--scaling", "strong",
                         "--batch-total", "1024", "--exact-steps", "--cpu-sample", "64", "--no-extra", "--latency-ticks", "0"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -329,7 +329,7 @@ def test_bench_two_ranks_on_one_gpu(tmp_path):
     import subprocess
     import sys
     env = dict(os.environ, LTPL_BENCH_SHARE_GPU="1")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "2", "--batch", "4096",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "2", "--full", "--batch", "4096",
                         "--exact-steps", "--cpu-sample", "64", "--fleet-planners", "512", "--fleet-ticks", "40"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of library variants on ONE box (boxes differ by +-3 %): tools/ab_bench.sh <lib or "base"> ...   -> ticks/s, path kernel ms per variant
 # alternating runs, 2 rounds
-ARGS="--steps 100 --warmup 10 --no-cpu --latency-ticks 0 --dropin-ticks 0 --no-extra"
+ARGS="--full --steps 100 --warmup 10 --no-cpu --latency-ticks 0 --dropin-ticks 0 --no-extra"
 for round in 1 2; do
   for V in "$@"; do
     if [ "$V" = base ]; then unset LTPL_HIP_LIB; else export LTPL_HIP_LIB=$PWD/$V; fi

@@ -1,11 +1,13 @@
 #!/usr/bin/env python
-"""One-screen summary of a bench.py JSON line (tools/gpu_session.sh): headline, path kernel, parity, latency, the extra legs."""
+"""One-screen summary of a bench.py JSON line (tools/gpu_session.sh): headline; with --full also path kernel, parity, latency, the extra legs."""
 import json
 import sys
 
 d = json.loads([l for l in open(sys.argv[1]).read().splitlines() if l.startswith("{")][-1])
-r = d["roofline"]
 print("value %.3f M %s  ms/step %.4f  n_gpus %d  scaling %s  dtype %s" % (d["value"] / 1e6, d["unit"], d["ms_per_step"], d["n_gpus"], d["scaling"], d["dtype"]))
+if "roofline" not in d:
+    sys.exit(0)                 # a plain run (no --full): the headline is all the line holds
+r = d["roofline"]
 print("k_paths live %.4f ms  alone %.4f ms  frac %.3f  bound %s  pipeline %s" % (r["kernel_ms"], r["kernel_ms_not_overlapped"], r["frac"], r["bound"],
                                                                               {k: round(v, 4) for k, v in r["pipeline_ms"].items()}))
 if "parity_detail" in d:

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Same-box A/B of ENVIRONMENT settings on the headline (alternating short bench runs, 2 rounds):  tools/env_ab.sh "LTPL_FINAL_Y=8" "LTPL_FINAL_Y=2" ...
-ARGS="--steps 100 --warmup 10 --no-cpu --latency-ticks 0 --dropin-ticks 0 --no-extra"
+ARGS="--full --steps 100 --warmup 10 --no-cpu --latency-ticks 0 --dropin-ticks 0 --no-extra"
 for round in 1 2; do
   for S in "$@"; do
     env $S python bench.py $ARGS 2>/dev/null | python -c "

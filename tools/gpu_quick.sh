@@ -10,6 +10,7 @@ if [ "$T" = "tests" ]; then
   echo "gpu tests rc=$?"; tail -4 gpurun_out/${TAG}_gputest.log
 fi
 ARGS=${@:-"--steps 100 --warmup 10 --no-cpu --latency-ticks 300 --dropin-ticks 600 --no-extra"}
+ARGS="--full $ARGS"                       # (the summary below reads the roofline and latency fields)
 timeout 600 python bench.py $ARGS > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err
 echo "bench rc=$?"
 python - <<PY

@@ -7,7 +7,7 @@
 # Steps (executed in the order given; a step that fails is reported and the session goes on):
 #   tests[:<pytest -k expr>]   the GPU parity suite (pytest -m gpu), optionally a subset             -> gputest.txt
 #   smoke                      __graft_entry__.smoke()                                                -> smoke.txt
-#   bench[:<args>]             python bench.py [args] (default: the driver's form, no flags)          -> bench.json, bench_time.txt
+#   bench[:<args>]             python bench.py [args] (default: the driver's plain form; bench:--full for every leg) -> bench.json, bench_time.txt
 #   quick                      short bench line without CPU leg / extras                              -> quick.json
 #   stats                      rocprofv3 --kernel-trace --stats of a short bench run                  -> kernel_stats.csv
 #   stats_alone                the same with LTPL_NO_OVERLAP=1 (per-kernel durations without overlap) -> kernel_stats_alone.csv
@@ -35,11 +35,11 @@ for STEP in "$@"; do
       ( time timeout 1200 python bench.py $ARG > $O/bench.json 2> $O/bench.err ) 2> $O/bench_time.txt; echo "bench rc=$?"
       python tools/bench_brief.py $O/bench.json; tail -3 $O/bench_time.txt; tail -3 $O/bench.err ;;
     quick)
-      timeout 600 python bench.py --steps 100 --warmup 10 --no-cpu --latency-ticks 300 --dropin-ticks 600 --no-extra $ARG > $O/quick.json 2> $O/quick.err; echo "quick rc=$?"
+      timeout 600 python bench.py --full --steps 100 --warmup 10 --no-cpu --latency-ticks 300 --dropin-ticks 600 --no-extra $ARG > $O/quick.json 2> $O/quick.err; echo "quick rc=$?"
       python tools/bench_brief.py $O/quick.json ;;
     stats|stats_alone)
       [ $NAME = stats_alone ] && export LTPL_NO_OVERLAP=1
-      timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$NAME -o k -- python bench.py --steps 50 --warmup 5 --no-cpu --latency-ticks 200 --dropin-ticks 300 --exact-steps --no-extra > $O/$NAME.log 2>&1; echo "$NAME rc=$?"
+      timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$NAME -o k -- python bench.py --full --steps 50 --warmup 5 --no-cpu --latency-ticks 200 --dropin-ticks 300 --exact-steps --no-extra > $O/$NAME.log 2>&1; echo "$NAME rc=$?"
       unset LTPL_NO_OVERLAP
       F=kernel_stats.csv; [ $NAME = stats_alone ] && F=kernel_stats_alone.csv
       find $O/$NAME -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/$F; head -14 $O/$F | cut -c1-170 ;;

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of LTPL_VEL_CUS (velocity streams confined to n compute units by a CU mask) on ONE box: tools/vel_cus_ab.sh <n> ...   (0 = no mask)
-ARGS="--steps 100 --warmup 10 --no-cpu --latency-ticks 0 --dropin-ticks 0 --no-extra"
+ARGS="--full --steps 100 --warmup 10 --no-cpu --latency-ticks 0 --dropin-ticks 0 --no-extra"
 for round in 1 2; do
   for N in "$@"; do
     LTPL_VEL_CUS=$N python bench.py $ARGS 2>/dev/null | python -c "

@@ -1,7 +1,7 @@
 #!/bin/bash
 # fp32 vs fp64 operand records of the lane kernels (|kappa|, element length): ticks/s and worst relative error per quantity of both builds on
 # ONE box.   tools/vel_precision_ab.sh <fp32 variant library>     (round 6: fp64 records are the default; the variant is built with -DLTPL_VEL_F32_OPERANDS)
-ARGS="--steps 100 --warmup 10 --latency-ticks 0 --dropin-ticks 0 --no-extra --cpu-sample 1024"
+ARGS="--full --steps 100 --warmup 10 --latency-ticks 0 --dropin-ticks 0 --no-extra --cpu-sample 1024"
 for round in 1 2; do
   for V in base "$1"; do
     if [ "$V" = base ]; then unset LTPL_HIP_LIB; T="fp64 operands (default)"; else export LTPL_HIP_LIB=$PWD/$V; T="fp32 operands ($V)"; fi
