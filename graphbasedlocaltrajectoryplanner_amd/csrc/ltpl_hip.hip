@@ -2553,6 +2553,8 @@ struct ltpl_handle {
     int plan_class = 0;              // LDS plan of the one-wave batch kernel: 0 = runtime (PlanRt), 1 = PlanA, 2 = PlanB, 3 = PlanC
     int plan_class4 = 0;             // LDS plan of the four-wave kernels: 0 = runtime, 1 = PlanA4
     int long_horizon = 0;            // 1: parent tables in global memory (PlanRtG), velocity stage always through the lane kernels
+    int fused_fits = 1;              // 0: the fused tick's LDS footprint (fused_tick_lds) is above the budget, or long_horizon: every tick runs the
+                                     // pipeline (single ticks included: its path kernel then takes the four-wave team)
     int nw1_min_scen = PIPELINE_MIN_SCEN;   // calls with at least this many scenarios use one-wave teams
     // ltpl_tick_batch & co: calls with at least this many scenarios run the batch PIPELINE (one wave per scenario + the three velocity kernels),
     // smaller ones the FUSED tick kernel (one four-wave workgroup per scenario, one launch). Rounds 1-5: 64. Round 6, measured on the MI355X
@@ -2797,6 +2799,15 @@ static int upload(ltpl_handle* h, const T* src, size_t n, const T** dst)
 }
 
 static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// LDS of one workgroup of the fused tick kernel (k_tick, k_tick_persistent): the four-wave path plan, then the velocity scratch of the three
+// primitives (cap = max_path_pts rows each) and a byte row. ltpl_create routes every tick of a lattice whose footprint is above the budget
+// to the pipeline; tick_prepare launches the fused kernel with exactly this much.
+static const size_t FUSED_TICK_LDS_BUDGET = 150 * 1024;
+static size_t fused_tick_lds(int lp4_total, int cap)
+{
+    return (size_t)lp4_total + vel_scratch_bytes(cap, false, true) * LTPL_MAX_ACTIONS + align_up((size_t)cap + 16, 16);
+}
 
 // planning-range statistics over all start layers (sizes the LDS plan and the output capacities)
 static int horizon_stats(const ltpl_lattice_desc* d, int* hmax, int* ehmax, int* nhmax, int* ptsmax, int* kmax,
@@ -3142,6 +3153,9 @@ try {
         else if (kmax <= PlanB::c_kpad && hmax + 1 <= PlanB::c_hmax && d->num_layers >= PlanB::c_hmax) { h->plan_class = 2; make_fixed_plan(PlanB(), &h->lp1); }
         else if (kmax <= PlanC::c_kpad && hmax + 1 <= PlanC::c_hmax && d->num_layers >= PlanC::c_hmax) { h->plan_class = 3; make_fixed_plan(PlanC(), &h->lp1); }
     }
+    // between the two limits (the plan fits, plan + velocity scratch does not: C5 at 0.5 m spacing with a 120 .. 190 m horizon) the fused
+    // tick cannot run: the pipeline serves every batch size there, as it does in the long-horizon mode
+    h->fused_fits = (!h->long_horizon && fused_tick_lds(h->lp4.total, (int)align_up((size_t)ptsmax, 16)) <= FUSED_TICK_LDS_BUDGET) ? 1 : 0;
     if (const char* e = getenv("LTPL_BATCH_NW")) h->batch_nw = atoi(e) == 4 ? 4 : 1;
     h->zc_out = 1;
     if (const char* e = getenv("LTPL_ZC_OUT")) h->zc_out = atoi(e);
@@ -3154,7 +3168,7 @@ try {
     {
         const char* e = getenv("LTPL_PERSISTENT_TICK");
         const bool want = (flags & LTPL_CREATE_PERSISTENT_TICK) != 0u || (e && atoi(e) != 0);
-        h->pt.enabled = (want && h->plan_class4 == 1 && !h->long_horizon && h->zc_out) ? 1 : 0;
+        h->pt.enabled = (want && h->plan_class4 == 1 && h->fused_fits && h->zc_out) ? 1 : 0;
         if (const char* m = getenv("LTPL_PERSIST_IDLE_MS")) { const double v = atof(m); if (v > 0.0) h->pt.idle_ms = v; }
     }
     if (h->poll || h->pt.enabled) {
@@ -3209,9 +3223,10 @@ try {
     h->caps.device = device; h->caps.num_cus = prop.multiProcessorCount; h->caps.lds_bytes_paths = h->lp1.total;
     {
         // fused tick vs pipeline (see pipeline_min_scen): workgroups of the fused kernel that fit one compute unit by LDS (its footprint is
-        // the four-wave path plan + the velocity scratch of three primitives), at most two counted
-        const size_t lds_tick = (size_t)h->lp4.total + vel_scratch_bytes(h->caps.max_path_pts, false, true) * LTPL_MAX_ACTIONS + (size_t)h->caps.max_path_pts + 32;
-        const int per_cu = lds_tick > 0 && 160 * 1024 / lds_tick >= 2 ? 2 : 1;
+        // fused_tick_lds), at most two counted, against the 160 KiB of LDS of one compute unit. (Lattices whose footprint is above the budget
+        // never run the fused tick: fused_fits.)
+        const size_t lds_tick = fused_tick_lds(h->lp4.total, h->caps.max_path_pts);
+        const int per_cu = 160 * 1024 / lds_tick >= 2 ? 2 : 1;
         h->pipeline_min_scen = (prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256) * per_cu + 1;
         if (h->pipeline_min_scen < PIPELINE_MIN_SCEN) h->pipeline_min_scen = PIPELINE_MIN_SCEN;
         if (const char* e = getenv("LTPL_PIPELINE_MIN_SCEN")) { if (atoi(e) > 0) h->pipeline_min_scen = atoi(e); }
@@ -3801,7 +3816,7 @@ static int tick_prepare(ltpl_handle* h, const ltpl_paths_in* in, const ltpl_tick
     t->ax = b.add(sizeof(double) * (size_t)n * LTPL_MAX_ACTIONS * (size_t)cap_pts);
     t->vel_bound = b.add(sizeof(int) * (size_t)n * LTPL_MAX_ACTIONS);
     t->too_close = b.add(sizeof(int) * (size_t)n * LTPL_MAX_ACTIONS);
-    t->pipeline = h->long_horizon || (n >= h->pipeline_min_scen && !h->force_fused);
+    t->pipeline = h->long_horizon || (!h->force_fused && (!h->fused_fits || n >= h->pipeline_min_scen));
     t->prep_odist = b.add(sizeof(double) * (size_t)n * LTPL_MAX_ACTIONS);
     t->prep_vobj = b.add(sizeof(double) * (size_t)n * LTPL_MAX_ACTIONS);
     t->prep_ox = b.add(sizeof(double) * (size_t)n * LTPL_MAX_ACTIONS);
@@ -3821,8 +3836,8 @@ static int tick_prepare(ltpl_handle* h, const ltpl_paths_in* in, const ltpl_tick
     t->vel_cap = h->caps.max_path_pts;
     t->vel_stride = (int)vel_scratch_bytes(t->vel_cap, false, true);
     t->vel_off = h->lp4.total;
-    t->lds = (size_t)h->lp4.total + (size_t)t->vel_stride * LTPL_MAX_ACTIONS + align_up((size_t)t->vel_cap + 16, 16);
-    if (!t->pipeline && t->lds > 150 * 1024) { h->err = "fused tick exceeds the LDS budget"; return LTPL_ERR_CAPACITY; }
+    t->lds = fused_tick_lds(h->lp4.total, t->vel_cap);
+    if (!t->pipeline && t->lds > FUSED_TICK_LDS_BUDGET) { h->err = "fused tick exceeds the LDS budget"; return LTPL_ERR_CAPACITY; }   // (LTPL_FORCE_FUSED)
     return LTPL_OK;
 }
 
@@ -3954,7 +3969,7 @@ static void tick_scatter(const unsigned char* hb, const TickLayout& t, ltpl_path
 
 static int tick_set_lds_limit(ltpl_handle* h, size_t lds, int variant)
 {
-    if (h->long_horizon) return LTPL_OK;                  // the fused kernel is not used
+    if (!h->fused_fits) return LTPL_OK;                   // the fused kernel is not used
     static std::atomic<size_t> g_set[16][8][2];           // (process-wide limit: raised on demand, never lowered, not re-set per tick)
     std::atomic<size_t>& cur = g_set[h->device & 15][variant & 7][h->plan_class4 == 1 ? 1 : 0];
     if (lds > 48 * 1024 && lds > cur.load(std::memory_order_relaxed)) {

@@ -24,7 +24,9 @@
  *   LTPL_NO_SCEN_ORDER=1        batches of >= 2048 scenarios planned in the caller's order instead of sorted by start layer (identical results)
  *   LTPL_FOLLOW_EMIT_MIN_SCEN=<n>  smallest pipeline batch whose follow jobs are finished by the lane kernel instead of k_vel_final (8192)
  *   LTPL_PIPELINE_MIN_SCEN=<n>  smallest tick batch that runs the one-wave pipeline instead of the fused tick kernel (default: more than two
- *                               fused workgroups per compute unit -- 513 on the MI355X; rounds 1-5: 64)
+ *                               fused workgroups per compute unit -- 513 on the MI355X, 257 where only one fits; rounds 1-5: 64). Lattices
+ *                               whose fused tick (four-wave plan + velocity scratch) needs more than 150 KiB of LDS run the pipeline at
+ *                               every batch size, single ticks included: the long-horizon mode and e.g. C5 with a 120 .. 190 m horizon
  *   LTPL_FINAL_Y=<n>            row-chunk blocks per tile of the final velocity kernel (8)
  *   LTPL_ZC_OUT=0 / LTPL_ZC_IN=1   zero-copy outputs (default on) / inputs (default off) of calls with <= 8 scenarios
  *   LTPL_POLL=1 (+ LTPL_POLL_SYNC_EVERY, LTPL_POLL_QUERY)   completion of small calls through a polled word instead of a stream sync
