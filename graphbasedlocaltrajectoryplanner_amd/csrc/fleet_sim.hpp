@@ -5,6 +5,10 @@
 //   k_fleet_sim_step     one wave64 per planner: clock, action choice, opponents (one lane each), ingestion (one lane per object, ballot
 //                        compaction inside the planner's range), ego tracker (trajectory staged in LDS, two-nearest search across the wave,
 //                        the 1 ms loop on lane 0)
+//                        and its heading (psi of the two rows around the same s, read in place, interpolated across the +-pi wrap)
+//   k_fleet_sim_mates    (races with more than one planner only: ltpl_fleet_sim_race) one wave64 per planner, one lane per mate: every
+//                        other planner of the race, at the pose / speed / heading its tracker wrote above, through the same ingestion,
+//                        appended behind the planner's opponents and statics. Its own launch: every tracker of the tick is done first
 //   k_fleet_sim_offsets  exclusive scan of the on-track counts -> veh_off (one workgroup)
 //   k_fleet_sim_compact  survivors into the fleet's object layout (one lane per planner)
 //   then paths_pre | path kernel | paths_post (+ vel_a) | velocity stages as in ltpl_fleet_tape_run. Tick k + 1's inputs depend on tick k's
@@ -49,6 +53,24 @@ __device__ __forceinline__ int sim_advance(double x, const double* xp, int n, in
     return j;
 }
 
+// heading at s on segment j of the trimmed trajectory (`psi(i)`: column psi of row i): np.interp's clamping, the step taken the short way
+// round the circle, the result wrapped into (-pi, pi]. The operation order is the one of sim.peer_heading.
+template <class PSI>
+__device__ __forceinline__ double sim_heading(double s, const double* ts, int n, int j, PSI psi)
+{
+    if (j < 0) return psi(0);
+    if (j >= n - 1) return psi(n - 1);
+    if (ts[j + 1] == ts[j]) return psi(j);
+    const double p0 = psi(j);
+    double d = psi(j + 1) - p0;
+    if (d > kPi) d -= 2 * kPi;
+    else if (d < -kPi) d += 2 * kPi;
+    double th = p0 + d * ((s - ts[j]) / (ts[j + 1] - ts[j]));
+    if (th > kPi) th -= 2 * kPi;
+    else if (th <= -kPi) th += 2 * kPi;
+    return th;
+}
+
 }  // namespace fleet
 
 #define SIM_OBJ_CAP MAX_VEH                // objects (opponents + static) per planner
@@ -61,8 +83,12 @@ struct SimDev {
     const int* pref_off; const int* pref;
     double dt; int n_export;
     double* now; int* sel; int* started; double* pos_x; double* pos_y; double* vel;
+    double* theta;                         // [N] heading of the tracked pose (heading0 of ltpl_fleet_sim_race until the first trajectory)
+    int* live;                             // [N] 1: the planner ran this tick's step (no error word): it takes its mates in
     int* cnt;                              // [N] on-track objects of the tick
-    double* g_x; double* g_y; double* g_px; double* g_py; double* g_r; double* g_v;   // survivors, planner p's from opp_off[p] + st_off[p] on
+    const int* obj_base;                   // [N] first staging slot of planner p: opponents, statics and mates of the planners before p
+    double* g_x; double* g_y; double* g_px; double* g_py; double* g_r; double* g_v;   // survivors, planner p's from obj_base[p] on
+    const int* mate_lo; const int* mate_hi; const double* mate_len;   // [N] race of planner p: planners mate_lo .. mate_hi - 1; length
     int* prev_action; double* t_now; int* veh_off; double* o_r; double* o_v; double* o_px; double* o_py;   // the tick's fleet::FObj arrays
 };
 
@@ -84,7 +110,7 @@ __global__ __launch_bounds__(64) void k_fleet_sim_step(FleetArgs F, DevLat lat, 
     __shared__ double ox[SIM_OBJ_CAP], oy[SIM_OBJ_CAP], oth[SIM_OBJ_CAP], ov[SIM_OBJ_CAP], ol[SIM_OBJ_CAP];
     __shared__ double first_xy[2];
     fleet_load(x, B, &S);
-    double now = sd.now[p], pos_x = sd.pos_x[p], pos_y = sd.pos_y[p], vel = sd.vel[p];
+    double now = sd.now[p], pos_x = sd.pos_x[p], pos_y = sd.pos_y[p], vel = sd.vel[p], theta = sd.theta[p];
     int sel = sd.sel[p], cnt = 0;
     bool failed = false;
     if (lane == 0) { first_xy[0] = NAN; first_xy[1] = NAN; }
@@ -135,7 +161,7 @@ __global__ __launch_bounds__(64) void k_fleet_sim_step(FleetArgs F, DevLat lat, 
             }
             __syncthreads();
             // ingestion: survivors in list order (ballot + prefix count), staged from the planner's first object slot on
-            const int base = o0 + s0, nobj = no + ns;
+            const int base = sd.obj_base[p], nobj = no + ns;
             for (int b0 = 0; b0 < nobj; b0 += 64) {
                 const int k = b0 + lane;
                 ObjIngest r{0, 0.0, 0.0, 0.0};
@@ -184,6 +210,7 @@ __global__ __launch_bounds__(64) void k_fleet_sim_step(FleetArgs F, DevLat lat, 
                         pos_x = fleet::sim_interp(s, ts, n, j, [&](int i) { return tx[i]; });
                         pos_y = fleet::sim_interp(s, ts, n, j, [&](int i) { return ty[i]; });
                         vel = fleet::sim_interp(s, ts, n, j, vx);
+                        theta = fleet::sim_heading(s, ts, n, j, [&](int i) { return tr.at(i, 3); });   // (two rows: read in place)
                     }
                 }
             }
@@ -193,7 +220,9 @@ __global__ __launch_bounds__(64) void k_fleet_sim_step(FleetArgs F, DevLat lat, 
     if (lane == 0) {
         if (!failed && !S.err) {
             sd.now[p] = now; sd.sel[p] = sel; sd.started[p] = 1; sd.pos_x[p] = pos_x; sd.pos_y[p] = pos_y; sd.vel[p] = vel;
+            sd.theta[p] = theta;
         }
+        sd.live[p] = !failed && !S.err;
         sd.cnt[p] = cnt; sd.prev_action[p] = sd.sel[p]; sd.t_now[p] = sd.now[p];
         if (trace) {
             double* o = trace + (size_t)p * LTPL_FLEET_SIM_TRACE_DOUBLES;
@@ -201,6 +230,42 @@ __global__ __launch_bounds__(64) void k_fleet_sim_step(FleetArgs F, DevLat lat, 
         }
     }
     if (failed) fleet_store(x, B, &S, p, F.err_word);
+}
+
+// the planner's mates (every other planner of its race, ascending) as objects at their tracked pose, speed and heading: the ingestion of
+// k_fleet_sim_step, appended behind the opponents and statics that step kept. A failed planner takes no objects; a failed mate stays at
+// its last state. Trace fields [5] .. [7] of step are completed here.
+__global__ __launch_bounds__(64) void k_fleet_sim_mates(DevLat lat, SimDev sd, double* trace /* this tick's records or null */)
+{
+    const int p = blockIdx.x, lane = threadIdx.x;
+    const int lo = sd.mate_lo[p], hi = sd.mate_hi[p];
+    if (hi - lo < 2 || !sd.live[p]) return;
+    const int base = sd.obj_base[p], c0 = sd.cnt[p];
+    double* o = trace ? trace + (size_t)p * LTPL_FLEET_SIM_TRACE_DOUBLES : nullptr;
+    int cnt = c0;
+    for (int b0 = lo; b0 < hi; b0 += 64) {
+        const int q = b0 + lane;
+        const bool mate = q < hi && q != p;
+        ObjIngest r{0, 0.0, 0.0, 0.0};
+        double qx = 0.0, qy = 0.0, qv = 0.0;
+        if (mate) {
+            qx = sd.pos_x[q]; qy = sd.pos_y[q]; qv = sd.vel[q];
+            r = process_object_dev(lat, 0.2, qx, qy, sd.theta[q], qv, sd.mate_len[q]);     // ObjectListInterface.py:121
+        }
+        const bool keep = mate && r.on_track;
+        const unsigned long long m = __ballot(keep);
+        const int idx = cnt + __popcll(m & ((1ull << lane) - 1ull));
+        if (keep) {
+            sd.g_x[base + idx] = qx; sd.g_y[base + idx] = qy; sd.g_px[base + idx] = r.pred_x; sd.g_py[base + idx] = r.pred_y;
+            sd.g_r[base + idx] = r.radius; sd.g_v[base + idx] = qv;
+            if (idx == 0 && o) { o[6] = qx; o[7] = qy; }
+        }
+        cnt += __popcll(m);
+    }
+    if (lane == 0 && cnt != c0) {
+        sd.cnt[p] = cnt;
+        if (o) o[5] = (double)cnt;
+    }
 }
 
 // exclusive scan of the on-track counts (one workgroup; a few hundred thousand planners at most)
@@ -229,7 +294,7 @@ __global__ __launch_bounds__(64) void k_fleet_sim_compact(SimDev sd, int n)
 {
     const int p = blockIdx.x * 64 + threadIdx.x;
     if (p >= n) return;
-    const int base = sd.opp_off[p] + sd.st_off[p], o = sd.veh_off[p], c = sd.cnt[p];
+    const int base = sd.obj_base[p], o = sd.veh_off[p], c = sd.cnt[p];
     for (int i = 0; i < c; ++i) {
         const int v = o + i, g = base + i;
         sd.o_r[v] = sd.g_r[g]; sd.o_v[v] = sd.g_v[g];
@@ -242,30 +307,85 @@ __global__ __launch_bounds__(64) void k_fleet_sim_compact(SimDev sd, int n)
 // ---------------------------------------------------------------------------------------------------------------------
 struct FleetSim {
     std::vector<void*> allocs;
+    std::vector<void*> stage_allocs;        // staging slots, the tick's object arrays and obj_base: sized again by ltpl_fleet_sim_race
+    std::vector<void*> race_allocs;         // mate_lo / mate_hi / mate_len of ltpl_fleet_sim_race
     SimDev sd{};
     fleet::FObj ob{}; const int* zone_off = nullptr; const int* zone_gid = nullptr;
     FleetTickIn velt;                       // velocity arguments of ltpl_fleet_sim_vel (its own arena)
     bool has_vel = false;
+    bool has_mates = false;                 // some race holds more than one planner: k_fleet_sim_mates runs every tick
+    bool ran = false;                       // ltpl_fleet_sim_run was called (ltpl_fleet_sim_race comes before it)
     int n_opp = 0, n_obj = 0;
+    std::vector<int> own;                   // [N] opponents + statics of planner p
+};
+static void sim_free_list(std::vector<void*>& l)
+{
+    for (void* p : l) (void)hipFree(p);
+    l.clear();
+}
+// device buffers of a call that become the fleet's only when the whole call succeeded: freed on every early return
+struct SimAllocs {
+    std::vector<void*> p;
+    ~SimAllocs() { sim_free_list(p); }
 };
 static void fleet_sim_free(FleetSim* s)
 {
     if (!s) return;
+    sim_free_list(s->stage_allocs); sim_free_list(s->race_allocs);
     for (void* p : s->allocs) (void)hipFree(p);
     if (s->velt.d_buf) (void)hipFree(s->velt.d_buf);
     delete s;
 }
 
 template <class T>
-static int sim_upload(ltpl_fleet* f, FleetSim* s, const T* src, size_t n, T** out)
+static int sim_upload(ltpl_fleet* f, std::vector<void*>& allocs, const T* src, size_t n, T** out)
 {
     void* p = nullptr;
     FLEET_TRY(f, hipMalloc(&p, (n ? n : 1) * sizeof(T)));
-    s->allocs.push_back(p);
+    allocs.push_back(p);
     if (src && n) FLEET_TRY(f, hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice));
     else FLEET_TRY(f, hipMemset(p, 0, (n ? n : 1) * sizeof(T)));
     *out = static_cast<T*>(p);
     return LTPL_OK;
+}
+template <class T>
+static int sim_upload(ltpl_fleet* f, FleetSim* s, const T* src, size_t n, T** out) { return sim_upload(f, s->allocs, src, n, out); }
+
+// staging slots of every planner from obj_base[p] on (slots[p] of them) and the tick's object arrays of the fleet (pos_off[v] = 2 v):
+// allocated by sim_stage_alloc into a list of their own, which sim_stage_commit hands to the fleet (freeing the previous staging)
+struct SimStage {
+    SimAllocs a;
+    int* obj_base = nullptr; int* pos_off = nullptr;
+    double* g[6] = {};                      // g_x, g_y, g_px, g_py, g_r, g_v
+    double* o[4] = {};                      // o_r, o_v, o_px, o_py
+};
+static int sim_stage_alloc(ltpl_fleet* f, const std::vector<int>& slots, SimStage* st)
+{
+    const int N = f->D.N;
+    std::vector<int> base((size_t)N);
+    int total = 0;
+    for (int p = 0; p < N; ++p) { base[(size_t)p] = total; total += slots[(size_t)p]; }
+    std::vector<int> pos_off((size_t)total + 1);
+    for (int v = 0; v <= total; ++v) pos_off[(size_t)v] = 2 * v;
+    int rc;
+    const double* z = nullptr;
+#define SIM_UP(dst, src, n) do { if ((rc = sim_upload(f, st->a.p, src, (size_t)(n), &dst))) return rc; } while (0)
+    SIM_UP(st->obj_base, base.data(), N);
+    for (double*& g : st->g) SIM_UP(g, z, total);
+    SIM_UP(st->pos_off, pos_off.data(), total + 1);
+    SIM_UP(st->o[0], z, total); SIM_UP(st->o[1], z, total); SIM_UP(st->o[2], z, 2 * total); SIM_UP(st->o[3], z, 2 * total);
+#undef SIM_UP
+    return LTPL_OK;
+}
+static void sim_stage_commit(FleetSim* s, SimStage* st)
+{
+    sim_free_list(s->stage_allocs);
+    s->stage_allocs.swap(st->a.p);
+    SimDev& d = s->sd;
+    d.obj_base = st->obj_base;
+    d.g_x = st->g[0]; d.g_y = st->g[1]; d.g_px = st->g[2]; d.g_py = st->g[3]; d.g_r = st->g[4]; d.g_v = st->g[5];
+    d.o_r = st->o[0]; d.o_v = st->o[1]; d.o_px = st->o[2]; d.o_py = st->o[3];
+    s->ob = fleet::FObj{d.prev_action, d.t_now, d.veh_off, st->pos_off, d.o_r, d.o_v, d.o_px, d.o_py};
 }
 
 static int sim_check_csr(ltpl_fleet* f, const int32_t* off, int N, const char* what, int* total)
@@ -330,9 +450,9 @@ try {
     }
     const std::vector<double> tic(n_opp, in->tic0), now(N, in->t0);
     const std::vector<int> sel(N, LTPL_ACT_NONE);
-    std::vector<int> pos_off((size_t)n_obj + 1);
-    for (int v = 0; v <= n_obj; ++v) pos_off[(size_t)v] = 2 * v;
-    int* pi = nullptr; double* pd = nullptr; int* po = nullptr;
+    s->own.resize((size_t)N);
+    for (int p = 0; p < N; ++p) s->own[(size_t)p] = (in->opp_off[p + 1] - in->opp_off[p]) + (in->static_off[p + 1] - in->static_off[p]);
+    int* pi = nullptr; double* pd = nullptr;
 #define SIM_UP(dst, src, n) do { if ((rc = sim_upload(f, s.get(), src, (size_t)(n), &dst))) return rc; } while (0)
     SIM_UP(pi, in->opp_off, N + 1); d.opp_off = pi;
     SIM_UP(d.opp_s, in->opp_s0, n_opp); SIM_UP(d.opp_tic, tic.data(), n_opp);
@@ -343,17 +463,17 @@ try {
     SIM_UP(pi, in->pref_off, N + 1); d.pref_off = pi; SIM_UP(pi, in->pref_action, n_pref); d.pref = pi;
     SIM_UP(d.now, now.data(), N); SIM_UP(d.sel, sel.data(), N); SIM_UP(d.started, (const int*)nullptr, N);
     SIM_UP(d.pos_x, in->pos_est_x, N); SIM_UP(d.pos_y, in->pos_est_y, N); SIM_UP(d.vel, in->vel_est, N);
+    SIM_UP(d.theta, (const double*)nullptr, N); SIM_UP(d.live, (const int*)nullptr, N);
     SIM_UP(d.cnt, (const int*)nullptr, N);
-    SIM_UP(d.g_x, (const double*)nullptr, n_obj); SIM_UP(d.g_y, (const double*)nullptr, n_obj); SIM_UP(d.g_px, (const double*)nullptr, n_obj);
-    SIM_UP(d.g_py, (const double*)nullptr, n_obj); SIM_UP(d.g_r, (const double*)nullptr, n_obj); SIM_UP(d.g_v, (const double*)nullptr, n_obj);
     SIM_UP(d.prev_action, sel.data(), N); SIM_UP(d.t_now, now.data(), N); SIM_UP(d.veh_off, (const int*)nullptr, N + 1);
-    SIM_UP(po, pos_off.data(), n_obj + 1);
-    SIM_UP(d.o_r, (const double*)nullptr, n_obj); SIM_UP(d.o_v, (const double*)nullptr, n_obj);
-    SIM_UP(d.o_px, (const double*)nullptr, 2 * n_obj); SIM_UP(d.o_py, (const double*)nullptr, 2 * n_obj);
     int* zo = nullptr; int* zg = nullptr;
     SIM_UP(zo, in->zone_off, N + 1); SIM_UP(zg, in->zone_gid, n_zone);
 #undef SIM_UP
-    s->ob = fleet::FObj{d.prev_action, d.t_now, d.veh_off, po, d.o_r, d.o_v, d.o_px, d.o_py};
+    {
+        SimStage st;
+        if ((rc = sim_stage_alloc(f, s->own, &st))) return rc;
+        sim_stage_commit(s.get(), &st);
+    }
     s->zone_off = zo; s->zone_gid = zg;
     f->sim = s.release();
     return LTPL_OK;
@@ -398,12 +518,17 @@ try {
     t.vin.pos_x = s.sd.pos_x; t.vin.pos_y = s.sd.pos_y; t.vin.vel_est = s.sd.vel;
     t.has_paths = true;
     hipStream_t st = f->h->stream;
+    s.ran = true;
     FLEET_TRY(f, hipStreamSynchronize(st));
     FLEET_TRY(f, hipEventRecord(e0, st));
     for (int k = 0; k < n_ticks; ++k) {
         double* tr = d_trace ? d_trace + rec * (size_t)k : nullptr;
         hipLaunchKernelGGL(k_fleet_sim_step, dim3(N), dim3(64), 0, st, f->args, f->h->lat, s.sd, tr);
         FLEET_TRY(f, hipGetLastError());
+        if (s.has_mates) {
+            hipLaunchKernelGGL(k_fleet_sim_mates, dim3(N), dim3(64), 0, st, f->h->lat, s.sd, tr);
+            FLEET_TRY(f, hipGetLastError());
+        }
         hipLaunchKernelGGL(k_fleet_sim_offsets, dim3(1), dim3(1024), 0, st, (const int*)s.sd.cnt, N, s.sd.veh_off);
         FLEET_TRY(f, hipGetLastError());
         hipLaunchKernelGGL(k_fleet_sim_compact, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, st, s.sd, N);
@@ -445,5 +570,72 @@ try {
     if (now) FLEET_TRY(f, hipMemcpy(now, d.now, 8 * n, hipMemcpyDeviceToHost));
     if (opp_s && no) FLEET_TRY(f, hipMemcpy(opp_s, d.opp_s, 8 * no, hipMemcpyDeviceToHost));
     if (opp_tic && no) FLEET_TRY(f, hipMemcpy(opp_tic, d.opp_tic, 8 * no, hipMemcpyDeviceToHost));
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+// every argument is checked before the first HIP call
+static int sim_check_race(ltpl_fleet* f, const ltpl_fleet_sim_race_in* in)
+{
+    const int N = f->D.N;
+    auto bad = [&](const char* why, int code = LTPL_ERR_INVALID_ARG) { f->err = std::string("fleet sim race: ") + why; return code; };
+    if (!f->sim) return bad("ltpl_fleet_sim_setup first");
+    if (f->sim->ran) return bad("races are set before the first ltpl_fleet_sim_run (ltpl_fleet_sim_setup starts over)");
+    if (in->n_races < 1 || !in->race_off) return bad("race offsets missing");
+    const int32_t* off = in->race_off;
+    if (off[0] != 0 || off[in->n_races] != N) return bad("race offsets must cover the planners 0 .. n");
+    for (int r = 0; r < in->n_races; ++r) if (off[r + 1] < off[r]) return bad("race offsets must not decrease");
+    if (!in->length || !in->heading0) return bad("length / heading0 missing");
+    for (int p = 0; p < N; ++p) {
+        if (!std::isfinite(in->length[p]) || !(in->length[p] > 0.0)) return bad("a length must be finite and positive");
+        if (!std::isfinite(in->heading0[p])) return bad("a heading0 must be finite");
+    }
+    for (int r = 0; r < in->n_races; ++r)
+        for (int p = off[r]; p < off[r + 1]; ++p)
+            if (f->sim->own[(size_t)p] + (off[r + 1] - off[r] - 1) > SIM_OBJ_CAP)
+                return bad("opponents + statics + mates above 96 for one planner", LTPL_ERR_CAPACITY);
+    return LTPL_OK;
+}
+
+extern "C" int ltpl_fleet_sim_race(ltpl_fleet* f, const ltpl_fleet_sim_race_in* in)
+try {
+    if (!f || !in) return LTPL_ERR_INVALID_ARG;
+    int rc = sim_check_race(f, in);
+    if (rc) return rc;
+    if ((rc = fleet_enter(f))) return rc;
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    FleetSim& s = *f->sim;
+    const int N = f->D.N;
+    std::vector<int> lo((size_t)N), hi((size_t)N), slots(s.own);
+    bool mates = false;
+    for (int r = 0; r < in->n_races; ++r)
+        for (int p = in->race_off[r]; p < in->race_off[r + 1]; ++p) {
+            lo[(size_t)p] = in->race_off[r]; hi[(size_t)p] = in->race_off[r + 1];
+            slots[(size_t)p] += in->race_off[r + 1] - in->race_off[r] - 1;
+            mates = mates || in->race_off[r + 1] - in->race_off[r] > 1;
+        }
+    // everything new is allocated first; the fleet keeps its previous races and staging (all of it valid) unless every step succeeds
+    SimStage st;
+    SimAllocs ra;
+    int* d_lo = nullptr; int* d_hi = nullptr; double* d_len = nullptr;
+    if ((rc = sim_stage_alloc(f, slots, &st))) return rc;
+    if ((rc = sim_upload(f, ra.p, lo.data(), (size_t)N, &d_lo))) return rc;
+    if ((rc = sim_upload(f, ra.p, hi.data(), (size_t)N, &d_hi))) return rc;
+    if ((rc = sim_upload(f, ra.p, in->length, (size_t)N, &d_len))) return rc;
+    FLEET_TRY(f, hipMemcpy(s.sd.theta, in->heading0, sizeof(double) * (size_t)N, hipMemcpyHostToDevice));
+    sim_stage_commit(&s, &st);
+    sim_free_list(s.race_allocs);
+    s.race_allocs.swap(ra.p);
+    s.sd.mate_lo = d_lo; s.sd.mate_hi = d_hi; s.sd.mate_len = d_len;
+    s.has_mates = mates;
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+extern "C" int ltpl_fleet_sim_heading(ltpl_fleet* f, double* theta)
+try {
+    if (!f || !theta) return LTPL_ERR_INVALID_ARG;
+    if (!f->sim) { f->err = "fleet sim: ltpl_fleet_sim_setup first"; return LTPL_ERR_INVALID_ARG; }
+    FLEET_TRY(f, hipSetDevice(f->h->device));
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    FLEET_TRY(f, hipMemcpy(theta, f->sim->sd.theta, sizeof(double) * (size_t)f->D.N, hipMemcpyDeviceToHost));
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))

@@ -27,6 +27,10 @@ class SimIn(C.Structure):                 # ltpl_fleet_sim_in (pointer members a
                 ("zone_off", C.c_void_p), ("zone_gid", C.c_void_p)]
 
 
+class SimRaceIn(C.Structure):             # ltpl_fleet_sim_race_in
+    _fields_ = [("n_races", C.c_int32), ("race_off", C.c_void_p), ("length", C.c_void_p), ("heading0", C.c_void_p)]
+
+
 SIM_TRACE_DOUBLES = 8 + 8 + 9 * _capi.PLANNER_MAX_KEYS     # LTPL_FLEET_SIM_TRACE_DOUBLES
 
 
@@ -49,12 +53,26 @@ class Fleet(Planner):
             f("sim_vel").argtypes = [C.c_void_p, C.POINTER(PlannerVelIn)]
             f("sim_run").argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_float)]
             f("sim_state").argtypes = [C.c_void_p] + [C.c_void_p] * 7
+        if hasattr(self.lib, "ltpl_fleet_sim_race"):
+            f("sim_race").argtypes = [C.c_void_p, C.POINTER(SimRaceIn)]
+            f("sim_heading").argtypes = [C.c_void_p, C.c_void_p]
+
+    def set_start(self, scen, pos, heading, vel=0.0, max_heading_offset=math.pi / 4):
+        out = Planner.set_start(self, scen, pos, heading, vel, max_heading_offset)
+        self._start_heading()[int(scen)] = float(heading)
+        return out
+
+    def _start_heading(self):
+        if getattr(self, "_heading", None) is None:
+            self._heading = np.zeros(self.n_scen, np.float64)
+        return self._heading
 
     def set_start_range(self, first, past_last, pos, heading, vel=0.0, max_heading_offset=math.pi / 4):
         """``set_start`` with the same pose for the planners [first, past_last) in one call (ltpl_fleet_set_start_range)."""
         it, ch = C.c_int32(1), C.c_int32(1)
         self._check(self._fn("set_start_range")(self.handle, int(first), int(past_last), float(pos[0]), float(pos[1]), float(heading),
                                                 float(vel), float(max_heading_offset), C.byref(it), C.byref(ch)))
+        self._start_heading()[int(first):int(past_last)] = float(heading)
         return bool(it.value), bool(ch.value)
 
     # ---- tape ---------------------------------------------------------------------------------------------------------------
@@ -294,6 +312,34 @@ class Fleet(Planner):
         self.last_trace, self.last_ms = out, float(ms.value)
         self._check(rc)
         return out, float(ms.value)
+
+    def sim_race(self, races, length=5.0, heading0=None):
+        """Planners that see one another (ltpl_fleet_sim_race; after ``sim_setup``, refused after the first ``sim_run``). ``races``: sizes
+        summing to the number of planners, or ranges of consecutive planners covering them all in order. Every other planner of a race
+        is an object of a planner's list, behind its opponents and statics: the pose, speed and heading its tracker wrote this tick, with
+        ``length`` (scalar or one per planner). ``heading0`` (scalar or one per planner; default: the heading given to ``set_start``) is a
+        planner's heading until its first trajectory."""
+        n = self.n_scen
+        races = list(races)
+        if races and all(isinstance(r, range) for r in races):
+            if [q for r in races for q in r] != list(range(n)) or any(r.step != 1 for r in races):
+                raise ValueError("sim_race: the ranges must cover the planners 0 .. n - 1 in order")
+            sizes = [len(r) for r in races]
+        else:
+            sizes = [int(r) for r in races]
+        off = np.ascontiguousarray(np.concatenate(([0], np.cumsum(sizes))).astype(np.int32))
+        lens = np.ascontiguousarray(np.broadcast_to(np.asarray(length, np.float64), (n,)))
+        h0 = self._start_heading() if heading0 is None else np.broadcast_to(np.asarray(heading0, np.float64), (n,))
+        h0 = np.ascontiguousarray(h0, np.float64)
+        ri = SimRaceIn()
+        ri.n_races, ri.race_off, ri.length, ri.heading0 = len(sizes), off.ctypes.data, lens.ctypes.data, h0.ctypes.data
+        self._check(self._fn("sim_race")(self.handle, C.byref(ri)))
+
+    def sim_heading(self):
+        """[n] heading of every planner's tracked pose (``sim_race``'s heading0 until its first trajectory)."""
+        out = np.zeros(self.n_scen, np.float64)
+        self._check(self._fn("sim_heading")(self.handle, out.ctypes.data))
+        return out
 
     def sim_state(self):
         """Simulation state: dict of pos_est [n, 2], vel_est, sel_action (ids), now, opponent s / tic (all opponents in planner order)."""

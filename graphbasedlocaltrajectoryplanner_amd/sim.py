@@ -9,6 +9,12 @@ driver runs around the planner on every tick --
   ``vdc_step``       one ``vdc_dummy`` call (graph_ltpl/testing_tools/src/vdc_dummy.py:5-58): the ideal tracker that moves the ego
                      along its last trajectory for one tick.
 
+and of the races of ``ltpl_fleet_sim_race`` (planners of one fleet that see one another) --
+
+  ``vdc_track``      ``vdc_step`` that also returns the final arc length and segment of the tracker;
+  ``peer_heading``   the heading of the tracked pose: psi of the same trajectory at that arc length and segment, across the +-pi wrap;
+  ``race_objects``   the object dicts the mates of one planner contribute to its object list.
+
 Both restate ``np.interp`` (numpy's ``arr_interp``) in the operation order of the device functions (``interp_at`` here,
 ``fleet::sim_interp`` there), so that host and device give the same bits as the reference.
 """
@@ -112,11 +118,18 @@ def vdc_step(pos_est, traj, iter_time):
     """One ``vdc_dummy`` call: ``traj`` = the exported trajectory (rows [s, x, y, psi, kappa, vx, ax], already trimmed to the exported
     rows). Returns (pos_out [x, y], vel_est). Exact ties of the two-nearest search take the lower index (numpy leaves their order
     open)."""
+    pos, vel, _, _ = vdc_track(pos_est, traj, iter_time)
+    return pos, vel
+
+
+def vdc_track(pos_est, traj, iter_time):
+    """``vdc_step`` returning (pos_out [x, y], vel_est, s, j): the tracker's final arc length and its segment (``segment``), both None
+    where the pose stays (at most 2 rows)."""
     traj = np.asarray(traj, dtype=float)
     sc, px, py, vx = (traj[:, c].tolist() for c in (0, 1, 2, 5))
     n = len(sc)
     if n <= 2:
-        return [float(pos_est[0]), float(pos_est[1])], float(vx[0])
+        return [float(pos_est[0]), float(pos_est[1])], float(vx[0]), None, None
     ex, ey = float(pos_est[0]), float(pos_est[1])
     d2 = [(px[i] - ex) * (px[i] - ex) + (py[i] - ey) * (py[i] - ey) for i in range(n)]
     i1 = min(range(n), key=lambda i: (d2[i], i))
@@ -128,4 +141,36 @@ def vdc_step(pos_est, traj, iter_time):
         s += max(interp(s, sc, vx) * OPP_DT, VDC_MIN_STEP)
         t += OPP_DT
     j = segment(s, sc)
-    return [interp_at(s, sc, px, j), interp_at(s, sc, py, j)], interp_at(s, sc, vx, j)
+    return [interp_at(s, sc, px, j), interp_at(s, sc, py, j)], interp_at(s, sc, vx, j), s, j
+
+
+def peer_heading(s, j, ts, psi):
+    """Heading at arc length ``s`` on segment ``j`` of a trajectory (``ts``: its s column, ``psi``: its heading column; ``vdc_track``'s
+    s and j): clamped like np.interp, the step between two rows taken the short way round the circle, the result wrapped into
+    (-pi, pi]. The operation order of the device (fleet::sim_heading)."""
+    n = len(ts)
+    if j < 0:
+        return float(psi[0])
+    if j >= n - 1:
+        return float(psi[n - 1])
+    if ts[j + 1] == ts[j]:
+        return float(psi[j])
+    d = float(psi[j + 1]) - float(psi[j])
+    if d > math.pi:
+        d -= 2 * math.pi
+    elif d < -math.pi:
+        d += 2 * math.pi
+    theta = float(psi[j]) + d * ((s - float(ts[j])) / (float(ts[j + 1]) - float(ts[j])))
+    if theta > math.pi:
+        theta -= 2 * math.pi
+    elif theta <= -math.pi:
+        theta += 2 * math.pi
+    return theta
+
+
+def race_objects(p, race, pos, vel, theta, length, id0=100):
+    """The objects planner ``p`` sees of its mates: every other planner of ``race`` (its planner indices, ascending) as a 'physical'
+    object at its tracked pose ``pos[q]`` [x, y], speed ``vel[q]``, heading ``theta[q]`` and ``length[q]`` (id ``id0 + q``), in list
+    order. They follow the planner's opponents and static objects."""
+    return [{'X': float(pos[q][0]), 'Y': float(pos[q][1]), 'theta': float(theta[q]), 'type': 'physical', 'id': id0 + int(q),
+             'length': float(length[q]), 'v': float(vel[q])} for q in sorted(race) if q != p]

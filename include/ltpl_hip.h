@@ -712,6 +712,33 @@ int ltpl_fleet_sim_run(ltpl_fleet* fleet, int32_t n_ticks, double* trace, int32_
 int ltpl_fleet_sim_state(ltpl_fleet* fleet, double* pos_est_x, double* pos_est_y, double* vel_est, int32_t* sel_action, double* now,
                          double* opp_s, double* opp_tic);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Additive to ABI v9 -- RACES: planners of one fleet that see one another. A race is a contiguous range of planners,
+ * race_off[r] .. race_off[r + 1] - 1. The tracker of step 5 above also yields a heading theta: psi (column 3) of the same trimmed
+ * trajectory at the same s and segment j as x, y and vx --
+ *     j < 0: psi[0]     j >= n - 1: psi[n - 1]     ts[j + 1] == ts[j]: psi[j]
+ *     else:  d = psi[j + 1] - psi[j]; d > pi: d -= 2 pi, d < -pi: d += 2 pi; theta = psi[j] + d * ((s - ts[j]) / (ts[j + 1] - ts[j]));
+ *            theta > pi: theta -= 2 pi, theta <= -pi: theta += 2 pi
+ * (the pose unchanged -- not started, <= 2 rows -- keeps theta; before the first trajectory theta = heading0). After EVERY planner's
+ * tracker of the tick (a kernel boundary), each mate q != p of p's race, in ascending planner order, becomes the object
+ * {X: pos_x[q], Y: pos_y[q], theta: theta[q], v: vel[q], length: length[q]} of step 4's ingestion; the survivors follow p's opponents and
+ * statics, trace field [5] counts them, [6] / [7] hold the first surviving object of the whole list. A failed planner takes no objects
+ * and stays in its mates' lists at its last pose, speed and heading. Opponents + statics + (race size - 1) <= 96 for every planner
+ * (else LTPL_ERR_CAPACITY). Races of size 1 change nothing: the same kernels run, the trace is bit-identical.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct {
+    int32_t n_races;                /* >= 1                                                                       */
+    const int32_t* race_off;        /* [n_races + 1] non-decreasing, 0 .. n                                        */
+    const double*  length;          /* [n] object length of planner p as a mate (radius = length / 2), finite > 0  */
+    const double*  heading0;        /* [n] heading before the first trajectory, finite                             */
+} ltpl_fleet_sim_race_in;
+
+/* after ltpl_fleet_sim_setup (which clears the races), before the first ltpl_fleet_sim_run (after it: LTPL_ERR_INVALID_ARG): sets the races
+ * and every planner's heading to heading0. A failing call (LTPL_ERR_HIP) leaves the previous races in place. */
+int ltpl_fleet_sim_race(ltpl_fleet* fleet, const ltpl_fleet_sim_race_in* in);
+/* [n] heading of every planner's tracked pose */
+int ltpl_fleet_sim_heading(ltpl_fleet* fleet, double* theta);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,9 @@
 """Closed-loop SIMULATION rate of a fleet (ltpl_fleet_sim_*): N planners, each with its own eight C2-style race-line opponents (SURVEY.md
 section 8d: s0_k = 250 + 280 k, vel_scale_k = 0.30 + 0.05 (k mod 4), here staggered by 10 m (p mod 16) per planner), run the example
 driver's loop on the device for T ticks without host work per tick.   tools/sim_rate.py [--planners 32768] [--ticks 200] [--no-tape]
-Prints planner-ticks per second of sim_run (device time of the run) next to tape_run on the C2 tape (recorded inputs, tools/fleet_rate.py)."""
+[--race-size K]. Prints planner-ticks per second of sim_run (device time of the run) next to tape_run on the C2 tape (recorded inputs,
+tools/fleet_rate.py). --race-size K > 1: races of K consecutive planners (ltpl_fleet_sim_race) that see one another, started 30 m apart
+along the race line with its heading; K = 1 (default) is the run without races."""
 import argparse
 import os
 import sys
@@ -24,6 +26,7 @@ def main():
     ap.add_argument("--ticks", type=int, default=200)
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--no-tape", action="store_true", help="skip the tape_run comparison on the C2 recording")
+    ap.add_argument("--race-size", type=int, default=1, help="planners per race (1: no races)")
     a = ap.parse_args()
     lat = Lattice.load(os.path.join(ROOT, "tests", "golden", "monteblanco_lattice.npz"))
     race = RaceLineTable.from_track(np.load(os.path.join(ROOT, "tests", "golden", "monteblanco_track.npz")))
@@ -34,11 +37,27 @@ def main():
     n = a.planners
     entries = [dict(opponents=[(250.0 + 280.0 * k + 10.0 * (p % 16), 0.30 + 0.05 * (k % 4), 5.0) for k in range(8)],
                     pref=("right", "left", "straight", "follow"), pos_est=st['pos'], vel_est=0.0, zone_gids=zones) for p in range(n)]
+    K = a.race_size
+    if K > 1:
+        # slot i of a race starts 30 m ahead of slot i - 1 on the race line, with the race line's heading
+        s0 = race.s_rl[int(np.argmin(np.hypot(race.x - st['pos'][0], race.y - st['pos'][1])))]
+        slots = [int(np.argmin(np.abs(race.s_rl - (s0 + 30.0 * i)))) for i in range(K)]
+        slot_pose = [((race.x[i], race.y[i]), race.psi[i] - 2 * np.pi if race.psi[i] > np.pi else race.psi[i]) for i in slots]
+        for p in range(n):
+            entries[p]['pos_est'] = slot_pose[p % K][0]
+        sizes = [K] * (n // K) + ([n % K] if n % K else [])
     best = None
     for rep in range(a.reps):
         fleet = Fleet(hip, n)
-        fleet.set_start_range(0, n, st['pos'], st['heading'], st['vel'], st['max_heading_offset'])
+        if K > 1:
+            for p in range(n):
+                pos, h = slot_pose[p % K]
+                fleet.set_start(p, pos, h, st['vel'], st['max_heading_offset'])
+        else:
+            fleet.set_start_range(0, n, st['pos'], st['heading'], st['vel'], st['max_heading_offset'])
         fleet.sim_setup(race, entries)
+        if K > 1:
+            fleet.sim_race(sizes)
         fleet.sim_vel(vel_max=va['vel_max'], gg_scale=va['gg_scale'], local_gg=tuple(va['local_gg']), safety_d=va['safety_d'],
                       ax_max_machines=va['ax_max_machines'])
         t0 = time.perf_counter()
@@ -51,8 +70,8 @@ def main():
             print("  (%d planners stopped with an error: %s)" % (failed, str(e)[:160]))
         wall = time.perf_counter() - t0
         best = ms if best is None else min(best, ms)
-        print("rep %d: sim_run %d planners x %d ticks: device %.1f ms (wall %.1f ms) = %.3f M planner-ticks/s; %.3f ms per tick of the fleet" % (
-            rep, n, a.ticks, ms, wall * 1e3, n * a.ticks / ms / 1e3, ms / a.ticks))
+        print("rep %d: sim_run %d planners (races of %d) x %d ticks: device %.1f ms (wall %.1f ms) = %.3f M planner-ticks/s; %.3f ms per tick of the fleet" % (
+            rep, n, K, a.ticks, ms, wall * 1e3, n * a.ticks / ms / 1e3, ms / a.ticks))
         if failed == 0:
             sel = np.bincount(fleet.sim_state()['sel_action'] + 1, minlength=6)
             print("  last selected actions (none, straight, follow, left, right, emergency): %s" % sel.tolist())
