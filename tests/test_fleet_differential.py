@@ -123,3 +123,60 @@ def test_long_horizon_fleet_on_the_device():
         st = drive(lat, A, B, seed, 60, exact=False, scen_b=2)
         assert st['ticks'] >= 40, st
         A.close(); B.close()
+
+
+# Exponent 2 with the PDtan controller on the one-row machine table (even seeds of the driver), exponent 1.5 on its three-row table (odd seeds):
+# the fleet's velocity kernels (vel_kernel_const_of / vel_kernel_rows_of, the lane kernels) in their forms for dyn_model_exp != 1 -- every
+# other closed loop of the suite runs at exponent 1 with the PD controller.
+OTHER_EXPONENTS = {
+    "exp2_PDtan_one_row": (4, dict(dyn_model_exp=2.0, follow_control_type="PDtan",
+                                   follow_control_params={"c_p": 1.15, "k_d": 0.025, "k_p": 0.2, "tan_w": 15.0})),
+    "exp1p5_three_rows": (1, dict(dyn_model_exp=1.5)),
+}
+
+
+@pytest.mark.parametrize("case", sorted(OTHER_EXPONENTS))
+def test_fleet_and_host_planner_agree_at_other_exponents(monteblanco, case):
+    """The host state machines over the oracle's arithmetic (exact), as a statement about the driver: the loops below stay alive and
+    reach follow mode at these parameters."""
+    from oracle.fleet_host import HostFleetBackend
+    from oracle.planner_host import HostPlannerBackend
+    seed, cfg = OTHER_EXPONENTS[case]
+    A, B = HostPlannerBackend(monteblanco).planner(1, **cfg), HostFleetBackend(monteblanco).planner(2, **cfg)
+    st = drive(monteblanco, A, B, seed, 300, exact=True, scen_b=1)
+    assert st['ticks'] >= 200 and 'follow' in st['keys'], st
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("follow_form", [None, "0"])
+@pytest.mark.parametrize("case", sorted(OTHER_EXPONENTS))
+def test_fleet_and_host_planner_agree_on_the_device_at_other_exponents(monteblanco, monkeypatch, case, follow_form):
+    """ltpl_fleet_* (70 planners) against ltpl_planner_* on the MI355X as in test_fleet_and_host_planner_agree_on_the_device, both created
+    with the other exponent / controller; follow_form "0": the lane form of the follow jobs."""
+    from graphbasedlocaltrajectoryplanner_amd import _capi
+    from graphbasedlocaltrajectoryplanner_amd.fleet import Fleet
+    from graphbasedlocaltrajectoryplanner_amd.planner import Planner
+    if follow_form is not None:
+        monkeypatch.setenv("LTPL_FLEET_FOLLOW_WAVES", follow_form)
+    seed, cfg = OTHER_EXPONENTS[case]
+    hip = _capi.HipBackend(monteblanco)
+    A, B = Planner(hip, 1, **cfg), Fleet(hip, 70, **cfg)
+    st = drive(monteblanco, A, B, seed, 300, exact=False, scen_b=69)
+    assert st['ticks'] >= 200 and 'follow' in st['keys'], st
+    A.close(); B.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", sorted(OTHER_EXPONENTS))
+def test_device_fleet_agrees_with_the_host_planner_over_the_oracle_at_other_exponents(monteblanco, case):
+    """... and against arithmetic that shares nothing with the kernels: the host planner of the CPU harness (oracle/planner_host.py, the
+    oracle's velocity solver) drives, the device fleet gets the same inputs."""
+    from oracle.planner_host import HostPlannerBackend
+    from graphbasedlocaltrajectoryplanner_amd import _capi
+    from graphbasedlocaltrajectoryplanner_amd.fleet import Fleet
+    seed, cfg = OTHER_EXPONENTS[case]
+    hip = _capi.HipBackend(monteblanco)
+    A, B = HostPlannerBackend(monteblanco).planner(1, **cfg), Fleet(hip, 70, **cfg)
+    st = drive(monteblanco, A, B, seed, 300, exact=False, scen_b=69)
+    assert st['ticks'] >= 200 and 'follow' in st['keys'], st
+    A.close(); B.close()

@@ -38,8 +38,10 @@ def default_backend(lat, **kw):
 def sub_batch(scen, vels, vel, lo, hi):
     """Scenarios lo .. hi-1 of a batch (scenarios, vehicle speeds, TickVelBatch) as a batch of their own."""
     veh = [x for x in vels[lo:hi] if len(x)]
+    t = vel.struct
     v = _capi.TickVelBatch(vel.params, hi - lo, vel.vel_plan[lo:hi], vel.vel_est[lo:hi],
-                           np.column_stack((vel.pos_x[lo:hi], vel.pos_y[lo:hi])), np.concatenate(veh) if veh else np.zeros(0))
+                           np.column_stack((vel.pos_x[lo:hi], vel.pos_y[lo:hi])), np.concatenate(veh) if veh else np.zeros(0),
+                           gg=(t.gg_ax, t.gg_ay), gg_brake_scale=t.gg_brake_scale, safety_d=t.safety_d, v_max_offset=t.v_max_offset)
     return _capi.PathsBatch(scen[lo:hi], w_last_edges=W_LAST), v
 
 

@@ -4,7 +4,10 @@ import pytest
 
 from helpers import load_golden, assert_close_rel, assert_vx_elementwise, assert_ax_elementwise
 from scenarios import random_scenarios, raceline_state
-from test_oracle_vel_golden import make_vp, replay_vel_call, check_vel_output
+from test_oracle_vel_golden import (make_vp, replay_vel_call, check_vel_output, replay_velparams_fixture, assert_velparams_coverage,
+                                    VELPARAMS_FIXTURE)
+from vel_jobs import (random_jobs, VARIANT_SETS, VARIANT_IDS, CHUNK_EDGE_LENGTHS, params_of, chunk_edge_jobs, edge_jobs,   # noqa: F401
+                      brake_job_stopping_at, table_64_rows)
 from graphbasedlocaltrajectoryplanner_amd import _capi
 
 pytestmark = pytest.mark.gpu
@@ -22,41 +25,13 @@ def test_hip_matches_reference_vel_recordings(monteblanco, hip_backend, fixture)
     assert {'calc_vel_profile', 'calc_vel_profile_follow'} <= seen or fixture != "c2_vel_calls.npz"
 
 
-def random_jobs(lat, rng, n_jobs, varying_gg):
-    jobs = []
-    track_len = float(lat.glob_rl[-1, 0])
-    for _ in range(n_jobs):
-        n = int(rng.integers(2, 400))
-        mode = int(rng.integers(0, 3))
-        # curvature profile: piecewise smooth with straights (exact zeros) and tight corners
-        kappa = 0.08 * np.sin(np.linspace(0, rng.uniform(1, 12), n) + rng.uniform(0, 6)) * rng.uniform(0, 1)
-        kappa[np.abs(kappa) < 0.004] = 0.0
-        el = rng.uniform(1.5, 3.5, n - 1)
-        if varying_gg:
-            gg = np.column_stack((rng.uniform(3.0, 8.0, n), rng.uniform(3.0, 8.0, n)))
-        else:
-            gg = np.ones((n, 2)) * rng.uniform(3.0, 9.0, 2)
-        job = {"mode": mode, "kappa": kappa, "loc_gg": gg, "v_start": float(rng.uniform(0, 70))}
-        if mode == _capi.VEL_FB:
-            job["el_lengths"] = el
-            job["v_end"] = float(rng.uniform(0, 60)) if rng.random() < 0.8 else None
-        elif mode == _capi.VEL_BRAKE:
-            job["el_lengths"] = el
-        else:
-            job["el_lengths"] = np.append(el, 0.0)
-            x, y, _, v = raceline_state(lat, rng.uniform(0, track_len))
-            job.update(v_ego=job["v_start"] + rng.uniform(-1, 1), v_obj=float(v) * rng.uniform(0.1, 1.0),
-                       safety_d=float(rng.uniform(5, 40)), obj_dist=float(rng.uniform(-5, 400)),
-                       obj_pos=(float(x + rng.uniform(-2, 2)), float(y + rng.uniform(-2, 2))))
-        jobs.append(job)
-    return jobs
-
-
 @pytest.mark.parametrize("exp,axm,ctrl,varying_gg", [
     (1.0, [[100.0, 5.0]], "PD", False),
     (1.0, [[0.0, 6.0], [36.0, 6.0], [48.0, 4.8], [60.0, 3.9], [72.0, 2.5]], "PD", True),
     (2.0, [[100.0, 5.0]], "PDtan", False),
     (1.5, [[0.0, 6.0], [72.0, 2.5]], "PD", True),
+    (2.0, [[0.0, 6.0], [36.0, 6.0], [72.0, 2.5]], "PD", True),             # with these two: all six kernel variants
+    (1.5, [[100.0, 4.0]], "PDtan", False),
 ])
 def test_hip_vel_matches_oracle_on_random_jobs(monteblanco, hip_backend, oracle_backend, exp, axm, ctrl, varying_gg):
     rng = np.random.default_rng(int(exp * 10) + len(axm))
@@ -73,6 +48,115 @@ def test_hip_vel_matches_oracle_on_random_jobs(monteblanco, hip_backend, oracle_
         assert tc == rtc
         n_flag_mismatch += int(vb != rvb)
     assert n_flag_mismatch == 0
+
+
+def compare_jobs(jobs, got, exp_):
+    """The assertions of the random-job test, job by job, a failure naming the job."""
+    assert len(got) == len(exp_) == len(jobs)
+    for jb, (vx, tc, vb), (rx, rtc, rvb) in zip(jobs, got, exp_):
+        what = "job '%s' mode %d n %d" % (jb["name"], jb["mode"], jb["kappa"].size)
+        assert_close_rel(vx, rx, what=what)
+        assert_vx_elementwise(vx, rx, what)
+        assert tc == rtc, what + " too_close"
+        assert vb == rvb, what + " vel_bound"
+
+
+_largest_n = {}
+
+
+def largest_accepted_n(hip, lat):
+    """The longest job ltpl_vel_profile accepts on this handle (its solver keeps a job in LDS; longer ones are refused with
+    LTPL_ERR_CAPACITY before anything is launched), found by bisection."""
+    if "n" not in _largest_n:
+        params = params_of(lat, 1.0, [[100.0, 5.0]], "PD", 60.0)
+
+        def accepted(n):
+            job = {"name": "probe", "mode": _capi.VEL_FOLLOW, "kappa": np.zeros(n), "el_lengths": np.full(n, 2.0), "loc_gg": np.full((n, 2), 5.0),
+                   "v_start": 10.0, "v_ego": 10.0, "v_obj": 5.0, "safety_d": 20.0, "obj_dist": 50.0, "obj_pos": tuple(lat.glob_rl[0, 1:3])}
+            try:
+                hip.vel_profile(params, [job])
+            except _capi.BackendError as exc:
+                assert "capacity exceeded" in str(exc), exc
+                return False
+            return True
+        lo, hi = 512, 65536
+        assert accepted(lo) and not accepted(hi)
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            lo, hi = (mid, hi) if accepted(mid) else (lo, mid)
+        _largest_n["n"] = lo
+    return _largest_n["n"]
+
+
+@pytest.mark.parametrize("k", range(6), ids=VARIANT_IDS)
+def test_hip_vel_matches_oracle_at_the_edges_of_the_sweeps_passes(monteblanco, hip_backend, oracle_backend, k):
+    """fb_sweep, brake_profile and the cumulative sums run 64 steps per pass, unrolled by four, with steps that must change nothing beyond
+    the job's end: every mode at n - 1 = 1, 2, 3, 4, 62 .. 65, 126 .. 129, 192 and at the longest job the entry point accepts, mixed in one
+    call so that neighbouring jobs differ in length and mode."""
+    exp, axm, ctrl, varying_gg = VARIANT_SETS[k]
+    n_max = largest_accepted_n(hip_backend, monteblanco)
+    assert n_max > 1024
+    print("largest job ltpl_vel_profile accepts: %d points" % n_max)
+    params = params_of(monteblanco, exp, axm, ctrl, 60.0 + 6.0 * k)
+    jobs = chunk_edge_jobs(monteblanco, 400 + k, varying_gg, CHUNK_EDGE_LENGTHS + (n_max,))
+    assert len(jobs) == 4 * (len(CHUNK_EDGE_LENGTHS) + 1)
+    assert all(a["kappa"].size != b["kappa"].size or a["mode"] != b["mode"] for a, b in zip(jobs, jobs[1:]))
+    compare_jobs(jobs, hip_backend.vel_profile(params, jobs), oracle_backend.vel_profile(params, jobs))
+
+
+@pytest.mark.parametrize("v_max", (95.0, 42.0))
+@pytest.mark.parametrize("k", range(6), ids=VARIANT_IDS)
+def test_hip_vel_matches_oracle_on_named_edge_inputs(monteblanco, hip_backend, oracle_backend, k, v_max):
+    """vel_jobs.edge_jobs, and brake jobs that reach standstill at the last point of a pass, the first of the next and next to them.
+    v_max = 42 m/s puts the solver's "> v_max" break within reach of the straights; at 95 m/s speeds above the machine tables' last row
+    occur."""
+    exp, axm, ctrl, varying_gg = VARIANT_SETS[k]
+    params = params_of(monteblanco, exp, axm, ctrl, v_max)
+    jobs = edge_jobs(monteblanco, 500 + k, varying_gg, v_max)
+    for stop in (63, 64, 65, 128, 129):
+        jobs.append(brake_job_stopping_at(monteblanco, oracle_backend, params, 600 + 10 * k + stop, varying_gg, stop))
+    exp_ = oracle_backend.vel_profile(params, jobs)
+    by_name = {jb["name"]: out for jb, out in zip(jobs, exp_)}
+    # (on the oracle's result: the jobs do what their names say)
+    assert float(by_name["brake that never stops"][0].min()) > 1.0
+    assert float(by_name["brake that stops inside the first pass"][0][40]) == 0.0
+    for stop in (63, 64, 65, 128, 129):
+        vx = by_name["brake that stops at point %d" % stop][0]
+        assert vx[stop] == 0.0 and vx[stop - 1] > 0.0
+    assert by_name["follow, obj_dist negative"][1] and by_name["follow, obj_dist zero"][1]
+    if v_max < 50.0:
+        vx = by_name["straight that reaches v_max early, then a corner and a second straight"][0]
+        assert vx[:40].max() == v_max and vx.min() < 0.5 * v_max and vx[-1] > vx.min() + 5.0
+    compare_jobs(jobs, hip_backend.vel_profile(params, jobs), exp_)
+
+
+@pytest.mark.parametrize("exp", (1.0, 2.0, 1.5))
+def test_hip_vel_machine_table_of_64_rows_and_refusal_of_65(monteblanco, hip_backend, oracle_backend, exp):
+    """64 rows is the most make_vel_params admits; the table starts at 10 m/s and ends at 73 m/s, so speeds below its first and above its
+    last row occur. 65 rows are refused with LTPL_ERR_CAPACITY."""
+    table = table_64_rows()
+    assert table.shape == (64, 2)
+    params = params_of(monteblanco, exp, table, "PD", 95.0)
+    rng = np.random.default_rng(64)
+    jobs = edge_jobs(monteblanco, 700, True, 95.0)
+    for i, jb in enumerate(random_jobs(monteblanco, rng, 60, True)):
+        jb["name"] = "random job %d" % i
+        jobs.append(jb)
+    exp_ = oracle_backend.vel_profile(params, jobs)
+    vmin, vmax = min(float(o[0].min()) for o in exp_), max(float(o[0].max()) for o in exp_)
+    assert vmin < table[0, 0] and vmax > table[-1, 0]
+    compare_jobs(jobs, hip_backend.vel_profile(params, jobs), exp_)
+    v = 10.0 + np.arange(65.0)
+    too_long = params_of(monteblanco, exp, np.column_stack((v, 6.5 - 0.06 * (v - 10.0))), "PD", 95.0)
+    with pytest.raises(_capi.BackendError, match="capacity exceeded"):
+        hip_backend.vel_profile(too_long, jobs[:1])
+
+
+def test_hip_matches_reference_at_every_variants_parameters(monteblanco, hip_backend):
+    """The unmodified reference's VpForwardBackward at the six variants' parameter sets (oracle/gen_golden_velparams.py), replayed on the
+    kernels -- the recordings above run at exponent 1, the stock tables and the PD controller only."""
+    recs = load_golden(VELPARAMS_FIXTURE)
+    assert_velparams_coverage(recs, replay_velparams_fixture(hip_backend, monteblanco, recs))
 
 
 def make_tick_inputs(lat, n, seed, n_veh=8):
