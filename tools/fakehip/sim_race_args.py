@@ -149,6 +149,15 @@ else:
 assert failures >= 10, failures
 print("allocation failure at each of the %d allocations of ltpl_fleet_sim_race: previous state kept" % failures)
 print("launches per tick: %d without mates, %d with" % (plain, plain + 1))
+# exactly at the cap: 93 own objects + 3 mates = 96 fits, one own object more is refused
+at_cap = dict(good, opponents=[(10.0 * k, 0.3, 5.0) for k in range(93)])
+fleet.sim_setup(table, [at_cap] * N)
+fleet.sim_vel()
+assert call([0, N])[0] == 0
+fleet.sim_setup(table, [at_cap] * (N - 1) + [dict(at_cap, static=[(0.0, 0.0, 0.0, 0.0, 4.0)])])
+fleet.sim_vel()
+expect(no_allocation(lambda: call([0, N])), 4, "above 96")                       # LTPL_ERR_CAPACITY
+print("own objects + mates: 96 accepted, 97 refused")
 fleet.close()
 hip.close()
 print("sim race args OK")
