@@ -181,7 +181,41 @@ struct FVelIn { const double* pos_x; const double* pos_y; const double* vel_est;
                 const int* ax_off; const int* ax_idx;
                 // location dependent friction (local_gg as a dict, OTH.py:649-666; null: the constant tuple): rows gg_off[p * MK + k] ..
                 // gg_off[p * MK + k + 1] of gg_rows ([ax, ay] per path coordinate) belong to planner p's k-th path key, MK = LTPL_PLANNER_MAX_KEYS
-                const int* gg_off; const double* gg_rows; };
+                const int* gg_off; const double* gg_rows;
+                // friction maps resident on the device (ltpl_fleet_friction; null: none). Defaults: callers that build this struct member by
+                // member (host planner, CPU harness) stay as they are
+                const struct FrMap* fr_maps = nullptr; const double* fr_nodes = nullptr; const int* fr_idx = nullptr; const double* fr_scale = nullptr; };
+
+// A friction map: a regular grid of [ax, ay] nodes (rows of nx nodes from y0 upwards; node (iy, ix) = pair `off + iy nx + ix` of the stacked
+// node array, ax and ay adjacent: one 16-byte load fetches both). friction.FrictionGrid.rows is the definition, operation by operation:
+//   tx = (x - x0) / dx;  fx = floor(tx), not (fx >= 0) -> 0, fx > nx - 2 -> nx - 2;  u = tx - fx, u < 0 -> 0, u > 1 -> 1;  y likewise (fy, v)
+//   lo = (1 - u) a[fy][fx] + u a[fy][fx + 1];  hi = (1 - u) a[fy + 1][fx] + u a[fy + 1][fx + 1];  value = ((1 - v) lo + v hi) scale
+// for ax and ay each. + - * / floor only and no contraction (-ffp-contract=off): the device result equals the mirror's bit for bit.
+struct FrMap { double x0, y0, dx, dy; int nx, ny, off, pad_; };
+struct alignas(16) FrVal { double ax, ay; };
+FLT_FN void friction_cell(double t0, double d, double q, int n, int& i, double& u)
+{
+    const double t = (q - t0) / d;
+    double f = floor(t);
+    if (!(f >= 0.0)) f = 0.0;
+    if (f > (double)(n - 2)) f = (double)(n - 2);
+    u = t - f;
+    if (u < 0.0) u = 0.0;
+    if (u > 1.0) u = 1.0;
+    i = (int)f;
+}
+FLT_FN FrVal friction_at(const FrMap& m, const double* nodes, double x, double y, double scale)
+{
+    int ix, iy; double u, v;
+    friction_cell(m.x0, m.dx, x, m.nx, ix, u);
+    friction_cell(m.y0, m.dy, y, m.ny, iy, v);
+    const FrVal* a = reinterpret_cast<const FrVal*>(nodes) + (size_t)m.off + (size_t)iy * m.nx + ix;     // four node loads, 16 bytes each
+    const FrVal a00 = a[0], a01 = a[1], a10 = a[m.nx], a11 = a[m.nx + 1];
+    const double cu = 1.0 - u, cv = 1.0 - v;
+    const double lox = cu * a00.ax + u * a01.ax, hix = cu * a10.ax + u * a11.ax;
+    const double loy = cu * a00.ay + u * a01.ay, hiy = cu * a10.ay + u * a11.ay;
+    return FrVal{(cv * lox + v * hix) * scale, (cv * loy + v * hiy) * scale};
+}
 
 // seam (2): job table + pooled arrays (the layout k_vel_profile reads). Job slot j owns 4 R doubles of `pool` (kappa R | el R | gg 2 R)
 // and R doubles of `out`; an unused slot has n = 0.
@@ -649,7 +683,10 @@ FLT_FN int make_job(const X& x, const Dims& D, const FJobs& J, int p, int slot, 
 // ---------------------------------------------------------------------------------------------------------------------
 // OTH.calc_vel_profile, stage A: get_ref_idx, slicing (:700-731), job construction (:736-903)
 // ---------------------------------------------------------------------------------------------------------------------
-template <class X>
+// FR: the friction maps are compiled in. A fleet without a map launches the FR = false kernels, which hold no map code; their source differs
+// from the form before the maps by the null tests of gg_off / gg_rows inside the loop (one register less in k_fleet_vel_a), and that their
+// results are the same is what the tests show (traces of fleets without a map are bit-identical), not an identity of the code
+template <class X, bool FR = false>
 FLT_FN void vel_a(const X& x, const FLat& lat, const FCfg& cfg, const Block& B, PlannerS& S, int p, const FObj& ob, const FVelIn& vin, const FJobs& J)
 {
     const Dims& D = B.D;
@@ -670,7 +707,12 @@ FLT_FN void vel_a(const X& x, const FLat& lat, const FCfg& cfg, const Block& B, 
     // constant tuple. Rows are kept next to the path rows (same window: they are trimmed with them) and, from the cut on, in Block::gv(k)
     // for stage C (the emergency profile uses the FIRST kept key's rows even when that key falls back to the backup plan). Its own loop
     // in front of the job construction: calls without rows (the common case) pay one uniform branch.
-    if (vin.gg_off && vin.gg_rows && B.g) {
+    // Third source (FR): the planner's friction map, evaluated at x, y of every path row of a key the caller gave no rows for, times the
+    // planner's grip factor (lane per row, four node loads per row) -- written into the same windows, so trimming, the backup plan's own
+    // rows and stage C work as with caller rows.
+    int fmap = -1;
+    if constexpr (FR) { if (vin.fr_idx && B.g) fmap = vin.fr_idx[p]; }
+    if ((vin.gg_off && vin.gg_rows && B.g) || fmap >= 0) {
         const int MK = LTPL_PLANNER_MAX_KEYS;
         for (int k = 0; k < S.n_last; ++k) {
             const int sl = S.last_slot[k];
@@ -678,7 +720,7 @@ FLT_FN void vel_a(const X& x, const FLat& lat, const FCfg& cfg, const Block& B, 
             const int rows = T.rows;
             const int c0 = S.cut_index_pos < 0 ? 0 : (S.cut_index_pos < rows ? S.cut_index_pos : rows);
             int g_n = 0; const double* g_src = vin.gg_rows;
-            if (k < MK) { const int o0 = vin.gg_off[p * MK + k]; g_n = vin.gg_off[p * MK + k + 1] - o0; g_src += (size_t)o0 * 2; }
+            if (k < MK && vin.gg_off && vin.gg_rows) { const int o0 = vin.gg_off[p * MK + k]; g_n = vin.gg_off[p * MK + k + 1] - o0; g_src += (size_t)o0 * 2; }
             if (g_n > 0 && g_n != rows) { fail(S, LTPL_ERR_INVALID_ARG, E_GG_ROWS); return; }
             if (g_n > 0) {
                 const Rows G = B.gg(set, sl).from(T.r0), gv = B.gv(k);
@@ -689,6 +731,18 @@ FLT_FN void vel_a(const X& x, const FLat& lat, const FCfg& cfg, const Block& B, 
                 }
             }
             T.has_gg = g_n > 0 ? 1 : 0;
+            if constexpr (FR) {
+                if (fmap >= 0 && g_n <= 0 && rows > 0) {
+                    const FrMap fm = vin.fr_maps[fmap]; const double fs = vin.fr_scale[p];
+                    const Rows P = B.pp(set, sl).from(T.r0), G = B.gg(set, sl).from(T.r0), gv = B.gv(k);
+                    for (int i = x.lane(); i < rows; i += X::W) {
+                        const FrVal a = friction_at(fm, vin.fr_nodes, P.at(i, 0), P.at(i, 1), fs);
+                        G.at(i, 0) = a.ax; G.at(i, 1) = a.ay;
+                        if (i >= c0) { gv.at(i - c0, 0) = a.ax; gv.at(i - c0, 1) = a.ay; }
+                    }
+                    T.has_gg = 1;
+                }
+            }
         }
         x.sync();
     } else {

@@ -167,13 +167,15 @@ __global__ __launch_bounds__(64) void k_fleet_digest(FleetArgs F, double* out, i
 #ifndef LTPL_FLEET_VELA_WAVES
 #define LTPL_FLEET_VELA_WAVES 4       // waves per SIMD the stage-A kernels are compiled for (their register budget): A/B in profiles/r05k_fleet_occ_ab.txt
 #endif
+// FR: fleets with a friction map (ltpl_fleet_friction) launch the variants that hold the map evaluation; every other fleet the variants without it
+template <bool FR>
 __global__ __launch_bounds__(64, LTPL_FLEET_VELA_WAVES) void k_fleet_vel_a(FleetArgs F, fleet::FObj ob, fleet::FVelIn vin, fleet::FJobs JA)
 {
     const int p = blockIdx.x; const WaveX x{(int)threadIdx.x};
     const fleet::Block B{F.state + F.D.stride * (size_t)p, F.D, F.gg ? F.gg + F.D.gg_stride * (size_t)p : nullptr};
     __shared__ fleet::PlannerS S;
     fleet_load(x, B, &S);
-    fleet::vel_a(x, F.lat, F.cfg, B, S, p, ob, vin, JA);
+    fleet::vel_a<WaveX, FR>(x, F.lat, F.cfg, B, S, p, ob, vin, JA);
     fleet_store(x, B, &S, p, F.err_word);
 }
 
@@ -181,6 +183,7 @@ __global__ __launch_bounds__(64, LTPL_FLEET_VELA_WAVES) void k_fleet_vel_a(Fleet
 // ONE kernel -- the scalars are loaded / stored once and a kernel boundary (drain + refill of 8 192 short waves) goes away:
 //   paths_post + vel_a            (behind seam (1))
 //   vel_c | vel_d + paths_pre     (behind the last velocity launch of tick t: the first kernel of tick t + 1)
+template <bool FR>
 __global__ __launch_bounds__(64, LTPL_FLEET_VELA_WAVES) void k_fleet_post_vel_a(FleetArgs F, fleet::FPathsOut po, fleet::FObj ob, fleet::FVelIn vin, fleet::FJobs JA)
 {
     const int p = blockIdx.x; const WaveX x{(int)threadIdx.x};
@@ -189,7 +192,7 @@ __global__ __launch_bounds__(64, LTPL_FLEET_VELA_WAVES) void k_fleet_post_vel_a(
     fleet_load(x, B, &S);
     if (!S.err) fleet::paths_post(x, F.lat, B, S, p, po);
     x.sync();
-    fleet::vel_a(x, F.lat, F.cfg, B, S, p, ob, vin, JA);
+    fleet::vel_a<WaveX, FR>(x, F.lat, F.cfg, B, S, p, ob, vin, JA);
     fleet_store(x, B, &S, p, F.err_word);
 }
 template <bool D>      // D: the tick had an emergency launch -> stage D in front of the next tick; else stage C
@@ -382,6 +385,10 @@ struct ltpl_fleet {
     size_t vel_lds = 0, vel_lds_lite = 0, vel_lds_gg = 0, vel_lds_lite_gg = 0;
     bool tape_fuse = !(getenv("LTPL_FLEET_NO_FUSE") && atoi(getenv("LTPL_FLEET_NO_FUSE")) != 0);     // tape runs with fused stage kernels (results identical)
     FleetSim* sim = nullptr;                          // ltpl_fleet_sim_setup
+    // friction maps (ltpl_fleet_friction, fleet_friction.hpp): geometry, stacked nodes, map and grip factor of every planner; fr_on: some
+    // planner has a map -- the velocity stage then runs the FR variants of stage A and the rows form of the job kernels
+    fleet::FrMap* fr_maps = nullptr; double* fr_nodes = nullptr; int* fr_idx = nullptr; double* fr_scale = nullptr;
+    std::vector<fleet::FrMap> fr_host; bool fr_on = false;
     ~ltpl_fleet()
     {
         if (h) { (void)hipSetDevice(h->device); (void)hipStreamSynchronize(h->stream); --h->n_planners; }
@@ -390,6 +397,7 @@ struct ltpl_fleet {
         if (ev_a) (void)hipEventDestroy(ev_a);
         if (ev_b) (void)hipEventDestroy(ev_b);
         for (void* p : allocs) (void)hipFree(p);
+        for (void* p : {(void*)fr_maps, (void*)fr_nodes, (void*)fr_idx, (void*)fr_scale}) if (p) (void)hipFree(p);
         if (cur.d_buf) (void)hipFree(cur.d_buf);
         if (curv.d_buf) (void)hipFree(curv.d_buf);
         for (FleetTickIn& t : tape) if (t.d_buf) (void)hipFree(t.d_buf);
@@ -813,8 +821,15 @@ static int fleet_launch_vel(ltpl_fleet* f, const FleetTickIn& t, const fleet::FP
     vp.n_ax_max_machines = t.n_axm; vp.ax_max_machines = one_row;      // (the table itself is read on the device: t.axm)
     vp.follow_control_type = f->pc.follow_control_type; vp.c_p = f->pc.c_p; vp.k_p = f->pc.k_p; vp.k_d = f->pc.k_d; vp.tan_w = f->pc.tan_w; vp.v_max = t.vel_max;
     int rc;
-    if (fused_post) hipLaunchKernelGGL(k_fleet_post_vel_a, dim3(N), dim3(64), 0, st, f->args, *fused_post, t.ob, t.vin, f->JA.view());
-    else hipLaunchKernelGGL(k_fleet_vel_a, dim3(N), dim3(64), 0, st, f->args, t.ob, t.vin, f->JA.view());
+    // the fleet's friction maps are bound at the launch (a tape or a simulation keeps its inputs; the maps may change between runs)
+    fleet::FVelIn vin = t.vin;
+    if (f->fr_on) {
+        vin.fr_maps = f->fr_maps; vin.fr_nodes = f->fr_nodes; vin.fr_idx = f->fr_idx; vin.fr_scale = f->fr_scale;
+        if (fused_post) hipLaunchKernelGGL(k_fleet_post_vel_a<true>, dim3(N), dim3(64), 0, st, f->args, *fused_post, t.ob, vin, f->JA.view());
+        else hipLaunchKernelGGL(k_fleet_vel_a<true>, dim3(N), dim3(64), 0, st, f->args, t.ob, vin, f->JA.view());
+    }
+    else if (fused_post) hipLaunchKernelGGL(k_fleet_post_vel_a<false>, dim3(N), dim3(64), 0, st, f->args, *fused_post, t.ob, vin, f->JA.view());
+    else hipLaunchKernelGGL(k_fleet_vel_a<false>, dim3(N), dim3(64), 0, st, f->args, t.ob, vin, f->JA.view());
     FLEET_TRY(f, hipGetLastError());
     {   // forward-backward jobs (slots >= 1), one lane per job, on the second stream: 512 long waves for 8 192 planners -- next to the follow jobs
         DevVelParams p;
@@ -829,7 +844,9 @@ static int fleet_launch_vel(ltpl_fleet* f, const FleetTickIn& t, const fleet::FP
         FLEET_TRY(f, hipGetLastError());
         FLEET_TRY(f, hipEventRecord(f->ev_b, f->stream2));
     }
-    const bool rows = t.has_gg != 0, multi = t.multi_axm != 0;
+    // (a tick on a map counts as a tick with rows: seen_gg stays set after the maps are cleared, because a planner's backup plan may still
+    //  hold rows of an earlier tick -- the brake / emergency launches keep the rows form, stage A and the lane kernels go back)
+    const bool rows = t.has_gg != 0 || f->fr_on, multi = t.multi_axm != 0;
     if (rows) f->seen_gg = true;
     const bool rows_mem = rows || f->seen_gg;          // jobs built from the planners' memory (backup plans) may carry rows of an earlier tick
     if (f->JA.ke_follow >= 0) {                                                                  // follow jobs (slot 0) without friction rows: one LANE per job (round 5)
@@ -847,14 +864,14 @@ static int fleet_launch_vel(ltpl_fleet* f, const FleetTickIn& t, const fleet::FP
     hipLaunchKernelGGL(k_fleet_vel_b, dim3(N), dim3(64), 0, st, f->args, f->JA.view(), f->JB.view());
     FLEET_TRY(f, hipGetLastError());
     if ((rc = fleet_launch_vel_jobs(f, vp, t.axm, f->JB, 1, multi, rows_mem))) return rc;
-    if (next && !t.any_emerg) hipLaunchKernelGGL(k_fleet_tail_pre<false>, dim3(N), dim3(64), 0, st, f->args, t.vin, f->JB.view(), f->JC.view(), next->ob, f->pin);
-    else hipLaunchKernelGGL(k_fleet_vel_c, dim3(N), dim3(64), 0, st, f->args, t.vin, f->JB.view(), f->JC.view());
+    if (next && !t.any_emerg) hipLaunchKernelGGL(k_fleet_tail_pre<false>, dim3(N), dim3(64), 0, st, f->args, vin, f->JB.view(), f->JC.view(), next->ob, f->pin);
+    else hipLaunchKernelGGL(k_fleet_vel_c, dim3(N), dim3(64), 0, st, f->args, vin, f->JB.view(), f->JC.view());
     FLEET_TRY(f, hipGetLastError());
     if (t.any_emerg) {
         ltpl_vel_params ve = vp; ve.dyn_model_exp = 1.0; ve.drag_coeff = 0.854; ve.m_veh = 1160.0;       // calc_brake_emergency.py:4-6,31-36
         if ((rc = fleet_launch_vel_jobs(f, ve, t.axm, f->JC, 1, false, rows_mem))) return rc;
-        if (next) hipLaunchKernelGGL(k_fleet_tail_pre<true>, dim3(N), dim3(64), 0, st, f->args, t.vin, f->JB.view(), f->JC.view(), next->ob, f->pin);
-        else hipLaunchKernelGGL(k_fleet_vel_d, dim3(N), dim3(64), 0, st, f->args, t.vin, f->JC.view());
+        if (next) hipLaunchKernelGGL(k_fleet_tail_pre<true>, dim3(N), dim3(64), 0, st, f->args, vin, f->JB.view(), f->JC.view(), next->ob, f->pin);
+        else hipLaunchKernelGGL(k_fleet_vel_d, dim3(N), dim3(64), 0, st, f->args, vin, f->JC.view());
         FLEET_TRY(f, hipGetLastError());
     }
     return LTPL_OK;

@@ -4797,3 +4797,4 @@ try {
 // ---------------------------------------------------------------------------------------------------------------------
 #include "fleet_dev.hpp"
 #include "fleet_sim.hpp"
+#include "fleet_friction.hpp"

@@ -31,6 +31,12 @@ class SimRaceIn(C.Structure):             # ltpl_fleet_sim_race_in
     _fields_ = [("n_races", C.c_int32), ("race_off", C.c_void_p), ("length", C.c_void_p), ("heading0", C.c_void_p)]
 
 
+class FrictionIn(C.Structure):            # ltpl_fleet_friction_in
+    _fields_ = [("n_maps", C.c_int32), ("x0", C.c_void_p), ("y0", C.c_void_p), ("dx", C.c_void_p), ("dy", C.c_void_p),
+                ("nx", C.c_void_p), ("ny", C.c_void_p), ("node_off", C.c_void_p), ("nodes", C.c_void_p),
+                ("map_idx", C.c_void_p), ("scale", C.c_void_p)]
+
+
 SIM_TRACE_DOUBLES = 8 + 8 + 9 * _capi.PLANNER_MAX_KEYS     # LTPL_FLEET_SIM_TRACE_DOUBLES
 
 
@@ -56,6 +62,10 @@ class Fleet(Planner):
         if hasattr(self.lib, "ltpl_fleet_sim_race"):
             f("sim_race").argtypes = [C.c_void_p, C.POINTER(SimRaceIn)]
             f("sim_heading").argtypes = [C.c_void_p, C.c_void_p]
+        if hasattr(self.lib, "ltpl_fleet_friction"):
+            f("friction").argtypes = [C.c_void_p, C.POINTER(FrictionIn)]
+            f("friction_scale").argtypes = [C.c_void_p, C.c_void_p]
+            f("friction_rows").argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p]
 
     def set_start(self, scen, pos, heading, vel=0.0, max_heading_offset=math.pi / 4):
         out = Planner.set_start(self, scen, pos, heading, vel, max_heading_offset)
@@ -295,7 +305,8 @@ class Fleet(Planner):
 
     def sim_vel(self, ax_tables=None, ax_table_idx=None, **vel_kwargs):
         """Velocity arguments of the following ``sim_run`` calls (keywords of ``calc_vel_profile`` without pos_est / vel_est, scalars or one
-        value per planner; ``ax_tables`` + ``ax_table_idx``: a machine table per planner). local_gg as a dict is not supported."""
+        value per planner; ``ax_tables`` + ``ax_table_idx``: a machine table per planner). local_gg as a dict is not supported: location dependent grip comes from a map
+        on the device (``friction``)."""
         vi, keep = self._pack_vel_in([(0.0, 0.0)] * self.n_scen, 0.0, **vel_kwargs)
         if ax_tables is not None:
             keep = [keep]
@@ -339,6 +350,53 @@ class Fleet(Planner):
         """[n] heading of every planner's tracked pose (``sim_race``'s heading0 until its first trajectory)."""
         out = np.zeros(self.n_scen, np.float64)
         self._check(self._fn("sim_heading")(self.handle, out.ctypes.data))
+        return out
+
+    # ---- friction maps on the device ------------------------------------------------------------------------------------------------
+    def friction(self, maps, map_idx=None, scale=1.0):
+        """Location dependent grip from maps resident on the device (ltpl_fleet_friction; local_gg as a dict, OTH.py:633-666). ``maps``:
+        a ``friction.FrictionGrid`` or a list of them (empty / None: clears the maps); ``map_idx``: the map of every planner (scalar or one
+        per planner, -1: the planner keeps its constant ``local_gg`` tuple; default: map 0 for all); ``scale``: grip factor per planner.
+        A planner with a map takes the rows of every offered key from the map on every route of the velocity stage
+        (``calc_vel_profile``, ``tape_run``, ``sim_run`` with or without races); between ticks or runs at any time."""
+        n, f64, i32 = self.n_scen, np.float64, np.int32
+        if maps is None:
+            maps = []
+        elif hasattr(maps, "rows"):
+            maps = [maps]
+        maps = list(maps)
+        fi = FrictionIn()
+        fi.n_maps = len(maps)
+        keep = []
+        if maps:
+            def col(vals, dt):
+                a = np.ascontiguousarray(np.array(vals, dt))
+                keep.append(a)
+                return a.ctypes.data
+            fi.x0, fi.y0 = col([m.x0 for m in maps], f64), col([m.y0 for m in maps], f64)
+            fi.dx, fi.dy = col([m.dx for m in maps], f64), col([m.dy for m in maps], f64)
+            fi.nx, fi.ny = col([m.nx for m in maps], i32), col([m.ny for m in maps], i32)
+            fi.node_off = col(np.concatenate(([0], np.cumsum([m.nx * m.ny for m in maps]))), i32)
+            nodes = np.ascontiguousarray(np.concatenate([m.nodes() for m in maps]), f64)
+            idx = np.ascontiguousarray(np.broadcast_to(np.asarray(0 if map_idx is None else map_idx, i32), (n,)))
+            sc = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, f64), (n,)))
+            keep += [nodes, idx, sc]
+            fi.nodes, fi.map_idx, fi.scale = nodes.ctypes.data, idx.ctypes.data, sc.ctypes.data
+        self._check(self._fn("friction")(self.handle, C.byref(fi)))
+
+    def friction_scale(self, scale):
+        """New grip factors (scalar or one per planner) on the maps set by ``friction`` (ltpl_fleet_friction_scale)."""
+        sc = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, np.float64), (self.n_scen,)))
+        self._check(self._fn("friction_scale")(self.handle, sc.ctypes.data))
+
+    def friction_rows(self, map, xy, scale=1.0):
+        """[n, 2] = [ax, ay] of map ``map`` at the points ``xy`` [n, 2] times ``scale``, evaluated on the device
+        (ltpl_fleet_friction_rows); equals ``FrictionGrid.rows`` bit for bit."""
+        xy = np.asarray(xy, np.float64).reshape(-1, 2)
+        x, y = np.ascontiguousarray(xy[:, 0]), np.ascontiguousarray(xy[:, 1])
+        out = np.zeros((xy.shape[0], 2), np.float64)
+        self._check(self._fn("friction_rows")(self.handle, int(map), x.ctypes.data, y.ctypes.data, int(xy.shape[0]), float(scale),
+                                              out.ctypes.data))
         return out
 
     def sim_state(self):

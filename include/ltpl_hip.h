@@ -53,7 +53,8 @@ extern "C" {
 #endif
 
 #define LTPL_ABI_VERSION 9        /* v7 (round 5, additive): ltpl_paths_kernel_symbol, ltpl_layer_grid, ltpl_fleet_digest; v8 (additive): ltpl_assembly_records;
-                                     v9 (round 6, additive): ltpl_create_ex, ltpl_tick_persistent_stop / _stats */
+                                     v9 (round 6, additive): ltpl_create_ex, ltpl_tick_persistent_stop / _stats;
+                                     additive to v9: ltpl_fleet_sim_race / _heading, ltpl_fleet_friction / _scale / _rows */
 
 /* status codes */
 #define LTPL_OK               0
@@ -701,7 +702,8 @@ typedef struct {
 
 /* (re)initialises the simulation of every planner; the planners' own memory (ltpl_fleet_set_start) is not touched */
 int ltpl_fleet_sim_setup(ltpl_fleet* fleet, const ltpl_fleet_sim_in* in);
-/* velocity arguments of the following runs (pos_est / vel_est members ignored; gg_row_off / gg_rows: LTPL_ERR_UNSUPPORTED) */
+/* velocity arguments of the following runs (pos_est / vel_est members ignored; gg_row_off / gg_rows: LTPL_ERR_UNSUPPORTED -- location
+ * dependent friction of a simulation comes from the fleet's maps, ltpl_fleet_friction below) */
 int ltpl_fleet_sim_vel(ltpl_fleet* fleet, const ltpl_planner_vel_in* in);
 /* n_ticks ticks back to back on the handle's stream; trace (may be NULL): [n_ticks][n][doubles_per_tick_planner] with
  * doubles_per_tick_planner == LTPL_FLEET_SIM_TRACE_DOUBLES, copied out once at the end; ms_total (may be NULL): device time of the run.
@@ -738,6 +740,45 @@ typedef struct {
 int ltpl_fleet_sim_race(ltpl_fleet* fleet, const ltpl_fleet_sim_race_in* in);
 /* [n] heading of every planner's tracked pose */
 int ltpl_fleet_sim_heading(ltpl_fleet* fleet, double* theta);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Additive to ABI v9 -- FRICTION MAPS resident on the device: location dependent grip for a fleet (local_gg as a dict,
+ * OnlineTrajectoryHandler.py:633-666: one [ax, ay] row per path coordinate of every offered key). A map is a regular grid of nodes,
+ * interpolated bilinearly and clamped at its border. For x (y likewise, with y0, dy, ny, fy, v):
+ *     tx = (x - x0) / dx;  fx = floor(tx), not (fx >= 0): fx = 0, fx > nx - 2: fx = nx - 2;  u = tx - fx, u < 0: u = 0, u > 1: u = 1
+ *     lo = (1 - u) a[fy][fx] + u a[fy][fx + 1];  hi = (1 - u) a[fy + 1][fx] + u a[fy + 1][fx + 1];  value = ((1 - v) lo + v hi) * scale
+ * in exactly this order of fp64 operations, for ax and ay each (host mirror: friction.FrictionGrid.rows, equal bit for bit).
+ * A planner with a map takes the rows of every offered key from the map -- columns x, y of the stitched path_param times the planner's
+ * scale -- on every route that runs the fleet's velocity stage (ltpl_fleet_calc_vel_profile, ltpl_fleet_tape_run, ltpl_fleet_sim_run with or
+ * without races). The call's constant tuple (gg_ax / gg_ay) is not used for that planner -- the reference does not read a tuple either when
+ * it is handed a dict --, gg_scale applies on top, rows handed over for a key through gg_row_off / gg_rows take precedence, and the
+ * emergency profile on a backup plan with rows is reported as with caller rows (OTH.py:1029-1036).
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct {
+    int32_t n_maps;                 /* 0: clears the maps (every other member is ignored)                          */
+    const double*  x0;              /* [n_maps] coordinates of node (0, 0), finite                                 */
+    const double*  y0;
+    const double*  dx;              /* [n_maps] node spacing, finite > 0                                           */
+    const double*  dy;
+    const int32_t* nx;              /* [n_maps] nodes per row / rows, >= 2                                         */
+    const int32_t* ny;
+    const int32_t* node_off;        /* [n_maps + 1] first node of every map in `nodes`: node_off[m + 1] - node_off[m] == nx[m] * ny[m] */
+    const double*  nodes;           /* [node_off[n_maps]][2] = [ax, ay] of node (iy, ix) at node_off[m] + iy * nx[m] + ix; finite > 0  */
+    const int32_t* map_idx;         /* [n] map of planner p, -1: the planner keeps its constant tuple               */
+    const double*  scale;           /* [n] grip factor of planner p on its map, finite > 0                          */
+} ltpl_fleet_friction_in;
+
+/* OTH.py:633-666. Sets (or clears) the fleet's maps; between ticks or runs at any time, also after ltpl_fleet_sim_run. Every argument is
+ * checked before the first HIP call; a failing call leaves the previous maps in place. After n_maps = 0 the planners plan on the call's
+ * constant tuple again (same results as a fleet handed rows up to that tick and tuples from then on); a backup plan stored while on a map
+ * keeps its own rows (OTH.py:963-968), so the brake / emergency launches of such a fleet stay in their rows form. */
+int ltpl_fleet_friction(ltpl_fleet* fleet, const ltpl_fleet_friction_in* in);
+/* OTH.py:633-666. scale [n]: new grip factors on the maps set before (a map that loses grip in the middle of a run), finite > 0 */
+int ltpl_fleet_friction_scale(ltpl_fleet* fleet, const double* scale);
+/* OTH.py:633-666. Batched lookup on the device: out [n_pts][2] = [ax, ay] of map `map` at (x[i], y[i]) times `scale`. A pure lookup: `scale`
+ * is any finite factor (zero and negative values included), unlike the planners' grip factors above, which the velocity stage divides by
+ * and which therefore must be positive. */
+int ltpl_fleet_friction_rows(ltpl_fleet* fleet, int32_t map, const double* x, const double* y, int32_t n_pts, double scale, double* out);
 
 #ifdef __cplusplus
 }

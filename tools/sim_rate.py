@@ -1,9 +1,11 @@
 """Closed-loop SIMULATION rate of a fleet (ltpl_fleet_sim_*): N planners, each with its own eight C2-style race-line opponents (SURVEY.md
 section 8d: s0_k = 250 + 280 k, vel_scale_k = 0.30 + 0.05 (k mod 4), here staggered by 10 m (p mod 16) per planner), run the example
 driver's loop on the device for T ticks without host work per tick.   tools/sim_rate.py [--planners 32768] [--ticks 200] [--no-tape]
-[--race-size K]. Prints planner-ticks per second of sim_run (device time of the run) next to tape_run on the C2 tape (recorded inputs,
+[--race-size K] [--friction-map] [--lib PATH]. Prints planner-ticks per second of sim_run (device time of the run) next to tape_run on the C2 tape (recorded inputs,
 tools/fleet_rate.py). --race-size K > 1: races of K consecutive planners (ltpl_fleet_sim_race) that see one another, started 30 m apart
-along the race line with its heading; K = 1 (default) is the run without races."""
+along the race line with its heading; K = 1 (default) is the run without races. --friction-map: the same fleet on the friction grid of
+tests/golden/friction_grid.npz (ltpl_fleet_friction: rows evaluated on the device, grip factors 1.0 .. 0.7 over the planners) instead of
+the constant tuple. --lib PATH: another build of the library (A/B against the parent's)."""
 import argparse
 import os
 import sys
@@ -27,10 +29,16 @@ def main():
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--no-tape", action="store_true", help="skip the tape_run comparison on the C2 recording")
     ap.add_argument("--race-size", type=int, default=1, help="planners per race (1: no races)")
+    ap.add_argument("--friction-map", action="store_true", help="every planner on the friction grid, own grip factor")
+    ap.add_argument("--lib", default=None, help="path of the library to load (default: the in-tree build)")
     a = ap.parse_args()
     lat = Lattice.load(os.path.join(ROOT, "tests", "golden", "monteblanco_lattice.npz"))
     race = RaceLineTable.from_track(np.load(os.path.join(ROOT, "tests", "golden", "monteblanco_track.npz")))
-    hip = _capi.HipBackend(lat)
+    hip = _capi.HipBackend(lat, lib_path=a.lib) if a.lib else _capi.HipBackend(lat)
+    grid = None
+    if a.friction_map:
+        from graphbasedlocaltrajectoryplanner_amd.friction import FrictionGrid
+        grid = FrictionGrid.load(os.path.join(ROOT, "tests", "golden", "friction_grid.npz"))
     ticks = pr.load_ticks("c2")
     st, va = ticks[0]['start'], ticks[0]['vel_args']
     zones = pr.zone_gids_of_tick(lat, ticks[0])
@@ -58,6 +66,8 @@ def main():
         fleet.sim_setup(race, entries)
         if K > 1:
             fleet.sim_race(sizes)
+        if grid is not None:
+            fleet.friction(grid, scale=1.0 - 0.3 * (np.arange(n) % 16) / 15.0)
         fleet.sim_vel(vel_max=va['vel_max'], gg_scale=va['gg_scale'], local_gg=tuple(va['local_gg']), safety_d=va['safety_d'],
                       ax_max_machines=va['ax_max_machines'])
         t0 = time.perf_counter()
@@ -77,7 +87,7 @@ def main():
             print("  last selected actions (none, straight, follow, left, right, emergency): %s" % sel.tolist())
         fleet.close()
     print("closed_loop_sim_ticks_per_s %.0f" % (n * a.ticks / best * 1e3))
-    if a.no_tape:
+    if a.no_tape or grid is not None:
         return
     fleet = Fleet(hip, n)
     for k in range(a.ticks):
