@@ -9,6 +9,12 @@
 //   k_fleet_sim_mates    (races with more than one planner only: ltpl_fleet_sim_race) one wave64 per planner, one lane per mate: every
 //                        other planner of the race, at the pose / speed / heading its tracker wrote above, through the same ingestion,
 //                        appended behind the planner's opponents and statics. Its own launch: every tracker of the tick is done first
+//   k_fleet_sim_tele     (telemetry on only: ltpl_fleet_sim_telemetry) one wave64 per planner: the tracked pose projected on the race line
+//                        (get_s_coord_dev, closed), the clearance to every on-track object of the tick (one lane per object, DPP wave
+//                        minimum, ties to the lower slot), then lane 0 updates the planner's 22-double record and writes its progress
+//   k_fleet_sim_rank     (telemetry on and races with more than one planner) one wave64 per planner, one lane per mate: rank by ballot /
+//                        popcount over every mate's progress of this tick, gap to the nearest car ahead by a wave minimum. Its own
+//                        launch: every planner's progress of the tick is written first
 //   k_fleet_sim_offsets  exclusive scan of the on-track counts -> veh_off (one workgroup)
 //   k_fleet_sim_compact  survivors into the fleet's object layout (one lane per planner)
 //   then paths_pre | path kernel | paths_post (+ vel_a) | velocity stages as in ltpl_fleet_tape_run. Tick k + 1's inputs depend on tick k's
@@ -268,6 +274,114 @@ __global__ __launch_bounds__(64) void k_fleet_sim_mates(DevLat lat, SimDev sd, d
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// race telemetry (ltpl_fleet_sim_telemetry, include/ltpl_hip.h): a record of LTPL_FLEET_SIM_TELE_DOUBLES doubles per planner, updated in
+// every tick in which the planner is live, behind its tracker and its mates. fp64, + - * / sqrt only, in the operation order of the
+// header's table (host mirror: sim.Telemetry). The pointers live in a struct of their own: k_fleet_sim_step carries none of them.
+// ---------------------------------------------------------------------------------------------------------------------
+enum { TELE_TICKS = 0, TELE_S, TELE_DIST, TELE_LAPS, TELE_T_CROSS, TELE_LAP_LAST, TELE_LAP_BEST, TELE_VEL_SUM, TELE_VEL_MAX, TELE_ACT,
+       TELE_CLEAR_MIN = 14, TELE_CLEAR_TICK, TELE_CLEAR_SLOT, TELE_CONTACT, TELE_RANK, TELE_PASSES, TELE_PASSED, TELE_GAP };
+static_assert(TELE_GAP + 1 == LTPL_FLEET_SIM_TELE_DOUBLES, "telemetry record layout");
+
+struct SimTele {
+    int n_rl; const double* rl_x; const double* rl_y; const double* rl_s;   // the lattice's race line, one point per layer, contiguous
+    double length;                         // closed length of the race line
+    const double* radius;                  // [N] contact radius
+    double* grid_s;                        // [N] progress offset of planner p (NaN: s of its first live tick, written there)
+    double* rec;                           // [N][LTPL_FLEET_SIM_TELE_DOUBLES]
+    double* prog;                          // [N] grid_s + dist of the last live tick (-inf before the first: behind everybody)
+};
+
+__global__ __launch_bounds__(64) void k_fleet_sim_tele(SimDev sd, SimTele te, int tick)
+{
+    const int p = blockIdx.x, lane = threadIdx.x;
+    if (!sd.live[p]) return;
+    const double px = sd.pos_x[p], py = sd.pos_y[p];
+    // (a pose that is not finite, or so far out that its squared distances overflow, has no closest point: the search would leave its index unset)
+    const double s = fabs(px) <= 1e100 && fabs(py) <= 1e100 ? get_s_coord_dev(te.n_rl, te.rl_x, te.rl_y, 1, te.rl_s, 1, px, py, true, lane, nullptr) : NAN;
+    // smallest clearance over the objects the planner is handed this tick (first smallest: the lower slot)
+    const int base = sd.obj_base[p], cnt = sd.cnt[p];
+    double cd = INFINITY; int ci = 0x7fffffff;
+    for (int b0 = 0; b0 < cnt; b0 += 64) {
+        const int k = b0 + lane;
+        if (k < cnt) {
+            const double dx = sd.g_x[base + k] - px, dy = sd.g_y[base + k] - py;
+            const double c = sqrt(dx * dx + dy * dy) - sd.g_r[base + k];
+            if (c < cd) { cd = c; ci = k; }
+        }
+    }
+    wave_min2(cd, ci);
+    if (lane != 0) return;
+    double* r = te.rec + (size_t)p * LTPL_FLEET_SIM_TELE_DOUBLES;
+    const double L = te.length, t_now = sd.now[p], vel = sd.vel[p];
+    double delta = 0.0;
+    bool fwd = false, bwd = false;
+    if (r[TELE_TICKS] == 0.0) {
+        if (isnan(te.grid_s[p])) te.grid_s[p] = s;
+    } else {
+        delta = s - r[TELE_S];
+        if (delta < -(L / 2)) { delta += L; fwd = true; }
+        else if (delta > L / 2) { delta -= L; bwd = true; }
+    }
+    r[TELE_TICKS] += 1.0;
+    r[TELE_S] = s;
+    r[TELE_DIST] += delta;
+    if (fwd) {
+        r[TELE_LAPS] += 1.0;
+        const double tc = delta > 0.0 ? t_now - sd.dt * (s / delta) : t_now;
+        const double prev = r[TELE_T_CROSS];
+        r[TELE_T_CROSS] = tc;
+        if (!isnan(prev)) {
+            const double lap = tc - prev;
+            r[TELE_LAP_LAST] = lap;
+            if (isnan(r[TELE_LAP_BEST]) || lap < r[TELE_LAP_BEST]) r[TELE_LAP_BEST] = lap;
+        }
+    }
+    if (bwd) r[TELE_LAPS] -= 1.0;
+    r[TELE_VEL_SUM] += vel;
+    if (vel > r[TELE_VEL_MAX]) r[TELE_VEL_MAX] = vel;
+    const int sel = sd.sel[p];
+    if (sel >= LTPL_ACT_STRAIGHT && sel <= LTPL_ACT_EMERGENCY) r[TELE_ACT + sel] += 1.0;
+    if (cnt > 0) {
+        if (cd < r[TELE_CLEAR_MIN]) { r[TELE_CLEAR_MIN] = cd; r[TELE_CLEAR_TICK] = (double)tick; r[TELE_CLEAR_SLOT] = (double)ci; }
+        if (cd < te.radius[p]) r[TELE_CONTACT] += 1.0;
+    }
+    te.prog[p] = te.grid_s[p] + r[TELE_DIST];
+    if (!sd.mate_lo || sd.mate_hi[p] - sd.mate_lo[p] < 2) r[TELE_RANK] = 1.0;          // alone in its race: no passes, no gap
+}
+
+// rank of planner p among the planners of its race by progress (ahead: larger, or equal and a lower planner index) and the gap to the
+// nearest one ahead. A mate that has not lived a tick stands at -inf; a failed mate stays where it stopped.
+__global__ __launch_bounds__(64) void k_fleet_sim_rank(SimDev sd, SimTele te)
+{
+    const int p = blockIdx.x, lane = threadIdx.x;
+    const int lo = sd.mate_lo[p], hi = sd.mate_hi[p];
+    if (hi - lo < 2 || !sd.live[p]) return;
+    const double mine = te.prog[p];
+    int ahead = 0;
+    double gap = INFINITY;
+    for (int b0 = lo; b0 < hi; b0 += 64) {
+        const int q = b0 + lane;
+        bool a = false;
+        if (q < hi && q != p) {
+            const double pq = te.prog[q];
+            a = pq > mine || (pq == mine && q < p);
+            if (a) { const double g = pq - mine; if (g < gap) gap = g; }
+        }
+        ahead += __popcll(__ballot(a));
+    }
+    gap = wave_min_f64(gap);
+    if (lane != 0) return;
+    double* r = te.rec + (size_t)p * LTPL_FLEET_SIM_TELE_DOUBLES;
+    const double rank = (double)(1 + ahead), prev = r[TELE_RANK];
+    if (r[TELE_TICKS] > 1.0) {
+        if (rank < prev) r[TELE_PASSES] += prev - rank;
+        else if (rank > prev) r[TELE_PASSED] += rank - prev;
+    }
+    r[TELE_RANK] = rank;
+    r[TELE_GAP] = ahead ? gap : NAN;
+}
+
 // exclusive scan of the on-track counts (one workgroup; a few hundred thousand planners at most)
 __global__ __launch_bounds__(1024) void k_fleet_sim_offsets(const int* cnt, int n, int* veh_off)
 {
@@ -317,6 +431,10 @@ struct FleetSim {
     bool ran = false;                       // ltpl_fleet_sim_run was called (ltpl_fleet_sim_race comes before it)
     int n_opp = 0, n_obj = 0;
     std::vector<int> own;                   // [N] opponents + statics of planner p
+    std::vector<void*> tele_allocs;         // race-line copies, radius, grid_s, records and progress of ltpl_fleet_sim_telemetry
+    SimTele te{};
+    bool has_tele = false;                  // k_fleet_sim_tele (and k_fleet_sim_rank with has_mates) run every tick
+    int tele_tick = 0;                      // ticks of ltpl_fleet_sim_run since the telemetry was set
 };
 static void sim_free_list(std::vector<void*>& l)
 {
@@ -331,7 +449,7 @@ struct SimAllocs {
 static void fleet_sim_free(FleetSim* s)
 {
     if (!s) return;
-    sim_free_list(s->stage_allocs); sim_free_list(s->race_allocs);
+    sim_free_list(s->stage_allocs); sim_free_list(s->race_allocs); sim_free_list(s->tele_allocs);
     for (void* p : s->allocs) (void)hipFree(p);
     if (s->velt.d_buf) (void)hipFree(s->velt.d_buf);
     delete s;
@@ -529,6 +647,14 @@ try {
             hipLaunchKernelGGL(k_fleet_sim_mates, dim3(N), dim3(64), 0, st, f->h->lat, s.sd, tr);
             FLEET_TRY(f, hipGetLastError());
         }
+        if (s.has_tele) {
+            hipLaunchKernelGGL(k_fleet_sim_tele, dim3(N), dim3(64), 0, st, s.sd, s.te, s.tele_tick++);
+            FLEET_TRY(f, hipGetLastError());
+            if (s.has_mates) {
+                hipLaunchKernelGGL(k_fleet_sim_rank, dim3(N), dim3(64), 0, st, s.sd, s.te);
+                FLEET_TRY(f, hipGetLastError());
+            }
+        }
         hipLaunchKernelGGL(k_fleet_sim_offsets, dim3(1), dim3(1024), 0, st, (const int*)s.sd.cnt, N, s.sd.veh_off);
         FLEET_TRY(f, hipGetLastError());
         hipLaunchKernelGGL(k_fleet_sim_compact, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, st, s.sd, N);
@@ -637,5 +763,79 @@ try {
     FLEET_TRY(f, hipSetDevice(f->h->device));
     FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
     FLEET_TRY(f, hipMemcpy(theta, f->sim->sd.theta, sizeof(double) * (size_t)f->D.N, hipMemcpyDeviceToHost));
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+// every argument is checked before the first HIP call
+static int sim_check_tele(ltpl_fleet* f, const ltpl_fleet_sim_tele_in* in)
+{
+    const int N = f->D.N;
+    auto bad = [&](const char* why, int code = LTPL_ERR_INVALID_ARG) { f->err = std::string("fleet sim telemetry: ") + why; return code; };
+    if (!f->sim) return bad("ltpl_fleet_sim_setup first");
+    if (!in) return LTPL_OK;
+    if (!in->radius) return bad("radius missing");
+    for (int p = 0; p < N; ++p) if (!std::isfinite(in->radius[p]) || !(in->radius[p] >= 0.0)) return bad("a radius must be finite and not negative");
+    if (in->grid_s) for (int p = 0; p < N; ++p) if (!std::isfinite(in->grid_s[p])) return bad("a grid_s must be finite");
+    const ltplp::HostLat& hl = f->h->hostlat;
+    if (!f->h->has_hostlat || hl.L < 2) return bad("the lattice carries no race line", LTPL_ERR_UNSUPPORTED);
+    // get_s_coord.py:67-68 shifts an s array that does not start at 0 by one entry; the wave-wide projection reads the array as it is
+    if (hl.s_rl[0] > 0.05) return bad("s_raceline[0] above 0.05 (the shifted s array of get_s_coord is not supported)", LTPL_ERR_UNSUPPORTED);
+    return LTPL_OK;
+}
+
+extern "C" int ltpl_fleet_sim_telemetry(ltpl_fleet* f, const ltpl_fleet_sim_tele_in* in)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    int rc = sim_check_tele(f, in);
+    if (rc) return rc;
+    if ((rc = fleet_enter(f))) return rc;
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    FleetSim& s = *f->sim;
+    if (!in) {
+        sim_free_list(s.tele_allocs);
+        s.te = SimTele{}; s.has_tele = false; s.tele_tick = 0;
+        return LTPL_OK;
+    }
+    const int N = f->D.N;
+    const ltplp::HostLat& hl = f->h->hostlat;
+    const int n = hl.L;
+    SimTele te{};
+    te.n_rl = n;
+    {
+        const double dx = hl.race_x[0] - hl.race_x[(size_t)n - 1], dy = hl.race_y[0] - hl.race_y[(size_t)n - 1];
+        te.length = hl.s_rl[(size_t)n - 1] + std::sqrt(dx * dx + dy * dy);
+    }
+    std::vector<double> rec((size_t)N * LTPL_FLEET_SIM_TELE_DOUBLES, 0.0);
+    for (int p = 0; p < N; ++p) {
+        double* r = rec.data() + (size_t)p * LTPL_FLEET_SIM_TELE_DOUBLES;
+        r[TELE_S] = r[TELE_T_CROSS] = r[TELE_LAP_LAST] = r[TELE_LAP_BEST] = r[TELE_GAP] = NAN;
+        r[TELE_VEL_MAX] = -INFINITY; r[TELE_CLEAR_MIN] = INFINITY; r[TELE_CLEAR_TICK] = r[TELE_CLEAR_SLOT] = -1.0;
+    }
+    const std::vector<double> prog((size_t)N, -INFINITY), grid_nan((size_t)N, NAN);
+    // everything new is allocated first; the fleet keeps its previous telemetry unless every step succeeds
+    SimAllocs a;
+    double* pd = nullptr;
+#define SIM_UP(dst, src, cnt) do { if ((rc = sim_upload(f, a.p, src, (size_t)(cnt), &dst))) return rc; } while (0)
+    SIM_UP(pd, hl.race_x.data(), n); te.rl_x = pd; SIM_UP(pd, hl.race_y.data(), n); te.rl_y = pd; SIM_UP(pd, hl.s_rl.data(), n); te.rl_s = pd;
+    SIM_UP(pd, in->radius, N); te.radius = pd;
+    SIM_UP(te.grid_s, in->grid_s ? in->grid_s : grid_nan.data(), N);
+    SIM_UP(te.rec, rec.data(), rec.size()); SIM_UP(te.prog, prog.data(), N);
+#undef SIM_UP
+    sim_free_list(s.tele_allocs);
+    s.tele_allocs.swap(a.p);
+    s.te = te; s.has_tele = true; s.tele_tick = 0;
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+extern "C" int ltpl_fleet_sim_telemetry_read(ltpl_fleet* f, double* out, int32_t doubles_per_planner, double* track_length)
+try {
+    if (!f || !out) return LTPL_ERR_INVALID_ARG;
+    if (!f->sim) { f->err = "fleet sim telemetry: ltpl_fleet_sim_setup first"; return LTPL_ERR_INVALID_ARG; }
+    if (!f->sim->has_tele) { f->err = "fleet sim telemetry: telemetry is off (ltpl_fleet_sim_telemetry first)"; return LTPL_ERR_INVALID_ARG; }
+    if (doubles_per_planner != LTPL_FLEET_SIM_TELE_DOUBLES) { f->err = "fleet sim telemetry: record size mismatch"; return LTPL_ERR_INVALID_ARG; }
+    FLEET_TRY(f, hipSetDevice(f->h->device));
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    FLEET_TRY(f, hipMemcpy(out, f->sim->te.rec, sizeof(double) * (size_t)f->D.N * LTPL_FLEET_SIM_TELE_DOUBLES, hipMemcpyDeviceToHost));
+    if (track_length) *track_length = f->sim->te.length;
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))

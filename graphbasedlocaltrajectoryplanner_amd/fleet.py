@@ -14,6 +14,7 @@ import numpy as np
 
 from . import _capi
 from .planner import KEY_IDS, Planner, PlannerPathsIn, PlannerVelIn
+from .sim import TELEMETRY_DOUBLES, TELEMETRY_FIELDS, telemetry_dict      # noqa: F401  (published here: fleet.TELEMETRY_FIELDS)
 
 
 class SimIn(C.Structure):                 # ltpl_fleet_sim_in (pointer members as plain addresses)
@@ -35,6 +36,10 @@ class FrictionIn(C.Structure):            # ltpl_fleet_friction_in
     _fields_ = [("n_maps", C.c_int32), ("x0", C.c_void_p), ("y0", C.c_void_p), ("dx", C.c_void_p), ("dy", C.c_void_p),
                 ("nx", C.c_void_p), ("ny", C.c_void_p), ("node_off", C.c_void_p), ("nodes", C.c_void_p),
                 ("map_idx", C.c_void_p), ("scale", C.c_void_p)]
+
+
+class SimTeleIn(C.Structure):             # ltpl_fleet_sim_tele_in
+    _fields_ = [("radius", C.c_void_p), ("grid_s", C.c_void_p)]
 
 
 SIM_TRACE_DOUBLES = 8 + 8 + 9 * _capi.PLANNER_MAX_KEYS     # LTPL_FLEET_SIM_TRACE_DOUBLES
@@ -62,6 +67,9 @@ class Fleet(Planner):
         if hasattr(self.lib, "ltpl_fleet_sim_race"):
             f("sim_race").argtypes = [C.c_void_p, C.POINTER(SimRaceIn)]
             f("sim_heading").argtypes = [C.c_void_p, C.c_void_p]
+        if hasattr(self.lib, "ltpl_fleet_sim_telemetry"):
+            f("sim_telemetry").argtypes = [C.c_void_p, C.POINTER(SimTeleIn)]
+            f("sim_telemetry_read").argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_double)]
         if hasattr(self.lib, "ltpl_fleet_friction"):
             f("friction").argtypes = [C.c_void_p, C.POINTER(FrictionIn)]
             f("friction_scale").argtypes = [C.c_void_p, C.c_void_p]
@@ -351,6 +359,33 @@ class Fleet(Planner):
         out = np.zeros(self.n_scen, np.float64)
         self._check(self._fn("sim_heading")(self.handle, out.ctypes.data))
         return out
+
+    # ---- race telemetry on the device ---------------------------------------------------------------------------------------------
+    def sim_telemetry(self, radius=2.5, grid_s=None):
+        """(Re)starts the race telemetry of the following ``sim_run`` calls (ltpl_fleet_sim_telemetry; after ``sim_setup``, between runs
+        at any time): a record per planner, accumulated on the device in every tick the planner is live. ``radius``: contact radius
+        (scalar or one per planner; None switches the telemetry off); ``grid_s``: progress offset of every planner (default: s of its
+        first live tick; hand it in for grids that straddle the start line)."""
+        if radius is None:
+            self._check(self._fn("sim_telemetry")(self.handle, None))
+            return
+        n = self.n_scen
+        rad = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float64), (n,)))
+        ti = SimTeleIn()
+        ti.radius, ti.grid_s = rad.ctypes.data, None
+        if grid_s is not None:
+            gs = np.ascontiguousarray(np.broadcast_to(np.asarray(grid_s, np.float64), (n,)))
+            ti.grid_s = gs.ctypes.data
+        self._check(self._fn("sim_telemetry")(self.handle, C.byref(ti)))
+
+    def sim_telemetry_read(self):
+        """The records as they stand (ltpl_fleet_sim_telemetry_read; accumulation goes on): dict of named arrays, one entry per planner
+        (``TELEMETRY_FIELDS``: counts as int64, ``act`` [n, 5] in the order straight, follow, left, right, emergency), plus
+        ``track_length``, the closed length of the race line. BackendError while the telemetry is off."""
+        out = np.zeros((self.n_scen, TELEMETRY_DOUBLES), np.float64)
+        length = C.c_double(0.0)
+        self._check(self._fn("sim_telemetry_read")(self.handle, out.ctypes.data, TELEMETRY_DOUBLES, C.byref(length)))
+        return telemetry_dict(out, float(length.value))
 
     # ---- friction maps on the device ------------------------------------------------------------------------------------------------
     def friction(self, maps, map_idx=None, scale=1.0):

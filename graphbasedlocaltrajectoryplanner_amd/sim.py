@@ -15,7 +15,11 @@ and of the races of ``ltpl_fleet_sim_race`` (planners of one fleet that see one 
   ``peer_heading``   the heading of the tracked pose: psi of the same trajectory at that arc length and segment, across the +-pi wrap;
   ``race_objects``   the object dicts the mates of one planner contribute to its object list.
 
-Both restate ``np.interp`` (numpy's ``arr_interp``) in the operation order of the device functions (``interp_at`` here,
+and of the race telemetry of ``ltpl_fleet_sim_telemetry`` (a record per planner, accumulated on the device) --
+
+  ``Telemetry``      the rules of include/ltpl_hip.h in the operation order of k_fleet_sim_tele / k_fleet_sim_rank.
+
+Both simulators restate ``np.interp`` (numpy's ``arr_interp``) in the operation order of the device functions (``interp_at`` here,
 ``fleet::sim_interp`` there), so that host and device give the same bits as the reference.
 """
 import bisect
@@ -174,3 +178,141 @@ def race_objects(p, race, pos, vel, theta, length, id0=100):
     order. They follow the planner's opponents and static objects."""
     return [{'X': float(pos[q][0]), 'Y': float(pos[q][1]), 'theta': float(theta[q]), 'type': 'physical', 'id': id0 + int(q),
              'length': float(length[q]), 'v': float(vel[q])} for q in sorted(race) if q != p]
+
+
+# name, first index, doubles, integer valued: the record of ltpl_fleet_sim_telemetry (LTPL_FLEET_SIM_TELE_DOUBLES = 22 per planner)
+TELEMETRY_FIELDS = (("ticks", 0, 1, True), ("s", 1, 1, False), ("dist", 2, 1, False), ("laps", 3, 1, True), ("t_cross", 4, 1, False),
+                    ("lap_last", 5, 1, False), ("lap_best", 6, 1, False), ("vel_sum", 7, 1, False), ("vel_max", 8, 1, False),
+                    ("act", 9, 5, True), ("clear_min", 14, 1, False), ("clear_tick", 15, 1, True), ("clear_slot", 16, 1, True),
+                    ("contact_ticks", 17, 1, True), ("rank", 18, 1, True), ("passes", 19, 1, True), ("passed", 20, 1, True),
+                    ("gap_ahead", 21, 1, False))
+TELEMETRY_DOUBLES = 22
+_ACT_INDEX = {"straight": 0, "follow": 1, "left": 2, "right": 3, "emergency": 4}
+
+
+def closed_length(raceline, s_raceline):
+    """Closed length of a race line (one point per layer): ``s_raceline[-1]`` plus the distance from the last point back to the first."""
+    dx, dy = float(raceline[0][0]) - float(raceline[-1][0]), float(raceline[0][1]) - float(raceline[-1][1])
+    return float(s_raceline[-1]) + math.sqrt(dx * dx + dy * dy)
+
+
+def telemetry_dict(rows, track_length=None):
+    """[n, 22] records as a dict of named arrays (integer valued fields as int64, ``act`` as [n, 5])."""
+    rows = np.asarray(rows, np.float64).reshape(-1, TELEMETRY_DOUBLES)
+    out = {}
+    for name, i, cnt, is_int in TELEMETRY_FIELDS:
+        a = rows[:, i] if cnt == 1 else rows[:, i:i + cnt]
+        out[name] = a.astype(np.int64) if is_int else a.copy()
+    if track_length is not None:
+        out["track_length"] = float(track_length)
+    return out
+
+
+class Telemetry(object):
+    """Host mirror of the fleet's race telemetry (ltpl_fleet_sim_telemetry; k_fleet_sim_tele / k_fleet_sim_rank in csrc/fleet_sim.hpp): the
+    rules of include/ltpl_hip.h in the same order of fp64 operations. ``races``: sizes summing to ``n`` (or ranges of consecutive planners);
+    ``radius`` / ``grid_s``: scalars or one value per planner (``grid_s`` None: s of the first live tick); ``s_of``: any callable
+    pos -> s on the race line; ``track_length``: its closed length (``closed_length``)."""
+
+    def __init__(self, n, races, radius, track_length, s_of, dt, grid_s=None):
+        self.n, self.L, self.s_of, self.dt = int(n), float(track_length), s_of, float(dt)
+        sizes = [len(r) if isinstance(r, range) else int(r) for r in races]
+        if sum(sizes) != self.n:
+            raise ValueError("Telemetry: the races must cover the planners")
+        self.lo, self.hi = [0] * self.n, [0] * self.n
+        a = 0
+        for sz in sizes:
+            for p in range(a, a + sz):
+                self.lo[p], self.hi[p] = a, a + sz
+            a += sz
+        self.radius = [float(v) for v in np.broadcast_to(np.asarray(radius, np.float64), (self.n,))]
+        self.grid = [float("nan")] * self.n if grid_s is None else [float(v) for v in np.broadcast_to(np.asarray(grid_s, np.float64), (self.n,))]
+        self.prog = [-math.inf] * self.n
+        r = np.zeros((self.n, TELEMETRY_DOUBLES), np.float64)
+        r[:, [1, 4, 5, 6, 21]] = np.nan
+        r[:, 8], r[:, 14], r[:, 15], r[:, 16] = -np.inf, np.inf, -1.0, -1.0
+        self.rec = r
+
+    def update(self, tick_index, recs):
+        """One fleet tick: ``recs`` = one dict per planner with ``live``, ``sel`` (action name or id), ``now``, ``pos``, ``vel`` and
+        ``objects`` = [(x, y, radius), ...] in list order (a planner that is not live needs ``live`` only)."""
+        L, rec = self.L, self.rec
+        for p, d in enumerate(recs):
+            if not d["live"]:
+                continue
+            r = rec[p]
+            px, py = float(d["pos"][0]), float(d["pos"][1])
+            s = float(self.s_of((px, py)))
+            cd, ci = math.inf, -1
+            for k, (ox, oy, orad) in enumerate(d["objects"]):
+                dx, dy = float(ox) - px, float(oy) - py
+                c = math.sqrt(dx * dx + dy * dy) - float(orad)
+                if c < cd:
+                    cd, ci = c, k
+            delta, fwd, bwd = 0.0, False, False
+            if r[0] == 0.0:
+                if math.isnan(self.grid[p]):
+                    self.grid[p] = s
+            else:
+                delta = s - float(r[1])
+                if delta < -(L / 2):
+                    delta, fwd = delta + L, True
+                elif delta > L / 2:
+                    delta, bwd = delta - L, True
+            r[0] += 1.0
+            r[1] = s
+            r[2] += delta
+            now, vel = float(d["now"]), float(d["vel"])
+            if fwd:
+                r[3] += 1.0
+                tc = now - self.dt * (s / delta) if delta > 0.0 else now
+                prev = float(r[4])
+                r[4] = tc
+                if not math.isnan(prev):
+                    lap = tc - prev
+                    r[5] = lap
+                    if math.isnan(r[6]) or lap < r[6]:
+                        r[6] = lap
+            if bwd:
+                r[3] -= 1.0
+            r[7] += vel
+            if vel > r[8]:
+                r[8] = vel
+            sel = d["sel"]
+            sel = _ACT_INDEX.get(sel, -1) if isinstance(sel, str) else int(sel)
+            if 0 <= sel <= 4:
+                r[9 + sel] += 1.0
+            if len(d["objects"]) > 0:
+                if cd < r[14]:
+                    r[14], r[15], r[16] = cd, float(tick_index), float(ci)
+                if cd < self.radius[p]:
+                    r[17] += 1.0
+            self.prog[p] = self.grid[p] + float(r[2])
+            if self.hi[p] - self.lo[p] < 2:
+                r[18] = 1.0
+        for p, d in enumerate(recs):                      # every planner's progress of the tick is known: rank and gap
+            lo, hi = self.lo[p], self.hi[p]
+            if hi - lo < 2 or not d["live"]:
+                continue
+            r, mine = rec[p], self.prog[p]
+            ahead, gap = 0, math.inf
+            for q in range(lo, hi):
+                if q != p and (self.prog[q] > mine or (self.prog[q] == mine and q < p)):
+                    ahead += 1
+                    g = self.prog[q] - mine
+                    if g < gap:
+                        gap = g
+            rank, prev = float(1 + ahead), float(r[18])
+            if r[0] > 1.0:
+                if rank < prev:
+                    r[19] += prev - rank
+                elif rank > prev:
+                    r[20] += rank - prev
+            r[18] = rank
+            r[21] = gap if ahead else float("nan")
+
+    def rows(self):
+        return self.rec.copy()
+
+    def as_dict(self):
+        return telemetry_dict(self.rec, self.L)

@@ -780,6 +780,56 @@ int ltpl_fleet_friction_scale(ltpl_fleet* fleet, const double* scale);
  * and which therefore must be positive. */
 int ltpl_fleet_friction_rows(ltpl_fleet* fleet, int32_t map, const double* x, const double* y, int32_t n_pts, double scale, double* out);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Additive to ABI v9 -- RACE TELEMETRY accumulated on the device: what happened in a simulated race, without the trace. Every planner
+ * has a record of LTPL_FLEET_SIM_TELE_DOUBLES doubles, updated by ltpl_fleet_sim_run in every tick in which the planner is live (no error
+ * word, an action found), after its tracker and after its mates were appended (csrc/fleet_sim.hpp: k_fleet_sim_tele, one wave64 per
+ * planner; k_fleet_sim_rank for races with more than one planner). The reference logs the first of these numbers per tick itself:
+ * s_coord = get_s_coord(raceline, pos_est, s_raceline, closed=True) (Graph_LTPL.py:436-440).
+ *   L       = s_raceline[last] + sqrt(dx * dx + dy * dy), dx, dy = raceline[0] - raceline[last]: the closed length of the lattice's race line
+ *   s(x, y) = what ltpl_raceline_s returns (the wave-wide projection of the device code; a lattice whose s_raceline[0] exceeds 0.05 --
+ *             get_s_coord.py:67-68 shifts such an array -- is refused with LTPL_ERR_UNSUPPORTED)
+ * The update reads the tracked pose, vel_est, the selected action and t_now of the tick, and the on-track objects the planner is handed
+ * this tick (own position and radius; the predictions are not used). Fields, "before the first tick" value in brackets:
+ *   [0]  ticks         live ticks accumulated [0]
+ *   [1]  s             s(pos) of the last live tick [NaN]
+ *   [2]  dist          sum of d = s_k - s_(k-1) (first live tick: 0); d < -L/2: d += L and a forward crossing; d > L/2: d -= L and a
+ *                      backward crossing [0]
+ *   [3]  laps          forward minus backward crossings [0]
+ *   [4]  t_cross       time of the last forward crossing: t_now - dt * (s_k / d) with the wrapped d; t_now if !(d > 0) [NaN]
+ *   [5]  lap_last      t_cross minus the previous t_cross [NaN until there are two]
+ *   [6]  lap_best      smallest lap_last [NaN]
+ *   [7]  vel_sum       sum of vel_est over the live ticks [0]         [8] vel_max  their maximum [-inf]
+ *   [9 .. 13] act[5]   live ticks with the selected action LTPL_ACT_STRAIGHT / FOLLOW / LEFT / RIGHT / EMERGENCY [0]
+ *   [14] clear_min     smallest sqrt(dx * dx + dy * dy) - radius of the object over all live ticks and all objects of the tick [+inf]
+ *   [15] clear_tick    fleet tick index (ticks of ltpl_fleet_sim_run since the telemetry was set) and
+ *   [16] clear_slot    list position at which clear_min was set: replaced only on a strictly smaller value, within a tick the first
+ *                      smallest counts [-1]
+ *   [17] contact_ticks live ticks in which the tick's smallest clearance is < radius[p] [0]
+ *   [18] rank          1 + the number of planners q of p's race that are ahead: prog[q] > prog[p], or equal and q < p, with
+ *                      prog = grid_s + dist. A mate that has not lived a tick is behind everybody; a failed mate stays where it stopped
+ *                      [0; a planner alone in its race: 1 from its first live tick on]
+ *   [19] passes        sum of the rank's decreases and  [20] passed  of its increases from one live tick to the next [0]
+ *   [21] gap_ahead     prog[q] - prog[p] of the nearest q ahead [NaN; NaN for the leader]
+ * Everything is fp64, + - * / and sqrt only, in the order written here (host mirror: sim.Telemetry). Ranks are per race; a race never
+ * crosses a shard. A fleet without telemetry launches exactly the kernels it launches without this feature.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define LTPL_FLEET_SIM_TELE_DOUBLES 22
+typedef struct {
+    const double* radius;   /* [n] contact radius of planner p, finite >= 0 */
+    const double* grid_s;   /* [n] or NULL: s of the first live tick        */
+} ltpl_fleet_sim_tele_in;
+
+/* (re)starts the telemetry with every record at its "before the first tick" values; in == NULL switches it off. After ltpl_fleet_sim_setup
+ * (which switches it off) at any time between runs, also after ltpl_fleet_sim_race. Every argument is checked before the first HIP call
+ * (no simulation, NaN / infinite / negative radius, non-finite grid_s: LTPL_ERR_INVALID_ARG); everything new is allocated before anything
+ * old is freed: a failing call keeps the previous telemetry. */
+int ltpl_fleet_sim_telemetry(ltpl_fleet* fleet, const ltpl_fleet_sim_tele_in* in);
+/* synchronises the handle's stream and copies the records out: out [n][doubles_per_planner] with doubles_per_planner ==
+ * LTPL_FLEET_SIM_TELE_DOUBLES; track_length (may be NULL): L. Accumulation goes on undisturbed. No simulation, a wrong record size or
+ * telemetry off: LTPL_ERR_INVALID_ARG. */
+int ltpl_fleet_sim_telemetry_read(ltpl_fleet* fleet, double* out, int32_t doubles_per_planner, double* track_length /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,11 +1,12 @@
 """Closed-loop SIMULATION rate of a fleet (ltpl_fleet_sim_*): N planners, each with its own eight C2-style race-line opponents (SURVEY.md
 section 8d: s0_k = 250 + 280 k, vel_scale_k = 0.30 + 0.05 (k mod 4), here staggered by 10 m (p mod 16) per planner), run the example
 driver's loop on the device for T ticks without host work per tick.   tools/sim_rate.py [--planners 32768] [--ticks 200] [--no-tape]
-[--race-size K] [--friction-map] [--lib PATH]. Prints planner-ticks per second of sim_run (device time of the run) next to tape_run on the C2 tape (recorded inputs,
+[--race-size K] [--friction-map] [--telemetry] [--lib PATH]. Prints planner-ticks per second of sim_run (device time of the run) next to tape_run on the C2 tape (recorded inputs,
 tools/fleet_rate.py). --race-size K > 1: races of K consecutive planners (ltpl_fleet_sim_race) that see one another, started 30 m apart
 along the race line with its heading; K = 1 (default) is the run without races. --friction-map: the same fleet on the friction grid of
 tests/golden/friction_grid.npz (ltpl_fleet_friction: rows evaluated on the device, grip factors 1.0 .. 0.7 over the planners) instead of
-the constant tuple. --lib PATH: another build of the library (A/B against the parent's)."""
+the constant tuple. --telemetry: race telemetry on (ltpl_fleet_sim_telemetry, contact radius 2.5: k_fleet_sim_tele every tick, k_fleet_sim_rank
+with races); the records of the first planners are printed after the run. --lib PATH: another build of the library (A/B against the parent's)."""
 import argparse
 import os
 import sys
@@ -30,6 +31,7 @@ def main():
     ap.add_argument("--no-tape", action="store_true", help="skip the tape_run comparison on the C2 recording")
     ap.add_argument("--race-size", type=int, default=1, help="planners per race (1: no races)")
     ap.add_argument("--friction-map", action="store_true", help="every planner on the friction grid, own grip factor")
+    ap.add_argument("--telemetry", action="store_true", help="race telemetry on (radius 2.5); prints the first planners' records")
     ap.add_argument("--lib", default=None, help="path of the library to load (default: the in-tree build)")
     a = ap.parse_args()
     lat = Lattice.load(os.path.join(ROOT, "tests", "golden", "monteblanco_lattice.npz"))
@@ -70,6 +72,8 @@ def main():
             fleet.friction(grid, scale=1.0 - 0.3 * (np.arange(n) % 16) / 15.0)
         fleet.sim_vel(vel_max=va['vel_max'], gg_scale=va['gg_scale'], local_gg=tuple(va['local_gg']), safety_d=va['safety_d'],
                       ax_max_machines=va['ax_max_machines'])
+        if a.telemetry:
+            fleet.sim_telemetry(radius=2.5)
         t0 = time.perf_counter()
         failed = 0
         try:
@@ -85,6 +89,15 @@ def main():
         if failed == 0:
             sel = np.bincount(fleet.sim_state()['sel_action'] + 1, minlength=6)
             print("  last selected actions (none, straight, follow, left, right, emergency): %s" % sel.tolist())
+        if a.telemetry and rep == a.reps - 1:
+            d = fleet.sim_telemetry_read()
+            print("  telemetry (track length %.3f m), planners 0 .. %d:" % (d["track_length"], min(n, max(K, 4)) - 1))
+            for p in range(min(n, max(K, 4))):
+                print("    %d: ticks %d s %.2f dist %.2f laps %d vel mean %.2f max %.2f act %s clear_min %.3f (tick %d, slot %d) contact %d "
+                      "rank %d passes %d passed %d gap %.2f" % (p, d["ticks"][p], d["s"][p], d["dist"][p], d["laps"][p],
+                                                                d["vel_sum"][p] / max(d["ticks"][p], 1), d["vel_max"][p], d["act"][p].tolist(),
+                                                                d["clear_min"][p], d["clear_tick"][p], d["clear_slot"][p], d["contact_ticks"][p],
+                                                                d["rank"][p], d["passes"][p], d["passed"][p], d["gap_ahead"][p]))
         fleet.close()
     print("closed_loop_sim_ticks_per_s %.0f" % (n * a.ticks / best * 1e3))
     if a.no_tape or grid is not None:
