@@ -4790,6 +4790,40 @@ try {
     (void)hipFree(d);
     return rc;
 } LTPL_ABI_CATCH(nullptr)
+// experiment build only: fast_rcp (reciprocals of the spline solve and of the re-sampling parameter) / rsqrt_cubed (curvature of a path
+// sample) for n caller-provided values (host memory)
+__global__ void k_exp_fast_rcp(const double* x, double* out, int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = fast_rcp(x[i]);
+}
+__global__ void k_exp_rsqrt_cubed(const double* x, double* out, int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = rsqrt_cubed(x[i]);
+}
+static int exp_unary(int32_t device, const double* x, double* out, int32_t n, bool cubed)
+{
+    if (!x || !out || n <= 0) return LTPL_ERR_INVALID_ARG;
+    if (hipSetDevice(device) != hipSuccess) return LTPL_ERR_HIP;
+    double* d = nullptr;
+    int rc = LTPL_OK;
+    const size_t b = sizeof(double) * (size_t)n;
+    if (hipMalloc(&d, 2 * b) != hipSuccess) return LTPL_ERR_HIP;
+    if (hipMemcpy(d, x, b, hipMemcpyHostToDevice) != hipSuccess) rc = LTPL_ERR_HIP;
+    if (!rc) {
+        const dim3 grid((unsigned)((n + 255) / 256));
+        if (cubed) hipLaunchKernelGGL(k_exp_rsqrt_cubed, grid, dim3(256), 0, 0, d, d + n, n);
+        else hipLaunchKernelGGL(k_exp_fast_rcp, grid, dim3(256), 0, 0, d, d + n, n);
+        if (hipGetLastError() != hipSuccess || hipMemcpy(out, d + n, b, hipMemcpyDeviceToHost) != hipSuccess) rc = LTPL_ERR_HIP;
+    }
+    (void)hipFree(d);
+    return rc;
+}
+extern "C" int ltpl_exp_fast_rcp(int32_t device, const double* x, double* out, int32_t n)
+try { return exp_unary(device, x, out, n, false); } LTPL_ABI_CATCH(nullptr)
+extern "C" int ltpl_exp_rsqrt_cubed(int32_t device, const double* x, double* out, int32_t n)
+try { return exp_unary(device, x, out, n, true); } LTPL_ABI_CATCH(nullptr)
 #endif
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -42,6 +42,9 @@
  * Timing / fault-injection switches (LTPL_ABLATE, LTPL_EXP_SKIP, LTPL_LDS_POISON, LTPL_SCRATCH_POISON, LTPL_DEBUG_TIMING,
  * LTPL_DEBUG_OCC) skip work, overwrite memory or instrument kernels; they are compiled into the EXPERIMENT build only
  * (-DLTPL_EXPERIMENT -> libltpl_hip_exp.so, used by tools/ and one fault-injection test) and do not exist in libltpl_hip.so.
+ * The experiment build also exports the check entry points of tests/test_gpu_wave_ops.py (host arrays in, one launch, host arrays out):
+ * ltpl_exp_wave_ops_check, ltpl_exp_heading_atan2, ltpl_exp_heading_sincos, ltpl_exp_fast_rcp, ltpl_exp_rsqrt_cubed -- the device
+ * helpers of csrc/paths_team.hpp applied to caller-provided values.
  */
 #ifndef LTPL_HIP_H
 #define LTPL_HIP_H

@@ -238,36 +238,86 @@ def test_tick_paths_equal_plan_paths(monteblanco, hip_backend):
         assert np.array_equal(getattr(res, name), getattr(res1, name)), name
 
 
+def compact_inputs(lat, n):
+    from scenarios import random_scenarios
+    scen, vels = random_scenarios(lat, n, seed=31 + n)
+    batch = _capi.PathsBatch(scen, w_last_edges=[0.0, 0.5, 0.8])
+    params = _capi.VelParamSet(len_veh=lat.veh_length)
+    pos = np.array([lat.node_pos[lat.layer_off[s['start_node'][0]] + s['start_node'][1]] for s in scen])
+    return batch, _capi.TickVelBatch(params, n, np.full(n, 25.0), np.full(n, 25.0), pos, np.concatenate(vels))
+
+
+def check_compact_against_slabs(lat, hip_backend, n, max_rows=115, s_bound=None):
+    """One batch of ``n`` scenarios through ltpl_tick_batch and ltpl_tick_batch_compact. ``s_bound``: the s column also against a long-double
+    running sum, relative to its last value. Returns (slab results, compact result)."""
+    batch, vel = compact_inputs(lat, n)
+    res, vres = hip_backend.tick_batch(batch, vel)
+    comp = hip_backend.new_compact_trajectories(n, max_rows=max_rows)
+    hip_backend.tick_batch_compact(batch, vel, comp)
+    cut = max_rows if max_rows > 0 else hip_backend.caps.max_path_pts
+    assert comp.struct.total_rows == int(np.minimum(res.n_pts * res.valid, cut).sum())
+    for s in range(n):
+        tr = comp.trajectories(s)
+        names = [_capi.ACTION_NAMES[int(res.action_id[s, a])] for a in range(int(res.n_actions[s])) if res.valid[s, a]]
+        assert list(tr.keys()) == names
+        for a in range(int(res.n_actions[s])):
+            if not res.valid[s, a]:
+                continue
+            m = min(int(res.n_pts[s, a]), cut)
+            t = tr[_capi.ACTION_NAMES[int(res.action_id[s, a])]][0]
+            assert t.shape == (m, 7)
+            assert np.array_equal(t[:, 1:5], res.path_param[s, a, :m, 0:4])
+            assert np.array_equal(t[:, 5], vres.vx[s, a, :m]) and np.array_equal(t[:, 6], vres.ax[s, a, :m])
+            s_ref = np.concatenate(([0.0], np.cumsum(res.path_param[s, a, :m - 1, 4])))
+            assert_close_rel(t[:, 0], s_ref, what="s column")
+            if s_bound is not None:
+                s_ld = np.concatenate(([np.longdouble(0)], np.cumsum(res.path_param[s, a, :m - 1, 4].astype(np.longdouble))))
+                err = float(np.max(np.abs(t[:, 0].astype(np.longdouble) - s_ld)))
+                assert err <= s_bound * float(s_ld[-1]), "s column of scenario %d slot %d: %.3e > %.1e * %.3f" % (s, a, err, s_bound, float(s_ld[-1]))
+            assert comp.vel_bound[s * 3 + a] == vres.vel_bound[s, a] and comp.reduced[s * 3 + a] == res.reduced[s, a]
+    return res, vres, comp
+
+
 def test_compact_trajectories_equal_the_slab_outputs(monteblanco, hip_backend):
     """ltpl_tick_batch_compact packs exactly the rows ltpl_tick_batch returns (trimmed to max_rows), for a batch on the
     one-wave pipeline and for a small batch on the fused kernel; s is the running sum of the element lengths (OTH.py:743)."""
-    from scenarios import random_scenarios
-    lat = monteblanco
     for n in (96, 5):
-        scen, vels = random_scenarios(lat, n, seed=31 + n)
-        batch = _capi.PathsBatch(scen, w_last_edges=[0.0, 0.5, 0.8])
-        params = _capi.VelParamSet(len_veh=lat.veh_length)
-        pos = np.array([lat.node_pos[lat.layer_off[s['start_node'][0]] + s['start_node'][1]] for s in scen])
-        vel = _capi.TickVelBatch(params, n, np.full(n, 25.0), np.full(n, 25.0), pos, np.concatenate(vels))
-        res, vres = hip_backend.tick_batch(batch, vel)
-        comp = hip_backend.new_compact_trajectories(n, max_rows=115)
-        hip_backend.tick_batch_compact(batch, vel, comp)
-        assert comp.struct.total_rows == int(np.minimum(res.n_pts * res.valid, 115).sum())
-        for s in range(n):
-            tr = comp.trajectories(s)
-            names = [_capi.ACTION_NAMES[int(res.action_id[s, a])] for a in range(int(res.n_actions[s])) if res.valid[s, a]]
-            assert list(tr.keys()) == names
-            for a in range(int(res.n_actions[s])):
-                if not res.valid[s, a]:
-                    continue
-                m = min(int(res.n_pts[s, a]), 115)
-                t = tr[_capi.ACTION_NAMES[int(res.action_id[s, a])]][0]
-                assert t.shape == (m, 7)
-                assert np.array_equal(t[:, 1:5], res.path_param[s, a, :m, 0:4])
-                assert np.array_equal(t[:, 5], vres.vx[s, a, :m]) and np.array_equal(t[:, 6], vres.ax[s, a, :m])
-                s_ref = np.concatenate(([0.0], np.cumsum(res.path_param[s, a, :m - 1, 4])))
-                assert_close_rel(t[:, 0], s_ref, what="s column")
-                assert comp.vel_bound[s * 3 + a] == vres.vel_bound[s, a] and comp.reduced[s * 3 + a] == res.reduced[s, a]
+        check_compact_against_slabs(monteblanco, hip_backend, n)
+
+
+@pytest.mark.parametrize("max_rows", (115, 0))
+@pytest.mark.parametrize("n", (341, 342, 700))
+def test_compact_trajectories_with_several_slots_per_thread_of_the_offset_scan(monteblanco, hip_backend, n, max_rows):
+    """k_compact_offsets is ONE block of 1024 threads, each of which owns ceil(slots / 1024) consecutive slots: 341, 342 and 700 scenarios
+    are 1023, 1026 and 2100 slots -- one, two and three slots per thread, with trailing threads that own fewer or none (the 96- and
+    5-scenario batches above give every thread at most one). With trimming to 115 rows and without (max_rows = 0). The s column is held
+    against a long-double running sum at 1e-13 of its last value: at most ~150 additions, each half an ulp of the running sum, give
+    <= 150 * 1.1e-16 = 2e-14."""
+    res, _, comp = check_compact_against_slabs(monteblanco, hip_backend, n, max_rows=max_rows, s_bound=1e-13)
+    assert 3 * n == {341: 1023, 342: 1026, 700: 2100}[n]
+    rows = res.n_pts * res.valid
+    assert int(rows.max()) > 115 and int((rows == 0).sum()) > 0          # trimming bites; empty slots lie between the kept ones
+    assert int(comp.n_rows.max()) == (115 if max_rows else int(rows.max()))
+    kept = comp.n_rows > 0
+    assert np.array_equal(comp.row_off[kept], (np.cumsum(comp.n_rows) - comp.n_rows)[kept])      # back to back, in slot order
+
+
+def test_compact_capacity_one_row_short_is_refused_and_the_backend_stays_usable(monteblanco, hip_backend):
+    n = 342
+    batch, vel = compact_inputs(monteblanco, n)
+    full = hip_backend.new_compact_trajectories(n, max_rows=115)
+    hip_backend.tick_batch_compact(batch, vel, full)
+    need = int(full.struct.total_rows)
+    assert need > 115
+    short = hip_backend.new_compact_trajectories(n, max_rows=115, capacity_rows=need - 1)
+    with pytest.raises(_capi.BackendError, match="capacity_rows"):
+        hip_backend.tick_batch_compact(batch, vel, short)
+    assert int(short.struct.total_rows) == need                           # the need, for the caller's next attempt
+    again = hip_backend.new_compact_trajectories(n, max_rows=115, capacity_rows=need)
+    hip_backend.tick_batch_compact(batch, vel, again)                     # exactly enough; the backend serves the next call
+    assert int(again.struct.total_rows) == need
+    assert np.array_equal(again.n_rows, full.n_rows) and np.array_equal(again.row_off, full.row_off)
+    assert np.array_equal(again.rows[:need], full.rows[:need])
 
 
 def test_follow_jobs_finished_by_the_lane_kernel_or_by_the_final_kernel(monteblanco, hip_backend, monkeypatch):
