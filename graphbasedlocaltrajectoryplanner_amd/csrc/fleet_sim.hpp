@@ -17,6 +17,9 @@
 //                        launch: every planner's progress of the tick is written first
 //   k_fleet_sim_offsets  exclusive scan of the on-track counts -> veh_off (one workgroup)
 //   k_fleet_sim_compact  survivors into the fleet's object layout (one lane per planner)
+//   k_fleet_sim_rec_paths / k_fleet_sim_rec_vel   (flight recorder on only: ltpl_fleet_sim_record) one wave64 per RECORDED planner: the
+//                        tick's paths behind paths_post, and its head, objects and trajectories behind the last velocity kernel, into
+//                        the planner's record of ring slot tick % depth. The tick then takes the unfused launch sequence
 //   then paths_pre | path kernel | paths_post (+ vel_a) | velocity stages as in ltpl_fleet_tape_run. Tick k + 1's inputs depend on tick k's
 //   trajectories, so the tape's "next paths_pre inside the last kernel" fusion does not apply: paths_pre is launched on its own.
 // The host mirrors of the same arithmetic are graphbasedlocaltrajectoryplanner_amd/sim.py.
@@ -382,6 +385,139 @@ __global__ __launch_bounds__(64) void k_fleet_sim_rank(SimDev sd, SimTele te)
     r[TELE_GAP] = ahead ? gap : NAN;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// flight recorder (ltpl_fleet_sim_record, include/ltpl_hip.h): for M chosen planners a full record of every tick, kept in a ring of
+// `depth` ticks. Record of (tick, recorded planner m): `stride` doubles at ring + ((tick % depth) M + m) stride --
+//   head, REC_HEAD doubles (integers as exact doubles):
+//     [0] fleet tick since the recorder was set  [1] planner  [2] error word (PlannerS::err)  [3] selected action  [4] t_now
+//     [5] [6] tracked pose x, y  [7] vel_est  [8] heading  [9] objects handed to the planner
+//     [10] cut_index_pos  [11] cut_layer  [12] vel_plan  [13] acc_plan  [14] trajectory keys  [15] id pairs
+//     [16 + 3 k ..] trajectory key k: key id, trajectory id, rows (untrimmed)        [28 + 2 k ..] id pair k: key id, id value
+//     [36] [37] start node (layer, node; -1: none)  [38] const_rows (-1: None)  [39] closest_obj_index (-1: None)  [40] path keys
+//     [41 + 4 k ..] path key k: key id, n_rows, n_nodes, red_len                      [57 .. 63] zero
+//   objects  [6][96]  column-major: radius, velocity, x, y, predicted x, predicted y of object i at [c][i], list order
+//   const    [2][R]   x, y of rows [0, min(const_rows, n_rows of key 0)) of the first path key's path_param (R = cap_rows)
+//   traj     [K][7][E] column-major per key: columns s, x, y, psi, kappa, vx, ax of rows [0, min(rows, E)) (E = n_export)
+//   nodes    [K][CN][2] int32: the (layer, node) pairs of every path key (CN = cap_nodes, -1 = None)
+// K = LTPL_PLANNER_MAX_KEYS. Every section is written column by column with the lanes walking rows: the state's row tables are column-major,
+// so loads and stores are contiguous runs. Counts of a planner whose error word is set are zero. What lies behind a count is stale.
+// ---------------------------------------------------------------------------------------------------------------------
+#define REC_HEAD 64
+enum { REC_TICK = 0, REC_PLANNER, REC_ERR, REC_SEL, REC_T_NOW, REC_X, REC_Y, REC_VEL, REC_THETA, REC_N_OBJ, REC_CUT_POS, REC_CUT_LAYER,
+       REC_VEL_PLAN, REC_ACC_PLAN, REC_N_TRAJ, REC_N_IDS, REC_TRAJ = 16, REC_IDS = 28, REC_START = 36, REC_CONST_ROWS = 38, REC_CLOSEST,
+       REC_N_PATHS, REC_PATHS };
+static_assert(LTPL_PLANNER_MAX_KEYS == 4 && REC_TRAJ + 3 * LTPL_PLANNER_MAX_KEYS == REC_IDS && REC_IDS + 2 * LTPL_PLANNER_MAX_KEYS == REC_START &&
+              REC_PATHS + 4 * LTPL_PLANNER_MAX_KEYS <= REC_HEAD, "flight recorder: head layout");
+
+struct SimRec {
+    const int* planners;                   // [M] recorded planner indices, in the caller's order
+    double* ring;                          // [depth][M][stride]
+    int M, E;                              // recorded planners; exported rows per trajectory
+    size_t stride;                         // doubles per record
+    size_t o_obj, o_const, o_traj, o_nodes;     // first double of every section
+};
+static SimRec sim_rec_layout(const fleet::Dims& D, int n_export)
+{
+    SimRec r{};
+    r.E = n_export;
+    r.o_obj = REC_HEAD;
+    r.o_const = r.o_obj + (size_t)6 * SIM_OBJ_CAP;
+    r.o_traj = r.o_const + (size_t)2 * D.R;
+    r.o_nodes = r.o_traj + (size_t)LTPL_PLANNER_MAX_KEYS * 7 * n_export;
+    r.stride = (r.o_nodes + (size_t)LTPL_PLANNER_MAX_KEYS * D.CN + 31) / 32 * 32;        // (a pair of int32 per double; records start on 256 bytes)
+    return r;
+}
+
+// capture P, behind paths_post: what ltpl_fleet_get_paths would return now (Graph_LTPL.py:336-340; the velocity stage trims it afterwards)
+__global__ __launch_bounds__(64) void k_fleet_sim_rec_paths(FleetArgs F, SimRec rc, int slot)
+{
+    const int m = blockIdx.x, lane = threadIdx.x; const WaveX x{lane};
+    const int p = rc.planners[m];
+    const fleet::Block B{F.state + F.D.stride * (size_t)p, F.D, nullptr};
+    __shared__ fleet::PlannerS S;
+    fleet_load(x, B, &S);
+    constexpr int K = LTPL_PLANNER_MAX_KEYS;
+    double* o = rc.ring + ((size_t)slot * rc.M + m) * rc.stride;
+    const bool ok = !S.err;
+    const int nk = !ok ? 0 : (S.n_last < K ? S.n_last : K);
+    if (lane == 0) {
+        o[REC_START] = ok && S.has_start ? (double)S.start_node[0] : -1.0; o[REC_START + 1] = ok && S.has_start ? (double)S.start_node[1] : -1.0;
+        o[REC_CONST_ROWS] = ok ? (double)S.const_rows : -1.0; o[REC_CLOSEST] = ok ? (double)S.closest_obj_index : -1.0;
+        o[REC_N_PATHS] = (double)nk;
+    }
+    if (lane < 4 * K) {
+        const int k = lane >> 2, c = lane & 3;
+        double v = 0.0;
+        if (k < nk) { const fleet::TrajM& T = S.tm[S.cur_set][S.last_slot[k]]; v = (double)(c == 0 ? T.id : c == 1 ? T.rows : c == 2 ? T.nn : T.red_len); }
+        o[REC_PATHS + lane] = v;
+    }
+    int* nodes = reinterpret_cast<int*>(o + rc.o_nodes);
+    for (int k = 0; k < nk; ++k) {
+        const int sl = S.last_slot[k]; const fleet::TrajM& T = S.tm[S.cur_set][sl];
+        const int room = F.D.CN - T.n0, nn = T.nn < room ? T.nn : room;
+        const int* nd = B.nodes(S.cur_set, sl) + (size_t)T.n0 * 2;
+        for (int i = lane; i < nn * 2; i += 64) nodes[(size_t)k * F.D.CN * 2 + i] = nd[i];
+    }
+    if (nk > 0 && S.const_rows > 0) {                                      // TickLogWriter.snapshot_paths: path_param[keys[0]][:const_rows, 0:2]
+        const int sl = S.last_slot[0]; const fleet::TrajM& T = S.tm[S.cur_set][sl];
+        int n = S.const_rows < T.rows ? S.const_rows : T.rows;
+        if (n > F.D.R - T.r0) n = F.D.R - T.r0;
+        const fleet::Rows r = B.pp(S.cur_set, sl).from(T.r0);
+        double* cx = o + rc.o_const; double* cy = cx + F.D.R;
+        for (int i = lane; i < n; i += 64) cx[i] = r.at(i, 0);
+        for (int i = lane; i < n; i += 64) cy[i] = r.at(i, 1);
+    }
+}
+
+// capture V, behind the last kernel of the velocity stage: the simulation's head of the tick, the objects the planner was handed (its slice
+// of the tick's object arrays) and what ltpl_fleet_get_trajectories would return now, rows trimmed to n_export, without vel_course
+__global__ __launch_bounds__(64) void k_fleet_sim_rec_vel(FleetArgs F, SimDev sd, SimRec rc, int slot, int tick)
+{
+    const int m = blockIdx.x, lane = threadIdx.x; const WaveX x{lane};
+    const int p = rc.planners[m];
+    const fleet::Block B{F.state + F.D.stride * (size_t)p, F.D, nullptr};
+    __shared__ fleet::PlannerS S;
+    fleet_load(x, B, &S);
+    constexpr int K = LTPL_PLANNER_MAX_KEYS;
+    double* o = rc.ring + ((size_t)slot * rc.M + m) * rc.stride;
+    const bool ok = !S.err;
+    int cnt = ok ? sd.cnt[p] : 0;
+    if (cnt > SIM_OBJ_CAP) cnt = SIM_OBJ_CAP;
+    const int nb = !ok ? 0 : (S.n_bp < K ? S.n_bp : K), ni = !ok ? 0 : (S.n_ids < K ? S.n_ids : K);
+    if (lane == 0) {
+        o[REC_TICK] = (double)tick; o[REC_PLANNER] = (double)p; o[REC_ERR] = (double)S.err; o[REC_SEL] = (double)sd.sel[p]; o[REC_T_NOW] = sd.now[p];
+        o[REC_X] = sd.pos_x[p]; o[REC_Y] = sd.pos_y[p]; o[REC_VEL] = sd.vel[p]; o[REC_THETA] = sd.theta[p]; o[REC_N_OBJ] = (double)cnt;
+        o[REC_CUT_POS] = (double)S.cut_index_pos; o[REC_CUT_LAYER] = (double)S.cut_layer; o[REC_VEL_PLAN] = S.vel_plan; o[REC_ACC_PLAN] = S.acc_plan;
+        o[REC_N_TRAJ] = (double)nb; o[REC_N_IDS] = (double)ni;
+    }
+    if (lane < 3 * K) {
+        const int k = lane / 3, c = lane % 3;
+        o[REC_TRAJ + lane] = k < nb ? (double)(c == 0 ? S.bp_id[k] : c == 1 ? S.bp_traj_id[k] : S.bp_rows[k]) : 0.0;
+    }
+    if (lane < 2 * K) {
+        const int k = lane >> 1;
+        o[REC_IDS + lane] = k < ni ? (double)((lane & 1) ? S.id_val[k] : S.id_key[k]) : 0.0;
+    }
+    if (lane >= REC_PATHS + 4 * K && lane < REC_HEAD) o[lane] = 0.0;
+    {
+        const int v0 = sd.veh_off[p];
+        double* ob = o + rc.o_obj;
+        for (int i = lane; i < cnt; i += 64) {
+            const int v = v0 + i;
+            ob[i] = sd.o_r[v]; ob[SIM_OBJ_CAP + i] = sd.o_v[v];
+            ob[2 * SIM_OBJ_CAP + i] = sd.o_px[2 * v]; ob[3 * SIM_OBJ_CAP + i] = sd.o_py[2 * v];
+            ob[4 * SIM_OBJ_CAP + i] = sd.o_px[2 * v + 1]; ob[5 * SIM_OBJ_CAP + i] = sd.o_py[2 * v + 1];
+        }
+    }
+    for (int k = 0; k < nb; ++k) {
+        const fleet::Rows r = B.bp(S.bp_slot[k]);
+        int n = S.bp_rows[k] < rc.E ? S.bp_rows[k] : rc.E;
+        if (n > F.D.R) n = F.D.R;
+        double* t = o + rc.o_traj + (size_t)k * 7 * rc.E;
+        for (int c = 0; c < 7; ++c) for (int i = lane; i < n; i += 64) t[(size_t)c * rc.E + i] = r.at(i, c);
+    }
+}
+
 // exclusive scan of the on-track counts (one workgroup; a few hundred thousand planners at most)
 __global__ __launch_bounds__(1024) void k_fleet_sim_offsets(const int* cnt, int n, int* veh_off)
 {
@@ -435,6 +571,13 @@ struct FleetSim {
     SimTele te{};
     bool has_tele = false;                  // k_fleet_sim_tele (and k_fleet_sim_rank with has_mates) run every tick
     int tele_tick = 0;                      // ticks of ltpl_fleet_sim_run since the telemetry was set
+    std::vector<void*> rec_allocs;          // planner indices and ring of ltpl_fleet_sim_record
+    SimRec rec{};
+    bool has_rec = false;                   // k_fleet_sim_rec_paths / k_fleet_sim_rec_vel run every tick, on the unfused launch sequence
+    int rec_depth = 0, rec_tick = 0;        // ring depth; ticks of ltpl_fleet_sim_run since the recorder was set
+    std::vector<int> rec_planners;          // host copy of the indices
+    std::vector<double> rec_host;           // host copy of the ring (ltpl_fleet_sim_record_get), valid until the next run or recorder
+    bool rec_host_valid = false;
 };
 static void sim_free_list(std::vector<void*>& l)
 {
@@ -449,7 +592,7 @@ struct SimAllocs {
 static void fleet_sim_free(FleetSim* s)
 {
     if (!s) return;
-    sim_free_list(s->stage_allocs); sim_free_list(s->race_allocs); sim_free_list(s->tele_allocs);
+    sim_free_list(s->stage_allocs); sim_free_list(s->race_allocs); sim_free_list(s->tele_allocs); sim_free_list(s->rec_allocs);
     for (void* p : s->allocs) (void)hipFree(p);
     if (s->velt.d_buf) (void)hipFree(s->velt.d_buf);
     delete s;
@@ -637,6 +780,7 @@ try {
     t.has_paths = true;
     hipStream_t st = f->h->stream;
     s.ran = true;
+    s.rec_host_valid = false;
     FLEET_TRY(f, hipStreamSynchronize(st));
     FLEET_TRY(f, hipEventRecord(e0, st));
     for (int k = 0; k < n_ticks; ++k) {
@@ -659,13 +803,24 @@ try {
         FLEET_TRY(f, hipGetLastError());
         hipLaunchKernelGGL(k_fleet_sim_compact, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, st, s.sd, N);
         FLEET_TRY(f, hipGetLastError());
-        if (f->tape_fuse) {
+        if (f->tape_fuse && !s.has_rec) {
             fleet::FPathsOut po{};
             if ((rc = fleet_launch_paths(f, t, true, true, false, &po))) return rc;
             if ((rc = fleet_launch_vel(f, t, &po))) return rc;
         } else {
+            // (the recorder looks at the state between paths_post and stage A: the launch sequence of LTPL_FLEET_NO_FUSE)
             if ((rc = fleet_launch_paths(f, t, true, true))) return rc;
+            if (s.has_rec) {
+                hipLaunchKernelGGL(k_fleet_sim_rec_paths, dim3(s.rec.M), dim3(64), 0, st, f->args, s.rec, s.rec_tick % s.rec_depth);
+                FLEET_TRY(f, hipGetLastError());
+            }
             if ((rc = fleet_launch_vel(f, t))) return rc;
+        }
+        if (s.has_rec) {
+            // (the object arrays and veh_off through the simulation's pointers of this launch: ltpl_fleet_sim_race re-allocates the staging)
+            hipLaunchKernelGGL(k_fleet_sim_rec_vel, dim3(s.rec.M), dim3(64), 0, st, f->args, s.sd, s.rec, s.rec_tick % s.rec_depth, s.rec_tick);
+            FLEET_TRY(f, hipGetLastError());
+            ++s.rec_tick;
         }
         if (tr) {
             hipLaunchKernelGGL(k_fleet_digest, dim3(N), dim3(64), 0, st, f->args, tr + 8, (int)LTPL_FLEET_SIM_TRACE_DOUBLES);
@@ -837,5 +992,137 @@ try {
     FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
     FLEET_TRY(f, hipMemcpy(out, f->sim->te.rec, sizeof(double) * (size_t)f->D.N * LTPL_FLEET_SIM_TELE_DOUBLES, hipMemcpyDeviceToHost));
     if (track_length) *track_length = f->sim->te.length;
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+// every argument is checked before the first HIP call
+static int sim_check_record(ltpl_fleet* f, const int32_t* planners, int32_t n_planners, int32_t depth)
+{
+    const int N = f->D.N;
+    auto bad = [&](const char* why) { f->err = std::string("fleet sim record: ") + why; return LTPL_ERR_INVALID_ARG; };
+    if (!f->sim) return bad("ltpl_fleet_sim_setup first");
+    if (n_planners < 0) return bad("n_planners must not be negative");
+    if (!planners || n_planners == 0) return LTPL_OK;
+    if (n_planners > N) return bad("more recorded planners than planners");
+    if (depth < 1) return bad("depth must be positive");
+    std::vector<char> seen((size_t)N, 0);
+    for (int i = 0; i < n_planners; ++i) {
+        if (planners[i] < 0 || planners[i] >= N) return bad("planner index out of range");
+        if (seen[(size_t)planners[i]]) return bad("a planner index is given twice");
+        seen[(size_t)planners[i]] = 1;
+    }
+    return LTPL_OK;
+}
+
+extern "C" int ltpl_fleet_sim_record(ltpl_fleet* f, const int32_t* planners, int32_t n_planners, int32_t depth)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    int rc = sim_check_record(f, planners, n_planners, depth);
+    if (rc) return rc;
+    if ((rc = fleet_enter(f))) return rc;
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    FleetSim& s = *f->sim;
+    auto reset = [&]() { s.rec_tick = 0; s.rec_host_valid = false; s.rec_host.clear(); s.rec_host.shrink_to_fit(); };
+    if (!planners || n_planners == 0) {
+        sim_free_list(s.rec_allocs);
+        s.rec = SimRec{}; s.has_rec = false; s.rec_depth = 0; s.rec_planners.clear();
+        reset();
+        return LTPL_OK;
+    }
+    SimRec r = sim_rec_layout(f->D, s.sd.n_export);
+    r.M = n_planners;
+    // everything new is allocated first; the fleet keeps its previous recorder unless every step succeeds
+    SimAllocs a;
+    int* d_idx = nullptr;
+    if ((rc = sim_upload(f, a.p, planners, (size_t)n_planners, &d_idx))) return rc;
+    if ((rc = sim_upload(f, a.p, (const double*)nullptr, (size_t)depth * (size_t)n_planners * r.stride, &r.ring))) return rc;
+    r.planners = d_idx;
+    sim_free_list(s.rec_allocs);
+    s.rec_allocs.swap(a.p);
+    s.rec = r; s.has_rec = true; s.rec_depth = depth; s.rec_planners.assign(planners, planners + n_planners);
+    reset();
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+extern "C" int ltpl_fleet_sim_record_info(ltpl_fleet* f, int32_t* n_planners, int32_t* depth, int32_t* first_tick, int32_t* n_ticks)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    if (!f->sim) { f->err = "fleet sim record: ltpl_fleet_sim_setup first"; return LTPL_ERR_INVALID_ARG; }
+    const FleetSim& s = *f->sim;
+    const int held = s.has_rec ? (s.rec_tick < s.rec_depth ? s.rec_tick : s.rec_depth) : 0;
+    if (n_planners) *n_planners = s.has_rec ? s.rec.M : 0;
+    if (depth) *depth = s.rec_depth;
+    if (first_tick) *first_tick = s.rec_tick - held;
+    if (n_ticks) *n_ticks = held;
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+extern "C" int ltpl_fleet_sim_record_get(ltpl_fleet* f, int32_t tick, int32_t slot, ltpl_fleet_sim_record_head* head, double* objects,
+                                         ltpl_planner_paths_view* pv, double* const_xy, ltpl_planner_traj_view* tv)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    auto bad = [&](const char* why) { f->err = std::string("fleet sim record: ") + why; return LTPL_ERR_INVALID_ARG; };
+    if (!f->sim) return bad("ltpl_fleet_sim_setup first");
+    FleetSim& s = *f->sim;
+    if (!s.has_rec) return bad("the recorder is off (ltpl_fleet_sim_record first)");
+    const int held = s.rec_tick < s.rec_depth ? s.rec_tick : s.rec_depth;
+    if (tick < s.rec_tick - held || tick >= s.rec_tick) return bad("the ring does not hold this tick (ltpl_fleet_sim_record_info)");
+    if (slot < 0 || slot >= s.rec.M) return bad("slot outside the recorded planners");
+    FLEET_TRY(f, hipSetDevice(f->h->device));
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    const SimRec& r = s.rec;
+    if (!s.rec_host_valid) {                                    // once per run: later calls are served from the host copy
+        const size_t n = (size_t)s.rec_depth * (size_t)r.M * r.stride;
+        s.rec_host.resize(n);
+        FLEET_TRY(f, hipMemcpy(s.rec_host.data(), r.ring, sizeof(double) * n, hipMemcpyDeviceToHost));
+        s.rec_host_valid = true;
+    }
+    const double* o = s.rec_host.data() + ((size_t)(tick % s.rec_depth) * (size_t)r.M + (size_t)slot) * r.stride;
+    const int R = f->D.R, CN = f->D.CN, E = r.E;
+    const int n_obj = (int)o[REC_N_OBJ];
+    if (head) {
+        head->tick = (int32_t)o[REC_TICK]; head->planner = (int32_t)o[REC_PLANNER]; head->error = (int32_t)o[REC_ERR];
+        head->sel_action = (int32_t)o[REC_SEL]; head->t_now = o[REC_T_NOW]; head->pos_x = o[REC_X]; head->pos_y = o[REC_Y];
+        head->vel_est = o[REC_VEL]; head->heading = o[REC_THETA]; head->n_objects = n_obj; head->reserved0 = 0;
+    }
+    if (objects) {
+        const double* ob = o + r.o_obj;
+        for (int i = 0; i < n_obj; ++i) for (int c = 0; c < 6; ++c) objects[(size_t)i * 6 + c] = ob[(size_t)c * SIM_OBJ_CAP + i];
+    }
+    const int nk = (int)o[REC_N_PATHS];
+    const int const_rows = (int)o[REC_CONST_ROWS];
+    if (pv) {
+        pv->n_keys = nk;
+        pv->start_node[0] = (int32_t)o[REC_START]; pv->start_node[1] = (int32_t)o[REC_START + 1];
+        pv->const_rows = const_rows; pv->closest_obj_index = (int32_t)o[REC_CLOSEST];
+        const int* nodes = reinterpret_cast<const int*>(o + r.o_nodes);
+        for (int k = 0; k < nk; ++k) {
+            const double* q = o + REC_PATHS + 4 * k;
+            pv->key_id[k] = (int32_t)q[0]; pv->n_rows[k] = (int32_t)q[1]; pv->n_nodes[k] = (int32_t)q[2]; pv->red_len[k] = (int32_t)q[3];
+            const int nn = pv->n_nodes[k] < CN ? pv->n_nodes[k] : CN;
+            if (pv->nodes[k] && nn > 0) std::memcpy(pv->nodes[k], nodes + (size_t)k * CN * 2, sizeof(int) * 2 * (size_t)nn);
+        }
+    }
+    if (const_xy && nk > 0 && const_rows > 0) {
+        int n = const_rows < (int)o[REC_PATHS + 1] ? const_rows : (int)o[REC_PATHS + 1];
+        if (n > R) n = R;
+        const double* cx = o + r.o_const; const double* cy = cx + R;
+        for (int i = 0; i < n; ++i) { const_xy[(size_t)i * 2] = cx[i]; const_xy[(size_t)i * 2 + 1] = cy[i]; }
+    }
+    if (tv) {
+        const int nb = (int)o[REC_N_TRAJ], ni = (int)o[REC_N_IDS];
+        tv->n_keys = nb; tv->n_ids = ni; tv->n_vel_course = 0;
+        tv->cut_index_pos = (int32_t)o[REC_CUT_POS]; tv->cut_layer = (int32_t)o[REC_CUT_LAYER]; tv->vel_plan = o[REC_VEL_PLAN]; tv->acc_plan = o[REC_ACC_PLAN];
+        for (int k = 0; k < ni; ++k) { tv->id_key[k] = (int32_t)o[REC_IDS + 2 * k]; tv->id_val[k] = (int32_t)o[REC_IDS + 2 * k + 1]; }
+        for (int k = 0; k < nb; ++k) {
+            const double* q = o + REC_TRAJ + 3 * k;
+            tv->key_id[k] = (int32_t)q[0]; tv->traj_id[k] = (int32_t)q[1]; tv->n_rows[k] = (int32_t)q[2];
+            if (tv->traj[k]) {
+                const int n = tv->n_rows[k] < E ? tv->n_rows[k] : E;
+                const double* t = o + r.o_traj + (size_t)k * 7 * E;
+                for (int i = 0; i < n; ++i) for (int c = 0; c < 7; ++c) tv->traj[k][(size_t)i * 7 + c] = t[(size_t)c * E + i];
+            }
+        }
+    }
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))

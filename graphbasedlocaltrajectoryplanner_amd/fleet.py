@@ -13,7 +13,7 @@ import math
 import numpy as np
 
 from . import _capi
-from .planner import KEY_IDS, Planner, PlannerPathsIn, PlannerVelIn
+from .planner import KEY_IDS, KEY_NAMES, PathsView, Planner, PlannerPathsIn, PlannerVelIn, TrajView
 from .sim import TELEMETRY_DOUBLES, TELEMETRY_FIELDS, telemetry_dict      # noqa: F401  (published here: fleet.TELEMETRY_FIELDS)
 
 
@@ -42,7 +42,14 @@ class SimTeleIn(C.Structure):             # ltpl_fleet_sim_tele_in
     _fields_ = [("radius", C.c_void_p), ("grid_s", C.c_void_p)]
 
 
+class SimRecordHead(C.Structure):         # ltpl_fleet_sim_record_head
+    _fields_ = [("tick", C.c_int32), ("planner", C.c_int32), ("error", C.c_int32), ("sel_action", C.c_int32),
+                ("t_now", C.c_double), ("pos_x", C.c_double), ("pos_y", C.c_double), ("vel_est", C.c_double), ("heading", C.c_double),
+                ("n_objects", C.c_int32), ("reserved0", C.c_int32)]
+
+
 SIM_TRACE_DOUBLES = 8 + 8 + 9 * _capi.PLANNER_MAX_KEYS     # LTPL_FLEET_SIM_TRACE_DOUBLES
+SIM_RECORD_OBJECTS = 96                                    # LTPL_FLEET_SIM_RECORD_OBJECTS
 
 
 class Fleet(Planner):
@@ -70,6 +77,11 @@ class Fleet(Planner):
         if hasattr(self.lib, "ltpl_fleet_sim_telemetry"):
             f("sim_telemetry").argtypes = [C.c_void_p, C.POINTER(SimTeleIn)]
             f("sim_telemetry_read").argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_double)]
+        if hasattr(self.lib, "ltpl_fleet_sim_record"):
+            f("sim_record").argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
+            f("sim_record_info").argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 4
+            f("sim_record_get").argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(SimRecordHead), C.c_void_p, C.POINTER(PathsView),
+                                            C.c_void_p, C.POINTER(TrajView)]
         if hasattr(self.lib, "ltpl_fleet_friction"):
             f("friction").argtypes = [C.c_void_p, C.POINTER(FrictionIn)]
             f("friction_scale").argtypes = [C.c_void_p, C.c_void_p]
@@ -309,7 +321,7 @@ class Fleet(Planner):
             setattr(si, k, a.ctypes.data)
         si.n_rl, si.t0, si.tic0, si.dt, si.n_export = rows.shape[0], float(t0), float(t0 if tic0 is None else tic0), float(dt), int(n_export)
         self._check(self._fn("sim_setup")(self.handle, C.byref(si)))
-        self._sim_opp = int(arrs["opp_off"][-1])
+        self._sim_opp, self._sim_export = int(arrs["opp_off"][-1]), int(n_export)
 
     def sim_vel(self, ax_tables=None, ax_table_idx=None, **vel_kwargs):
         """Velocity arguments of the following ``sim_run`` calls (keywords of ``calc_vel_profile`` without pos_est / vel_est, scalars or one
@@ -386,6 +398,78 @@ class Fleet(Planner):
         length = C.c_double(0.0)
         self._check(self._fn("sim_telemetry_read")(self.handle, out.ctypes.data, TELEMETRY_DOUBLES, C.byref(length)))
         return telemetry_dict(out, float(length.value))
+
+    # ---- flight recorder on the device ----------------------------------------------------------------------------------------------
+    def sim_record(self, planners, depth=1):
+        """(Re)starts the flight recorder of the following ``sim_run`` calls (ltpl_fleet_sim_record; after ``sim_setup``, between runs at
+        any time): for the ``planners`` (distinct indices, any order) the device keeps a full record of each of the last ``depth`` ticks.
+        ``planners=None`` switches the recorder off. Tick indices count from this call on."""
+        if planners is None:
+            self._check(self._fn("sim_record")(self.handle, None, 0, int(depth)))
+            return
+        idx = np.ascontiguousarray(np.asarray(list(planners), np.int64).reshape(-1).astype(np.int32))
+        self._check(self._fn("sim_record")(self.handle, idx.ctypes.data if idx.size else None, int(idx.size), int(depth)))
+
+    def sim_record_info(self):
+        """dict(n_planners, depth, first_tick, n_ticks): the ring holds the fleet ticks first_tick .. first_tick + n_ticks - 1."""
+        v = [C.c_int32(0) for _ in range(4)]
+        self._check(self._fn("sim_record_info")(self.handle, *[C.byref(x) for x in v]))
+        return dict(zip(("n_planners", "depth", "first_tick", "n_ticks"), (int(x.value) for x in v)))
+
+    def sim_record_read(self, first=None, count=None):
+        """The held ticks (``first`` .. ``first + count - 1``; default: all of them), oldest first: a list over ticks of lists over the
+        recorded planners in the order given to ``sim_record``. Every element is a dict -- ``tick``, ``planner``, ``error`` (error word, 0:
+        none), ``sel`` (action name), ``t_now``, ``pos_est``, ``vel_est``, ``heading``, ``vehicles`` [(radius, vel, positions (2, 2))] as
+        ``calc_paths`` takes them, ``paths`` (``start_node``, ``keys``, ``nodes``, ``n_rows``, ``red_len``, ``const_rows``,
+        ``closest_obj_index`` named as by ``paths()``, plus ``const_path_seg``: (const_rows, 2) array or None), taken between the tick's
+        calc_paths and its velocity stage, and ``traj``: the triple of ``trajectories()`` with rows trimmed to n_export and no vel_course.
+        ``TickLogWriter.write_sim_record`` turns such a dict into a row of the reference's tick log."""
+        info = self.sim_record_info()
+        first = info["first_tick"] if first is None else int(first)
+        count = info["first_tick"] + info["n_ticks"] - first if count is None else int(count)
+        head, pv, tv = SimRecordHead(), PathsView(), self._tv
+        obj = np.zeros((SIM_RECORD_OBJECTS, 6))
+        cxy = np.zeros((self.cap_rows, 2))
+        for k in range(_capi.PLANNER_MAX_KEYS):
+            pv.nodes[k] = self._pv.nodes[k]                # (path_param, coeff and node_idx are not recorded: no buffers)
+        vc, tv.vel_course = tv.vel_course, None
+        get = self._fn("sim_record_get")
+        out = []
+        try:
+            for t in range(first, first + count):
+                row = []
+                for m in range(info["n_planners"]):
+                    self._check(get(self.handle, t, m, C.byref(head), obj.ctypes.data, C.byref(pv), cxy.ctypes.data, C.byref(tv)))
+                    row.append(self._record_dict(head, obj, pv, cxy, tv))
+                out.append(row)
+        finally:
+            tv.vel_course = vc
+        return out
+
+    def _record_dict(self, head, obj, pv, cxy, tv):
+        nk = pv.n_keys
+        key_id, n_rows, n_nodes, red = pv.key_id[:nk], pv.n_rows[:nk], pv.n_nodes[:nk], pv.red_len[:nk]
+        coi = pv.closest_obj_index
+        paths = {"keys": [], "nodes": {}, "n_rows": {}, "red_len": {}, "start_node": pv.start_node[:2], "const_rows": pv.const_rows,
+                 "closest_obj_index": None if coi < 0 else coi, "const_path_seg": None}
+        for k in range(nk):
+            name = KEY_NAMES[key_id[k]]
+            nodes = self._nd[k][:n_nodes[k]].tolist()
+            if nodes and nodes[0][0] < 0:                   # the start spline's pseudo node [None, None] (OTH.py:267)
+                nodes = [[None if a < 0 else a, None if b < 0 else b] for a, b in nodes]
+            paths["keys"].append(name)
+            paths["nodes"][name], paths["n_rows"][name], paths["red_len"][name] = nodes, n_rows[k], bool(red[k])
+        if pv.const_rows >= 0 and nk:
+            paths["const_path_seg"] = cxy[:min(pv.const_rows, n_rows[0])].copy()
+        nb, ni, ne = tv.n_keys, tv.n_ids, self._sim_export
+        traj = {KEY_NAMES[tv.key_id[k]]: [self._tr[k][:min(tv.n_rows[k], ne)].copy()] for k in range(nb)}
+        ids = {KEY_NAMES[tv.id_key[k]]: tv.id_val[k] for k in range(ni)}
+        ref = {"cut_index_pos": tv.cut_index_pos, "cut_layer": tv.cut_layer, "vel_plan": tv.vel_plan, "acc_plan": tv.acc_plan,
+               "vel_course": np.zeros(0)}
+        veh = [(float(obj[i, 0]), float(obj[i, 1]), obj[i, 2:6].reshape(2, 2).copy()) for i in range(head.n_objects)]
+        return {"tick": head.tick, "planner": head.planner, "error": head.error, "sel": KEY_NAMES.get(head.sel_action),
+                "t_now": head.t_now, "pos_est": [head.pos_x, head.pos_y], "vel_est": head.vel_est, "heading": head.heading,
+                "vehicles": veh, "paths": paths, "traj": (traj, ids, ref)}
 
     # ---- friction maps on the device ------------------------------------------------------------------------------------------------
     def friction(self, maps, map_idx=None, scale=1.0):

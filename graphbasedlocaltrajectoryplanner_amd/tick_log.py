@@ -5,7 +5,7 @@ planning tick, column for column what ``Logging.log_onlinegraph`` writes
 (graph_ltpl/visualization/src/visualize_graph_log.py:66-130) opens logs produced through the planner entry points, and logs
 written by the reference itself can be read back here.
 
-  TickLogWriter   writes rows (from a ``Planner`` or from explicit values)
+  TickLogWriter   writes rows (from a ``Planner``, from a record of the fleet simulation's flight recorder, or from explicit values)
   read_log        parses a log (ours or the reference's) into dict rows
   revalidate      re-runs seam (1) for EVERY logged tick in one batched launch and compares the node lists with the logged
                   ones -- the batched form of the viewer's RECALC_VALIDATION (visualize_graph_log.py:210-234); logs double as
@@ -98,6 +98,27 @@ class TickLogWriter(object):
             const = p["path_param"][p["keys"][0]][ref["cut_index_pos"]:max(p["const_rows"] - 0, 0), :]
         self.write(time, backend.raceline_s(pos_est), p["start_node"], obj_veh, zones, {k: [p["nodes"][k]] for k in p["keys"]},
                    traj, ids, list(map(float, pos_est)), action_id_prev, 0, const)
+
+    def write_sim_record(self, rec, backend, zone_layers=(), zone_nodes=()):
+        """One row from a record of the fleet simulation's flight recorder (a dict of ``Fleet.sim_record_read``), column for column what
+        ``write_planner_tick`` writes with a ``paths_snapshot``: the record's paths were taken between calc_paths and the velocity stage,
+        the constant segment is logged from the cut index on (Graph_LTPL.py:445-447), ``s_coord`` comes from ``backend.raceline_s`` and
+        ``action_id_prev`` is the action the simulation selected. A record with an error word is skipped (the reference's loop would have
+        raised). Returns whether a row was written."""
+        if rec["error"]:
+            return False
+        traj, ids, ref = rec["traj"]
+        p = rec["paths"]
+        const = p["const_path_seg"]
+        if const is not None:
+            const = np.asarray(const)[ref["cut_index_pos"]:, :]
+        pos_est = list(map(float, rec["pos_est"]))
+        obj_veh = [[k, list(map(float, pos[0])), 0.0, float(r), float(v), np.asarray(pos[1:]).reshape(-1, 2)]
+                   for k, (r, v, pos) in enumerate(rec["vehicles"])]
+        zones = [[[list(map(int, zone_layers)), list(map(int, zone_nodes))], [[0.0, 0.0], [0.0, 0.0]]]] if len(zone_layers) else []
+        self.write(rec["t_now"], backend.raceline_s(pos_est), list(p["start_node"]), obj_veh, zones, {k: [p["nodes"][k]] for k in p["keys"]},
+                   traj, ids, pos_est, rec["sel"], 0, const)
+        return True
 
 
 def read_log(log_path: str):

@@ -833,6 +833,67 @@ int ltpl_fleet_sim_telemetry(ltpl_fleet* fleet, const ltpl_fleet_sim_tele_in* in
  * telemetry off: LTPL_ERR_INVALID_ARG. */
 int ltpl_fleet_sim_telemetry_read(ltpl_fleet* fleet, double* out, int32_t doubles_per_planner, double* track_length /* may be NULL */);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Additive to ABI v9 -- FLIGHT RECORDER: for a chosen subset of planners the device keeps a full record of every tick of
+ * ltpl_fleet_sim_run in a ring of `depth` ticks, taken at the two points of the tick where the reference itself looks
+ * (csrc/fleet_sim.hpp, one wave64 per RECORDED planner: the grid is the subset, not the fleet):
+ *   capture P  k_fleet_sim_rec_paths, behind paths_post and in front of the velocity stage: what ltpl_fleet_get_paths would return at
+ *              that moment -- start node, const_rows, closest_obj_index, per path key its id, n_rows, n_nodes, red_len and (layer, node)
+ *              list -- and x, y of rows [0, const_rows) of the first key's path_param, the constant path segment as the reference logs it
+ *              (Graph_LTPL.py:336-340, :445-447; the velocity stage trims the planner's memory to the cut layer afterwards, OTH.py:714-731);
+ *   capture V  k_fleet_sim_rec_vel, behind the last kernel of the velocity stage: the head below, the objects the planner was handed this
+ *              tick (its slice of the tick's object arrays, list order, <= 96: opponents and statics, then mates) and what
+ *              ltpl_fleet_get_trajectories would return -- cut_index_pos, cut_layer, vel_plan, acc_plan, the id pairs, per trajectory key
+ *              its id, trajectory id, UNTRIMMED row count and rows [0, min(rows, n_export)) -- without vel_course.
+ * Record of (tick, recorded planner m) on the device: `stride` doubles at ring[(tick % depth) M + m], integers as exact doubles --
+ *   head [64]: [0] tick [1] planner [2] error word [3] selected action [4] t_now [5] [6] pose x, y [7] vel_est [8] heading [9] objects
+ *              [10] cut_index_pos [11] cut_layer [12] vel_plan [13] acc_plan [14] trajectory keys [15] id pairs
+ *              [16 + 3 k ..] trajectory key k: key id, trajectory id, rows   [28 + 2 k ..] id pair k: key id, value
+ *              [36] [37] start node [38] const_rows [39] closest_obj_index [40] path keys [41 + 4 k ..] path key k: id, n_rows, n_nodes, red_len
+ *   objects [6][96] column-major (radius, velocity, x, y, predicted x, predicted y) | const [2][cap_rows] (x | y)
+ *   | trajectories [K][7][n_export] column-major per key | nodes [K][cap_nodes][2] int32,   K = LTPL_PLANNER_MAX_KEYS
+ *   stride = 64 + 576 + 2 cap_rows + 7 K n_export + K cap_nodes, rounded up to a multiple of 32 (cap_*: ltpl_planner_caps).
+ * A live planner's head equals fields [0] .. [5] of its trace record. A planner whose error word is set gets a record in every tick as
+ * well: its head with the simulation's last state of it (clock, action, pose, speed, heading), and zero counts (objects, keys, ids, path
+ * keys; start node, const_rows and closest_obj_index -1). The recorder needs the state between paths_post and stage A, so a fleet with a
+ * recorder takes the unfused launch sequence (LTPL_FLEET_NO_FUSE) whatever the environment says; results are bit-identical. A fleet
+ * without a recorder launches exactly the kernels it launches without this feature. Indices are per fleet: a recorder never crosses a shard.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define LTPL_FLEET_SIM_RECORD_OBJECTS 96
+typedef struct {
+    int32_t tick;                   /* fleet tick: ticks of ltpl_fleet_sim_run since the recorder was set              */
+    int32_t planner;
+    int32_t error;                  /* error word of the planner (0: none), as field [0] of ltpl_fleet_digest            */
+    int32_t sel_action;             /* LTPL_ACT_*, as trace field [0]                                                    */
+    double  t_now;
+    double  pos_x, pos_y;           /* tracked pose                                                                      */
+    double  vel_est;
+    double  heading;
+    int32_t n_objects;              /* rows of `objects`, as trace field [5]                                             */
+    int32_t reserved0;
+} ltpl_fleet_sim_record_head;
+
+/* sets or restarts the recorder for the planners[0 .. n_planners) (distinct, any order) with a ring of `depth` >= 1 ticks; planners == NULL
+ * or n_planners == 0 switches it off. After ltpl_fleet_sim_setup (which switches it off) at any time between runs, before or after
+ * ltpl_fleet_sim_race and ltpl_fleet_sim_telemetry. Every argument is checked before the first HIP call (no simulation, an index outside
+ * 0 .. n - 1, an index given twice, depth < 1: LTPL_ERR_INVALID_ARG); everything new is allocated before anything old is freed: a failing
+ * call keeps the previous recorder, its ring and its tick count. */
+int ltpl_fleet_sim_record(ltpl_fleet* fleet, const int32_t* planners, int32_t n_planners, int32_t depth);
+/* the ring holds the fleet ticks first_tick .. first_tick + n_ticks - 1 (every pointer may be NULL). Tick indices count the ticks of
+ * ltpl_fleet_sim_run since the recorder was set and go on across several runs. Recorder off: n_planners = depth = n_ticks = 0. */
+int ltpl_fleet_sim_record_info(ltpl_fleet* fleet, int32_t* n_planners, int32_t* depth, int32_t* first_tick, int32_t* n_ticks);
+/* the record of fleet tick `tick` and recorded planner `slot` (position in the list given to ltpl_fleet_sim_record). Synchronises the
+ * handle's stream; the first call after a run copies the ring to the host once, later calls are served from that copy until the next run
+ * or a new recorder. Every pointer may be NULL. The view structs are filled the way ltpl_fleet_get_paths / _get_trajectories fill them:
+ * counts always, arrays where the caller's pointer is non-NULL -- `nodes` of the paths view, `traj` of the trajectory view (rows
+ * [0, min(n_rows, n_export)); n_rows is the untrimmed count). path_param, coeff, node_idx and vel_course are NOT recorded: those buffers
+ * are left untouched, n_vel_course is 0. objects: rows [radius, velocity, x, y, predicted x, predicted y], n_objects of them.
+ * const_xy: rows [x, y], min(const_rows, n_rows[0]) of them (none without a path key or with const_rows <= 0).
+ * A tick the ring does not hold, a slot outside 0 .. M - 1, a recorder that is off: LTPL_ERR_INVALID_ARG. */
+int ltpl_fleet_sim_record_get(ltpl_fleet* fleet, int32_t tick, int32_t slot, ltpl_fleet_sim_record_head* head,
+                              double* objects /* [96][6] or NULL */, ltpl_planner_paths_view* paths,
+                              double* const_xy /* [cap_rows][2] or NULL */, ltpl_planner_traj_view* traj);
+
 #ifdef __cplusplus
 }
 #endif

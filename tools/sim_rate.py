@@ -1,12 +1,15 @@
 """Closed-loop SIMULATION rate of a fleet (ltpl_fleet_sim_*): N planners, each with its own eight C2-style race-line opponents (SURVEY.md
 section 8d: s0_k = 250 + 280 k, vel_scale_k = 0.30 + 0.05 (k mod 4), here staggered by 10 m (p mod 16) per planner), run the example
 driver's loop on the device for T ticks without host work per tick.   tools/sim_rate.py [--planners 32768] [--ticks 200] [--no-tape]
-[--race-size K] [--friction-map] [--telemetry] [--lib PATH]. Prints planner-ticks per second of sim_run (device time of the run) next to tape_run on the C2 tape (recorded inputs,
+[--race-size K] [--friction-map] [--telemetry] [--record M [--record-depth D]] [--lib PATH]. Prints planner-ticks per second of sim_run (device time of the run) next to tape_run on the C2 tape (recorded inputs,
 tools/fleet_rate.py). --race-size K > 1: races of K consecutive planners (ltpl_fleet_sim_race) that see one another, started 30 m apart
 along the race line with its heading; K = 1 (default) is the run without races. --friction-map: the same fleet on the friction grid of
 tests/golden/friction_grid.npz (ltpl_fleet_friction: rows evaluated on the device, grip factors 1.0 .. 0.7 over the planners) instead of
 the constant tuple. --telemetry: race telemetry on (ltpl_fleet_sim_telemetry, contact radius 2.5: k_fleet_sim_tele every tick, k_fleet_sim_rank
-with races); the records of the first planners are printed after the run. --lib PATH: another build of the library (A/B against the parent's)."""
+with races); the records of the first planners are printed after the run. --record M: the flight recorder on for M planners spread evenly
+over the fleet (ltpl_fleet_sim_record, ring depth D, default: the run's ticks: k_fleet_sim_rec_paths / k_fleet_sim_rec_vel every tick on the
+unfused launch sequence -- compare with LTPL_FLEET_NO_FUSE=1 and the recorder off); the bytes per record and the last record's summary are
+printed. --lib PATH: another build of the library (A/B against the parent's)."""
 import argparse
 import os
 import sys
@@ -32,6 +35,8 @@ def main():
     ap.add_argument("--race-size", type=int, default=1, help="planners per race (1: no races)")
     ap.add_argument("--friction-map", action="store_true", help="every planner on the friction grid, own grip factor")
     ap.add_argument("--telemetry", action="store_true", help="race telemetry on (radius 2.5); prints the first planners' records")
+    ap.add_argument("--record", type=int, default=0, help="flight recorder on for this many planners, spread evenly over the fleet")
+    ap.add_argument("--record-depth", type=int, default=0, help="ring depth of the recorder (default: --ticks)")
     ap.add_argument("--lib", default=None, help="path of the library to load (default: the in-tree build)")
     a = ap.parse_args()
     lat = Lattice.load(os.path.join(ROOT, "tests", "golden", "monteblanco_lattice.npz"))
@@ -74,6 +79,8 @@ def main():
                       ax_max_machines=va['ax_max_machines'])
         if a.telemetry:
             fleet.sim_telemetry(radius=2.5)
+        if a.record:
+            fleet.sim_record([int(q) for q in np.linspace(0, n - 1, a.record).round()] if a.record > 1 else [0], a.record_depth or a.ticks)
         t0 = time.perf_counter()
         failed = 0
         try:
@@ -89,6 +96,18 @@ def main():
         if failed == 0:
             sel = np.bincount(fleet.sim_state()['sel_action'] + 1, minlength=6)
             print("  last selected actions (none, straight, follow, left, right, emergency): %s" % sel.tolist())
+        if a.record and rep == a.reps - 1:
+            info = fleet.sim_record_info()
+            t1 = time.perf_counter()
+            last = fleet.sim_record_read(first=info["first_tick"] + info["n_ticks"] - 1, count=1)[0]
+            rec_doubles = 64 + 6 * 96 + 2 * fleet.cap_rows + 7 * _capi.PLANNER_MAX_KEYS * fleet._sim_export + _capi.PLANNER_MAX_KEYS * fleet.cap_nodes
+            print("  recorder: %d planners, ticks %d .. %d held, %d bytes per record (cap_rows %d, cap_nodes %d), ring copy + one tick read %.1f ms" % (
+                info["n_planners"], info["first_tick"], info["first_tick"] + info["n_ticks"] - 1, (rec_doubles + 31) // 32 * 32 * 8, fleet.cap_rows,
+                fleet.cap_nodes, (time.perf_counter() - t1) * 1e3))
+            for r in last[:4]:
+                print("    planner %d tick %d: sel %s, %d objects, paths %s (const_rows %d), trajectories %s" % (
+                    r["planner"], r["tick"], r["sel"], len(r["vehicles"]), r["paths"]["keys"], r["paths"]["const_rows"],
+                    {k: v[0].shape[0] for k, v in r["traj"][0].items()}))
         if a.telemetry and rep == a.reps - 1:
             d = fleet.sim_telemetry_read()
             print("  telemetry (track length %.3f m), planners 0 .. %d:" % (d["track_length"], min(n, max(K, 4)) - 1))
