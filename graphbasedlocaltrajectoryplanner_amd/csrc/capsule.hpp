@@ -2,7 +2,9 @@
 // sample, the largest distance of a sample from that chord and the largest gap between consecutive sample projections.
 // The decisions the kernel derives from them (paths_team.hpp, phase 2) must be CONSERVATIVE with respect to the reference's
 // exact test (GraphBase.py:626-643: any sample with d^2 <= threshold^2); tests/test_capsule_cull.py checks that property on
-// the real lattices with the kernel's fp32 arithmetic restated in NumPy.
+// the real lattices with the kernel's fp32 arithmetic restated in NumPy, and tests/test_gpu_mask_boundary.py checks the kernel
+// itself, bit for bit against the oracle, on queries placed at both boundaries of the cull, at the boundary of the exact test
+// and in the gaps between two samples (tests/mask_cases.py; tests/test_mask_cases_host.py: the same probes on the CPU).
 #pragma once
 #include <algorithm>
 #include <cmath>

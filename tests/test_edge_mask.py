@@ -13,6 +13,11 @@ the edges gen_local_node_template.py:164-203 deletes from the "default" filter),
 The kernel tests every edge of a window inside the planning range; the reference / oracle only edges whose end nodes the zone filter
 left active (an edge at a removed node is unusable either way). The comparison is therefore made on the edges with two active end
 nodes -- a false HIT or a false MISS of the cull on ANY such edge fails, whether or not the edge lies on an optimum.
+
+The scenarios here are recordings and random traffic: every vehicle has radius 2.5 and its positions lie wherever the traffic put them. Queries
+placed ON PURPOSE at the boundary of the exact test, at the two boundaries of the cull and in the gaps between samples, thresholds that differ
+from lane to lane, the runtime LDS plan, parent tables in global memory, planning ranges beyond 63 layers and the plan classes 32x40 / 48x32
+are left to tests/test_gpu_mask_boundary.py (probes: tests/mask_cases.py), which uses `active_edges` of this module.
 """
 import numpy as np
 import pytest
