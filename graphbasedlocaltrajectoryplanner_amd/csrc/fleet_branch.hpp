@@ -1,0 +1,299 @@
+// fleet_branch.hpp -- included at the end of ltpl_hip.hip, behind fleet_sim.hpp. SNAPSHOT AND BRANCH of the fleet simulation's planner
+// state on the device (ltpl_fleet_sim_snapshot / _snapshot_info / _snapshot_drop / _branch, include/ltpl_hip.h, additive to ABI v9).
+// The rule: what the tick kernels WRITE travels with a planner's state, what the caller SET stays with the destination --
+//   copied   the planner block (Dims::stride bytes of d_state; the planner's error word PlannerS::err lies in it), its window of friction
+//            rows (Dims::gg_stride bytes of d_gg) when both sides have windows, now / sel / started / pos_x / pos_y / vel / theta / live,
+//            opp_s / opp_tic of its opponents, and with telemetry on both sides its record, grid_s and prog;
+//   stays    the race line, the opponents' vel_scale / length, statics, zones, preference list, dt, n_export, the velocity arguments,
+//            friction map index and scale, race membership and length as a mate, contact radius, the recorder's ring and indices.
+// Everything else the simulation holds per planner (cnt, prev_action, t_now, veh_off, the staging slots and object arrays, the job pools
+// of the velocity stage) is written by every tick before it is read.
+// One kernel serves the three directions live -> snapshot, snapshot -> live and live -> live: it copies between two VIEWS, each a set of
+// base pointers indexed by an entry per pair. The live fleet is the view whose entries are planner indices; a snapshot is the same set of
+// arrays allocated per slot, with its planners packed (entry k = the k-th planner of the list) and an opponent offset table of its own.
+#pragma once
+
+struct BranchView {
+    unsigned char* state; unsigned char* gg;            // [entries][stride], [entries][gg_stride] (gg null: no row windows)
+    double* now; int* sel; int* started; double* pos_x; double* pos_y; double* vel; double* theta; int* live;
+    const int* opp_off; double* opp_s; double* opp_tic; // opponents of entry e: opp_off[e] .. opp_off[e + 1] - 1
+    double* rec; double* grid_s; double* prog;          // telemetry part (rec null: none)
+};
+
+typedef unsigned int branch_u32x4 __attribute__((ext_vector_type(4)));
+#define BRANCH_THREADS 256
+#define BRANCH_LOADS 4                                    // 16-byte loads a lane issues before its first store
+#define BRANCH_CHUNK ((size_t)BRANCH_THREADS * 16 * BRANCH_LOADS)
+
+// grid (chunks of a planner image, pairs): chunk c < state_chunks covers bytes [c, c + 1) BRANCH_CHUNK of the planner block, the chunks
+// behind them the same of the row window. Both sizes are multiples of 256 bytes and both bases are 256-byte aligned (hipMalloc; strides),
+// so every 16-byte access is aligned and a group of 16 lanes is inside or outside as a whole: one predicate per load, no tail code.
+// Pairs beyond the grid's y extent are walked by the same workgroups. Wave 0 of chunk 0 copies the small parts: lane 0 the scalars, one
+// lane per opponent (any count, 0 included) and per double of the telemetry record. dst entries are distinct and, within one view, no
+// entry is read and written (checked by the host): plain loads and stores, no ordering between workgroups.
+template <bool NT>
+__global__ __launch_bounds__(BRANCH_THREADS) void k_fleet_sim_branch(BranchView S, BranchView T, const int* __restrict__ src_entry,
+                                                                     const int* __restrict__ dst_entry, int n_pairs, size_t stride,
+                                                                     size_t gg_stride, int state_chunks)
+{
+    const int c = blockIdx.x, t = threadIdx.x;
+    for (int k = blockIdx.y; k < n_pairs; k += gridDim.y) {
+        const size_t es = (size_t)src_entry[k], ed = (size_t)dst_entry[k];
+        const bool rows = c >= state_chunks;
+        const size_t bytes = rows ? gg_stride : stride;
+        const unsigned char* a = rows ? S.gg + gg_stride * es : S.state + stride * es;
+        unsigned char* b = rows ? T.gg + gg_stride * ed : T.state + stride * ed;
+        const size_t o0 = (size_t)(rows ? c - state_chunks : c) * BRANCH_CHUNK + (size_t)t * 16;
+        branch_u32x4 v[BRANCH_LOADS];
+#pragma unroll
+        for (int i = 0; i < BRANCH_LOADS; ++i) {
+            const size_t o = o0 + (size_t)i * BRANCH_THREADS * 16;
+            if (o < bytes) v[i] = *reinterpret_cast<const branch_u32x4*>(a + o);
+        }
+#pragma unroll
+        for (int i = 0; i < BRANCH_LOADS; ++i) {
+            const size_t o = o0 + (size_t)i * BRANCH_THREADS * 16;
+            if (o < bytes) {
+                if constexpr (NT) __builtin_nontemporal_store(v[i], reinterpret_cast<branch_u32x4*>(b + o));
+                else *reinterpret_cast<branch_u32x4*>(b + o) = v[i];
+            }
+        }
+        if (c != 0 || t >= 64) continue;
+        if (t == 0) {
+            T.now[ed] = S.now[es]; T.sel[ed] = S.sel[es]; T.started[ed] = S.started[es]; T.pos_x[ed] = S.pos_x[es]; T.pos_y[ed] = S.pos_y[es];
+            T.vel[ed] = S.vel[es]; T.theta[ed] = S.theta[es]; T.live[ed] = S.live[es];
+        }
+        const int so = S.opp_off[es], no = S.opp_off[es + 1] - so, to = T.opp_off[ed];       // (equal counts on both sides: the host's check)
+        for (int q = t; q < no; q += 64) { T.opp_s[to + q] = S.opp_s[so + q]; T.opp_tic[to + q] = S.opp_tic[so + q]; }
+        if (S.rec && T.rec) {
+            if (t < LTPL_FLEET_SIM_TELE_DOUBLES) T.rec[ed * LTPL_FLEET_SIM_TELE_DOUBLES + t] = S.rec[es * LTPL_FLEET_SIM_TELE_DOUBLES + t];
+            else if (t == LTPL_FLEET_SIM_TELE_DOUBLES) T.grid_s[ed] = S.grid_s[es];
+            else if (t == LTPL_FLEET_SIM_TELE_DOUBLES + 1) T.prog[ed] = S.prog[es];
+        }
+    }
+}
+static_assert(LTPL_FLEET_SIM_TELE_DOUBLES + 2 <= 64, "k_fleet_sim_branch: one lane per telemetry double");
+
+// ---------------------------------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------------------------------
+struct SimSnap {
+    std::vector<void*> allocs;
+    BranchView v{};
+    std::vector<int> planners;              // entry k holds planner planners[k]
+    std::vector<int> entry_of;              // [N] entry of planner p, -1: not in the snapshot
+    std::vector<int> opp_off;               // [entries + 1] host copy of v.opp_off
+    bool has_tele = false; int tele_gen = 0;     // a telemetry part, taken from the telemetry numbered tele_gen (FleetSim::tele_gen)
+    uint64_t bytes = 0;
+    bool held() const { return !planners.empty(); }
+};
+struct SimSnaps { SimSnap slot[LTPL_FLEET_SIM_SNAPSHOTS]; };
+static void sim_snaps_free(SimSnaps* s)
+{
+    if (!s) return;
+    for (SimSnap& q : s->slot) sim_free_list(q.allocs);
+    delete s;
+}
+
+static BranchView branch_live_view(const ltpl_fleet* f)
+{
+    const FleetSim& s = *f->sim; const SimDev& d = s.sd;
+    BranchView v{};
+    v.state = f->d_state; v.gg = f->d_gg;
+    v.now = d.now; v.sel = d.sel; v.started = d.started; v.pos_x = d.pos_x; v.pos_y = d.pos_y; v.vel = d.vel; v.theta = d.theta; v.live = d.live;
+    v.opp_off = d.opp_off; v.opp_s = d.opp_s; v.opp_tic = d.opp_tic;
+    if (s.has_tele) { v.rec = s.te.rec; v.grid_s = s.te.grid_s; v.prog = s.te.prog; }
+    return v;
+}
+
+// the pairs' entries go to the device in one allocation of the call ([src | dst]); the copy itself is one launch
+static int branch_launch(ltpl_fleet* f, BranchView S, BranchView T, const std::vector<int>& src_entry, const std::vector<int>& dst_entry, float* ms)
+{
+    const int n = (int)src_entry.size();
+    if (ms) *ms = 0.0f;
+    if (n == 0) return LTPL_OK;
+    if (!S.rec || !T.rec) S.rec = T.rec = nullptr;
+    const bool rows = S.gg && T.gg;
+    const size_t stride = f->D.stride, gg_stride = f->D.gg_stride;
+    const int state_chunks = (int)((stride + BRANCH_CHUNK - 1) / BRANCH_CHUNK), gg_chunks = rows ? (int)((gg_stride + BRANCH_CHUNK - 1) / BRANCH_CHUNK) : 0;
+    SimAllocs a;
+    int* d_idx = nullptr;
+    std::vector<int> idx(src_entry);
+    idx.insert(idx.end(), dst_entry.begin(), dst_entry.end());
+    int rc = sim_upload(f, a.p, idx.data(), idx.size(), &d_idx);
+    if (rc) return rc;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    struct Guard { hipEvent_t* a; hipEvent_t* b; ~Guard() { if (*a) (void)hipEventDestroy(*a); if (*b) (void)hipEventDestroy(*b); } } g{&e0, &e1};
+    FLEET_TRY(f, hipEventCreate(&e0)); FLEET_TRY(f, hipEventCreate(&e1));
+    hipStream_t st = f->h->stream;
+    const dim3 grid((unsigned)(state_chunks + gg_chunks), (unsigned)(n < 65535 ? n : 65535));
+    FLEET_TRY(f, hipEventRecord(e0, st));
+#ifdef LTPL_EXPERIMENT
+    if (getenv("LTPL_SIM_BRANCH_NT") && atoi(getenv("LTPL_SIM_BRANCH_NT")) != 0)        // (the store form: DESIGN 4.5c, measured with tools/sim_branch_rate.py)
+        hipLaunchKernelGGL(k_fleet_sim_branch<true>, grid, dim3(BRANCH_THREADS), 0, st, S, T, (const int*)d_idx, (const int*)d_idx + n, n, stride, gg_stride, state_chunks);
+    else
+#endif
+    hipLaunchKernelGGL(k_fleet_sim_branch<false>, grid, dim3(BRANCH_THREADS), 0, st, S, T, (const int*)d_idx, (const int*)d_idx + n, n, stride, gg_stride, state_chunks);
+    FLEET_TRY(f, hipGetLastError());
+    FLEET_TRY(f, hipEventRecord(e1, st));
+    FLEET_TRY(f, hipEventSynchronize(e1));
+    FLEET_TRY(f, hipStreamSynchronize(st));
+    if (ms) FLEET_TRY(f, hipEventElapsedTime(ms, e0, e1));
+    return LTPL_OK;
+}
+
+static int branch_bad(ltpl_fleet* f, const std::string& why, const char* what = "snapshot") { f->err = std::string("fleet sim ") + what + ": " + why; return LTPL_ERR_INVALID_ARG; }
+// the checks every one of the four calls starts with (before the first HIP call); slot -1: the live fleet, where `live_ok`
+static int branch_check_slot(ltpl_fleet* f, int32_t slot, bool live_ok)
+{
+    const char* what = live_ok ? "branch" : "snapshot";
+    if (!f->sim) return branch_bad(f, "ltpl_fleet_sim_setup first", what);
+    if (slot < (live_ok ? -1 : 0) || slot >= LTPL_FLEET_SIM_SNAPSHOTS)
+        return branch_bad(f, "slot " + std::to_string(slot) + " out of range (" + (live_ok ? "-1: the live fleet, " : "") + "0 .. " + std::to_string(LTPL_FLEET_SIM_SNAPSHOTS - 1) + ")", what);
+    return LTPL_OK;
+}
+
+extern "C" int ltpl_fleet_sim_snapshot(ltpl_fleet* f, int32_t slot, const int32_t* planners, int32_t n_planners)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    int rc = branch_check_slot(f, slot, false);
+    if (rc) return rc;
+    FleetSim& s = *f->sim;
+    const int N = f->D.N;
+    std::unique_ptr<SimSnap> q(new SimSnap());
+    q->entry_of.assign((size_t)N, -1);
+    if (!planners) {
+        q->planners.resize((size_t)N);
+        for (int p = 0; p < N; ++p) q->planners[(size_t)p] = q->entry_of[(size_t)p] = p;
+    } else {
+        if (n_planners < 1 || n_planners > N) return branch_bad(f, "a planner list needs 1 .. n entries");
+        for (int k = 0; k < n_planners; ++k) {
+            const int p = planners[k];
+            if (p < 0 || p >= N) return branch_bad(f, "planner index " + std::to_string(p) + " out of range");
+            if (q->entry_of[(size_t)p] >= 0) return branch_bad(f, "planner " + std::to_string(p) + " is given twice");
+            q->entry_of[(size_t)p] = k;
+        }
+        q->planners.assign(planners, planners + n_planners);
+    }
+    const size_t M = q->planners.size();
+    q->opp_off.assign(M + 1, 0);
+    for (size_t k = 0; k < M; ++k) { const size_t p = (size_t)q->planners[k]; q->opp_off[k + 1] = q->opp_off[k] + (s.opp_off[p + 1] - s.opp_off[p]); }
+    const size_t n_opp = (size_t)q->opp_off[M];
+    if ((rc = fleet_enter(f))) return rc;
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    // everything new is allocated first; the slot keeps its previous snapshot unless every step succeeds
+    SimAllocs a;
+    BranchView& v = q->v;
+    uint64_t bytes = 0;
+    auto take = [&](auto** out, size_t n, const int* init = nullptr) {
+        using T = std::remove_pointer_t<std::remove_pointer_t<decltype(out)>>;
+        void* p = nullptr;
+        const size_t b = (n ? n : 1) * sizeof(T);
+        if (hipMalloc(&p, b) != hipSuccess) { f->err = "fleet sim snapshot: hipMalloc of " + std::to_string(b) + " bytes failed"; return (int)LTPL_ERR_HIP; }
+        a.p.push_back(p); bytes += b;
+        if (init && hipMemcpy(p, init, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) { f->err = "fleet sim snapshot: upload failed"; return (int)LTPL_ERR_HIP; }
+        *out = static_cast<T*>(p);
+        return (int)LTPL_OK;
+    };
+#define SNAP_TAKE(...) do { if ((rc = take(__VA_ARGS__))) return rc; } while (0)
+    SNAP_TAKE(&v.state, f->D.stride * M);
+    if (f->d_gg) SNAP_TAKE(&v.gg, f->D.gg_stride * M);
+    SNAP_TAKE(&v.now, M); SNAP_TAKE(&v.sel, M); SNAP_TAKE(&v.started, M); SNAP_TAKE(&v.pos_x, M); SNAP_TAKE(&v.pos_y, M); SNAP_TAKE(&v.vel, M);
+    SNAP_TAKE(&v.theta, M); SNAP_TAKE(&v.live, M);
+    { int* o = nullptr; SNAP_TAKE(&o, M + 1, q->opp_off.data()); v.opp_off = o; }
+    SNAP_TAKE(&v.opp_s, n_opp); SNAP_TAKE(&v.opp_tic, n_opp);
+    if (s.has_tele) { SNAP_TAKE(&v.rec, M * LTPL_FLEET_SIM_TELE_DOUBLES); SNAP_TAKE(&v.grid_s, M); SNAP_TAKE(&v.prog, M); }
+#undef SNAP_TAKE
+    std::vector<int> dst(M);
+    for (size_t k = 0; k < M; ++k) dst[k] = (int)k;
+    if ((rc = branch_launch(f, branch_live_view(f), v, q->planners, dst, nullptr))) return rc;
+    q->allocs.swap(a.p);
+    q->has_tele = s.has_tele; q->tele_gen = s.tele_gen; q->bytes = bytes;
+    if (!s.snaps) s.snaps = new SimSnaps();
+    SimSnap& old = s.snaps->slot[slot];
+    sim_free_list(old.allocs);
+    old = std::move(*q);
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+extern "C" int ltpl_fleet_sim_snapshot_info(ltpl_fleet* f, int32_t slot, int32_t* n_planners, int32_t* planners, int32_t cap, uint64_t* bytes)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    int rc = branch_check_slot(f, slot, false);
+    if (rc) return rc;
+    const SimSnaps* sn = f->sim->snaps;
+    const SimSnap* q = sn && sn->slot[slot].held() ? &sn->slot[slot] : nullptr;
+    const int n = q ? (int)q->planners.size() : 0;
+    if (planners && cap < n) return branch_bad(f, "the planner buffer holds " + std::to_string(cap) + " of " + std::to_string(n) + " entries");
+    if (n_planners) *n_planners = n;
+    if (planners && n) std::memcpy(planners, q->planners.data(), sizeof(int32_t) * (size_t)n);
+    if (bytes) *bytes = q ? q->bytes : 0;
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+extern "C" int ltpl_fleet_sim_snapshot_drop(ltpl_fleet* f, int32_t slot)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    int rc = branch_check_slot(f, slot, false);
+    if (rc) return rc;
+    SimSnaps* sn = f->sim->snaps;
+    if (!sn || !sn->slot[slot].held()) return LTPL_OK;
+    if ((rc = fleet_enter(f))) return rc;
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    sim_free_list(sn->slot[slot].allocs);
+    sn->slot[slot] = SimSnap();
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+extern "C" int ltpl_fleet_sim_branch(ltpl_fleet* f, int32_t slot, const int32_t* src, const int32_t* dst, int32_t n_pairs, float* ms)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    if (ms) *ms = 0.0f;
+    int rc = branch_check_slot(f, slot, true);
+    if (rc) return rc;
+    FleetSim& s = *f->sim;
+    const int N = f->D.N;
+    const SimSnap* q = nullptr;
+    auto bad = [&](const std::string& why) { return branch_bad(f, why, "branch"); };
+    if (slot >= 0) {
+        q = s.snaps && s.snaps->slot[slot].held() ? &s.snaps->slot[slot] : nullptr;
+        if (!q) return bad("slot " + std::to_string(slot) + " is empty");
+    }
+    if (n_pairs < 0) return bad("n_pairs must not be negative");
+    if (n_pairs == 0) return LTPL_OK;                        // nothing to copy: no allocation, no launch
+    if (!src || !dst) return bad("src / dst missing");
+    auto pair = [&](int k) { return "pair " + std::to_string(k) + " (src " + std::to_string(src[k]) + ", dst " + std::to_string(dst[k]) + "): "; };
+    std::vector<char> is_dst((size_t)N, 0);
+    for (int k = 0; k < n_pairs; ++k) {
+        if (src[k] < 0 || src[k] >= N || dst[k] < 0 || dst[k] >= N) return bad(pair(k) + "planner index out of range");
+        if (is_dst[(size_t)dst[k]]) return bad(pair(k) + "the destination is given twice");
+        is_dst[(size_t)dst[k]] = 1;
+    }
+    std::vector<int> se, de;
+    se.reserve((size_t)n_pairs); de.reserve((size_t)n_pairs);
+    for (int k = 0; k < n_pairs; ++k) {
+        const int a = src[k], b = dst[k];
+        int no_src;
+        if (q) {
+            const int e = q->entry_of[(size_t)a];
+            if (e < 0) return bad(pair(k) + "the source is not a planner of snapshot " + std::to_string(slot));
+            no_src = q->opp_off[(size_t)e + 1] - q->opp_off[(size_t)e];
+            se.push_back(e);
+        } else {
+            if (a == b) continue;                            // a planner onto itself: nothing to do
+            if (is_dst[(size_t)a]) return bad(pair(k) + "with the live fleet as source no planner may be both a source and a destination");
+            no_src = s.opp_off[(size_t)a + 1] - s.opp_off[(size_t)a];
+            se.push_back(a);
+        }
+        const int no_dst = s.opp_off[(size_t)b + 1] - s.opp_off[(size_t)b];
+        if (no_src != no_dst) return bad(pair(k) + "the source has " + std::to_string(no_src) + " opponents, the destination " + std::to_string(no_dst));
+        de.push_back(b);
+    }
+    if ((rc = fleet_enter(f))) return rc;
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    BranchView S = q ? q->v : branch_live_view(f);
+    if (q && !(q->has_tele && s.has_tele && q->tele_gen == s.tele_gen)) S.rec = nullptr;      // (a telemetry set since then started its records anew)
+    if ((rc = branch_launch(f, S, branch_live_view(f), se, de, ms))) return rc;
+    f->cur.has_paths = false;           // (as after a run: a per-call calc_vel_profile needs its own calc_paths first)
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))

@@ -555,6 +555,9 @@ __global__ __launch_bounds__(64) void k_fleet_sim_compact(SimDev sd, int n)
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
+struct SimSnaps;                            // snapshot slots (fleet_branch.hpp, ltpl_fleet_sim_snapshot)
+static void sim_snaps_free(SimSnaps* s);
+
 struct FleetSim {
     std::vector<void*> allocs;
     std::vector<void*> stage_allocs;        // staging slots, the tick's object arrays and obj_base: sized again by ltpl_fleet_sim_race
@@ -578,6 +581,9 @@ struct FleetSim {
     std::vector<int> rec_planners;          // host copy of the indices
     std::vector<double> rec_host;           // host copy of the ring (ltpl_fleet_sim_record_get), valid until the next run or recorder
     bool rec_host_valid = false;
+    std::vector<int> opp_off;               // [N + 1] host copy of sd.opp_off (ltpl_fleet_sim_branch compares opponent counts)
+    int tele_gen = 0;                       // counts the calls of ltpl_fleet_sim_telemetry that took effect: a snapshot's telemetry part belongs to one
+    SimSnaps* snaps = nullptr;              // allocated by the first ltpl_fleet_sim_snapshot
 };
 static void sim_free_list(std::vector<void*>& l)
 {
@@ -592,6 +598,7 @@ struct SimAllocs {
 static void fleet_sim_free(FleetSim* s)
 {
     if (!s) return;
+    sim_snaps_free(s->snaps);
     sim_free_list(s->stage_allocs); sim_free_list(s->race_allocs); sim_free_list(s->tele_allocs); sim_free_list(s->rec_allocs);
     for (void* p : s->allocs) (void)hipFree(p);
     if (s->velt.d_buf) (void)hipFree(s->velt.d_buf);
@@ -700,6 +707,7 @@ try {
     std::unique_ptr<FleetSim, void (*)(FleetSim*)> s(new FleetSim(), fleet_sim_free);
     const int N = f->D.N, n_obj = n_opp + n_st;
     s->n_opp = n_opp; s->n_obj = n_obj;
+    s->opp_off.assign(in->opp_off, in->opp_off + N + 1);
     SimDev& d = s->sd;
     d.n_rl = in->n_rl; d.dt = in->dt; d.n_export = in->n_export;
     {
@@ -948,7 +956,7 @@ try {
     FleetSim& s = *f->sim;
     if (!in) {
         sim_free_list(s.tele_allocs);
-        s.te = SimTele{}; s.has_tele = false; s.tele_tick = 0;
+        s.te = SimTele{}; s.has_tele = false; s.tele_tick = 0; ++s.tele_gen;
         return LTPL_OK;
     }
     const int N = f->D.N;
@@ -978,7 +986,7 @@ try {
 #undef SIM_UP
     sim_free_list(s.tele_allocs);
     s.tele_allocs.swap(a.p);
-    s.te = te; s.has_tele = true; s.tele_tick = 0;
+    s.te = te; s.has_tele = true; s.tele_tick = 0; ++s.tele_gen;
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))
 

@@ -4831,4 +4831,5 @@ try { return exp_unary(device, x, out, n, true); } LTPL_ABI_CATCH(nullptr)
 // ---------------------------------------------------------------------------------------------------------------------
 #include "fleet_dev.hpp"
 #include "fleet_sim.hpp"
+#include "fleet_branch.hpp"
 #include "fleet_friction.hpp"

@@ -50,6 +50,7 @@ class SimRecordHead(C.Structure):         # ltpl_fleet_sim_record_head
 
 SIM_TRACE_DOUBLES = 8 + 8 + 9 * _capi.PLANNER_MAX_KEYS     # LTPL_FLEET_SIM_TRACE_DOUBLES
 SIM_RECORD_OBJECTS = 96                                    # LTPL_FLEET_SIM_RECORD_OBJECTS
+SIM_SNAPSHOTS = 8                                          # LTPL_FLEET_SIM_SNAPSHOTS
 
 
 class Fleet(Planner):
@@ -82,6 +83,11 @@ class Fleet(Planner):
             f("sim_record_info").argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 4
             f("sim_record_get").argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(SimRecordHead), C.c_void_p, C.POINTER(PathsView),
                                             C.c_void_p, C.POINTER(TrajView)]
+        if hasattr(self.lib, "ltpl_fleet_sim_branch"):
+            f("sim_snapshot").argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
+            f("sim_snapshot_info").argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_int32, C.POINTER(C.c_uint64)]
+            f("sim_snapshot_drop").argtypes = [C.c_void_p, C.c_int32]
+            f("sim_branch").argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_float)]
         if hasattr(self.lib, "ltpl_fleet_friction"):
             f("friction").argtypes = [C.c_void_p, C.POINTER(FrictionIn)]
             f("friction_scale").argtypes = [C.c_void_p, C.c_void_p]
@@ -470,6 +476,58 @@ class Fleet(Planner):
         return {"tick": head.tick, "planner": head.planner, "error": head.error, "sel": KEY_NAMES.get(head.sel_action),
                 "t_now": head.t_now, "pos_est": [head.pos_x, head.pos_y], "vel_est": head.vel_est, "heading": head.heading,
                 "vehicles": veh, "paths": paths, "traj": (traj, ids, ref)}
+
+    # ---- snapshot and branch on the device ------------------------------------------------------------------------------------------
+    def sim_snapshot(self, slot=0, planners=None):
+        """Copies the simulation state of the ``planners`` (distinct indices; default: all) into snapshot slot ``slot`` (0 ..
+        SIM_SNAPSHOTS - 1) on the device, replacing what the slot held (ltpl_fleet_sim_snapshot; after ``sim_setup``, before or after
+        runs). State is what the tick kernels write: a planner's memory with its error word, its friction-row window, clock, action,
+        tracked pose, speed and heading, its opponents' positions and -- with telemetry on -- its record. What the caller set
+        (preference lists, opponents' speeds, statics, zones, ``sim_vel`` arguments, friction maps, races, the recorder) is no part of it.
+        ``sim_setup`` drops every snapshot; ``sim_telemetry`` invalidates their telemetry part."""
+        if planners is None:
+            self._check(self._fn("sim_snapshot")(self.handle, int(slot), None, 0))
+            return
+        idx = np.ascontiguousarray(np.asarray(list(planners), np.int64).reshape(-1).astype(np.int32))
+        if idx.size == 0:
+            raise ValueError("sim_snapshot: an empty planner list (None: all planners)")
+        self._check(self._fn("sim_snapshot")(self.handle, int(slot), idx.ctypes.data, int(idx.size)))
+
+    def sim_snapshot_info(self, slot):
+        """dict(planners: int32 array in the order given to ``sim_snapshot``, bytes: device memory of the slot), or None for an empty slot."""
+        n, b = C.c_int32(0), C.c_uint64(0)
+        self._check(self._fn("sim_snapshot_info")(self.handle, int(slot), C.byref(n), None, 0, C.byref(b)))
+        if n.value == 0:
+            return None
+        idx = np.zeros(n.value, np.int32)
+        self._check(self._fn("sim_snapshot_info")(self.handle, int(slot), C.byref(n), idx.ctypes.data, int(idx.size), None))
+        return dict(planners=idx, bytes=int(b.value))
+
+    def sim_snapshot_drop(self, slot):
+        """Frees snapshot slot ``slot`` (ltpl_fleet_sim_snapshot_drop)."""
+        self._check(self._fn("sim_snapshot_drop")(self.handle, int(slot)))
+
+    def sim_branch(self, src, dst, snapshot=None):
+        """Planner ``dst[k]`` of the live fleet takes the state of planner ``src[k]`` (ltpl_fleet_sim_branch) -- of the live fleet, or of
+        snapshot slot ``snapshot``, which must hold it. A scalar ``src`` is broadcast over ``dst`` (fan-out of one situation into a bank
+        of planners with other ``vel_max`` / grip / machine tables). The configuration stays the destination's own (``sim_snapshot``), so
+        both planners of a pair need the same number of opponents; ``dst`` entries are distinct; with the live fleet as source no planner
+        is both a source and a destination (a pair ``src == dst`` is skipped). The error word travels: a healthy source revives a
+        failed planner. Returns the device time of the copy in ms."""
+        d = np.ascontiguousarray(np.asarray(dst, np.int64).reshape(-1).astype(np.int32))
+        s = np.ascontiguousarray(np.broadcast_to(np.asarray(src, np.int64).reshape(-1), d.shape).astype(np.int32))
+        ms = C.c_float(0.0)
+        self._check(self._fn("sim_branch")(self.handle, -1 if snapshot is None else int(snapshot), s.ctypes.data if s.size else None,
+                                           d.ctypes.data if d.size else None, int(d.size), C.byref(ms)))
+        return float(ms.value)
+
+    def sim_restore(self, slot):
+        """Every planner of snapshot ``slot`` back to the state the snapshot holds (``sim_branch`` with src == dst == the slot's planners).
+        Returns the device time of the copy in ms."""
+        info = self.sim_snapshot_info(slot)
+        if info is None:
+            raise ValueError("sim_restore: snapshot slot %d is empty" % int(slot))
+        return self.sim_branch(info["planners"], info["planners"], snapshot=slot)
 
     # ---- friction maps on the device ------------------------------------------------------------------------------------------------
     def friction(self, maps, map_idx=None, scale=1.0):

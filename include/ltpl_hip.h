@@ -57,7 +57,8 @@ extern "C" {
 
 #define LTPL_ABI_VERSION 9        /* v7 (round 5, additive): ltpl_paths_kernel_symbol, ltpl_layer_grid, ltpl_fleet_digest; v8 (additive): ltpl_assembly_records;
                                      v9 (round 6, additive): ltpl_create_ex, ltpl_tick_persistent_stop / _stats;
-                                     additive to v9: ltpl_fleet_sim_race / _heading, ltpl_fleet_friction / _scale / _rows */
+                                     additive to v9: ltpl_fleet_sim_race / _heading, ltpl_fleet_friction / _scale / _rows,
+                                     ltpl_fleet_sim_snapshot / _snapshot_info / _snapshot_drop / _branch */
 
 /* status codes */
 #define LTPL_OK               0
@@ -893,6 +894,52 @@ int ltpl_fleet_sim_record_info(ltpl_fleet* fleet, int32_t* n_planners, int32_t* 
 int ltpl_fleet_sim_record_get(ltpl_fleet* fleet, int32_t tick, int32_t slot, ltpl_fleet_sim_record_head* head,
                               double* objects /* [96][6] or NULL */, ltpl_planner_paths_view* paths,
                               double* const_xy /* [cap_rows][2] or NULL */, ltpl_planner_traj_view* traj);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Additive to ABI v9 -- SNAPSHOT AND BRANCH: the state of chosen planners of the simulation is copied on the device into one of
+ * LTPL_FLEET_SIM_SNAPSHOTS slots of the fleet (ltpl_fleet_sim_snapshot) and from a slot, or from other planners of the live fleet, into
+ * planners of the live fleet (ltpl_fleet_sim_branch): go back to the tick before a contact, run one situation with many parameter sets,
+ * revive a planner whose error word is set. One kernel (csrc/fleet_branch.hpp: k_fleet_sim_branch, grid = chunks of a planner image x
+ * pairs, 16 bytes per lane) serves all directions; no planner block passes through the host.
+ * THE RULE: what the tick kernels write travels with the state, what the caller set stays the destination's own --
+ *   copied (state)                                                     | stays (configuration)
+ *   the planner block (its memory of ltpl_fleet_*, its error word)     | the race line, the opponents' vel_scale / length
+ *   its window of friction rows, when windows exist on both sides      | statics, zones, preference list, dt, n_export
+ *   now, sel, started, pos_x, pos_y, vel, theta, live                  | the velocity arguments (ltpl_fleet_sim_vel)
+ *   opp_s / opp_tic of its opponents                                   | friction map index and scale
+ *   with telemetry on: its record, grid_s and progress                 | race membership and length as a mate, contact radius
+ *                                                                      | the recorder's ring and indices
+ * - src and dst of a pair carry the same NUMBER of opponents (their offsets may differ; statics may differ): otherwise
+ *   LTPL_ERR_INVALID_ARG, the message names the pair. The entries of dst are distinct. With the live fleet as source no planner is both a
+ *   source and a destination, except a pair src == dst, which is skipped: the copy has no read-after-write hazard and needs no staging.
+ * - The error word is copied: a healthy source revives a failed destination, a failed source fails the destination.
+ * - Host counters are never rewound: the tick counts of the telemetry and the recorder go on counting executed ticks; a copied record
+ *   keeps the source's clear_tick. The recorder is untouched: a recorded destination continues its ring.
+ * - A snapshot has a telemetry part only if telemetry was on when it was taken. ltpl_fleet_sim_telemetry starts every record anew and so
+ *   invalidates the telemetry part of the snapshots held; a branch copies the part only when both sides have one.
+ * - Row windows are allocated by the first call that needs them and never freed. A snapshot taken before they existed holds no block
+ *   that refers to rows; a branch from it leaves the destination's window alone.
+ * - ltpl_fleet_sim_setup drops every snapshot (arrays and opponent counts change); ltpl_fleet_sim_race, _telemetry, _record, _vel and
+ *   ltpl_fleet_friction* do not.
+ * - All four calls need ltpl_fleet_sim_setup first, may come before or after runs, check every argument before the first HIP call,
+ *   synchronise the handle's stream on entry and return after the copy has finished. A failing allocation returns LTPL_ERR_HIP and
+ *   changes nothing. After a branch a per-call ltpl_fleet_calc_vel_profile needs its own ltpl_fleet_calc_paths first, as after a run;
+ *   ltpl_fleet_get_paths / _get_trajectories read the device at every call and so return the branched state.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define LTPL_FLEET_SIM_SNAPSHOTS 8   /* snapshot slots of a fleet */
+
+/* copies the state of the chosen planners (planners == NULL: all n; else n_planners >= 1 distinct indices) into slot `slot`, replacing what
+ * the slot held; everything new is allocated before anything old is freed: a failing call keeps the old snapshot */
+int ltpl_fleet_sim_snapshot(ltpl_fleet* fleet, int32_t slot, const int32_t* planners, int32_t n_planners);
+/* n_planners: planners of the slot (0: empty); planners (may be NULL): their indices in the order given, cap >= that many entries;
+ * bytes (may be NULL): device memory of the slot */
+int ltpl_fleet_sim_snapshot_info(ltpl_fleet* fleet, int32_t slot, int32_t* n_planners, int32_t* planners, int32_t cap, uint64_t* bytes);
+/* frees the slot (an empty slot: nothing to do) */
+int ltpl_fleet_sim_snapshot_drop(ltpl_fleet* fleet, int32_t slot);
+/* for k < n_pairs: planner dst[k] of the LIVE fleet takes the state of planner src[k] of the source: slot == -1 the live fleet, else that
+ * snapshot (an empty slot, or a src[k] that is not one of its planners: LTPL_ERR_INVALID_ARG). n_pairs == 0: nothing to do.
+ * ms (may be NULL): device time of the copy. */
+int ltpl_fleet_sim_branch(ltpl_fleet* fleet, int32_t slot, const int32_t* src, const int32_t* dst, int32_t n_pairs, float* ms);
 
 #ifdef __cplusplus
 }

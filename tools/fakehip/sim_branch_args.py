@@ -1,0 +1,222 @@
+"""TEST TOOL: argument checks of ltpl_fleet_sim_snapshot / _snapshot_info / _snapshot_drop / ltpl_fleet_sim_branch (snapshot and branch of
+the fleet simulation's planner state on the device) without a device. The library's host code built against the stand-in runtime without
+sanitizers (FAKEHIP_SAN=none tools/fakehip/build.sh); kernels do nothing, so no copied state is looked at -- only the return codes, the
+messages, what ``info`` reports and the number of kernel launches:
+  - every refused call (null fleet, no simulation, slot out of range, empty slot, planner index out of range, a planner twice in a
+    snapshot list, a destination twice, a source that is not in the snapshot, unequal opponent counts, a planner that is source and
+    destination with the live fleet as source) returns LTPL_ERR_INVALID_ARG before any device allocation and launches nothing; so does
+    n_pairs == 0, which returns LTPL_OK;
+  - a pair src == dst with the live fleet as source is accepted (and skipped); ltpl_fleet_sim_setup empties every slot;
+  - an allocation failing at each allocation of ltpl_fleet_sim_snapshot leaves the slot's previous content and ``info`` unchanged;
+  - a tick of ltpl_fleet_sim_run launches the same kernels with and without snapshots held; a snapshot and a branch are one launch each."""
+import ctypes
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+from graphbasedlocaltrajectoryplanner_amd import _capi, sim               # noqa: E402
+from graphbasedlocaltrajectoryplanner_amd.fleet import SIM_SNAPSHOTS, Fleet   # noqa: E402
+from graphbasedlocaltrajectoryplanner_amd.lattice import Lattice          # noqa: E402
+
+FAKE = os.path.join(ROOT, "tools", "fakehip", "build_plain", "libltpl_hip_fake.so")
+N = 6
+OPPONENTS = (1, 1, 0, 2, 1, 1)                                            # per planner: the offsets of planners 4 and 5 differ from 0 and 1
+lat = Lattice.load(os.path.join(ROOT, "tests", "golden", "monteblanco_lattice.npz"))
+table = sim.RaceLineTable.from_track(np.load(os.path.join(ROOT, "tests", "golden", "monteblanco_track.npz")))
+hip = _capi.HipBackend(lat, lib_path=FAKE)
+lib = hip.lib
+lib.fakehip_launch_count.restype = ctypes.c_long
+lib.fakehip_fail_malloc_after.argtypes = [ctypes.c_long]
+lib.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
+lib.hipFree.argtypes = [ctypes.c_void_p]
+lib.ltpl_fleet_last_error.restype = ctypes.c_char_p
+lib.ltpl_fleet_last_error.argtypes = [ctypes.c_void_p]
+lib.ltpl_fleet_sim_snapshot.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32]
+lib.ltpl_fleet_sim_snapshot_info.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
+lib.ltpl_fleet_sim_snapshot_drop.argtypes = [ctypes.c_void_p, ctypes.c_int32]
+lib.ltpl_fleet_sim_branch.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
+fleet = Fleet(hip, N)
+h = fleet.handle
+
+
+def quiet(fn):
+    """Runs ``fn`` with an allocation failure armed for the next hipMalloc; asserts that ``fn`` neither allocated (the failure is still
+    pending afterwards) nor launched. Returns ``fn``'s result."""
+    before = lib.fakehip_launch_count()
+    lib.fakehip_fail_malloc_after(1)
+    try:
+        out = fn()
+    finally:
+        p = ctypes.c_void_p()
+        pending = lib.hipMalloc(ctypes.byref(p), 8) != 0
+        if not pending:
+            lib.hipFree(p)
+        lib.fakehip_fail_malloc_after(0)
+    assert pending, "a refused call allocated device memory"
+    assert lib.fakehip_launch_count() == before, "a refused call launched a kernel"
+    return out
+
+
+def msg():
+    return (lib.ltpl_fleet_last_error(h) or b"").decode()
+
+
+def snapshot(slot, planners=None):
+    if planners is None:
+        return lib.ltpl_fleet_sim_snapshot(h, slot, None, 0), msg()
+    idx = np.ascontiguousarray(np.asarray(list(planners) + [0], np.int32))                # (never a null pointer, an empty list included)
+    return lib.ltpl_fleet_sim_snapshot(h, slot, idx.ctypes.data, len(planners)), msg()
+
+
+def info(slot):
+    n, b = ctypes.c_int32(-1), ctypes.c_uint64(0)
+    idx = np.full(N, -1, np.int32)
+    rc = lib.ltpl_fleet_sim_snapshot_info(h, slot, ctypes.byref(n), idx.ctypes.data, N, ctypes.byref(b))
+    return rc, idx[:max(n.value, 0)].tolist(), b.value, msg()
+
+
+def branch(slot, src, dst):
+    s, d = np.ascontiguousarray(np.asarray(src, np.int32)), np.ascontiguousarray(np.asarray(dst, np.int32))
+    ms = ctypes.c_float(-1.0)
+    rc = lib.ltpl_fleet_sim_branch(h, slot, s.ctypes.data if s.size else None, d.ctypes.data if d.size else None, d.size, ctypes.byref(ms))
+    return rc, msg()
+
+
+def expect(rc_msg, text):
+    rc, m = rc_msg[0], rc_msg[-1]
+    assert rc == 1 and text in m, (rc, m, text)                           # LTPL_ERR_INVALID_ARG
+    print("refused (%d): %s" % (rc, m))
+
+
+def launches(fn):
+    before = lib.fakehip_launch_count()
+    out = fn()
+    return lib.fakehip_launch_count() - before, out
+
+
+def fresh():
+    fleet.sim_setup(table, [dict(opponents=[(250.0 + 100.0 * k, 0.3, 5.0) for k in range(no)], pref=("right", "straight"), pos_est=(0.0, 0.0),
+                                 zone_gids=[3]) for no in OPPONENTS])
+    fleet.sim_vel()
+
+
+# null fleet, no simulation
+assert lib.ltpl_fleet_sim_snapshot(None, 0, None, 0) == 1 and lib.ltpl_fleet_sim_snapshot_info(None, 0, None, None, 0, None) == 1
+assert lib.ltpl_fleet_sim_snapshot_drop(None, 0) == 1 and lib.ltpl_fleet_sim_branch(None, -1, None, None, 0, None) == 1
+expect(quiet(lambda: snapshot(0)), "ltpl_fleet_sim_setup first")
+expect(quiet(lambda: info(0)), "ltpl_fleet_sim_setup first")
+assert quiet(lambda: lib.ltpl_fleet_sim_snapshot_drop(h, 0)) == 1 and "ltpl_fleet_sim_setup first" in msg()
+expect(quiet(lambda: branch(-1, [0], [1])), "ltpl_fleet_sim_setup first")
+
+fresh()
+plain = launches(lambda: fleet.sim_run(1, trace=False))[0]
+# slots
+for slot in (-1, SIM_SNAPSHOTS, 1 << 20):
+    expect(quiet(lambda: snapshot(slot)), "out of range")
+    expect(quiet(lambda: info(slot)), "out of range")
+    assert quiet(lambda: lib.ltpl_fleet_sim_snapshot_drop(h, slot)) == 1 and "out of range" in msg()
+for slot in (-2, SIM_SNAPSHOTS):
+    expect(quiet(lambda: branch(slot, [0], [1])), "out of range")
+for slot in range(SIM_SNAPSHOTS):
+    assert quiet(lambda: info(slot))[:3] == (0, [], 0)
+    assert quiet(lambda: lib.ltpl_fleet_sim_snapshot_drop(h, slot)) == 0                  # an empty slot: nothing to do
+    expect(quiet(lambda: branch(slot, [0], [1])), "is empty")
+assert fleet.sim_snapshot_info(3) is None
+# planner lists of a snapshot
+expect(quiet(lambda: snapshot(0, [0, N])), "out of range")
+expect(quiet(lambda: snapshot(0, [-1])), "out of range")
+expect(quiet(lambda: snapshot(0, [1, 4, 1])), "planner 1 is given twice")
+expect(quiet(lambda: snapshot(0, [])), "1 .. n entries")
+assert quiet(lambda: info(0))[:3] == (0, [], 0)
+
+n_launch, rc = launches(lambda: snapshot(2, [4, 1, 3]))
+assert rc[0] == 0 and n_launch == 1, (rc, n_launch)                                     # one launch: k_fleet_sim_branch
+rc, planners, nbytes, _ = info(2)
+assert rc == 0 and planners == [4, 1, 3] and nbytes > 3 * 200000, (rc, planners, nbytes)
+assert fleet.sim_snapshot_info(2)["planners"].tolist() == [4, 1, 3] and fleet.sim_snapshot_info(2)["bytes"] == nbytes
+small = np.zeros(2, np.int32)
+assert quiet(lambda: lib.ltpl_fleet_sim_snapshot_info(h, 2, None, small.ctypes.data, 2, None)) == 1 and "planner buffer" in msg()
+assert launches(lambda: snapshot(5))[0] == 1 and info(5)[1] == list(range(N)) and info(5)[2] > nbytes
+
+# pairs of a branch
+expect(quiet(lambda: branch(-1, [0, N], [1, 4])), "pair 1 (src %d, dst 4): planner index out of range" % N)
+expect(quiet(lambda: branch(-1, [0], [-1])), "pair 0 (src 0, dst -1): planner index out of range")
+expect(quiet(lambda: branch(2, [4, 1], [0, 0])), "pair 1 (src 1, dst 0): the destination is given twice")
+expect(quiet(lambda: branch(2, [4, 0], [5, 1])), "pair 1 (src 0, dst 1): the source is not a planner of snapshot 2")
+expect(quiet(lambda: branch(2, [4, 3], [0, 1])), "pair 1 (src 3, dst 1): the source has 2 opponents, the destination 1")
+expect(quiet(lambda: branch(-1, [0, 1], [4, 2])), "pair 1 (src 1, dst 2): the source has 1 opponents, the destination 0")
+expect(quiet(lambda: branch(-1, [0, 1], [1, 4])), "pair 1 (src 1, dst 4): with the live fleet as source no planner may be both")
+expect(quiet(lambda: branch(-1, [0, 0], [0, 1])), "no planner may be both")              # (the identical pair excepts itself only)
+null_rc = quiet(lambda: lib.ltpl_fleet_sim_branch(h, -1, None, None, 2, None))
+assert null_rc == 1 and "src / dst missing" in msg()
+expect(quiet(lambda: (lib.ltpl_fleet_sim_branch(h, -1, None, None, -1, None), msg())), "n_pairs must not be negative")
+assert quiet(lambda: branch(-1, [], []))[0] == 0 and quiet(lambda: branch(2, [], []))[0] == 0     # n_pairs == 0: LTPL_OK, nothing done
+assert quiet(lambda: branch(-1, [3, 0], [3, 0]))[0] == 0                                # src == dst on the live fleet: accepted, nothing to copy
+n_launch, rc = launches(lambda: branch(-1, [3, 0, 0], [3, 1, 5]))                         # ... also next to real pairs (planner 5: another offset)
+assert rc[0] == 0 and n_launch == 1, (rc, n_launch)
+n_launch, rc = launches(lambda: branch(2, [4, 1, 3, 1], [0, 5, 3, 1]))                    # a snapshot's planner onto itself is a real copy
+assert rc[0] == 0 and n_launch == 1, (rc, n_launch)
+assert fleet.sim_branch(0, [1, 4, 5]) >= 0.0 and fleet.sim_branch(4, [0], snapshot=2) >= 0.0 and fleet.sim_restore(2) >= 0.0
+try:
+    fleet.sim_branch(0, [1], snapshot=2)
+    raise AssertionError("a source outside the snapshot accepted")
+except _capi.BackendError as e:
+    assert "not a planner of snapshot 2" in str(e)
+
+# a run launches what it launched before; the other settings keep the snapshots
+assert launches(lambda: fleet.sim_run(1, trace=False))[0] == plain
+fleet.sim_telemetry()
+assert info(2)[1] == [4, 1, 3] and launches(lambda: branch(2, [4], [0]))[0] == 1          # (no telemetry part: the state alone)
+with_tele = info(2)[2]
+assert snapshot(2, [4, 1, 3])[0] == 0 and info(2)[2] > with_tele                          # taken with telemetry on: the records as well
+fleet.sim_record([0, 1], 4)
+fleet.sim_vel(vel_max=50.0)
+assert info(2)[1] == [4, 1, 3] and info(5)[1] == list(range(N))
+fleet.sim_telemetry(radius=None)
+fleet.sim_record(None)
+assert lib.ltpl_fleet_sim_snapshot_drop(h, 5) == 0 and info(5)[:3] == (0, [], 0) and info(2)[1] == [4, 1, 3]
+fresh()                                                                                   # sim_setup empties every slot
+assert all(info(slot)[:3] == (0, [], 0) for slot in range(SIM_SNAPSHOTS))
+expect(quiet(lambda: branch(2, [4], [0])), "is empty")
+assert snapshot(7)[0] == 0
+fleet.sim_race([2, 4])                                                                    # (races are set before the first run)
+assert info(7)[1] == list(range(N)) and branch(7, [0], [4])[0] == 0
+fresh()
+assert launches(lambda: fleet.sim_run(1, trace=False))[0] == plain
+
+# an allocation failing at each allocation of ltpl_fleet_sim_snapshot: the slot keeps what it held
+for tele in (False, True):
+    failures = 0
+    for k in range(1, 40):
+        fresh()
+        if tele:
+            fleet.sim_telemetry()
+        assert snapshot(1, [5, 0])[0] == 0
+        held = info(1)[:3]
+        lib.fakehip_fail_malloc_after(k)
+        rc, m = snapshot(1, [1, 2, 3])
+        lib.fakehip_fail_malloc_after(0)
+        if rc == 0:
+            assert info(1)[1] == [1, 2, 3]
+            break
+        assert rc == 3 and "hipMalloc" in m, (k, rc, m)                                   # LTPL_ERR_HIP
+        failures += 1
+        assert info(1)[:3] == held and branch(1, [5], [4])[0] == 0, (k, info(1))
+    else:
+        raise AssertionError("ltpl_fleet_sim_snapshot never succeeded")
+    assert failures >= (16 if tele else 13), failures
+    print("allocation failure at each of the %d allocations of ltpl_fleet_sim_snapshot (telemetry %s): previous snapshot kept" % (
+        failures, "on" if tele else "off"))
+# ... and of ltpl_fleet_sim_branch (the pairs' entries): LTPL_ERR_HIP, nothing launched
+fresh()
+lib.fakehip_fail_malloc_after(1)
+n_launch, rc = launches(lambda: branch(-1, [0], [1]))
+lib.fakehip_fail_malloc_after(0)
+assert rc[0] == 3 and "hipMalloc" in rc[1] and n_launch == 0, (rc, n_launch)
+print("launches per tick: %d with and without snapshots; a snapshot and a branch: 1 launch each" % plain)
+fleet.close()
+hip.close()
+print("sim branch args OK")
