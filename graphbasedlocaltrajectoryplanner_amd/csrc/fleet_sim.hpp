@@ -557,6 +557,10 @@ __global__ __launch_bounds__(64) void k_fleet_sim_compact(SimDev sd, int n)
 // ---------------------------------------------------------------------------------------------------------------------
 struct SimSnaps;                            // snapshot slots (fleet_branch.hpp, ltpl_fleet_sim_snapshot)
 static void sim_snaps_free(SimSnaps* s);
+struct SimEvents;                           // scripted events (fleet_events.hpp, ltpl_fleet_sim_events)
+static void sim_events_free(SimEvents* e);
+static int sim_events_check_run(ltpl_fleet* f);                 // before the first launch of a run
+static int sim_events_tick(ltpl_fleet* f, FleetTickIn* t);      // head of a tick: the event kernels, t->any_emerg
 
 struct FleetSim {
     std::vector<void*> allocs;
@@ -584,6 +588,9 @@ struct FleetSim {
     std::vector<int> opp_off;               // [N + 1] host copy of sd.opp_off (ltpl_fleet_sim_branch compares opponent counts)
     int tele_gen = 0;                       // counts the calls of ltpl_fleet_sim_telemetry that took effect: a snapshot's telemetry part belongs to one
     SimSnaps* snaps = nullptr;              // allocated by the first ltpl_fleet_sim_snapshot
+    std::vector<int> st_off, pref_off;      // [N + 1] host copies of sd.st_off / sd.pref_off (ltpl_fleet_sim_events checks local indices)
+    std::vector<int> emerg; int n_emerg = 0;     // [N] host shadow of incl_emerg_traj (stored by ltpl_fleet_sim_vel, followed by the timed events) and its sum
+    SimEvents* events = nullptr;            // the event list of ltpl_fleet_sim_events (null: events are off)
 };
 static void sim_free_list(std::vector<void*>& l)
 {
@@ -599,6 +606,7 @@ static void fleet_sim_free(FleetSim* s)
 {
     if (!s) return;
     sim_snaps_free(s->snaps);
+    sim_events_free(s->events);
     sim_free_list(s->stage_allocs); sim_free_list(s->race_allocs); sim_free_list(s->tele_allocs); sim_free_list(s->rec_allocs);
     for (void* p : s->allocs) (void)hipFree(p);
     if (s->velt.d_buf) (void)hipFree(s->velt.d_buf);
@@ -708,6 +716,7 @@ try {
     const int N = f->D.N, n_obj = n_opp + n_st;
     s->n_opp = n_opp; s->n_obj = n_obj;
     s->opp_off.assign(in->opp_off, in->opp_off + N + 1);
+    s->st_off.assign(in->static_off, in->static_off + N + 1); s->pref_off.assign(in->pref_off, in->pref_off + N + 1);
     SimDev& d = s->sd;
     d.n_rl = in->n_rl; d.dt = in->dt; d.n_export = in->n_export;
     {
@@ -762,6 +771,8 @@ try {
     f->sim->has_vel = false;
     if ((rc = fleet_pack_inputs(f, &f->sim->velt, nullptr, &v, false))) return rc;
     FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    f->sim->emerg.assign((size_t)f->D.N, 0); f->sim->n_emerg = 0;
+    if (in->incl_emerg_traj) for (int p = 0; p < f->D.N; ++p) f->sim->n_emerg += (f->sim->emerg[(size_t)p] = in->incl_emerg_traj[p] ? 1 : 0);
     f->sim->has_vel = true;
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))
@@ -772,8 +783,9 @@ try {
     if (n_ticks < 1) { f->err = "fleet sim: n_ticks must be positive"; return LTPL_ERR_INVALID_ARG; }
     if (trace && doubles_per_tick_planner != LTPL_FLEET_SIM_TRACE_DOUBLES) { f->err = "fleet sim: trace record size mismatch"; return LTPL_ERR_INVALID_ARG; }
     if (!f->sim || !f->sim->has_vel) { f->err = "fleet sim: ltpl_fleet_sim_setup and ltpl_fleet_sim_vel first"; return LTPL_ERR_INVALID_ARG; }
-    int rc = fleet_enter(f);
+    int rc = sim_events_check_run(f);
     if (rc) return rc;
+    if ((rc = fleet_enter(f))) return rc;
     FleetSim& s = *f->sim;
     const int N = f->D.N;
     const size_t rec = (size_t)N * LTPL_FLEET_SIM_TRACE_DOUBLES;
@@ -783,6 +795,9 @@ try {
     if (trace) FLEET_TRY(f, hipMalloc(reinterpret_cast<void**>(&d_trace), sizeof(double) * rec * (size_t)n_ticks));
     FLEET_TRY(f, hipEventCreate(&e0)); FLEET_TRY(f, hipEventCreate(&e1));
     FleetTickIn t = s.velt;
+    // the emergency stage's launches follow the host's shadow of incl_emerg_traj: ltpl_fleet_sim_vel stores it (the same OR as
+    // velt.any_emerg then), timed events change it, and what they wrote stays after the list is switched off
+    t.any_emerg = s.n_emerg > 0 ? 1 : 0;
     t.ob = s.ob; t.zone_off = s.zone_off; t.zone_gid = s.zone_gid;
     t.vin.pos_x = s.sd.pos_x; t.vin.pos_y = s.sd.pos_y; t.vin.vel_est = s.sd.vel;
     t.has_paths = true;
@@ -793,6 +808,7 @@ try {
     FLEET_TRY(f, hipEventRecord(e0, st));
     for (int k = 0; k < n_ticks; ++k) {
         double* tr = d_trace ? d_trace + rec * (size_t)k : nullptr;
+        if (s.events && (rc = sim_events_tick(f, &t))) return rc;
         hipLaunchKernelGGL(k_fleet_sim_step, dim3(N), dim3(64), 0, st, f->args, f->h->lat, s.sd, tr);
         FLEET_TRY(f, hipGetLastError());
         if (s.has_mates) {

@@ -4040,7 +4040,16 @@ static void persist_stop(ltpl_handle* h)
 static int persist_start(ltpl_handle* h, const TickLayout& t, unsigned start_seq)
 {
     ltpl_handle::PersistTick& P = h->pt;
-    if (!P.stream) HIP_TRY(h, hipStreamCreateWithFlags(&P.stream, hipStreamNonBlocking));
+    if (!P.stream) {
+        // at the device's highest stream priority: the runtime keeps its hardware queues per priority, and nothing else of the library
+        // asks for this one by default -- the resident kernel, which never completes, then has a hardware queue that no stream of
+        // another handle (or fleet) shares, whatever their number. On a normal-priority stream it shared one of the (4 by default)
+        // queues with every other stream of the process mapped there: a kernel another handle launched behind it waited for the idle
+        // limit, and every persistent tick started the resident kernel again
+        int lo_p = 0, hi_p = 0;
+        (void)hipDeviceGetStreamPriorityRange(&lo_p, &hi_p);
+        HIP_TRY(h, hipStreamCreateWithPriority(&P.stream, hipStreamNonBlocking, hi_p));
+    }
     if (!P.mb) {
         HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&P.mb), sizeof(TickMailbox), hipHostMallocDefault));
         memset(P.mb, 0, sizeof(TickMailbox));
@@ -4833,3 +4842,4 @@ try { return exp_unary(device, x, out, n, true); } LTPL_ABI_CATCH(nullptr)
 #include "fleet_sim.hpp"
 #include "fleet_branch.hpp"
 #include "fleet_friction.hpp"
+#include "fleet_events.hpp"

@@ -15,6 +15,7 @@ import numpy as np
 from . import _capi
 from .planner import KEY_IDS, KEY_NAMES, PathsView, Planner, PlannerPathsIn, PlannerVelIn, TrajView
 from .sim import TELEMETRY_DOUBLES, TELEMETRY_FIELDS, telemetry_dict      # noqa: F401  (published here: fleet.TELEMETRY_FIELDS)
+from .sim import pack_events as sim_pack_events
 
 
 class SimIn(C.Structure):                 # ltpl_fleet_sim_in (pointer members as plain addresses)
@@ -42,6 +43,11 @@ class SimTeleIn(C.Structure):             # ltpl_fleet_sim_tele_in
     _fields_ = [("radius", C.c_void_p), ("grid_s", C.c_void_p)]
 
 
+class SimEventsIn(C.Structure):            # ltpl_fleet_sim_events_in
+    _fields_ = [("n_events", C.c_int32), ("ev_off", C.c_void_p), ("when_kind", C.c_void_p), ("when_index", C.c_void_p),
+                ("when_value", C.c_void_p), ("set_kind", C.c_void_p), ("set_index", C.c_void_p), ("set_value", C.c_void_p)]
+
+
 class SimRecordHead(C.Structure):         # ltpl_fleet_sim_record_head
     _fields_ = [("tick", C.c_int32), ("planner", C.c_int32), ("error", C.c_int32), ("sel_action", C.c_int32),
                 ("t_now", C.c_double), ("pos_x", C.c_double), ("pos_y", C.c_double), ("vel_est", C.c_double), ("heading", C.c_double),
@@ -51,6 +57,7 @@ class SimRecordHead(C.Structure):         # ltpl_fleet_sim_record_head
 SIM_TRACE_DOUBLES = 8 + 8 + 9 * _capi.PLANNER_MAX_KEYS     # LTPL_FLEET_SIM_TRACE_DOUBLES
 SIM_RECORD_OBJECTS = 96                                    # LTPL_FLEET_SIM_RECORD_OBJECTS
 SIM_SNAPSHOTS = 8                                          # LTPL_FLEET_SIM_SNAPSHOTS
+SIM_MAX_TRIGGERS = 16                                      # LTPL_FLEET_SIM_MAX_TRIGGERS
 
 
 class Fleet(Planner):
@@ -88,6 +95,9 @@ class Fleet(Planner):
             f("sim_snapshot_info").argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_int32, C.POINTER(C.c_uint64)]
             f("sim_snapshot_drop").argtypes = [C.c_void_p, C.c_int32]
             f("sim_branch").argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_float)]
+        if hasattr(self.lib, "ltpl_fleet_sim_events"):
+            f("sim_events").argtypes = [C.c_void_p, C.POINTER(SimEventsIn)]
+            f("sim_events_read").argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         if hasattr(self.lib, "ltpl_fleet_friction"):
             f("friction").argtypes = [C.c_void_p, C.POINTER(FrictionIn)]
             f("friction_scale").argtypes = [C.c_void_p, C.c_void_p]
@@ -328,6 +338,7 @@ class Fleet(Planner):
         si.n_rl, si.t0, si.tic0, si.dt, si.n_export = rows.shape[0], float(t0), float(t0 if tic0 is None else tic0), float(dt), int(n_export)
         self._check(self._fn("sim_setup")(self.handle, C.byref(si)))
         self._sim_opp, self._sim_export = int(arrs["opp_off"][-1]), int(n_export)
+        self._sim_event_order = np.zeros(0, np.int64)       # (sim_setup switches the events off)
 
     def sim_vel(self, ax_tables=None, ax_table_idx=None, **vel_kwargs):
         """Velocity arguments of the following ``sim_run`` calls (keywords of ``calc_vel_profile`` without pos_est / vel_est, scalars or one
@@ -528,6 +539,43 @@ class Fleet(Planner):
         if info is None:
             raise ValueError("sim_restore: snapshot slot %d is empty" % int(slot))
         return self.sim_branch(info["planners"], info["planners"], snapshot=slot)
+
+    # ---- scripted events on the device ----------------------------------------------------------------------------------------------
+    def sim_events(self, events):
+        """Sets the event list of the following ``sim_run`` calls (ltpl_fleet_sim_events; after ``sim_setup``, between runs at any time):
+        a list of ``sim.Event`` -- a condition (a schedule tick, an opponent within a distance, the speed below / above a value, a delay
+        after another event) and one write into the planner's configuration (an opponent's vel_scale / length, a static object, an entry
+        of the preference list, an argument of ``sim_vel``, the grip factor on the friction map). Executed on the device at the head of
+        every tick, each event at most once; the schedule tick counts the ticks run since this call. ``None`` (or an empty list)
+        switches the events off, and so does ``sim_setup``."""
+        events = list(events) if events is not None else []
+        if not events:
+            self._check(self._fn("sim_events")(self.handle, None))
+            self._sim_event_order = np.zeros(0, np.int64)
+            return
+        a = sim_pack_events(events, self.n_scen)
+        ei = SimEventsIn()
+        ei.n_events = len(events)
+        for k in ("ev_off", "when_kind", "when_index", "when_value", "set_kind", "set_index", "set_value"):
+            setattr(ei, k, a[k].ctypes.data)
+        self._check(self._fn("sim_events")(self.handle, C.byref(ei)))
+        self._sim_event_order = a["order"]
+
+    def sim_events_read(self):
+        """dict(fired_tick: int32 array, one entry per event in the order of the list given to ``sim_events`` -- the schedule tick in
+        which it fired, -1: not yet; tick: the schedule tick, i.e. the ticks run since ``sim_events``)."""
+        n, tick = C.c_int32(0), C.c_int32(0)
+        self._check(self._fn("sim_events_read")(self.handle, None, C.byref(n), C.byref(tick)))
+        packed = np.full(max(n.value, 1), -1, np.int32)
+        if n.value:
+            self._check(self._fn("sim_events_read")(self.handle, packed.ctypes.data, None, None))
+        order = getattr(self, "_sim_event_order", np.zeros(0, np.int64))
+        if len(order) != n.value:                          # (a list set through the C entry point itself: the library's order, planner by planner)
+            order = np.arange(n.value)
+        out = np.full(n.value, -1, np.int32)
+        if n.value:
+            out[order] = packed[:n.value]
+        return dict(fired_tick=out, tick=int(tick.value))
 
     # ---- friction maps on the device ------------------------------------------------------------------------------------------------
     def friction(self, maps, map_idx=None, scale=1.0):

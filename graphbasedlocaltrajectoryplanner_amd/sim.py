@@ -316,3 +316,153 @@ class Telemetry(object):
 
     def as_dict(self):
         return telemetry_dict(self.rec, self.L)
+
+
+# ---- scripted events (ltpl_fleet_sim_events, include/ltpl_hip.h; csrc/fleet_events.hpp) ---------------------------------------------
+WHEN_KINDS = {"tick": 0, "opp_within": 1, "vel_below": 2, "vel_above": 3, "after": 4}                       # LTPL_SIM_WHEN_*
+SET_KINDS = {"opp_vel_scale": 0, "opp_length": 1, "static_x": 2, "static_y": 3, "static_theta": 4, "static_v": 5, "static_length": 6,
+             "pref": 7, "vel_max": 8, "gg_scale": 9, "gg_ax": 10, "gg_ay": 11, "safety_d": 12, "incl_emerg": 13,
+             "friction_scale": 14}                                                                             # LTPL_SIM_SET_*
+SET_INDEXED = ("opp_vel_scale", "opp_length", "static_x", "static_y", "static_theta", "static_v", "static_length", "pref")
+MAX_TRIGGERS = 16                                                                                            # LTPL_FLEET_SIM_MAX_TRIGGERS
+_ACT_IDS = {"straight": 0, "follow": 1, "left": 2, "right": 3, "emergency": 4}
+_ACT_NAMES = {v: k for k, v in _ACT_IDS.items()}
+
+
+class Event(object):
+    """One scripted event of planner ``planner``: a condition and one write into the planner's configuration; it fires at most once.
+    ``when``: ("tick", k) | ("opp_within", opponent, distance) | ("vel_below", v) | ("vel_above", v) | ("after", j, delay) with j = the
+    place of an EARLIER state-conditioned event in this planner's own list (the events of the planner in the order given).
+    ``set``: (kind, index, value) for "opp_vel_scale", "opp_length", "static_x" / "_y" / "_theta" / "_v" / "_length" and "pref" (value:
+    an action name or id); (kind, value) for "vel_max", "gg_scale", "gg_ax", "gg_ay", "safety_d", "incl_emerg" (timed only) and
+    "friction_scale"."""
+
+    def __init__(self, planner, when, set):
+        self.planner, self.when, self.set = int(planner), tuple(when), tuple(set)
+        wk = self.when[0]
+        if wk not in WHEN_KINDS or len(self.when) != (2 if wk in ("tick", "vel_below", "vel_above") else 3):
+            raise ValueError("Event: when=%r" % (when,))
+        sk = self.set[0]
+        if sk not in SET_KINDS or len(self.set) != (3 if sk in SET_INDEXED else 2):
+            raise ValueError("Event: set=%r" % (set,))
+        self.when_kind, self.set_kind = WHEN_KINDS[wk], SET_KINDS[sk]
+        self.when_index = int(self.when[1]) if wk in ("tick", "opp_within", "after") else 0
+        self.when_value = 0.0 if wk == "tick" else float(self.when[-1])
+        self.set_index = int(self.set[1]) if sk in SET_INDEXED else 0
+        v = self.set[-1]
+        self.set_value = float(_ACT_IDS[v]) if isinstance(v, str) else float(v)
+
+    def write(self):
+        """The write as (kind name, index, value); the value of "pref" as an action name, of "incl_emerg" as a bool."""
+        sk, v = self.set[0], self.set_value
+        return sk, self.set_index, (_ACT_NAMES.get(int(v), int(v)) if sk == "pref" else bool(v) if sk == "incl_emerg" else v)
+
+    def __repr__(self):
+        return "Event(%d, when=%r, set=%r)" % (self.planner, self.when, self.set)
+
+
+def pack_events(events, n):
+    """The arrays of ``ltpl_fleet_sim_events_in`` for a list of ``Event``: dict of ev_off [n + 1], when_kind, when_index, when_value,
+    set_kind, set_index, set_value and ``order``: order[e] = the place in ``events`` of packed event e (planner by planner, each
+    planner's events in the order given)."""
+    events = list(events)
+    for e in events:
+        if not 0 <= e.planner < n:
+            raise ValueError("event of planner %d: the fleet has %d planners" % (e.planner, n))
+    order = sorted(range(len(events)), key=lambda i: (events[i].planner, i))
+    cnt = np.bincount([e.planner for e in events], minlength=n) if events else np.zeros(n, np.int64)
+    ev = [events[i] for i in order]
+
+    def col(name, dt):
+        a = np.array([getattr(e, name) for e in ev], dt)
+        return np.ascontiguousarray(a if a.size else np.zeros(1, dt))
+    return dict(ev_off=np.ascontiguousarray(np.concatenate(([0], np.cumsum(cnt))).astype(np.int32)),
+                when_kind=col("when_kind", np.int32), when_index=col("when_index", np.int32), when_value=col("when_value", np.float64),
+                set_kind=col("set_kind", np.int32), set_index=col("set_index", np.int32), set_value=col("set_value", np.float64),
+                order=np.asarray(order, np.int64))
+
+
+class EventScript(object):
+    """Host mirror of the scripted events (k_fleet_sim_events_timed / k_fleet_sim_triggers, csrc/fleet_events.hpp) in the same
+    operation order. ``events``: the list given to ``Fleet.sim_events``; ``n``: planners; ``race``: the ``RaceLineTable`` of the simulation
+    (needed by "opp_within" only). ``fired_tick[i]``: schedule tick in which ``events[i]`` fired, -1: not yet; ``tick``: the schedule tick."""
+
+    def __init__(self, events, n, race=None):
+        self.events, self.n = list(events), int(n)
+        packed = pack_events(self.events, self.n)              # (the range checks that need no simulation)
+        self.lists = race.lists() if race is not None else None
+        self.fired_tick = np.full(len(self.events), -1, np.int64)
+        self.tick = 0
+        self.own = [[] for _ in range(self.n)]                 # the planner's events in list order
+        for i in packed["order"]:
+            self.own[self.events[i].planner].append(int(i))
+        for p, own in enumerate(self.own):
+            trig = [i for i in own if self.events[i].when[0] != "tick"]
+            if len(trig) > MAX_TRIGGERS:
+                raise ValueError("planner %d: more than %d triggers" % (p, MAX_TRIGGERS))
+            for j, i in enumerate(own):
+                e = self.events[i]
+                if e.when[0] == "after":
+                    if not 0 <= e.when_index < j or self.events[own[e.when_index]].when[0] == "tick":
+                        raise ValueError("planner %d event %d: 'after' refers to an earlier state-conditioned event of the planner" % (p, j))
+                    if e.when_value < 1 or e.when_value != int(e.when_value):
+                        raise ValueError("planner %d event %d: a delay must be integral and at least 1" % (p, j))
+                if e.set[0] == "incl_emerg" and e.when[0] != "tick":
+                    raise ValueError("planner %d event %d: incl_emerg is timed only" % (p, j))
+        self.timed = {}
+        for i in packed["order"]:
+            if self.events[i].when[0] == "tick":
+                self.timed.setdefault(self.events[i].when_index, []).append(int(i))
+
+    def before_tick(self, state):
+        """The events that fire in front of the next tick, [(place in ``events``, planner, (kind, index, value))] in the order of
+        application: the timed events of the schedule tick, then per planner its triggers in list order. ``state``: what the tick before
+        left (before the first tick: the setup) -- ``pos`` [n][2], ``vel`` [n], ``opp_s`` [n][opponents] (or flat with ``opp_off``
+        [n + 1]), ``failed`` [n] (error flags; default none). A failed planner fires nothing. Advances the schedule tick."""
+        k = self.tick
+        pos, vel, failed = state["pos"], state["vel"], state.get("failed")
+        off = state.get("opp_off")
+        out = []
+
+        def is_failed(p):
+            return failed is not None and bool(failed[p])
+        for i in self.timed.get(k, ()):
+            e = self.events[i]
+            if not is_failed(e.planner):
+                self.fired_tick[i] = k
+                out.append((i, e.planner, e.write()))
+        for p in range(self.n):
+            if is_failed(p):
+                continue
+            for i in self.own[p]:
+                e = self.events[i]
+                wk = e.when[0]
+                if wk == "tick" or self.fired_tick[i] >= 0:
+                    continue
+                v = e.when_value
+                if wk == "opp_within":
+                    s = float(state["opp_s"][off[p] + e.when_index] if off is not None else state["opp_s"][p][e.when_index])
+                    s_rl, xs, ys = self.lists[0], self.lists[1], self.lists[2]
+                    dx = interp(s, s_rl, xs) - float(pos[p][0])
+                    dy = interp(s, s_rl, ys) - float(pos[p][1])
+                    fire = dx * dx + dy * dy <= v * v
+                elif wk == "vel_below":
+                    fire = float(vel[p]) < v
+                elif wk == "vel_above":
+                    fire = float(vel[p]) > v
+                else:
+                    t0 = self.fired_tick[self.own[p][e.when_index]]
+                    fire = t0 >= 0 and k == t0 + int(v)
+                if fire:
+                    self.fired_tick[i] = k
+                    out.append((i, p, e.write()))
+        self.tick += 1
+        return out
+
+    def opp_dist2(self, state, p, q):
+        """dx dx + dy dy of planner ``p`` to its opponent ``q`` as the "opp_within" condition forms it."""
+        off = state.get("opp_off")
+        s = float(state["opp_s"][off[p] + q] if off is not None else state["opp_s"][p][q])
+        dx = interp(s, self.lists[0], self.lists[1]) - float(state["pos"][p][0])
+        dy = interp(s, self.lists[0], self.lists[2]) - float(state["pos"][p][1])
+        return dx * dx + dy * dy

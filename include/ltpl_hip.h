@@ -941,6 +941,92 @@ int ltpl_fleet_sim_snapshot_drop(ltpl_fleet* fleet, int32_t slot);
  * ms (may be NULL): device time of the copy. */
 int ltpl_fleet_sim_branch(ltpl_fleet* fleet, int32_t slot, const int32_t* src, const int32_t* dst, int32_t n_pairs, float* ms);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Additive to ABI v9 -- SCRIPTED EVENTS: a per-planner event list, set once (ltpl_fleet_sim_events) and executed on the device inside
+ * ltpl_fleet_sim_run at the head of every tick, in front of k_fleet_sim_step (csrc/fleet_events.hpp: k_fleet_sim_events_timed,
+ * k_fleet_sim_triggers). An event is a condition (`when`) and ONE write into the planner's configuration (`set`). Every event fires at
+ * most once; the tick in which it fired is kept on the device (ltpl_fleet_sim_events_read).
+ * SCHEDULE TICK: the ticks ltpl_fleet_sim_run has executed since the events were set; 0 for the next tick to run. It goes on across
+ * calls and is never rewound, like the tick counts of the telemetry and the recorder.
+ * CONDITIONS are evaluated before tick k on the state as tick k - 1 left it (before the first tick: the state of ltpl_fleet_sim_setup).
+ * A planner whose error word is set fires nothing: an event whose tick passes meanwhile never fires.
+ *   LTPL_SIM_WHEN_TICK        fires at schedule tick when_index (>= 0); when_value is ignored
+ *   LTPL_SIM_WHEN_OPP_WITHIN  when_index: an opponent of the planner (0 .. count - 1). Fires at the first tick with
+ *                             dx dx + dy dy <= d d, d = when_value (finite, >= 0), dx / dy from the planner's tracked pose to the
+ *                             opponent's position: np.interp of the race line's x / y columns at the opponent's stored arc length
+ *                             (the x / y its last step produced, bit for bit). No sqrt; fp64, no contraction
+ *   LTPL_SIM_WHEN_VEL_BELOW / _VEL_ABOVE   fires at the first tick with vel_est < when_value / vel_est > when_value (strict; finite)
+ *   LTPL_SIM_WHEN_AFTER       when_index: an EARLIER event of the same planner (its place in the planner's list) whose kind is one of the
+ *                             three state conditions or LTPL_SIM_WHEN_AFTER. Fires at fired_tick[that] + when_value, when_value integral
+ *                             and >= 1. A reference to a LTPL_SIM_WHEN_TICK event is LTPL_ERR_INVALID_ARG (use LTPL_SIM_WHEN_TICK)
+ * WRITES (set_index is local to the planner):
+ *   LTPL_SIM_SET_OPP_VEL_SCALE / _OPP_LENGTH                  opponent set_index; finite; scale >= 0, length > 0
+ *   LTPL_SIM_SET_STATIC_X / _Y / _THETA / _V / _LENGTH         static object set_index; finite; length > 0. (No kind lets a static
+ *                                                             "appear": set it up off the track, where ingestion drops it, and move it)
+ *   LTPL_SIM_SET_PREF                                         entry set_index of the preference list (its length stays); an LTPL_ACT_*
+ *   LTPL_SIM_SET_VEL_MAX / _GG_SCALE / _GG_AX / _GG_AY / _SAFETY_D   the planner's element of ltpl_fleet_sim_vel's arrays (set_index 0);
+ *                                                             finite; > 0, safety_d >= 0
+ *   LTPL_SIM_SET_INCL_EMERG                                   incl_emerg_traj of the planner (0 / 1). ONLY with LTPL_SIM_WHEN_TICK (else
+ *                                                             LTPL_ERR_UNSUPPORTED): the host derives the launches of the emergency
+ *                                                             stage from these flags, so it follows them in a shadow of its own, and
+ *                                                             tick k launches exactly what a run split at k launches. The flag itself
+ *                                                             is written whatever the error word (the shadow stays exact); the event of
+ *                                                             a failed planner is still not marked fired
+ *   LTPL_SIM_SET_FRICTION_SCALE                               the planner's grip factor on its friction map (set_index 0); finite > 0.
+ *                                                             A run with such an event and no maps set is refused before its first launch
+ * ORDER: the timed events of tick k are applied first, then the state-conditioned and LTPL_SIM_WHEN_AFTER events ("triggers") that fire
+ * in tick k, per planner in list order: of two triggers that write the same target in the same tick the later one of the list wins. Two
+ * LTPL_SIM_WHEN_TICK events with the same tick, kind, planner and index are refused. Conditions read state only, never configuration: a
+ * write cannot change a condition of the same tick. At most LTPL_FLEET_SIM_MAX_TRIGGERS triggers per planner (LTPL_ERR_CAPACITY); timed
+ * events are unlimited in number.
+ * THE CALL follows the rules of ltpl_fleet_sim_telemetry: after ltpl_fleet_sim_setup at any time, between runs; every argument is checked
+ * before the first HIP call, the message names the planner and the event; everything new is allocated before anything old is freed; a
+ * failing call keeps the previous list, its tick and its fired ticks; a successful call replaces the list, sets the tick to 0 and every
+ * fired tick to -1. in == NULL or n_events == 0 switches the events off, and so does ltpl_fleet_sim_setup.
+ * INTERPLAY: the list, its tick and the fired ticks are the live fleet's own, like the recorder: ltpl_fleet_sim_snapshot / _branch copy
+ * none of it, and what events wrote is configuration, which stays the destination's own. A later ltpl_fleet_sim_vel, ltpl_fleet_friction
+ * or ltpl_fleet_friction_scale sets its arrays anew: events that fired earlier are not applied again. (Those calls may re-allocate their
+ * buffers; the event kernels are handed the target pointers at every launch.) A fleet without events launches per tick exactly the
+ * kernels it launched before, with unchanged arguments; with events a tick has one more launch where a timed event falls on it and one
+ * more while the list holds triggers.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define LTPL_FLEET_SIM_MAX_TRIGGERS 16   /* events of a planner that are not LTPL_SIM_WHEN_TICK */
+#define LTPL_SIM_WHEN_TICK        0
+#define LTPL_SIM_WHEN_OPP_WITHIN  1
+#define LTPL_SIM_WHEN_VEL_BELOW   2
+#define LTPL_SIM_WHEN_VEL_ABOVE   3
+#define LTPL_SIM_WHEN_AFTER       4
+#define LTPL_SIM_SET_OPP_VEL_SCALE   0
+#define LTPL_SIM_SET_OPP_LENGTH      1
+#define LTPL_SIM_SET_STATIC_X        2
+#define LTPL_SIM_SET_STATIC_Y        3
+#define LTPL_SIM_SET_STATIC_THETA    4
+#define LTPL_SIM_SET_STATIC_V        5
+#define LTPL_SIM_SET_STATIC_LENGTH   6
+#define LTPL_SIM_SET_PREF            7
+#define LTPL_SIM_SET_VEL_MAX         8
+#define LTPL_SIM_SET_GG_SCALE        9
+#define LTPL_SIM_SET_GG_AX          10
+#define LTPL_SIM_SET_GG_AY          11
+#define LTPL_SIM_SET_SAFETY_D       12
+#define LTPL_SIM_SET_INCL_EMERG     13
+#define LTPL_SIM_SET_FRICTION_SCALE 14
+
+typedef struct {
+    int32_t n_events;              /* 0 (or in == NULL): switches the events off */
+    const int32_t* ev_off;         /* [n + 1] events of planner p, in list order */
+    const int32_t* when_kind;      /* [n_events] LTPL_SIM_WHEN_*                 */
+    const int32_t* when_index;     /* [n_events]                                 */
+    const double*  when_value;     /* [n_events]                                 */
+    const int32_t* set_kind;       /* [n_events] LTPL_SIM_SET_*                  */
+    const int32_t* set_index;      /* [n_events]                                 */
+    const double*  set_value;      /* [n_events]                                 */
+} ltpl_fleet_sim_events_in;
+int ltpl_fleet_sim_events(ltpl_fleet* fleet, const ltpl_fleet_sim_events_in* in);
+/* fired_tick (may be NULL): [n_events] schedule tick in which event e fired, -1: not yet; n_events (may be NULL): events of the list (0: events
+ * are off); tick (may be NULL): the schedule tick. No simulation: LTPL_ERR_INVALID_ARG. */
+int ltpl_fleet_sim_events_read(ltpl_fleet* fleet, int32_t* fired_tick, int32_t* n_events, int32_t* tick);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,11 @@ the constant tuple. --telemetry: race telemetry on (ltpl_fleet_sim_telemetry, co
 with races); the records of the first planners are printed after the run. --record M: the flight recorder on for M planners spread evenly
 over the fleet (ltpl_fleet_sim_record, ring depth D, default: the run's ticks: k_fleet_sim_rec_paths / k_fleet_sim_rec_vel every tick on the
 unfused launch sequence -- compare with LTPL_FLEET_NO_FUSE=1 and the recorder off); the bytes per record and the last record's summary are
-printed. --lib PATH: another build of the library (A/B against the parent's)."""
+printed. --events: scripted events on (ltpl_fleet_sim_events): per planner one timed gg_scale event at a tick of its own and one opp_within
+trigger on its first opponent (it slows down; the odd planners' threshold lies above the opponent's first distance, the even planners'
+below it, and the opponent drives away: theirs never fires) with a chained "after" (it speeds up again): k_fleet_sim_triggers every tick,
+k_fleet_sim_events_timed in the ticks that hold a timed event; the fired events are counted after the run. --lib PATH: another build of
+the library (A/B against the parent's)."""
 import argparse
 import os
 import sys
@@ -23,7 +27,7 @@ import planner_replay as pr                                                   # 
 from graphbasedlocaltrajectoryplanner_amd import _capi                        # noqa: E402
 from graphbasedlocaltrajectoryplanner_amd.fleet import Fleet                  # noqa: E402
 from graphbasedlocaltrajectoryplanner_amd.lattice import Lattice              # noqa: E402
-from graphbasedlocaltrajectoryplanner_amd.sim import RaceLineTable            # noqa: E402
+from graphbasedlocaltrajectoryplanner_amd.sim import Event, RaceLineTable     # noqa: E402
 
 
 def main():
@@ -37,6 +41,7 @@ def main():
     ap.add_argument("--telemetry", action="store_true", help="race telemetry on (radius 2.5); prints the first planners' records")
     ap.add_argument("--record", type=int, default=0, help="flight recorder on for this many planners, spread evenly over the fleet")
     ap.add_argument("--record-depth", type=int, default=0, help="ring depth of the recorder (default: --ticks)")
+    ap.add_argument("--events", action="store_true", help="scripted events on: a timed gg_scale event and an opp_within trigger with a chained after per planner")
     ap.add_argument("--lib", default=None, help="path of the library to load (default: the in-tree build)")
     a = ap.parse_args()
     lat = Lattice.load(os.path.join(ROOT, "tests", "golden", "monteblanco_lattice.npz"))
@@ -81,6 +86,13 @@ def main():
             fleet.sim_telemetry(radius=2.5)
         if a.record:
             fleet.sim_record([int(q) for q in np.linspace(0, n - 1, a.record).round()] if a.record > 1 else [0], a.record_depth or a.ticks)
+        if a.events:
+            ev = []
+            for p in range(n):
+                ev += [Event(p, when=("tick", (37 * p) % a.ticks), set=("gg_scale", 0.9 - 0.2 * (p % 8) / 7.0)),
+                       Event(p, when=("opp_within", 0, 250.0 + 10.0 * (p % 16) + (5.0 if p % 2 else -20.0)), set=("opp_vel_scale", 0, 0.2)),
+                       Event(p, when=("after", 1, 40), set=("opp_vel_scale", 0, 0.5))]
+            fleet.sim_events(ev)
         t0 = time.perf_counter()
         failed = 0
         try:
@@ -96,6 +108,10 @@ def main():
         if failed == 0:
             sel = np.bincount(fleet.sim_state()['sel_action'] + 1, minlength=6)
             print("  last selected actions (none, straight, follow, left, right, emergency): %s" % sel.tolist())
+        if a.events:
+            ft = fleet.sim_events_read()["fired_tick"].reshape(n, 3)
+            print("  events: %d timed, %d opp_within and %d chained 'after' events fired of %d each (schedule tick %d)" % (
+                np.count_nonzero(ft[:, 0] >= 0), np.count_nonzero(ft[:, 1] >= 0), np.count_nonzero(ft[:, 2] >= 0), n, fleet.sim_events_read()["tick"]))
         if a.record and rep == a.reps - 1:
             info = fleet.sim_record_info()
             t1 = time.perf_counter()
