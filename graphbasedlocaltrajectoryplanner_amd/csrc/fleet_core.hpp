@@ -340,7 +340,12 @@ FLT_FN Foot project_on_polyline(const X& x, const Poly& p, double qx, double qy,
     if (closed) { i1 = nb - 1; i2 = nb + 1; if (i2 > p.n - 1) i2 = 0; }
     else { i1 = nb - 1 > 0 ? nb - 1 : 0; i2 = nb + 1 < p.n - 1 ? nb + 1 : p.n - 1; }
     const int i1p = i1 < 0 ? i1 + p.n : i1;
-    const int ord = angle_order(p.px(nb), p.py(nb), qx, qy, p.px(i1p), p.py(i1p), p.px(i2), p.py(i2));      // |a1| vs |a2|
+    // A neighbour that the open polyline's clamp put onto nb itself (nb = 0 / nb = n - 1): the reference has ang1 (ang2) == 0 exactly and never
+    // takes the degenerate segment a == b; the cosines of angle_order compare |u|^2 |v| with itself up to rounding and did (s = 0 / 0). Start:
+    // the reference's own form (its 0 for ang2 == 0 decides the index pair); end: the first segment (the reference's 0 there is its own 0 / 0).
+    const int ord = (!closed && i2 == nb) ? 1
+                  : (!closed && i1 == nb) ? angle_order_atan2(p.px(nb), p.py(nb), qx, qy, p.px(i1p), p.py(i1p), p.px(i2), p.py(i2))
+                  : angle_order(p.px(nb), p.py(nb), qx, qy, p.px(i1p), p.py(i1p), p.px(i2), p.py(i2));      // |a1| vs |a2|
     Foot f; f.s = 0.0;
     if (want_s) {
         const bool first = ord > 0;

@@ -753,8 +753,16 @@ __device__ __forceinline__ double angle3pt_dev(double ax, double ay, double bx, 
 // monotone there: |ang1| > |ang2|  <=>  u.v1 / |v1| < u.v2 / |v2|  (|u| cancels). Two dot products and two square roots instead
 // of four atan2 (~600 instructions per projection). Degenerate vectors (pos on a polyline point) take the atan2 form.
 // Returns -1 / 0 / +1 for |ang1| < / == / > |ang2|.
-__device__ __forceinline__ int angle_order_dev(double nx, double ny, double px, double py, double x1, double y1, double x2, double y2)
+// `clamp1` / `clamp2`: the open polyline's index clamp put neighbour 1 / 2 onto the closest point itself (nb = 0 / nb = n - 1). The reference
+// then has ang1 (ang2) == 0 EXACTLY -- both atan2 calls see the same vectors -- and never takes the degenerate segment a == b, while the
+// cosines compare |u|^2 |v| with itself up to rounding (Cauchy-Schwarz equality) and did, for queries collinear with the end segment:
+// t = 0 / 0, s = NaN. Neighbour 1 clamped: -1 (the reference's 0 for ang2 == 0 selects the same segment and the same first index);
+// neighbour 2 clamped: +1 (the reference's 0 for ang1 == 0 is its own 0 / 0).
+__device__ __forceinline__ int angle_order_dev(double nx, double ny, double px, double py, double x1, double y1, double x2, double y2,
+                                               bool clamp1 = false, bool clamp2 = false)
 {
+    if (clamp2) return 1;
+    if (clamp1) return -1;
     const double ux = nx - px, uy = ny - py, v1x = x1 - px, v1y = y1 - py, v2x = x2 - px, v2y = y2 - py;
     const double n1 = v1x * v1x + v1y * v1y, n2 = v2x * v2x + v2y * v2y, nu = ux * ux + uy * uy;
     if (!(n1 > 0.0) || !(n2 > 0.0) || !(nu > 0.0)) {
@@ -782,7 +790,7 @@ __device__ __forceinline__ double get_s_coord_dev(int n, const double* x, const 
     const double nx = x[(size_t)nb * stride], ny = y[(size_t)nb * stride];
     const double x1 = x[(size_t)i1 * stride], y1 = y[(size_t)i1 * stride];
     const double x2 = x[(size_t)i2 * stride], y2 = y[(size_t)i2 * stride];
-    const int ord = angle_order_dev(nx, ny, px, py, x1, y1, x2, y2);
+    const int ord = angle_order_dev(nx, ny, px, py, x1, y1, x2, y2, i1 == nb, i2 == nb);
     double ax, ay, bx, by;
     if (ord > 0) { ax = x1; ay = y1; bx = nx; by = ny; } else { ax = nx; ay = ny; bx = x2; by = y2; }
     const double t = ((px - ax) * (bx - ax) + (py - ay) * (by - ay)) / ((bx - ax) * (bx - ax) + (by - ay) * (by - ay));
@@ -2404,7 +2412,7 @@ __global__ __launch_bounds__(64) void k_follow_prep(DevLat lat, DevPathsIn in, D
             const int i1 = nb - 1 > 0 ? nb - 1 : 0, i2 = nb + 1 < n - 1 ? nb + 1 : n - 1;
             const dbl2 pN = *reinterpret_cast<const dbl2*>(xy + 2 * kep_row(nb)), p1 = *reinterpret_cast<const dbl2*>(xy + 2 * kep_row(i1)),
                        p2 = *reinterpret_cast<const dbl2*>(xy + 2 * kep_row(i2));
-            const int ord = angle_order_dev(pN.x, pN.y, px, py, p1.x, p1.y, p2.x, p2.y);
+            const int ord = angle_order_dev(pN.x, pN.y, px, py, p1.x, p1.y, p2.x, p2.y, i1 == nb, i2 == nb);
             double ax, ay, bx, by;
             if (ord > 0) { ax = p1.x; ay = p1.y; bx = pN.x; by = pN.y; } else { ax = pN.x; ay = pN.y; bx = p2.x; by = p2.y; }
             const double t = ((px - ax) * (bx - ax) + (py - ay) * (by - ay)) / ((bx - ax) * (bx - ax) + (by - ay) * (by - ay));
@@ -4843,3 +4851,62 @@ try { return exp_unary(device, x, out, n, true); } LTPL_ABI_CATCH(nullptr)
 #include "fleet_branch.hpp"
 #include "fleet_friction.hpp"
 #include "fleet_events.hpp"
+
+#ifdef LTPL_EXPERIMENT
+// experiment build only: the device's projections of a point on a polyline (get_s_coord.py:8-99), one form per call, for nq caller-provided
+// queries on a caller-provided polyline (x, y, s: n entries each, host memory). form 0: get_s_coord_dev (one wave per query; i1_out = -1),
+// 1: globrl_index_dev (one wave per query) and 2: lane_globrl_index (one lane per query) through a DevLat in which only grx, gry and G are
+// set (closed lines; s_out = NaN, i1_out = -1), 3: project_on_polyline of fleet_core.hpp through WaveX (one wave per query).
+__global__ __launch_bounds__(64) void k_exp_project(int form, int n, const double* x, const double* y, const double* s, int closed, int nq,
+                                                    const double* qx, const double* qy, double* s_out, int* i0_out, int* i1_out)
+{
+    const int lane = threadIdx.x;
+    if (form == 2) {
+        const int q0 = (int)blockIdx.x * 64 + lane, q = q0 < nq ? q0 : nq - 1;      // (idle lanes repeat the last query: every lane must call)
+        DevLat lat; memset(&lat, 0, sizeof(lat));
+        lat.grx = x; lat.gry = y; lat.G = n + 1;
+        const int idx = lane_globrl_index(lat, qx[q], qy[q]);
+        if (q0 < nq) { s_out[q] = NAN; i0_out[q] = idx; i1_out[q] = -1; }
+        return;
+    }
+    const int q = (int)blockIdx.x;
+    if (q >= nq) return;
+    double sv = NAN; int i0 = -1, i1 = -1;
+    if (form == 0) sv = get_s_coord_dev(n, x, y, 1, s, 1, qx[q], qy[q], closed != 0, lane, &i0);
+    else if (form == 1) {
+        DevLat lat; memset(&lat, 0, sizeof(lat));
+        lat.grx = x; lat.gry = y; lat.G = n + 1;
+        i0 = globrl_index_dev(lat, qx[q], qy[q], lane);
+    } else {
+        const WaveX wx{lane};
+        const fleet::Poly pl{x, y, 1, n};
+        const fleet::Foot f = fleet::project_on_polyline(wx, pl, qx[q], qy[q], closed != 0, true, s, 1, n);
+        sv = f.s; i0 = f.i0; i1 = f.i1;
+    }
+    if (lane == 0) { s_out[q] = sv; i0_out[q] = i0; i1_out[q] = i1; }
+}
+extern "C" int ltpl_exp_project(int32_t device, int32_t form, int32_t n, const double* x, const double* y, const double* s, int32_t closed,
+                                int32_t nq, const double* qx, const double* qy, double* s_out, int32_t* i0_out, int32_t* i1_out)
+try {
+    if (!x || !y || !s || !qx || !qy || !s_out || !i0_out || !i1_out || n < 2 || nq <= 0 || form < 0 || form > 3) return LTPL_ERR_INVALID_ARG;
+    if ((form == 1 || form == 2) && !closed) return LTPL_ERR_INVALID_ARG;
+    if (hipSetDevice(device) != hipSuccess) return LTPL_ERR_HIP;
+    double* d = nullptr; int* di = nullptr;
+    int rc = LTPL_OK;
+    const size_t bn = sizeof(double) * (size_t)n, bq = sizeof(double) * (size_t)nq, iq = sizeof(int) * (size_t)nq;
+    if (hipMalloc(&d, 3 * bn + 3 * bq) != hipSuccess) return LTPL_ERR_HIP;
+    if (hipMalloc(&di, 2 * iq) != hipSuccess) { (void)hipFree(d); return LTPL_ERR_HIP; }
+    double* dx = d; double* dy = d + n; double* ds = d + 2 * (size_t)n; double* dqx = d + 3 * (size_t)n; double* dqy = dqx + nq; double* dso = dqy + nq;
+    if (hipMemcpy(dx, x, bn, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dy, y, bn, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(ds, s, bn, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dqx, qx, bq, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dqy, qy, bq, hipMemcpyHostToDevice) != hipSuccess) rc = LTPL_ERR_HIP;
+    if (!rc) {
+        const unsigned blocks = form == 2 ? (unsigned)((nq + 63) / 64) : (unsigned)nq;
+        hipLaunchKernelGGL(k_exp_project, dim3(blocks), dim3(64), 0, 0, form, n, dx, dy, ds, closed, nq, dqx, dqy, dso, di, di + nq);
+        if (hipGetLastError() != hipSuccess || hipMemcpy(s_out, dso, bq, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(i0_out, di, iq, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(i1_out, di + nq, iq, hipMemcpyDeviceToHost) != hipSuccess) rc = LTPL_ERR_HIP;
+    }
+    (void)hipFree(d); (void)hipFree(di);
+    return rc;
+} LTPL_ABI_CATCH(nullptr)
+#endif

@@ -44,7 +44,9 @@
  * (-DLTPL_EXPERIMENT -> libltpl_hip_exp.so, used by tools/ and one fault-injection test) and do not exist in libltpl_hip.so.
  * The experiment build also exports the check entry points of tests/test_gpu_wave_ops.py (host arrays in, one launch, host arrays out):
  * ltpl_exp_wave_ops_check, ltpl_exp_heading_atan2, ltpl_exp_heading_sincos, ltpl_exp_fast_rcp, ltpl_exp_rsqrt_cubed -- the device
- * helpers of csrc/paths_team.hpp applied to caller-provided values.
+ * helpers of csrc/paths_team.hpp applied to caller-provided values -- and ltpl_exp_project of tests/test_gpu_projection.py: the device's
+ * projections of a point on a polyline (get_s_coord_dev, globrl_index_dev, lane_globrl_index, project_on_polyline of csrc/fleet_core.hpp)
+ * for caller-provided queries on a caller-provided polyline.
  */
 #ifndef LTPL_HIP_H
 #define LTPL_HIP_H

@@ -33,6 +33,33 @@ def build(force=False):
     return LIB
 
 
+def _project(lib_path, entry, x, y, s, closed, qx, qy):
+    import numpy as np
+    x, y, s, qx, qy = (np.ascontiguousarray(a, np.float64) for a in (x, y, s, qx, qy))
+    assert x.shape == y.shape == s.shape and x.ndim == 1 and qx.shape == qy.shape and qx.ndim == 1
+    fn = getattr(C.CDLL(lib_path), entry)
+    fn.argtypes = [C.c_int32, _capi._pf64, _capi._pf64, _capi._pf64, C.c_int32, C.c_int32, _capi._pf64, _capi._pf64, _capi._pf64, _capi._pi32]
+    s_out, idx = np.empty(qx.size, np.float64), np.empty((qx.size, 2), np.int32)
+    pd = lambda a: a.ctypes.data_as(_capi._pf64)
+    rc = fn(x.size, pd(x), pd(y), pd(s), int(bool(closed)), qx.size, pd(qx), pd(qy), pd(s_out), idx.ctypes.data_as(_capi._pi32))
+    if rc != 0:
+        raise _capi.BackendError("%s: status %d" % (entry, rc))
+    return s_out, idx
+
+
+def get_s_coord(x, y, s, closed, qx, qy):
+    """The oracle's get_s_coord (oracle_get_s_coord) for arrays of queries on a caller's polyline: (s [nq], index pair [nq, 2])."""
+    return _project(build(), "oracle_get_s_coord", x, y, s, closed, qx, qy)
+
+
+def project_host(form, x, y, s, closed, qx, qy):
+    """The host instantiation of project_on_polyline of csrc/planner_core.hpp (``form`` "planner_core") or csrc/fleet_core.hpp ("fleet_core")
+    through oracle/planner_host_shim.cpp: (s [nq], index pair [nq, 2])."""
+    from oracle import planner_host
+    return _project(planner_host.build(), {"planner_core": "oracle_project_planner_core", "fleet_core": "oracle_project_fleet_core"}[form],
+                    x, y, s, closed, qx, qy)
+
+
 class OracleBackend(object):
     def __init__(self, lattice: Lattice):
         build()

@@ -39,6 +39,31 @@ int oracle_raceline_s(const ltpl_lattice_desc* d, double x, double y, double* s_
     *s_out = ltplp::raceline_s(lat, x, y);
     return LTPL_OK;
 }
+// the two host instantiations of project_on_polyline (csrc/planner_core.hpp and csrc/fleet_core.hpp with its one-lane policy) for nq queries
+// on a caller's polyline (x, y, s_arr: n entries each): s_out[nq], idx_out[nq][2] (tests/test_projection_cases_host.py)
+int oracle_project_planner_core(int32_t n, const double* x, const double* y, const double* s_arr, int32_t closed, int32_t nq,
+                                const double* qx, const double* qy, double* s_out, int32_t* idx_out)
+{
+    if (n < 1 || nq < 0 || !x || !y || !s_arr || !qx || !qy || !s_out || !idx_out) return LTPL_ERR_INVALID_ARG;
+    const ltplp::Poly pl{x, y, 1, n};
+    for (int q = 0; q < nq; ++q) {
+        const ltplp::Foot f = ltplp::project_on_polyline(pl, qx[q], qy[q], closed != 0, true, [&](int i) { return s_arr[i]; }, n);
+        s_out[q] = f.s; idx_out[2 * q] = f.i0; idx_out[2 * q + 1] = f.i1;
+    }
+    return LTPL_OK;
+}
+int oracle_project_fleet_core(int32_t n, const double* x, const double* y, const double* s_arr, int32_t closed, int32_t nq,
+                              const double* qx, const double* qy, double* s_out, int32_t* idx_out)
+{
+    if (n < 1 || nq < 0 || !x || !y || !s_arr || !qx || !qy || !s_out || !idx_out) return LTPL_ERR_INVALID_ARG;
+    const fleet::Poly pl{x, y, 1, n};
+    const fleet::HostX hx{};
+    for (int q = 0; q < nq; ++q) {
+        const fleet::Foot f = fleet::project_on_polyline(hx, pl, qx[q], qy[q], closed != 0, true, s_arr, 1, n);
+        s_out[q] = f.s; idx_out[2 * q] = f.i0; idx_out[2 * q + 1] = f.i1;
+    }
+    return LTPL_OK;
+}
 int oracle_planner_destroy(ltpl_planner* p) { delete p; return LTPL_OK; }
 int oracle_planner_get_caps(const ltpl_planner* p, ltpl_planner_caps* c) { return ltplp::api_get_caps(p, c); }
 const char* oracle_planner_last_error(const ltpl_planner* p) { return p ? p->P.err.c_str() : g_err.c_str(); }
