@@ -398,13 +398,18 @@ struct EdgeRegs { double c; unsigned meta; };     // meta: sweep-order edge word
 
 // goal node of layer j for filter f from the frontier distances in `dcur` (virtual goal edges, GraphBase.py:188-194):
 // lexicographic min over (dist + vgoal, dist, node); returns node | (tie << 30) or -1
+// WIDE: the layer may hold more than 64 nodes (runtime LDS plans), a lane then more than one of them -- two nodes of ONE lane at the least
+// total are a tie as well
+template <bool WIDE>
 __device__ __forceinline__ int team_goal(const DevLat& lat, const double* dcur, int v0, int Kb, int lane)
 {
     double g1 = INFINITY, g2 = INFINITY; int gn = 0x7fffffff;
+    [[maybe_unused]] bool dup = false;
     for (int n = lane; n < Kb; n += 64) {
         const double bestc = dcur[n];
         if (bestc < INFINITY) {
             const double tot = bestc + at(lat.vgoal, v0 + n);
+            if constexpr (WIDE) { if (tot < g1) dup = false; else if (tot == g1) dup = true; }
             if (tot < g1 || (tot == g1 && (bestc < g2 || (bestc == g2 && n < gn)))) { g1 = tot; g2 = bestc; gn = n; }
         }
     }
@@ -412,7 +417,11 @@ __device__ __forceinline__ int team_goal(const DevLat& lat, const double* dcur, 
     const double mt = wave_min_f64(g1);
     if (!(mt < INFINITY)) return -1;
     const unsigned long long eq = __ballot(g1 == mt);
-    if ((eq & (eq - 1ull)) == 0ull) return __builtin_amdgcn_readlane(gn, __ffsll((long long)eq) - 1);
+    if ((eq & (eq - 1ull)) == 0ull) {
+        const int one = __ffsll((long long)eq) - 1;
+        if constexpr (WIDE) return __builtin_amdgcn_readlane(gn | (dup ? 1 << 30 : 0), one);
+        else return __builtin_amdgcn_readlane(gn, one);
+    }
     double m1 = g1, m2 = g2; int mn = gn;
     wave_min3(m1, m2, mn);
     return mn | (1 << 30);                                     // (two or more lanes attain the total: the flag of the round-3 form)
@@ -529,7 +538,7 @@ __device__ LTPL_RESWEEP_ATTR void team_resweep(const DevLat& lat, const DevPaths
     }
     int b = sc.sl + J; if (b >= L) b -= L;
     const int v0 = at(layer_off, b), Kb = at(layer_off, b + 1) - v0;
-    const int g = team_goal(lat, dist + (size_t)(f * 2 + (J & 1)) * kpad, v0, Kb, lane);
+    const int g = team_goal<!P::fixed>(lat, dist + (size_t)(f * 2 + (J & 1)) * kpad, v0, Kb, lane);
     if (lane == 0) best[f * P::hmax(lp) + J] = g;
     wave_sync_lds();
 }
@@ -1959,7 +1968,7 @@ __device__ __forceinline__ WavePath team_paths_body(const DevLat& lat_, const De
             const int4 lyH = lay[H];
             for (int f = swave; f < NFILT; f += SWN)
                 if (((need >> f) & 1u) && best[f * hm + H] == -2) {
-                    const int g = team_goal(lat, dist + (size_t)(f * 2 + (H & 1)) * kpad, lyH.x, lyH.y & 0xffff, lane);
+                    const int g = team_goal<!P::fixed>(lat, dist + (size_t)(f * 2 + (H & 1)) * kpad, lyH.x, lyH.y & 0xffff, lane);
                     if (lane == 0) best[f * hm + H] = g;
                 }
         }
