@@ -6,6 +6,9 @@
 //                        compaction inside the planner's range), ego tracker (trajectory staged in LDS, two-nearest search across the wave,
 //                        the 1 ms loop on lane 0)
 //                        and its heading (psi of the two rows around the same s, read in place, interpolated across the +-pi wrap)
+//                        With sensor noise set (ltpl_fleet_sim_noise; the generator: fleet_noise.hpp) the tick launches k_fleet_sim_step_noise
+//                        and k_fleet_sim_mates_noise instead: the same bodies, every object perturbed in its ingestion lane before
+//                        process_object_dev and the planner's pos_est / vel_est written behind the tracker (registers only, no LDS added)
 //   k_fleet_sim_mates    (races with more than one planner only: ltpl_fleet_sim_race) one wave64 per planner, one lane per mate: every
 //                        other planner of the race, at the pose / speed / heading its tracker wrote above, through the same ingestion,
 //                        appended behind the planner's opponents and statics. Its own launch: every tracker of the tick is done first
@@ -24,6 +27,8 @@
 //   trajectories, so the tape's "next paths_pre inside the last kernel" fusion does not apply: paths_pre is launched on its own.
 // The host mirrors of the same arithmetic are graphbasedlocaltrajectoryplanner_amd/sim.py.
 #pragma once
+
+#include "fleet_noise.hpp"
 
 namespace fleet {
 
@@ -101,6 +106,17 @@ struct SimDev {
     int* prev_action; double* t_now; int* veh_off; double* o_r; double* o_v; double* o_px; double* o_py;   // the tick's fleet::FObj arrays
 };
 
+// sensor noise (ltpl_fleet_sim_noise): what the noisy forms of k_fleet_sim_step / k_fleet_sim_mates get besides SimDev. The plain kernels
+// carry none of it.
+struct SimNoise {
+    const uint64_t* seed;                  // [N]
+    const double* sigma;                   // [5][N]: pos, vel, obj_pos, obj_theta, obj_vel
+    double* est_x; double* est_y; double* est_v;   // [N] the planner's pos_est / vel_est of the tick (ltpl_fleet_sim_estimate)
+    double* g_tx; double* g_ty;            // true x, y of every kept object, next to the perceived g_x / g_y (telemetry measures against truth)
+    uint32_t tick;                         // tick0 + fleet ticks since the noise was set
+};
+enum { NZ_POS = 0, NZ_VEL, NZ_OBJ_POS, NZ_OBJ_THETA, NZ_OBJ_VEL, NZ_SIGMAS };
+
 struct SimBest { double d; int i; };
 __device__ __forceinline__ SimBest sim_better(SimBest a, SimBest b) { return (b.d < a.d || (b.d == a.d && b.i < a.i)) ? b : a; }
 __device__ __forceinline__ SimBest sim_wave_min(SimBest v)
@@ -110,7 +126,10 @@ __device__ __forceinline__ SimBest sim_wave_min(SimBest v)
     return v;
 }
 
-__global__ __launch_bounds__(64) void k_fleet_sim_step(FleetArgs F, DevLat lat, SimDev sd, double* trace /* this tick's records or null */)
+// the body of k_fleet_sim_step (NOISE false: `nz` is not touched and the code is the one without noise) and of k_fleet_sim_step_noise: every
+// object perturbed in its ingestion lane (registers only: no LDS is added), the ego estimate written behind the tracker by lane 0
+template <bool NOISE>
+__device__ __forceinline__ void sim_step_body(const FleetArgs& F, const DevLat& lat, const SimDev& sd, double* trace, const SimNoise& nz)
 {
     const int p = blockIdx.x, lane = threadIdx.x; const WaveX x{lane};
     const fleet::Block B{F.state + F.D.stride * (size_t)p, F.D, nullptr};
@@ -174,14 +193,27 @@ __global__ __launch_bounds__(64) void k_fleet_sim_step(FleetArgs F, DevLat lat, 
             for (int b0 = 0; b0 < nobj; b0 += 64) {
                 const int k = b0 + lane;
                 ObjIngest r{0, 0.0, 0.0, 0.0};
-                if (k < nobj) r = process_object_dev(lat, 0.2, ox[k], oy[k], oth[k], ov[k], ol[k]);     // ObjectListInterface.py:121
+                double kx = 0.0, ky = 0.0, kth = 0.0, kv = 0.0;          // the object as the planner perceives it
+                if (k < nobj) {
+                    kx = ox[k]; ky = oy[k]; kth = oth[k]; kv = ov[k];
+                    if constexpr (NOISE) {
+                        const uint64_t seed = nz.seed[p]; const int N = (int)gridDim.x;
+                        const double sp = nz.sigma[(size_t)NZ_OBJ_POS * N + p];
+                        kx = fleet::noise_add(kx, sp, seed, nz.tick, (uint32_t)k, 0);
+                        ky = fleet::noise_add(ky, sp, seed, nz.tick, (uint32_t)k, 1);
+                        kth = fleet::noise_add(kth, nz.sigma[(size_t)NZ_OBJ_THETA * N + p], seed, nz.tick, (uint32_t)k, 2);
+                        kv = fleet::noise_add_speed(kv, nz.sigma[(size_t)NZ_OBJ_VEL * N + p], seed, nz.tick, (uint32_t)k, 3);
+                    }
+                    r = process_object_dev(lat, 0.2, kx, ky, kth, kv, ol[k]);     // ObjectListInterface.py:121
+                }
                 const bool keep = k < nobj && r.on_track;
                 const unsigned long long m = __ballot(keep);
                 const int idx = cnt + __popcll(m & ((1ull << lane) - 1ull));
                 if (keep) {
-                    sd.g_x[base + idx] = ox[k]; sd.g_y[base + idx] = oy[k]; sd.g_px[base + idx] = r.pred_x; sd.g_py[base + idx] = r.pred_y;
-                    sd.g_r[base + idx] = r.radius; sd.g_v[base + idx] = ov[k];
-                    if (idx == 0) { first_xy[0] = ox[k]; first_xy[1] = oy[k]; }
+                    sd.g_x[base + idx] = kx; sd.g_y[base + idx] = ky; sd.g_px[base + idx] = r.pred_x; sd.g_py[base + idx] = r.pred_y;
+                    sd.g_r[base + idx] = r.radius; sd.g_v[base + idx] = kv;
+                    if constexpr (NOISE) { nz.g_tx[base + idx] = ox[k]; nz.g_ty[base + idx] = oy[k]; }
+                    if (idx == 0) { first_xy[0] = kx; first_xy[1] = ky; }
                 }
                 cnt += __popcll(m);
             }
@@ -230,6 +262,13 @@ __global__ __launch_bounds__(64) void k_fleet_sim_step(FleetArgs F, DevLat lat, 
         if (!failed && !S.err) {
             sd.now[p] = now; sd.sel[p] = sel; sd.started[p] = 1; sd.pos_x[p] = pos_x; sd.pos_y[p] = pos_y; sd.vel[p] = vel;
             sd.theta[p] = theta;
+            if constexpr (NOISE) {          // the estimate the fleet's tick reads as pos_est / vel_est; the true pose stays in sd
+                const uint64_t seed = nz.seed[p]; const int N = (int)gridDim.x;
+                const double sp = nz.sigma[(size_t)NZ_POS * N + p];
+                nz.est_x[p] = fleet::noise_add(pos_x, sp, seed, nz.tick, fleet::kNoiseEgo, 0);
+                nz.est_y[p] = fleet::noise_add(pos_y, sp, seed, nz.tick, fleet::kNoiseEgo, 1);
+                nz.est_v[p] = fleet::noise_add_speed(vel, nz.sigma[(size_t)NZ_VEL * N + p], seed, nz.tick, fleet::kNoiseEgo, 2);
+            }
         }
         sd.live[p] = !failed && !S.err;
         sd.cnt[p] = cnt; sd.prev_action[p] = sd.sel[p]; sd.t_now[p] = sd.now[p];
@@ -240,11 +279,20 @@ __global__ __launch_bounds__(64) void k_fleet_sim_step(FleetArgs F, DevLat lat, 
     }
     if (failed) fleet_store(x, B, &S, p, F.err_word);
 }
+__global__ __launch_bounds__(64) void k_fleet_sim_step(FleetArgs F, DevLat lat, SimDev sd, double* trace /* this tick's records or null */)
+{
+    sim_step_body<false>(F, lat, sd, trace, SimNoise{});
+}
+__global__ __launch_bounds__(64) void k_fleet_sim_step_noise(FleetArgs F, DevLat lat, SimDev sd, double* trace, SimNoise nz)
+{
+    sim_step_body<true>(F, lat, sd, trace, nz);
+}
 
 // the planner's mates (every other planner of its race, ascending) as objects at their tracked pose, speed and heading: the ingestion of
 // k_fleet_sim_step, appended behind the opponents and statics that step kept. A failed planner takes no objects; a failed mate stays at
 // its last state. Trace fields [5] .. [7] of step are completed here.
-__global__ __launch_bounds__(64) void k_fleet_sim_mates(DevLat lat, SimDev sd, double* trace /* this tick's records or null */)
+template <bool NOISE>
+__device__ __forceinline__ void sim_mates_body(const DevLat& lat, const SimDev& sd, double* trace, const SimNoise& nz)
 {
     const int p = blockIdx.x, lane = threadIdx.x;
     const int lo = sd.mate_lo[p], hi = sd.mate_hi[p];
@@ -256,10 +304,21 @@ __global__ __launch_bounds__(64) void k_fleet_sim_mates(DevLat lat, SimDev sd, d
         const int q = b0 + lane;
         const bool mate = q < hi && q != p;
         ObjIngest r{0, 0.0, 0.0, 0.0};
-        double qx = 0.0, qy = 0.0, qv = 0.0;
+        double qx = 0.0, qy = 0.0, qv = 0.0, tx = 0.0, ty = 0.0;
         if (mate) {
             qx = sd.pos_x[q]; qy = sd.pos_y[q]; qv = sd.vel[q];
-            r = process_object_dev(lat, 0.2, qx, qy, sd.theta[q], qv, sd.mate_len[q]);     // ObjectListInterface.py:121
+            double qth = sd.theta[q];
+            if constexpr (NOISE) {          // the mate as planner p perceives it: p's seed, the mate's place in the race
+                const uint64_t seed = nz.seed[p]; const int N = (int)gridDim.x;
+                const uint32_t obj = fleet::kNoiseMate | (uint32_t)(q - lo);
+                const double sp = nz.sigma[(size_t)NZ_OBJ_POS * N + p];
+                tx = qx; ty = qy;
+                qx = fleet::noise_add(qx, sp, seed, nz.tick, obj, 0);
+                qy = fleet::noise_add(qy, sp, seed, nz.tick, obj, 1);
+                qth = fleet::noise_add(qth, nz.sigma[(size_t)NZ_OBJ_THETA * N + p], seed, nz.tick, obj, 2);
+                qv = fleet::noise_add_speed(qv, nz.sigma[(size_t)NZ_OBJ_VEL * N + p], seed, nz.tick, obj, 3);
+            }
+            r = process_object_dev(lat, 0.2, qx, qy, qth, qv, sd.mate_len[q]);     // ObjectListInterface.py:121
         }
         const bool keep = mate && r.on_track;
         const unsigned long long m = __ballot(keep);
@@ -267,6 +326,7 @@ __global__ __launch_bounds__(64) void k_fleet_sim_mates(DevLat lat, SimDev sd, d
         if (keep) {
             sd.g_x[base + idx] = qx; sd.g_y[base + idx] = qy; sd.g_px[base + idx] = r.pred_x; sd.g_py[base + idx] = r.pred_y;
             sd.g_r[base + idx] = r.radius; sd.g_v[base + idx] = qv;
+            if constexpr (NOISE) { nz.g_tx[base + idx] = tx; nz.g_ty[base + idx] = ty; }
             if (idx == 0 && o) { o[6] = qx; o[7] = qy; }
         }
         cnt += __popcll(m);
@@ -275,6 +335,14 @@ __global__ __launch_bounds__(64) void k_fleet_sim_mates(DevLat lat, SimDev sd, d
         sd.cnt[p] = cnt;
         if (o) o[5] = (double)cnt;
     }
+}
+__global__ __launch_bounds__(64) void k_fleet_sim_mates(DevLat lat, SimDev sd, double* trace /* this tick's records or null */)
+{
+    sim_mates_body<false>(lat, sd, trace, SimNoise{});
+}
+__global__ __launch_bounds__(64) void k_fleet_sim_mates_noise(DevLat lat, SimDev sd, double* trace, SimNoise nz)
+{
+    sim_mates_body<true>(lat, sd, trace, nz);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -295,7 +363,9 @@ struct SimTele {
     double* prog;                          // [N] grid_s + dist of the last live tick (-inf before the first: behind everybody)
 };
 
-__global__ __launch_bounds__(64) void k_fleet_sim_tele(SimDev sd, SimTele te, int tick)
+// `g_tx`, `g_ty` (null while the noise is off): the true positions of the tick's objects. Clearance and contacts are measured against
+// them; the planner was handed the perceived g_x / g_y.
+__global__ __launch_bounds__(64) void k_fleet_sim_tele(SimDev sd, SimTele te, int tick, const double* g_tx, const double* g_ty)
 {
     const int p = blockIdx.x, lane = threadIdx.x;
     if (!sd.live[p]) return;
@@ -304,11 +374,12 @@ __global__ __launch_bounds__(64) void k_fleet_sim_tele(SimDev sd, SimTele te, in
     const double s = fabs(px) <= 1e100 && fabs(py) <= 1e100 ? get_s_coord_dev(te.n_rl, te.rl_x, te.rl_y, 1, te.rl_s, 1, px, py, true, lane, nullptr) : NAN;
     // smallest clearance over the objects the planner is handed this tick (first smallest: the lower slot)
     const int base = sd.obj_base[p], cnt = sd.cnt[p];
+    const double* gx = g_tx ? g_tx : sd.g_x; const double* gy = g_tx ? g_ty : sd.g_y;
     double cd = INFINITY; int ci = 0x7fffffff;
     for (int b0 = 0; b0 < cnt; b0 += 64) {
         const int k = b0 + lane;
         if (k < cnt) {
-            const double dx = sd.g_x[base + k] - px, dy = sd.g_y[base + k] - py;
+            const double dx = gx[base + k] - px, dy = gy[base + k] - py;
             const double c = sqrt(dx * dx + dy * dy) - sd.g_r[base + k];
             if (c < cd) { cd = c; ci = k; }
         }
@@ -591,6 +662,10 @@ struct FleetSim {
     std::vector<int> st_off, pref_off;      // [N + 1] host copies of sd.st_off / sd.pref_off (ltpl_fleet_sim_events checks local indices)
     std::vector<int> emerg; int n_emerg = 0;     // [N] host shadow of incl_emerg_traj (stored by ltpl_fleet_sim_vel, followed by the timed events) and its sum
     SimEvents* events = nullptr;            // the event list of ltpl_fleet_sim_events (null: events are off)
+    std::vector<void*> noise_allocs;        // seeds and sigmas of ltpl_fleet_sim_noise
+    SimNoise nz{};                          // est_x / est_y / est_v live in `allocs` (ltpl_fleet_sim_setup), g_tx / g_ty in the staging
+    bool has_noise = false;                 // the tick launches k_fleet_sim_step_noise / k_fleet_sim_mates_noise and reads pos_est / vel_est from nz.est_*
+    int noise_tick0 = 0, noise_tick = 0;    // tick0; ticks of ltpl_fleet_sim_run since the noise was set
 };
 static void sim_free_list(std::vector<void*>& l)
 {
@@ -608,6 +683,7 @@ static void fleet_sim_free(FleetSim* s)
     sim_snaps_free(s->snaps);
     sim_events_free(s->events);
     sim_free_list(s->stage_allocs); sim_free_list(s->race_allocs); sim_free_list(s->tele_allocs); sim_free_list(s->rec_allocs);
+    sim_free_list(s->noise_allocs);
     for (void* p : s->allocs) (void)hipFree(p);
     if (s->velt.d_buf) (void)hipFree(s->velt.d_buf);
     delete s;
@@ -632,7 +708,7 @@ static int sim_upload(ltpl_fleet* f, FleetSim* s, const T* src, size_t n, T** ou
 struct SimStage {
     SimAllocs a;
     int* obj_base = nullptr; int* pos_off = nullptr;
-    double* g[6] = {};                      // g_x, g_y, g_px, g_py, g_r, g_v
+    double* g[8] = {};                      // g_x, g_y, g_px, g_py, g_r, g_v; g_tx, g_ty (written and read only while sensor noise is set)
     double* o[4] = {};                      // o_r, o_v, o_px, o_py
 };
 static int sim_stage_alloc(ltpl_fleet* f, const std::vector<int>& slots, SimStage* st)
@@ -661,6 +737,7 @@ static void sim_stage_commit(FleetSim* s, SimStage* st)
     d.obj_base = st->obj_base;
     d.g_x = st->g[0]; d.g_y = st->g[1]; d.g_px = st->g[2]; d.g_py = st->g[3]; d.g_r = st->g[4]; d.g_v = st->g[5];
     d.o_r = st->o[0]; d.o_v = st->o[1]; d.o_px = st->o[2]; d.o_py = st->o[3];
+    s->nz.g_tx = st->g[6]; s->nz.g_ty = st->g[7];
     s->ob = fleet::FObj{d.prev_action, d.t_now, d.veh_off, st->pos_off, d.o_r, d.o_v, d.o_px, d.o_py};
 }
 
@@ -743,6 +820,7 @@ try {
     SIM_UP(d.pos_x, in->pos_est_x, N); SIM_UP(d.pos_y, in->pos_est_y, N); SIM_UP(d.vel, in->vel_est, N);
     SIM_UP(d.theta, (const double*)nullptr, N); SIM_UP(d.live, (const int*)nullptr, N);
     SIM_UP(d.cnt, (const int*)nullptr, N);
+    SIM_UP(s->nz.est_x, in->pos_est_x, N); SIM_UP(s->nz.est_y, in->pos_est_y, N); SIM_UP(s->nz.est_v, in->vel_est, N);
     SIM_UP(d.prev_action, sel.data(), N); SIM_UP(d.t_now, now.data(), N); SIM_UP(d.veh_off, (const int*)nullptr, N + 1);
     int* zo = nullptr; int* zg = nullptr;
     SIM_UP(zo, in->zone_off, N + 1); SIM_UP(zg, in->zone_gid, n_zone);
@@ -800,6 +878,7 @@ try {
     t.any_emerg = s.n_emerg > 0 ? 1 : 0;
     t.ob = s.ob; t.zone_off = s.zone_off; t.zone_gid = s.zone_gid;
     t.vin.pos_x = s.sd.pos_x; t.vin.pos_y = s.sd.pos_y; t.vin.vel_est = s.sd.vel;
+    if (s.has_noise) { t.vin.pos_x = s.nz.est_x; t.vin.pos_y = s.nz.est_y; t.vin.vel_est = s.nz.est_v; }   // get_ref_idx and the velocity stage see the estimate
     t.has_paths = true;
     hipStream_t st = f->h->stream;
     s.ran = true;
@@ -809,14 +888,22 @@ try {
     for (int k = 0; k < n_ticks; ++k) {
         double* tr = d_trace ? d_trace + rec * (size_t)k : nullptr;
         if (s.events && (rc = sim_events_tick(f, &t))) return rc;
-        hipLaunchKernelGGL(k_fleet_sim_step, dim3(N), dim3(64), 0, st, f->args, f->h->lat, s.sd, tr);
+        if (s.has_noise) {
+            // (the tick advances whether or not a planner is live: a draw depends on the fleet's tick, not on the planner's history)
+            s.nz.tick = (uint32_t)s.noise_tick0 + (uint32_t)s.noise_tick++;
+            hipLaunchKernelGGL(k_fleet_sim_step_noise, dim3(N), dim3(64), 0, st, f->args, f->h->lat, s.sd, tr, s.nz);
+        } else {
+            hipLaunchKernelGGL(k_fleet_sim_step, dim3(N), dim3(64), 0, st, f->args, f->h->lat, s.sd, tr);
+        }
         FLEET_TRY(f, hipGetLastError());
         if (s.has_mates) {
-            hipLaunchKernelGGL(k_fleet_sim_mates, dim3(N), dim3(64), 0, st, f->h->lat, s.sd, tr);
+            if (s.has_noise) hipLaunchKernelGGL(k_fleet_sim_mates_noise, dim3(N), dim3(64), 0, st, f->h->lat, s.sd, tr, s.nz);
+            else hipLaunchKernelGGL(k_fleet_sim_mates, dim3(N), dim3(64), 0, st, f->h->lat, s.sd, tr);
             FLEET_TRY(f, hipGetLastError());
         }
         if (s.has_tele) {
-            hipLaunchKernelGGL(k_fleet_sim_tele, dim3(N), dim3(64), 0, st, s.sd, s.te, s.tele_tick++);
+            hipLaunchKernelGGL(k_fleet_sim_tele, dim3(N), dim3(64), 0, st, s.sd, s.te, s.tele_tick++,
+                               (const double*)(s.has_noise ? s.nz.g_tx : nullptr), (const double*)(s.has_noise ? s.nz.g_ty : nullptr));
             FLEET_TRY(f, hipGetLastError());
             if (s.has_mates) {
                 hipLaunchKernelGGL(k_fleet_sim_rank, dim3(N), dim3(64), 0, st, s.sd, s.te);
@@ -1148,5 +1235,112 @@ try {
             }
         }
     }
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+// ---------------------------------------------------------------------------------------------------------------------
+// sensor noise (ltpl_fleet_sim_noise, include/ltpl_hip.h; the generator: fleet_noise.hpp)
+// ---------------------------------------------------------------------------------------------------------------------
+// every argument is checked before the first HIP call
+static int sim_check_noise(ltpl_fleet* f, const ltpl_fleet_sim_noise_in* in)
+{
+    const int N = f->D.N;
+    auto bad = [&](const char* why) { f->err = std::string("fleet sim noise: ") + why; return LTPL_ERR_INVALID_ARG; };
+    if (!f->sim) return bad("ltpl_fleet_sim_setup first");
+    if (!in) return LTPL_OK;
+    if (!in->seed) return bad("seed missing");
+    if (in->tick0 < 0) return bad("tick0 must not be negative");
+    const double* sg[NZ_SIGMAS] = {in->sigma_pos, in->sigma_vel, in->sigma_obj_pos, in->sigma_obj_theta, in->sigma_obj_vel};
+    for (const double* a : sg)
+        if (a) for (int p = 0; p < N; ++p) if (!std::isfinite(a[p]) || !(a[p] >= 0.0)) return bad("a sigma must be finite and not negative");
+    return LTPL_OK;
+}
+
+extern "C" int ltpl_fleet_sim_noise(ltpl_fleet* f, const ltpl_fleet_sim_noise_in* in)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    int rc = sim_check_noise(f, in);
+    if (rc) return rc;
+    if ((rc = fleet_enter(f))) return rc;
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    FleetSim& s = *f->sim;
+    if (!in) {
+        sim_free_list(s.noise_allocs);
+        s.nz.seed = nullptr; s.nz.sigma = nullptr; s.has_noise = false; s.noise_tick0 = s.noise_tick = 0;
+        return LTPL_OK;
+    }
+    const size_t N = (size_t)f->D.N;
+    std::vector<double> sigma(NZ_SIGMAS * N, 0.0);
+    const double* sg[NZ_SIGMAS] = {in->sigma_pos, in->sigma_vel, in->sigma_obj_pos, in->sigma_obj_theta, in->sigma_obj_vel};
+    for (int c = 0; c < NZ_SIGMAS; ++c) if (sg[c]) std::copy(sg[c], sg[c] + N, sigma.begin() + (size_t)c * N);
+    // everything new is allocated first; the fleet keeps its previous noise and its tick count unless every step succeeds
+    SimAllocs a;
+    uint64_t* d_seed = nullptr; double* d_sigma = nullptr;
+    if ((rc = sim_upload(f, a.p, in->seed, N, &d_seed))) return rc;
+    if ((rc = sim_upload(f, a.p, sigma.data(), sigma.size(), &d_sigma))) return rc;
+    if (!s.has_noise) {                     // until the first noisy tick the estimate is the true state
+        FLEET_TRY(f, hipMemcpy(s.nz.est_x, s.sd.pos_x, 8 * N, hipMemcpyDeviceToDevice));
+        FLEET_TRY(f, hipMemcpy(s.nz.est_y, s.sd.pos_y, 8 * N, hipMemcpyDeviceToDevice));
+        FLEET_TRY(f, hipMemcpy(s.nz.est_v, s.sd.vel, 8 * N, hipMemcpyDeviceToDevice));
+    }
+    sim_free_list(s.noise_allocs);
+    s.noise_allocs.swap(a.p);
+    s.nz.seed = d_seed; s.nz.sigma = d_sigma; s.has_noise = true; s.noise_tick0 = in->tick0; s.noise_tick = 0;
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+extern "C" int ltpl_fleet_sim_estimate(ltpl_fleet* f, double* x, double* y, double* v)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    if (!f->sim) { f->err = "fleet sim noise: ltpl_fleet_sim_setup first"; return LTPL_ERR_INVALID_ARG; }
+    FLEET_TRY(f, hipSetDevice(f->h->device));
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    const FleetSim& s = *f->sim;
+    const size_t n = (size_t)f->D.N;
+    if (x) FLEET_TRY(f, hipMemcpy(x, s.has_noise ? s.nz.est_x : s.sd.pos_x, 8 * n, hipMemcpyDeviceToHost));
+    if (y) FLEET_TRY(f, hipMemcpy(y, s.has_noise ? s.nz.est_y : s.sd.pos_y, 8 * n, hipMemcpyDeviceToHost));
+    if (v) FLEET_TRY(f, hipMemcpy(v, s.has_noise ? s.nz.est_v : s.sd.vel, 8 * n, hipMemcpyDeviceToHost));
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+// the test hook of the generator: one lane per tuple
+__global__ __launch_bounds__(256) void k_fleet_noise_draws(const uint64_t* seed, const uint32_t* tick, const uint32_t* obj, const uint32_t* comp, int n,
+                                                           double* g, uint32_t* words /* [n][12] or null */)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    uint32_t w[12];
+    g[i] = fleet::noise_gauss(seed[i], tick[i], obj[i], comp[i], w);
+    if (words) for (int k = 0; k < 12; ++k) words[(size_t)i * 12 + k] = w[k];
+}
+
+extern "C" int ltpl_fleet_sim_noise_draws(ltpl_fleet* f, const uint64_t* seed, const uint32_t* tick, const uint32_t* obj, const uint32_t* comp, int32_t n,
+                                          double* g, uint32_t* words)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    auto bad = [&](const char* why) { f->err = std::string("fleet sim noise: ") + why; return LTPL_ERR_INVALID_ARG; };
+    if (n < 0) return bad("n must not be negative");
+    if (n > 0 && (!seed || !tick || !obj || !comp || !g)) return bad("seed / tick / obj / comp / g missing");
+    if (n == 0) return LTPL_OK;
+    int rc = fleet_enter(f);
+    if (rc) return rc;
+    const size_t m = (size_t)n;
+    // seed [n] u64 | g [n] f64 | tick, obj, comp [n] 32 bit each | words [n][12] u32
+    unsigned char* d = nullptr;
+    struct Guard { void* a = nullptr; ~Guard() { if (a) (void)hipFree(a); } } gd;
+    FLEET_TRY(f, hipMalloc(reinterpret_cast<void**>(&d), (8 + 8 + 12 + 48) * m)); gd.a = d;
+    uint64_t* d_seed = reinterpret_cast<uint64_t*>(d); double* d_g = reinterpret_cast<double*>(d + 8 * m);
+    uint32_t* d_tick = reinterpret_cast<uint32_t*>(d + 16 * m); uint32_t* d_obj = reinterpret_cast<uint32_t*>(d + 20 * m);
+    uint32_t* d_comp = reinterpret_cast<uint32_t*>(d + 24 * m); uint32_t* d_words = reinterpret_cast<uint32_t*>(d + 28 * m);
+    FLEET_TRY(f, hipMemcpy(d_seed, seed, 8 * m, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d_tick, tick, 4 * m, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d_obj, obj, 4 * m, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d_comp, comp, 4 * m, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_fleet_noise_draws, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, f->h->stream, (const uint64_t*)d_seed, (const uint32_t*)d_tick,
+                       (const uint32_t*)d_obj, (const uint32_t*)d_comp, (int)n, d_g, words ? d_words : (uint32_t*)nullptr);
+    FLEET_TRY(f, hipGetLastError());
+    FLEET_TRY(f, hipMemcpyAsync(g, d_g, 8 * m, hipMemcpyDeviceToHost, f->h->stream));
+    if (words) FLEET_TRY(f, hipMemcpyAsync(words, d_words, 48 * m, hipMemcpyDeviceToHost, f->h->stream));
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))

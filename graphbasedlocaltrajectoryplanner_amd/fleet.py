@@ -48,6 +48,11 @@ class SimEventsIn(C.Structure):            # ltpl_fleet_sim_events_in
                 ("when_value", C.c_void_p), ("set_kind", C.c_void_p), ("set_index", C.c_void_p), ("set_value", C.c_void_p)]
 
 
+class SimNoiseIn(C.Structure):             # ltpl_fleet_sim_noise_in
+    _fields_ = [("seed", C.c_void_p), ("sigma_pos", C.c_void_p), ("sigma_vel", C.c_void_p), ("sigma_obj_pos", C.c_void_p),
+                ("sigma_obj_theta", C.c_void_p), ("sigma_obj_vel", C.c_void_p), ("tick0", C.c_int32)]
+
+
 class SimRecordHead(C.Structure):         # ltpl_fleet_sim_record_head
     _fields_ = [("tick", C.c_int32), ("planner", C.c_int32), ("error", C.c_int32), ("sel_action", C.c_int32),
                 ("t_now", C.c_double), ("pos_x", C.c_double), ("pos_y", C.c_double), ("vel_est", C.c_double), ("heading", C.c_double),
@@ -98,6 +103,10 @@ class Fleet(Planner):
         if hasattr(self.lib, "ltpl_fleet_sim_events"):
             f("sim_events").argtypes = [C.c_void_p, C.POINTER(SimEventsIn)]
             f("sim_events_read").argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        if hasattr(self.lib, "ltpl_fleet_sim_noise"):
+            f("sim_noise").argtypes = [C.c_void_p, C.POINTER(SimNoiseIn)]
+            f("sim_estimate").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            f("sim_noise_draws").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         if hasattr(self.lib, "ltpl_fleet_friction"):
             f("friction").argtypes = [C.c_void_p, C.POINTER(FrictionIn)]
             f("friction_scale").argtypes = [C.c_void_p, C.c_void_p]
@@ -576,6 +585,45 @@ class Fleet(Planner):
         if n.value:
             out[order] = packed[:n.value]
         return dict(fired_tick=out, tick=int(tick.value))
+
+    # ---- seeded sensor noise on the device --------------------------------------------------------------------------------------------
+    def sim_noise(self, seed=None, pos=0.0, vel=0.0, obj_pos=0.0, obj_theta=0.0, obj_vel=0.0, tick0=0):
+        """Localisation and perception errors of the following ``sim_run`` calls (ltpl_fleet_sim_noise; after ``sim_setup``, between runs
+        at any time). ``seed``: 64-bit seed (scalar or one per planner; None switches the noise off); standard deviations, scalars or one
+        per planner: ``pos`` [m] and ``vel`` [m/s] of the planner's own estimate, ``obj_pos`` [m], ``obj_theta`` [rad], ``obj_vel`` [m/s]
+        of every opponent, static object and mate it perceives. A sigma of 0 draws nothing. ``tick0``: the noise tick of the next tick
+        to run (draws depend on seed, tick, object and component only: ``sim.noise_gauss``, ``sim.NoiseModel``)."""
+        if seed is None:
+            self._check(self._fn("sim_noise")(self.handle, None))
+            return
+        n = self.n_scen
+        ni = SimNoiseIn()
+        keep = [np.ascontiguousarray(np.broadcast_to(np.asarray(seed, np.uint64), (n,)))]
+        ni.seed, ni.tick0 = keep[0].ctypes.data, int(tick0)
+        for name, v in (("sigma_pos", pos), ("sigma_vel", vel), ("sigma_obj_pos", obj_pos), ("sigma_obj_theta", obj_theta),
+                        ("sigma_obj_vel", obj_vel)):
+            keep.append(np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float64), (n,))))
+            setattr(ni, name, keep[-1].ctypes.data)
+        self._check(self._fn("sim_noise")(self.handle, C.byref(ni)))
+
+    def sim_estimate(self):
+        """dict(pos_est [n, 2], vel_est [n]): what every planner was handed as its pose and speed in the last tick
+        (ltpl_fleet_sim_estimate); the true state of ``sim_state`` while the noise is off."""
+        x, y, v = (np.zeros(self.n_scen, np.float64) for _ in range(3))
+        self._check(self._fn("sim_estimate")(self.handle, x.ctypes.data, y.ctypes.data, v.ctypes.data))
+        return dict(pos_est=np.column_stack((x, y)), vel_est=v)
+
+    def sim_noise_draws(self, seed, tick, obj, comp, words=False):
+        """g(seed, tick, obj, comp) for arrays of tuples (they broadcast), evaluated on the device (ltpl_fleet_sim_noise_draws); equals
+        ``sim.noise_gauss`` bit for bit. ``words=True``: returns (g, [n, 12] uint32 output words of the generator)."""
+        a = np.broadcast_arrays(np.asarray(seed, np.uint64), np.asarray(tick, np.uint32), np.asarray(obj, np.uint32), np.asarray(comp, np.uint32))
+        sd, tk, ob, cp = (np.ascontiguousarray(v.reshape(-1)) for v in a)
+        n = int(sd.size)
+        g = np.zeros(n, np.float64)
+        w = np.zeros((max(n, 1), 12), np.uint32) if words else None
+        self._check(self._fn("sim_noise_draws")(self.handle, sd.ctypes.data, tk.ctypes.data, ob.ctypes.data, cp.ctypes.data, n, g.ctypes.data,
+                                                None if w is None else w.ctypes.data))
+        return (g, w[:n]) if words else g
 
     # ---- friction maps on the device ------------------------------------------------------------------------------------------------
     def friction(self, maps, map_idx=None, scale=1.0):

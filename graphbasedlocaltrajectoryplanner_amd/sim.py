@@ -19,6 +19,12 @@ and of the race telemetry of ``ltpl_fleet_sim_telemetry`` (a record per planner,
 
   ``Telemetry``      the rules of include/ltpl_hip.h in the operation order of k_fleet_sim_tele / k_fleet_sim_rank.
 
+and of the seeded sensor noise of ``ltpl_fleet_sim_noise`` (csrc/fleet_noise.hpp) --
+
+  ``philox4x32``     Philox4x32-10, scalars or arrays;
+  ``noise_gauss``    the noise sample g(seed, tick, obj, comp): integer arithmetic and exact fp64 steps, so the device's bits;
+  ``NoiseModel``     what a planner perceives of itself, of its objects and of its mates, in the operation order of the kernels.
+
 Both simulators restate ``np.interp`` (numpy's ``arr_interp``) in the operation order of the device functions (``interp_at`` here,
 ``fleet::sim_interp`` there), so that host and device give the same bits as the reference.
 """
@@ -466,3 +472,90 @@ class EventScript(object):
         dx = interp(s, self.lists[0], self.lists[1]) - float(state["pos"][p][0])
         dy = interp(s, self.lists[0], self.lists[2]) - float(state["pos"][p][1])
         return dx * dx + dy * dy
+
+
+# ---- seeded sensor noise (ltpl_fleet_sim_noise, include/ltpl_hip.h; csrc/fleet_noise.hpp) ------------------------------------------------
+NOISE_EGO = 0xFFFFFFFF          # obj of the ego estimate
+NOISE_MATE = 0x80000000         # obj of mate q of a race: NOISE_MATE | (q - first planner of the race)
+_M32 = np.uint64(0xFFFFFFFF)
+_S32 = np.uint64(32)
+
+
+def philox4x32(counter, key):
+    """Philox4x32-10: ``counter`` 4 words, ``key`` 2 words (ints or arrays that broadcast) -> tuple of 4 output words (uint32)."""
+    c = [np.asarray(v, np.uint64) & _M32 for v in counter]
+    k0, k1 = (np.asarray(v, np.uint64) & _M32 for v in key)
+    m0, m1, w0, w1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57), np.uint64(0x9E3779B9), np.uint64(0xBB67AE85)
+    for _ in range(10):
+        p0, p1 = m0 * c[0], m1 * c[2]                      # (32 x 32 bits: no overflow of the uint64)
+        c = [(p1 >> _S32) ^ c[1] ^ k0, p1 & _M32, (p0 >> _S32) ^ c[3] ^ k1, p0 & _M32]
+        k0, k1 = (k0 + w0) & _M32, (k1 + w1) & _M32
+    return tuple(np.asarray(v).astype(np.uint32) for v in c)
+
+
+def noise_words(seed, tick, obj, comp):
+    """[..., 12] uint32: the output words of the three blocks (tick, obj, 3 comp + b, 0), b = 0, 1, 2, under the key (seed low, seed high)."""
+    seed = np.asarray(seed, np.uint64)
+    comp = np.asarray(comp, np.uint64)
+    out = []
+    for b in range(3):
+        out += philox4x32((tick, obj, np.uint64(3) * comp + np.uint64(b), 0), (seed & _M32, seed >> _S32))
+    return np.stack(np.broadcast_arrays(*out), axis=-1)
+
+
+def noise_gauss(seed, tick, obj, comp):
+    """g(seed, tick, obj, comp): the sum K of the 12 words, ((double)K + 6.0) 2^-32 - 6.0 -- twelve uniforms minus six. Every step is exact
+    in fp64. Scalars give a float, arrays an array."""
+    k = noise_words(seed, tick, obj, comp).astype(np.uint64).sum(axis=-1, dtype=np.uint64)
+    g = (k.astype(np.float64) + 6.0) * 2.0 ** -32 - 6.0
+    return float(g) if g.ndim == 0 else g
+
+
+class NoiseModel(object):
+    """Host mirror of the sensor noise of k_fleet_sim_step_noise / k_fleet_sim_mates_noise: ``value + sigma * g`` (one multiply, one add), a
+    sigma of 0 draws nothing and hands the value through, speeds clamped at 0. ``seed`` and the sigmas: scalars or one per planner;
+    ``races``: sizes summing to ``n`` (default: every planner alone)."""
+
+    def __init__(self, n, seed, pos=0.0, vel=0.0, obj_pos=0.0, obj_theta=0.0, obj_vel=0.0, races=None):
+        self.n = int(n)
+        self.seed = [int(v) for v in np.broadcast_to(np.asarray(seed, np.uint64), (self.n,))]
+
+        def per(v):
+            return [float(x) for x in np.broadcast_to(np.asarray(v, np.float64), (self.n,))]
+        self.pos, self.vel, self.obj_pos, self.obj_theta, self.obj_vel = per(pos), per(vel), per(obj_pos), per(obj_theta), per(obj_vel)
+        sizes = [1] * self.n if races is None else [len(r) if isinstance(r, range) else int(r) for r in races]
+        if sum(sizes) != self.n:
+            raise ValueError("NoiseModel: the races must cover the planners")
+        self.lo, self.hi = [0] * self.n, [0] * self.n
+        a = 0
+        for sz in sizes:
+            for p in range(a, a + sz):
+                self.lo[p], self.hi[p] = a, a + sz
+            a += sz
+
+    def _add(self, v, sigma, p, tick, obj, comp, speed=False):
+        if sigma == 0.0:
+            return float(v)
+        w = float(v) + sigma * noise_gauss(self.seed[p], tick, obj, comp)
+        return (w if w > 0.0 else 0.0) if speed else w
+
+    def ego(self, p, tick, pos, vel):
+        """([est_x, est_y], est_v) of planner ``p`` at noise tick ``tick`` from its true ``pos`` / ``vel``."""
+        return ([self._add(pos[0], self.pos[p], p, tick, NOISE_EGO, 0), self._add(pos[1], self.pos[p], p, tick, NOISE_EGO, 1)],
+                self._add(vel, self.vel[p], p, tick, NOISE_EGO, 2, speed=True))
+
+    def _rows(self, p, tick, rows, objs):
+        return [(self._add(r[0], self.obj_pos[p], p, tick, o, 0), self._add(r[1], self.obj_pos[p], p, tick, o, 1),
+                 self._add(r[2], self.obj_theta[p], p, tick, o, 2), self._add(r[3], self.obj_vel[p], p, tick, o, 3, speed=True)) + tuple(r[4:])
+                for r, o in zip(rows, objs)]
+
+    def objects(self, p, tick, rows):
+        """``rows`` [(x, y, theta, v, length)]: the planner's own object list (opponents, then statics) -> the rows as perceived."""
+        return self._rows(p, tick, rows, range(len(rows)))
+
+    def mates(self, p, tick, rows):
+        """``rows``: every other planner of ``p``'s race, ascending -> the rows as ``p`` perceives them."""
+        objs = [NOISE_MATE | (q - self.lo[p]) for q in range(self.lo[p], self.hi[p]) if q != p]
+        if len(objs) != len(rows):
+            raise ValueError("NoiseModel.mates: one row per mate expected")
+        return self._rows(p, tick, rows, objs)

@@ -60,7 +60,8 @@ extern "C" {
 #define LTPL_ABI_VERSION 9        /* v7 (round 5, additive): ltpl_paths_kernel_symbol, ltpl_layer_grid, ltpl_fleet_digest; v8 (additive): ltpl_assembly_records;
                                      v9 (round 6, additive): ltpl_create_ex, ltpl_tick_persistent_stop / _stats;
                                      additive to v9: ltpl_fleet_sim_race / _heading, ltpl_fleet_friction / _scale / _rows,
-                                     ltpl_fleet_sim_snapshot / _snapshot_info / _snapshot_drop / _branch */
+                                     ltpl_fleet_sim_snapshot / _snapshot_info / _snapshot_drop / _branch,
+                                     ltpl_fleet_sim_noise / _estimate / _noise_draws */
 
 /* status codes */
 #define LTPL_OK               0
@@ -1028,6 +1029,53 @@ int ltpl_fleet_sim_events(ltpl_fleet* fleet, const ltpl_fleet_sim_events_in* in)
 /* fired_tick (may be NULL): [n_events] schedule tick in which event e fired, -1: not yet; n_events (may be NULL): events of the list (0: events
  * are off); tick (may be NULL): the schedule tick. No simulation: LTPL_ERR_INVALID_ARG. */
 int ltpl_fleet_sim_events_read(ltpl_fleet* fleet, int32_t* fired_tick, int32_t* n_events, int32_t* tick);
+
+/* ------------------------------------------------------------------------------------------------------------------------------------------
+ * Additive to ABI v9 -- SEEDED SENSOR NOISE: localisation and perception errors of every planner of the closed-loop simulation, drawn on
+ * the device inside ltpl_fleet_sim_run (csrc/fleet_sim.hpp: k_fleet_sim_step_noise, k_fleet_sim_mates_noise; the generator:
+ * csrc/fleet_noise.hpp). Without it every planner sees its tracked pose and every object exactly.
+ * THE SAMPLE g(seed, tick, obj, comp): Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85, ten
+ * rounds) under the key (seed low word, seed high word) on the three counters (tick, obj, 3 comp + b, 0), b = 0, 1, 2; K = the sum of the
+ * 12 output words as uint64; g = ((double)K + 6.0) 2^-32 - 6.0: the sum of twelve uniforms minus six, mean 0, variance 1 - 2^-64, |g| < 6.
+ * Every step is exact in fp64: host (sim.noise_gauss) and device agree to the last bit.
+ *   obj   0xFFFFFFFF: the ego estimate | k: entry k of the planner's own object list, opponents first, then statics (the index BEFORE the
+ *         on-track compaction) | 0x80000000 | (q - first planner of the race): mate q of a race
+ *   comp  ego: 0 x, 1 y, 2 v; object: 0 x, 1 y, 2 theta, 3 v
+ *   tick  tick0 + the fleet ticks ltpl_fleet_sim_run has executed since the noise was set; it advances every tick, live planner or not
+ * A draw depends on the planner's seed, never on its index: a planner computes the same in any fleet and on any shard.
+ * WHAT IS PERTURBED, one multiply and one add each (value + sigma g); a sigma of 0 draws nothing and hands the value through untouched:
+ *   ego      est_x = pos_x + sigma_pos g(.., 0), est_y likewise with comp 1, est_v = max(0, vel + sigma_vel g(.., 2)), written behind the
+ *            tracker. The fleet's tick (get_ref_idx, the velocity stage) reads them as pos_est / vel_est. The TRUE pose stays what the
+ *            tracker starts from, what the mates see of one another, and what ltpl_fleet_sim_state, the trace ([2] .. [4]), telemetry,
+ *            the events' conditions and the flight recorder's head hold.
+ *   objects  x, y (sigma_obj_pos), theta (sigma_obj_theta) and v (sigma_obj_vel, clamped at 0) of every opponent, static object and mate
+ *            in front of the ingestion. The PERCEIVED values are what the planner is handed, what decides "on the track", and what trace
+ *            fields [6] [7] and the recorder's objects hold.
+ * TELEMETRY measures clearance and contacts against the TRUE positions of the objects the planner was handed. Limit: an object perceived
+ * off the track is dropped by the ingestion and so is not measured, even where it truly is on the track.
+ * A planner whose sigmas are all 0 computes bit for bit what a fleet without noise computes. Snapshot and branch copy state, not
+ * configuration: seeds and sigmas stay the destination's own.
+ * THE CALL: after ltpl_fleet_sim_setup (which switches the noise off) at any time between runs; in == NULL switches it off. Every argument
+ * is checked before the first HIP call: no simulation, a sigma that is negative or not finite, a missing seed array or a negative tick0 are
+ * LTPL_ERR_INVALID_ARG with a message. Everything new is allocated before anything old is freed: a failing call keeps the previous noise and
+ * its tick count.
+ * ------------------------------------------------------------------------------------------------------------------------------------------ */
+typedef struct {
+    const uint64_t* seed;            /* [n]                                            */
+    const double* sigma_pos;         /* [n] m;   NULL: all zero (every sigma array)     */
+    const double* sigma_vel;         /* [n] m/s                                        */
+    const double* sigma_obj_pos;     /* [n] m                                          */
+    const double* sigma_obj_theta;   /* [n] rad                                        */
+    const double* sigma_obj_vel;     /* [n] m/s                                        */
+    int32_t tick0;                   /* >= 0: the noise tick of the next tick to run   */
+} ltpl_fleet_sim_noise_in;
+int ltpl_fleet_sim_noise(ltpl_fleet* fleet, const ltpl_fleet_sim_noise_in* in);
+/* the planners' pos_est / vel_est of the last tick (each may be NULL); the true state while the noise is off and until the first noisy tick */
+int ltpl_fleet_sim_estimate(ltpl_fleet* fleet, double* x, double* y, double* v);
+/* the test hook of the generator (k_fleet_noise_draws, one lane per tuple): g[i] = g(seed[i], tick[i], obj[i], comp[i]); words (may be
+ * NULL): [n][12] the output words of the three blocks. Needs a fleet, no simulation. */
+int ltpl_fleet_sim_noise_draws(ltpl_fleet* fleet, const uint64_t* seed, const uint32_t* tick, const uint32_t* obj, const uint32_t* comp, int32_t n,
+                               double* g, uint32_t* words);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,7 @@
 """Closed-loop SIMULATION rate of a fleet (ltpl_fleet_sim_*): N planners, each with its own eight C2-style race-line opponents (SURVEY.md
 section 8d: s0_k = 250 + 280 k, vel_scale_k = 0.30 + 0.05 (k mod 4), here staggered by 10 m (p mod 16) per planner), run the example
 driver's loop on the device for T ticks without host work per tick.   tools/sim_rate.py [--planners 32768] [--ticks 200] [--no-tape]
-[--race-size K] [--friction-map] [--telemetry] [--record M [--record-depth D]] [--lib PATH]. Prints planner-ticks per second of sim_run (device time of the run) next to tape_run on the C2 tape (recorded inputs,
+[--race-size K] [--friction-map] [--telemetry] [--record M [--record-depth D]] [--events] [--noise] [--lib PATH]. Prints planner-ticks per second of sim_run (device time of the run) next to tape_run on the C2 tape (recorded inputs,
 tools/fleet_rate.py). --race-size K > 1: races of K consecutive planners (ltpl_fleet_sim_race) that see one another, started 30 m apart
 along the race line with its heading; K = 1 (default) is the run without races. --friction-map: the same fleet on the friction grid of
 tests/golden/friction_grid.npz (ltpl_fleet_friction: rows evaluated on the device, grip factors 1.0 .. 0.7 over the planners) instead of
@@ -12,7 +12,10 @@ unfused launch sequence -- compare with LTPL_FLEET_NO_FUSE=1 and the recorder of
 printed. --events: scripted events on (ltpl_fleet_sim_events): per planner one timed gg_scale event at a tick of its own and one opp_within
 trigger on its first opponent (it slows down; the odd planners' threshold lies above the opponent's first distance, the even planners'
 below it, and the opponent drives away: theirs never fires) with a chained "after" (it speeds up again): k_fleet_sim_triggers every tick,
-k_fleet_sim_events_timed in the ticks that hold a timed event; the fired events are counted after the run. --lib PATH: another build of
+k_fleet_sim_events_timed in the ticks that hold a timed event; the fired events are counted after the run. --noise: seeded sensor noise on
+(ltpl_fleet_sim_noise) with all five sigmas set (pos 0.1 m, vel 0.2 m/s, obj_pos 0.3 m, obj_theta 0.02 rad, obj_vel 0.5 m/s) and a seed per
+planner: k_fleet_sim_step_noise (and k_fleet_sim_mates_noise with races) in place of the plain kernels; the largest distance between
+estimate and true pose is printed after the run. --lib PATH: another build of
 the library (A/B against the parent's)."""
 import argparse
 import os
@@ -42,6 +45,7 @@ def main():
     ap.add_argument("--record", type=int, default=0, help="flight recorder on for this many planners, spread evenly over the fleet")
     ap.add_argument("--record-depth", type=int, default=0, help="ring depth of the recorder (default: --ticks)")
     ap.add_argument("--events", action="store_true", help="scripted events on: a timed gg_scale event and an opp_within trigger with a chained after per planner")
+    ap.add_argument("--noise", action="store_true", help="seeded sensor noise on, all five sigmas set, a seed per planner")
     ap.add_argument("--lib", default=None, help="path of the library to load (default: the in-tree build)")
     a = ap.parse_args()
     lat = Lattice.load(os.path.join(ROOT, "tests", "golden", "monteblanco_lattice.npz"))
@@ -93,6 +97,8 @@ def main():
                        Event(p, when=("opp_within", 0, 250.0 + 10.0 * (p % 16) + (5.0 if p % 2 else -20.0)), set=("opp_vel_scale", 0, 0.2)),
                        Event(p, when=("after", 1, 40), set=("opp_vel_scale", 0, 0.5))]
             fleet.sim_events(ev)
+        if a.noise:
+            fleet.sim_noise(seed=np.arange(n, dtype=np.uint64) + np.uint64(1), pos=0.1, vel=0.2, obj_pos=0.3, obj_theta=0.02, obj_vel=0.5)
         t0 = time.perf_counter()
         failed = 0
         try:
@@ -108,6 +114,10 @@ def main():
         if failed == 0:
             sel = np.bincount(fleet.sim_state()['sel_action'] + 1, minlength=6)
             print("  last selected actions (none, straight, follow, left, right, emergency): %s" % sel.tolist())
+        if a.noise:
+            est, tru = fleet.sim_estimate(), fleet.sim_state()
+            print("  noise: estimate up to %.3f m and %.3f m/s off the true state in the last tick" % (
+                np.max(np.hypot(*(est["pos_est"] - tru["pos_est"]).T)), np.max(np.abs(est["vel_est"] - tru["vel_est"]))))
         if a.events:
             ft = fleet.sim_events_read()["fired_tick"].reshape(n, 3)
             print("  events: %d timed, %d opp_within and %d chained 'after' events fired of %d each (schedule tick %d)" % (
