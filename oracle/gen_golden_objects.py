@@ -10,6 +10,13 @@ reference itself):
                                     (check_inside_bounds.py:7-59), plus object lists run through
                                     ObjectListInterface.process_object_list (ObjectListInterface.py:75-153): kept ids,
                                     prediction points, radii
+
+    python -m oracle.gen_golden_objects boundary
+
+  tests/golden/objects_boundary.npz the probes of tests/object_cases.py at the decision boundaries of check_inside_bounds (families bound,
+                                    index, segment, centre, tie, on-point) on the Monteblanco, Millbrook and open lattices and the C3 oval:
+                                    points, labels and the verdict of the same unmodified function; the numpy version (np.argpartition
+                                    decides exact ties of the squared distance, and not the same way in every version)
 """
 import os
 import sys
@@ -74,5 +81,32 @@ def main():
     print("written tests/golden/objects_bounds.npz")
 
 
+def boundary():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import object_cases as oc
+    gl, _ = ref_env.load_reference()
+    cib = gl.online_graph.src.check_inside_bounds.check_inside_bounds
+    cols = {f: [] for f in ("qx", "qy", "family", "k", "offset_index", "param", "pair", "verdict")}
+    names, counts = [], []
+    for name in oc.LATTICES:
+        ps = oc.probe_set(name)
+        T, p = ps.track, ps.probes
+        sel = np.nonzero(oc.in_fixture(ps))[0]
+        assert np.array_equal(sel, np.arange(len(sel)))                        # (the stored families lie in front: `pair` indexes them as it stands)
+        with np.errstate(invalid="ignore", over="ignore"):
+            v = np.array([bool(cib(bound1=T.b1, bound2=T.b2, pos=[float(p.qx[i]), float(p.qy[i])])) for i in sel])
+        names.append(name); counts.append(len(sel))
+        cols["qx"].append(p.qx[sel]); cols["qy"].append(p.qy[sel]); cols["family"].append(p.family[sel].astype(np.int8))
+        cols["k"].append(p.k[sel].astype(np.int16)); cols["param"].append(p.param[sel]); cols["pair"].append(p.pair[sel].astype(np.int32))
+        cols["offset_index"].append(np.array([oc.OFFSETS.index(o) for o in p.offset[sel].tolist()], np.int8))
+        cols["verdict"].append(v.astype(np.int8))
+        print("%-12s %6d probes, %d on the track, reference differs from the restatement on %d" % (
+            name, len(sel), int(v.sum()), int((v != ps.ref.verdict[sel]).sum())))
+    out = os.path.join(ROOT, "tests", "golden", "objects_boundary.npz")
+    np.savez_compressed(out, names=np.array(names), counts=np.array(counts, np.int64), numpy_version=np.array(np.__version__),
+                        **{f: np.concatenate(c) for f, c in cols.items()})
+    print("written %s: %d probes, %d bytes" % (out, int(sum(counts)), os.path.getsize(out)))
+
+
 if __name__ == "__main__":
-    main()
+    boundary() if sys.argv[1:] == ["boundary"] else main()
