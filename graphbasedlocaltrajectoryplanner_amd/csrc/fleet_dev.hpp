@@ -321,20 +321,12 @@ __global__ __launch_bounds__(64) void k_fleet_follow_lanes(DevLat lat, DevVelPar
 typedef void (*fleet_follow_kernel_t)(DevLat, DevVelParams, const DevVelJob*, const double*, const ke_t*, int, int, double*, double*, int, int, int, double*, int*);
 static fleet_follow_kernel_t fleet_follow_kernel_of(int v)
 {
-    switch (v) {
-        case 0: return k_fleet_follow_lanes<0, false>; case 1: return k_fleet_follow_lanes<0, true>;
-        case 2: return k_fleet_follow_lanes<1, false>; case 3: return k_fleet_follow_lanes<1, true>;
-        case 4: return k_fleet_follow_lanes<2, false>; default: return k_fleet_follow_lanes<2, true>;
-    }
+    return with_vel_variant(v, [](auto em, auto axm1) -> fleet_follow_kernel_t { return k_fleet_follow_lanes<em.value, axm1.value>; });
 }
 typedef void (*fleet_lanes_kernel_t)(DevVelParams, const DevVelJob*, const double*, const ke_t*, int, double*, int, int, int, double*);
 static fleet_lanes_kernel_t fleet_lanes_kernel_of(int v)
 {
-    switch (v) {
-        case 0: return k_fleet_fb_lanes<0, false>; case 1: return k_fleet_fb_lanes<0, true>;
-        case 2: return k_fleet_fb_lanes<1, false>; case 3: return k_fleet_fb_lanes<1, true>;
-        case 4: return k_fleet_fb_lanes<2, false>; default: return k_fleet_fb_lanes<2, true>;
-    }
+    return with_vel_variant(v, [](auto em, auto axm1) -> fleet_lanes_kernel_t { return k_fleet_fb_lanes<em.value, axm1.value>; });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -1325,13 +1325,14 @@ try {
     int rc = fleet_enter(f);
     if (rc) return rc;
     const size_t m = (size_t)n;
-    // seed [n] u64 | g [n] f64 | tick, obj, comp [n] 32 bit each | words [n][12] u32
+    Arena ar;     // one device block
+    const size_t o_seed = ar.add(8 * m), o_g = ar.add(8 * m), o_tick = ar.add(4 * m), o_obj = ar.add(4 * m), o_comp = ar.add(4 * m), o_words = ar.add(48 * m);
     unsigned char* d = nullptr;
     struct Guard { void* a = nullptr; ~Guard() { if (a) (void)hipFree(a); } } gd;
-    FLEET_TRY(f, hipMalloc(reinterpret_cast<void**>(&d), (8 + 8 + 12 + 48) * m)); gd.a = d;
-    uint64_t* d_seed = reinterpret_cast<uint64_t*>(d); double* d_g = reinterpret_cast<double*>(d + 8 * m);
-    uint32_t* d_tick = reinterpret_cast<uint32_t*>(d + 16 * m); uint32_t* d_obj = reinterpret_cast<uint32_t*>(d + 20 * m);
-    uint32_t* d_comp = reinterpret_cast<uint32_t*>(d + 24 * m); uint32_t* d_words = reinterpret_cast<uint32_t*>(d + 28 * m);
+    FLEET_TRY(f, hipMalloc(reinterpret_cast<void**>(&d), ar.size)); gd.a = d;
+    uint64_t* d_seed = reinterpret_cast<uint64_t*>(d + o_seed); double* d_g = reinterpret_cast<double*>(d + o_g);
+    uint32_t* d_tick = reinterpret_cast<uint32_t*>(d + o_tick); uint32_t* d_obj = reinterpret_cast<uint32_t*>(d + o_obj);
+    uint32_t* d_comp = reinterpret_cast<uint32_t*>(d + o_comp); uint32_t* d_words = reinterpret_cast<uint32_t*>(d + o_words);
     FLEET_TRY(f, hipMemcpy(d_seed, seed, 8 * m, hipMemcpyHostToDevice));
     FLEET_TRY(f, hipMemcpy(d_tick, tick, 4 * m, hipMemcpyHostToDevice));
     FLEET_TRY(f, hipMemcpy(d_obj, obj, 4 * m, hipMemcpyHostToDevice));

@@ -1,7 +1,8 @@
 // ltpl_hip.hip -- MI355X (gfx950 / CDNA4) backend of the graph_ltpl online hot path. C ABI: include/ltpl_hip.h.
 //
 // Seam (1) lives in paths_team.hpp: a team of NW wave64s plans one scenario (NW = 1 for batches, NW = 4 for single
-// ticks). Seam (2) (velocity profiles) and the fused tick live in this file.
+// ticks). Seam (2) (velocity profiles): vel_wave.hpp (one wave per profile), vel_lanes.hpp (one lane per profile); the fused tick's kernels
+// live in this file, the host side of the tick in tick_host.hpp.
 // The lattice (< 15 MB for Monteblanco) is uploaded once and is L2 / Infinity-Cache resident afterwards.
 // Everything is IEEE fp64 and compiled with -ffp-contract=off so that masks, arg-mins and path costs are
 // bit-identical to the NumPy arithmetic of the reference.
@@ -26,6 +27,7 @@
 #include "capsule.hpp"
 #include "layer_grid.hpp"
 #include "assembly_records.hpp"
+#include "vel_layout.hpp"
 
 #define WG_THREADS 256
 #define PIPELINE_MIN_SCEN 64   // seam (1) alone: batches from this size on use one-wave teams (nw1_min_scen). The fused tick against the batch
@@ -197,223 +199,7 @@ __device__ __forceinline__ void vl_stamp(long long* dbg, int row, int k)
 __device__ __forceinline__ void vl_stamp(long long*, int, int) {}
 #endif
 
-// ---------------------------------------------------------------------------------------------------------------------
-// wave helpers (wave64)
-// ---------------------------------------------------------------------------------------------------------------------
-// CROSS-LANE MOVES ON THE VECTOR ALU (round 5). `__shfl_xor` / `__shfl_up` compile to ds_bpermute_b32: an LDS-pipe instruction with an LDS
-// round trip of latency per step, in kernels whose LDS pipe is a co-limiter and whose waves spend ~46 % of their cycles in s_waitcnt
-// (275 of the 907 static LDS-pipe instructions of the round-4 batch path kernel were ds_bpermute). The reductions and scans below exchange
-// through DPP row operations (partner at distance 1, 2, 4, 8 inside a row of 16 lanes) and the gfx950 row / half swaps
-// (v_permlane16_swap, v_permlane32_swap: distance 16 and 32) instead: no LDS instruction, no lgkmcnt wait.
-// ALL 64 LANES MUST BE ACTIVE at the call (wave-uniform control flow): a DPP move from an inactive lane delivers no data.
-// (the round-4 `__shfl_xor` forms: tools/experiments/r05_lost_switches.patch)
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
-#error "the DPP / v_permlane16_swap / v_permlane32_swap reductions below are gfx950 code: build with --offload-arch=gfx950 (the round-4 shuffle forms: tools/experiments/r05_lost_switches.patch)"
-#endif
-#define DPP_XOR1 0xB1                   // quad_perm:[1,0,3,2]
-#define DPP_XOR2 0x4E                   // quad_perm:[2,3,0,1]
-#define DPP_HALF_MIRROR 0x141           // lane i <-> 7 - i  of every 8: the partner at distance 4 once the quads are uniform
-#define DPP_MIRROR 0x140                // lane i <-> 15 - i of every 16: the partner at distance 8 once the halves of 8 are uniform
-#define DPP_ROR8 0x128                  // row_ror:8 = lane i ^ 8
-#define DPP_SHL4 0x104                  // row_shl:4 (lane i <- lane i + 4)
-#define DPP_SHR(n) (0x110 + (n))        // row_shr:n (lane i <- lane i - n inside the row)
-#define DPP_BCAST15 0x142               // lane 15 of every row -> the next row
-#define DPP_BCAST31 0x143               // lane 31 -> rows 2 and 3
-typedef unsigned lane_pair_t __attribute__((ext_vector_type(2)));
-template <int CTRL> __device__ __forceinline__ int dpp_i32(int v) { return __builtin_amdgcn_mov_dpp(v, CTRL, 0xf, 0xf, false); }
-template <int CTRL> __device__ __forceinline__ double dpp_f64(double v)
-{
-    return __hiloint2double(dpp_i32<CTRL>(__double2hiint(v)), dpp_i32<CTRL>(__double2loint(v)));
-}
-// the value of lane (i ^ M), M = 1, 2, 4, 8, for ANY lane contents (the mirror forms above need uniform sub-groups)
-template <int M> __device__ __forceinline__ int xor_i32(int v)
-{
-    if constexpr (M == 1) return dpp_i32<DPP_XOR1>(v);
-    else if constexpr (M == 2) return dpp_i32<DPP_XOR2>(v);
-    else if constexpr (M == 4) {           // banks (= quads of a row) 0, 2 take the quad above, banks 1, 3 the quad below
-        const int up = __builtin_amdgcn_update_dpp(v, v, DPP_SHL4, 0xf, 0x5, false);
-        return __builtin_amdgcn_update_dpp(up, v, DPP_SHR(4), 0xf, 0xa, false);
-    } else { static_assert(M == 8, "distance inside a row"); return dpp_i32<DPP_ROR8>(v); }
-}
-template <int M> __device__ __forceinline__ double xor_f64(double v) { return __hiloint2double(xor_i32<M>(__double2hiint(v)), xor_i32<M>(__double2loint(v))); }
-// distance 16 / 32: with both operands = v the swap returns, in every lane i, the pair {v[i], v[i ^ M]} (in an order that depends on the
-// lane's half) -- symmetric combinations (min, lexicographic min) need not know which is which
-template <int M> __device__ __forceinline__ lane_pair_t swap_pair(unsigned v)
-{
-    if constexpr (M == 16) return __builtin_amdgcn_permlane16_swap(v, v, false, false);
-    else { static_assert(M == 32, "row / half swap"); return __builtin_amdgcn_permlane32_swap(v, v, false, false); }
-}
-template <int M> __device__ __forceinline__ void swap_pair_f64(double v, double& a, double& b)
-{
-    const lane_pair_t lo = swap_pair<M>((unsigned)__double2loint(v)), hi = swap_pair<M>((unsigned)__double2hiint(v));
-    a = __hiloint2double((int)hi.x, (int)lo.x); b = __hiloint2double((int)hi.y, (int)lo.y);
-}
-
-// minimum of a double over the wave (no NaN among the keys), in every lane. The first key decides nearly always, so the callers reduce it
-// alone and fall back to wave_min3 only when it is attained more than once.
-__device__ __forceinline__ double wave_min_f64(double k)
-{
-    k = __builtin_fmin(k, dpp_f64<DPP_XOR1>(k));
-    k = __builtin_fmin(k, dpp_f64<DPP_XOR2>(k));
-    k = __builtin_fmin(k, dpp_f64<DPP_HALF_MIRROR>(k));
-    k = __builtin_fmin(k, dpp_f64<DPP_MIRROR>(k));
-    double a, b;
-    swap_pair_f64<16>(k, a, b); k = __builtin_fmin(a, b);
-    swap_pair_f64<32>(k, a, b); k = __builtin_fmin(a, b);
-    return k;
-}
-__device__ __forceinline__ int wave_min_i32(int k)
-{
-    k = min(k, dpp_i32<DPP_XOR1>(k));
-    k = min(k, dpp_i32<DPP_XOR2>(k));
-    k = min(k, dpp_i32<DPP_HALF_MIRROR>(k));
-    k = min(k, dpp_i32<DPP_MIRROR>(k));
-    lane_pair_t r = swap_pair<16>((unsigned)k); k = min((int)r.x, (int)r.y);
-    r = swap_pair<32>((unsigned)k); k = min((int)r.x, (int)r.y);
-    return k;
-}
-__device__ __forceinline__ int wave_max_i32(int k)
-{
-    k = max(k, dpp_i32<DPP_XOR1>(k));
-    k = max(k, dpp_i32<DPP_XOR2>(k));
-    k = max(k, dpp_i32<DPP_HALF_MIRROR>(k));
-    k = max(k, dpp_i32<DPP_MIRROR>(k));
-    lane_pair_t r = swap_pair<16>((unsigned)k); k = max((int)r.x, (int)r.y);
-    r = swap_pair<32>((unsigned)k); k = max((int)r.x, (int)r.y);
-    return k;
-}
-// maximum over every group of eight lanes (lanes 8 k .. 8 k + 7), in each of its lanes
-__device__ __forceinline__ int oct_max_i32(int k)
-{
-    k = max(k, dpp_i32<DPP_XOR1>(k));
-    k = max(k, dpp_i32<DPP_XOR2>(k));
-    return max(k, dpp_i32<DPP_HALF_MIRROR>(k));
-}
-// lexicographic minimum over (k1, k2, idx) / (k, idx): one exchange step at distance M (true partner: the keys differ from lane to lane)
-template <int M> __device__ __forceinline__ void min3_step(double& k1, double& k2, int& idx)
-{
-    if constexpr (M < 16) {
-        const double o1 = xor_f64<M>(k1), o2 = xor_f64<M>(k2); const int oi = xor_i32<M>(idx);
-        const bool take = (o1 < k1) || (o1 == k1 && ((o2 < k2) || (o2 == k2 && oi < idx)));
-        if (take) { k1 = o1; k2 = o2; idx = oi; }
-    } else {
-        double a1, b1, a2, b2; swap_pair_f64<M>(k1, a1, b1); swap_pair_f64<M>(k2, a2, b2);
-        const lane_pair_t ri = swap_pair<M>((unsigned)idx);
-        const int ai = (int)ri.x, bi = (int)ri.y;
-        const bool take_b = (b1 < a1) || (b1 == a1 && ((b2 < a2) || (b2 == a2 && bi < ai)));
-        k1 = take_b ? b1 : a1; k2 = take_b ? b2 : a2; idx = take_b ? bi : ai;
-    }
-}
-template <int M> __device__ __forceinline__ void min2_step(double& k, int& idx)
-{
-    if constexpr (M < 16) {
-        const double o = xor_f64<M>(k); const int oi = xor_i32<M>(idx);
-        const bool take = (o < k) || (o == k && oi < idx);
-        if (take) { k = o; idx = oi; }
-    } else {
-        double a, b; swap_pair_f64<M>(k, a, b);
-        const lane_pair_t ri = swap_pair<M>((unsigned)idx);
-        const int ai = (int)ri.x, bi = (int)ri.y;
-        const bool take_b = (b < a) || (b == a && bi < ai);
-        k = take_b ? b : a; idx = take_b ? bi : ai;
-    }
-}
-__device__ __forceinline__ void wave_min3(double& k1, double& k2, int& idx)
-{
-    min3_step<1>(k1, k2, idx); min3_step<2>(k1, k2, idx); min3_step<4>(k1, k2, idx); min3_step<8>(k1, k2, idx);
-    min3_step<16>(k1, k2, idx); min3_step<32>(k1, k2, idx);
-}
-// the same for (key, index) pairs: the closest-point searches carry no second key
-__device__ __forceinline__ void wave_min2(double& k, int& idx)
-{
-    min2_step<1>(k, idx); min2_step<2>(k, idx); min2_step<4>(k, idx); min2_step<8>(k, idx); min2_step<16>(k, idx); min2_step<32>(k, idx);
-}
-// ... over the lanes that agree in their low bits (lane & (np2 - 1)): the steps at distance >= np2 only (np2 a power of two, uniform)
-__device__ __forceinline__ void wave_min2_from(double& k, int& idx, int np2)
-{
-    if (np2 <= 1) min2_step<1>(k, idx);
-    if (np2 <= 2) min2_step<2>(k, idx);
-    if (np2 <= 4) min2_step<4>(k, idx);
-    if (np2 <= 8) min2_step<8>(k, idx);
-    if (np2 <= 16) min2_step<16>(k, idx);
-    if (np2 <= 32) min2_step<32>(k, idx);
-}
-
-// exclusive prefix sum of an int over the wave (+ the total): Hillis-Steele inside the rows (row_shr, lanes without a source add 0), then
-// the row totals through the two broadcast forms
-__device__ __forceinline__ int wave_excl_scan(int v, int lane, int& total)
-{
-    (void)lane;
-    int x = v;
-    x += __builtin_amdgcn_update_dpp(0, x, DPP_SHR(1), 0xf, 0xf, true);
-    x += __builtin_amdgcn_update_dpp(0, x, DPP_SHR(2), 0xf, 0xf, true);
-    x += __builtin_amdgcn_update_dpp(0, x, DPP_SHR(4), 0xf, 0xf, true);
-    x += __builtin_amdgcn_update_dpp(0, x, DPP_SHR(8), 0xf, 0xf, true);
-    x += __builtin_amdgcn_update_dpp(0, x, DPP_BCAST15, 0xa, 0xf, false);      // rows 1 and 3 += total of the row below
-    x += __builtin_amdgcn_update_dpp(0, x, DPP_BCAST31, 0xc, 0xf, false);      // rows 2 and 3 += total of rows 0 and 1
-    total = __builtin_amdgcn_readlane(x, 63);
-    return x - v;
-}
-
-// Self-check of the cross-lane helpers above: every helper against a plain loop over the wave's values in LDS. err[0] = number of lanes that
-// disagree. Part of the create-time self-test of the product library since round 6 (wave_ops_selftest: the helpers are DPP / permlane-swap code
-// that only exists for gfx950 and assumes 64 active lanes); tests/test_gpu_wave_ops.py drives it with its own data through the experiment build.
-__global__ __launch_bounds__(64) void k_exp_wave_ops(const double* vals, const int* ivals, int rounds, int* err)
-{
-    __shared__ double sd[64], sd2[64];
-    __shared__ int si[64];
-    const int lane = threadIdx.x;
-    int bad = 0;
-    for (int r = 0; r < rounds; ++r) {
-        const double d = vals[(size_t)r * 128 + lane], d2 = vals[(size_t)r * 128 + 64 + lane];
-        const int iv = ivals[(size_t)r * 64 + lane];
-        sd[lane] = d; sd2[lane] = d2; si[lane] = iv;
-        __syncthreads();
-        double rmin = INFINITY; int imin = 0x7fffffff, imax = -0x7fffffff - 1, isum = 0, ipre = 0, omax = -0x7fffffff - 1;
-        double a1 = INFINITY, a2 = INFINITY; int ai = 0x7fffffff;          // lexicographic minimum over (d, d2, iv)
-        double b1 = INFINITY; int bi = 0x7fffffff;                          // ... over (d, iv)
-        for (int l = 0; l < 64; ++l) {
-            rmin = sd[l] < rmin ? sd[l] : rmin; imin = si[l] < imin ? si[l] : imin; imax = si[l] > imax ? si[l] : imax;
-            isum += si[l] & 0xff; if (l < lane) ipre += si[l] & 0xff;
-            if ((l >> 3) == (lane >> 3)) omax = si[l] > omax ? si[l] : omax;
-            if (sd[l] < a1 || (sd[l] == a1 && (sd2[l] < a2 || (sd2[l] == a2 && si[l] < ai)))) { a1 = sd[l]; a2 = sd2[l]; ai = si[l]; }
-            if (sd[l] < b1 || (sd[l] == b1 && si[l] < bi)) { b1 = sd[l]; bi = si[l]; }
-        }
-        if (wave_min_f64(d) != rmin) ++bad;
-        if (wave_min_i32(iv) != imin) ++bad;
-        if (wave_max_i32(iv) != imax) ++bad;
-        if (oct_max_i32(iv) != omax) ++bad;
-        { int tot; const int ex = wave_excl_scan(iv & 0xff, lane, tot); if (ex != ipre || tot != isum) ++bad; }
-        { double k1 = d, k2 = d2; int ix = iv; wave_min3(k1, k2, ix); if (k1 != a1 || k2 != a2 || ix != ai) ++bad; }
-        { double k = d; int ix = iv; wave_min2(k, ix); if (k != b1 || ix != bi) ++bad; }
-        for (int np2 = 1; np2 <= 64; np2 <<= 1) {                            // segment merge of phase 1: lanes with equal (lane & (np2 - 1))
-            double k = d; int ix = iv; wave_min2_from(k, ix, np2);
-            double c1 = INFINITY; int ci = 0x7fffffff;
-            for (int l = lane & (np2 - 1); l < 64; l += np2) if (sd[l] < c1 || (sd[l] == c1 && si[l] < ci)) { c1 = sd[l]; ci = si[l]; }
-            if (k != c1 || ix != ci) ++bad;
-        }
-        __syncthreads();
-    }
-    if (bad) atomicAdd(err, 1);
-}
-
-// LDS hand-over between the lanes of ONE wave: DS operations of a wave execute in order, so only the compiler has to be
-// kept from reordering (wavefront-scope fences emit no s_waitcnt vmcnt and do not serialise outstanding global loads)
-__device__ __forceinline__ void wave_sync_lds()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ double normalize_psi_dev(double psi)
-{
-    double sgn = (psi > 0.0) ? 1.0 : ((psi < 0.0) ? -1.0 : 0.0);
-    double out = sgn * fmod(fabs(psi), 2.0 * D_PI);
-    if (out >= D_PI) out -= 2.0 * D_PI;
-    else if (out < -D_PI) out += 2.0 * D_PI;
-    return out;
-}
+#include "wave_ops.hpp"
 
 // ---------------------------------------------------------------------------------------------------------------------
 // the path kernel (seam 1)
@@ -453,735 +239,7 @@ typedef PlanFx<48, 32, 1> PlanC;      // <= 48 nodes per layer, <= 31 layers (be
 typedef PlanFx<32, 32, NUM_WAVES> PlanA4;   // class A for the four-wave latency kernels (k_paths<4>, k_tick)
 
 
-// ---------------------------------------------------------------------------------------------------------------------
-// velocity stage (seam 2): tph.calc_vel_profile / calc_vel_profile_brake / calc_vel_profile_follow on the device
-// ---------------------------------------------------------------------------------------------------------------------
-// One wave64 owns one profile. Vectorisable parts (curvature -> lateral-limit speed, run-start detection, final
-// sqrt, acceleration) are spread over the lanes; the forward / backward recurrences are inherently sequential scans
-// and run on lane 0 over LDS-resident arrays. The recurrence state is w = v^2, which removes the sqrt and the
-// divisions from the dependent chain (v_{i+1}^2 = v_i^2 + 2 a_x(v_i) ds_i); comparisons happen in w as well (sqrt is
-// monotone). Differences to the reference's v-state arithmetic are rounding-level (~1e-16 relative).
-struct DevVelParams {
-    double e, inv_e, drag_m, len_veh, v_max;
-    int n_axm, ctrl;
-    const double* axm;          // [n_axm * 2] in device memory
-    double c_p, k_p, k_d, tan_w;
-};
-
-// per-wave LDS scratch of the velocity stage; every array holds cap + 1 doubles
-struct VelScratch {
-    double* w;        // profile state (v^2)
-    double* kabs;     // |kappa|
-    double* el;       // element lengths
-    double* gax;      // per-point longitudinal limit (nullptr -> constant)
-    double* gay;      // per-point lateral limit      (nullptr -> constant)
-    double* igay;     // 1 / gay (division-free recurrence)
-    double* axm;      // LDS copy of ax_max_machines rows [v, ax] (<= 64 rows)
-    long long* dbg;
-    double* s;        // arc length (cap + 1)
-    double* wb;       // ego brake profile (follow)
-    double* wc;       // scratch profile (follow)
-    unsigned char* start;   // run-start flags
-    double* chunk;    // 128 doubles: staging of the global race line for the opponent brake scan
-    int cap;
-};
-
-// np.interp(v, axm[:, 0], axm[:, 1]) on the LDS copy of the table
-__device__ __forceinline__ double interp_axm(double v, const double* t, int n)
-{
-    if (n == 1 || v <= t[0]) return t[1];
-    if (v >= t[2 * (n - 1)]) return t[2 * (n - 1) + 1];
-    int j = 0;
-    while (j + 1 < n && t[2 * (j + 1)] <= v) ++j;
-    const double x0 = t[2 * j], x1 = t[2 * (j + 1)], f0 = t[2 * j + 1], f1 = t[2 * (j + 1) + 1];
-    return (f1 - f0) / (x1 - x0) * (v - x0) + f0;
-}
-
-// tire share of tph calc_ax_poss: ax_max * (1 - (ay_used / ay_max)^e)^(1/e), 0 when the radicand is not positive.
-// EM selects the exponent at compile time (1: e == 1, 2: e == 2, 0: general pow) so that the recurrences below are
-// straight-line code: with one wave per profile every taken branch is a pipeline refill nobody hides.
-template <int EM>
-__device__ __forceinline__ double tire_avail(double q, double ax_max, const DevVelParams& p)
-{
-    if constexpr (EM == 1) {
-        const double rad = 1.0 - q;
-        return rad > 0.0 ? ax_max * rad : 0.0;
-    } else if constexpr (EM == 2) {
-        const double rad = 1.0 - q * q;
-        return rad > 0.0 ? ax_max * sqrt(rad) : 0.0;
-    } else {
-        const double rad = 1.0 - pow(q, p.e);
-        return rad > 0.0 ? ax_max * pow(rad, p.inv_e) : 0.0;
-    }
-}
-
-#define VMODE_ACCEL_FORW 0
-#define VMODE_DECEL_FORW 1
-#define VMODE_DECEL_BACKW 2
-
-// tph calc_ax_poss in w = v^2; kq = |kappa| / ay_max (so that ay_used / ay_max = w * kq); axm1 = machine limit when the
-// table has a single row (AXM1), otherwise the LDS copy of the table is interpolated at v = sqrt(w)
-template <int EM, bool AXM1, int MODE>
-__device__ __forceinline__ double ax_poss_w(double w, double kq, double ax_max, const DevVelParams& p,
-                                            const double* axm_tab, double axm1)
-{
-    const double q = w * kq;
-    double ax = tire_avail<EM>(q, fabs(ax_max), p);
-    if constexpr (MODE == VMODE_ACCEL_FORW) {
-        const double axm = AXM1 ? axm1 : interp_axm(sqrt(w), axm_tab, p.n_axm);
-        ax = ax < axm ? ax : axm;
-        return ax - w * p.drag_m;
-    } else if constexpr (MODE == VMODE_DECEL_FORW) {
-        return -ax - w * p.drag_m;
-    } else {
-        return ax + w * p.drag_m;
-    }
-}
-
-// lane l <- lane l - 1 across the whole wave64 (DPP wave_shr:1); lane 0 receives `first`
-__device__ __forceinline__ double wave_shr1_f64(double v, double first)
-{
-    const int lo = __builtin_amdgcn_update_dpp(__double2loint(first), __double2loint(v), 0x138, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(first), __double2hiint(v), 0x138, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ int wave_shr1_i32(int v, int first)
-{
-    return __builtin_amdgcn_update_dpp(first, v, 0x138, 0xf, 0xf, false);
-}
-
-// one sweep of tph __solver_fb_acc_profile on w[0..n). Backward sweeps address the profile, curvature and element
-// lengths mirrored but -- restated quirk of the reference solver -- the gg limits unmirrored.
-// The recurrence is sequential, but everything except the state is known up front. SYSTOLIC form: the wave handles 64
-// steps at a time, lane l holds the operands of step base + l (for exponent 1 and a constant machine limit: the affine
-// coefficients); in every iteration ALL lanes evaluate their step on the state handed over by the lane below (DPP
-// wave_shr:1, no LDS, no broadcast), so after iteration l lane l holds the final value of its step. One iteration is the
-// bare dependent chain: ~a dozen VALU instructions.
-template <int EM, bool AXM1, bool GGARR, bool BACK>
-__device__ __forceinline__ void fb_sweep(int n, const VelScratch& vs, double cax, double cay, const DevVelParams& p, double vmax2, int lane)
-{
-    if (n < 2) return;
-    // run starts: first index of every run of positive differences of the (mirrored) profile BEFORE the sweep
-    for (int i = lane; i < n - 1; i += 64) {
-        const int a = BACK ? n - 1 - i : i, b = BACK ? n - 2 - i : i + 1;
-        const bool acc = vs.w[b] - vs.w[a] > 0.0;
-        bool prev = false;
-        if (i > 0) { const int a0 = BACK ? n - i : i - 1, b0 = BACK ? n - 1 - i : i; prev = vs.w[b0] - vs.w[a0] > 0.0; }
-        vs.start[i] = (acc && !prev) ? 1 : 0;
-    }
-    wave_sync_lds();
-    constexpr int MODE = BACK ? VMODE_DECEL_BACKW : VMODE_ACCEL_FORW;
-    constexpr bool AFFINE = EM == 1 && AXM1;
-    const double icay = 1.0 / cay, axm1 = vs.axm[1], dm = p.drag_m;
-    double wi = vs.w[BACK ? n - 1 : 0];                   // state entering the chunk (uniform)
-    int active = 0;
-    for (int base = 0; base < n - 1; base += 64) {
-        const int cnt = (n - 1 - base) < 64 ? (n - 1 - base) : 64;
-        const int ic = (lane < cnt) ? base + lane : base + cnt - 1;
-        const int Pa = BACK ? n - 1 - ic : ic, Pb = BACK ? n - 2 - ic : ic + 1, Ei = BACK ? n - 2 - ic : ic;
-        // operands of step ic (the gg limits are indexed by the step, the rest by the mirrored point)
-        const double kq_i = vs.kabs[Pa] * (GGARR ? vs.igay[ic] : icay), kq_n = vs.kabs[Pb] * (GGARR ? vs.igay[ic + 1] : icay);
-        const double ax_i = GGARR ? fabs(vs.gax[ic]) : fabs(cax), ax_n = GGARR ? fabs(vs.gax[ic + 1]) : fabs(cax);
-        const double e_i = vs.el[Ei], wold = vs.w[Pb];
-        const int st = vs.start[ic];
-        // affine coefficients (state independent):
-        //   forward : w' = min(max(T, Z), M),  T = w A1 + B1, Z = w A0, M = w A0 + B2
-        //   backward: w' = max(T, Z), then the look-ahead with the limits of the next point (t0 = wn C0 + w, t1 = wn C1 + w + D1)
-        const double te = 2.0 * e_i;
-        const double A0 = BACK ? 1.0 + te * dm : 1.0 - te * dm, A1 = A0 - te * (ax_i * kq_i), B1 = te * ax_i, B2 = te * axm1;
-        const double C0 = te * dm, C1 = C0 - te * (ax_n * kq_n), D1 = te * ax_n;
-        double w_in = wi, wnext = wold;
-        int act_in = active, act_out = 0;
-        // four steps per loop iteration: steps beyond cnt recompute final values from final inputs (idempotent), nothing is stored for them
-        auto sys_step = [&]() {
-            const bool act = (act_in | st) != 0;
-            double wn;
-            if constexpr (AFFINE) {
-                if constexpr (!BACK) {
-                    const double Z = A0 * w_in, T = fma(A1, w_in, B1), M = fma(A0, w_in, B2);
-                    wn = fmax(fmin(fmax(T, Z), M), 0.0);
-                } else {
-                    const double Z = A0 * w_in, T = fma(A1, w_in, B1);
-                    wn = fmax(fmax(T, Z), 0.0);
-                    const double t0 = fma(C0, wn, w_in), t1 = fma(C1, wn, w_in + D1);
-                    wn = fmin(fmax(fmax(t1, t0), 0.0), wn);
-                }
-            } else {
-                const double acur = ax_poss_w<EM, AXM1, MODE>(w_in, kq_i, ax_i, p, vs.axm, axm1);
-                wn = w_in + 2.0 * acur * e_i;
-                wn = wn < 0.0 ? 0.0 : wn;
-                if constexpr (BACK) {
-                    const double anext = ax_poss_w<EM, AXM1, MODE>(wn, kq_n, ax_n, p, vs.axm, axm1);
-                    double wt = w_in + 2.0 * anext * e_i;
-                    wt = wt < 0.0 ? 0.0 : wt;
-                    wn = wt < wn ? wt : wn;
-                }
-            }
-            wnext = (act && (wn < wold)) ? wn : wold;
-            act_out = (act && !(wn > vmax2)) ? 1 : 0;
-            // hand the state to the next lane; lane 0 keeps the state entering the chunk
-            w_in = wave_shr1_f64(wnext, wi);
-            act_in = wave_shr1_i32(act_out, active);
-                };
-        for (int it = 0; it < cnt; it += 4) { sys_step(); sys_step(); sys_step(); sys_step(); }
-        if (lane < cnt) vs.w[Pb] = wnext;
-        wi = readlane_f64(wnext, cnt - 1);
-        active = __builtin_amdgcn_readlane(act_out, cnt - 1);
-        wave_sync_lds();
-    }
-}
-
-// tph.calc_vel_profile(closed=False): vs.kabs / el / (gax, gay) hold the inputs, result in vs.w (as v^2)
-template <int EM, bool AXM1, bool GGARR>
-__device__ __forceinline__ void fb_profile(int n, const VelScratch& vs, double cax, double cay, const DevVelParams& p, double v_max,
-                           double v_start, bool has_v_end, double v_end, int lane)
-{
-    if (v_start < 0.0) v_start = 0.0;
-    if (has_v_end && v_end < 0.0) v_end = 0.0;
-    const double vmax2 = v_max * v_max;
-    for (int i = lane; i < n; i += 64) {
-        const double ay = GGARR ? vs.gay[i] : cay;
-        double w = ay / vs.kabs[i];                 // ay * radius; kappa == 0 -> inf
-        if (!(w < vmax2)) w = vmax2;
-        if (i == 0 && w > v_start * v_start) w = v_start * v_start;
-        vs.w[i] = w;
-    }
-    wave_sync_lds();
-    dbg_stamp(vs.dbg, 8);
-    fb_sweep<EM, AXM1, GGARR, false>(n, vs, cax, cay, p, vmax2, lane);
-    dbg_stamp(vs.dbg, 9);
-    if (lane == 0 && has_v_end && vs.w[n - 1] > v_end * v_end) vs.w[n - 1] = v_end * v_end;
-    wave_sync_lds();
-    fb_sweep<EM, AXM1, GGARR, true>(n, vs, cax, cay, p, vmax2, lane);
-    dbg_stamp(vs.dbg, 10);
-}
-
-// tph.calc_vel_profile_brake on LDS arrays: out[0..n) as v^2, zeros after standstill. Same systolic scheme as fb_sweep.
-template <int EM, bool GGARR>
-__device__ __forceinline__ void brake_profile(int n, double* out, const VelScratch& vs, double cax, double cay, double v_start,
-                              const DevVelParams& p, int lane)
-{
-    const double icay = 1.0 / cay;
-    double w = v_start * v_start;                          // state entering the chunk (uniform)
-    int stopped = 0;
-    if (lane == 0) out[0] = w;
-    for (int base = 0; base < n - 1; base += 64) {
-        const int cnt = (n - 1 - base) < 64 ? (n - 1 - base) : 64;
-        const int ic = (lane < cnt) ? base + lane : base + cnt - 1;
-        const double kq_i = vs.kabs[ic] * (GGARR ? vs.igay[ic] : icay), e_i = vs.el[ic], ax_i = GGARR ? vs.gax[ic] : cax;
-        const double te = 2.0 * e_i, axa = fabs(ax_i);
-        const double A0 = 1.0 - te * p.drag_m, A1 = A0 + te * (axa * kq_i), B1 = te * axa;
-        double w_in = w, w_out = w; int st_in = stopped, st_out = 0;
-        double r = 0.0;
-        auto sys_step = [&]() {
-            if constexpr (EM == 1) r = fmin(fma(A1, w_in, -B1), A0 * w_in);
-            else r = w_in + 2.0 * ax_poss_w<EM, true, VMODE_DECEL_FORW>(w_in, kq_i, ax_i, p, vs.axm, 0.0) * e_i;
-            st_out = (st_in || (r < 0.0)) ? 1 : 0;
-            w_out = st_out ? w_in : r;
-            w_in = wave_shr1_f64(w_out, w);
-            st_in = wave_shr1_i32(st_out, stopped);
-                };
-        for (int it = 0; it < cnt; it += 4) { sys_step(); sys_step(); sys_step(); sys_step(); }      // (idempotent beyond cnt)
-        if (lane < cnt) out[base + lane + 1] = st_out ? 0.0 : r;
-        w = readlane_f64(w_out, cnt - 1);
-        stopped = __builtin_amdgcn_readlane(st_out, cnt - 1);
-    }
-    wave_sync_lds();
-}
-
-// out[0] = 0, out[i] = out[i - 1] + src[i - 1] for i < m, in the SEQUENTIAL summation order of np.cumsum (bit-identical),
-// executed systolically: lane l adds its element to the partial sum handed over by lane l - 1 (DPP wave_shr:1)
-__device__ __forceinline__ void wave_cumsum_seq(const double* src, double* out, int m, int lane)
-{
-    double carry = 0.0;
-    if (lane == 0 && m > 0) out[0] = 0.0;
-    for (int base = 0; base < m - 1; base += 64) {
-        const int cnt = (m - 1 - base) < 64 ? (m - 1 - base) : 64;
-        const double e = src[(lane < cnt) ? base + lane : base + cnt - 1];
-        double s_in = carry, s_out = 0.0;
-        for (int it = 0; it < cnt; it += 4) {                        // (idempotent beyond cnt)
-#pragma unroll
-            for (int u = 0; u < 4; ++u) { s_out = s_in + e; s_in = wave_shr1_f64(s_out, carry); }
-        }
-        if (lane < cnt) out[base + lane + 1] = s_out;
-        carry = readlane_f64(s_out, cnt - 1);
-    }
-    wave_sync_lds();
-}
-
-// out[0] = 0, out[i] = sum of src[0 .. i-1] for i < m as a wave-parallel prefix sum (log-step shuffles, 64 elements per round).
-// NOT the summation order of np.cumsum: used where the arc length only enters results with a 1e-5 tolerance (distance to the
-// object in the batch follow preparation), never where indices are derived from it.
-__device__ __forceinline__ void wave_cumsum_par(const double* src, double* out, int m, int lane)
-{
-    double carry = 0.0;
-    if (lane == 0 && m > 0) out[0] = 0.0;
-    for (int base = 0; base < m - 1; base += 64) {
-        const int i = base + lane;
-        const double e = i < m - 1 ? src[i] : 0.0;
-        double x = e;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const double y = __shfl_up(x, d); if (lane >= d) x += y; }
-        if (i < m - 1) out[i + 1] = carry + x;
-        carry += __shfl(x, 63);
-    }
-    wave_sync_lds();
-}
-
-// first index i in [0, m) with pred(i), or m (wave-parallel search; pred is evaluated per lane)
-template <typename Pred>
-__device__ __forceinline__ int wave_find_first(int m, int lane, Pred pred)
-{
-    for (int base = 0; base < m; base += 64) {
-        const int i = base + lane;
-        const unsigned long long b = __ballot(i < m && pred(i));
-        if (b) return base + __ffsll((long long)b) - 1;
-    }
-    return m;
-}
-
-__device__ __forceinline__ double angle3pt_dev(double ax, double ay, double bx, double by, double cx, double cy)
-{
-    double ang = atan2(cy - by, cx - bx) - atan2(ay - by, ax - bx);
-    if (ang > D_PI) ang -= 2.0 * D_PI;
-    else if (ang <= -D_PI) ang += 2.0 * D_PI;
-    return ang;
-}
-
-// get_s_coord.py:34-47 picks the neighbour of the closest point by comparing |angle3pt(nb, pos, neighbour)|. The wrapped
-// difference of two atan2 values is the angle between u = nb - pos and v = neighbour - pos in [0, pi], and the cosine is
-// monotone there: |ang1| > |ang2|  <=>  u.v1 / |v1| < u.v2 / |v2|  (|u| cancels). Two dot products and two square roots instead
-// of four atan2 (~600 instructions per projection). Degenerate vectors (pos on a polyline point) take the atan2 form.
-// Returns -1 / 0 / +1 for |ang1| < / == / > |ang2|.
-// `clamp1` / `clamp2`: the open polyline's index clamp put neighbour 1 / 2 onto the closest point itself (nb = 0 / nb = n - 1). The reference
-// then has ang1 (ang2) == 0 EXACTLY -- both atan2 calls see the same vectors -- and never takes the degenerate segment a == b, while the
-// cosines compare |u|^2 |v| with itself up to rounding (Cauchy-Schwarz equality) and did, for queries collinear with the end segment:
-// t = 0 / 0, s = NaN. Neighbour 1 clamped: -1 (the reference's 0 for ang2 == 0 selects the same segment and the same first index);
-// neighbour 2 clamped: +1 (the reference's 0 for ang1 == 0 is its own 0 / 0).
-__device__ __forceinline__ int angle_order_dev(double nx, double ny, double px, double py, double x1, double y1, double x2, double y2,
-                                               bool clamp1 = false, bool clamp2 = false)
-{
-    if (clamp2) return 1;
-    if (clamp1) return -1;
-    const double ux = nx - px, uy = ny - py, v1x = x1 - px, v1y = y1 - py, v2x = x2 - px, v2y = y2 - py;
-    const double n1 = v1x * v1x + v1y * v1y, n2 = v2x * v2x + v2y * v2y, nu = ux * ux + uy * uy;
-    if (!(n1 > 0.0) || !(n2 > 0.0) || !(nu > 0.0)) {
-        const double a1 = fabs(angle3pt_dev(nx, ny, px, py, x1, y1)), a2 = fabs(angle3pt_dev(nx, ny, px, py, x2, y2));
-        return a1 > a2 ? 1 : (a1 < a2 ? -1 : 0);
-    }
-    const double c1 = (ux * v1x + uy * v1y) * sqrt(n2), c2 = (ux * v2x + uy * v2y) * sqrt(n1);
-    return c1 < c2 ? 1 : (c1 > c2 ? -1 : 0);
-}
-
-// get_s_coord.py:8-99 on a strided polyline in global / LDS memory, all lanes take part; every lane returns s and idx0
-__device__ __forceinline__ double get_s_coord_dev(int n, const double* x, const double* y, int stride, const double* s_arr, int s_stride,
-                                  double px, double py, bool closed, int lane, int* idx0)
-{
-    double bd = INFINITY; int nb = 0x7fffffff;
-    for (int i = lane; i < n; i += 64) {
-        const double dx = x[(size_t)i * stride] - px, dy = y[(size_t)i * stride] - py;
-        const double d2 = dx * dx + dy * dy;
-        if (d2 < bd) { bd = d2; nb = i; }
-    }
-    wave_min2(bd, nb);
-    int i1, i2;
-    if (closed) { i1 = nb - 1; if (i1 < 0) i1 += n; i2 = nb + 1; if (i2 > n - 1) i2 = 0; }
-    else { i1 = nb - 1 > 0 ? nb - 1 : 0; i2 = nb + 1 < n - 1 ? nb + 1 : n - 1; }
-    const double nx = x[(size_t)nb * stride], ny = y[(size_t)nb * stride];
-    const double x1 = x[(size_t)i1 * stride], y1 = y[(size_t)i1 * stride];
-    const double x2 = x[(size_t)i2 * stride], y2 = y[(size_t)i2 * stride];
-    const int ord = angle_order_dev(nx, ny, px, py, x1, y1, x2, y2, i1 == nb, i2 == nb);
-    double ax, ay, bx, by;
-    if (ord > 0) { ax = x1; ay = y1; bx = nx; by = ny; } else { ax = nx; ay = ny; bx = x2; by = y2; }
-    const double t = ((px - ax) * (bx - ax) + (py - ay) * (by - ay)) / ((bx - ax) * (bx - ax) + (by - ay) * (by - ay));
-    const double fx = ax + t * (bx - ax), fy = ay + t * (by - ay);
-    const double ds = sqrt((ax - fx) * (ax - fx) + (ay - fy) * (ay - fy));
-    const double s = (ord > 0 ? s_arr[(size_t)i1 * s_stride] : s_arr[(size_t)nb * s_stride]) + ds;
-    if (idx0) *idx0 = (ord >= 0) ? i1 : nb;
-    return s;
-}
-
-// Index pair start of the global race line segment an object is projected on (calc_vel_profile_follow.py:172-176:
-// get_s_coord(closed=True, only the first index is used). All 2 x ceil(G / 64) loads of a lane are independent: four points per
-// round trip from the contiguous x / y copies instead of one strided load per iteration.
-__device__ __forceinline__ int globrl_index_dev(const DevLat& lat, double px, double py, int lane)
-{
-    const int G = lat.G - 1;
-    double bd = INFINITY; int nb = 0x7fffffff;
-    for (int i0 = 0; i0 < G; i0 += 256) {
-        double xs[4], ys[4]; int id[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { const int i = i0 + u * 64 + lane; id[u] = i < G ? i : G - 1; xs[u] = at(lat.grx, id[u]); ys[u] = at(lat.gry, id[u]); }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const double dx = xs[u] - px, dy = ys[u] - py, d2 = dx * dx + dy * dy;
-            if (d2 < bd) { bd = d2; nb = id[u]; }
-        }
-    }
-    wave_min2(bd, nb);
-    int i1 = nb - 1; if (i1 < 0) i1 += G;
-    int i2 = nb + 1; if (i2 > G - 1) i2 = 0;
-    const int ord = angle_order_dev(at(lat.grx, nb), at(lat.gry, nb), px, py, at(lat.grx, i1), at(lat.gry, i1), at(lat.grx, i2), at(lat.gry, i2));
-    return ord >= 0 ? i1 : nb;
-}
-
-// Index pair start of the global race line segment ONE LANE's object is projected on (calc_vel_profile_follow.py:172-176; the wave form is
-// globrl_index_dev): closest race line point (first minimum, like np.argmin; the points are read with uniform indices, every lane compares
-// with its own object), then the neighbour test of get_s_coord (closed = True). Every lane of the wave must call it.
-__device__ __forceinline__ int lane_globrl_index(const DevLat& lat, double ox, double oy)
-{
-    const int G = lat.G - 1;
-    double bd = INFINITY; int nb = 0;
-#pragma unroll 8
-    for (int i = 0; i < G; ++i) {
-        const double dx = lat.grx[i] - ox, dy = lat.gry[i] - oy, d2 = dx * dx + dy * dy;
-        if (d2 < bd) { bd = d2; nb = i; }
-    }
-    int i1 = nb - 1; if (i1 < 0) i1 += G;
-    int i2 = nb + 1; if (i2 > G - 1) i2 = 0;
-    const int ord = angle_order_dev(at(lat.grx, nb), at(lat.gry, nb), ox, oy, at(lat.grx, i1), at(lat.gry, i1), at(lat.grx, i2), at(lat.gry, i2));
-    return ord >= 0 ? i1 : nb;
-}
-
-struct FollowIn { double v_start, v_ego, v_obj, safety_d, obj_dist, obj_x, obj_y; };
-
-// calc_vel_profile_follow.py:78-313. Inputs: vs.kabs[n], vs.el[n_el >= n] (tailing zero), gg; result vs.w (v^2).
-// `ext_sync`: when set, the unconstrained profile (:297-307) has been computed by ANOTHER wave of the workgroup into vs.w; the
-// function then joins that wave at a workgroup barrier instead of computing it itself (k_tick: wave 3 works for wave 0).
-template <int EM, bool AXM1, bool GGARR>
-__device__ __forceinline__ void follow_profile(const DevLat& lat, int n, int n_el, const VelScratch& vs, double cax, double cay,
-                               const DevVelParams& p, const FollowIn& fi, int lane, int* too_close, int* vel_bound,
-                               bool ext_sync = false, bool skip_free = false)
-{
-    int vb = 1;
-    const double control_d = p.c_p * fi.safety_d + p.len_veh;                            // :141
-    const double safety_d = fi.safety_d + p.len_veh;                                     // :144
-    const int tc = (fi.obj_dist - safety_d) < 0.0;                                       // :147-149
-    const double v_max = p.v_max;
-
-    dbg_stamp(vs.dbg, 4);
-    brake_profile<EM, GGARR>(n, vs.wb, vs, cax, cay, fi.v_start, p, lane);   // :152-159
-    dbg_stamp(vs.dbg, 5);
-    // arc length s = [0, cumsum(el[:-1])] (:203) next to the ego stop distance (:162-166)
-    wave_cumsum_seq(vs.el, vs.s, n_el, lane);                  // s[i] = sum of el[0 .. i-1], sequential order
-    // first point at or below 0.1 m/s on the brake profile; the ego stop distance is the arc length up to it (:162-166)
-    int idb = wave_find_first(n, lane, [&](int i) { return !(vs.wb[i] > 0.01); });
-    if (idb > n_el) idb = n_el;
-    double ego_stop = 0.0;
-    if (idb > 0) ego_stop = (idb < n_el) ? vs.s[idb] : vs.s[n_el - 1] + vs.el[n_el - 1];
-
-    // opponent: closest point of the global race line (:172-179), brake scan with ggv [100, 14, 14] (:134,185-199)
-    const int G = lat.G - 1;
-    const double* grl = lat.glob_rl;
-    dbg_stamp(vs.dbg, 6);
-    const int idx_s_opp = globrl_index_dev(lat, fi.obj_x, fi.obj_y, lane);
-    dbg_stamp(vs.dbg, 7);
-    const double vel0 = grl[(size_t)idx_s_opp * 5 + 4];
-    const double vel_start = fi.v_obj < vel0 ? fi.v_obj : vel0;                          // :182
-    double opp_stop = 0.0, wopp = vel_start * vel_start;
-    int stopped = (wopp > 0.01) ? 0 : 1;                                                 // id_brake counts v > 0.1
-    for (int c0 = 0; c0 < G && !stopped; c0 += 64) {
-        const int i = c0 + lane;
-        if (i < G) {
-            int j = i + idx_s_opp; if (j >= G) j -= G;
-            vs.chunk[lane] = fabs(grl[(size_t)j * 5 + 3]);
-            vs.chunk[64 + lane] = grl[(size_t)(j + 1) * 5] - grl[(size_t)j * 5];
-        }
-        wave_sync_lds();
-        if (lane == 0) {
-            const int m = (G - c0) < 64 ? (G - c0) : 64;
-            for (int k = 0; k < m; ++k) {
-                // point c0 + k has v > 0.1: its element length counts towards the stop distance
-                opp_stop += vs.chunk[64 + k];
-                if (c0 + k + 1 >= G) { stopped = 1; break; }
-                const double a = ax_poss_w<EM, true, VMODE_DECEL_FORW>(wopp, vs.chunk[k] * (1.0 / 14.0), 14.0, p, vs.axm, 0.0);
-                const double r = wopp + 2.0 * a * vs.chunk[64 + k];
-                wopp = r < 0.0 ? 0.0 : r;                                                // standstill: profile stays 0
-                if (!(wopp > 0.01)) { stopped = 1; break; }
-            }
-        }
-        stopped = __shfl(stopped, 0);
-        wave_sync_lds();
-    }
-    opp_stop = __shfl(opp_stop, 0);
-
-    dbg_stamp(vs.dbg, 11);
-    // characteristic indices (:201-221)
-    const double s_stop = fi.obj_dist - safety_d + opp_stop;                             // :206
-    int stop_idx = wave_find_first(n_el - 1, lane, [&](int i) { return !(vs.s[i] < s_stop); });   // :208-209
-    double v_end = 0.0;
-    if (lane == 0) {
-        if (s_stop > vs.s[n_el - 1]) {                                                   // :212-221
-            const double s_ends = opp_stop - (s_stop - vs.s[n_el - 1]);
-            int idx = 0; double summed = 0.0;
-            while (summed < s_ends && idx < G) {
-                int j = idx + idx_s_opp; if (j >= G) j -= G;
-                summed += grl[(size_t)(j + 1) * 5] - grl[(size_t)j * 5];
-                ++idx;
-            }
-            int j = (idx % G) + idx_s_opp; if (j >= G) j -= G;
-            v_end = grl[(size_t)j * 5 + 4];
-        }
-    }
-    v_end = __shfl(v_end, 0);
-    dbg_stamp(vs.dbg, 12);
-
-    // control velocity (:232-239, get_control_vel :28-75)
-    double v_control;
-    if (p.ctrl == 0) v_control = (fi.v_obj - p.k_p * (control_d - fi.obj_dist) + p.k_d * (fi.v_obj - fi.v_ego));
-    else {
-        double a = (control_d - fi.obj_dist) * D_PI / 2 * 1 / p.tan_w;
-        const double lo = -D_PI / 2 + 1e-5, hi = D_PI / 2 - 1e-5;
-        a = a < lo ? lo : (a > hi ? hi : a);
-        v_control = (fi.v_obj - tan(a) * p.k_p + p.k_d * (fi.v_obj - fi.v_ego));
-    }
-    if (v_control < 0.0) v_control = 0.0;
-    if (v_control > v_max) v_control = v_max;
-
-    // vs.wc <- "vx_profile" (:247-294)
-    if (ego_stop < s_stop) {
-        int idx_c = 0, n_decel = 0; double vcs = fi.v_start;      // vx_control_start
-        if (fi.v_start > v_control && stop_idx >= 2) {                                   // :250-258
-            const double wctl = v_control * v_control;
-            int first = 0x7fffffff;
-            for (int i = lane; i < n; i += 64) if (vs.wb[i] <= wctl) { first = i; break; }
-            const int di = wave_min_i32(first);                                           // (first index over the lanes: an integer minimum)
-            idx_c = (di == 0x7fffffff) ? 0 : di;                                          // np.argmax of an all-False mask
-            if (idx_c > stop_idx) idx_c = stop_idx;
-            if (idx_c == 0) idx_c = stop_idx;
-            n_decel = idx_c + 1 < n ? idx_c + 1 : n;
-            vcs = sqrt(vs.wb[n_decel - 1]);
-        } else {
-            if (!(stop_idx >= 2)) vb = 0;                                                // :260-261
-        }
-        // SEGMENT 2 (:267-286): FB profile on [idx_c, stop_idx] capped at v_control
-        const int m = (stop_idx + 1 < n ? stop_idx + 1 : n) - idx_c;
-        if (stop_idx - idx_c > 0) {
-            VelScratch sub = vs;
-            sub.w = vs.wc + idx_c; sub.kabs = vs.kabs + idx_c; sub.el = vs.el + idx_c;
-            sub.gax = vs.gax ? vs.gax + idx_c : nullptr; sub.gay = vs.gay ? vs.gay + idx_c : nullptr;
-            sub.igay = vs.igay ? vs.igay + idx_c : nullptr;
-            fb_profile<EM, AXM1, GGARR>(m, sub, cax, cay, p, v_control, vcs, true, v_end, lane);
-            if (fabs(sqrt(vs.wc[idx_c]) - vcs) > 1.0) vb = 0;
-        } else if (stop_idx - idx_c == 0) {
-            if (lane == 0) vs.wc[idx_c] = vcs * vcs;
-        }
-        // vx_decel[:-1] in front, zeros behind (:289)
-        for (int i = lane; i < n; i += 64) {
-            if (i < n_decel - 1) vs.wc[i] = vs.wb[i];
-            else if (i > stop_idx) vs.wc[i] = 0.0;
-        }
-        wave_sync_lds();
-        if (fabs(sqrt(vs.wc[0]) - fi.v_start) > 1.0) vb = 0;                             // :291-292
-    } else {
-        for (int i = lane; i < n; i += 64) vs.wc[i] = vs.wb[i];                          // :294
-        wave_sync_lds();
-    }
-    // complete profile (:297-307) and intersection (:310)
-    if (skip_free) {                                           // LTPL_VEL_FOLLOW_CONTROLLED: the caller intersects (:297-310)
-        for (int i = lane; i < n; i += 64) vs.w[i] = vs.wc[i];
-        wave_sync_lds();
-        *too_close = tc; *vel_bound = vb;
-        return;
-    }
-    if (ext_sync) __syncthreads();                             // the helper wave has written vs.w
-    else fb_profile<EM, AXM1, GGARR>(n, vs, cax, cay, p, v_max, fi.v_start, false, 0.0, lane);
-    for (int i = lane; i < n; i += 64) { const double a = vs.wc[i], b = vs.w[i]; vs.w[i] = a < b ? a : b; }
-    wave_sync_lds();
-    *too_close = tc; *vel_bound = vb;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// kernels of the velocity seam and the fused tick
-// ---------------------------------------------------------------------------------------------------------------------
-struct DevVelJob {
-    int mode, n, n_el, has_v_end;
-    int off_kappa, off_el, off_gg, off_out;       // offsets (in doubles) into the pooled job arrays
-    double v_start, v_end, v_ego, v_obj, safety_d, obj_dist, obj_x, obj_y;
-    // the car of the job (fleet::VelJob, ABI v6): v_max <= 0 / n_axm == 0 -> the launch's parameter set (seam 2, host planner)
-    double v_max;
-    int axm_off, n_axm;                           // rows [axm_off, axm_off + n_axm) of the launch's stacked machine tables
-    int gg_rows, lane_form;                       // gg_rows 1: off_gg holds n caller-supplied [ax, ay] rows (local_gg as a dict, OTH.py:649-666) instead of two
-                                                  // constants; lane_form 1 (fleet): operands in the lane plane, the job belongs to a lane kernel
-};
-
-// `lite`: only what the forward-backward and brake profiles touch (w, kabs, el, machine table, run flags) -- no arc length, no follow scratch
-__device__ __forceinline__ VelScratch carve_vel_scratch(unsigned char* base, int cap, bool with_gg, bool with_xy,
-                                                        double** px, double** py, bool lite = false)
-{
-    VelScratch vs;
-    double* d = reinterpret_cast<double*>(base);
-    const int c1 = cap + 2;
-    vs.w = d; d += c1; vs.kabs = d; d += c1; vs.el = d; d += c1;
-    if (!lite) { vs.s = d; d += c1; vs.wb = d; d += c1; vs.wc = d; d += c1; }
-    else { vs.s = nullptr; vs.wb = nullptr; vs.wc = nullptr; }
-    if (with_gg) { vs.gax = d; d += c1; vs.gay = d; d += c1; vs.igay = d; d += c1; }
-    else { vs.gax = nullptr; vs.gay = nullptr; vs.igay = nullptr; }
-    if (with_xy) { *px = d; d += c1; *py = d; d += c1; }
-    if (!lite) { vs.chunk = d; d += 128; } else vs.chunk = nullptr;
-    vs.axm = d; d += 128;
-    vs.start = reinterpret_cast<unsigned char*>(d);
-    vs.cap = cap;
-    vs.dbg = nullptr;
-    return vs;
-}
-
-static size_t vel_scratch_bytes(int cap, bool with_gg, bool with_xy, bool lite = false)
-{
-    size_t arrays = (lite ? 3 : 6) + (with_gg ? 3 : 0) + (with_xy ? 2 : 0);
-    size_t b = sizeof(double) * (arrays * (size_t)(cap + 2) + (lite ? 128 : 256)) + (size_t)cap + 16;
-    return (b + 15) / 16 * 16;
-}
-
-// seam (2): one wave per job. GG = false: the job's friction limits are constant along the path (the fleet's jobs: rows 0 of loc_gg hold
-// them) -- three LDS arrays less per wave and no per-point loads of the limits. SEL (fleet): the occupancy of these launches is bound by
-// the LDS a wave needs and the recurrences are latency chains (~200 cycles per point), so the fleet runs the forward-backward / brake jobs
-// (SEL 1: three arrays, "lite" scratch) and the follow jobs (SEL 2: six arrays, job slot 0 of every planner) as two launches; a block
-// whose job belongs to the other launch returns at once. SEL 3 (fleet, calls with location dependent friction): the forward-backward
-// jobs whose limits are ROWS (DevVelJob::gg_rows) -- the lane kernel that solves a tick's other forward-backward jobs takes constants only.
-// `job_stride`: block b works on job b * job_stride.
-template <int EM, bool AXM1, bool GG = true, int SEL = 0>
-__global__ __launch_bounds__(64) void k_vel_profile(DevLat lat, DevVelParams p_, const DevVelJob* jobs,
-                                                    const double* pool, double* out_pool, int* out_flags, int cap,
-                                                    long long* dbg, DoneSignal done, int job_stride)
-{
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int lane = threadIdx.x;
-    dbg_stamp(dbg, 0);
-    const int j = blockIdx.x * job_stride;
-    const DevVelJob jb = jobs[j];
-    if (jb.n <= 0) { signal_done(done); return; }          // unused slot of a fleet's job table (fleet_dev.hpp); seam (2) itself rejects empty jobs
-    // the car of the job: its own vel_max / machine table (a fleet of different cars), else the launch's
-    DevVelParams p = p_;
-    if (jb.v_max > 0.0) p.v_max = jb.v_max;
-    if (jb.n_axm > 0) { p.n_axm = jb.n_axm; p.axm = p_.axm + 2 * jb.axm_off; }
-    const bool follow = jb.mode == LTPL_VEL_FOLLOW || jb.mode == LTPL_VEL_FOLLOW_CONTROLLED;
-    if constexpr (SEL == 1) { if (follow) return; }
-    if constexpr (SEL == 2) { if (!follow || jb.lane_form) return; }      // (fleet: follow jobs without friction rows run one lane per job, k_fleet_follow_lanes)
-    if constexpr (SEL == 3) { if (follow || !jb.gg_rows) return; }
-    constexpr bool LITE = SEL == 1 || SEL == 3;
-    VelScratch vs = carve_vel_scratch(smem, cap, GG, false, nullptr, nullptr, LITE);
-    vs.dbg = dbg;
-    const int n = jb.n;
-    for (int i = lane; i < n; i += 64) {
-        vs.kabs[i] = fabs(pool[jb.off_kappa + i]);
-        if constexpr (GG) {
-            vs.gax[i] = pool[jb.off_gg + 2 * i];
-            const double ay = pool[jb.off_gg + 2 * i + 1];
-            vs.gay[i] = ay; vs.igay[i] = 1.0 / ay;
-        }
-    }
-    const double cax = GG ? 1.0 : pool[jb.off_gg], cay = GG ? 1.0 : pool[jb.off_gg + 1];
-    for (int i = lane; i < 2 * p.n_axm; i += 64) vs.axm[i] = p.axm[i];
-    for (int i = lane; i < jb.n_el; i += 64) vs.el[i] = pool[jb.off_el + i];
-    wave_sync_lds();
-    dbg_stamp(dbg, 1);
-    int too_close = 0, vel_bound = 1;
-    if (jb.mode == LTPL_VEL_FB) {
-        fb_profile<EM, AXM1, GG>(n, vs, cax, cay, p, p.v_max, jb.v_start, jb.has_v_end != 0, jb.v_end, lane);
-    } else if (jb.mode == LTPL_VEL_BRAKE) {
-        brake_profile<EM, GG>(n, vs.w, vs, cax, cay, jb.v_start, p, lane);
-    } else if constexpr (!LITE) {
-        FollowIn fi; fi.v_start = jb.v_start; fi.v_ego = jb.v_ego; fi.v_obj = jb.v_obj; fi.safety_d = jb.safety_d;
-        fi.obj_dist = jb.obj_dist; fi.obj_x = jb.obj_x; fi.obj_y = jb.obj_y;
-        follow_profile<EM, AXM1, GG>(lat, n, jb.n_el, vs, cax, cay, p, fi, lane, &too_close, &vel_bound, false,
-                                     jb.mode == LTPL_VEL_FOLLOW_CONTROLLED);
-    }
-    dbg_stamp(dbg, 2);
-    for (int i = lane; i < n; i += 64) out_pool[jb.off_out + i] = sqrt(vs.w[i]);
-    if (lane == 0) { out_flags[2 * j] = too_close; out_flags[2 * j + 1] = vel_bound; }
-    dbg_stamp(dbg, 3);
-    signal_done(done);
-}
-
-struct DevTickVelIn {
-    double gg_ax, gg_ay, safety_d, v_max_offset;
-    const double* vel_plan; const double* vel_est; const double* pos_est_x; const double* pos_est_y;
-    const double* veh_vel;
-};
-struct DevTickVelOut { double* vx; double* ax; int* vel_bound; int* too_close; };
-
-// per-primitive velocity stage of OnlineTrajectoryHandler.calc_vel_profile (OTH.py:688-941) on a fresh path:
-// cut_index_pos = 0, vel_course empty, no brake prefix (the host rejects vel_plan > v_max + 0.1, for which the
-// reference itself fails at OTH.py:919 because the prefix it computes is never merged back)
-template <int EM, bool AXM1>
-__device__ __forceinline__ void tick_vel_stage(const DevLat& lat, const DevPathsIn& in, const DevPathsOut& out, const WavePath& wp,
-                               const VelScratch& vs, const double* px, const double* py, const DevVelParams& p,
-                               const DevTickVelIn& vin, const DevTickVelOut& vout, int s, int slot, int lane,
-                               bool helper_wave)
-{
-    // vs.kabs already holds |kappa| (k_tick). helper_wave: another wave computes the unconstrained follow profile into vs.w
-    const int n = wp.n_pts;
-    const double vel_plan = vin.vel_plan[s];
-    const double cax = vin.gg_ax, cay = vin.gg_ay;
-    // s = [0, cumsum(el[:-1])] (OTH.py:743), one extra entry for get_s_coord's zero-prefixed cumsum (:777)
-    wave_cumsum_seq(vs.el, vs.s, n + 1, lane);
-    int too_close = 0, vel_bound = 1;
-    bool have_follow = false;
-    if (wp.name == LTPL_ACT_FOLLOW) {                                                    // OTH.py:763-830
-        FollowIn fi; fi.v_start = vel_plan; fi.v_ego = vin.vel_est[s]; fi.safety_d = vin.safety_d;
-        const int ci = out.closest_obj_index[s];
-        const int v0 = in.veh_off[s];
-        if (ci < 0 || ci >= in.veh_off[s + 1] - v0) {
-            fi.obj_dist = 0.0; fi.v_obj = 0.0; fi.obj_x = vin.pos_est_x[s]; fi.obj_y = vin.pos_est_y[s];
-        } else {
-            const int pp = in.pos_off[v0 + ci];
-            fi.obj_x = in.pos_x[pp]; fi.obj_y = in.pos_y[pp]; fi.v_obj = vin.veh_vel[v0 + ci];
-            const double s_obj = get_s_coord_dev(n, px, py, 1, vs.s, 1, fi.obj_x, fi.obj_y, false, lane, nullptr);
-            const double s_sta = get_s_coord_dev(n, px, py, 1, vs.s, 1, vin.pos_est_x[s], vin.pos_est_y[s], false, lane, nullptr);
-            fi.obj_dist = s_obj - s_sta;
-        }
-        // follow_profile rebuilds vs.s as [0, cumsum(el[:-1])] for n_el = n: identical values
-        follow_profile<EM, AXM1, false>(lat, n, n, vs, cax, cay, p, fi, lane, &too_close, &vel_bound, helper_wave);
-        have_follow = true;
-    }
-    if (wp.name != LTPL_ACT_FOLLOW || wp.reduced) {                                      // OTH.py:834-923
-        if (have_follow) { for (int i = lane; i < n; i += 64) vs.wb[i] = vs.w[i]; wave_sync_lds(); }
-        const int rl = lat.rl_idx[wp.goal_layer];
-        int dn = wp.end_node - rl; if (dn < 0) dn = -dn;
-        const double raceline_offset = (double)dn * lat.lat_offset;
-        double v_end; int v_idx;
-        if (wp.reduced) {
-            v_end = 0.0;
-            const double spl_len = vs.s[n - 1];
-            int first = 0x7fffffff;
-            for (int i = lane; i < n - 1; i += 64) if (!(vs.s[i + 1] < (spl_len - 5.0))) { first = i; break; }
-            const int di = wave_min_i32(first);
-            v_idx = ((di == 0x7fffffff) ? 0 : di) + 1;
-            if (v_idx == 1 && n > 1) v_idx = n;
-        } else {
-            v_end = lat.vel_rl[wp.goal_layer];
-            const double red = v_end * lat.vel_decrease_lat * raceline_offset;
-            v_end -= (red < v_end ? red : v_end);
-            v_idx = n;
-        }
-        if (v_idx > 1) fb_profile<EM, AXM1, false>(v_idx, vs, cax, cay, p, p.v_max, vel_plan, true, v_end, lane);
-        else { if (lane == 0) vs.w[0] = 0.0; }
-        for (int i = (v_idx > 1 ? v_idx : 1) + lane; i < n; i += 64) vs.w[i] = 0.0;         // OTH.py:901-903
-        wave_sync_lds();
-        vel_bound = fabs(sqrt(vs.w[0]) - vel_plan) < vin.v_max_offset ? 1 : 0;           // OTH.py:906-911
-        if (have_follow && n >= 6) {
-            // OTH.py:923 compares ROW 5 of both arrays; only column 5 (vx) can differ, so the whole profile switches
-            const bool take_follow = sqrt(vs.wb[5]) < sqrt(vs.w[5]);
-            if (take_follow) { for (int i = lane; i < n; i += 64) vs.w[i] = vs.wb[i]; wave_sync_lds(); }
-        }
-    }
-    // finalise (OTH.py:925-941): filt_window == 1 is the identity; ax from neighbouring points, -5 at standstill
-    double* o_vx = vout.vx + (size_t)slot * out.cap_pts;
-    double* o_ax = vout.ax + (size_t)slot * out.cap_pts;
-    for (int i = lane; i < n; i += 64) {
-        const double wi = vs.w[i];
-        const double v = sqrt(wi);
-        o_vx[i] = v;
-        double a = 0.0;
-        if (i < n - 1) {
-            a = (vs.w[i + 1] - wi) / (2.0 * (vs.s[i + 1] - vs.s[i]));
-            if (fabs(v) <= 1e-8 && fabs(a) <= 1e-8) a = -5.0;
-        }
-        o_ax[i] = a;
-    }
-    if (lane == 0) { vout.vel_bound[slot] = vel_bound; vout.too_close[slot] = too_close; }
-}
+#include "vel_wave.hpp"
 
 // the arguments of k_tick as they lie in the kernarg segment
 struct TickKArgs { PathsKArgs pk; DevVelParams p; DevTickVelIn vin; DevTickVelOut vout; int vel_off, vel_stride, vel_cap; };
@@ -1227,7 +285,7 @@ __device__ __forceinline__ void tick_body(const DevLat& lat_, const DevPathsIn& 
         if (follow_n > 0) {
             double* dpx; double* dpy;
             VelScratch v0 = carve_vel_scratch(smem + vel_off, vel_cap, false, true, &dpx, &dpy);   // wave 0's arrays
-            v0.start = smem + vel_off + (size_t)LTPL_MAX_ACTIONS * vel_stride;                     // own run-start flags
+            v0.start = smem + fused_tick_flags_off(vel_off, vel_stride);                           // own run-start flags
             v0.dbg = nullptr;
             fb_profile<EM, AXM1, false>(follow_n, v0, vin.gg_ax, vin.gg_ay, p, p.v_max, vin.vel_plan[s], false, 0.0, lane);
         }
@@ -1365,1126 +423,7 @@ __global__ __launch_bounds__(WG_THREADS) void k_tick_persistent(const TickKArgs*
     if (threadIdx.x == 0) __hip_atomic_store(&mb->exited, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// throughput form of the velocity stage: ONE LANE PER PROFILE
-// ---------------------------------------------------------------------------------------------------------------------
-// The recurrences are sequential per profile, so a wave that owns a single profile runs them with 1/64 of its lanes.
-// For batches the velocity stage therefore runs as its own kernel in which every lane of a wave64 integrates its own
-// profile: 64 independent dependent-chains per instruction stream. All per-row data a lane touches lives in TILED
-// planes: element (slot, row) at ((slot / 64) * cap_pts + row) * 64 + slot % 64, so that the 64 lanes of a wave
-// (64 consecutive slots) read / write row i as ONE coalesced 512-byte line. The path kernel writes |kappa| and the
-// element lengths of every path into two such planes.
-//   job type 0 (one lane per action slot):  'follow' -> the controlled profile (ego brake, opponent stop distance, segment
-//            forward-backward profile; calc_vel_profile_follow.py:151-294); other primitives -> the generic
-//            forward-backward profile with the race-line end velocity (OTH.py:834-903)
-//   job type 1 (one lane per scenario):     the unconstrained profile of a 'follow' slot (calc_vel_profile_follow.py:297-307)
-//            -- independent of type 0, so the two halves of the follow mode run on different lanes
-// k_vel_final (lane per slot, no recurrence) intersects / selects the profiles, derives ax and writes the outputs.
-struct DevVelPrep {             // per-slot scalars produced by k_follow_prep (follow action only)
-    double* obj_dist; double* v_obj; double* obj_x; double* obj_y; int* idx_s_opp;
-};
-
-struct VelPlanes {              // tiled planes (doubles), tile index = job index: generic jobs [0, n_slots_pad), follow jobs behind
-    ke_t* KE;                   // (|kappa|, element length) as an fp64 pair: ONE 16-byte load per row and lane   n_slots_pad + n_scen_pad tiles
-    double* P0;                 // type 0 result: follow -> "vx_profile" (:289/:294), else the generic profile     (same size)
-    double* P1;                 // type 1 result: unconstrained profile of a follow job                n_scen_pad tiles
-    double* P2;                 // ego brake profile (follow)                                           n_scen_pad tiles
-    double* P3;                 // segment profile (follow), afterwards the generic profile of a reduced-horizon follow job
-    double* XY;                 // (x, y) pairs of the follow jobs' path points (written by the path kernel)   n_scen_pad tiles x 2
-    int* flags;                 // per tile: VF_* bits
-    int* fseg;                  // per follow job [2]: n_decel (-1: everything from the brake profile), stop_idx -- composition of
-                                // "vx_profile" (:289 / :294) from P2 / P3 / zeros, done by k_vel_final (VF_COMPOSE)
-    int cap_pts;
-    int plane_rows;             // rows of the blocked planes KE / XY (kep_base / kep_row, paths_team.hpp)
-};
-
-__device__ __forceinline__ size_t tile_base(int idx, int cap_pts) { return ((size_t)(idx >> 6) * cap_pts) * 64 + (idx & 63); }
-
-struct LaneProf {
-    const ke_t* KE;                       // tile-strided: element i at [i * 64]
-};
-
-// a / b with the hardware reciprocal and two Newton steps (~1 ulp; the velocity stage is checked to 1e-5 relative). b = 0
-// yields NaN, which the callers' `!(w < vmax2)` clamp treats like +inf.
-__device__ __forceinline__ double fast_div(double a, double b)
-{
-    double r = __builtin_amdgcn_rcp(b);
-    r = fma(fma(-b, r, 1.0), r, r);
-    r = fma(fma(-b, r, 1.0), r, r);
-    return a * r;
-}
-
-// Issue priority of the velocity kernels' waves (s_setprio 0 .. 3) inside a SIMD they share with path waves. EXPERIMENT (round 5, -DLTPL_VEL_PRIO=<n>):
-// a velocity wave blocks the slot of a fourth path wave for as long as it lives; with a higher priority it issues whenever it is ready and
-// lives shorter. Default 0 = off (the A/B is in DESIGN.md section 9).
-#ifndef LTPL_VEL_PRIO
-#define LTPL_VEL_PRIO 0
-#endif
-#define LTPL_VEL_SETPRIO() do { if (LTPL_VEL_PRIO > 0) __builtin_amdgcn_s_setprio(LTPL_VEL_PRIO); } while (0)
-#define LCH 8      // rows per register chunk: all loads of a chunk are issued before the chunk's recurrence steps
-#ifndef LCHF
-#define LCHF 16    // forward sweep of lane_fb_profile: one 8-byte (|kappa|, el) load per row -> 16 rows per chunk in 32 registers
-#endif
-#ifndef LCHA
-#define LCHA 16    // affine case, forward sweep: rows per register chunk
-#endif
-#ifndef LCHB
-#define LCHB 12    // backward sweep: (|kappa|, el) + the fp64 profile state per row
-#endif
-
-// DIRECT OUTPUT OF THE GENERIC PROFILES (round 5). The rows of a generic job (every non-follow primitive) used to take a detour: the
-// backward sweep rewrote the plane, k_vel_final read plane and element lengths again, took the root, differentiated and wrote vx / ax.
-// Now the backward sweep of lane_fb_profile<.., EMIT = true> produces vx / ax of the rows it finalises (row r: v = sqrt(w_r),
-// a = (w_r+1 - w_r) / (2 e_r), -5 at standstill, OTH.py:925-941 -- the operations of k_vel_final) and hands a chunk of LCHB rows per lane to
-// lane_emit_flush, which transposes through LDS exactly like k_vel_final: lane = job writes its rows, lane = (job of a group of 8, pair of
-// rows) stores 16 contiguous bytes of the slot's output row. The sweep runs wave-uniformly in this mode (all 64 lanes take part in every
-// flush, lanes that have no rows left contribute none). k_vel_final only serves the follow jobs (compositions, intersections, row-5 choice).
-struct LaneEmit {
-    double* tbuf;                  // LDS [32 * LE_PITCH]
-    int* s_cnt; int* s_rhi;        // LDS [64]: rows of the job's chunk, row of its first value (values run DOWNWARDS from there)
-    unsigned long long* s_o;       // LDS [64]: vx row base of every lane's job (0: idle lane), written by the caller
-    long long ax_delta;            // vout.ax - vout.vx in doubles: the ax row of a job lies at the same offset of the other array
-    double w0;                     // out: v^2 of row 0 after the backward sweep
-};
-#define LE_PITCH (LCHB + 2)        // doubles per job row in LDS (16-byte aligned pairs); the buffer is sized for the longest chunk
-#ifndef LCHC
-#define LCHC 8                     // rows per chunk of the CAPPED backward sweep (follow jobs, round 6): three operands per row -- (|kappa|, el), the forward
-                                   // value, the cap -- double-buffered next to the chunk's outputs: 8 rows keep the kernel at 256 registers
-#endif
-template <int NCH>
-__device__ __forceinline__ void lane_emit_flush(const LaneEmit& E, int lane, int cnt, int r_hi, const double (&vv)[NCH], const double (&aa)[NCH])
-{
-    static_assert(NCH % 2 == 0 && NCH <= 16 && NCH <= LCHB, "pairs of rows, eight pieces per job, the LDS buffer of the longest chunk");
-    constexpr int PITCH = NCH + 2;
-    E.s_cnt[lane] = cnt; E.s_rhi[lane] = r_hi;
-    const int q = lane >> 3, piece = lane & 7;
-#pragma unroll
-    for (int pass = 0; pass < 4; ++pass) {
-        const int half = pass & 1;                                      // jobs [32 half, 32 half + 32); passes 0, 1: vx, 2, 3: ax
-        if ((lane >> 5) == half) {
-#pragma unroll
-            for (int c = 0; c < NCH; c += 2) store2(&E.tbuf[(lane & 31) * PITCH + c], pass < 2 ? vv[c] : aa[c], pass < 2 ? vv[c + 1] : aa[c + 1]);
-        }
-        wave_sync_lds();
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int jl = k * 8 + q, jj = half * 32 + jl, c = 2 * piece;
-            const int cn = E.s_cnt[jj];
-            if (c >= cn || c >= NCH) continue;
-            const dbl2 v = *reinterpret_cast<const dbl2*>(&E.tbuf[jl * PITCH + c]);     // rows r - c (x) and r - c - 1 (y)
-            double* o = reinterpret_cast<double*>(E.s_o[jj]) + (pass < 2 ? 0 : E.ax_delta) + (E.s_rhi[jj] - c);
-            if (c + 1 < cn) store2_u(o - 1, v.y, v.x); else o[0] = v.x;
-        }
-        wave_sync_lds();
-    }
-}
-
-// tph.calc_vel_profile(closed=False) for one lane: rows [off, off + n) of the path, result into plane D (as v^2).
-// Rows are processed in register chunks of LCH; the rows of the NEXT chunk are requested before the current chunk's recurrence
-// steps run (double buffer). Two things keep the compiler's s_waitcnt placement tight (measured: a per-step vmcnt(0) -- i.e. a
-// full store acknowledgement per row -- made the kernel 8x slower than its instruction count):
-//   * the function is force-inlined into the kernel, so the planes are addressed with GLOBAL instructions (an out-of-line copy
-//     takes them by reference as generic pointers -> FLAT loads / stores, which always wait on vmcnt(0) and lgkmcnt(0));
-//   * a recurrence step is branch-free (selects instead of `if (active)`), so a chunk is one basic block and the waits are
-//     counted exactly: the stores of a chunk stay in flight while the next chunk's operands are awaited.
-// What the EMIT form puts out per finalised row: the profile's own v^2 (NoCap: the generic jobs), or -- FollowCap, round 6 -- the MINIMUM of it and
-// the row of the follow job's "vx_profile" (calc_vel_profile_follow.py:289 / :294: ego brake profile P2 in front of row n_decel - 1, segment
-// profile P3 up to stop_idx, zeros behind), i.e. what k_vel_final composed from four planes for every follow job: the unconstrained profile's
-// backward sweep now finalises the follow job's rows itself and k_vel_final only serves the (rare) reduced-horizon follow jobs.
-struct NoCap { static constexpr bool active = false; __device__ __forceinline__ double at(int) const { return INFINITY; } };
-struct FollowCap {
-    static constexpr bool active = true;
-    const double* P2; const double* P3; int nd, stop_idx;          // nd < 0: every row from the brake profile
-    __device__ __forceinline__ double at(int r) const
-    {
-        const bool from_b = nd < 0 || r < nd - 1;
-        const double* src = from_b ? P2 : P3;
-        const double v = src[(size_t)r * 64];
-        return (!from_b && r > stop_idx) ? 0.0 : v;
-    }
-};
-
-template <int EM, bool AXM1, bool EMIT = false, class CAP = NoCap>
-__device__ __forceinline__ void lane_fb_profile(const LaneProf& L, double* D, int off, int n, double cax, double cay,
-                                                const DevVelParams& p, const double* axm_tab, double v_max, double v_start,
-                                                bool has_v_end, double v_end, long long* dbg = nullptr, int drow = -1, LaneEmit* em = nullptr, int lane = 0,
-                                                const CAP& cap = CAP())
-{
-    if (v_start < 0.0) v_start = 0.0;
-    if (has_v_end && v_end < 0.0) v_end = 0.0;
-    const double vmax2 = v_max * v_max, icay = 1.0 / cay, axm1 = axm_tab[1], dm = p.drag_m, axa = fabs(cax);
-    const double vend2 = has_v_end ? v_end * v_end : INFINITY;
-    const ke_t* KEb = L.KE;                         // row r of this profile: KEb[kep_row(off + r)]
-#define KE_AT(r) KEb[kep_row(off + (r))]
-    double* Dp = D + (size_t)off * 64;
-    const ke_t rec0 = KE_AT(0);
-    double kabs_i = (double)rec0.x, e_i = (double)rec0.y;
-    double wi = fmin(cay * ke_rcp(rec0), vmax2);
-    if (wi > v_start * v_start) wi = v_start * v_start;
-    Dp[0] = wi;
-    if constexpr (!EMIT) { if (n < 2) return; }
-    do {                                   // (EMIT: a lane without a profile -- n < 2 -- skips the forward sweep but takes part in the flushes below)
-    if constexpr (EMIT) { if (n < 2) break; }
-    // ---- lateral-limit speed + forward sweep (accel_forw) in one pass -------------------------------------------------
-    if constexpr (EM == 1 && AXM1) {
-        // Affine case (exponent 1, one-row machine table). A velocity wave is alone on its SIMD and issues one instruction every
-        // ~13 cycles whether or not it depends on the previous one (measured: 610 cycles per row for ~50 instructions; splitting
-        // a chunk into independent coefficient work and a short dependent chain changed nothing), so the step is written for
-        // the smallest instruction COUNT:  w' = max(A0 w + te min(max(axa - g w, 0), axm), 0)  with te = 2 e, A0 = 1 - te dm,
-        // g = axa |kappa| / ay  -- algebraically the reference's min(tyre, machine) - drag step; the limit speed comes from the
-        // fp32 hardware reciprocal of |kappa| (no fp64 division), full chunks run without the `valid` selects (the partial chunk at the end has them).
-        constexpr int CA = CAP::active ? LCHC : LCHA;             // rows per register chunk (the capped form carries more state through the sweeps)
-        const double axg = axa * icay;
-        double orig_p = wi, g_p = kabs_i * axg, e_p = e_i;      // operands of the row in front of the current step
-        bool active = false, prev_acc = false;
-        ke_t kr[CA], kn[CA];
-        const int nst = n - 1;
-#pragma unroll
-        for (int c = 0; c < CA; ++c) { const int r = 1 + c < n ? 1 + c : n - 1; kr[c] = KE_AT(r); }
-        auto step = [&](const ke_t& rec, int i, bool valid) {
-            const double w0n = fmin(cay * ke_rcp(rec), vmax2);    // inf on straights
-            const bool acc = w0n > orig_p;
-            const bool act = active || (acc && !prev_acc);
-            const double te = e_p + e_p;
-            const double u = fmin(fmax(fma(-g_p, wi, axa), 0.0), axm1);
-            const double wn = fmax(fma(te, u, fma(-(te * dm), wi, wi)), 0.0);
-            const double wnext = (act && wn < w0n) ? wn : w0n;
-            if (valid) {
-                Dp[(size_t)(i + 1) * 64] = wnext;
-                active = act && !(wn > vmax2); prev_acc = acc;
-                wi = wnext; orig_p = w0n; g_p = (double)rec.x * axg; e_p = (double)rec.y;
-            }
-        };
-        int base = 0;
-        for (; base + CA <= nst; base += CA) {
-#pragma unroll
-            for (int c = 0; c < CA; ++c) {                   // operands of the next chunk (clamped rows: harmless re-reads at the end)
-                const int r = base + CA + 1 + c < n ? base + CA + 1 + c : n - 1;
-                kn[c] = KE_AT(r);
-            }
-#pragma unroll
-            for (int c = 0; c < CA; ++c) step(kr[c], base + c, true);
-#pragma unroll
-            for (int c = 0; c < CA; ++c) kr[c] = kn[c];
-        }
-        if (base < nst) {
-#pragma unroll
-            for (int c = 0; c < CA; ++c) step(kr[c], base + c, base + c < nst);
-        }
-        if (wi > vend2) { wi = vend2; Dp[(size_t)(n - 1) * 64] = wi; }            // the end-velocity clamp of the last step
-        kabs_i = (double)KE_AT(n - 1).x;                             // |kappa| of the last row (start of the backward sweep)
-    } else {
-        double orig_i = wi;
-        bool active = false, prev_acc = false;
-        ke_t kr[LCHF], kn[LCHF];
-#pragma unroll
-        for (int c = 0; c < LCHF; ++c) { const int r = 1 + c < n ? 1 + c : n - 1; kr[c] = KE_AT(r); }
-        for (int base = 0; base < n - 1; base += LCHF) {
-#pragma unroll
-            for (int c = 0; c < LCHF; ++c) {                   // operands of the next chunk (clamped rows: harmless re-reads at the end)
-                const int r = base + LCHF + 1 + c < n ? base + LCHF + 1 + c : n - 1;
-                kn[c] = KE_AT(r);
-            }
-#pragma unroll
-            for (int c = 0; c < LCHF; ++c) {
-                const int i = base + c;
-                const bool valid = i < n - 1;
-                const double k_c = (double)kr[c].x, e_c = (double)kr[c].y;
-                double w0n = fast_div(cay, k_c);
-                w0n = (w0n < vmax2) ? w0n : vmax2;
-                const bool acc = w0n - orig_i > 0.0;
-                const bool act = active || (acc && !prev_acc);
-                const double kq_i = kabs_i * icay;
-                double wn;
-                if constexpr (EM == 1 && AXM1) {
-                    const double te = 2.0 * e_i;
-                    const double A0 = 1.0 - te * dm, A1 = A0 - te * (axa * kq_i), B1 = te * axa, B2 = te * axm1;
-                    wn = fmax(fmin(fmax(fma(A1, wi, B1), A0 * wi), fma(A0, wi, B2)), 0.0);
-                } else {
-                    const double a = ax_poss_w<EM, AXM1, VMODE_ACCEL_FORW>(wi, kq_i, cax, p, axm_tab, axm1);
-                    wn = fmax(wi + 2.0 * a * e_i, 0.0);
-                }
-                double wnext = (act && wn < w0n) ? wn : w0n;
-                const bool act_out = act && !(wn > vmax2);
-                wnext = (i + 1 == n - 1 && wnext > vend2) ? vend2 : wnext;
-                if (valid) Dp[(size_t)(i + 1) * 64] = wnext;
-                active = valid ? act_out : active; prev_acc = valid ? acc : prev_acc;
-                orig_i = valid ? w0n : orig_i; wi = valid ? wnext : wi; kabs_i = valid ? k_c : kabs_i; e_i = valid ? e_c : e_i;
-            }
-#pragma unroll
-            for (int c = 0; c < LCHF; ++c) kr[c] = kn[c];
-        }
-    }
-    } while (0);
-    vl_stamp(dbg, drow, 8);
-    // ---- backward sweep (decel_backw), mirrored indices; with a constant gg the unmirrored-gg quirk is void --------------
-    if constexpr (EMIT) {
-        // wave-uniform form with direct output (see LaneEmit): every lane walks the chunks of the LONGEST profile of the wave, its own steps
-        // masked by `valid`; the plane is only read (forward values), vx / ax of the finalised rows go out through lane_emit_flush
-        constexpr int CB = CAP::active ? LCHC : LCHB;             // rows per chunk
-        const int nst = n >= 2 ? n - 1 : 0;
-        const double axg = axa * icay;
-        double orig_p = wi, g_p = kabs_i * axg;                       // affine form: operands of the row above
-        double orig_i = wi;                                           // general form
-        bool active = false, prev_acc = false;
-        ke_t kr[CB], kn[CB]; double wr[CB], wq[CB];
-        [[maybe_unused]] double cr[CB], cq[CB];                   // CAP: the cap's rows of the current / the next chunk
-        [[maybe_unused]] double fprev = 0.0;                          // CAP: the value put out for the row above
-        if constexpr (CAP::active) { if (n >= 1) fprev = fmin(cap.at(n - 1), wi); }
-#pragma unroll
-        for (int c = 0; c < CB; ++c) {
-            const int r = n - 2 - c >= 0 ? n - 2 - c : 0;
-            kr[c] = KE_AT(r); wr[c] = Dp[(size_t)r * 64];
-            if constexpr (CAP::active) cr[c] = cap.at(r);
-        }
-        for (int base = 0; __ballot(base < nst) != 0ull; base += CB) {
-#pragma unroll
-            for (int c = 0; c < CB; ++c) {
-                const int r = n - 2 - base - CB - c >= 0 ? n - 2 - base - CB - c : 0;
-                kn[c] = KE_AT(r); wq[c] = Dp[(size_t)r * 64];
-                if constexpr (CAP::active) cq[c] = cap.at(r);
-            }
-            double vv[CB], aa[CB];
-#pragma unroll
-            for (int c = 0; c < CB; ++c) {
-                const bool valid = base + c < nst;
-                const double wold = wr[c], e_b = (double)kr[c].y, k_c = (double)kr[c].x;
-                double wn; bool acc;
-                if constexpr (EM == 1 && AXM1) {
-                    acc = wold > orig_p;
-                    const double te = 2.0 * e_b, tdm = te * dm, g_n = k_c * axg;
-                    const double w1 = fmax(fma(te, fmax(fma(-g_p, wi, axa), 0.0), fma(tdm, wi, wi)), 0.0);
-                    wn = fmin(fmax(fma(te, fmax(fma(-g_n, w1, axa), 0.0), fma(tdm, w1, wi)), 0.0), w1);
-                } else {
-                    acc = wold - orig_i > 0.0;
-                    const double kq_i = kabs_i * icay, kq_n = k_c * icay;
-                    const double a = ax_poss_w<EM, AXM1, VMODE_DECEL_BACKW>(wi, kq_i, cax, p, axm_tab, axm1);
-                    wn = fmax(wi + 2.0 * a * e_b, 0.0);
-                    const double a2 = ax_poss_w<EM, AXM1, VMODE_DECEL_BACKW>(wn, kq_n, cax, p, axm_tab, axm1);
-                    wn = fmin(fmax(wi + 2.0 * a2 * e_b, 0.0), wn);
-                }
-                const bool act = active || (acc && !prev_acc);
-                const double wnext = (act && wn < wold) ? wn : wold;
-                double v = 0.0, a_out = 0.0;
-                if (valid) {
-                    if constexpr (CAP::active) {
-                        const double f = fmin(cr[c], wnext);           // the follow job's row: min("vx_profile", unconstrained profile)
-                        v = sqrt(f);
-                        a_out = (fprev - f) / (2.0 * e_b);
-                        fprev = f;
-                    } else {
-                        v = sqrt(wnext);
-                        a_out = (wi - wnext) / (2.0 * e_b);            // (w_r+1 - w_r) / (2 e_r): the row above is the state before this step
-                    }
-                    if (fabs(v) <= 1e-8 && fabs(a_out) <= 1e-8) a_out = -5.0;
-                    active = act && !(wn > vmax2); prev_acc = acc;
-                    wi = wnext; orig_p = wold; orig_i = wold; g_p = k_c * axg; kabs_i = k_c;
-                }
-                vv[c] = v; aa[c] = a_out;
-            }
-            const int left = nst - base;
-            lane_emit_flush(*em, lane, left < 0 ? 0 : (left < CB ? left : CB), n - 2 - base, vv, aa);
-#pragma unroll
-            for (int c = 0; c < CB; ++c) { kr[c] = kn[c]; wr[c] = wq[c]; if constexpr (CAP::active) cr[c] = cq[c]; }
-        }
-        em->w0 = wi;
-    } else if constexpr (EM == 1 && AXM1) {
-        // same form: w1 = max(A0 w + te max(axa - g_i w, 0), 0), w' = min(max(te dm w1 + w + te max(axa - g_n w1, 0), 0), w1),
-        // A0 = 1 + te dm (no machine limit under braking)
-        const double axg = axa * icay;
-        double orig_p = wi, g_p = kabs_i * axg;
-        bool active = false, prev_acc = false;
-        ke_t kr[LCHB], kn[LCHB]; double wr[LCHB], wq[LCHB];
-        const int nst = n - 1;
-#pragma unroll
-        for (int c = 0; c < LCHB; ++c) {
-            const int r = n - 2 - c >= 0 ? n - 2 - c : 0;
-            kr[c] = KE_AT(r); wr[c] = Dp[(size_t)r * 64];
-        }
-        auto step = [&](const ke_t& rec, double wold, int i, bool valid) {
-            const bool acc = wold > orig_p;
-            const bool act = active || (acc && !prev_acc);
-            const double te = 2.0 * (double)rec.y, tdm = te * dm, g_n = (double)rec.x * axg;
-            const double w1 = fmax(fma(te, fmax(fma(-g_p, wi, axa), 0.0), fma(tdm, wi, wi)), 0.0);
-            const double wn = fmin(fmax(fma(te, fmax(fma(-g_n, w1, axa), 0.0), fma(tdm, w1, wi)), 0.0), w1);
-            const bool take = act && wn < wold;
-            const double wnext = take ? wn : wold;
-            if (valid) {
-                // only rows the sweep lowers are rewritten: an unconditional store per row made the sweep 1.5x slower (gfx9 counts
-                // loads and stores in ONE in-order vmcnt, so every wait for prefetched rows also waits for the older stores)
-                if (take) Dp[(size_t)(n - 2 - i) * 64] = wn;
-                active = act && !(wn > vmax2); prev_acc = acc;
-                wi = wnext; orig_p = wold; g_p = g_n;
-            }
-        };
-        int base = 0;
-        for (; base + LCHB <= nst; base += LCHB) {
-            // rows of the next chunk are not written by this chunk's steps (a step only rewrites its own row n - 2 - i)
-#pragma unroll
-            for (int c = 0; c < LCHB; ++c) {
-                const int r = n - 2 - base - LCHB - c >= 0 ? n - 2 - base - LCHB - c : 0;
-                kn[c] = KE_AT(r); wq[c] = Dp[(size_t)r * 64];
-            }
-#pragma unroll
-            for (int c = 0; c < LCHB; ++c) step(kr[c], wr[c], base + c, true);
-#pragma unroll
-            for (int c = 0; c < LCHB; ++c) { kr[c] = kn[c]; wr[c] = wq[c]; }
-        }
-        if (base < nst) {
-#pragma unroll
-            for (int c = 0; c < LCHB; ++c) step(kr[c], wr[c], base + c, base + c < nst);
-        }
-    } else {
-        double orig_i = wi;
-        bool active = false, prev_acc = false;
-        ke_t kr[LCHB], kn[LCHB]; double wr[LCHB], wq[LCHB];
-#pragma unroll
-        for (int c = 0; c < LCHB; ++c) {
-            const int r = n - 2 - c >= 0 ? n - 2 - c : 0;
-            kr[c] = KE_AT(r); wr[c] = Dp[(size_t)r * 64];
-        }
-        for (int base = 0; base < n - 1; base += LCHB) {
-            // rows of the next chunk are not written by this chunk's steps (a step only rewrites its own row n - 2 - i)
-#pragma unroll
-            for (int c = 0; c < LCHB; ++c) {
-                const int r = n - 2 - base - LCHB - c >= 0 ? n - 2 - base - LCHB - c : 0;
-                kn[c] = KE_AT(r); wq[c] = Dp[(size_t)r * 64];
-            }
-#pragma unroll
-            for (int c = 0; c < LCHB; ++c) {
-                const int i = base + c;
-                const bool valid = i < n - 1;
-                const double wold = wr[c], e_b = (double)kr[c].y, k_c = (double)kr[c].x;
-                const bool acc = wold - orig_i > 0.0;
-                const bool act = active || (acc && !prev_acc);
-                const double kq_i = kabs_i * icay, kq_n = k_c * icay;
-                double wn;
-                if constexpr (EM == 1 && AXM1) {
-                    const double te = 2.0 * e_b;
-                    const double A0 = 1.0 + te * dm, A1 = A0 - te * (axa * kq_i), B1 = te * axa;
-                    const double C0 = te * dm, C1 = C0 - te * (axa * kq_n), D1 = te * axa;
-                    wn = fmax(fmax(fma(A1, wi, B1), A0 * wi), 0.0);
-                    const double t0 = fma(C0, wn, wi), t1 = fma(C1, wn, wi + D1);
-                    wn = fmin(fmax(fmax(t1, t0), 0.0), wn);
-                } else {
-                    const double a = ax_poss_w<EM, AXM1, VMODE_DECEL_BACKW>(wi, kq_i, cax, p, axm_tab, axm1);
-                    wn = fmax(wi + 2.0 * a * e_b, 0.0);
-                    const double a2 = ax_poss_w<EM, AXM1, VMODE_DECEL_BACKW>(wn, kq_n, cax, p, axm_tab, axm1);
-                    wn = fmin(fmax(wi + 2.0 * a2 * e_b, 0.0), wn);
-                }
-                const bool take = act && wn < wold;
-                const double wnext = take ? wn : wold;
-                if (valid && take) Dp[(size_t)(n - 2 - i) * 64] = wn;
-                const bool act_out = act && !(wn > vmax2);
-                active = valid ? act_out : active; prev_acc = valid ? acc : prev_acc;
-                orig_i = valid ? wold : orig_i; wi = valid ? wnext : wi; kabs_i = valid ? k_c : kabs_i;
-            }
-#pragma unroll
-            for (int c = 0; c < LCHB; ++c) { kr[c] = kn[c]; wr[c] = wq[c]; }
-        }
-    }
-}
-
-#undef KE_AT
-
-#define VF_BOUND_FOLLOW 1
-#define VF_TOO_CLOSE    2
-#define VF_HAS_GENERIC  4
-#define VF_BOUND_GENERIC 8
-#define VF_COMPOSE 16
-#define VF_DONE 32                 // the lane kernel wrote the slot's vx / ax / flags itself (round 6: follow jobs of batches): nothing left for k_vel_final
-
-// The CONTROLLED part of calc_vel_profile_follow.py:78-294 for one lane (= one follow job): ego brake profile -> plane P2, opponent stop
-// distance on the global race line from index idx_s_opp, characteristic indices, segment profile -> plane P3. "vx_profile" (:289 / :294)
-// is then: P2 in front of row n_decel - 1 (all rows when !two_seg), P3 up to stop_idx, zeros behind -- composed by the caller. Shared by the
-// batch velocity stage (k_vel_lanes) and the fleet's lane kernel of the follow jobs (k_fleet_follow_lanes, round 5).
-struct LaneFollowOut { int vel_bound, too_close, two_seg, n_decel, stop_idx; };
-template <int EM, bool AXM1>
-__device__ __forceinline__ LaneFollowOut lane_follow_controlled(const DevLat& lat, const LaneProf& L, double* P2, double* P3, int n, double cax, double cay,
-                                                                const DevVelParams& p, const double* axm_tab, double v_start, double v_ego, double v_obj,
-                                                                double obj_dist, double safety_d_in, int idx_s_opp, long long* dbg, int drow)
-{
-    const double icay = 1.0 / cay;
-    int vel_bound = 1;
-    const double control_d = p.c_p * safety_d_in + p.len_veh, safety_d = safety_d_in + p.len_veh;
-    const int too_close = (obj_dist - safety_d) < 0.0 ? 1 : 0;
-    const double v_max = p.v_max;
-    double v_control;
-    if (p.ctrl == 0) v_control = (v_obj - p.k_p * (control_d - obj_dist) + p.k_d * (v_obj - v_ego));
-    else {
-        double a = (control_d - obj_dist) * D_PI / 2 * 1 / p.tan_w;
-        const double lo = -D_PI / 2 + 1e-5, hi = D_PI / 2 - 1e-5;
-        a = a < lo ? lo : (a > hi ? hi : a);
-        v_control = (v_obj - tan(a) * p.k_p + p.k_d * (v_obj - v_ego));
-    }
-    if (v_control < 0.0) v_control = 0.0;
-    if (v_control > v_max) v_control = v_max;
-    const double wctl = v_control * v_control;
-
-    // opponent brake distance on the global race line (:169-199); rows are gathered in chunks
-    const int G = lat.G - 1;
-    const double* grl = lat.glob_rl;
-    const double vel0 = grl[(size_t)idx_s_opp * 5 + 4];
-    double wopp = fmin(v_obj, vel0); wopp *= wopp;
-    double opp_stop = 0.0;
-    for (int base = 0; base < G && wopp > 0.01; base += LCH) {
-        double kr[LCH], lr[LCH];
-#pragma unroll
-        for (int c = 0; c < LCH; ++c) {
-            int j = base + c + idx_s_opp; j = j % G;
-            kr[c] = fabs(grl[(size_t)j * 5 + 3]); lr[c] = grl[(size_t)(j + 1) * 5] - grl[(size_t)j * 5];
-        }
-#pragma unroll
-        for (int c = 0; c < LCH; ++c) {
-            const int k = base + c;
-            if (k < G && wopp > 0.01) {
-                opp_stop += lr[c];
-                if (k + 1 >= G) wopp = 0.0;
-                else {
-                    const double a = ax_poss_w<EM, true, VMODE_DECEL_FORW>(wopp, kr[c] * (1.0 / 14.0), 14.0, p, axm_tab, 0.0);
-                    const double r = wopp + 2.0 * a * lr[c];
-                    wopp = r < 0.0 ? 0.0 : r;
-                }
-            }
-        }
-    }
-    vl_stamp(dbg, drow, 1);
-    // one pass over the path rows: ego brake profile -> P2 (:152-159), ego stop distance (:162-166), first index at
-    // or below the control speed (:254), arc length and stop index (:203-209)
-    const double s_stop = obj_dist - safety_d + opp_stop;                            // :206
-    double ego_stop = 0.0, s_run = 0.0, s_last = 0.0; int first_le = -1, stop_idx = 0;
-    {
-        double w = v_start * v_start; bool braking = true, counting = true, searching = true;
-        double kr[LCH], er[LCH], kn[LCH], en[LCH];
-        auto load_rows = [&](int base, double (&k)[LCH], double (&e)[LCH]) {
-#pragma unroll
-            for (int c = 0; c < LCH; ++c) {
-                const int r = base + c < n ? base + c : n - 1;
-                const ke_t ke = L.KE[kep_row(r)]; k[c] = (double)ke.x; e[c] = (double)ke.y;
-            }
-        };
-        load_rows(0, kr, er);
-        for (int base = 0; base < n; base += LCH) {
-            if (base + LCH < n) load_rows(base + LCH, kn, en);         // next chunk in flight during this chunk's steps
-#pragma unroll
-            for (int c = 0; c < LCH; ++c) {
-                const int i = base + c;
-                if (i < n) {
-                    const double wv = braking ? w : 0.0;
-                    P2[(size_t)i * 64] = wv;
-                    if (first_le < 0 && wv <= wctl) first_le = i;
-                    if (counting) { if (wv > 0.01) ego_stop += er[c]; else counting = false; }
-                    if (searching) { if (i < n - 1 && s_run < s_stop) stop_idx = i + 1; else searching = false; }
-                    if (i == n - 1) s_last = s_run; // s[n - 1]
-                    s_run += er[c];                 // s[i + 1]
-                    if (braking && i + 1 < n) {
-                        const double kq = kr[c] * icay, e = er[c];
-                        double r;
-                        if constexpr (EM == 1) {
-                            const double te = 2.0 * e, axa = fabs(cax);
-                            const double A0 = 1.0 - te * p.drag_m, A1 = A0 + te * (axa * kq);
-                            r = fmin(fma(A1, w, -te * axa), A0 * w);
-                        } else {
-                            r = w + 2.0 * ax_poss_w<EM, true, VMODE_DECEL_FORW>(w, kq, cax, p, axm_tab, 0.0) * e;
-                        }
-                        if (r < 0.0) braking = false; else w = r;
-                    }
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < LCH; ++c) { kr[c] = kn[c]; er[c] = en[c]; }
-        }
-    }
-    vl_stamp(dbg, drow, 2);
-    double v_end = 0.0;
-    if (s_stop > s_last) {                                                           // :212-221
-        // the stop point lies beyond the path: end velocity = race-line velocity where the opponent's remaining brake
-        // distance is used up; the element lengths are fetched LCH at a time (one round trip per chunk, not per step)
-        const double s_ends = opp_stop - (s_stop - s_last);
-        int idx = 0; double summed = 0.0; bool run = summed < s_ends;
-        while (run) {
-            double dl[LCH];
-#pragma unroll
-            for (int c = 0; c < LCH; ++c) {
-                int j = idx + c + idx_s_opp; j = j % G;
-                dl[c] = grl[(size_t)(j + 1) * 5] - grl[(size_t)j * 5];
-            }
-#pragma unroll
-            for (int c = 0; c < LCH; ++c)
-                if (run) { if (summed < s_ends && idx < G) { summed += dl[c]; ++idx; } else run = false; }
-            if (run && !(summed < s_ends && idx < G)) run = false;
-        }
-        int j = (idx % G) + idx_s_opp; if (j >= G) j -= G;
-        v_end = grl[(size_t)j * 5 + 4];
-    }
-    vl_stamp(dbg, drow, 3);
-    int idx_c = 0, n_decel = 0; const bool two_seg = ego_stop < s_stop;
-    if (two_seg) {                                                                   // :247-292
-        double vcs = v_start;
-        if (v_start > v_control && stop_idx >= 2) {
-            idx_c = first_le < 0 ? 0 : first_le;
-            if (idx_c > stop_idx) idx_c = stop_idx;
-            if (idx_c == 0) idx_c = stop_idx;
-            n_decel = idx_c + 1 < n ? idx_c + 1 : n;
-            vcs = sqrt(P2[(size_t)(n_decel - 1) * 64]);
-        } else if (!(stop_idx >= 2)) vel_bound = 0;
-        const int m = (stop_idx + 1 < n ? stop_idx + 1 : n) - idx_c;
-        if (stop_idx - idx_c > 0) {
-            lane_fb_profile<EM, AXM1>(L, P3, idx_c, m, cax, cay, p, axm_tab, v_control, vcs, true, v_end);
-            if (fabs(sqrt(P3[(size_t)idx_c * 64]) - vcs) > 1.0) vel_bound = 0;
-        } else if (stop_idx - idx_c == 0) P3[(size_t)idx_c * 64] = vcs * vcs;
-        const double first_v = (n_decel - 1 > 0) ? sqrt(P2[0]) : sqrt(P3[0]);
-        if (fabs(first_v - v_start) > 1.0) vel_bound = 0;
-    }
-    vl_stamp(dbg, drow, 4);
-    LaneFollowOut o; o.vel_bound = vel_bound; o.too_close = too_close; o.two_seg = two_seg ? 1 : 0; o.n_decel = n_decel; o.stop_idx = stop_idx;
-    return o;
-}
-
-// the generic forward-backward profile of a slot (OTH.py:834-903) into plane D; returns its vel_bound flag
-template <int EM, bool AXM1>
-__device__ __forceinline__ int lane_generic_profile(const DevLat& lat, const DevPathsOut& out, const LaneProf& L, double* D, int slot, int n,
-                                    int reduced, double cax, double cay, const DevVelParams& p, const double* axm_tab,
-                                    double vel_plan, double v_max_offset)
-{
-    const int goal = out.goal_layer[slot];
-    const int end_node = out.nodes[(size_t)slot * out.cap_nodes + out.n_nodes[slot] - 1];
-    int dn = end_node - lat.rl_idx[goal]; if (dn < 0) dn = -dn;
-    const double raceline_offset = (double)dn * lat.lat_offset;
-    double v_end; int v_idx;
-    if (reduced) {
-        v_end = 0.0;
-        double spl_len = 0.0;
-        for (int i = 0; i < n - 1; ++i) spl_len += (double)L.KE[kep_row(i)].y;
-        int first = -1; double c = 0.0;
-        for (int i = 0; i < n - 1; ++i) { c += (double)L.KE[kep_row(i)].y; if (first < 0 && !(c < (spl_len - 5.0))) first = i; }
-        v_idx = (first < 0 ? 0 : first) + 1;
-        if (v_idx == 1 && n > 1) v_idx = n;
-    } else {
-        v_end = lat.vel_rl[goal];
-        const double red = v_end * lat.vel_decrease_lat * raceline_offset;
-        v_end -= (red < v_end ? red : v_end);
-        v_idx = n;
-    }
-    if (v_idx > 1) lane_fb_profile<EM, AXM1>(L, D, 0, v_idx, cax, cay, p, axm_tab, p.v_max, vel_plan, true, v_end);
-    else D[0] = 0.0;
-    for (int i = (v_idx > 1 ? v_idx : 1); i < n; ++i) D[(size_t)i * 64] = 0.0;
-    return fabs(sqrt(D[0]) - vel_plan) < v_max_offset ? 1 : 0;
-}
-
-// The same with DIRECT OUTPUT (LaneEmit): vx / ax of the slot are written from here -- the rows the backward sweep finalises through the
-// LDS transposition of lane_emit_flush, the rows it does not own (the profile's last row, the zero tail of a reduced horizon) by the lane
-// itself. Called by ALL 64 lanes of the wave (`have` = the lane owns a job); returns the vel_bound flag.
-template <int EM, bool AXM1>
-__device__ __forceinline__ int lane_generic_profile_emit(const DevLat& lat, const DevPathsOut& out, const LaneProf& L, double* D, bool have, int slot, int n,
-                                                         int reduced, double cax, double cay, const DevVelParams& p, const double* axm_tab,
-                                                         double vel_plan, double v_max_offset, LaneEmit& E, int lane, double* o_vx)
-{
-    double v_end = 0.0; int v_idx = 0;
-    if (have) {
-        const int goal = out.goal_layer[slot];
-        const int end_node = out.nodes[(size_t)slot * out.cap_nodes + out.n_nodes[slot] - 1];
-        int dn = end_node - lat.rl_idx[goal]; if (dn < 0) dn = -dn;
-        const double raceline_offset = (double)dn * lat.lat_offset;
-        if (reduced) {
-            double spl_len = 0.0;
-            for (int i = 0; i < n - 1; ++i) spl_len += (double)L.KE[kep_row(i)].y;
-            int first = -1; double c = 0.0;
-            for (int i = 0; i < n - 1; ++i) { c += (double)L.KE[kep_row(i)].y; if (first < 0 && !(c < (spl_len - 5.0))) first = i; }
-            v_idx = (first < 0 ? 0 : first) + 1;
-            if (v_idx == 1 && n > 1) v_idx = n;
-        } else {
-            v_end = lat.vel_rl[goal];
-            const double red = v_end * lat.vel_decrease_lat * raceline_offset;
-            v_end -= (red < v_end ? red : v_end);
-            v_idx = n;
-        }
-    }
-    const int n_prof = v_idx > 1 ? v_idx : 0;                   // rows of the profile proper (0: the path has none, everything is zero)
-    lane_fb_profile<EM, AXM1, true>(L, D, 0, n_prof, cax, cay, p, axm_tab, p.v_max, vel_plan, true, v_end, nullptr, -1, &E, lane);
-    if (!have) return 0;
-    // rows n_prof - 1 .. n - 1: the profile's last row (its v^2 is in the plane: the backward sweep starts below it) and the zero tail;
-    // ax of a row differentiates towards the row above, which is zero (or absent: last row of the path, ax = 0) for all of them
-    const double w0 = n_prof >= 2 ? E.w0 : 0.0;
-    double* o_ax = o_vx + E.ax_delta;
-    for (int i = (n_prof >= 2 ? n_prof - 1 : 0); i < n; ++i) {
-        const double w = (n_prof >= 2 && i == n_prof - 1) ? D[(size_t)i * 64] : 0.0;
-        const double v = sqrt(w);
-        double a = 0.0;
-        if (i < n - 1) {
-            a = (0.0 - w) / (2.0 * (double)L.KE[kep_row(i)].y);
-            if (fabs(v) <= 1e-8 && fabs(a) <= 1e-8) a = -5.0;
-        }
-        o_vx[i] = v; o_ax[i] = a;
-    }
-    return fabs(sqrt(w0) - vel_plan) < v_max_offset ? 1 : 0;
-}
-
-// amdgpu_waves_per_eu(2): at most 256 registers. A velocity wave shares its SIMD with path waves of 128 registers each (4 x 128 = the whole
-// file): one of up to 256 registers waits for TWO of them to retire, one of 257+ for THREE. Same-box A/B of this kernel at 265 registers
-// (what the allocator takes when left alone, round 6) against 256 with four values parked in scratch: 38.4 against 40.6 M ticks/s
-// (profiles/r06j_ab_follow_emit.txt) -- the footprint of a velocity wave is what the path kernel pays for.
-template <int EM, bool AXM1>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_vel_lanes(DevLat lat, DevPathsIn in, DevPathsOut out, DevVelParams p,
-                                                  DevTickVelIn vin, DevVelPrep prep, VelPlanes vp, int n_slots, int n_scen,
-                                                  int n_blocks0, long long* dbg, DevTickVelOut vout, int emit)
-{
-    LTPL_VEL_SETPRIO();
-    __shared__ __align__(16) double le_tbuf[32 * LE_PITCH];        // direct output of the generic jobs (LaneEmit)
-    __shared__ int le_cnt[64], le_rhi[64];
-    __shared__ unsigned long long le_o[64];
-    // blocks [0, nbG): generic jobs; [nbG, nbG + nbF): follow jobs, controlled part; [nbG + nbF, nbG + 2 nbF): follow jobs,
-    // unconstrained profile. Waves beyond the job counters (known only on the device) exit at once.
-    __shared__ double axm_tab[128];
-    const int lane = threadIdx.x;
-    const int nbG = n_blocks0, nbF = (n_scen + 63) / 64;
-    const int cntG = out.job_cnt[0], cntF = out.job_cnt[1];
-    const int b = blockIdx.x;
-    if ((b < nbG && b * 64 >= cntG) || (b >= nbG && ((b - nbG) % nbF) * 64 >= cntF)) return;
-    for (int i = lane; i < 2 * p.n_axm; i += 64) axm_tab[i] = p.axm[i];
-    __syncthreads();
-    const int drow = b < nbG ? (b < 64 ? b : -1) : (b < nbG + nbF ? (b - nbG < 64 ? 64 + b - nbG : -1) : (b - nbG - nbF < 64 ? 128 + b - nbG - nbF : -1));
-    vl_stamp(dbg, drow, 0);
-    const double cax = vin.gg_ax, cay = vin.gg_ay;
-    const int fbase = out.n_slots_pad;
-    if (b >= nbG + nbF) {
-        // ---- follow jobs, unconstrained profile (calc_vel_profile_follow.py:297-307) -------------------------------------
-        const int j = (b - nbG - nbF) * 64 + lane;
-        if (j >= cntF) return;
-        const int2 js = out.job_slot[fbase + j];
-        const int slot = js.x;
-        if ((emit & 2) && !out.reduced[slot]) return;                 // (large batches: the follow block below runs this profile itself and puts the job's rows out)
-        LaneProf L; L.KE = vp.KE + kep_base(fbase + j, vp.plane_rows);
-        lane_fb_profile<EM, AXM1>(L, vp.P1 + tile_base(j, vp.cap_pts), 0, js.y, cax, cay, p, axm_tab, p.v_max,
-                                  vin.vel_plan[slot / LTPL_MAX_ACTIONS], false, 0.0, dbg, drow);
-        vl_stamp(dbg, drow, 6);
-        return;
-    }
-    const bool emit_generic = (emit & 1) != 0;                       // emit bit 0: generic jobs write their outputs here; bit 1: follow jobs do
-    if (b < nbG && emit_generic) {
-        // ---- generic jobs (every non-follow primitive, OTH.py:834-941): profile AND outputs, all 64 lanes stay for the output transposition.
-        //      Batches only (emit_generic = the launch has >= LTPL_EMIT_MIN_SCEN scenarios): the transposition is ~160 instructions per chunk
-        //      of 12 rows on the lane kernel's serial chain -- with a handful of jobs (single ticks on the long-horizon lattice: C5, 1 200
-        //      rows) k_vel_final's many short waves do that work faster (measured: +100 us on a 1.5 ms tick) ----
-        const int j = b * 64 + lane;
-        const bool have = j < cntG;
-        const int2 js = have ? out.job_slot[j] : make_int2(0, 0);
-        const int slot = js.x, n = have ? js.y : 0;
-        {   // longest profile of the launch (k_vel_final skips row chunks beyond it): one atomic per wave
-            const int nmax = wave_max_i32(n);
-            if (lane == 0) atomicMax(&out.job_cnt[2], nmax);
-        }
-        LaneProf L; L.KE = vp.KE + kep_base(j, vp.plane_rows);
-        double* o_vx = vout.vx + (size_t)slot * out.cap_pts;
-        le_o[lane] = have ? (unsigned long long)o_vx : 0ull;
-        LaneEmit E; E.tbuf = le_tbuf; E.s_cnt = le_cnt; E.s_rhi = le_rhi; E.s_o = le_o; E.ax_delta = (long long)(vout.ax - vout.vx); E.w0 = 0.0;
-        wave_sync_lds();
-        const int bound = lane_generic_profile_emit<EM, AXM1>(lat, out, L, vp.P0 + tile_base(j, vp.cap_pts), have, slot, n, have ? out.reduced[slot] : 0,
-                                                              cax, cay, p, axm_tab, have ? vin.vel_plan[slot / LTPL_MAX_ACTIONS] : 0.0, vin.v_max_offset, E, lane, o_vx);
-        if (have) {
-            vout.vel_bound[slot] = bound; vout.too_close[slot] = 0;
-            vp.flags[j] = VF_BOUND_FOLLOW | (bound ? VF_BOUND_GENERIC : 0);
-        }
-        vl_stamp(dbg, drow, 6);
-        return;
-    }
-    if (b >= nbG && (emit & 2)) {
-        // ---- follow jobs of LARGE batches (round 6): the controlled part, then the UNCONSTRAINED profile in the same lane, whose backward sweep puts
-        //      out min("vx_profile", unconstrained profile) -- the follow job's rows (FollowCap) -- with vx / ax through the same LDS transposition as
-        //      the generic jobs. Otherwise the two halves run on two waves and k_vel_final reads four planes per follow job to compose, intersect,
-        //      differentiate and transpose: as much wave-time as the lane kernel itself (profiles/r06f_vel_pmc.txt). Same operations on the same
-        //      values in the same order: results unchanged bit for bit. Reduced-horizon follow jobs (rare) keep the old route inside this block.
-        //      Large batches only (ltpl_handle::follow_emit_min_scen): the lane now runs five sweeps one after the other instead of three next to
-        //      two -- neutral on the throughput of 32 768 scenarios per step, 135 against 117 us for a step of 1 024 (profiles/r06z_bench.json).
-        const int j = (b - nbG) * 64 + lane;
-        const bool have = j < cntF;
-        const int tile = fbase + j;                                   // (the planes hold n_scen_pad follow tiles: a lane without a job has one too)
-        const int2 js = have ? out.job_slot[tile] : make_int2(0, 0);
-        const int slot = js.x, n = have ? js.y : 0;
-        {
-            const int nmax = wave_max_i32(n);
-            if (lane == 0) atomicMax(&out.job_cnt[2], nmax);
-        }
-        const int s = slot / LTPL_MAX_ACTIONS;
-        LaneProf L; L.KE = vp.KE + kep_base(tile, vp.plane_rows);
-        double* P2 = vp.P2 + tile_base(j, vp.cap_pts);
-        double* P3 = vp.P3 + tile_base(j, vp.cap_pts);
-        const double vel_plan = have ? vin.vel_plan[s] : 0.0;
-        const int reduced = have ? out.reduced[slot] : 0;
-        FollowCap cap; cap.P2 = P2; cap.P3 = P3; cap.nd = -1; cap.stop_idx = 0;
-        bool direct = false;
-        int o_bound = 0, o_close = 0;
-        if (have) {
-            const LaneFollowOut fo = lane_follow_controlled<EM, AXM1>(lat, L, P2, P3, n, cax, cay, p, axm_tab, vel_plan, vin.vel_est[s], prep.v_obj[slot],
-                                                                      prep.obj_dist[slot], vin.safety_d, prep.idx_s_opp[slot], dbg, drow);
-            o_bound = fo.vel_bound; o_close = fo.too_close;
-            if (!reduced) { direct = true; cap.nd = fo.two_seg ? fo.n_decel : -1; cap.stop_idx = fo.stop_idx; }
-            else {
-                // reduced horizon: "vx_profile" materialised in P0, the generic profile on top of it in P3 (OTH.py:834-923), k_vel_final chooses by
-                // row 5; the unconstrained profile of such a job comes from its own wave below
-                double* P0 = vp.P0 + tile_base(tile, vp.cap_pts);
-                int flags = VF_BOUND_FOLLOW | VF_HAS_GENERIC;
-                if (fo.too_close) flags |= VF_TOO_CLOSE;
-                if (!fo.vel_bound) flags &= ~VF_BOUND_FOLLOW;
-                const bool two_seg = fo.two_seg != 0;
-                for (int i = 0; i < n; ++i) {
-                    const bool from_b = !two_seg || i < fo.n_decel - 1;
-                    P0[(size_t)i * 64] = from_b ? P2[(size_t)i * 64] : ((i > fo.stop_idx) ? 0.0 : P3[(size_t)i * 64]);
-                }
-                if (lane_generic_profile<EM, AXM1>(lat, out, L, P3, slot, n, reduced, cax, cay, p, axm_tab, vel_plan, vin.v_max_offset))
-                    flags |= VF_BOUND_GENERIC;
-                vp.flags[tile] = flags;
-            }
-        }
-        double* o_vx = vout.vx + (size_t)slot * out.cap_pts;
-        le_o[lane] = direct ? (unsigned long long)o_vx : 0ull;
-        LaneEmit E; E.tbuf = le_tbuf; E.s_cnt = le_cnt; E.s_rhi = le_rhi; E.s_o = le_o; E.ax_delta = (long long)(vout.ax - vout.vx); E.w0 = 0.0;
-        wave_sync_lds();
-        // (a lane that puts nothing out walks the sweep with zero rows; its one store -- the start value of row 0 -- goes to its brake plane, not to the
-        //  unconstrained plane another wave may be writing for a reduced-horizon job)
-        double* D = direct ? vp.P1 + tile_base(j, vp.cap_pts) : P2;
-        lane_fb_profile<EM, AXM1, true, FollowCap>(L, D, 0, direct && n >= 2 ? n : 0, cax, cay, p, axm_tab, p.v_max, vel_plan, false, 0.0, nullptr, -1, &E, lane, cap);
-        if (direct) {
-            // the top row: the backward sweep starts below it; its ax differentiates towards nothing (last row of the path)
-            const int i = n - 1;
-            const double w = fmin(cap.at(i), D[(size_t)i * 64]);
-            o_vx[i] = sqrt(w); o_vx[i + E.ax_delta] = 0.0;
-            vout.vel_bound[slot] = o_bound; vout.too_close[slot] = o_close;
-            vp.flags[tile] = VF_DONE;
-        }
-        vl_stamp(dbg, drow, 6);
-        return;
-    }
-    const bool fjob = b >= nbG;                                 // (follow jobs, controlled part; generic jobs of small launches: profile into P0, outputs by k_vel_final)
-    const int j = (fjob ? b - nbG : b) * 64 + lane;
-    if (j >= (fjob ? cntF : cntG)) return;
-    const int tile = fjob ? fbase + j : j;
-    const int2 js = out.job_slot[tile];
-    const int slot = js.x;
-    {
-        // longest profile of the launch (k_vel_final skips row chunks beyond it): one atomic per wave
-        int nmax = js.y;
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) { const int o = __shfl_xor(nmax, m); nmax = o > nmax ? o : nmax; }   // (lanes beyond the job count have left: no DPP form here)
-        if (lane == 0) atomicMax(&out.job_cnt[2], nmax);
-    }
-    const int s = slot / LTPL_MAX_ACTIONS;
-    const int n = js.y;
-    LaneProf L; L.KE = vp.KE + kep_base(tile, vp.plane_rows);
-    double* P0 = vp.P0 + tile_base(tile, vp.cap_pts);
-    double* P2 = vp.P2 + tile_base(fjob ? j : 0, vp.cap_pts);
-    double* P3 = vp.P3 + tile_base(fjob ? j : 0, vp.cap_pts);
-    const double vel_plan = vin.vel_plan[s];
-    const int name = out.action_id[slot], reduced = out.reduced[slot];
-    int flags = VF_BOUND_FOLLOW;
-
-    if (name == LTPL_ACT_FOLLOW) {                                                       // OTH.py:763-830
-        // calc_vel_profile_follow.py:78-294 for this lane
-        const LaneFollowOut fo = lane_follow_controlled<EM, AXM1>(lat, L, P2, P3, n, cax, cay, p, axm_tab, vel_plan, vin.vel_est[s], prep.v_obj[slot],
-                                                                  prep.obj_dist[slot], vin.safety_d, prep.idx_s_opp[slot], dbg, drow);
-        if (fo.too_close) flags |= VF_TOO_CLOSE;
-        int vel_bound = fo.vel_bound;
-        const bool two_seg = fo.two_seg != 0; const int n_decel = fo.n_decel, stop_idx = fo.stop_idx;
-        // "vx_profile" (:289 / :294) = brake profile in front, segment profile up to the stop index, zeros behind. Normally only
-        // described (two indices) and composed by the row-parallel final kernel; a reduced-horizon follow job needs P3 for its
-        // generic profile, so there the composition is materialised in P0 here.
-        if (!reduced) { vp.fseg[2 * j] = two_seg ? n_decel : -1; vp.fseg[2 * j + 1] = stop_idx; flags |= VF_COMPOSE; }
-        else for (int base = 0; base < n; base += LCH) {
-            double a[LCH];
-#pragma unroll
-            for (int c = 0; c < LCH; ++c) {
-                const int i = base + c < n ? base + c : n - 1;
-                const bool from_b = !two_seg || i < n_decel - 1;
-                a[c] = from_b ? P2[(size_t)i * 64] : ((i > stop_idx) ? 0.0 : P3[(size_t)i * 64]);
-            }
-#pragma unroll
-            for (int c = 0; c < LCH; ++c) if (base + c < n) P0[(size_t)(base + c) * 64] = a[c];
-        }
-        vl_stamp(dbg, drow, 5);
-        if (!vel_bound) flags &= ~VF_BOUND_FOLLOW;
-        if (reduced) {                                                                   // OTH.py:834-923 on top of follow
-            flags |= VF_HAS_GENERIC;
-            if (lane_generic_profile<EM, AXM1>(lat, out, L, P3, slot, n, reduced, cax, cay, p, axm_tab, vel_plan, vin.v_max_offset))
-                flags |= VF_BOUND_GENERIC;
-        }
-    } else {
-        if (lane_generic_profile<EM, AXM1>(lat, out, L, P0, slot, n, reduced, cax, cay, p, axm_tab, vel_plan, vin.v_max_offset))
-            flags |= VF_BOUND_GENERIC;
-    }
-    vp.flags[tile] = flags;
-    vl_stamp(dbg, drow, 6);
-}
-
-// final step of the batch velocity stage, no recurrence: intersection of the two follow profiles
-// (calc_vel_profile_follow.py:310), choice between follow and generic profile for reduced horizons (OTH.py:923, row 5),
-// vx = sqrt(w), ax from neighbouring points with -5 at standstill (OTH.py:925-941). Rows are independent of each other
-// (ax_i only needs w_i, w_i+1 and the element length e_i), so the work is spread over (tile of 64 jobs, chunk of FCH rows).
-// Two lane mappings in one wave: the planes are tiled by job, so they are READ with lane = job (one coalesced 512-byte line per
-// row); the outputs are rows of a slot, so they are WRITTEN with lane = (job, pair of rows) after a transposition through LDS: one
-// store instruction covers 8 jobs x 128 contiguous bytes instead of 64 jobs x 16 bytes on 64 different lines (round 2: 122 us ->
-// see DESIGN.md section 6; the stores of the lane = job form kept the address units busy, not HBM).
-#define FCH 16
-#define FPITCH (FCH + 2)           // doubles per job row in LDS (16-byte aligned pairs, odd multiple of 16 bytes: conflict-free b128 access)
-__global__ __launch_bounds__(64) void k_vel_final(DevPathsOut out, DevTickVelIn vin, DevTickVelOut vout, VelPlanes vp, int n_slots,
-                                                  int n_scen, int first_block)
-{
-    LTPL_VEL_SETPRIO();
-    __shared__ __align__(16) double tbuf[32 * FPITCH];     // 32 jobs at a time: 4.5 KB, so that many blocks fit next to a resident path kernel
-    __shared__ int s_slot[64], s_n[64];
-    // blocks [0, nbG): generic jobs, [nbG, nbG + nbF): follow jobs; slots without a path were initialised by the path kernel
-    // (round 5: launched for the follow tiles only -- first_block = nbG; the generic jobs' outputs come from the lane kernel's backward sweep)
-    const int nbG = (n_slots + 63) / 64;
-    const int bx = (int)blockIdx.x + first_block;
-    const bool fjob = bx >= nbG;
-    const int lane = threadIdx.x;
-    const int j = (fjob ? bx - nbG : bx) * 64 + lane;
-    const int cnt = out.job_cnt[fjob ? 1 : 0];
-    if ((j - lane) >= cnt) return;                                      // whole tile without jobs (uniform)
-    const bool have = j < cnt;
-    const int tile = fjob ? out.n_slots_pad + j : j;
-    const int nmax_all = out.job_cnt[2];                                // longest profile of the launch (lane kernel)
-    const int2 js = have ? out.job_slot[tile] : make_int2(0, 0);
-    const int slot = js.x;
-    // (round 6: a follow job of a batch is finished by the lane kernel -- VF_DONE -- unless its horizon is reduced; such a job counts zero rows here,
-    //  and a tile without anything left leaves at once)
-    const int tflags = have ? vp.flags[tile] : VF_DONE;
-    const int n = (tflags & VF_DONE) ? 0 : js.y;
-    if (__ballot(n > 0) == 0ull) return;
-    s_slot[lane] = slot; s_n[lane] = n;
-    // blockIdx.y strides over the row chunks: a few long-lived blocks per tile instead of one block per (tile, chunk), most of
-    // which used to find nothing to do
-    for (int base = (int)blockIdx.y * FCH; base < nmax_all; base += (int)gridDim.y * FCH) {
-    const bool act = have && base < n;
-    if (__ballot(act) == 0ull) continue;                                // uniform
-    double vv[FCH], aa[FCH];
-    if (act) {
-        const int flags = tflags;
-        const bool follow = fjob;
-        const double* P0 = vp.P0 + tile_base(tile, vp.cap_pts);
-        const double* P1 = vp.P1 + tile_base(fjob ? j : 0, vp.cap_pts);
-        const double* P2 = vp.P2 + tile_base(fjob ? j : 0, vp.cap_pts);
-        const double* P3 = vp.P3 + tile_base(fjob ? j : 0, vp.cap_pts);
-        const ke_t* KE = vp.KE + kep_base(tile, vp.plane_rows);
-        const bool compose = follow && (flags & VF_COMPOSE);
-        const int nd = compose ? vp.fseg[2 * j] : 0, stop_idx = compose ? vp.fseg[2 * j + 1] : 0;
-        int vel_bound = follow ? ((flags & VF_BOUND_FOLLOW) ? 1 : 0) : ((flags & VF_BOUND_GENERIC) ? 1 : 0);
-        int sel = follow ? 1 : 0;                     // 0: P0, 1: min(P0, P1), 2: P3
-        if (follow && (flags & VF_HAS_GENERIC)) {
-            vel_bound = (flags & VF_BOUND_GENERIC) ? 1 : 0;
-            sel = 2;
-            if (n >= 6) {
-                const double f5 = fmin(P0[5 * 64], P1[5 * 64]);
-                if (sqrt(f5) < sqrt(P3[5 * 64])) sel = 1;
-            }
-        }
-        auto value = [&](int i) {
-            const size_t o = (size_t)i * 64;
-            if (compose) {                                     // sel == 1: min("vx_profile", unconstrained profile)
-                const double a = (nd < 0 || i < nd - 1) ? P2[o] : (i > stop_idx ? 0.0 : P3[o]);
-                return fmin(a, P1[o]);
-            }
-            return sel == 0 ? P0[o] : (sel == 1 ? fmin(P0[o], P1[o]) : P3[o]);
-        };
-        double w[FCH + 1], er[FCH];
-#pragma unroll
-        for (int c = 0; c <= FCH; ++c) w[c] = value(base + c < n ? base + c : n - 1);
-        // element lengths: two rows per 16-byte load (rows 2m, 2m + 1 are adjacent in the blocked plane and `base` is a multiple of 16;
-        // rows beyond n - 1 are unused padding of the block -- never NaN-sensitive: their ax is discarded)
-#pragma unroll
-        for (int c = 0; c < FCH; c += 2) {
-#ifndef LTPL_VEL_F32_OPERANDS
-            er[c] = KE[kep_row(base + c)].y; er[c + 1] = KE[kep_row(base + c + 1)].y;
-#else
-            static_assert(KE_RB >= 2, "pairs of rows in one load");
-            const float4 v = *reinterpret_cast<const float4*>(&KE[kep_row(base + c)]);
-            er[c] = (double)v.y; er[c + 1] = (double)v.w;
-#endif
-        }
-#pragma unroll
-        for (int c = 0; c < FCH; ++c) {
-            const int i = base + c;
-            const double v = sqrt(w[c]);
-            double a = 0.0;
-            if (i < n - 1) {
-                // the reference divides by 2 (s_i+1 - s_i) with s the running sum of the element lengths; e_i differs from that
-                // difference by rounding only (~1e-13 relative, tolerance of ax: 1e-5)
-                a = (w[c + 1] - w[c]) / (2.0 * er[c]);
-                if (fabs(v) <= 1e-8 && fabs(a) <= 1e-8) a = -5.0;
-            }
-            vv[c] = v; aa[c] = a;
-        }
-        if (base == 0) { vout.vel_bound[slot] = vel_bound; vout.too_close[slot] = (flags & VF_TOO_CLOSE) ? 1 : 0; }
-    } else {
-#pragma unroll
-        for (int c = 0; c < FCH; ++c) { vv[c] = 0.0; aa[c] = 0.0; }
-    }
-    // transposition: lane = job writes its FCH values as one LDS row; lane = (job q of a group of 8, pair of rows) reads 16 bytes
-    // and stores them to the slot's row (8-byte aligned 16-byte stores; rows of a slot are contiguous)
-    const int q = lane >> 3, piece = lane & 7;
-#pragma unroll
-    for (int pass = 0; pass < 4; ++pass) {
-        const int half = pass & 1;                                      // jobs [32 half, 32 half + 32)
-        double* dst_base = pass < 2 ? vout.vx : vout.ax;
-        if ((lane >> 5) == half) {
-#pragma unroll
-            for (int c = 0; c < FCH; c += 2) store2(&tbuf[(lane & 31) * FPITCH + c], pass < 2 ? vv[c] : aa[c], pass < 2 ? vv[c + 1] : aa[c + 1]);
-        }
-        wave_sync_lds();
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int jl = k * 8 + q, jj = half * 32 + jl;
-            const int nn = s_n[jj], i = base + 2 * piece;
-            if (i >= nn) continue;
-            const dbl2 v = *reinterpret_cast<const dbl2*>(&tbuf[jl * FPITCH + 2 * piece]);
-            double* o = dst_base + (size_t)s_slot[jj] * out.cap_pts + i;
-            if (i + 1 < nn) store2_u(o, v.x, v.y); else o[0] = v.x;
-        }
-        wave_sync_lds();
-    }
-    }
-}
-
-// follow preparation (projection of the object and of the ego position on the path, OTH.py:774-784; projection of the object
-// on the global race line, calc_vel_profile_follow.py:172-176), ONE LANE PER FOLLOW JOB like the lane kernel. Round 2 history: the
-// wave-per-job form spent ~1 900 instructions per job on cross-lane reductions and half-empty lanes (47 M instructions per
-// 32 768-scenario step, 8 % of the path kernel's -- 118 us of the overlapped step); a lane that scans its own job serially needs
-// ~190: the race line is read with scalar loads (uniform index), the path points come from a tiled (x, y) plane the path kernel
-// writes for follow jobs (coalesced rows), closest point, arc length at the foot point (a running prefix: np.cumsum's order) and
-// the element in front of it are picked up in ONE pass for both query points.
-#define PCH 8
-__global__ __launch_bounds__(64) void k_follow_prep(DevLat lat, DevPathsIn in, DevPathsOut out, DevTickVelIn vin,
-                                                    DevVelPrep prep, VelPlanes vp, int n_slots, long long* dbg)
-{
-    LTPL_VEL_SETPRIO();
-    const int lane = threadIdx.x, cnt = out.job_cnt[1];
-    if ((int)blockIdx.x * 64 >= cnt) return;
-    const int drow = blockIdx.x < 64 ? 192 + (int)blockIdx.x : -1;      // LTPL_DEBUG_TIMING: rows 192 .. 255 of the stamp table
-    vl_stamp(dbg, drow, 0);
-    const int j0 = (int)blockIdx.x * 64 + lane;
-    const bool have_job = j0 < cnt;
-    const int j = have_job ? j0 : cnt - 1;                  // idle lanes repeat the last job (uniform control flow), nothing stored
-    const int2 js = out.job_slot[out.n_slots_pad + j];
-    const int slot = js.x, s = slot / LTPL_MAX_ACTIONS, n = js.y;
-    const int ci = out.closest_obj_index[s], v0 = in.veh_off[s];
-    const bool have = !(ci < 0 || ci >= in.veh_off[s + 1] - v0);
-    const double ex = vin.pos_est_x[s], ey = vin.pos_est_y[s];
-    double ox = ex, oy = ey, vobj = 0.0, odist = 0.0;
-    if (have) { const int q = in.pos_off[v0 + ci]; ox = in.pos_x[q]; oy = in.pos_y[q]; vobj = vin.veh_vel[v0 + ci]; }
-    vl_stamp(dbg, drow, 1);
-    const int idx = lane_globrl_index(lat, ox, oy);
-    vl_stamp(dbg, drow, 2);
-    if (__ballot(have) != 0ull) {
-        const double* xy = vp.XY + 2 * kep_base(j, vp.plane_rows);         // pairs: row r of this lane's job at xy + 2 * kep_row(r)
-        const ke_t* KE = vp.KE + kep_base(out.n_slots_pad + j, vp.plane_rows);
-        int nmax = n;
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) { const int o = __shfl_xor(nmax, m); nmax = o > nmax ? o : nmax; }   // (lanes beyond the job count have left: no DPP form here)
-        // one pass: closest path point of the object (o) and of the ego position (e), arc length in front of it and the element before
-        double bo = INFINITY, be = INFINITY, so = 0.0, se = 0.0, po = 0.0, pe = 0.0, run = 0.0, e_prev = 0.0;
-        int no = 0, ne = 0;
-        dbl2 pr[PCH], pn[PCH]; ke_t kr[PCH], kn[PCH];
-        auto load_rows = [&](int base, dbl2 (&p)[PCH], ke_t (&k)[PCH]) {
-#pragma unroll
-            for (int c = 0; c < PCH; ++c) {
-                const int r = base + c < n ? base + c : n - 1;
-                p[c] = *reinterpret_cast<const dbl2*>(xy + 2 * kep_row(r)); k[c] = KE[kep_row(r)];
-            }
-        };
-        load_rows(0, pr, kr);
-        for (int base = 0; base < nmax; base += PCH) {
-            load_rows(base + PCH, pn, kn);
-#pragma unroll
-            for (int c = 0; c < PCH; ++c) {
-                const int i = base + c;
-                const bool valid = i < n;
-                const double x = pr[c].x, y = pr[c].y, e = (double)kr[c].y;
-                const double ao = (x - ox) * (x - ox) + (y - oy) * (y - oy), ae = (x - ex) * (x - ex) + (y - ey) * (y - ey);
-                if (valid && ao < bo) { bo = ao; no = i; so = run; po = e_prev; }
-                if (valid && ae < be) { be = ae; ne = i; se = run; pe = e_prev; }
-                if (valid) { run += e; e_prev = e; }
-            }
-#pragma unroll
-            for (int c = 0; c < PCH; ++c) { pr[c] = pn[c]; kr[c] = kn[c]; }
-        }
-        vl_stamp(dbg, drow, 3);
-        // get_s_coord.py:34-99 (closed = False) for one query: arc length of the foot point
-        auto foot = [&](int nb, double s_nb, double e_before, double px, double py) {
-            const int i1 = nb - 1 > 0 ? nb - 1 : 0, i2 = nb + 1 < n - 1 ? nb + 1 : n - 1;
-            const dbl2 pN = *reinterpret_cast<const dbl2*>(xy + 2 * kep_row(nb)), p1 = *reinterpret_cast<const dbl2*>(xy + 2 * kep_row(i1)),
-                       p2 = *reinterpret_cast<const dbl2*>(xy + 2 * kep_row(i2));
-            const int ord = angle_order_dev(pN.x, pN.y, px, py, p1.x, p1.y, p2.x, p2.y, i1 == nb, i2 == nb);
-            double ax, ay, bx, by;
-            if (ord > 0) { ax = p1.x; ay = p1.y; bx = pN.x; by = pN.y; } else { ax = pN.x; ay = pN.y; bx = p2.x; by = p2.y; }
-            const double t = ((px - ax) * (bx - ax) + (py - ay) * (by - ay)) / ((bx - ax) * (bx - ax) + (by - ay) * (by - ay));
-            const double fx = ax + t * (bx - ax), fy = ay + t * (by - ay);
-            const double ds = sqrt((ax - fx) * (ax - fx) + (ay - fy) * (ay - fy));
-            return (ord > 0 ? (nb > 0 ? s_nb - e_before : 0.0) : s_nb) + ds;        // s[i1] = s[nb] - el[nb - 1]; s[0] = 0
-        };
-        const double s_obj = foot(no, so, po, ox, oy), s_sta = foot(ne, se, pe, ex, ey);
-        if (have) odist = s_obj - s_sta;
-        vl_stamp(dbg, drow, 4);
-    }
-    if (have_job) { prep.obj_dist[slot] = odist; prep.v_obj[slot] = vobj; prep.obj_x[slot] = ox; prep.obj_y[slot] = oy; prep.idx_s_opp[slot] = idx; }
-    vl_stamp(dbg, drow, 5);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// compact trajectory export (ltpl_tick_batch_compact): rows [s, x, y, psi, kappa, vx, ax] of the valid slots, back to back
-// ---------------------------------------------------------------------------------------------------------------------
-// rows kept per slot and their exclusive prefix (one block; n_slots <= a few hundred thousand)
-__global__ __launch_bounds__(1024) void k_compact_offsets(const int* valid, const int* n_pts, int n_slots, int max_rows,
-                                                          int* rows_out, long long* off_out, long long* total)
-{
-    __shared__ long long part[1024];
-    const int t = threadIdx.x, per = (n_slots + 1023) / 1024;
-    const int a = t * per, b = a + per < n_slots ? a + per : n_slots;
-    long long sum = 0;
-    for (int i = a; i < b; ++i) {
-        int r = valid[i] ? n_pts[i] : 0;
-        if (max_rows > 0 && r > max_rows) r = max_rows;
-        rows_out[i] = r; sum += r;
-    }
-    part[t] = sum;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const long long v = t >= d ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    long long run = part[t] - sum;
-    for (int i = a; i < b; ++i) { off_out[i] = run; run += rows_out[i]; }
-    if (t == 1023) *total = part[1023];
-}
-
-// one wave per slot: s = [0, cumsum(el[:-1])] (OTH.py:743, wave-parallel prefix), then the seven columns of every kept row
-__global__ __launch_bounds__(64) void k_compact_rows(DevPathsOut out, DevTickVelOut vout, const int* rows_kept, const long long* off,
-                                                     double* dst, long long capacity_rows)
-{
-    const int slot = blockIdx.x, lane = threadIdx.x;
-    const int n = rows_kept[slot];
-    if (n <= 0) return;
-    const long long o = off[slot];
-    if (o + n > capacity_rows) return;
-    const double* pp = out.path_param + (size_t)slot * out.cap_pts * 5;
-    const double* vx = vout.vx + (size_t)slot * out.cap_pts;
-    const double* ax = vout.ax + (size_t)slot * out.cap_pts;
-    double carry = 0.0;
-    for (int base = 0; base < n; base += 64) {
-        const int i = base + lane;
-        const double e = (i < n) ? pp[(size_t)i * 5 + 4] : 0.0;
-        double x = e;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const double y = __shfl_up(x, d); if (lane >= d) x += y; }
-        if (i < n) {
-            double* r = dst + (size_t)(o + i) * 7;
-            r[0] = carry + (x - e);
-            r[1] = pp[(size_t)i * 5]; r[2] = pp[(size_t)i * 5 + 1]; r[3] = pp[(size_t)i * 5 + 2]; r[4] = pp[(size_t)i * 5 + 3];
-            r[5] = vx[i]; r[6] = ax[i];
-        }
-        carry += __shfl(x, 63);
-    }
-}
+#include "vel_lanes.hpp"
 
 // ---------------------------------------------------------------------------------------------------------------------
 // object ingestion: ObjectListInterface.process_object_list (ObjectListInterface.py:75-153)
@@ -2806,16 +745,9 @@ static int upload(ltpl_handle* h, const T* src, size_t n, const T** dst)
     return LTPL_OK;
 }
 
-static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-// LDS of one workgroup of the fused tick kernel (k_tick, k_tick_persistent): the four-wave path plan, then the velocity scratch of the three
-// primitives (cap = max_path_pts rows each) and a byte row. ltpl_create routes every tick of a lattice whose footprint is above the budget
-// to the pipeline; tick_prepare launches the fused kernel with exactly this much.
+// LDS of one workgroup of the fused tick kernel (k_tick, k_tick_persistent): fused_tick_lds (vel_layout.hpp), cap = max_path_pts rows. ltpl_create
+// routes every tick of a lattice whose footprint is above this budget to the pipeline; tick_prepare launches the fused kernel with exactly that much.
 static const size_t FUSED_TICK_LDS_BUDGET = 150 * 1024;
-static size_t fused_tick_lds(int lp4_total, int cap)
-{
-    return (size_t)lp4_total + vel_scratch_bytes(cap, false, true) * LTPL_MAX_ACTIONS + align_up((size_t)cap + 16, 16);
-}
 
 // planning-range statistics over all start layers (sizes the LDS plan and the output capacities)
 static int horizon_stats(const ltpl_lattice_desc* d, int* hmax, int* ehmax, int* nhmax, int* ptsmax, int* kmax,
@@ -3265,6 +1197,7 @@ struct Arena {
     size_t size = 0;
     size_t add(size_t bytes) { size_t o = size; size = align_up(size + bytes, 256); return o; }   // arrays start on cache-line multiples
 };
+template <class T> static void bind_at(T*& p, unsigned char* base, size_t off) { p = reinterpret_cast<T*>(base + off); }      // p = the array `off` bytes behind base
 
 // The device-resident batch of ltpl_batch_upload points into the staging buffers (d_in / d_out / d_planes). Every other
 // entry point reuses (and may reallocate) them, so it drops the resident batch first: a later ltpl_batch_run / _download then
@@ -3278,6 +1211,19 @@ static void drop_resident(ltpl_handle* h, bool keep_persistent_tick = false)
     for (int i = 0; i < ltpl_handle::PIPE_SETS - 1; ++i) { free_resident(h->resident_x[i]); h->resident_x[i] = nullptr; }
 }
 
+// grow-only device buffer: when `need` exceeds its capacity it is freed and allocated anew with `alloc` bytes (default: exactly `need`); the
+// contents are not kept. After a failed allocation the buffer is empty (null, capacity 0).
+static int grow_device(ltpl_handle* h, void** p, size_t* cap, size_t need, size_t alloc = 0)
+{
+    if (need <= *cap) return LTPL_OK;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr; *cap = 0;
+    HIP_TRY(h, hipMalloc(p, alloc ? alloc : need));
+    *cap = alloc ? alloc : need;
+    return LTPL_OK;
+}
+
+// the staging pair of an entry point: page-locked host buffer + device buffer, both grown by half more than needed
 static int ensure(ltpl_handle* h, void** hp, size_t* hcap, void** dp, size_t* dcap, size_t need)
 {
     if (need > *hcap) {
@@ -3287,12 +1233,19 @@ static int ensure(ltpl_handle* h, void** hp, size_t* hcap, void** dp, size_t* dc
         HIP_TRY(h, hipHostMalloc(hp, cap, hipHostMallocDefault));
         *hcap = cap;
     }
-    if (need > *dcap) {
-        if (*dp) (void)hipFree(*dp);
-        *dp = nullptr; *dcap = 0;
-        size_t cap = align_up(need + need / 2, 4096);
-        HIP_TRY(h, hipMalloc(dp, cap));
-        *dcap = cap;
+    return grow_device(h, dp, dcap, need, align_up(need + need / 2, 4096));
+}
+
+// The dynamic-LDS limit of a kernel is process-wide state per device: raised when a launch needs more than the default 48 KiB and more than
+// the last value set, never lowered, not re-set per call. `slot`: the kernel's place in the table = LDS_SLOT_* + its velocity variant.
+enum { LDS_SLOT_VEL = 0, LDS_SLOT_TICK = 8, LDS_SLOT_TICK_A = 16, LDS_SLOT_PTICK = 24, LDS_SLOTS = 32 };
+static int raise_lds_limit(ltpl_handle* h, const void* func, size_t lds, int slot)
+{
+    static std::atomic<size_t> g_set[16][LDS_SLOTS];
+    std::atomic<size_t>* cur = (unsigned)h->device < 16u ? &g_set[h->device][slot] : nullptr;      // (a device beyond the table: set every time)
+    if (lds > 48 * 1024 && (!cur || lds > cur->load(std::memory_order_relaxed))) {
+        HIP_TRY(h, hipFuncSetAttribute(func, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (cur) *cur = lds;
     }
     return LTPL_OK;
 }
@@ -3629,52 +1582,23 @@ typedef void (*lanes_kernel_t)(DevLat, DevPathsIn, DevPathsOut, DevVelParams, De
 #ifndef LTPL_EMIT_MIN_SCEN
 #define LTPL_EMIT_MIN_SCEN 256        // launches with at least this many scenarios write the generic jobs' vx / ax from the lane kernel (k_vel_lanes)
 #endif
-static lanes_kernel_t lanes_kernel_of(int v)
-{
-    switch (v) {
-        case 0: return k_vel_lanes<0, false>; case 1: return k_vel_lanes<0, true>;
-        case 2: return k_vel_lanes<1, false>; case 3: return k_vel_lanes<1, true>;
-        case 4: return k_vel_lanes<2, false>; default: return k_vel_lanes<2, true>;
-    }
-}
-static vel_kernel_t vel_kernel_of(int v)
-{
-    switch (v) {
-        case 0: return k_vel_profile<0, false>; case 1: return k_vel_profile<0, true>;
-        case 2: return k_vel_profile<1, false>; case 3: return k_vel_profile<1, true>;
-        case 4: return k_vel_profile<2, false>; default: return k_vel_profile<2, true>;
-    }
-}
+// (one line per kernel family; the six (EM, AXM1) cases: with_vel_variant, vel_layout.hpp)
+static lanes_kernel_t lanes_kernel_of(int v) { return with_vel_variant(v, [](auto em, auto axm1) -> lanes_kernel_t { return k_vel_lanes<em.value, axm1.value>; }); }
+static vel_kernel_t vel_kernel_of(int v) { return with_vel_variant(v, [](auto em, auto axm1) -> vel_kernel_t { return k_vel_profile<em.value, axm1.value>; }); }
 template <int SEL>
 static vel_kernel_t vel_kernel_const_of(int v)          // constant friction limits per job (fleet); SEL: see k_vel_profile
 {
-    switch (v) {
-        case 0: return k_vel_profile<0, false, false, SEL>; case 1: return k_vel_profile<0, true, false, SEL>;
-        case 2: return k_vel_profile<1, false, false, SEL>; case 3: return k_vel_profile<1, true, false, SEL>;
-        case 4: return k_vel_profile<2, false, false, SEL>; default: return k_vel_profile<2, true, false, SEL>;
-    }
+    return with_vel_variant(v, [](auto em, auto axm1) -> vel_kernel_t { return k_vel_profile<em.value, axm1.value, false, SEL>; });
 }
 template <int SEL>
 static vel_kernel_t vel_kernel_rows_of(int v)           // friction limits as rows per job (fleet, local_gg as a dict): the interpolating machine-table form only
 {
-    switch (v >> 1) {
-        case 0: return k_vel_profile<0, false, true, SEL>; case 1: return k_vel_profile<1, false, true, SEL>;
-        default: return k_vel_profile<2, false, true, SEL>;
-    }
+    return with_vel_variant(v, [](auto em, auto) -> vel_kernel_t { return k_vel_profile<em.value, false, true, SEL>; });
 }
 static tick_kernel_t tick_kernel_of(int v, bool plan_a = false)
 {
-    if (plan_a)
-        switch (v) {
-            case 0: return k_tick<0, false, PlanA4>; case 1: return k_tick<0, true, PlanA4>;
-            case 2: return k_tick<1, false, PlanA4>; case 3: return k_tick<1, true, PlanA4>;
-            case 4: return k_tick<2, false, PlanA4>; default: return k_tick<2, true, PlanA4>;
-        }
-    switch (v) {
-        case 0: return k_tick<0, false, PlanRt>; case 1: return k_tick<0, true, PlanRt>;
-        case 2: return k_tick<1, false, PlanRt>; case 3: return k_tick<1, true, PlanRt>;
-        case 4: return k_tick<2, false, PlanRt>; default: return k_tick<2, true, PlanRt>;
-    }
+    if (plan_a) return with_vel_variant(v, [](auto em, auto axm1) -> tick_kernel_t { return k_tick<em.value, axm1.value, PlanA4>; });
+    return with_vel_variant(v, [](auto em, auto axm1) -> tick_kernel_t { return k_tick<em.value, axm1.value, PlanRt>; });
 }
 
 static int make_vel_params(ltpl_handle* h, const ltpl_vel_params* vp, const double* d_axm, DevVelParams* p)
@@ -3744,15 +1668,7 @@ try {
         memcpy(pool + d.off_gg, jb.loc_gg, sizeof(double) * 2 * (size_t)jb.n);
     }
     vel_kernel_t kern = vel_kernel_of(vel_variant(vp));
-    {
-        // the dynamic-LDS limit of a kernel is process-wide state: raised when a call needs more, never lowered, not re-set per tick
-        static std::atomic<size_t> g_set[16][8];
-        std::atomic<size_t>& cur = g_set[h->device & 15][vel_variant(vp) & 7];
-        if (lds > 48 * 1024 && lds > cur.load(std::memory_order_relaxed)) {
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            cur = lds;
-        }
-    }
+    if ((rc = raise_lds_limit(h, reinterpret_cast<const void*>(kern), lds, LDS_SLOT_VEL + vel_variant(vp)))) return rc;
     prof_pack.stop();
     LTPL_PROF(prof_enq, "vel_profile.enqueue");
     if (!zci) HIP_TRY(h, hipMemcpyAsync(h->d_in, h->h_in, ain.size, hipMemcpyHostToDevice, h->stream));
@@ -3783,659 +1699,7 @@ try {
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(h))
 
-// ---- fused tick ------------------------------------------------------------------------------------------------------
-struct TickLayout {
-    InLayout in; size_t axm, vel_plan, vel_est, pos_x, pos_y, veh_vel, in_total;
-    OutLayout out; size_t vx, ax, vel_bound, too_close, out_total;
-    int n_scen, cap_nodes, cap_pts;
-    DevPathsIn di; DevPathsOut dout; DevVelParams p; DevTickVelIn dvin; DevTickVelOut dvout;
-    int vel_off, vel_stride, vel_cap; size_t lds;
-    int variant;
-    // two-kernel batch pipeline (n_scen >= pipeline_min_scen)
-    bool pipeline; size_t prep_odist, prep_vobj, prep_ox, prep_oy, prep_idx; size_t planes_bytes;
-    DevVelPrep dprep; int prep_off, prep_stride;
-    VelPlanes vp{}; int n_slots_pad = 0, n_scen_pad = 0;
-};
-
-static int tick_prepare(ltpl_handle* h, const ltpl_paths_in* in, const ltpl_tick_vel_in* vin, int cap_nodes, int cap_pts,
-                        TickLayout* t)
-{
-    int rc = validate_and_layout(h, in, &t->in);
-    if (rc) return rc;
-    if (!vin || !vin->params) { h->err = "velocity inputs missing"; return LTPL_ERR_INVALID_ARG; }
-    if (cap_nodes < h->caps.max_path_nodes || cap_pts < h->caps.max_path_pts) { h->err = "output capacity too small"; return LTPL_ERR_CAPACITY; }
-    const int n = in->n_scen;
-    for (int s = 0; s < n; ++s)
-        if (vin->vel_plan[s] > vin->params->v_max + 0.1) {
-            h->err = "vel_plan > v_max + 0.1: the brake-prefix branch is not part of the fused tick (the reference raises at OTH.py:919)";
-            return LTPL_ERR_UNSUPPORTED;
-        }
-    t->n_scen = n; t->cap_nodes = cap_nodes; t->cap_pts = cap_pts;
-    t->variant = vel_variant(vin->params);
-    Arena a; a.size = t->in.total;
-    t->axm = a.add(sizeof(double) * 2 * (size_t)vin->params->n_ax_max_machines);
-    t->vel_plan = a.add(sizeof(double) * (size_t)n); t->vel_est = a.add(sizeof(double) * (size_t)n);
-    t->pos_x = a.add(sizeof(double) * (size_t)n); t->pos_y = a.add(sizeof(double) * (size_t)n);
-    t->veh_vel = a.add(sizeof(double) * (size_t)(t->in.n_veh + 1));
-    t->in_total = a.size;
-    layout_out(n, cap_nodes, cap_pts, &t->out);
-    Arena b; b.size = t->out.total;
-    t->vx = b.add(sizeof(double) * (size_t)n * LTPL_MAX_ACTIONS * (size_t)cap_pts);
-    t->ax = b.add(sizeof(double) * (size_t)n * LTPL_MAX_ACTIONS * (size_t)cap_pts);
-    t->vel_bound = b.add(sizeof(int) * (size_t)n * LTPL_MAX_ACTIONS);
-    t->too_close = b.add(sizeof(int) * (size_t)n * LTPL_MAX_ACTIONS);
-    t->pipeline = h->long_horizon || (!h->force_fused && (!h->fused_fits || n >= h->pipeline_min_scen));
-    t->prep_odist = b.add(sizeof(double) * (size_t)n * LTPL_MAX_ACTIONS);
-    t->prep_vobj = b.add(sizeof(double) * (size_t)n * LTPL_MAX_ACTIONS);
-    t->prep_ox = b.add(sizeof(double) * (size_t)n * LTPL_MAX_ACTIONS);
-    t->prep_oy = b.add(sizeof(double) * (size_t)n * LTPL_MAX_ACTIONS);
-    t->prep_idx = b.add(sizeof(int) * (size_t)n * LTPL_MAX_ACTIONS);
-    t->out_total = b.size;
-    t->n_slots_pad = (int)align_up((size_t)n * LTPL_MAX_ACTIONS, 64); t->n_scen_pad = (int)align_up((size_t)n, 64);
-    // tiled planes by job: K, E, P0 for generic + follow jobs, P1, P2, P3 for follow jobs; flags, job table and counters behind
-    {
-        const size_t tiles = (size_t)t->n_slots_pad + (size_t)t->n_scen_pad;
-        const size_t plane_rows = align_up((size_t)cap_pts, 8);
-        // (the operand plane holds plane_rows = cap_pts rounded up to 8 records of sizeof(ke_t) = 16 bytes per tile)
-        t->planes_bytes = t->pipeline ? sizeof(double) * (2 * plane_rows * tiles + (size_t)cap_pts * (tiles + 3 * (size_t)t->n_scen_pad) + 2 * plane_rows * (size_t)t->n_scen_pad)
-                                            + sizeof(int) * (3 * tiles + 16 + 2 * (size_t)t->n_scen_pad) : 0;
-    }
-    t->prep_off = 0; t->prep_stride = 0;
-    t->vel_cap = h->caps.max_path_pts;
-    t->vel_stride = (int)vel_scratch_bytes(t->vel_cap, false, true);
-    t->vel_off = h->lp4.total;
-    t->lds = fused_tick_lds(h->lp4.total, t->vel_cap);
-    if (!t->pipeline && t->lds > FUSED_TICK_LDS_BUDGET) { h->err = "fused tick exceeds the LDS budget"; return LTPL_ERR_CAPACITY; }   // (LTPL_FORCE_FUSED)
-    return LTPL_OK;
-}
-
-// device-side output pointers of a tick layout for one buffer set (output slab + tiled planes)
-static void tick_bind_outputs(TickLayout* t, unsigned char* dob, double* planes)
-{
-    bind_out(dob, t->out, t->cap_nodes, t->cap_pts, &t->dout);
-    t->dvout.vx = reinterpret_cast<double*>(dob + t->vx); t->dvout.ax = reinterpret_cast<double*>(dob + t->ax);
-    t->dvout.vel_bound = reinterpret_cast<int*>(dob + t->vel_bound);
-    t->dvout.too_close = reinterpret_cast<int*>(dob + t->too_close);
-    t->dprep.obj_dist = reinterpret_cast<double*>(dob + t->prep_odist);
-    t->dprep.v_obj = reinterpret_cast<double*>(dob + t->prep_vobj);
-    t->dprep.obj_x = reinterpret_cast<double*>(dob + t->prep_ox);
-    t->dprep.obj_y = reinterpret_cast<double*>(dob + t->prep_oy);
-    t->dprep.idx_s_opp = reinterpret_cast<int*>(dob + t->prep_idx);
-    if (t->pipeline && planes) {
-        const size_t tiles = (size_t)t->n_slots_pad + (size_t)t->n_scen_pad;
-        const size_t per_all = (size_t)t->cap_pts * tiles, per_scen = (size_t)t->cap_pts * (size_t)t->n_scen_pad;
-        const size_t plane_rows = align_up((size_t)t->cap_pts, 8);
-        static_assert(sizeof(ke_t) <= 2 * sizeof(double), "operand plane: two doubles per row and tile");
-        t->vp.KE = reinterpret_cast<ke_t*>(planes); t->vp.P0 = planes + 2 * plane_rows * tiles;
-        t->vp.P1 = t->vp.P0 + per_all; t->vp.P2 = t->vp.P1 + per_scen; t->vp.P3 = t->vp.P2 + per_scen;
-        t->vp.XY = t->vp.P3 + per_scen;
-        int* ints = reinterpret_cast<int*>(t->vp.XY + 2 * plane_rows * (size_t)t->n_scen_pad);
-        t->vp.flags = ints; t->dout.job_slot = reinterpret_cast<int2*>(ints + tiles); t->dout.job_cnt = ints + 3 * tiles; t->vp.fseg = ints + 3 * tiles + 16;
-        t->dout.n_slots_pad = t->n_slots_pad;
-        t->vp.cap_pts = t->cap_pts; t->vp.plane_rows = (int)plane_rows;
-        t->dout.vke = t->vp.KE; t->dout.vxy = t->vp.XY;
-    }
-}
-
-static int tick_pack(ltpl_handle* h, const ltpl_paths_in* in, const ltpl_tick_vel_in* vin, TickLayout* t,
-                     unsigned char* hb, unsigned char* db, unsigned char* dob)
-{
-    pack_in(in, t->in, hb, db, &t->di, h->scen_order != 0);
-    const int n = in->n_scen;
-    memcpy(hb + t->axm, vin->params->ax_max_machines, sizeof(double) * 2 * (size_t)vin->params->n_ax_max_machines);
-    memcpy(hb + t->vel_plan, vin->vel_plan, sizeof(double) * (size_t)n);
-    memcpy(hb + t->vel_est, vin->vel_est, sizeof(double) * (size_t)n);
-    memcpy(hb + t->pos_x, vin->pos_est_x, sizeof(double) * (size_t)n);
-    memcpy(hb + t->pos_y, vin->pos_est_y, sizeof(double) * (size_t)n);
-    if (t->in.n_veh > 0) memcpy(hb + t->veh_vel, vin->veh_vel, sizeof(double) * (size_t)t->in.n_veh);
-    int rc = make_vel_params(h, vin->params, reinterpret_cast<const double*>(db + t->axm), &t->p);
-    if (rc) return rc;
-    t->dvin.gg_ax = vin->gg_ax; t->dvin.gg_ay = vin->gg_ay; t->dvin.safety_d = vin->safety_d;
-    t->dvin.v_max_offset = vin->v_max_offset;
-    t->dvin.vel_plan = reinterpret_cast<const double*>(db + t->vel_plan);
-    t->dvin.vel_est = reinterpret_cast<const double*>(db + t->vel_est);
-    t->dvin.pos_est_x = reinterpret_cast<const double*>(db + t->pos_x);
-    t->dvin.pos_est_y = reinterpret_cast<const double*>(db + t->pos_y);
-    t->dvin.veh_vel = reinterpret_cast<const double*>(db + t->veh_vel);
-    if (t->pipeline && t->planes_bytes > h->d_planes_cap) {
-        if (h->d_planes) (void)hipFree(h->d_planes);
-        h->d_planes = nullptr; h->d_planes_cap = 0;
-        HIP_TRY(h, hipMalloc(&h->d_planes, t->planes_bytes));
-        h->d_planes_cap = t->planes_bytes;
-    }
-    tick_bind_outputs(t, dob, static_cast<double*>(h->d_planes));
-    return LTPL_OK;
-}
-
-static int tick_launch_paths(ltpl_handle* h, const TickLayout& t, hipStream_t st)
-{
-    if (t.dout.job_cnt) HIP_TRY(h, hipMemsetAsync(t.dout.job_cnt, 0, 3 * sizeof(int), st));
-    return launch_paths(h, (t.n_scen >= h->nw1_min_scen && h->batch_nw == 1) ? 1 : NUM_WAVES, t.n_scen, st, t.di, t.dout);
-}
-
-static int tick_launch_vel(ltpl_handle* h, const TickLayout& t, hipStream_t st, hipEvent_t ev_after_prep = nullptr)
-{
-    // slots without a path: vel_bound = too_close = 0 (the job kernels only touch slots that own a job)
-    HIP_TRY(h, hipMemsetAsync(t.dvout.vel_bound, 0, sizeof(int) * (size_t)t.n_scen * LTPL_MAX_ACTIONS, st));
-    HIP_TRY(h, hipMemsetAsync(t.dvout.too_close, 0, sizeof(int) * (size_t)t.n_scen * LTPL_MAX_ACTIONS, st));
-#ifdef LTPL_EXPERIMENT
-    if (!(h->exp_skip & 1))
-#endif
-    hipLaunchKernelGGL(k_follow_prep, dim3((t.n_scen + 63) / 64), dim3(64), 0, st, h->lat, t.di, t.dout,
-                       t.dvin, t.dprep, t.vp, t.n_scen, h->lp4.dbg);
-    HIP_TRY(h, hipGetLastError());
-    if (ev_after_prep) HIP_TRY(h, hipEventRecord(ev_after_prep, st));
-    const int n_slots = t.n_scen * LTPL_MAX_ACTIONS;
-    const int nb0 = (n_slots + 63) / 64, nb1 = (t.n_scen + 63) / 64;
-    const int emit_generic = t.n_scen >= LTPL_EMIT_MIN_SCEN ? 1 : 0;
-    const int emit = emit_generic | ((emit_generic && t.n_scen >= h->follow_emit_min_scen) ? 2 : 0);
-#ifdef LTPL_EXPERIMENT
-    if (!(h->exp_skip & 2))
-#endif
-    hipLaunchKernelGGL(lanes_kernel_of(t.variant), dim3(nb0 + 2 * nb1), dim3(64), 0, st, h->lat, t.di, t.dout,
-                       t.p, t.dvin, t.dprep, t.vp, n_slots, t.n_scen, nb0, h->lp4.dbg, t.dvout, emit);
-    HIP_TRY(h, hipGetLastError());
-#ifdef LTPL_EXPERIMENT
-    if (!(h->exp_skip & 4))
-#endif
-    hipLaunchKernelGGL(k_vel_final, dim3(emit_generic ? nb1 : nb0 + nb1, h->final_y), dim3(64), 0, st, t.dout, t.dvin, t.dvout, t.vp, n_slots, t.n_scen,
-                       emit_generic ? nb0 : 0);
-    HIP_TRY(h, hipGetLastError());
-    return LTPL_OK;
-}
-
-static int tick_launch(ltpl_handle* h, const TickLayout& t, hipEvent_t* ev = nullptr)
-{
-    // ev (optional, 4 events): recorded before the path kernel, after it, after the follow preparation, after the lane kernels
-    if (ev) HIP_TRY(h, hipEventRecord(ev[0], h->stream));
-    if (t.pipeline) {
-        int rc = tick_launch_paths(h, t, h->stream);
-        if (rc) return rc;
-        if (ev) HIP_TRY(h, hipEventRecord(ev[1], h->stream));
-        if ((rc = tick_launch_vel(h, t, h->stream, ev ? ev[2] : nullptr))) return rc;
-        if (ev) HIP_TRY(h, hipEventRecord(ev[3], h->stream));
-        return LTPL_OK;
-    }
-    hipLaunchKernelGGL(tick_kernel_of(t.variant, h->plan_class4 == 1), dim3(t.n_scen), dim3(WG_THREADS), t.lds, h->stream, h->lat, t.di, t.dout, h->lp4, t.p,
-                       t.dvin, t.dvout, t.vel_off, t.vel_stride, t.vel_cap);
-    HIP_TRY(h, hipGetLastError());
-    if (ev) { HIP_TRY(h, hipEventRecord(ev[1], h->stream)); HIP_TRY(h, hipEventRecord(ev[2], h->stream)); HIP_TRY(h, hipEventRecord(ev[3], h->stream)); }
-    return LTPL_OK;
-}
-
-static void tick_scatter(const unsigned char* hb, const TickLayout& t, ltpl_paths_out* out, ltpl_tick_vel_out* vout)
-{
-    scatter_out(hb, t.out, t.n_scen, out);
-    const size_t A = LTPL_MAX_ACTIONS, n = (size_t)t.n_scen;
-    if (out->cap_pts == t.cap_pts) {
-        memcpy(vout->vx, hb + t.vx, sizeof(double) * n * A * (size_t)t.cap_pts);
-        memcpy(vout->ax, hb + t.ax, sizeof(double) * n * A * (size_t)t.cap_pts);
-    }
-    memcpy(vout->vel_bound, hb + t.vel_bound, sizeof(int) * n * A);
-    memcpy(vout->too_close, hb + t.too_close, sizeof(int) * n * A);
-}
-
-static int tick_set_lds_limit(ltpl_handle* h, size_t lds, int variant)
-{
-    if (!h->fused_fits) return LTPL_OK;                   // the fused kernel is not used
-    static std::atomic<size_t> g_set[16][8][2];           // (process-wide limit: raised on demand, never lowered, not re-set per tick)
-    std::atomic<size_t>& cur = g_set[h->device & 15][variant & 7][h->plan_class4 == 1 ? 1 : 0];
-    if (lds > 48 * 1024 && lds > cur.load(std::memory_order_relaxed)) {
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(tick_kernel_of(variant, h->plan_class4 == 1)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        cur = lds;
-    }
-    return LTPL_OK;
-}
-
-// The fused single tick as one hipGraph launch (LTPL_TICK_GRAPH=1): copy node (packed inputs, H2D) -> kernel node (k_tick) -> copy node
-// (outputs, D2H; absent with zero-copy outputs). Built once; every tick re-parameterises the nodes of the executable graph (sizes and the
-// pointers into the staging buffers follow the tick's counts) and launches it. A change of topology or kernel rebuilds the graph.
-static int tick_launch_graph(ltpl_handle* h, TickLayout& t, bool zc)
-{
-    const void* func = reinterpret_cast<const void*>(tick_kernel_of(t.variant, h->plan_class4 == 1));
-    int vel_off = t.vel_off, vel_stride = t.vel_stride, vel_cap = t.vel_cap;
-    void* kargs[] = {&h->lat, &t.di, &t.dout, &h->lp4, &t.p, &t.dvin, &t.dvout, &vel_off, &vel_stride, &vel_cap};
-    hipKernelNodeParams kp{};
-    kp.func = const_cast<void*>(func); kp.gridDim = dim3(t.n_scen); kp.blockDim = dim3(WG_THREADS); kp.sharedMemBytes = (unsigned)t.lds;
-    kp.kernelParams = kargs; kp.extra = nullptr;
-    const int has_out = zc ? 0 : 1;
-    bool ok = h->tg_exec && h->tg_func == func && h->tg_has_out == has_out;
-    if (ok) {
-        ok = hipGraphExecMemcpyNodeSetParams1D(h->tg_exec, h->tg_n_in, h->d_in, h->h_in, t.in_total, hipMemcpyHostToDevice) == hipSuccess &&
-             hipGraphExecKernelNodeSetParams(h->tg_exec, h->tg_n_k, &kp) == hipSuccess &&
-             (!has_out || hipGraphExecMemcpyNodeSetParams1D(h->tg_exec, h->tg_n_out, h->h_out, h->d_out, t.out_total, hipMemcpyDeviceToHost) == hipSuccess);
-        if (!ok) (void)hipGetLastError();
-    }
-    if (!ok) {
-        if (h->tg_exec) { (void)hipGraphExecDestroy(h->tg_exec); h->tg_exec = nullptr; }
-        if (h->tg_graph) { (void)hipGraphDestroy(h->tg_graph); h->tg_graph = nullptr; }
-        HIP_TRY(h, hipGraphCreate(&h->tg_graph, 0));
-        HIP_TRY(h, hipGraphAddMemcpyNode1D(&h->tg_n_in, h->tg_graph, nullptr, 0, h->d_in, h->h_in, t.in_total, hipMemcpyHostToDevice));
-        HIP_TRY(h, hipGraphAddKernelNode(&h->tg_n_k, h->tg_graph, &h->tg_n_in, 1, &kp));
-        if (has_out) HIP_TRY(h, hipGraphAddMemcpyNode1D(&h->tg_n_out, h->tg_graph, &h->tg_n_k, 1, h->h_out, h->d_out, t.out_total, hipMemcpyDeviceToHost));
-        HIP_TRY(h, hipGraphInstantiate(&h->tg_exec, h->tg_graph, nullptr, nullptr, 0));
-        h->tg_func = func; h->tg_has_out = has_out;
-    }
-    HIP_TRY(h, hipGraphLaunch(h->tg_exec, h->stream));
-    return LTPL_OK;
-}
-
-// ---- the persistent single tick (k_tick_persistent): host side --------------------------------------------------------------------------
-typedef void (*ptick_kernel_t)(const TickKArgs*, TickMailbox*, const unsigned char*, unsigned char*, unsigned, unsigned long long);
-static ptick_kernel_t ptick_kernel_of(int v)
-{
-    switch (v) {
-        case 0: return k_tick_persistent<0, false, PlanA4>; case 1: return k_tick_persistent<0, true, PlanA4>;
-        case 2: return k_tick_persistent<1, false, PlanA4>; case 3: return k_tick_persistent<1, true, PlanA4>;
-        case 4: return k_tick_persistent<2, false, PlanA4>; default: return k_tick_persistent<2, true, PlanA4>;
-    }
-}
-
-// Tell the resident kernel to leave and wait until it has (every entry point that reuses the staging buffers or synchronises the device
-// calls this first; ltpl_destroy too). Cheap when nothing is resident.
-static void persist_stop(ltpl_handle* h)
-{
-    ltpl_handle::PersistTick& P = h->pt;
-    if (!P.running) return;
-    __atomic_store_n(&P.mb->cmd, PT_CMD_EXIT, __ATOMIC_RELAXED);
-    if (++P.seq == 0u) ++P.seq;
-    __atomic_store_n(&P.mb->seq, P.seq, __ATOMIC_RELEASE);
-    (void)hipStreamSynchronize(P.stream);                     // the kernel sees the command within one poll (or had idled out already)
-    P.busy_clk += P.mb->busy_clk; P.busy_n += P.mb->n_done;
-    P.running = 0;
-}
-
-static int persist_start(ltpl_handle* h, const TickLayout& t, unsigned start_seq)
-{
-    ltpl_handle::PersistTick& P = h->pt;
-    if (!P.stream) {
-        // at the device's highest stream priority: the runtime keeps its hardware queues per priority, and nothing else of the library
-        // asks for this one by default -- the resident kernel, which never completes, then has a hardware queue that no stream of
-        // another handle (or fleet) shares, whatever their number. On a normal-priority stream it shared one of the (4 by default)
-        // queues with every other stream of the process mapped there: a kernel another handle launched behind it waited for the idle
-        // limit, and every persistent tick started the resident kernel again
-        int lo_p = 0, hi_p = 0;
-        (void)hipDeviceGetStreamPriorityRange(&lo_p, &hi_p);
-        HIP_TRY(h, hipStreamCreateWithPriority(&P.stream, hipStreamNonBlocking, hi_p));
-    }
-    if (!P.mb) {
-        HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&P.mb), sizeof(TickMailbox), hipHostMallocDefault));
-        memset(P.mb, 0, sizeof(TickMailbox));
-    }
-    if (!P.d_args) HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&P.d_args), 2048));
-    const void* func = reinterpret_cast<const void*>(ptick_kernel_of(t.variant));
-    if (t.lds > 48 * 1024) HIP_TRY(h, hipFuncSetAttribute(func, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t.lds));
-    P.mb->exited = 0; P.mb->n_done = 0; P.mb->busy_clk = 0; P.mb->cmd = PT_CMD_TICK;
-    __atomic_store_n(&P.mb->seq, start_seq, __ATOMIC_RELEASE);
-    const unsigned long long idle_limit = (unsigned long long)(P.idle_ms * 1e5);           // wall_clock64 counts at 100 MHz
-    hipLaunchKernelGGL(ptick_kernel_of(t.variant), dim3(1), dim3(WG_THREADS), t.lds, P.stream, (const TickKArgs*)P.d_args, P.mb,
-                       static_cast<const unsigned char*>(h->h_in), static_cast<unsigned char*>(h->d_in), start_seq, idle_limit);
-    HIP_TRY(h, hipGetLastError());
-    P.running = 1; P.variant = t.variant; P.lds = t.lds; P.h_in = h->h_in; P.d_in = h->d_in; P.seq = start_seq; ++P.launches;
-    return LTPL_OK;
-}
-
-// one tick through the resident kernel: staging buffers packed as for k_tick (zero-copy outputs, polled completion word)
-static int persist_tick(ltpl_handle* h, TickLayout& t)
-{
-    ltpl_handle::PersistTick& P = h->pt;
-    // the kernel idled out since the last tick (its last store: `exited`), or serves another kernel variant / other buffers: (re)start
-    if (P.running && __atomic_load_n(&P.mb->exited, __ATOMIC_ACQUIRE) != 0u) {
-        HIP_TRY(h, hipStreamSynchronize(P.stream));
-        P.busy_clk += P.mb->busy_clk; P.busy_n += P.mb->n_done; P.running = 0;
-    }
-    if (P.running && (P.variant != t.variant || P.lds != t.lds || P.h_in != h->h_in || P.d_in != h->d_in)) persist_stop(h);
-    int rc;
-    if (!P.running && (rc = persist_start(h, t, P.seq))) return rc;
-    TickKArgs ka;
-    memset(&ka, 0, sizeof(ka));
-    ka.pk.lat = h->lat; ka.pk.in = t.di; ka.pk.out = t.dout; ka.pk.lp = h->lp4;
-    ka.p = t.p; ka.vin = t.dvin; ka.vout = t.dvout; ka.vel_off = t.vel_off; ka.vel_stride = t.vel_stride; ka.vel_cap = t.vel_cap;
-    memcpy(P.mb->args, &ka, sizeof(ka));
-    P.mb->in_bytes = (unsigned)align_up(t.in_total, 16);
-    P.mb->cmd = PT_CMD_TICK;
-    if (++P.seq == 0u) ++P.seq;
-    __atomic_store_n(&P.mb->seq, P.seq, __ATOMIC_RELEASE);
-    const unsigned want = t.dout.done.seq;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned spins = 1;; ++spins) {
-        if (__atomic_load_n(h->h_flag, __ATOMIC_ACQUIRE) == want) break;
-        if ((spins & 0xfffu) != 0u) continue;
-        if (__atomic_load_n(&P.mb->exited, __ATOMIC_ACQUIRE) != 0u) {
-            // the kernel left (idle limit) between our check and our post: it cannot have seen this tick -- unless the completion word says so
-            HIP_TRY(h, hipStreamSynchronize(P.stream));
-            P.busy_clk += P.mb->busy_clk; P.busy_n += P.mb->n_done; P.running = 0;
-            if (__atomic_load_n(h->h_flag, __ATOMIC_ACQUIRE) == want) break;
-            const unsigned posted = P.seq;
-            if ((rc = persist_start(h, t, posted - 1u))) return rc;    // the new kernel starts "one behind" ...
-            P.seq = posted;
-            __atomic_store_n(&P.mb->seq, posted, __ATOMIC_RELEASE);  // ... and finds the tick that is still in the mailbox
-            continue;
-        }
-        if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2000)) {
-            __atomic_store_n(&P.mb->cmd, PT_CMD_EXIT, __ATOMIC_RELAXED);
-            h->err = "persistent tick: no completion within 2 s"; return LTPL_ERR_HIP;
-        }
-    }
-    ++P.ticks;
-    return LTPL_OK;
-}
-
-extern "C" int ltpl_tick_persistent_stop(ltpl_handle* h)
-try {
-    if (!h) return LTPL_ERR_INVALID_ARG;
-    HIP_TRY(h, hipSetDevice(h->device));
-    persist_stop(h);
-    return LTPL_OK;
-} LTPL_ABI_CATCH(abi_err_of(h))
-
-extern "C" int ltpl_tick_persistent_stats(ltpl_handle* h, ltpl_persistent_stats* st)
-try {
-    if (!h || !st) return LTPL_ERR_INVALID_ARG;
-    const ltpl_handle::PersistTick& P = h->pt;
-    st->enabled = P.enabled; st->resident = (P.running && P.mb && __atomic_load_n(&P.mb->exited, __ATOMIC_ACQUIRE) == 0u) ? 1 : 0;
-    st->ticks = (long long)P.ticks; st->launches = (long long)P.launches;
-    unsigned long long clk = P.busy_clk, n = P.busy_n;
-    if (P.running && P.mb) { clk += P.mb->busy_clk; n += P.mb->n_done; }
-    st->device_us_mean = n ? (double)clk / (double)n / 100.0 : 0.0;
-    st->device_us_last = (P.mb ? (double)P.mb->last_clk : 0.0) / 100.0;
-    st->idle_ms = P.idle_ms;
-    return LTPL_OK;
-} LTPL_ABI_CATCH(abi_err_of(h))
-
-extern "C" int ltpl_tick_batch(ltpl_handle* h, const ltpl_paths_in* in, const ltpl_tick_vel_in* vin, ltpl_paths_out* out,
-                               ltpl_tick_vel_out* vout)
-try {
-    if (!h) return LTPL_ERR_INVALID_ARG;
-    if (!out || !vout) { h->err = "null output"; return LTPL_ERR_INVALID_ARG; }
-    HIP_TRY(h, hipSetDevice(h->device));
-    const bool persistent = h->pt.enabled && in && in->n_scen == 1 && h->zc_out && !h->d_dbg;
-    drop_resident(h, persistent);
-    TickLayout t;
-    int rc = tick_prepare(h, in, vin, out->cap_nodes, out->cap_pts, &t);
-    if (rc) return rc;
-    if (persistent && !t.pipeline) {
-        // (growing a staging buffer frees the old one: the resident kernel leaves first -- persist_tick starts it again on the new buffers)
-        if (t.in_total > h->h_in_cap || t.in_total > h->d_in_cap || t.out_total > h->h_out_cap || t.out_total > h->d_out_cap) persist_stop(h);
-        if ((rc = ensure(h, &h->h_in, &h->h_in_cap, &h->d_in, &h->d_in_cap, align_up(t.in_total, 16)))) return rc;
-        if ((rc = ensure(h, &h->h_out, &h->h_out_cap, &h->d_out, &h->d_out_cap, t.out_total))) return rc;
-        if ((rc = tick_pack(h, in, vin, &t, static_cast<unsigned char*>(h->h_in), static_cast<unsigned char*>(h->d_in),
-                            static_cast<unsigned char*>(h->h_out)))) return rc;
-        t.dout.done = next_done_signal(h);
-        if ((rc = persist_tick(h, t))) return rc;
-        tick_scatter(static_cast<const unsigned char*>(h->h_out), t, out, vout);
-        return LTPL_OK;
-    }
-    persist_stop(h);
-    if ((rc = ensure(h, &h->h_in, &h->h_in_cap, &h->d_in, &h->d_in_cap, t.in_total))) return rc;
-    if ((rc = ensure(h, &h->h_out, &h->h_out_cap, &h->d_out, &h->d_out_cap, t.out_total))) return rc;
-    // single ticks (fused kernel): outputs straight into the page-locked buffer, completion through the polled word (see plan_paths_impl)
-    const bool zc = h->zc_out && !t.pipeline && in->n_scen <= 8;
-    const bool polled = zc && h->poll && !h->d_dbg;
-    if ((rc = tick_pack(h, in, vin, &t, static_cast<unsigned char*>(h->h_in), static_cast<unsigned char*>(h->d_in),
-                        static_cast<unsigned char*>(zc ? h->h_out : h->d_out)))) return rc;
-    if (polled) t.dout.done = next_done_signal(h);
-    if ((rc = tick_set_lds_limit(h, t.lds, t.variant))) return rc;
-    if (h->tick_graph && !t.pipeline) {
-        if ((rc = tick_launch_graph(h, t, zc))) return rc;
-    } else {
-        HIP_TRY(h, hipMemcpyAsync(h->d_in, h->h_in, t.in_total, hipMemcpyHostToDevice, h->stream));
-        if ((rc = tick_launch(h, t))) return rc;
-        if (!zc) HIP_TRY(h, hipMemcpyAsync(h->h_out, h->d_out, t.out_total, hipMemcpyDeviceToHost, h->stream));
-    }
-    if (polled) { if ((rc = wait_done(h, t.dout.done.seq))) return rc; }
-    else HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (t.pipeline) dbg_report_lanes(h); else dbg_report(h, "k_tick", in->n_scen);
-    tick_scatter(static_cast<const unsigned char*>(h->h_out), t, out, vout);
-    return LTPL_OK;
-} LTPL_ABI_CATCH(abi_err_of(h))
-
-extern "C" void* ltpl_host_alloc(size_t bytes)
-{
-    void* p = nullptr;
-    if (hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault) != hipSuccess) return nullptr;
-    return p;
-}
-extern "C" void ltpl_host_free(void* p) { if (p) (void)hipHostFree(p); }
-
-extern "C" int ltpl_tick_batch_compact(ltpl_handle* h, const ltpl_paths_in* in, const ltpl_tick_vel_in* vin, ltpl_traj_out* out)
-try {
-    if (!h) return LTPL_ERR_INVALID_ARG;
-    if (!out || !out->rows || !out->action_id || !out->n_rows || !out->vel_bound || !out->reduced || !out->row_off || out->capacity_rows < 0) {
-        h->err = "null output"; return LTPL_ERR_INVALID_ARG;
-    }
-    HIP_TRY(h, hipSetDevice(h->device));
-    drop_resident(h);
-    TickLayout t;
-    int rc = tick_prepare(h, in, vin, h->caps.max_path_nodes, h->caps.max_path_pts, &t);
-    if (rc) return rc;
-    const size_t n_slots = (size_t)in->n_scen * LTPL_MAX_ACTIONS;
-    // device scratch behind the regular output slab: rows kept, offsets, total, packed rows
-    Arena b; b.size = t.out_total;
-    const size_t o_rows = b.add(sizeof(int) * n_slots), o_off = b.add(sizeof(long long) * n_slots), o_tot = b.add(sizeof(long long));
-    const size_t o_pack = b.add(sizeof(double) * 7 * (size_t)out->capacity_rows);
-    if ((rc = ensure(h, &h->h_in, &h->h_in_cap, &h->d_in, &h->d_in_cap, t.in_total))) return rc;
-    // host staging only for the small per-slot arrays (+ the packed rows when the caller's buffer is not page-locked)
-    hipPointerAttribute_t attr; bool pinned = false;
-    if (hipPointerGetAttributes(&attr, out->rows) == hipSuccess) pinned = attr.type == hipMemoryTypeHost;
-    else (void)hipGetLastError();
-    const size_t small_bytes = sizeof(int) * n_slots * 4 + sizeof(long long) * (n_slots + 1) + 64;
-    const size_t h_need = small_bytes + (pinned ? 0 : sizeof(double) * 7 * (size_t)out->capacity_rows);
-    if ((rc = ensure(h, &h->h_out, &h->h_out_cap, &h->d_out, &h->d_out_cap, b.size > h_need ? b.size : h_need))) return rc;
-    if ((rc = tick_pack(h, in, vin, &t, static_cast<unsigned char*>(h->h_in), static_cast<unsigned char*>(h->d_in),
-                        static_cast<unsigned char*>(h->d_out)))) return rc;
-    if ((rc = tick_set_lds_limit(h, t.lds, t.variant))) return rc;
-    HIP_TRY(h, hipMemcpyAsync(h->d_in, h->h_in, t.in_total, hipMemcpyHostToDevice, h->stream));
-    if ((rc = tick_launch(h, t))) return rc;
-    unsigned char* dob = static_cast<unsigned char*>(h->d_out);
-    int* d_rows = reinterpret_cast<int*>(dob + o_rows); long long* d_off = reinterpret_cast<long long*>(dob + o_off);
-    long long* d_tot = reinterpret_cast<long long*>(dob + o_tot); double* d_pack = reinterpret_cast<double*>(dob + o_pack);
-    hipLaunchKernelGGL(k_compact_offsets, dim3(1), dim3(1024), 0, h->stream, t.dout.valid, t.dout.n_pts, (int)n_slots, out->max_rows, d_rows, d_off, d_tot);
-    hipLaunchKernelGGL(k_compact_rows, dim3((unsigned)n_slots), dim3(64), 0, h->stream, t.dout, t.dvout, d_rows, d_off, d_pack, (long long)out->capacity_rows);
-    HIP_TRY(h, hipGetLastError());
-    // small arrays first (they tell how many packed bytes there are)
-    unsigned char* hb = static_cast<unsigned char*>(h->h_out);
-    int* h_rows = reinterpret_cast<int*>(hb); int* h_act = h_rows + n_slots; int* h_vb = h_act + n_slots; int* h_red = h_vb + n_slots;
-    long long* h_off = reinterpret_cast<long long*>(h_red + n_slots + 2); long long* h_tot = h_off + n_slots;
-    HIP_TRY(h, hipMemcpyAsync(h_rows, d_rows, sizeof(int) * n_slots, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h_act, t.dout.action_id, sizeof(int) * n_slots, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h_vb, t.dvout.vel_bound, sizeof(int) * n_slots, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h_red, t.dout.reduced, sizeof(int) * n_slots, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h_off, d_off, sizeof(long long) * n_slots, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h_tot, d_tot, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    const long long total = *h_tot;
-    out->total_rows = total;
-    if (total > out->capacity_rows) { h->err = "ltpl_traj_out.capacity_rows too small (total_rows holds the need)"; return LTPL_ERR_CAPACITY; }
-    double* h_pack = pinned ? out->rows : reinterpret_cast<double*>(hb + small_bytes);
-    if (total > 0) {
-        HIP_TRY(h, hipMemcpyAsync(h_pack, d_pack, sizeof(double) * 7 * (size_t)total, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (!pinned) memcpy(out->rows, h_pack, sizeof(double) * 7 * (size_t)total);
-    }
-    memcpy(out->n_rows, h_rows, sizeof(int) * n_slots); memcpy(out->action_id, h_act, sizeof(int) * n_slots);
-    memcpy(out->vel_bound, h_vb, sizeof(int) * n_slots); memcpy(out->reduced, h_red, sizeof(int) * n_slots);
-    memcpy(out->row_off, h_off, sizeof(long long) * n_slots);
-    return LTPL_OK;
-} LTPL_ABI_CATCH(abi_err_of(h))
-
-// device-resident batch (benchmarks): inputs stay in HBM, the fused kernel is replayed on the handle's stream
-extern "C" int ltpl_batch_upload(ltpl_handle* h, const ltpl_paths_in* in, const ltpl_tick_vel_in* vin, int32_t cap_nodes,
-                                 int32_t cap_pts)
-try {
-    if (!h) return LTPL_ERR_INVALID_ARG;
-    HIP_TRY(h, hipSetDevice(h->device));
-    drop_resident(h);
-    TickLayout* t = new TickLayout();
-    int rc = tick_prepare(h, in, vin, cap_nodes, cap_pts, t);
-    if (rc) { delete t; return rc; }
-    if ((rc = ensure(h, &h->h_in, &h->h_in_cap, &h->d_in, &h->d_in_cap, t->in_total))) { delete t; return rc; }
-    if ((rc = ensure(h, &h->h_out, &h->h_out_cap, &h->d_out, &h->d_out_cap, t->out_total))) { delete t; return rc; }
-    if ((rc = tick_pack(h, in, vin, t, static_cast<unsigned char*>(h->h_in), static_cast<unsigned char*>(h->d_in),
-                        static_cast<unsigned char*>(h->d_out)))) { delete t; return rc; }
-    if ((rc = tick_set_lds_limit(h, t->lds, t->variant))) { delete t; return rc; }
-    HIP_TRY(h, hipMemcpyAsync(h->d_in, h->h_in, t->in_total, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->resident = t;
-    h->last_set = 0;
-    if (t->pipeline && !h->no_overlap) {
-        // further buffer sets for the software pipeline of ltpl_batch_run
-        for (int i = 0; i < ltpl_handle::VEL_STREAMS; ++i) if (!h->vel_stream[i]) {
-            // LTPL_VEL_STREAM_PRIO=1 (experiment): the velocity streams at the device's highest stream priority (their waves are dispatched
-            // ahead of the path kernel's whenever a slot frees up)
-            static const bool hi = getenv("LTPL_VEL_STREAM_PRIO") && atoi(getenv("LTPL_VEL_STREAM_PRIO")) != 0;
-            // LTPL_VEL_CUS=<n> (round-5 experiment): the velocity streams confined to n compute units by a CU mask. The velocity waves are few,
-            // long-lived (a serial recurrence over the rows of a profile) and hold 197 VGPRs: next to one of them a SIMD keeps two path waves
-            // instead of four. Confined, they run among themselves on a corner of the chip. 0 / unset: no mask.
-            static const int vel_cus = getenv("LTPL_VEL_CUS") ? atoi(getenv("LTPL_VEL_CUS")) : 0;
-            bool made = false;
-            if (vel_cus > 0) {
-                const int ncu = h->caps.num_cus > 0 ? h->caps.num_cus : 256;
-                std::vector<uint32_t> mask((size_t)(ncu + 31) / 32, 0u);
-                for (int c = 0; c < vel_cus && c < ncu; ++c) mask[(size_t)c >> 5] |= 1u << (c & 31);
-                made = hipExtStreamCreateWithCUMask(&h->vel_stream[i], (uint32_t)mask.size(), mask.data()) == hipSuccess;
-                if (!made) { (void)hipGetLastError(); h->vel_stream[i] = nullptr; }
-            }
-            if (made) continue;
-            if (hi) { int lo_p = 0, hi_p = 0; (void)hipDeviceGetStreamPriorityRange(&lo_p, &hi_p); HIP_TRY(h, hipStreamCreateWithPriority(&h->vel_stream[i], hipStreamNonBlocking, hi_p)); }
-            else HIP_TRY(h, hipStreamCreateWithFlags(&h->vel_stream[i], hipStreamNonBlocking));
-        }
-        {
-            const char* ps = getenv("LTPL_PATH_STREAMS");
-            h->path_streams = (ps && atoi(ps) == 2) ? 2 : 1;
-            if (h->path_streams == 2 && !h->path_stream2) HIP_TRY(h, hipStreamCreateWithFlags(&h->path_stream2, hipStreamNonBlocking));
-            if (!h->ev_begin) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_begin, hipEventDisableTiming));
-        }
-        for (int i = 0; i < ltpl_handle::PIPE_SETS; ++i) {
-            if (!h->ev_paths[i]) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_paths[i], hipEventDisableTiming));
-            if (!h->ev_vel[i]) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_vel[i], hipEventDisableTiming));
-        }
-        for (int i = 0; i < ltpl_handle::PIPE_SETS - 1; ++i) {
-            if (t->out_total > h->d_out_x_cap[i]) {
-                if (h->d_out_x[i]) (void)hipFree(h->d_out_x[i]);
-                h->d_out_x[i] = nullptr; h->d_out_x_cap[i] = 0;
-                HIP_TRY(h, hipMalloc(&h->d_out_x[i], t->out_total)); h->d_out_x_cap[i] = t->out_total;
-            }
-            if (t->planes_bytes > h->d_planes_x_cap[i]) {
-                if (h->d_planes_x[i]) (void)hipFree(h->d_planes_x[i]);
-                h->d_planes_x[i] = nullptr; h->d_planes_x_cap[i] = 0;
-                HIP_TRY(h, hipMalloc(&h->d_planes_x[i], t->planes_bytes)); h->d_planes_x_cap[i] = t->planes_bytes;
-            }
-            TickLayout* tx = new TickLayout(*t);
-            tick_bind_outputs(tx, static_cast<unsigned char*>(h->d_out_x[i]), static_cast<double*>(h->d_planes_x[i]));
-            h->resident_x[i] = tx;
-        }
-    }
-    return LTPL_OK;
-} LTPL_ABI_CATCH(abi_err_of(h))
-
-extern "C" int ltpl_batch_run(ltpl_handle* h, int reps, float* ms_total)
-try {
-    if (!h) return LTPL_ERR_INVALID_ARG;
-    if (!h->resident) { h->err = "no resident batch: call ltpl_batch_upload first"; return LTPL_ERR_INVALID_ARG; }
-    if (reps < 1) { h->err = "reps < 1"; return LTPL_ERR_INVALID_ARG; }
-    HIP_TRY(h, hipSetDevice(h->device));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (ms_total) {
-        HIP_TRY(h, hipEventCreate(&e0)); HIP_TRY(h, hipEventCreate(&e1));
-        HIP_TRY(h, hipEventRecord(e0, h->stream));
-    }
-    if (h->resident_x[0] && ms_total) {
-        while (h->ev_step.size() < 2 * (size_t)reps) { hipEvent_t e; HIP_TRY(h, hipEventCreate(&e)); h->ev_step.push_back(e); }
-    }
-    h->last_paths_ms = 0.0f; h->last_paths_n = 0;
-    if (h->resident_x[0]) {
-        // software pipeline over steps: path kernel of step r on `stream`, velocity kernels of step r on `vel_stream[r % VEL_STREAMS]` (alternating:
-        // the chains of consecutive steps run next to each other), PIPE_SETS buffer sets; the path kernel of step r + PIPE_SETS waits
-        // until the velocity kernels of step r released its set
-        constexpr int K = ltpl_handle::PIPE_SETS;
-        const bool two = h->path_streams == 2 && h->path_stream2;
-        if (two) {      // the second path stream starts behind everything queued on `stream` so far
-            HIP_TRY(h, hipEventRecord(h->ev_begin, h->stream));
-            HIP_TRY(h, hipStreamWaitEvent(h->path_stream2, h->ev_begin, 0));
-        }
-        for (int r = 0; r < reps; ++r) {
-            const int set = r % K;
-            const TickLayout& T = set ? *h->resident_x[set - 1] : *h->resident;
-            hipStream_t sp = (two && (r & 1)) ? h->path_stream2 : h->stream;
-            if (r >= K) HIP_TRY(h, hipStreamWaitEvent(sp, h->ev_vel[set], 0));
-            if (ms_total) HIP_TRY(h, hipEventRecord(h->ev_step[2 * (size_t)r], sp));
-            int rc = tick_launch_paths(h, T, sp);
-            if (rc) return rc;
-            if (ms_total) HIP_TRY(h, hipEventRecord(h->ev_step[2 * (size_t)r + 1], sp));
-            HIP_TRY(h, hipEventRecord(h->ev_paths[set], sp));
-            hipStream_t sv = h->vel_stream[r % ltpl_handle::VEL_STREAMS];
-            HIP_TRY(h, hipStreamWaitEvent(sv, h->ev_paths[set], 0));
-            if ((rc = tick_launch_vel(h, T, sv))) return rc;
-            HIP_TRY(h, hipEventRecord(h->ev_vel[set], sv));
-            h->last_set = set;
-        }
-        // everything joins `stream` again (the caller's events / synchronisation are on it)
-        for (int i = 0; i < K && i < reps; ++i) HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_vel[i], 0));
-    } else {
-        for (int r = 0; r < reps; ++r) { int rc = tick_launch(h, *h->resident); if (rc) return rc; }
-    }
-    if (ms_total) {
-        HIP_TRY(h, hipEventRecord(e1, h->stream));
-        HIP_TRY(h, hipEventSynchronize(e1));
-        HIP_TRY(h, hipEventElapsedTime(ms_total, e0, e1));
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-        if (h->resident_x[0]) {
-            for (int r = 0; r < reps; ++r) {
-                float ms = 0.0f;
-                HIP_TRY(h, hipEventElapsedTime(&ms, h->ev_step[2 * (size_t)r], h->ev_step[2 * (size_t)r + 1]));
-                h->last_paths_ms += ms;
-            }
-            h->last_paths_n = reps;
-        }
-    } else {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-    }
-    return LTPL_OK;
-} LTPL_ABI_CATCH(abi_err_of(h))
-
-extern "C" int ltpl_batch_last_paths_ms(ltpl_handle* h, float* ms_avg)
-{
-    if (!h || !ms_avg) return LTPL_ERR_INVALID_ARG;
-    *ms_avg = h->last_paths_n > 0 ? h->last_paths_ms / (float)h->last_paths_n : 0.0f;
-    return LTPL_OK;
-}
-
-extern "C" int ltpl_batch_run_profile(ltpl_handle* h, int reps, float* ms_kernels)
-try {
-    if (!h) return LTPL_ERR_INVALID_ARG;
-    if (!h->resident) { h->err = "no resident batch: call ltpl_batch_upload first"; return LTPL_ERR_INVALID_ARG; }
-    if (reps < 1 || !ms_kernels) { h->err = "reps < 1 or null output"; return LTPL_ERR_INVALID_ARG; }
-    HIP_TRY(h, hipSetDevice(h->device));
-    hipEvent_t ev[4];
-    for (int i = 0; i < 4; ++i) HIP_TRY(h, hipEventCreate(&ev[i]));
-    ms_kernels[0] = ms_kernels[1] = ms_kernels[2] = 0.0f;
-    for (int r = 0; r < reps; ++r) {
-        int rc = tick_launch(h, *h->resident, ev);
-        if (rc) return rc;
-        HIP_TRY(h, hipEventSynchronize(ev[3]));
-        for (int k = 0; k < 3; ++k) { float ms = 0.0f; HIP_TRY(h, hipEventElapsedTime(&ms, ev[k], ev[k + 1])); ms_kernels[k] += ms; }
-    }
-    for (int i = 0; i < 4; ++i) (void)hipEventDestroy(ev[i]);
-    return LTPL_OK;
-} LTPL_ABI_CATCH(abi_err_of(h))
-
-extern "C" int ltpl_batch_download(ltpl_handle* h, ltpl_paths_out* out, ltpl_tick_vel_out* vout)
-try {
-    if (!h) return LTPL_ERR_INVALID_ARG;
-    if (!h->resident) { h->err = "no resident batch"; return LTPL_ERR_INVALID_ARG; }
-    if (!out || !vout || out->cap_nodes != h->resident->cap_nodes || out->cap_pts != h->resident->cap_pts) {
-        h->err = "output capacities differ from ltpl_batch_upload"; return LTPL_ERR_INVALID_ARG;
-    }
-    HIP_TRY(h, hipSetDevice(h->device));
-    const void* src = (h->resident_x[0] && h->last_set >= 1) ? h->d_out_x[h->last_set - 1] : h->d_out;
-    HIP_TRY(h, hipMemcpyAsync(h->h_out, src, h->resident->out_total, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    tick_scatter(static_cast<const unsigned char*>(h->h_out), *h->resident, out, vout);
-    return LTPL_OK;
-} LTPL_ABI_CATCH(abi_err_of(h))
-
-static void free_resident(TickLayout* t) { delete t; }
+#include "tick_host.hpp"
 
 // ---------------------------------------------------------------------------------------------------------------------
 // offline lattice build: every candidate edge of a track in one launch, lane = edge

@@ -1,7 +1,7 @@
 """
 Host-side mirror of seam (2): class ``VpForwardBackward`` (graph_ltpl/online_graph/src/VpForwardBackward.py:11-255) with
 the same constructor, methods, argument names and return values; the arithmetic (tph.calc_vel_profile,
-tph.calc_vel_profile_brake and calc_vel_profile_follow.py) runs in the velocity kernels of csrc/ltpl_hip.hip.
+tph.calc_vel_profile_brake and calc_vel_profile_follow.py) runs in the velocity kernels of csrc/vel_wave.hpp and csrc/vel_lanes.hpp.
 """
 import logging
 import numpy as np

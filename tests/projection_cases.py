@@ -1,7 +1,7 @@
 """Probe generators of the projection boundary tests (tests/test_projection_cases_host.py on the CPU, tests/test_gpu_projection.py on the GPU):
 query points placed ON PURPOSE at the decision boundaries of `get_s_coord` (get_s_coord.py:8-99) -- the projection of a point on a polyline
 that every follow job, the planner's cut index and its start node go through -- in all its forms: get_s_coord_dev, globrl_index_dev,
-lane_globrl_index and the foot lambda of k_follow_prep (csrc/ltpl_hip.hip), project_on_polyline of csrc/fleet_core.hpp and of
+lane_globrl_index and the foot lambda of k_follow_prep (csrc/vel_wave.hpp, csrc/vel_lanes.hpp), project_on_polyline of csrc/fleet_core.hpp and of
 csrc/planner_core.hpp, the oracle's get_s_coord. Pure NumPy, seeded; nothing here runs a kernel.
 
 THE TWO RULES. The reference picks the neighbour of the closest point nb by comparing |angle3pt| of the two neighbours (four atan2); the kernels

@@ -1,4 +1,4 @@
-"""GPU: the cross-lane helpers of the kernels (DPP row operations + v_permlane16/32_swap, csrc/ltpl_hip.hip "CROSS-LANE MOVES ON THE
+"""GPU: the cross-lane helpers of the kernels (DPP row operations + v_permlane16/32_swap, csrc/wave_ops.hpp "CROSS-LANE MOVES ON THE
 VECTOR ALU") against plain loops over the wave's values -- wave minima / maxima, the lexicographic two- and three-key minima with
 many exact ties, the segment merge of the closest-layer search for every segment width, the exclusive prefix sum.
 Likewise the small numeric routines of the path assembly (csrc/paths_team.hpp: heading_atan2, heading_sincos, fast_rcp, rsqrt_cubed) against

@@ -4,7 +4,8 @@ Resolve compile-time switches in the kernel sources as if they were never define
 `#ifdef X / #ifndef X / #if defined(X) / #elif defined(X) / #else / #endif` that a build WITHOUT -DX compiles stay, the others and the
 directives go. Used once in round 6 to move the experiment switches whose same-box A/B was lost (docs/HISTORY.md, "Round 5: experiment
 log") out of csrc/paths_team.hpp and csrc/ltpl_hip.hip; the removed text is kept as a patch under tools/experiments/ (apply with
-`git apply` to get a switch back). The generated code of the default build must not change: compare __graft_entry__.build_stamp before / after.
+`git apply` to get a switch back). The generated code of the default build must not change: compare __graft_entry__.build_stamp before / after,
+and every kernel of the two libraries with tools/compare_device_code.py.
 
     python tools/strip_switches.py <file> SWITCH [SWITCH ...]        (rewrites <file> in place, prints the number of directives resolved)
 """
