@@ -3,9 +3,14 @@
 // The rule: what the tick kernels WRITE travels with a planner's state, what the caller SET stays with the destination --
 //   copied   the planner block (Dims::stride bytes of d_state; the planner's error word PlannerS::err lies in it), its window of friction
 //            rows (Dims::gg_stride bytes of d_gg) when both sides have windows, now / sel / started / pos_x / pos_y / vel / theta / live,
-//            opp_s / opp_tic of its opponents, and with telemetry on both sides its record, grid_s and prog;
+//            opp_s / opp_tic of its opponents, with telemetry on both sides its record, grid_s and prog, and the vehicle model's record
+//            (state and statistics, ltpl_fleet_sim_vehicle) where the DESTINATION has model 1;
 //   stays    the race line, the opponents' vel_scale / length, statics, zones, preference list, dt, n_export, the velocity arguments,
-//            friction map index and scale, race membership and length as a mate, contact radius, the recorder's ring and indices.
+//            friction map index and scale, race membership and length as a mate, contact radius, the recorder's ring and indices,
+//            the vehicle model's switch and parameters.
+// Vehicle model, the mixed cases: a destination on the ideal tracker (or a fleet without the model) takes no vehicle record and keeps its
+// NaN record, whatever the source drives; a destination with model 1 needs a source that had model 1 when it was copied (the live
+// planner now, the snapshot's planner when the snapshot was taken) -- otherwise the pair is refused with LTPL_ERR_INVALID_ARG.
 // Everything else the simulation holds per planner (cnt, prev_action, t_now, veh_off, the staging slots and object arrays, the job pools
 // of the velocity stage) is written by every tick before it is read.
 // One kernel serves the three directions live -> snapshot, snapshot -> live and live -> live: it copies between two VIEWS, each a set of
@@ -18,6 +23,7 @@ struct BranchView {
     double* now; int* sel; int* started; double* pos_x; double* pos_y; double* vel; double* theta; int* live;
     const int* opp_off; double* opp_s; double* opp_tic; // opponents of entry e: opp_off[e] .. opp_off[e + 1] - 1
     double* rec; double* grid_s; double* prog;          // telemetry part (rec null: none)
+    double* veh; const int* veh_model;                  // vehicle records (veh null: none); as a destination: the model of every entry
 };
 
 typedef unsigned int branch_u32x4 __attribute__((ext_vector_type(4)));
@@ -70,6 +76,8 @@ __global__ __launch_bounds__(BRANCH_THREADS) void k_fleet_sim_branch(BranchView 
             else if (t == LTPL_FLEET_SIM_TELE_DOUBLES) T.grid_s[ed] = S.grid_s[es];
             else if (t == LTPL_FLEET_SIM_TELE_DOUBLES + 1) T.prog[ed] = S.prog[es];
         }
+        if (S.veh && T.veh && t < LTPL_FLEET_SIM_VEH_DOUBLES && T.veh_model[ed] != 0)
+            T.veh[ed * LTPL_FLEET_SIM_VEH_DOUBLES + t] = S.veh[es * LTPL_FLEET_SIM_VEH_DOUBLES + t];
     }
 }
 static_assert(LTPL_FLEET_SIM_TELE_DOUBLES + 2 <= 64, "k_fleet_sim_branch: one lane per telemetry double");
@@ -84,6 +92,7 @@ struct SimSnap {
     std::vector<int> entry_of;              // [N] entry of planner p, -1: not in the snapshot
     std::vector<int> opp_off;               // [entries + 1] host copy of v.opp_off
     bool has_tele = false; int tele_gen = 0;     // a telemetry part, taken from the telemetry numbered tele_gen (FleetSim::tele_gen)
+    std::vector<int> veh_model;             // [entries] the model of entry k when the snapshot was taken (empty: the model was off)
     uint64_t bytes = 0;
     bool held() const { return !planners.empty(); }
 };
@@ -103,6 +112,7 @@ static BranchView branch_live_view(const ltpl_fleet* f)
     v.now = d.now; v.sel = d.sel; v.started = d.started; v.pos_x = d.pos_x; v.pos_y = d.pos_y; v.vel = d.vel; v.theta = d.theta; v.live = d.live;
     v.opp_off = d.opp_off; v.opp_s = d.opp_s; v.opp_tic = d.opp_tic;
     if (s.has_tele) { v.rec = s.te.rec; v.grid_s = s.te.grid_s; v.prog = s.te.prog; }
+    if (s.has_veh) { v.veh = s.vh.rec; v.veh_model = s.vh.model; }
     return v;
 }
 
@@ -203,6 +213,12 @@ try {
     { int* o = nullptr; SNAP_TAKE(&o, M + 1, q->opp_off.data()); v.opp_off = o; }
     SNAP_TAKE(&v.opp_s, n_opp); SNAP_TAKE(&v.opp_tic, n_opp);
     if (s.has_tele) { SNAP_TAKE(&v.rec, M * LTPL_FLEET_SIM_TELE_DOUBLES); SNAP_TAKE(&v.grid_s, M); SNAP_TAKE(&v.prog, M); }
+    if (s.has_veh) {                                     // (the snapshot's entries carry the source's model: its records are copied as they are)
+        q->veh_model.resize(M);
+        for (size_t k = 0; k < M; ++k) q->veh_model[k] = s.veh_model[(size_t)q->planners[k]];
+        SNAP_TAKE(&v.veh, M * LTPL_FLEET_SIM_VEH_DOUBLES);
+        { int* o = nullptr; SNAP_TAKE(&o, M, q->veh_model.data()); v.veh_model = o; }
+    }
 #undef SNAP_TAKE
     std::vector<int> dst(M);
     for (size_t k = 0; k < M; ++k) dst[k] = (int)k;
@@ -287,6 +303,10 @@ try {
         }
         const int no_dst = s.opp_off[(size_t)b + 1] - s.opp_off[(size_t)b];
         if (no_src != no_dst) return bad(pair(k) + "the source has " + std::to_string(no_src) + " opponents, the destination " + std::to_string(no_dst));
+        if (s.has_veh && s.veh_model[(size_t)b] != 0) {      // (a destination on the ideal tracker takes no vehicle record)
+            const bool src_has = q ? !q->veh_model.empty() && q->veh_model[(size_t)se.back()] != 0 : s.veh_model[(size_t)a] != 0;
+            if (!src_has) return bad(pair(k) + "the destination drives the vehicle model, the source has no vehicle state (model 0 when it was copied)");
+        }
         de.push_back(b);
     }
     if ((rc = fleet_enter(f))) return rc;

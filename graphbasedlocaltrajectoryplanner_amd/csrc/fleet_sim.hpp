@@ -9,6 +9,10 @@
 //                        With sensor noise set (ltpl_fleet_sim_noise; the generator: fleet_noise.hpp) the tick launches k_fleet_sim_step_noise
 //                        and k_fleet_sim_mates_noise instead: the same bodies, every object perturbed in its ingestion lane before
 //                        process_object_dev and the planner's pos_est / vel_est written behind the tracker (registers only, no LDS added)
+//                        With a vehicle model set (ltpl_fleet_sim_vehicle; the model: fleet_vehicle.hpp) it launches k_fleet_sim_step_veh /
+//                        k_fleet_sim_step_noise_veh: the same body with column ax staged as well; a planner with model 1 (wave-uniform)
+//                        drives the car instead of the ideal tracker -- every lane runs the 1 ms loop on the same values, the
+//                        projection of a control step walks the segments with one lane each and ends in sim_wave_min
 //   k_fleet_sim_mates    (races with more than one planner only: ltpl_fleet_sim_race) one wave64 per planner, one lane per mate: every
 //                        other planner of the race, at the pose / speed / heading its tracker wrote above, through the same ingestion,
 //                        appended behind the planner's opponents and statics. Its own launch: every tracker of the tick is done first
@@ -29,6 +33,7 @@
 #pragma once
 
 #include "fleet_noise.hpp"
+#include "fleet_vehicle.hpp"
 
 namespace fleet {
 
@@ -126,10 +131,44 @@ __device__ __forceinline__ SimBest sim_wave_min(SimBest v)
     return v;
 }
 
+// vehicle model (ltpl_fleet_sim_vehicle): what the _veh forms of k_fleet_sim_step get besides SimDev. The other kernels carry none of it.
+#define VEH_PARAMS 9                       // fleet::VehParams
+struct SimVeh {
+    const int* model;                      // [N] 0: the ideal tracker, 1: the model
+    const double* par;                     // [N][VEH_PARAMS] in the order of fleet::VehParams
+    double* rec;                           // [N][LTPL_FLEET_SIM_VEH_DOUBLES] state and statistics (NaN for a planner on the ideal tracker)
+    int ctl_steps;                         // control period in plant steps
+};
+enum { VEH_X = 0, VEH_Y, VEH_C, VEH_S, VEH_V, VEH_A, VEH_KAPPA, VEH_E, VEH_E_MAX, VEH_E2_SUM, VEH_DV_MAX, VEH_CTL, VEH_SAT_LAT, VEH_SAT_LON,
+       VEH_OFF_TRACK };
+static_assert(VEH_OFF_TRACK + 1 == LTPL_FLEET_SIM_VEH_DOUBLES && sizeof(fleet::VehParams) == VEH_PARAMS * sizeof(double), "vehicle record layout");
+
+__device__ __forceinline__ fleet::VehParams sim_vehicle_params(const double* q)
+{
+    return fleet::VehParams{q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8]};
+}
+// a tick of the model by a whole wave: every lane holds the same state and runs the same loop; the projection of a control step is
+// lane-parallel over the segments (fleet::veh_seg) and ends in the wave-wide minimum, ties to the lower segment (sim_better)
+__device__ __forceinline__ void sim_vehicle_tick(int lane, fleet::VehState& S, const fleet::VehParams& P, const fleet::VehRows& R, double dt,
+                                                 int ctl_steps, fleet::VehStats& st)
+{
+    fleet::veh_tick(S, P, R, dt, ctl_steps, st, [&](double px, double py) {
+        SimBest b{INFINITY, fleet::kVehNone};
+        for (int i = lane; i + 1 < R.n; i += 64) {
+            double d2;
+            if (fleet::veh_seg(R, i, px, py, &d2)) b = sim_better(b, SimBest{d2, i});
+        }
+        b = sim_wave_min(b);
+        return fleet::VehBest{b.d, b.i};
+    });
+}
+
 // the body of k_fleet_sim_step (NOISE false: `nz` is not touched and the code is the one without noise) and of k_fleet_sim_step_noise: every
-// object perturbed in its ingestion lane (registers only: no LDS is added), the ego estimate written behind the tracker by lane 0
-template <bool NOISE>
-__device__ __forceinline__ void sim_step_body(const FleetArgs& F, const DevLat& lat, const SimDev& sd, double* trace, const SimNoise& nz)
+// object perturbed in its ingestion lane (registers only: no LDS is added), the ego estimate written behind the tracker by lane 0.
+// VEH (k_fleet_sim_step_veh, k_fleet_sim_step_noise_veh): column ax staged too; a planner with vh.model[p] != 0 drives the vehicle model
+template <bool NOISE, bool VEH>
+__device__ __forceinline__ void sim_step_body(const FleetArgs& F, const DevLat& lat, const SimDev& sd, double* trace, const SimNoise& nz,
+                                              const SimVeh& vh)
 {
     const int p = blockIdx.x, lane = threadIdx.x; const WaveX x{lane};
     const fleet::Block B{F.state + F.D.stride * (size_t)p, F.D, nullptr};
@@ -137,6 +176,8 @@ __device__ __forceinline__ void sim_step_body(const FleetArgs& F, const DevLat& 
     __shared__ double ts[LTPL_FLEET_SIM_MAX_EXPORT], tx[LTPL_FLEET_SIM_MAX_EXPORT], ty[LTPL_FLEET_SIM_MAX_EXPORT], tv[LTPL_FLEET_SIM_MAX_EXPORT];
     __shared__ double ox[SIM_OBJ_CAP], oy[SIM_OBJ_CAP], oth[SIM_OBJ_CAP], ov[SIM_OBJ_CAP], ol[SIM_OBJ_CAP];
     __shared__ double first_xy[2];
+    double* ta = nullptr;                  // column ax: LDS of the _veh forms only
+    if constexpr (VEH) { __shared__ double ta_lds[LTPL_FLEET_SIM_MAX_EXPORT]; ta = ta_lds; }
     fleet_load(x, B, &S);
     double now = sd.now[p], pos_x = sd.pos_x[p], pos_y = sd.pos_y[p], vel = sd.vel[p], theta = sd.theta[p];
     int sel = sd.sel[p], cnt = 0;
@@ -222,8 +263,23 @@ __device__ __forceinline__ void sim_step_body(const FleetArgs& F, const DevLat& 
                 const fleet::Rows tr = B.bp(S.bp_slot[slot]);
                 const int n = S.bp_rows[slot] < sd.n_export ? S.bp_rows[slot] : sd.n_export;
                 for (int i = lane; i < n; i += 64) { ts[i] = tr.at(i, 0); tx[i] = tr.at(i, 1); ty[i] = tr.at(i, 2); tv[i] = tr.at(i, 5); }
+                if constexpr (VEH) for (int i = lane; i < n; i += 64) ta[i] = tr.at(i, 6);
                 __syncthreads();
-                if (n <= 2) {
+                if (VEH && vh.model[p] != 0) {
+                    // the vehicle model in place of the ideal tracker (fleet_vehicle.hpp): the record is the state, pos / vel / theta its outputs
+                    double* r = vh.rec + (size_t)p * LTPL_FLEET_SIM_VEH_DOUBLES;
+                    fleet::VehState V{r[VEH_X], r[VEH_Y], r[VEH_C], r[VEH_S], r[VEH_V], r[VEH_A], r[VEH_KAPPA]};
+                    fleet::VehStats st{r[VEH_E], r[VEH_E_MAX], r[VEH_E2_SUM], r[VEH_DV_MAX], r[VEH_CTL], r[VEH_SAT_LAT], r[VEH_SAT_LON]};
+                    sim_vehicle_tick(lane, V, sim_vehicle_params(vh.par + (size_t)p * VEH_PARAMS), fleet::VehRows{ts, tx, ty, tv, ta, n}, sd.dt,
+                                     vh.ctl_steps, st);
+                    pos_x = V.x; pos_y = V.y; vel = V.v; theta = heading_atan2(-V.c, V.s);
+                    if (lane == 0) {
+                        r[VEH_X] = V.x; r[VEH_Y] = V.y; r[VEH_C] = V.c; r[VEH_S] = V.s; r[VEH_V] = V.v; r[VEH_A] = V.a; r[VEH_KAPPA] = V.kappa;
+                        r[VEH_E] = st.e; r[VEH_E_MAX] = st.e_max; r[VEH_E2_SUM] = st.e2_sum; r[VEH_DV_MAX] = st.dv_max; r[VEH_CTL] = st.ctl;
+                        r[VEH_SAT_LAT] = st.sat_lat; r[VEH_SAT_LON] = st.sat_lon;
+                        if (!process_object_dev(lat, 0.2, V.x, V.y, 0.0, 0.0, 0.0).on_track) r[VEH_OFF_TRACK] += 1.0;   // the ingestion's track test
+                    }
+                } else if (n <= 2) {
                     vel = n > 0 ? tv[0] : vel;
                 } else {
                     const double ex = pos_x, ey = pos_y;
@@ -281,11 +337,19 @@ __device__ __forceinline__ void sim_step_body(const FleetArgs& F, const DevLat& 
 }
 __global__ __launch_bounds__(64) void k_fleet_sim_step(FleetArgs F, DevLat lat, SimDev sd, double* trace /* this tick's records or null */)
 {
-    sim_step_body<false>(F, lat, sd, trace, SimNoise{});
+    sim_step_body<false, false>(F, lat, sd, trace, SimNoise{}, SimVeh{});
 }
 __global__ __launch_bounds__(64) void k_fleet_sim_step_noise(FleetArgs F, DevLat lat, SimDev sd, double* trace, SimNoise nz)
 {
-    sim_step_body<true>(F, lat, sd, trace, nz);
+    sim_step_body<true, false>(F, lat, sd, trace, nz, SimVeh{});
+}
+__global__ __launch_bounds__(64) void k_fleet_sim_step_veh(FleetArgs F, DevLat lat, SimDev sd, double* trace, SimVeh vh)
+{
+    sim_step_body<false, true>(F, lat, sd, trace, SimNoise{}, vh);
+}
+__global__ __launch_bounds__(64) void k_fleet_sim_step_noise_veh(FleetArgs F, DevLat lat, SimDev sd, double* trace, SimNoise nz, SimVeh vh)
+{
+    sim_step_body<true, true>(F, lat, sd, trace, nz, vh);
 }
 
 // the planner's mates (every other planner of its race, ascending) as objects at their tracked pose, speed and heading: the ingestion of
@@ -666,6 +730,10 @@ struct FleetSim {
     SimNoise nz{};                          // est_x / est_y / est_v live in `allocs` (ltpl_fleet_sim_setup), g_tx / g_ty in the staging
     bool has_noise = false;                 // the tick launches k_fleet_sim_step_noise / k_fleet_sim_mates_noise and reads pos_est / vel_est from nz.est_*
     int noise_tick0 = 0, noise_tick = 0;    // tick0; ticks of ltpl_fleet_sim_run since the noise was set
+    std::vector<void*> veh_allocs;          // model, parameters and records of ltpl_fleet_sim_vehicle
+    SimVeh vh{};
+    bool has_veh = false;                   // the tick launches k_fleet_sim_step_veh / k_fleet_sim_step_noise_veh
+    std::vector<int> veh_model;             // [N] host copy of vh.model (KEEP_STATE; ltpl_fleet_sim_branch compares models)
 };
 static void sim_free_list(std::vector<void*>& l)
 {
@@ -683,7 +751,7 @@ static void fleet_sim_free(FleetSim* s)
     sim_snaps_free(s->snaps);
     sim_events_free(s->events);
     sim_free_list(s->stage_allocs); sim_free_list(s->race_allocs); sim_free_list(s->tele_allocs); sim_free_list(s->rec_allocs);
-    sim_free_list(s->noise_allocs);
+    sim_free_list(s->noise_allocs); sim_free_list(s->veh_allocs);
     for (void* p : s->allocs) (void)hipFree(p);
     if (s->velt.d_buf) (void)hipFree(s->velt.d_buf);
     delete s;
@@ -891,7 +959,10 @@ try {
         if (s.has_noise) {
             // (the tick advances whether or not a planner is live: a draw depends on the fleet's tick, not on the planner's history)
             s.nz.tick = (uint32_t)s.noise_tick0 + (uint32_t)s.noise_tick++;
-            hipLaunchKernelGGL(k_fleet_sim_step_noise, dim3(N), dim3(64), 0, st, f->args, f->h->lat, s.sd, tr, s.nz);
+            if (s.has_veh) hipLaunchKernelGGL(k_fleet_sim_step_noise_veh, dim3(N), dim3(64), 0, st, f->args, f->h->lat, s.sd, tr, s.nz, s.vh);
+            else hipLaunchKernelGGL(k_fleet_sim_step_noise, dim3(N), dim3(64), 0, st, f->args, f->h->lat, s.sd, tr, s.nz);
+        } else if (s.has_veh) {
+            hipLaunchKernelGGL(k_fleet_sim_step_veh, dim3(N), dim3(64), 0, st, f->args, f->h->lat, s.sd, tr, s.vh);
         } else {
             hipLaunchKernelGGL(k_fleet_sim_step, dim3(N), dim3(64), 0, st, f->args, f->h->lat, s.sd, tr);
         }
@@ -1342,6 +1413,167 @@ try {
     FLEET_TRY(f, hipGetLastError());
     FLEET_TRY(f, hipMemcpyAsync(g, d_g, 8 * m, hipMemcpyDeviceToHost, f->h->stream));
     if (words) FLEET_TRY(f, hipMemcpyAsync(words, d_words, 48 * m, hipMemcpyDeviceToHost, f->h->stream));
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+// ---------------------------------------------------------------------------------------------------------------------
+// vehicle model (ltpl_fleet_sim_vehicle, include/ltpl_hip.h; the model: fleet_vehicle.hpp)
+// ---------------------------------------------------------------------------------------------------------------------
+// every argument is checked before the first HIP call
+static int sim_check_vehicle(ltpl_fleet* f, const ltpl_fleet_sim_vehicle_in* in)
+{
+    const int N = f->D.N;
+    auto bad = [&](const std::string& why) { f->err = "fleet sim vehicle: " + why; return LTPL_ERR_INVALID_ARG; };
+    if (!f->sim) return bad("ltpl_fleet_sim_setup first");
+    if (!in) return LTPL_OK;
+    if (in->flags & ~(uint32_t)LTPL_SIM_VEH_KEEP_STATE) return bad("unknown flag");
+    if (in->ctl_steps < 1) return bad("ctl_steps must be at least 1");
+    if (!in->model) return bad("model missing");
+    const double* a[VEH_PARAMS] = {in->ax_max, in->ay_max, in->grip, in->kappa_max, in->tau_a, in->tau_kappa, in->k_v, in->t_look, in->ld_min};
+    static const char* const name[VEH_PARAMS] = {"ax_max", "ay_max", "grip", "kappa_max", "tau_a", "tau_kappa", "k_v", "t_look", "ld_min"};
+    for (int c = 0; c < VEH_PARAMS; ++c) if (!a[c]) return bad(std::string(name[c]) + " missing");
+    for (int p = 0; p < N; ++p) {
+        if (in->model[p] != 0 && in->model[p] != 1) return bad("planner " + std::to_string(p) + ": model must be 0 or 1");
+        if (in->model[p] == 0) continue;            // (the parameters of a planner on the ideal tracker are not read)
+        for (int c = 0; c < VEH_PARAMS; ++c) {
+            const double v = a[c][p];
+            if (!std::isfinite(v) || !(v > 0.0)) return bad("planner " + std::to_string(p) + ": " + name[c] + " must be finite and positive");
+            if ((c == 4 || c == 5) && v < 0.001) return bad("planner " + std::to_string(p) + ": " + name[c] + " must be at least 0.001 s");
+        }
+    }
+    return LTPL_OK;
+}
+
+extern "C" int ltpl_fleet_sim_vehicle(ltpl_fleet* f, const ltpl_fleet_sim_vehicle_in* in)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    int rc = sim_check_vehicle(f, in);
+    if (rc) return rc;
+    if ((rc = fleet_enter(f))) return rc;
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    FleetSim& s = *f->sim;
+    if (!in) {
+        sim_free_list(s.veh_allocs);
+        s.vh = SimVeh{}; s.has_veh = false; s.veh_model.clear();
+        return LTPL_OK;
+    }
+    const size_t N = (size_t)f->D.N;
+    constexpr size_t RD = LTPL_FLEET_SIM_VEH_DOUBLES;
+    const bool keep = (in->flags & LTPL_SIM_VEH_KEEP_STATE) && s.has_veh;
+    const double* a[VEH_PARAMS] = {in->ax_max, in->ay_max, in->grip, in->kappa_max, in->tau_a, in->tau_kappa, in->k_v, in->t_look, in->ld_min};
+    std::vector<double> par(N * VEH_PARAMS), rec(N * RD, NAN), old, px(N), py(N), pv(N), pt(N);
+    for (size_t p = 0; p < N; ++p) for (int c = 0; c < VEH_PARAMS; ++c) par[p * VEH_PARAMS + c] = a[c][p];
+    FLEET_TRY(f, hipMemcpy(px.data(), s.sd.pos_x, 8 * N, hipMemcpyDeviceToHost));
+    FLEET_TRY(f, hipMemcpy(py.data(), s.sd.pos_y, 8 * N, hipMemcpyDeviceToHost));
+    FLEET_TRY(f, hipMemcpy(pv.data(), s.sd.vel, 8 * N, hipMemcpyDeviceToHost));
+    FLEET_TRY(f, hipMemcpy(pt.data(), s.sd.theta, 8 * N, hipMemcpyDeviceToHost));
+    if (keep) {
+        old.resize(N * RD);
+        FLEET_TRY(f, hipMemcpy(old.data(), s.vh.rec, 8 * N * RD, hipMemcpyDeviceToHost));
+    }
+    for (size_t p = 0; p < N; ++p) {
+        if (in->model[p] == 0) continue;            // NaN: no state, no statistics
+        double* r = rec.data() + p * RD;
+        if (keep && s.veh_model[p] == 1) { std::copy(old.begin() + p * RD, old.begin() + (p + 1) * RD, r); continue; }
+        std::fill(r, r + RD, 0.0);
+        r[VEH_X] = px[p]; r[VEH_Y] = py[p]; r[VEH_C] = -std::sin(pt[p]); r[VEH_S] = std::cos(pt[p]); r[VEH_V] = pv[p];
+    }
+    // everything new is allocated first; the fleet keeps its previous model, state and statistics unless every step succeeds
+    SimAllocs al;
+    int* d_model = nullptr; double* d_par = nullptr; double* d_rec = nullptr;
+    if ((rc = sim_upload(f, al.p, in->model, N, &d_model))) return rc;
+    if ((rc = sim_upload(f, al.p, par.data(), par.size(), &d_par))) return rc;
+    if ((rc = sim_upload(f, al.p, rec.data(), rec.size(), &d_rec))) return rc;
+    sim_free_list(s.veh_allocs);
+    s.veh_allocs.swap(al.p);
+    s.vh = SimVeh{d_model, d_par, d_rec, in->ctl_steps};
+    s.has_veh = true;
+    s.veh_model.assign(in->model, in->model + N);
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+extern "C" int ltpl_fleet_sim_vehicle_read(ltpl_fleet* f, double* out, int32_t doubles_per_planner)
+try {
+    if (!f || !out) return LTPL_ERR_INVALID_ARG;
+    if (!f->sim) { f->err = "fleet sim vehicle: ltpl_fleet_sim_setup first"; return LTPL_ERR_INVALID_ARG; }
+    if (!f->sim->has_veh) { f->err = "fleet sim vehicle: the model is off (ltpl_fleet_sim_vehicle first)"; return LTPL_ERR_INVALID_ARG; }
+    if (doubles_per_planner != LTPL_FLEET_SIM_VEH_DOUBLES) { f->err = "fleet sim vehicle: record size mismatch"; return LTPL_ERR_INVALID_ARG; }
+    FLEET_TRY(f, hipSetDevice(f->h->device));
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    FLEET_TRY(f, hipMemcpy(out, f->sim->vh.rec, sizeof(double) * (size_t)f->D.N * LTPL_FLEET_SIM_VEH_DOUBLES, hipMemcpyDeviceToHost));
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+// the test hook of the model: one wave per case, the device function of the tick (sim_vehicle_tick) on the case's own rows, staged in LDS
+// as the tick stages a trajectory. out: the state after the tick, the tick's statistics (from zero), 1.0 in VEH_OFF_TRACK where the
+// pose fails the ingestion's track test on the fleet's lattice; theta: the library's heading of (s, c)
+__global__ __launch_bounds__(64) void k_fleet_sim_vehicle_step(DevLat lat, const double* state, const double* par, const int* row_off, const double* rows,
+                                                               const double* dt, const int* ctl_steps, double* out, double* theta)
+{
+    const int q = blockIdx.x, lane = threadIdx.x;
+    __shared__ double ts[LTPL_FLEET_SIM_MAX_EXPORT], tx[LTPL_FLEET_SIM_MAX_EXPORT], ty[LTPL_FLEET_SIM_MAX_EXPORT], tv[LTPL_FLEET_SIM_MAX_EXPORT],
+        ta[LTPL_FLEET_SIM_MAX_EXPORT];
+    const int r0 = row_off[q];
+    int n = row_off[q + 1] - r0;
+    if (n > LTPL_FLEET_SIM_MAX_EXPORT) n = LTPL_FLEET_SIM_MAX_EXPORT;      // (refused by the host)
+    for (int i = lane; i < n; i += 64) {
+        const double* r = rows + (size_t)(r0 + i) * 5;
+        ts[i] = r[0]; tx[i] = r[1]; ty[i] = r[2]; tv[i] = r[3]; ta[i] = r[4];
+    }
+    __syncthreads();
+    const double* s0 = state + (size_t)q * 7;
+    fleet::VehState V{s0[0], s0[1], s0[2], s0[3], s0[4], s0[5], s0[6]};
+    fleet::VehStats st{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    sim_vehicle_tick(lane, V, sim_vehicle_params(par + (size_t)q * VEH_PARAMS), fleet::VehRows{ts, tx, ty, tv, ta, n}, dt[q], ctl_steps[q], st);
+    if (lane != 0) return;
+    double* r = out + (size_t)q * LTPL_FLEET_SIM_VEH_DOUBLES;
+    r[VEH_X] = V.x; r[VEH_Y] = V.y; r[VEH_C] = V.c; r[VEH_S] = V.s; r[VEH_V] = V.v; r[VEH_A] = V.a; r[VEH_KAPPA] = V.kappa;
+    r[VEH_E] = st.e; r[VEH_E_MAX] = st.e_max; r[VEH_E2_SUM] = st.e2_sum; r[VEH_DV_MAX] = st.dv_max; r[VEH_CTL] = st.ctl;
+    r[VEH_SAT_LAT] = st.sat_lat; r[VEH_SAT_LON] = st.sat_lon;
+    r[VEH_OFF_TRACK] = process_object_dev(lat, 0.2, V.x, V.y, 0.0, 0.0, 0.0).on_track ? 0.0 : 1.0;
+    theta[q] = heading_atan2(-V.c, V.s);
+}
+
+extern "C" int ltpl_fleet_sim_vehicle_step(ltpl_fleet* f, int32_t n_cases, const double* state, const double* params, const int32_t* row_off,
+                                           const double* rows, const double* dt, const int32_t* ctl_steps, double* out, int32_t doubles_per_case,
+                                           double* theta)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    auto bad = [&](const std::string& why) { f->err = "fleet sim vehicle step: " + why; return LTPL_ERR_INVALID_ARG; };
+    if (n_cases < 0) return bad("n_cases must not be negative");
+    if (n_cases == 0) return LTPL_OK;
+    if (!state || !params || !row_off || !dt || !ctl_steps || !out || !theta) return bad("state / params / row_off / dt / ctl_steps / out / theta missing");
+    if (doubles_per_case != LTPL_FLEET_SIM_VEH_DOUBLES) return bad("record size mismatch");
+    if (row_off[0] != 0) return bad("row offsets must start at 0");
+    for (int q = 0; q < n_cases; ++q) {
+        const int n = row_off[q + 1] - row_off[q];
+        if (n < 0 || n > LTPL_FLEET_SIM_MAX_EXPORT) return bad("case " + std::to_string(q) + ": 0 .. 256 rows");
+        if (!(dt[q] > 0.0) || !(dt[q] <= 1.0)) return bad("case " + std::to_string(q) + ": dt must lie in (0, 1] s");
+        if (ctl_steps[q] < 1) return bad("case " + std::to_string(q) + ": ctl_steps must be at least 1");
+    }
+    const size_t m = (size_t)n_cases, nr = (size_t)row_off[n_cases];
+    if (nr > 0 && !rows) return bad("rows missing");
+    int rc = fleet_enter(f);
+    if (rc) return rc;
+    Arena ar;     // one device block
+    const size_t o_state = ar.add(56 * m), o_par = ar.add(8 * VEH_PARAMS * m), o_rows = ar.add(40 * (nr ? nr : 1)), o_dt = ar.add(8 * m),
+                 o_out = ar.add(8 * LTPL_FLEET_SIM_VEH_DOUBLES * m), o_theta = ar.add(8 * m), o_off = ar.add(4 * (m + 1)), o_ctl = ar.add(4 * m);
+    unsigned char* d = nullptr;
+    struct Guard { void* a = nullptr; ~Guard() { if (a) (void)hipFree(a); } } gd;
+    FLEET_TRY(f, hipMalloc(reinterpret_cast<void**>(&d), ar.size)); gd.a = d;
+    FLEET_TRY(f, hipMemcpy(d + o_state, state, 56 * m, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_par, params, 8 * VEH_PARAMS * m, hipMemcpyHostToDevice));
+    if (nr) FLEET_TRY(f, hipMemcpy(d + o_rows, rows, 40 * nr, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_dt, dt, 8 * m, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_off, row_off, 4 * (m + 1), hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_ctl, ctl_steps, 4 * m, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_fleet_sim_vehicle_step, dim3((unsigned)m), dim3(64), 0, f->h->stream, f->h->lat, (const double*)(d + o_state),
+                       (const double*)(d + o_par), (const int*)(d + o_off), (const double*)(d + o_rows), (const double*)(d + o_dt),
+                       (const int*)(d + o_ctl), reinterpret_cast<double*>(d + o_out), reinterpret_cast<double*>(d + o_theta));
+    FLEET_TRY(f, hipGetLastError());
+    FLEET_TRY(f, hipMemcpyAsync(out, d + o_out, 8 * LTPL_FLEET_SIM_VEH_DOUBLES * m, hipMemcpyDeviceToHost, f->h->stream));
+    FLEET_TRY(f, hipMemcpyAsync(theta, d + o_theta, 8 * m, hipMemcpyDeviceToHost, f->h->stream));
     FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))

@@ -15,6 +15,7 @@ import numpy as np
 from . import _capi
 from .planner import KEY_IDS, KEY_NAMES, PathsView, Planner, PlannerPathsIn, PlannerVelIn, TrajView
 from .sim import TELEMETRY_DOUBLES, TELEMETRY_FIELDS, telemetry_dict      # noqa: F401  (published here: fleet.TELEMETRY_FIELDS)
+from .sim import VEHICLE_DEFAULTS, VEHICLE_DOUBLES, VEHICLE_FIELDS, VEHICLE_PARAMS, vehicle_dict      # noqa: F401  (fleet.VEHICLE_FIELDS)
 from .sim import pack_events as sim_pack_events
 
 
@@ -51,6 +52,10 @@ class SimEventsIn(C.Structure):            # ltpl_fleet_sim_events_in
 class SimNoiseIn(C.Structure):             # ltpl_fleet_sim_noise_in
     _fields_ = [("seed", C.c_void_p), ("sigma_pos", C.c_void_p), ("sigma_vel", C.c_void_p), ("sigma_obj_pos", C.c_void_p),
                 ("sigma_obj_theta", C.c_void_p), ("sigma_obj_vel", C.c_void_p), ("tick0", C.c_int32)]
+
+
+class SimVehicleIn(C.Structure):           # ltpl_fleet_sim_vehicle_in
+    _fields_ = [("model", C.c_void_p)] + [(k, C.c_void_p) for k in VEHICLE_PARAMS] + [("ctl_steps", C.c_int32), ("flags", C.c_uint32)]
 
 
 class SimRecordHead(C.Structure):         # ltpl_fleet_sim_record_head
@@ -107,6 +112,10 @@ class Fleet(Planner):
             f("sim_noise").argtypes = [C.c_void_p, C.POINTER(SimNoiseIn)]
             f("sim_estimate").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             f("sim_noise_draws").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        if hasattr(self.lib, "ltpl_fleet_sim_vehicle"):
+            f("sim_vehicle").argtypes = [C.c_void_p, C.POINTER(SimVehicleIn)]
+            f("sim_vehicle_read").argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+            f("sim_vehicle_step").argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 7 + [C.c_int32, C.c_void_p]
         if hasattr(self.lib, "ltpl_fleet_friction"):
             f("friction").argtypes = [C.c_void_p, C.POINTER(FrictionIn)]
             f("friction_scale").argtypes = [C.c_void_p, C.c_void_p]
@@ -624,6 +633,58 @@ class Fleet(Planner):
         self._check(self._fn("sim_noise_draws")(self.handle, sd.ctypes.data, tk.ctypes.data, ob.ctypes.data, cp.ctypes.data, n, g.ctypes.data,
                                                 None if w is None else w.ctypes.data))
         return (g, w[:n]) if words else g
+
+    # ---- vehicle model on the device ------------------------------------------------------------------------------------------------
+    def sim_vehicle(self, model=1, keep_state=False, **params):
+        """A car between the planned trajectory and the pose of the next tick (ltpl_fleet_sim_vehicle; after ``sim_setup`` -- and after
+        ``sim_race`` where its heading0 matters --, between runs at any time). ``model``: 0 the ideal tracker, 1 the vehicle model (scalar
+        or one per planner; None switches the model off); ``params``: keywords of ``sim.VEHICLE_DEFAULTS`` (scalars or one per planner;
+        ``ctl_steps``: one integer). The state of every planner with model 1 starts from its present true pose, speed and heading with
+        a = kappa = 0 and cleared statistics; ``keep_state=True``: planners that already drove the model keep state and statistics and
+        only the parameters change (a grip that drops between two runs). Host mirror: ``sim.VehicleModel``."""
+        if model is None:
+            self._check(self._fn("sim_vehicle")(self.handle, None))
+            return
+        unknown = set(params) - set(VEHICLE_DEFAULTS)
+        if unknown:
+            raise TypeError("sim_vehicle: unknown parameter(s) %s" % sorted(unknown))
+        par = dict(VEHICLE_DEFAULTS, **params)
+        n = self.n_scen
+        vi = SimVehicleIn()
+        keep = [np.ascontiguousarray(np.broadcast_to(np.asarray(model, np.int32), (n,)))]
+        vi.model, vi.ctl_steps, vi.flags = keep[0].ctypes.data, int(par["ctl_steps"]), 1 if keep_state else 0
+        for name in VEHICLE_PARAMS:
+            keep.append(np.ascontiguousarray(np.broadcast_to(np.asarray(par[name], np.float64), (n,))))
+            setattr(vi, name, keep[-1].ctypes.data)
+        self._check(self._fn("sim_vehicle")(self.handle, C.byref(vi)))
+
+    def sim_vehicle_read(self, raw=False):
+        """dict of named arrays (``sim.VEHICLE_FIELDS``): state x, y, c, s, v, a, kappa and statistics e, e_max, e2_sum, dv_max, ctl_steps,
+        sat_lat, sat_lon, off_track_ticks of every planner (ltpl_fleet_sim_vehicle_read). A planner on the ideal tracker holds NaN (its
+        counters read -1). ``raw=True``: the [n, 15] records."""
+        out = np.zeros((self.n_scen, VEHICLE_DOUBLES), np.float64)
+        self._check(self._fn("sim_vehicle_read")(self.handle, out.ctypes.data, VEHICLE_DOUBLES))
+        return out if raw else vehicle_dict(out)
+
+    def sim_vehicle_step(self, state, params, rows, dt, ctl_steps):
+        """The model's test hook (ltpl_fleet_sim_vehicle_step): one tick of independent cases on the device, one wave each. ``state``
+        [m, 7]; ``params`` [m, 9] in the order of ``sim.VEHICLE_PARAMS``; ``rows``: a list of m arrays [n_q, 5] = s, x, y, vx, ax
+        (0 .. 256 rows); ``dt``, ``ctl_steps``: scalars or one per case. Returns (records [m, 15]: the state after the tick and the
+        tick's statistics, theta [m]); equals ``sim.VehicleModel.tick`` bit for bit."""
+        state = np.ascontiguousarray(np.asarray(state, np.float64).reshape(-1, 7))
+        m = state.shape[0]
+        params = np.ascontiguousarray(np.broadcast_to(np.asarray(params, np.float64), (m, len(VEHICLE_PARAMS))))
+        rows = [np.asarray(r, np.float64).reshape(-1, 5) for r in rows]
+        if len(rows) != m:
+            raise ValueError("sim_vehicle_step: one row table per case expected")
+        off = np.ascontiguousarray(np.concatenate(([0], np.cumsum([r.shape[0] for r in rows]))).astype(np.int32))
+        flat = np.ascontiguousarray(np.concatenate(rows + [np.zeros((1, 5))]))
+        dts = np.ascontiguousarray(np.broadcast_to(np.asarray(dt, np.float64), (m,)))
+        ctl = np.ascontiguousarray(np.broadcast_to(np.asarray(ctl_steps, np.int32), (m,)))
+        out, theta = np.zeros((max(m, 1), VEHICLE_DOUBLES), np.float64), np.zeros(max(m, 1), np.float64)
+        self._check(self._fn("sim_vehicle_step")(self.handle, m, state.ctypes.data, params.ctypes.data, off.ctypes.data, flat.ctypes.data,
+                                                 dts.ctypes.data, ctl.ctypes.data, out.ctypes.data, VEHICLE_DOUBLES, theta.ctypes.data))
+        return out[:m], theta[:m]
 
     # ---- friction maps on the device ------------------------------------------------------------------------------------------------
     def friction(self, maps, map_idx=None, scale=1.0):

@@ -25,6 +25,12 @@ and of the seeded sensor noise of ``ltpl_fleet_sim_noise`` (csrc/fleet_noise.hpp
   ``noise_gauss``    the noise sample g(seed, tick, obj, comp): integer arithmetic and exact fp64 steps, so the device's bits;
   ``NoiseModel``     what a planner perceives of itself, of its objects and of its mates, in the operation order of the kernels.
 
+and of the vehicle model of ``ltpl_fleet_sim_vehicle`` (csrc/fleet_vehicle.hpp) --
+
+  ``VehicleModel``   a kinematic single-track car with actuator lags, a friction circle and a pure-pursuit / speed controller in place
+                     of the ideal tracker: + - * / sqrt on Python floats in the operation order of the kernels, so the device's bits;
+  ``VEHICLE_DEFAULTS`` / ``VEHICLE_FIELDS`` / ``vehicle_dict``   its parameters and the record of ``Fleet.sim_vehicle_read``.
+
 Both simulators restate ``np.interp`` (numpy's ``arr_interp``) in the operation order of the device functions (``interp_at`` here,
 ``fleet::sim_interp`` there), so that host and device give the same bits as the reference.
 """
@@ -559,3 +565,185 @@ class NoiseModel(object):
         if len(objs) != len(rows):
             raise ValueError("NoiseModel.mates: one row per mate expected")
         return self._rows(p, tick, rows, objs)
+
+
+# ---- vehicle model (ltpl_fleet_sim_vehicle, include/ltpl_hip.h; csrc/fleet_vehicle.hpp) ---------------------------------------------------
+# name, index, integer valued: the record of ltpl_fleet_sim_vehicle_read (LTPL_FLEET_SIM_VEH_DOUBLES = 15 per planner)
+VEHICLE_FIELDS = (("x", 0, False), ("y", 1, False), ("c", 2, False), ("s", 3, False), ("v", 4, False), ("a", 5, False), ("kappa", 6, False),
+                  ("e", 7, False), ("e_max", 8, False), ("e2_sum", 9, False), ("dv_max", 10, False), ("ctl_steps", 11, True),
+                  ("sat_lat", 12, True), ("sat_lon", 13, True), ("off_track_ticks", 14, True))
+VEHICLE_DOUBLES = 15
+VEHICLE_PARAMS = ("ax_max", "ay_max", "grip", "kappa_max", "tau_a", "tau_kappa", "k_v", "t_look", "ld_min")
+# A car with 20 % headroom over a planner that plans on a gg of 5 m/s^2 (the stock local_gg): with less it saturates and runs wide
+VEHICLE_DEFAULTS = dict(ax_max=6.0, ay_max=6.0, grip=1.0, kappa_max=0.2, tau_a=0.1, tau_kappa=0.08, k_v=1.0, t_look=0.3, ld_min=4.0,
+                        ctl_steps=10)
+VEH_STEP = 0.001
+
+
+def vehicle_dict(rows):
+    """[n, 15] records as a dict of named arrays (counters as int64; planners on the ideal tracker hold NaN and read -1 there)."""
+    rows = np.asarray(rows, np.float64).reshape(-1, VEHICLE_DOUBLES)
+    return {name: (np.where(np.isnan(rows[:, i]), -1.0, rows[:, i]).astype(np.int64) if is_int else rows[:, i].copy())
+            for name, i, is_int in VEHICLE_FIELDS}
+
+
+def _veh_interp(x, xp, fp, n):
+    return x if math.isnan(x) else interp_at(x, xp, fp, segment(x, xp))
+
+
+class VehicleModel(object):
+    """Scalar host mirror of one planner's vehicle model in the operation order of csrc/fleet_vehicle.hpp (veh_tick): plain Python
+    floats, + - * / sqrt only, so the device's bits. ``tick(traj_rows, dt)`` advances the car along a trajectory; ``stats`` are the
+    accumulated statistics of ltpl_fleet_sim_vehicle_read. Parameters: ``VEHICLE_DEFAULTS``. (c, s) is the unit vector of the direction
+    of travel; ``theta`` is the project's heading, measured from the y axis (the direction of travel is (-sin theta, cos theta), as in
+    the psi column of a trajectory): c = -sin theta, s = cos theta, theta = atan2(-c, s)."""
+
+    def __init__(self, x, y, theta, v, **params):
+        par = dict(VEHICLE_DEFAULTS, **params)
+        unknown = set(par) - set(VEHICLE_DEFAULTS)
+        if unknown:
+            raise TypeError("VehicleModel: unknown parameter(s) %s" % sorted(unknown))
+        self.ctl_steps = int(par.pop("ctl_steps"))
+        self.par = {k: float(par[k]) for k in VEHICLE_PARAMS}
+        self.x, self.y, self.c, self.s, self.v, self.a, self.kappa = float(x), float(y), -math.sin(theta), math.cos(theta), float(v), 0.0, 0.0
+        self.stats = dict(e=0.0, e_max=0.0, e2_sum=0.0, dv_max=0.0, ctl_steps=0, sat_lat=0, sat_lon=0, off_track_ticks=0)
+
+    @property
+    def theta(self):
+        return math.atan2(-self.c, self.s)
+
+    def state(self):
+        return [self.x, self.y, self.c, self.s, self.v, self.a, self.kappa]
+
+    def set_state(self, state, stats=None):
+        self.x, self.y, self.c, self.s, self.v, self.a, self.kappa = (float(q) for q in state)
+        if stats is not None:
+            st = self.stats
+            st["e"], st["e_max"], st["e2_sum"], st["dv_max"] = (float(q) for q in stats[:4])
+            st["ctl_steps"], st["sat_lat"], st["sat_lon"], st["off_track_ticks"] = (int(q) for q in stats[4:8])
+
+    def record(self):
+        """The planner's record of ltpl_fleet_sim_vehicle_read (VEHICLE_FIELDS)."""
+        st = self.stats
+        return self.state() + [st["e"], st["e_max"], st["e2_sum"], st["dv_max"], float(st["ctl_steps"]), float(st["sat_lat"]),
+                               float(st["sat_lon"]), float(st["off_track_ticks"])]
+
+    @staticmethod
+    def columns(traj_rows):
+        """(s, x, y, vx, ax) as Python lists from rows [s, x, y, vx, ax] or trajectory rows [s, x, y, psi, kappa, vx, ax]."""
+        a = np.asarray(traj_rows, np.float64)
+        a = a.reshape(-1, 5) if a.size == 0 else a
+        cols = (0, 1, 2, 5, 6) if a.shape[1] == 7 else (0, 1, 2, 3, 4)
+        return tuple(a[:, k].tolist() for k in cols)
+
+    @staticmethod
+    def _seg(tx, ty, i, px, py):
+        dx, dy = tx[i + 1] - tx[i], ty[i + 1] - ty[i]
+        l2 = dx * dx + dy * dy
+        if not l2 > 0.0:
+            return None
+        u = ((px - tx[i]) * dx + (py - ty[i]) * dy) / l2
+        if u < 0.0:
+            u = 0.0
+        if u > 1.0:
+            u = 1.0
+        fx, fy = tx[i] + u * dx, ty[i] + u * dy
+        ex, ey = px - fx, py - fy
+        return ex * ex + ey * ey, u, dx, dy, l2
+
+    def control(self, cols):
+        """One control step at the present state -> (kappa_cmd, a_cmd)."""
+        ts, tx, ty, tv, ta = cols
+        P, st, n = self.par, self.stats, len(ts)
+        ax_lim, ay_lim = P["ax_max"] * P["grip"], P["ay_max"] * P["grip"]
+        px, py = self.x, self.y
+        best, bd = None, math.inf
+        if n > 2:
+            for i in range(n - 1):
+                r = self._seg(tx, ty, i, px, py)
+                if r is not None and (r[0] < bd or (best is None and r[0] == bd)):       # (ties: the lower i stays; a NaN never wins)
+                    best, bd = (i, r), r[0]
+        if best is None:
+            return self.kappa, -ax_lim
+        i, (_, u, dx, dy, l2) = best
+        e = (dx * (py - ty[i]) - dy * (px - tx[i])) / math.sqrt(l2)
+        sf = ts[i] + u * (ts[i + 1] - ts[i])
+        vref, aff = _veh_interp(sf, ts, tv, n), _veh_interp(sf, ts, ta, n)
+        tl = P["t_look"] * self.v
+        ld = tl if tl > P["ld_min"] else P["ld_min"]
+        sl = sf + ld
+        gx, gy = _veh_interp(sl, ts, tx, n), _veh_interp(sl, ts, ty, n)
+        if sl > ts[n - 1]:
+            for k in range(n - 2, -1, -1):
+                ex, ey = tx[k + 1] - tx[k], ty[k + 1] - ty[k]
+                m2 = ex * ex + ey * ey
+                if m2 > 0.0:
+                    m, over = math.sqrt(m2), sl - ts[n - 1]
+                    gx += over * (ex / m)
+                    gy += over * (ey / m)
+                    break
+        rx, ry = gx - px, gy - py
+        yl = -self.s * rx + self.c * ry
+        l2r = rx * rx + ry * ry
+        kc = (2.0 * yl) / l2r if l2r > 0.0 else 0.0
+        if kc > P["kappa_max"]:
+            kc = P["kappa_max"]
+        if kc < -P["kappa_max"]:
+            kc = -P["kappa_max"]
+        v2 = self.v * self.v
+        if abs(kc) * v2 > ay_lim:
+            kc = math.copysign(ay_lim / v2, kc)
+            st["sat_lat"] += 1
+        q = (kc * v2) / ay_lim
+        w = 1.0 - q * q
+        rem = ax_lim * math.sqrt(w if w > 0.0 else 0.0)
+        dv = vref - self.v
+        ac = aff + P["k_v"] * dv
+        if ac > rem:
+            ac = rem
+            st["sat_lon"] += 1
+        elif ac < -rem:
+            ac = -rem
+            st["sat_lon"] += 1
+        st["e"] = e
+        if abs(e) > st["e_max"]:
+            st["e_max"] = abs(e)
+        st["e2_sum"] += e * e
+        if abs(dv) > st["dv_max"]:
+            st["dv_max"] = abs(dv)
+        st["ctl_steps"] += 1
+        return kc, ac
+
+    def plant(self, kappa_cmd, a_cmd):
+        """One 1 ms plant step."""
+        P, h = self.par, VEH_STEP
+        self.a += (a_cmd - self.a) * (h / P["tau_a"])
+        self.kappa += (kappa_cmd - self.kappa) * (h / P["tau_kappa"])
+        self.v += self.a * h
+        if self.v < 0.0:
+            self.v = 0.0
+        ds = self.v * h
+        t = 0.5 * self.kappa * ds
+        tt, t2 = t * t, 2.0 * t
+        cn, sn = ((1.0 - tt) * self.c - t2 * self.s) / (1.0 + tt), ((1.0 - tt) * self.s + t2 * self.c) / (1.0 + tt)
+        self.x += ds * (0.5 * (self.c + cn))
+        self.y += ds * (0.5 * (self.s + sn))
+        self.c, self.s = cn, sn
+
+    def tick(self, traj_rows, dt, on_track=None):
+        """One tick of ``dt`` on ``traj_rows`` (``columns``); ``on_track(x, y)`` (optional): the track test of the pose at the end of the
+        tick, counted in ``stats['off_track_ticks']``. Returns ([x, y], v, theta)."""
+        cols = traj_rows if isinstance(traj_rows, tuple) else self.columns(traj_rows)
+        t, k = 0.0, 0
+        cmd = (self.kappa, 0.0)
+        while t < dt:
+            if k % self.ctl_steps == 0:
+                cmd = self.control(cols)
+            self.plant(*cmd)
+            t += VEH_STEP
+            k += 1
+        r = math.sqrt(self.c * self.c + self.s * self.s)
+        self.c, self.s = self.c / r, self.s / r
+        if on_track is not None and not on_track(self.x, self.y):
+            self.stats["off_track_ticks"] += 1
+        return [self.x, self.y], self.v, self.theta

@@ -61,7 +61,8 @@ extern "C" {
                                      v9 (round 6, additive): ltpl_create_ex, ltpl_tick_persistent_stop / _stats;
                                      additive to v9: ltpl_fleet_sim_race / _heading, ltpl_fleet_friction / _scale / _rows,
                                      ltpl_fleet_sim_snapshot / _snapshot_info / _snapshot_drop / _branch,
-                                     ltpl_fleet_sim_noise / _estimate / _noise_draws */
+                                     ltpl_fleet_sim_noise / _estimate / _noise_draws,
+                                     ltpl_fleet_sim_vehicle / _vehicle_read / _vehicle_step */
 
 /* status codes */
 #define LTPL_OK               0
@@ -1076,6 +1077,79 @@ int ltpl_fleet_sim_estimate(ltpl_fleet* fleet, double* x, double* y, double* v);
  * NULL): [n][12] the output words of the three blocks. Needs a fleet, no simulation. */
 int ltpl_fleet_sim_noise_draws(ltpl_fleet* fleet, const uint64_t* seed, const uint32_t* tick, const uint32_t* obj, const uint32_t* comp, int32_t n,
                                double* g, uint32_t* words);
+
+/* ------------------------------------------------------------------------------------------------------------------------------------------
+ * Additive to ABI v9 -- VEHICLE MODEL: a car between the planned trajectory and the pose of the next tick, integrated on the device inside
+ * ltpl_fleet_sim_run (csrc/fleet_sim.hpp: k_fleet_sim_step_veh, k_fleet_sim_step_noise_veh; the model: csrc/fleet_vehicle.hpp). Without it
+ * step 5 of a tick is the ideal tracker: the car is put ONTO its previous trajectory at exactly the planned speed. A planner with model 1
+ * drives a kinematic single-track car with actuator lags, a friction circle of its TRUE grip and a pure-pursuit / speed controller over the
+ * same trimmed rows of the previous trajectory of the selected action (columns s, x, y, vx and ax). Before the first trajectory nothing
+ * moves, as with the ideal tracker.
+ * ARITHMETIC: fp64, + - * / sqrt only, one fixed order (the library is built with -ffp-contract=off): the host mirror sim.VehicleModel and
+ * the device agree to the last bit. The heading is carried as a unit vector (c, s), never as an angle: the direction of travel. The
+ * library's headings (heading0, the psi column, ltpl_fleet_sim_heading) are measured from the y axis -- the direction of travel of a
+ * heading theta is (-sin theta, cos theta) -- so c = -sin theta, s = cos theta and theta = atan2(-c, s).
+ * STATE per planner: x, y, c, s, v, a, kappa.  A TICK: t = 0; k = 0; while (t < dt) { if (k % ctl_steps == 0) control; plant; t += 0.001; ++k; }
+ * CONTROL at the pose p = (x, y):
+ *   1 projection  every segment i = 0 .. n - 2 of the rows with l2 = dx dx + dy dy > 0: u = ((px - x_i) dx + (py - y_i) dy) / l2 clamped to
+ *                 [0, 1], foot f = (x_i + u dx, y_i + u dy), d2 = |p - f|^2. The smallest d2 wins, ties to the lower i. On the winner
+ *                 e = (dx (py - y_i) - dy (px - x_i)) / sqrt(l2) (positive: left of the trajectory), sf = s_i + u (s_{i+1} - s_i)
+ *   2 references  vref, aff = np.interp of vx, ax at sf
+ *   3 look-ahead  Ld = max(ld_min, t_look v), st = sf + Ld, target = np.interp of x, y at st (clamped at the last row); where
+ *                 st > s_{n-1}: target += (st - s_{n-1}) (dx / sqrt(l2), dy / sqrt(l2)) of the last segment with l2 > 0
+ *   4 curvature   r = target - p, yl = -s r_x + c r_y, L2 = r_x r_x + r_y r_y; kappa_cmd = L2 > 0 ? (2 yl) / L2 : 0, clamped to +-kappa_max
+ *   5 friction    ay_lim = ay_max grip, ax_lim = ax_max grip, v2 = v v. |kappa_cmd| v2 > ay_lim: kappa_cmd = copysign(ay_lim / v2, kappa_cmd)
+ *                 and sat_lat counts. q = (kappa_cmd v2) / ay_lim, rem = ax_lim sqrt(max(0, 1 - q q)); a_cmd = aff + k_v (vref - v),
+ *                 clamped to +-rem; sat_lon counts where it was clamped
+ *   6 statistics  e, e_max = max |e|, e2_sum += e e, dv_max = max |vref - v|, ctl += 1
+ *   no usable trajectory (n <= 2, or no segment with l2 > 0): kappa_cmd = kappa (the steering is held), a_cmd = -ax_lim, and no statistic
+ *   of 5 and 6 changes: ctl counts the control steps that had a trajectory
+ * PLANT, h = 0.001: a += (a_cmd - a) (h / tau_a); kappa += (kappa_cmd - kappa) (h / tau_kappa); v += a h, a negative v becomes 0; ds = v h;
+ *   t = 0.5 kappa ds; c' = ((1 - t t) c - (2 t) s) / (1 + t t); s' = ((1 - t t) s + (2 t) c) / (1 + t t); x += ds (0.5 (c + c'));
+ *   y += ds (0.5 (s + s')); (c, s) = (c', s'). With kappa and v constant the car stays on the circle of radius 1 / kappa up to rounding.
+ * END OF TICK: (c, s) divided by sqrt(c c + s s); pos = (x, y), vel = v, and the heading from the library's device atan2 of (-c, s)
+ * (an output only: it never feeds the state; within 1e-12 of atan2). Everything downstream reads these unchanged: the mates, the noise
+ * estimates (noise is added to the model's true pose), telemetry, the events' conditions, the recorder's head and the trace.
+ * off_track_ticks counts the ticks in which the model ran and the pose at the end fails the track test of the object ingestion.
+ * SNAPSHOT / BRANCH: state and statistics are written by the tick and travel with the planner; model and parameters stay the
+ * destination's own. A destination on the ideal tracker takes no vehicle record (its own stays NaN); a destination with model 1 needs a
+ * source that had model 1 when it was copied -- otherwise LTPL_ERR_INVALID_ARG.
+ * THE CALL: after ltpl_fleet_sim_setup (which switches the model off; after ltpl_fleet_sim_race where heading0 matters) at any time between
+ * runs; in == NULL switches it off: the tick then launches the kernels it launched before. Every argument is checked before the first HIP
+ * call; the message names the planner and the field: model 0 or 1; for a planner with model 1 every parameter finite and positive, tau_a
+ * and tau_kappa at least 0.001 s (the parameters of a planner with model 0 are not read); ctl_steps >= 1; no unknown flag. Everything new
+ * is allocated before anything old is freed: a failing call keeps what was set. On success the state of every planner with model 1 is
+ * its current true pose, speed and heading ((c, s) = host -sin / cos of the heading), a = kappa = 0, statistics cleared. With
+ * LTPL_SIM_VEH_KEEP_STATE the planners that already had model 1 keep state and statistics and only the parameters change ("the grip
+ * drops at tick 300" is two runs with such a call between them).
+ * ------------------------------------------------------------------------------------------------------------------------------------------ */
+#define LTPL_FLEET_SIM_VEH_DOUBLES 15   /* x, y, c, s, v, a, kappa, e (last), e_max, e2_sum, dv_max, ctl, sat_lat, sat_lon, off_track_ticks */
+#define LTPL_SIM_VEH_KEEP_STATE 1u
+typedef struct {
+    const int32_t* model;            /* [n] 0: the ideal tracker, 1: the vehicle model */
+    const double* ax_max;            /* [n] m/s^2 (every array is needed)              */
+    const double* ay_max;            /* [n] m/s^2                                      */
+    const double* grip;              /* [n] true grip factor on both limits            */
+    const double* kappa_max;         /* [n] 1/m                                        */
+    const double* tau_a;             /* [n] s, >= 0.001                                */
+    const double* tau_kappa;         /* [n] s, >= 0.001                                */
+    const double* k_v;               /* [n] 1/s                                        */
+    const double* t_look;            /* [n] s                                          */
+    const double* ld_min;            /* [n] m                                          */
+    int32_t ctl_steps;               /* >= 1: control period in 1 ms plant steps       */
+    uint32_t flags;                  /* LTPL_SIM_VEH_KEEP_STATE                         */
+} ltpl_fleet_sim_vehicle_in;
+int ltpl_fleet_sim_vehicle(ltpl_fleet* fleet, const ltpl_fleet_sim_vehicle_in* in);
+/* out: [n][LTPL_FLEET_SIM_VEH_DOUBLES]; every double of a planner on the ideal tracker is NaN. No simulation, the model off or a wrong
+ * record size: LTPL_ERR_INVALID_ARG. */
+int ltpl_fleet_sim_vehicle_read(ltpl_fleet* fleet, double* out, int32_t doubles_per_planner);
+/* the test hook of the model (k_fleet_sim_vehicle_step, one wave per case, the tick's own device function): case q has the state
+ * state[q][7], the parameters params[q][9] (the order of the struct above), the rows rows[row_off[q] .. row_off[q + 1])[5] = s, x, y, vx,
+ * ax (0 .. 256 of them), dt[q] in (0, 1] and ctl_steps[q] >= 1. out[q]: the state after the tick, the tick's statistics from zero, and
+ * 1.0 as off_track_ticks where the pose fails the track test on the fleet's lattice; theta[q]: the heading. Needs a fleet, no simulation. */
+int ltpl_fleet_sim_vehicle_step(ltpl_fleet* fleet, int32_t n_cases, const double* state, const double* params, const int32_t* row_off,
+                                const double* rows, const double* dt, const int32_t* ctl_steps, double* out, int32_t doubles_per_case,
+                                double* theta);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,7 @@
 """Closed-loop SIMULATION rate of a fleet (ltpl_fleet_sim_*): N planners, each with its own eight C2-style race-line opponents (SURVEY.md
 section 8d: s0_k = 250 + 280 k, vel_scale_k = 0.30 + 0.05 (k mod 4), here staggered by 10 m (p mod 16) per planner), run the example
 driver's loop on the device for T ticks without host work per tick.   tools/sim_rate.py [--planners 32768] [--ticks 200] [--no-tape]
-[--race-size K] [--friction-map] [--telemetry] [--record M [--record-depth D]] [--events] [--noise] [--lib PATH]. Prints planner-ticks per second of sim_run (device time of the run) next to tape_run on the C2 tape (recorded inputs,
+[--race-size K] [--friction-map] [--telemetry] [--record M [--record-depth D]] [--events] [--noise] [--vehicle] [--lib PATH]. Prints planner-ticks per second of sim_run (device time of the run) next to tape_run on the C2 tape (recorded inputs,
 tools/fleet_rate.py). --race-size K > 1: races of K consecutive planners (ltpl_fleet_sim_race) that see one another, started 30 m apart
 along the race line with its heading; K = 1 (default) is the run without races. --friction-map: the same fleet on the friction grid of
 tests/golden/friction_grid.npz (ltpl_fleet_friction: rows evaluated on the device, grip factors 1.0 .. 0.7 over the planners) instead of
@@ -15,7 +15,10 @@ below it, and the opponent drives away: theirs never fires) with a chained "afte
 k_fleet_sim_events_timed in the ticks that hold a timed event; the fired events are counted after the run. --noise: seeded sensor noise on
 (ltpl_fleet_sim_noise) with all five sigmas set (pos 0.1 m, vel 0.2 m/s, obj_pos 0.3 m, obj_theta 0.02 rad, obj_vel 0.5 m/s) and a seed per
 planner: k_fleet_sim_step_noise (and k_fleet_sim_mates_noise with races) in place of the plain kernels; the largest distance between
-estimate and true pose is printed after the run. --lib PATH: another build of
+estimate and true pose is printed after the run. --vehicle: every planner drives the vehicle model (ltpl_fleet_sim_vehicle,
+sim.VEHICLE_DEFAULTS: k_fleet_sim_step_veh, or k_fleet_sim_step_noise_veh with --noise, in place of the step kernel); without races the
+planners are put into races of one, which hands the start heading to the simulation; the tracking statistics are printed after the run.
+--lib PATH: another build of
 the library (A/B against the parent's)."""
 import argparse
 import os
@@ -46,6 +49,7 @@ def main():
     ap.add_argument("--record-depth", type=int, default=0, help="ring depth of the recorder (default: --ticks)")
     ap.add_argument("--events", action="store_true", help="scripted events on: a timed gg_scale event and an opp_within trigger with a chained after per planner")
     ap.add_argument("--noise", action="store_true", help="seeded sensor noise on, all five sigmas set, a seed per planner")
+    ap.add_argument("--vehicle", action="store_true", help="every planner drives the vehicle model (sim.VEHICLE_DEFAULTS) instead of the ideal tracker")
     ap.add_argument("--lib", default=None, help="path of the library to load (default: the in-tree build)")
     a = ap.parse_args()
     lat = Lattice.load(os.path.join(ROOT, "tests", "golden", "monteblanco_lattice.npz"))
@@ -82,6 +86,8 @@ def main():
         fleet.sim_setup(race, entries)
         if K > 1:
             fleet.sim_race(sizes)
+        elif a.vehicle:
+            fleet.sim_race([1] * n)
         if grid is not None:
             fleet.friction(grid, scale=1.0 - 0.3 * (np.arange(n) % 16) / 15.0)
         fleet.sim_vel(vel_max=va['vel_max'], gg_scale=va['gg_scale'], local_gg=tuple(va['local_gg']), safety_d=va['safety_d'],
@@ -99,6 +105,8 @@ def main():
             fleet.sim_events(ev)
         if a.noise:
             fleet.sim_noise(seed=np.arange(n, dtype=np.uint64) + np.uint64(1), pos=0.1, vel=0.2, obj_pos=0.3, obj_theta=0.02, obj_vel=0.5)
+        if a.vehicle:
+            fleet.sim_vehicle(model=1)
         t0 = time.perf_counter()
         failed = 0
         try:
@@ -118,6 +126,11 @@ def main():
             est, tru = fleet.sim_estimate(), fleet.sim_state()
             print("  noise: estimate up to %.3f m and %.3f m/s off the true state in the last tick" % (
                 np.max(np.hypot(*(est["pos_est"] - tru["pos_est"]).T)), np.max(np.abs(est["vel_est"] - tru["vel_est"]))))
+        if a.vehicle:
+            d = fleet.sim_vehicle_read()
+            print("  vehicle: e_max up to %.3f m, rms e up to %.3f m, dv_max up to %.2f m/s, %d lateral and %d longitudinal saturations in %d control "
+                  "steps, %d planners left the track" % (np.max(d["e_max"]), np.sqrt(np.max(d["e2_sum"] / np.maximum(d["ctl_steps"], 1))), np.max(d["dv_max"]),
+                                                         d["sat_lat"].sum(), d["sat_lon"].sum(), d["ctl_steps"].sum(), np.count_nonzero(d["off_track_ticks"])))
         if a.events:
             ft = fleet.sim_events_read()["fired_tick"].reshape(n, 3)
             print("  events: %d timed, %d opp_within and %d chained 'after' events fired of %d each (schedule tick %d)" % (
