@@ -22,6 +22,11 @@
 //   k_fleet_sim_rank     (telemetry on and races with more than one planner) one wave64 per planner, one lane per mate: rank by ballot /
 //                        popcount over every mate's progress of this tick, gap to the nearest car ahead by a wave minimum. Its own
 //                        launch: every planner's progress of the tick is written first
+//   k_fleet_sim_sense    (sensor model set only: ltpl_fleet_sim_sensor; the rule: fleet_sensor.hpp) one wave64 per planner: the geometry of
+//                        the tick's on-track objects at their TRUE positions staged in LDS, one lane per object (two passes above 64)
+//                        through range, near field, cone, occlusion (every lane walks the same LDS entry: a broadcast) and dropout;
+//                        the staged arrays ballot-compacted in place, sd.cnt and trace [5] .. [7] rewritten, lane 0 updates the
+//                        planner's 10-double record. Behind telemetry, which measured against the complete list
 //   k_fleet_sim_offsets  exclusive scan of the on-track counts -> veh_off (one workgroup)
 //   k_fleet_sim_compact  survivors into the fleet's object layout (one lane per planner)
 //   k_fleet_sim_rec_paths / k_fleet_sim_rec_vel   (flight recorder on only: ltpl_fleet_sim_record) one wave64 per RECORDED planner: the
@@ -33,6 +38,7 @@
 #pragma once
 
 #include "fleet_noise.hpp"
+#include "fleet_sensor.hpp"
 #include "fleet_vehicle.hpp"
 
 namespace fleet {
@@ -521,6 +527,120 @@ __global__ __launch_bounds__(64) void k_fleet_sim_rank(SimDev sd, SimTele te)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// sensor model (ltpl_fleet_sim_sensor, include/ltpl_hip.h; the rule: fleet_sensor.hpp; host mirror: sim.SensorModel). A pure function of
+// the tick's true state: configuration and a statistics record, no state. The pointers live in a struct of their own: no other kernel
+// carries them.
+// ---------------------------------------------------------------------------------------------------------------------
+#define SENS_PARAMS 5                      // fleet::SensorParams
+enum { SENS_TICKS = 0, SENS_N_OBJ, SENS_N_SEEN, SENS_N_RANGE, SENS_N_FOV, SENS_N_OCCL, SENS_N_DROP, SENS_BLIND_TICKS, SENS_CLEAR_MIN, SENS_CLEAR_TICK };
+static_assert(SENS_CLEAR_TICK + 1 == LTPL_FLEET_SIM_SENSOR_DOUBLES && sizeof(fleet::SensorParams) == SENS_PARAMS * sizeof(double) &&
+              SENS_N_RANGE + fleet::kSenseDrop - fleet::kSenseRange == SENS_N_DROP, "sensor record layout");
+struct SimSense {
+    const double* par;                     // [N][SENS_PARAMS] in the order of fleet::SensorParams
+    const uint64_t* seed;                  // [N]
+    double* rec;                           // [N][LTPL_FLEET_SIM_SENSOR_DOUBLES]
+    uint32_t tick;                         // tick0 + fleet ticks since the sensor was set
+};
+struct SenseLds { double dx[SIM_OBJ_CAP], dy[SIM_OBJ_CAP], L2[SIM_OBJ_CAP], r[SIM_OBJ_CAP]; };
+
+// the geometry of n objects (x, y, r `stride` doubles apart) seen from (px, py), one lane per object
+__device__ __forceinline__ void sim_sense_stage(int lane, int n, double px, double py, const double* x, const double* y, const double* r, int stride,
+                                                SenseLds& L)
+{
+    for (int k = lane; k < n; k += 64) {
+        const fleet::SensorObj o = fleet::sensor_obj(px, py, x[(size_t)k * stride], y[(size_t)k * stride]);
+        L.dx[k] = o.dx; L.dy[k] = o.dy; L.L2[k] = o.L2; L.r[k] = r[(size_t)k * stride];
+    }
+}
+__device__ __forceinline__ fleet::SensorParams sim_sensor_params(const double* q) { return fleet::SensorParams{q[0], q[1], q[2], q[3], q[4]}; }
+
+// `g_tx`, `g_ty` (null while the noise is off): the true positions of the tick's objects -- what decides whether an object is detected; what
+// is handed on is what the noise made of it. Each lane loads the sources of its object before any lane stores (a barrier in between);
+// destination <= source, and the second pass writes behind what the first one wrote and reads from slot 64 on.
+__global__ __launch_bounds__(64) void k_fleet_sim_sense(SimDev sd, SimSense sn, double* g_tx, double* g_ty, double* trace /* this tick's records or null */)
+{
+    const int p = blockIdx.x, lane = threadIdx.x;
+    if (!sd.live[p]) return;
+    __shared__ SenseLds L;
+    const int base = sd.obj_base[p];
+    int cnt = sd.cnt[p];
+    if (cnt > SIM_OBJ_CAP) cnt = SIM_OBJ_CAP;
+    const double px = sd.pos_x[p], py = sd.pos_y[p], th = sd.theta[p];
+    const double fx = -sin(th), fy = cos(th);
+    sim_sense_stage(lane, cnt, px, py, (g_tx ? g_tx : sd.g_x) + base, (g_tx ? g_ty : sd.g_y) + base, sd.g_r + base, 1, L);
+    __syncthreads();
+    const fleet::SensorParams P = sim_sensor_params(sn.par + (size_t)p * SENS_PARAMS);
+    const uint64_t seed = sn.seed[p];
+    double* o = trace ? trace + (size_t)p * LTPL_FLEET_SIM_TRACE_DOUBLES : nullptr;
+    int kept = 0, lost[4] = {0, 0, 0, 0};
+    double cd = INFINITY; int ci = 0x7fffffff;
+    for (int b0 = 0; b0 < cnt; b0 += 64) {
+        const int k = b0 + lane, g = base + k;
+        int cause = -1;
+        double vx = 0.0, vy = 0.0, vpx = 0.0, vpy = 0.0, vr = 0.0, vv = 0.0, vtx = 0.0, vty = 0.0;
+        if (k < cnt) {
+            vx = sd.g_x[g]; vy = sd.g_y[g]; vpx = sd.g_px[g]; vpy = sd.g_py[g]; vr = sd.g_r[g]; vv = sd.g_v[g];
+            if (g_tx) { vtx = g_tx[g]; vty = g_ty[g]; }
+            double u;
+            cause = fleet::sensor_cause(P, seed, sn.tick, fx, fy, L.dx, L.dy, L.L2, L.r, cnt, k, &u);
+            if (cause != fleet::kSenseSeen) {
+                const double c = fleet::sensor_clearance(L.L2[k], L.r[k]);
+                if (c < cd) { cd = c; ci = k; }
+            }
+        }
+        const bool keep = cause == fleet::kSenseSeen;
+        const unsigned long long m = __ballot(keep);
+        const int d = base + kept + __popcll(m & ((1ull << lane) - 1ull));
+#pragma unroll
+        for (int c = 0; c < 4; ++c) lost[c] += __popcll(__ballot(cause == fleet::kSenseRange + c));
+        __syncthreads();
+        if (keep) {
+            sd.g_x[d] = vx; sd.g_y[d] = vy; sd.g_px[d] = vpx; sd.g_py[d] = vpy; sd.g_r[d] = vr; sd.g_v[d] = vv;
+            if (g_tx) { g_tx[d] = vtx; g_ty[d] = vty; }
+            if (d == base && o) { o[6] = vx; o[7] = vy; }
+        }
+        kept += __popcll(m);
+    }
+    wave_min2(cd, ci);
+    if (lane != 0) return;
+    sd.cnt[p] = kept;
+    if (o) {
+        o[5] = (double)kept;
+        if (kept == 0) { o[6] = NAN; o[7] = NAN; }
+    }
+    double* r = sn.rec + (size_t)p * LTPL_FLEET_SIM_SENSOR_DOUBLES;
+    r[SENS_TICKS] += 1.0; r[SENS_N_OBJ] += (double)cnt; r[SENS_N_SEEN] += (double)kept;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) r[SENS_N_RANGE + c] += (double)lost[c];
+    if (kept != cnt) {
+        r[SENS_BLIND_TICKS] += 1.0;
+        if (cd < r[SENS_CLEAR_MIN]) { r[SENS_CLEAR_MIN] = cd; r[SENS_CLEAR_TICK] = (double)sn.tick; }
+    }
+}
+
+// the test hook of the rule: one wave per case, the staging and the decision of k_fleet_sim_sense on the case's own objects. The forward
+// vector is handed in: no trigonometry here
+__global__ __launch_bounds__(64) void k_fleet_sim_sensor_eval(const double* pose_f, const double* par, const uint64_t* seed, const uint32_t* tick,
+                                                              const int* obj_off, const double* objs, int* cause, double* u)
+{
+    const int q = blockIdx.x, lane = threadIdx.x;
+    __shared__ SenseLds L;
+    const int o0 = obj_off[q];
+    int n = obj_off[q + 1] - o0;
+    if (n > SIM_OBJ_CAP) n = SIM_OBJ_CAP;      // (refused by the host)
+    const double* pf = pose_f + (size_t)q * 4;
+    const double* ob = objs + (size_t)o0 * 3;
+    sim_sense_stage(lane, n, pf[0], pf[1], ob, ob + 1, ob + 2, 3, L);
+    __syncthreads();
+    const fleet::SensorParams P = sim_sensor_params(par + (size_t)q * SENS_PARAMS);
+    for (int k = lane; k < n; k += 64) {
+        double uu = NAN;
+        cause[o0 + k] = fleet::sensor_cause(P, seed[q], tick[q], pf[2], pf[3], L.dx, L.dy, L.L2, L.r, n, k, &uu);
+        u[o0 + k] = uu;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // flight recorder (ltpl_fleet_sim_record, include/ltpl_hip.h): for M chosen planners a full record of every tick, kept in a ring of
 // `depth` ticks. Record of (tick, recorded planner m): `stride` doubles at ring + ((tick % depth) M + m) stride --
 //   head, REC_HEAD doubles (integers as exact doubles):
@@ -734,6 +854,10 @@ struct FleetSim {
     SimVeh vh{};
     bool has_veh = false;                   // the tick launches k_fleet_sim_step_veh / k_fleet_sim_step_noise_veh
     std::vector<int> veh_model;             // [N] host copy of vh.model (KEEP_STATE; ltpl_fleet_sim_branch compares models)
+    std::vector<void*> sens_allocs;         // parameters, seeds and records of ltpl_fleet_sim_sensor
+    SimSense sn{};
+    bool has_sens = false;                  // the tick launches k_fleet_sim_sense in front of k_fleet_sim_offsets
+    int sens_tick0 = 0, sens_tick = 0;      // tick0; ticks of ltpl_fleet_sim_run since the sensor was set
 };
 static void sim_free_list(std::vector<void*>& l)
 {
@@ -751,7 +875,7 @@ static void fleet_sim_free(FleetSim* s)
     sim_snaps_free(s->snaps);
     sim_events_free(s->events);
     sim_free_list(s->stage_allocs); sim_free_list(s->race_allocs); sim_free_list(s->tele_allocs); sim_free_list(s->rec_allocs);
-    sim_free_list(s->noise_allocs); sim_free_list(s->veh_allocs);
+    sim_free_list(s->noise_allocs); sim_free_list(s->veh_allocs); sim_free_list(s->sens_allocs);
     for (void* p : s->allocs) (void)hipFree(p);
     if (s->velt.d_buf) (void)hipFree(s->velt.d_buf);
     delete s;
@@ -980,6 +1104,13 @@ try {
                 hipLaunchKernelGGL(k_fleet_sim_rank, dim3(N), dim3(64), 0, st, s.sd, s.te);
                 FLEET_TRY(f, hipGetLastError());
             }
+        }
+        if (s.has_sens) {
+            // (the tick advances whether or not a planner is live, like the noise's)
+            s.sn.tick = (uint32_t)s.sens_tick0 + (uint32_t)s.sens_tick++;
+            hipLaunchKernelGGL(k_fleet_sim_sense, dim3(N), dim3(64), 0, st, s.sd, s.sn, s.has_noise ? s.nz.g_tx : (double*)nullptr,
+                               s.has_noise ? s.nz.g_ty : (double*)nullptr, tr);
+            FLEET_TRY(f, hipGetLastError());
         }
         hipLaunchKernelGGL(k_fleet_sim_offsets, dim3(1), dim3(1024), 0, st, (const int*)s.sd.cnt, N, s.sd.veh_off);
         FLEET_TRY(f, hipGetLastError());
@@ -1574,6 +1705,120 @@ try {
     FLEET_TRY(f, hipGetLastError());
     FLEET_TRY(f, hipMemcpyAsync(out, d + o_out, 8 * LTPL_FLEET_SIM_VEH_DOUBLES * m, hipMemcpyDeviceToHost, f->h->stream));
     FLEET_TRY(f, hipMemcpyAsync(theta, d + o_theta, 8 * m, hipMemcpyDeviceToHost, f->h->stream));
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+// ---------------------------------------------------------------------------------------------------------------------
+// sensor model (ltpl_fleet_sim_sensor, include/ltpl_hip.h; the rule: fleet_sensor.hpp)
+// ---------------------------------------------------------------------------------------------------------------------
+// every argument is checked before the first HIP call
+static int sim_check_sensor(ltpl_fleet* f, const ltpl_fleet_sim_sensor_in* in)
+{
+    const int N = f->D.N;
+    auto bad = [&](const std::string& why) { f->err = "fleet sim sensor: " + why; return LTPL_ERR_INVALID_ARG; };
+    if (!f->sim) return bad("ltpl_fleet_sim_setup first");
+    if (!in) return LTPL_OK;
+    const double* a[SENS_PARAMS] = {in->range, in->r_near, in->fov_cos, in->occl, in->p_drop};
+    static const char* const name[SENS_PARAMS] = {"range", "r_near", "fov_cos", "occl", "p_drop"};
+    for (int c = 0; c < SENS_PARAMS; ++c) if (!a[c]) return bad(std::string(name[c]) + " missing");
+    if (!in->seed) return bad("seed missing");
+    if (in->tick0 < 0) return bad("tick0 must not be negative");
+    for (int p = 0; p < N; ++p) {
+        const std::string who = "planner " + std::to_string(p) + ": ";
+        const double range = in->range[p], r_near = in->r_near[p], fov_cos = in->fov_cos[p], occl = in->occl[p], p_drop = in->p_drop[p];
+        if (!(range >= 0.0)) return bad(who + "range must not be negative or NaN (+inf: no limit)");
+        if (!(r_near >= 0.0) || !(r_near <= range)) return bad(who + "r_near must lie in [0, range]");
+        if (!(fov_cos >= -1.0) || !(fov_cos <= 1.0)) return bad(who + "fov_cos must lie in [-1, 1]");
+        if (!std::isfinite(occl) || !(occl >= 0.0)) return bad(who + "occl must be finite and not negative");
+        if (!(p_drop >= 0.0) || !(p_drop < 1.0)) return bad(who + "p_drop must lie in [0, 1)");
+    }
+    return LTPL_OK;
+}
+
+extern "C" int ltpl_fleet_sim_sensor(ltpl_fleet* f, const ltpl_fleet_sim_sensor_in* in)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    int rc = sim_check_sensor(f, in);
+    if (rc) return rc;
+    if ((rc = fleet_enter(f))) return rc;
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    FleetSim& s = *f->sim;
+    if (!in) {
+        sim_free_list(s.sens_allocs);
+        s.sn = SimSense{}; s.has_sens = false; s.sens_tick0 = s.sens_tick = 0;
+        return LTPL_OK;
+    }
+    const size_t N = (size_t)f->D.N;
+    constexpr size_t RD = LTPL_FLEET_SIM_SENSOR_DOUBLES;
+    const double* a[SENS_PARAMS] = {in->range, in->r_near, in->fov_cos, in->occl, in->p_drop};
+    std::vector<double> par(N * SENS_PARAMS), rec(N * RD, 0.0);
+    for (size_t p = 0; p < N; ++p) {
+        for (int c = 0; c < SENS_PARAMS; ++c) par[p * SENS_PARAMS + c] = a[c][p];
+        rec[p * RD + SENS_CLEAR_MIN] = INFINITY; rec[p * RD + SENS_CLEAR_TICK] = -1.0;
+    }
+    // everything new is allocated first; the fleet keeps its previous sensor, its tick count and its statistics unless every step succeeds
+    SimAllocs al;
+    double* d_par = nullptr; uint64_t* d_seed = nullptr; double* d_rec = nullptr;
+    if ((rc = sim_upload(f, al.p, par.data(), par.size(), &d_par))) return rc;
+    if ((rc = sim_upload(f, al.p, in->seed, N, &d_seed))) return rc;
+    if ((rc = sim_upload(f, al.p, rec.data(), rec.size(), &d_rec))) return rc;
+    sim_free_list(s.sens_allocs);
+    s.sens_allocs.swap(al.p);
+    s.sn = SimSense{d_par, d_seed, d_rec, 0u};
+    s.has_sens = true; s.sens_tick0 = in->tick0; s.sens_tick = 0;
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+extern "C" int ltpl_fleet_sim_sensor_read(ltpl_fleet* f, double* out, int32_t doubles_per_planner)
+try {
+    if (!f || !out) return LTPL_ERR_INVALID_ARG;
+    if (!f->sim) { f->err = "fleet sim sensor: ltpl_fleet_sim_setup first"; return LTPL_ERR_INVALID_ARG; }
+    if (!f->sim->has_sens) { f->err = "fleet sim sensor: the sensor is off (ltpl_fleet_sim_sensor first)"; return LTPL_ERR_INVALID_ARG; }
+    if (doubles_per_planner != LTPL_FLEET_SIM_SENSOR_DOUBLES) { f->err = "fleet sim sensor: record size mismatch"; return LTPL_ERR_INVALID_ARG; }
+    FLEET_TRY(f, hipSetDevice(f->h->device));
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    FLEET_TRY(f, hipMemcpy(out, f->sim->sn.rec, sizeof(double) * (size_t)f->D.N * LTPL_FLEET_SIM_SENSOR_DOUBLES, hipMemcpyDeviceToHost));
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+extern "C" int ltpl_fleet_sim_sensor_eval(ltpl_fleet* f, int32_t n_cases, const double* pose_f, const double* params, const uint64_t* seed,
+                                          const uint32_t* tick, const int32_t* obj_off, const double* objs, int32_t* cause, double* u)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    auto bad = [&](const std::string& why) { f->err = "fleet sim sensor eval: " + why; return LTPL_ERR_INVALID_ARG; };
+    if (n_cases < 0) return bad("n_cases must not be negative");
+    if (n_cases == 0) return LTPL_OK;
+    if (!pose_f || !params || !seed || !tick || !obj_off) return bad("pose_f / params / seed / tick / obj_off missing");
+    if (obj_off[0] != 0) return bad("object offsets must start at 0");
+    for (int q = 0; q < n_cases; ++q) {
+        const int n = obj_off[q + 1] - obj_off[q];
+        if (n < 0 || n > SIM_OBJ_CAP) return bad("case " + std::to_string(q) + ": 0 .. 96 objects");
+    }
+    const size_t m = (size_t)n_cases, no = (size_t)obj_off[n_cases];
+    if (no > 0 && (!objs || !cause || !u)) return bad("objs / cause / u missing");
+    int rc = fleet_enter(f);
+    if (rc) return rc;
+    Arena ar;     // one device block
+    const size_t o_pf = ar.add(32 * m), o_par = ar.add(8 * SENS_PARAMS * m), o_seed = ar.add(8 * m), o_objs = ar.add(24 * (no ? no : 1)),
+                 o_u = ar.add(8 * (no ? no : 1)), o_tick = ar.add(4 * m), o_off = ar.add(4 * (m + 1)), o_cause = ar.add(4 * (no ? no : 1));
+    unsigned char* d = nullptr;
+    struct Guard { void* a = nullptr; ~Guard() { if (a) (void)hipFree(a); } } gd;
+    FLEET_TRY(f, hipMalloc(reinterpret_cast<void**>(&d), ar.size)); gd.a = d;
+    FLEET_TRY(f, hipMemcpy(d + o_pf, pose_f, 32 * m, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_par, params, 8 * SENS_PARAMS * m, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_seed, seed, 8 * m, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_tick, tick, 4 * m, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_off, obj_off, 4 * (m + 1), hipMemcpyHostToDevice));
+    if (no) FLEET_TRY(f, hipMemcpy(d + o_objs, objs, 24 * no, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_fleet_sim_sensor_eval, dim3((unsigned)m), dim3(64), 0, f->h->stream, (const double*)(d + o_pf), (const double*)(d + o_par),
+                       (const uint64_t*)(d + o_seed), (const uint32_t*)(d + o_tick), (const int*)(d + o_off), (const double*)(d + o_objs),
+                       reinterpret_cast<int*>(d + o_cause), reinterpret_cast<double*>(d + o_u));
+    FLEET_TRY(f, hipGetLastError());
+    if (no) {
+        FLEET_TRY(f, hipMemcpyAsync(cause, d + o_cause, 4 * no, hipMemcpyDeviceToHost, f->h->stream));
+        FLEET_TRY(f, hipMemcpyAsync(u, d + o_u, 8 * no, hipMemcpyDeviceToHost, f->h->stream));
+    }
     FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))

@@ -16,6 +16,7 @@ from . import _capi
 from .planner import KEY_IDS, KEY_NAMES, PathsView, Planner, PlannerPathsIn, PlannerVelIn, TrajView
 from .sim import TELEMETRY_DOUBLES, TELEMETRY_FIELDS, telemetry_dict      # noqa: F401  (published here: fleet.TELEMETRY_FIELDS)
 from .sim import VEHICLE_DEFAULTS, VEHICLE_DOUBLES, VEHICLE_FIELDS, VEHICLE_PARAMS, vehicle_dict      # noqa: F401  (fleet.VEHICLE_FIELDS)
+from .sim import SENSOR_DOUBLES, SENSOR_FIELDS, SENSOR_PARAMS, sensor_dict, sensor_fov_cos      # noqa: F401  (fleet.SENSOR_FIELDS)
 from .sim import pack_events as sim_pack_events
 
 
@@ -56,6 +57,10 @@ class SimNoiseIn(C.Structure):             # ltpl_fleet_sim_noise_in
 
 class SimVehicleIn(C.Structure):           # ltpl_fleet_sim_vehicle_in
     _fields_ = [("model", C.c_void_p)] + [(k, C.c_void_p) for k in VEHICLE_PARAMS] + [("ctl_steps", C.c_int32), ("flags", C.c_uint32)]
+
+
+class SimSensorIn(C.Structure):            # ltpl_fleet_sim_sensor_in
+    _fields_ = [(k, C.c_void_p) for k in SENSOR_PARAMS] + [("seed", C.c_void_p), ("tick0", C.c_int32)]
 
 
 class SimRecordHead(C.Structure):         # ltpl_fleet_sim_record_head
@@ -116,6 +121,10 @@ class Fleet(Planner):
             f("sim_vehicle").argtypes = [C.c_void_p, C.POINTER(SimVehicleIn)]
             f("sim_vehicle_read").argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
             f("sim_vehicle_step").argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 7 + [C.c_int32, C.c_void_p]
+        if hasattr(self.lib, "ltpl_fleet_sim_sensor"):
+            f("sim_sensor").argtypes = [C.c_void_p, C.POINTER(SimSensorIn)]
+            f("sim_sensor_read").argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+            f("sim_sensor_eval").argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 8
         if hasattr(self.lib, "ltpl_fleet_friction"):
             f("friction").argtypes = [C.c_void_p, C.POINTER(FrictionIn)]
             f("friction_scale").argtypes = [C.c_void_p, C.c_void_p]
@@ -685,6 +694,57 @@ class Fleet(Planner):
         self._check(self._fn("sim_vehicle_step")(self.handle, m, state.ctypes.data, params.ctypes.data, off.ctypes.data, flat.ctypes.data,
                                                  dts.ctypes.data, ctl.ctypes.data, out.ctypes.data, VEHICLE_DOUBLES, theta.ctypes.data))
         return out[:m], theta[:m]
+
+    # ---- sensor model on the device ---------------------------------------------------------------------------------------------------
+    def sim_sensor(self, range=float("inf"), fov_deg=360.0, r_near=0.0, occl=0.0, p_drop=0.0, seed=None, tick0=0):
+        """Which of the tick's on-track objects every planner is shown (ltpl_fleet_sim_sensor; after ``sim_setup``, between runs at any
+        time): a ``range`` [m], a forward cone of the FULL opening angle ``fov_deg`` (exactly 360: no cone), an all-round near field
+        ``r_near`` inside which cone and occlusion do not apply, occlusion by nearer objects with their radii scaled by ``occl`` (0: off)
+        and a dropout probability ``p_drop`` per object and tick drawn from ``seed`` (scalars or one per planner; ``seed=None``: 0).
+        ``tick0``: the sensor tick of the next tick. ``range=None`` switches the sensor off. The statistics start anew with every
+        call. Host mirror: ``sim.SensorModel``."""
+        if range is None:
+            self._check(self._fn("sim_sensor")(self.handle, None))
+            return
+        n = self.n_scen
+        si = SimSensorIn()
+        val = dict(range=range, r_near=r_near, fov_cos=sensor_fov_cos(fov_deg), occl=occl, p_drop=p_drop)
+        keep = []
+        for name in SENSOR_PARAMS:
+            keep.append(np.ascontiguousarray(np.broadcast_to(np.asarray(val[name], np.float64), (n,))))
+            setattr(si, name, keep[-1].ctypes.data)
+        keep.append(np.ascontiguousarray(np.broadcast_to(np.asarray(0 if seed is None else seed, np.uint64), (n,))))
+        si.seed, si.tick0 = keep[-1].ctypes.data, int(tick0)
+        self._check(self._fn("sim_sensor")(self.handle, C.byref(si)))
+
+    def sim_sensor_read(self, raw=False):
+        """dict of named arrays (``sim.SENSOR_FIELDS``): live ticks, objects on the track, seen, lost to range / cone / occlusion / dropout,
+        ticks with a lost object, the smallest true clearance to a lost object and its sensor tick, of every planner
+        (ltpl_fleet_sim_sensor_read). ``raw=True``: the [n, 10] records."""
+        out = np.zeros((self.n_scen, SENSOR_DOUBLES), np.float64)
+        self._check(self._fn("sim_sensor_read")(self.handle, out.ctypes.data, SENSOR_DOUBLES))
+        return out if raw else sensor_dict(out)
+
+    def sim_sensor_eval(self, pose, f, params, seed, tick, objs):
+        """The sensor's test hook (ltpl_fleet_sim_sensor_eval): independent cases on the device, one wave each. ``pose`` [m, 2]; ``f``
+        [m, 2] the forward vector as given; ``params`` [m, 5] in the order of ``sim.SENSOR_PARAMS``; ``seed``, ``tick``: scalars or one
+        per case; ``objs``: a list of m arrays [n_q, 3] = x, y, r (0 .. 96 rows). Returns (causes, u): per case an int32 array (0 seen,
+        1 .. 4 the cause of loss) and the dropout draws (NaN where none was made); equals ``sim.SensorModel.evaluate`` bit for bit."""
+        pose = np.asarray(pose, np.float64).reshape(-1, 2)
+        m = pose.shape[0]
+        pf = np.ascontiguousarray(np.concatenate((pose, np.broadcast_to(np.asarray(f, np.float64), (m, 2))), axis=1))
+        params = np.ascontiguousarray(np.broadcast_to(np.asarray(params, np.float64), (m, len(SENSOR_PARAMS))))
+        seeds = np.ascontiguousarray(np.broadcast_to(np.asarray(seed, np.uint64), (m,)))
+        ticks = np.ascontiguousarray(np.broadcast_to(np.asarray(tick, np.uint32), (m,)))
+        objs = [np.asarray(o, np.float64).reshape(-1, 3) for o in objs]
+        if len(objs) != m:
+            raise ValueError("sim_sensor_eval: one object list per case expected")
+        off = np.ascontiguousarray(np.concatenate(([0], np.cumsum([o.shape[0] for o in objs]))).astype(np.int32))
+        flat = np.ascontiguousarray(np.concatenate(objs + [np.zeros((1, 3))]))
+        cause, u = np.zeros(int(off[-1]) + 1, np.int32), np.zeros(int(off[-1]) + 1, np.float64)
+        self._check(self._fn("sim_sensor_eval")(self.handle, m, pf.ctypes.data, params.ctypes.data, seeds.ctypes.data, ticks.ctypes.data,
+                                                off.ctypes.data, flat.ctypes.data, cause.ctypes.data, u.ctypes.data))
+        return [cause[off[q]:off[q + 1]].copy() for q in range(m)], [u[off[q]:off[q + 1]].copy() for q in range(m)]
 
     # ---- friction maps on the device ------------------------------------------------------------------------------------------------
     def friction(self, maps, map_idx=None, scale=1.0):

@@ -31,6 +31,12 @@ and of the vehicle model of ``ltpl_fleet_sim_vehicle`` (csrc/fleet_vehicle.hpp) 
                      of the ideal tracker: + - * / sqrt on Python floats in the operation order of the kernels, so the device's bits;
   ``VEHICLE_DEFAULTS`` / ``VEHICLE_FIELDS`` / ``vehicle_dict``   its parameters and the record of ``Fleet.sim_vehicle_read``.
 
+and of the sensor model of ``ltpl_fleet_sim_sensor`` (csrc/fleet_sensor.hpp) --
+
+  ``SensorModel``    which on-track objects a planner is shown (range, cone, near field, occlusion, dropout) and the statistics record,
+                     in the operation order of the header and of k_fleet_sim_sense, so the device's decisions;
+  ``sensor_uniform`` / ``sensor_fov_cos`` / ``SENSOR_FIELDS`` / ``sensor_dict``   the dropout draw, the cone's cosine and the record.
+
 Both simulators restate ``np.interp`` (numpy's ``arr_interp``) in the operation order of the device functions (``interp_at`` here,
 ``fleet::sim_interp`` there), so that host and device give the same bits as the reference.
 """
@@ -747,3 +753,119 @@ class VehicleModel(object):
         if on_track is not None and not on_track(self.x, self.y):
             self.stats["off_track_ticks"] += 1
         return [self.x, self.y], self.v, self.theta
+
+
+# ---- sensor model (ltpl_fleet_sim_sensor, include/ltpl_hip.h; csrc/fleet_sensor.hpp) ------------------------------------------------------
+# name, index, integer valued: the record of ltpl_fleet_sim_sensor_read (LTPL_FLEET_SIM_SENSOR_DOUBLES = 10 per planner)
+SENSOR_FIELDS = (("ticks", 0, True), ("n_obj", 1, True), ("n_seen", 2, True), ("n_range", 3, True), ("n_fov", 4, True), ("n_occl", 5, True),
+                 ("n_drop", 6, True), ("blind_ticks", 7, True), ("blind_clear_min", 8, False), ("blind_clear_tick", 9, True))
+SENSOR_DOUBLES = 10
+SENSOR_PARAMS = ("range", "r_near", "fov_cos", "occl", "p_drop")
+SENSOR_SEEN, SENSOR_RANGE, SENSOR_FOV, SENSOR_OCCL, SENSOR_DROP = 0, 1, 2, 3, 4      # cause of loss, in the order of the tests
+
+
+def sensor_dict(rows):
+    """[n, 10] records as a dict of named arrays (counters as int64; blind_clear_tick reads -1 until an object was lost)."""
+    rows = np.asarray(rows, np.float64).reshape(-1, SENSOR_DOUBLES)
+    return {name: (rows[:, i].astype(np.int64) if is_int else rows[:, i].copy()) for name, i, is_int in SENSOR_FIELDS}
+
+
+def sensor_fov_cos(fov_deg):
+    """Cosine of the half angle of the FULL opening angle ``fov_deg``; exactly 360 gives -1 (the test switched off)."""
+    d = np.asarray(fov_deg, np.float64)
+    return np.where(d == 360.0, -1.0, np.cos(np.radians(d) / 2.0))
+
+
+def sensor_uniform(seed, tick, k):
+    """u of the dropout test: ((double)w0 + 0.5) 2^-32 with w0 the first word of the block (tick, k, 0, 1) under the key (seed low, seed
+    high). Scalars give a float, arrays an array."""
+    seed = np.asarray(seed, np.uint64)
+    w0 = philox4x32((tick, k, 0, 1), (seed & _M32, seed >> _S32))[0]
+    u = (np.asarray(w0).astype(np.float64) + 0.5) * 2.0 ** -32
+    return float(u) if u.ndim == 0 else u
+
+
+class SensorModel(object):
+    """Scalar host mirror of the sensor model in the operation order of csrc/fleet_sensor.hpp (sensor_cause) and of the statistics of
+    k_fleet_sim_sense: plain Python floats, + - * sqrt and comparisons, so the device's bits. Parameters: scalars or one per planner;
+    ``fov_deg`` is the full opening angle (``fov_cos`` given directly takes precedence)."""
+
+    def __init__(self, n, range=float("inf"), fov_deg=360.0, r_near=0.0, occl=0.0, p_drop=0.0, seed=0, tick0=0, fov_cos=None):
+        self.n = int(n)
+
+        def per(v):
+            return [float(x) for x in np.broadcast_to(np.asarray(v, np.float64), (self.n,))]
+        self.range, self.r_near, self.occl, self.p_drop = per(range), per(r_near), per(occl), per(p_drop)
+        self.fov_cos = per(sensor_fov_cos(fov_deg) if fov_cos is None else fov_cos)
+        self.seed = [int(v) for v in np.broadcast_to(np.asarray(seed, np.uint64), (self.n,))]
+        self.tick0 = int(tick0)
+        self.rec = np.zeros((self.n, SENSOR_DOUBLES))
+        self.rec[:, 8], self.rec[:, 9] = np.inf, -1.0
+
+    @staticmethod
+    def forward(theta):
+        """Forward unit vector of the library's heading (measured from the y axis)."""
+        return (-math.sin(theta), math.cos(theta))
+
+    def evaluate(self, p, tick, pos, f, objs):
+        """``objs``: [(x, y, r)] at the TRUE positions, in list order -> (causes, u): the cause of loss of every object (0: seen) and
+        the dropout draw where one was made (NaN otherwise)."""
+        px, py, fx, fy = float(pos[0]), float(pos[1]), float(f[0]), float(f[1])
+        rng, near, fc, occl, pd = self.range[p], self.r_near[p], self.fov_cos[p], self.occl[p], self.p_drop[p]
+        dx = [float(o[0]) - px for o in objs]
+        dy = [float(o[1]) - py for o in objs]
+        rad = [float(o[2]) for o in objs]
+        L2 = [a * a + b * b for a, b in zip(dx, dy)]
+        n = len(objs)
+        causes, us = [], []
+        for k in range(n):
+            causes.append(self._cause(p, tick, fx, fy, dx, dy, L2, rad, n, k, rng, near, fc, occl, pd, us))
+        return causes, us
+
+    def _cause(self, p, tick, fx, fy, dx, dy, L2, rad, n, k, rng, near, fc, occl, pd, us):
+        us.append(float("nan"))
+        dxk, dyk, L2k = dx[k], dy[k], L2[k]
+        if L2k > rng * rng:
+            return SENSOR_RANGE
+        if not L2k <= near * near:
+            if fc > -1.0 and fx * dxk + fy * dyk < fc * math.sqrt(L2k):
+                return SENSOR_FOV
+            if occl > 0.0:
+                for j in range(n):
+                    if j == k or not L2[j] < L2k or not dx[j] * dxk + dy[j] * dyk > 0.0:
+                        continue
+                    cross, s = dx[j] * dyk - dy[j] * dxk, occl * rad[j]
+                    if cross * cross <= (s * s) * L2k:
+                        return SENSOR_OCCL
+        if pd > 0.0:
+            us[-1] = sensor_uniform(self.seed[p], tick & 0xFFFFFFFF, k)
+            if us[-1] < pd:
+                return SENSOR_DROP
+        return SENSOR_SEEN
+
+    def sense(self, p, tick, pos, theta, objs, f=None):
+        """One live tick of planner ``p`` at sensor tick ``tick`` (tick0 + fleet ticks since the sensor was set): the causes of
+        ``evaluate`` with f formed from ``theta`` (unless given), and the planner's statistics record updated."""
+        causes, _ = self.evaluate(p, tick, pos, self.forward(theta) if f is None else f, objs)
+        r = self.rec[p]
+        r[0] += 1.0
+        r[1] += len(objs)
+        r[2] += causes.count(SENSOR_SEEN)
+        for c in (SENSOR_RANGE, SENSOR_FOV, SENSOR_OCCL, SENSOR_DROP):
+            r[2 + c] += causes.count(c)
+        lost = [k for k, c in enumerate(causes) if c != SENSOR_SEEN]
+        if lost:
+            r[7] += 1.0
+            px, py = float(pos[0]), float(pos[1])
+            best = float("inf")
+            for k in lost:
+                dx, dy = float(objs[k][0]) - px, float(objs[k][1]) - py
+                c = math.sqrt(dx * dx + dy * dy) - float(objs[k][2])
+                if c < best:
+                    best = c
+            if best < r[8]:
+                r[8], r[9] = best, float(tick)
+        return causes
+
+    def as_dict(self):
+        return sensor_dict(self.rec)

@@ -62,7 +62,8 @@ extern "C" {
                                      additive to v9: ltpl_fleet_sim_race / _heading, ltpl_fleet_friction / _scale / _rows,
                                      ltpl_fleet_sim_snapshot / _snapshot_info / _snapshot_drop / _branch,
                                      ltpl_fleet_sim_noise / _estimate / _noise_draws,
-                                     ltpl_fleet_sim_vehicle / _vehicle_read / _vehicle_step */
+                                     ltpl_fleet_sim_vehicle / _vehicle_read / _vehicle_step,
+                                     ltpl_fleet_sim_sensor / _sensor_read / _sensor_eval */
 
 /* status codes */
 #define LTPL_OK               0
@@ -1150,6 +1151,70 @@ int ltpl_fleet_sim_vehicle_read(ltpl_fleet* fleet, double* out, int32_t doubles_
 int ltpl_fleet_sim_vehicle_step(ltpl_fleet* fleet, int32_t n_cases, const double* state, const double* params, const int32_t* row_off,
                                 const double* rows, const double* dt, const int32_t* ctl_steps, double* out, int32_t doubles_per_case,
                                 double* theta);
+
+/* ------------------------------------------------------------------------------------------------------------------------------------------
+ * Additive to ABI v9 -- SENSOR MODEL: which of the tick's on-track objects a planner is shown, decided on the device inside
+ * ltpl_fleet_sim_run (csrc/fleet_sim.hpp: k_fleet_sim_sense; the rule: csrc/fleet_sensor.hpp). Without it every planner is handed every
+ * on-track object of the tick, every tick. The sensor is a pure function of the tick's TRUE state with no memory from tick to tick: it
+ * is configuration, not state.
+ * ARITHMETIC: fp64, + - * sqrt and comparisons only, one fixed order (the library is built with -ffp-contract=off): the host mirror
+ * sim.SensorModel and the device agree to the last bit, given the same forward vector.
+ * PER PLANNER p AND TICK: the true pose (px, py), the forward unit vector f = (-sin theta, cos theta) of its heading (the library's heading
+ * is measured from the y axis; sin / cos are the device's), and the staged objects k = 0 .. cnt - 1 of the tick: opponents, statics and
+ * mates behind the on-track ingestion, at their TRUE positions (the positions before ltpl_fleet_sim_noise moved them) with their radii r.
+ *   dx = x - px;  dy = y - py;  L2 = dx dx + dy dy
+ * An object is tested in this order; the first test that fails is its cause of loss:
+ *   | # | cause     | lost when                                                                                   | off       |
+ *   | 1 | range     | L2 > range range                                                                            | +inf      |
+ *   | 2 | (near)    | L2 <= r_near r_near: tests 3 and 4 are skipped (all-round short-range sensing)              | 0         |
+ *   | 3 | fov       | fov_cos > -1 and fx dx + fy dy < fov_cos sqrt(L2); fov_cos = cosine of the HALF opening     | -1 (not   |
+ *   |   |           | angle                                                                                        | evaluated)|
+ *   | 4 | occlusion | occl > 0 and some j != k among ALL staged objects of the tick has L2_j < L2_k and            | 0         |
+ *   |   |           | dx_j dx_k + dy_j dy_k > 0 and cross cross <= ((occl r_j) (occl r_j)) L2_k, cross =           |           |
+ *   |   |           | dx_j dy_k - dy_j dx_k. occl scales the occluder's radius. A lost object still occludes;      |           |
+ *   |   |           | objects at equal distance never hide one another                                             |           |
+ *   | 5 | dropout   | p_drop > 0 and u < p_drop; u = ((double)w0 + 0.5) 2^-32, w0 the first output word of ONE    | 0 (draws  |
+ *   |   |           | Philox4x32-10 block, key = the sensor's seed of the planner, counter (tick, k, 0, 1)         | nothing)  |
+ * k is the object's slot in the tick's on-track list before the sensor; tick = tick0 + the fleet ticks run since the sensor was set (it
+ * advances whether or not a planner is live). Every block of ltpl_fleet_sim_noise has 0 in counter word 3: one seed may serve both.
+ * The seen objects keep their order (a stable compaction of the staged list, perceived values included). The "open" sensor (range +inf,
+ * fov_cos -1, occl 0, p_drop 0) keeps every object: bit-identical to a fleet without the call.
+ * STATISTICS per planner, LTPL_FLEET_SIM_SENSOR_DOUBLES doubles, updated in every tick in which the planner is live:
+ *   [0] ticks  [1] n_obj: sum of on-track counts  [2] n_seen  [3] n_range  [4] n_fov  [5] n_occl  [6] n_drop: objects lost to each cause
+ *   [7] blind_ticks: ticks with at least one lost object  [8] blind_clear_min: smallest sqrt(L2) - r over the lost objects (telemetry's
+ *   clearance, on truth; +inf at the start)  [9] blind_clear_tick: the sensor tick of that minimum (-1 at the start; the first smallest
+ *   wins, within a tick the lower slot)
+ * IN THE TICK: behind k_fleet_sim_tele / _rank, in front of k_fleet_sim_offsets. Telemetry (clearance, contacts), LTPL_SIM_WHEN_OPP_WITHIN
+ * and the mates' view of one another keep acting on truth; offsets, compaction, the planner and the flight recorder see what the sensor
+ * kept: the recorder's objects are the seen ones, and trace fields [5] .. [7] describe the list handed on. A planner that is not live is
+ * skipped. SNAPSHOT / BRANCH copy neither the configuration nor the statistics: both stay the destination's own. No event kind sets it.
+ * LIMITS: no memory between ticks -- no detection latency, no track persistence, no burst dropouts; an object the ingestion drops as off
+ * the track neither is seen nor occludes.
+ * THE CALL: after ltpl_fleet_sim_setup (which switches the sensor off) at any time between runs; in == NULL switches it off: the tick then
+ * launches the kernels it launched before. Every argument is checked before the first HIP call, the message names the argument: every
+ * array present; range not NaN and not negative (+inf allowed); r_near in [0, range]; fov_cos in [-1, 1]; occl finite and >= 0; p_drop
+ * in [0, 1); tick0 >= 0. Everything new is allocated before anything old is freed: a failing call keeps the previous sensor, its tick
+ * count and its statistics. A successful call starts the statistics anew.
+ * ------------------------------------------------------------------------------------------------------------------------------------------ */
+#define LTPL_FLEET_SIM_SENSOR_DOUBLES 10
+typedef struct {
+    const double* range;             /* [n] m, >= 0 or +inf (every array is needed)      */
+    const double* r_near;            /* [n] m, 0 .. range                               */
+    const double* fov_cos;           /* [n] cosine of the half opening angle, -1 .. 1   */
+    const double* occl;              /* [n] factor on the occluder's radius, 0: off     */
+    const double* p_drop;            /* [n] dropout probability per object and tick, [0, 1) */
+    const uint64_t* seed;            /* [n] key of the dropout draws                    */
+    int32_t tick0;                   /* >= 0: the sensor tick of the next fleet tick    */
+} ltpl_fleet_sim_sensor_in;
+int ltpl_fleet_sim_sensor(ltpl_fleet* fleet, const ltpl_fleet_sim_sensor_in* in);
+/* out: [n][LTPL_FLEET_SIM_SENSOR_DOUBLES]. No simulation, the sensor off or a wrong record size: LTPL_ERR_INVALID_ARG. */
+int ltpl_fleet_sim_sensor_read(ltpl_fleet* fleet, double* out, int32_t doubles_per_planner);
+/* the test hook of the rule (k_fleet_sim_sensor_eval, one wave per case, the tick's own device functions): case q has the pose and the
+ * forward vector pose_f[q][4] = px, py, fx, fy (f as given: no trigonometry), params[q][5] = range, r_near, fov_cos, occl, p_drop,
+ * seed[q], tick[q] and the objects objs[obj_off[q] .. obj_off[q + 1])[3] = x, y, r (0 .. 96 of them). cause[i]: 0 seen, 1 .. 4 the cause of
+ * loss in the order of the table; u[i]: the dropout draw where one was made, NaN otherwise. Needs a fleet, no simulation. */
+int ltpl_fleet_sim_sensor_eval(ltpl_fleet* fleet, int32_t n_cases, const double* pose_f, const double* params, const uint64_t* seed,
+                               const uint32_t* tick, const int32_t* obj_off, const double* objs, int32_t* cause, double* u);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,7 @@
 """Closed-loop SIMULATION rate of a fleet (ltpl_fleet_sim_*): N planners, each with its own eight C2-style race-line opponents (SURVEY.md
 section 8d: s0_k = 250 + 280 k, vel_scale_k = 0.30 + 0.05 (k mod 4), here staggered by 10 m (p mod 16) per planner), run the example
 driver's loop on the device for T ticks without host work per tick.   tools/sim_rate.py [--planners 32768] [--ticks 200] [--no-tape]
-[--race-size K] [--friction-map] [--telemetry] [--record M [--record-depth D]] [--events] [--noise] [--vehicle] [--lib PATH]. Prints planner-ticks per second of sim_run (device time of the run) next to tape_run on the C2 tape (recorded inputs,
+[--race-size K] [--friction-map] [--telemetry] [--record M [--record-depth D]] [--events] [--noise] [--vehicle] [--sensor [keep]] [--lib PATH]. Prints planner-ticks per second of sim_run (device time of the run) next to tape_run on the C2 tape (recorded inputs,
 tools/fleet_rate.py). --race-size K > 1: races of K consecutive planners (ltpl_fleet_sim_race) that see one another, started 30 m apart
 along the race line with its heading; K = 1 (default) is the run without races. --friction-map: the same fleet on the friction grid of
 tests/golden/friction_grid.npz (ltpl_fleet_friction: rows evaluated on the device, grip factors 1.0 .. 0.7 over the planners) instead of
@@ -18,6 +18,12 @@ planner: k_fleet_sim_step_noise (and k_fleet_sim_mates_noise with races) in plac
 estimate and true pose is printed after the run. --vehicle: every planner drives the vehicle model (ltpl_fleet_sim_vehicle,
 sim.VEHICLE_DEFAULTS: k_fleet_sim_step_veh, or k_fleet_sim_step_noise_veh with --noise, in place of the step kernel); without races the
 planners are put into races of one, which hands the start heading to the simulation; the tracking statistics are printed after the run.
+--sensor: every planner behind the sensor model (ltpl_fleet_sim_sensor) with all four tests active -- range 300 m, a cone of 240 degrees, a
+near field of 5 m, occlusion with the radius doubled, dropout 0.1, a seed per planner: k_fleet_sim_sense in front of k_fleet_sim_offsets;
+like --vehicle it puts the planners into races of one for the start heading; the planner then sees fewer objects, so the rate holds the
+sensor's kernel AND the changed planning work; the statistics are printed after the run. --sensor keep: every test evaluated and nothing
+lost (range 10^6 m, a cone of 359.999 degrees, occlusion with the radius times 10^-6, dropout 10^-12): the planning work of the run without
+a sensor plus the kernel.
 --lib PATH: another build of
 the library (A/B against the parent's)."""
 import argparse
@@ -50,6 +56,8 @@ def main():
     ap.add_argument("--events", action="store_true", help="scripted events on: a timed gg_scale event and an opp_within trigger with a chained after per planner")
     ap.add_argument("--noise", action="store_true", help="seeded sensor noise on, all five sigmas set, a seed per planner")
     ap.add_argument("--vehicle", action="store_true", help="every planner drives the vehicle model (sim.VEHICLE_DEFAULTS) instead of the ideal tracker")
+    ap.add_argument("--sensor", nargs="?", const="lossy", default=None, choices=("lossy", "keep"),
+                    help="every planner behind the sensor model: range, cone, near field, occlusion and dropout all active; 'keep': all evaluated, nothing lost")
     ap.add_argument("--lib", default=None, help="path of the library to load (default: the in-tree build)")
     a = ap.parse_args()
     lat = Lattice.load(os.path.join(ROOT, "tests", "golden", "monteblanco_lattice.npz"))
@@ -86,7 +94,7 @@ def main():
         fleet.sim_setup(race, entries)
         if K > 1:
             fleet.sim_race(sizes)
-        elif a.vehicle:
+        elif a.vehicle or a.sensor:
             fleet.sim_race([1] * n)
         if grid is not None:
             fleet.friction(grid, scale=1.0 - 0.3 * (np.arange(n) % 16) / 15.0)
@@ -107,6 +115,10 @@ def main():
             fleet.sim_noise(seed=np.arange(n, dtype=np.uint64) + np.uint64(1), pos=0.1, vel=0.2, obj_pos=0.3, obj_theta=0.02, obj_vel=0.5)
         if a.vehicle:
             fleet.sim_vehicle(model=1)
+        if a.sensor:
+            par = dict(range=300.0, fov_deg=240.0, r_near=5.0, occl=2.0, p_drop=0.1) if a.sensor == "lossy" else \
+                dict(range=1e6, fov_deg=359.999, r_near=0.0, occl=1e-6, p_drop=1e-12)
+            fleet.sim_sensor(seed=np.arange(n, dtype=np.uint64) + np.uint64(1), **par)
         t0 = time.perf_counter()
         failed = 0
         try:
@@ -131,6 +143,11 @@ def main():
             print("  vehicle: e_max up to %.3f m, rms e up to %.3f m, dv_max up to %.2f m/s, %d lateral and %d longitudinal saturations in %d control "
                   "steps, %d planners left the track" % (np.max(d["e_max"]), np.sqrt(np.max(d["e2_sum"] / np.maximum(d["ctl_steps"], 1))), np.max(d["dv_max"]),
                                                          d["sat_lat"].sum(), d["sat_lon"].sum(), d["ctl_steps"].sum(), np.count_nonzero(d["off_track_ticks"])))
+        if a.sensor:
+            d = fleet.sim_sensor_read()
+            print("  sensor: %d of %d objects seen; lost to range %d, cone %d, occlusion %d, dropout %d; %d planner-ticks with a lost object, smallest "
+                  "blind clearance %.3f m" % (d["n_seen"].sum(), d["n_obj"].sum(), d["n_range"].sum(), d["n_fov"].sum(), d["n_occl"].sum(), d["n_drop"].sum(),
+                                             d["blind_ticks"].sum(), np.min(d["blind_clear_min"])))
         if a.events:
             ft = fleet.sim_events_read()["fired_tick"].reshape(n, 3)
             print("  events: %d timed, %d opp_within and %d chained 'after' events fired of %d each (schedule tick %d)" % (
