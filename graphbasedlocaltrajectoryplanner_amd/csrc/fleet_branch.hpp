@@ -4,10 +4,14 @@
 //   copied   the planner block (Dims::stride bytes of d_state; the planner's error word PlannerS::err lies in it), its window of friction
 //            rows (Dims::gg_stride bytes of d_gg) when both sides have windows, now / sel / started / pos_x / pos_y / vel / theta / live,
 //            opp_s / opp_tic of its opponents, with telemetry on both sides its record, grid_s and prog, and the vehicle model's record
-//            (state and statistics, ltpl_fleet_sim_vehicle) where the DESTINATION has model 1;
+//            (state and statistics, ltpl_fleet_sim_vehicle) where the DESTINATION has model 1, and the object tracker's table, track
+//            count and next_id (ltpl_fleet_sim_tracker) where the destination has a tracker;
 //   stays    the race line, the opponents' vel_scale / length, statics, zones, preference list, dt, n_export, the velocity arguments,
 //            friction map index and scale, race membership and length as a mate, contact radius, the recorder's ring and indices,
-//            the vehicle model's switch and parameters.
+//            the vehicle model's switch and parameters, the tracker's parameters and statistics.
+// Object tracker, the mixed cases: a destination without a tracker takes nothing; a destination with one takes the table of a source that
+// held tracker state (a live planner while the tracker is set, a snapshot entry taken with one) -- a source without empties the
+// destination's table and sets next_id 0, the tracker's start state; a source with more tracks than the destination's C_p is refused.
 // Vehicle model, the mixed cases: a destination on the ideal tracker (or a fleet without the model) takes no vehicle record and keeps its
 // NaN record, whatever the source drives; a destination with model 1 needs a source that had model 1 when it was copied (the live
 // planner now, the snapshot's planner when the snapshot was taken) -- otherwise the pair is refused with LTPL_ERR_INVALID_ARG.
@@ -24,6 +28,7 @@ struct BranchView {
     const int* opp_off; double* opp_s; double* opp_tic; // opponents of entry e: opp_off[e] .. opp_off[e + 1] - 1
     double* rec; double* grid_s; double* prog;          // telemetry part (rec null: none)
     double* veh; const int* veh_model;                  // vehicle records (veh null: none); as a destination: the model of every entry
+    double* trk; int* trk_n; double* trk_next; const int* trk_base;   // tracker: rows of entry e from row trk_base[e] on (trk_n null: none)
 };
 
 typedef unsigned int branch_u32x4 __attribute__((ext_vector_type(4)));
@@ -78,6 +83,15 @@ __global__ __launch_bounds__(BRANCH_THREADS) void k_fleet_sim_branch(BranchView 
         }
         if (S.veh && T.veh && t < LTPL_FLEET_SIM_VEH_DOUBLES && T.veh_model[ed] != 0)
             T.veh[ed * LTPL_FLEET_SIM_VEH_DOUBLES + t] = S.veh[es * LTPL_FLEET_SIM_VEH_DOUBLES + t];
+        if (T.trk_n) {
+            const int nt = S.trk_n ? S.trk_n[es] : 0;       // (at most the destination's capacity: the host's check)
+            if (S.trk_n) {
+                const double* a_ = S.trk + (size_t)S.trk_base[es] * LTPL_FLEET_SIM_TRACK_DOUBLES;
+                double* b_ = T.trk + (size_t)T.trk_base[ed] * LTPL_FLEET_SIM_TRACK_DOUBLES;
+                for (int q = t; q < nt * LTPL_FLEET_SIM_TRACK_DOUBLES; q += 64) b_[q] = a_[q];
+            }
+            if (t == 0) { T.trk_n[ed] = nt; T.trk_next[ed] = S.trk_n ? S.trk_next[es] : 0.0; }
+        }
     }
 }
 static_assert(LTPL_FLEET_SIM_TELE_DOUBLES + 2 <= 64, "k_fleet_sim_branch: one lane per telemetry double");
@@ -93,6 +107,7 @@ struct SimSnap {
     std::vector<int> opp_off;               // [entries + 1] host copy of v.opp_off
     bool has_tele = false; int tele_gen = 0;     // a telemetry part, taken from the telemetry numbered tele_gen (FleetSim::tele_gen)
     std::vector<int> veh_model;             // [entries] the model of entry k when the snapshot was taken (empty: the model was off)
+    bool has_trk = false;                   // a tracker part: tables of the planners' capacities, counts and next_id
     uint64_t bytes = 0;
     bool held() const { return !planners.empty(); }
 };
@@ -113,6 +128,7 @@ static BranchView branch_live_view(const ltpl_fleet* f)
     v.opp_off = d.opp_off; v.opp_s = d.opp_s; v.opp_tic = d.opp_tic;
     if (s.has_tele) { v.rec = s.te.rec; v.grid_s = s.te.grid_s; v.prog = s.te.prog; }
     if (s.has_veh) { v.veh = s.vh.rec; v.veh_model = s.vh.model; }
+    if (s.has_trk) { v.trk = s.tk.rows; v.trk_n = s.tk.n; v.trk_next = s.tk.next_id; v.trk_base = s.tk.base; }
     return v;
 }
 
@@ -219,6 +235,13 @@ try {
         SNAP_TAKE(&v.veh, M * LTPL_FLEET_SIM_VEH_DOUBLES);
         { int* o = nullptr; SNAP_TAKE(&o, M, q->veh_model.data()); v.veh_model = o; }
     }
+    if (s.has_trk) {                                     // (with the tracker off the snapshot holds what it held before)
+        std::vector<int> tb(M + 1, 0);
+        for (size_t k = 0; k < M; ++k) tb[k + 1] = tb[k] + s.trk_cap[(size_t)q->planners[k]];
+        SNAP_TAKE(&v.trk, (size_t)tb[M] * LTPL_FLEET_SIM_TRACK_DOUBLES); SNAP_TAKE(&v.trk_n, M); SNAP_TAKE(&v.trk_next, M);
+        { int* o = nullptr; SNAP_TAKE(&o, M + 1, tb.data()); v.trk_base = o; }
+        q->has_trk = true;
+    }
 #undef SNAP_TAKE
     std::vector<int> dst(M);
     for (size_t k = 0; k < M; ++k) dst[k] = (int)k;
@@ -312,6 +335,15 @@ try {
     if ((rc = fleet_enter(f))) return rc;
     FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
     BranchView S = q ? q->v : branch_live_view(f);
+    if (s.has_trk && S.trk_n && !se.empty()) {              // the sources' track counts against the destinations' capacities
+        const size_t ns = q ? q->planners.size() : (size_t)N;
+        std::vector<int> nt(ns);
+        FLEET_TRY(f, hipMemcpy(nt.data(), S.trk_n, sizeof(int) * ns, hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < se.size(); ++k)
+            if (nt[(size_t)se[k]] > s.trk_cap[(size_t)de[k]])
+                return bad("the source of destination " + std::to_string(de[k]) + " holds " + std::to_string(nt[(size_t)se[k]]) + " tracks, the destination's table " +
+                           std::to_string(s.trk_cap[(size_t)de[k]]));
+    }
     if (q && !(q->has_tele && s.has_tele && q->tele_gen == s.tele_gen)) S.rec = nullptr;      // (a telemetry set since then started its records anew)
     if ((rc = branch_launch(f, S, branch_live_view(f), se, de, ms))) return rc;
     f->cur.has_paths = false;           // (as after a run: a per-call calc_vel_profile needs its own calc_paths first)

@@ -27,6 +27,10 @@
 //                        through range, near field, cone, occlusion (every lane walks the same LDS entry: a broadcast) and dropout;
 //                        the staged arrays ballot-compacted in place, sd.cnt and trace [5] .. [7] rewritten, lane 0 updates the
 //                        planner's 10-double record. Behind telemetry, which measured against the complete list
+//   k_fleet_sim_track    (object tracker set only: ltpl_fleet_sim_tracker; the rule: fleet_track.hpp) one wave64 per planner behind the
+//                        sensor: the planner's track table predicted, associated with the staged detections (greedy nearest neighbour,
+//                        one wave minimum per accepted pair), updated, coasted, compacted and extended by births; the staged arrays,
+//                        sd.cnt and trace [5] .. [7] rewritten with the list handed on, lane 0 updates the planner's 12-double record
 //   k_fleet_sim_offsets  exclusive scan of the on-track counts -> veh_off (one workgroup)
 //   k_fleet_sim_compact  survivors into the fleet's object layout (one lane per planner)
 //   k_fleet_sim_rec_paths / k_fleet_sim_rec_vel   (flight recorder on only: ltpl_fleet_sim_record) one wave64 per RECORDED planner: the
@@ -39,6 +43,7 @@
 
 #include "fleet_noise.hpp"
 #include "fleet_sensor.hpp"
+#include "fleet_track.hpp"
 #include "fleet_vehicle.hpp"
 
 namespace fleet {
@@ -641,6 +646,252 @@ __global__ __launch_bounds__(64) void k_fleet_sim_sensor_eval(const double* pose
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// object tracker (ltpl_fleet_sim_tracker, include/ltpl_hip.h; the rule: fleet_track.hpp; host mirror: sim.TrackerModel). Configuration, a
+// statistics record and STATE: the planner's track table, its count and next_id (copied by snapshot / branch, fleet_branch.hpp). The
+// pointers live in a struct of their own: no other kernel carries them.
+// ---------------------------------------------------------------------------------------------------------------------
+#define TRK_PARAMS 5                       // fleet::TrackParams
+static_assert(fleet::TRK_DOUBLES == LTPL_FLEET_SIM_TRACK_DOUBLES && fleet::TRS_DOUBLES == LTPL_FLEET_SIM_TRACKER_DOUBLES &&
+              sizeof(fleet::TrackParams) == TRK_PARAMS * sizeof(double) && fleet::kTrackCap == SIM_OBJ_CAP && SIM_OBJ_CAP <= 128,
+              "tracker record layout");
+struct SimTrack {
+    const double* par;                     // [N][TRK_PARAMS] in the order of fleet::TrackParams
+    const int* base;                       // [N] first table row of planner p
+    const int* cap;                        // [N] C_p = min(96, 2 S_p)
+    const int* slots;                      // [N] S_p: the planner's staging slots
+    double* rows;                          // [sum C_p][LTPL_FLEET_SIM_TRACK_DOUBLES]
+    int* n;                                // [N] tracks in the table
+    double* next_id;                       // [N]
+    double* rec;                           // [N][LTPL_FLEET_SIM_TRACKER_DOUBLES]
+    double adv;                            // dt / 0.2: ticks per prediction horizon of the ingestion
+    uint32_t tick;                         // tick0 + fleet ticks since the tracker was set
+};
+struct TrackLds { double xp[SIM_OBJ_CAP], yp[SIM_OBJ_CAP], d[6][SIM_OBJ_CAP]; int tm[SIM_OBJ_CAP]; };
+// detections in, handed-on list out: six arrays (x, y, px, py, r, v), elements `stride` doubles apart. Both may be the same memory: every
+// detection is staged in LDS before the first store
+struct TrackIo { const double* in[6]; double* out[6]; int stride; };
+
+// the nearest free gated track of detection (xk, yk): lowest (d2, t). tf0 / tf1: the free tracks, uniform; every lane walks t in step
+__device__ __forceinline__ void sim_track_scan(const TrackLds& L, int T, unsigned long long tf0, unsigned long long tf1, double xk, double yk, double g2,
+                                               double& bd, int& bt)
+{
+    bd = INFINITY; bt = -1;
+    for (int t = 0; t < T; ++t) {
+        if (!((t < 64 ? tf0 >> t : tf1 >> (t - 64)) & 1ull)) continue;
+        const double d2 = fleet::track_d2(xk, yk, L.xp[t], L.yp[t]);
+        if (fleet::track_gated(d2, g2) && d2 < bd) { bd = d2; bt = t; }
+    }
+}
+__device__ __forceinline__ fleet::TrackDet sim_track_lds_det(const TrackLds& L, int k)
+{
+    return fleet::TrackDet{L.d[0][k], L.d[1][k], L.d[2][k], L.d[3][k], L.d[4][k], L.d[5][k]};
+}
+
+// One tick of one planner's tracker by one wave64 (every lane enters). Lane l holds tracks l and l + 64 and detections l and l + 64 in
+// registers from the staging to the stores at the end: sources are read before any destination is written. Returns the number of
+// objects handed on (uniform). `assign` (or null): per detection the matched id, kTrackUnmatched or kTrackOverflow; `first` (or null):
+// x, y of the first object handed on.
+__device__ __forceinline__ int sim_track_tick(int lane, const fleet::TrackParams& P, double adv, double tick, int cap, int slots, double* rows, int* n_trk,
+                                              double* next_id, int K, const TrackIo& io, int* assign, double* rec, double* first, TrackLds& L)
+{
+    constexpr int RD = LTPL_FLEET_SIM_TRACK_DOUBLES;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    int T = *n_trk;
+    if (T > cap) T = cap;                  // (never: the host refuses a copy above the capacity)
+    const double id0 = *next_id;
+    fleet::TrackRow row[2];
+    double xp[2] = {0.0, 0.0}, yp[2] = {0.0, 0.0};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int t = lane + 64 * h;
+#pragma unroll
+        for (int c = 0; c < RD; ++c) row[h].f[c] = t < T ? rows[(size_t)t * RD + c] : 0.0;
+        if (t < T) {
+            xp[h] = fleet::track_predict(row[h].f[fleet::TRK_X], adv, row[h].f[fleet::TRK_EX]);
+            yp[h] = fleet::track_predict(row[h].f[fleet::TRK_Y], adv, row[h].f[fleet::TRK_EY]);
+            L.xp[t] = xp[h]; L.yp[t] = yp[h]; L.tm[t] = -1;
+        }
+    }
+    for (int k = lane; k < K; k += 64) {
+        const size_t i = (size_t)k * io.stride;
+        const fleet::TrackDet d = fleet::track_det(io.in[0][i], io.in[1][i], io.in[2][i], io.in[3][i], io.in[4][i], io.in[5][i]);
+        L.d[0][k] = d.x; L.d[1][k] = d.y; L.d[2][k] = d.ex; L.d[3][k] = d.ey; L.d[4][k] = d.r; L.d[5][k] = d.v;
+    }
+    __syncthreads();
+    // step 2: one accepted pair per round, the wave's minimum over (d2, t 128 + k); a lane rescans only when its best track was taken
+    const double g2 = fleet::track_gate2(P.gate);
+    unsigned long long tf0 = T >= 64 ? ~0ull : (1ull << T) - 1ull, tf1 = T > 64 ? (1ull << (T - 64)) - 1ull : 0ull;
+    double bd[2], xk[2], yk[2]; int bt[2]; bool unm[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int k = lane + 64 * h;
+        unm[h] = k < K; bd[h] = INFINITY; bt[h] = -1; xk[h] = yk[h] = 0.0;
+        if (unm[h]) { xk[h] = L.d[0][k]; yk[h] = L.d[1][k]; sim_track_scan(L, T, tf0, tf1, xk[h], yk[h], g2, bd[h], bt[h]); }
+    }
+    for (;;) {
+        double key = INFINITY; int idx = 0x7fffffff;
+        if (bt[0] >= 0) { key = bd[0]; idx = bt[0] * 128 + lane; }
+        if (bt[1] >= 0) {
+            const int i1 = bt[1] * 128 + lane + 64;
+            if (bd[1] < key || (bd[1] == key && i1 < idx)) { key = bd[1]; idx = i1; }
+        }
+        wave_min2(key, idx);
+        if (idx == 0x7fffffff) break;
+        const int ts = idx >> 7, ks = idx & 127;
+        if (ts < 64) tf0 &= ~(1ull << ts); else tf1 &= ~(1ull << (ts - 64));
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            if (ks == lane + 64 * h) { L.tm[ts] = ks; unm[h] = false; bt[h] = -1; }
+            else if (bt[h] == ts) sim_track_scan(L, T, tf0, tf1, xk[h], yk[h], g2, bd[h], bt[h]);
+        }
+    }
+    __syncthreads();
+    // steps 3 and 4: 1 matched, 2 coasting, 3 deleted as tentative, 4 deleted after n_coast misses (0: no track)
+    int st[2] = {0, 0};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int t = lane + 64 * h;
+        if (t < T) {
+            const int k = L.tm[t];
+            if (k >= 0) {
+                fleet::track_update(P, row[h], xp[h], yp[h], sim_track_lds_det(L, k));
+                if (assign) assign[k] = (int)row[h].f[fleet::TRK_ID];
+                st[h] = 1;
+            } else {
+                st[h] = 2 + fleet::track_miss(P, row[h], xp[h], yp[h]);
+            }
+        }
+    }
+    // step 6: the survivors' rows, then the births
+    int pos[2], n = 0, n_matched = 0, del_tent = 0, del_coast = 0, confirmed = 0;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const unsigned long long m = __ballot(st[h] == 1 || st[h] == 2);
+        pos[h] = n + __popcll(m & lt); n += __popcll(m);
+        n_matched += __popcll(__ballot(st[h] == 1)); del_tent += __popcll(__ballot(st[h] == 3)); del_coast += __popcll(__ballot(st[h] == 4));
+        confirmed += __popcll(__ballot(st[h] == 1 && fleet::track_confirmed_now(P, row[h])));
+    }
+    const int n_surv = n;
+    fleet::TrackRow brow[2]; int bpos[2], nb = 0; bool born[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int k = lane + 64 * h;
+        const unsigned long long m = __ballot(unm[h]);
+        const int rank = nb + __popcll(m & lt);
+        nb += __popcll(m);
+        bpos[h] = n_surv + rank;
+        born[h] = unm[h] && bpos[h] < cap;
+        brow[h] = fleet::track_born(sim_track_lds_det(L, unm[h] ? k : 0), id0 + (double)rank, tick);
+        if (unm[h] && assign) assign[k] = born[h] ? fleet::kTrackUnmatched : fleet::kTrackOverflow;
+        confirmed += __popcll(__ballot(born[h] && fleet::track_confirmed_now(P, brow[h])));
+    }
+    const int n_born = nb < cap - n_surv ? nb : cap - n_surv, overflow = nb - n_born;
+    // step 7: positions in the list handed on
+    int opos[2], obpos[2], cpos[2], m_out = 0;
+    bool lc[2], lb[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        lc[h] = st[h] == 1 && fleet::track_confirmed(P, row[h]);
+        const unsigned long long m = __ballot(lc[h]);
+        opos[h] = m_out + __popcll(m & lt); m_out += __popcll(m);
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        lb[h] = born[h] && fleet::track_confirmed(P, brow[h]);
+        const unsigned long long m = __ballot(lb[h]);
+        obpos[h] = m_out + __popcll(m & lt); m_out += __popcll(m);
+    }
+    const int n_live_out = m_out;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const unsigned long long m = __ballot(st[h] == 2);
+        cpos[h] = m_out + __popcll(m & lt); m_out += __popcll(m);
+    }
+    const int n_out = m_out < slots ? m_out : slots, out_coast = n_out > n_live_out ? n_out - n_live_out : 0, withheld = m_out - n_out;
+    __syncthreads();
+    auto hand_on = [&](const fleet::TrackRow& r, int at) {
+        double o[6];
+        fleet::track_out(r, o);
+        const size_t i = (size_t)at * io.stride;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) io.out[c][i] = o[c];
+        if (at == 0 && first) { first[0] = o[0]; first[1] = o[1]; }
+    };
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if (st[h] == 1 || st[h] == 2) {
+#pragma unroll
+            for (int c = 0; c < RD; ++c) rows[(size_t)pos[h] * RD + c] = row[h].f[c];
+        }
+        if (born[h]) {
+#pragma unroll
+            for (int c = 0; c < RD; ++c) rows[(size_t)bpos[h] * RD + c] = brow[h].f[c];
+        }
+        if (lc[h] && opos[h] < slots) hand_on(row[h], opos[h]);
+        if (lb[h] && obpos[h] < slots) hand_on(brow[h], obpos[h]);
+        if (st[h] == 2 && cpos[h] < slots) hand_on(row[h], cpos[h]);
+    }
+    if (lane == 0) {
+        const int n_new = n_surv + n_born;
+        *n_trk = n_new; *next_id = id0 + (double)n_born;
+        rec[fleet::TRS_TICKS] += 1.0; rec[fleet::TRS_N_DET] += (double)K; rec[fleet::TRS_N_MATCHED] += (double)n_matched;
+        rec[fleet::TRS_N_BORN] += (double)n_born; rec[fleet::TRS_N_CONFIRMED] += (double)confirmed; rec[fleet::TRS_N_DEL_TENT] += (double)del_tent;
+        rec[fleet::TRS_N_DEL_COAST] += (double)del_coast; rec[fleet::TRS_N_OUT] += (double)n_out; rec[fleet::TRS_N_OUT_COAST] += (double)out_coast;
+        rec[fleet::TRS_N_WITHHELD] += (double)withheld; rec[fleet::TRS_N_OVERFLOW] += (double)overflow;
+        if ((double)n_new > rec[fleet::TRS_TRACKS_MAX]) rec[fleet::TRS_TRACKS_MAX] = (double)n_new;
+    }
+    return n_out;
+}
+__device__ __forceinline__ fleet::TrackParams sim_track_params(const double* q) { return fleet::TrackParams{q[0], q[1], q[2], q[3], q[4]}; }
+
+// behind k_fleet_sim_sense (or telemetry / mates), in front of k_fleet_sim_offsets: the staged list of the planner is replaced by what its
+// tracker hands on; sd.cnt and trace [5] .. [7] rewritten as k_fleet_sim_sense rewrites them. g_tx / g_ty are left alone
+__global__ __launch_bounds__(64) void k_fleet_sim_track(SimDev sd, SimTrack tk, double* trace /* this tick's records or null */)
+{
+    const int p = blockIdx.x, lane = threadIdx.x;
+    if (!sd.live[p]) return;
+    __shared__ TrackLds L;
+    const int base = sd.obj_base[p];
+    int cnt = sd.cnt[p];
+    if (cnt > SIM_OBJ_CAP) cnt = SIM_OBJ_CAP;
+    const fleet::TrackParams P = sim_track_params(tk.par + (size_t)p * TRK_PARAMS);
+    double* o = trace ? trace + (size_t)p * LTPL_FLEET_SIM_TRACE_DOUBLES : nullptr;
+    TrackIo io;
+    io.in[0] = io.out[0] = sd.g_x + base; io.in[1] = io.out[1] = sd.g_y + base; io.in[2] = io.out[2] = sd.g_px + base;
+    io.in[3] = io.out[3] = sd.g_py + base; io.in[4] = io.out[4] = sd.g_r + base; io.in[5] = io.out[5] = sd.g_v + base;
+    io.stride = 1;
+    const int n_out = sim_track_tick(lane, P, tk.adv, (double)tk.tick, tk.cap[p], tk.slots[p], tk.rows + (size_t)tk.base[p] * LTPL_FLEET_SIM_TRACK_DOUBLES,
+                                     tk.n + p, tk.next_id + p, cnt, io, nullptr, tk.rec + (size_t)p * LTPL_FLEET_SIM_TRACKER_DOUBLES, o ? o + 6 : nullptr, L);
+    if (lane != 0) return;
+    sd.cnt[p] = n_out;
+    if (o) {
+        o[5] = (double)n_out;
+        if (n_out == 0) { o[6] = NAN; o[7] = NAN; }
+    }
+}
+
+// the test hook of the rule: one wave per case, the tick of k_fleet_sim_track on the case's own table (in place: tables [q][96][10], n_trk,
+// next_id) and detections; cs[q] = capacity, slots
+__global__ __launch_bounds__(64) void k_fleet_sim_tracker_eval(const double* par, const double* adv, const uint32_t* tick, const int* cs, double* tables,
+                                                               int* n_trk, double* next_id, const int* det_off, const double* dets, double* out,
+                                                               int* n_out, int* assign, double* rec)
+{
+    const int q = blockIdx.x, lane = threadIdx.x;
+    __shared__ TrackLds L;
+    const int o0 = det_off[q];
+    int K = det_off[q + 1] - o0;
+    if (K > SIM_OBJ_CAP) K = SIM_OBJ_CAP;      // (refused by the host)
+    const fleet::TrackParams P = sim_track_params(par + (size_t)q * TRK_PARAMS);
+    TrackIo io;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) { io.in[c] = dets + (size_t)o0 * 6 + c; io.out[c] = out + (size_t)q * SIM_OBJ_CAP * 6 + c; }
+    io.stride = 6;
+    const int m = sim_track_tick(lane, P, adv[q], (double)tick[q], cs[2 * q], cs[2 * q + 1], tables + (size_t)q * SIM_OBJ_CAP * LTPL_FLEET_SIM_TRACK_DOUBLES,
+                                 n_trk + q, next_id + q, K, io, assign + o0, rec + (size_t)q * LTPL_FLEET_SIM_TRACKER_DOUBLES, nullptr, L);
+    if (lane == 0) n_out[q] = m;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // flight recorder (ltpl_fleet_sim_record, include/ltpl_hip.h): for M chosen planners a full record of every tick, kept in a ring of
 // `depth` ticks. Record of (tick, recorded planner m): `stride` doubles at ring + ((tick % depth) M + m) stride --
 //   head, REC_HEAD doubles (integers as exact doubles):
@@ -858,6 +1109,13 @@ struct FleetSim {
     SimSense sn{};
     bool has_sens = false;                  // the tick launches k_fleet_sim_sense in front of k_fleet_sim_offsets
     int sens_tick0 = 0, sens_tick = 0;      // tick0; ticks of ltpl_fleet_sim_run since the sensor was set
+    std::vector<int> slots;                 // [N] staging slots of planner p (own + mates): the tracker's S_p
+    std::vector<void*> trk_allocs;          // parameters, tables, counts and records of ltpl_fleet_sim_tracker
+    SimTrack tk{};
+    bool has_trk = false;                   // the tick launches k_fleet_sim_track in front of k_fleet_sim_offsets
+    int trk_tick0 = 0, trk_tick = 0;        // tick0; ticks of ltpl_fleet_sim_run since the tracker was set
+    std::vector<double> trk_par;            // [N][TRK_PARAMS] host copy (ltpl_fleet_sim_race allocates the tables again)
+    std::vector<int> trk_cap;               // [N] host copy of tk.cap (ltpl_fleet_sim_branch compares track counts with it)
 };
 static void sim_free_list(std::vector<void*>& l)
 {
@@ -875,7 +1133,7 @@ static void fleet_sim_free(FleetSim* s)
     sim_snaps_free(s->snaps);
     sim_events_free(s->events);
     sim_free_list(s->stage_allocs); sim_free_list(s->race_allocs); sim_free_list(s->tele_allocs); sim_free_list(s->rec_allocs);
-    sim_free_list(s->noise_allocs); sim_free_list(s->veh_allocs); sim_free_list(s->sens_allocs);
+    sim_free_list(s->noise_allocs); sim_free_list(s->veh_allocs); sim_free_list(s->sens_allocs); sim_free_list(s->trk_allocs);
     for (void* p : s->allocs) (void)hipFree(p);
     if (s->velt.d_buf) (void)hipFree(s->velt.d_buf);
     delete s;
@@ -931,6 +1189,43 @@ static void sim_stage_commit(FleetSim* s, SimStage* st)
     d.o_r = st->o[0]; d.o_v = st->o[1]; d.o_px = st->o[2]; d.o_py = st->o[3];
     s->nz.g_tx = st->g[6]; s->nz.g_ty = st->g[7];
     s->ob = fleet::FObj{d.prev_action, d.t_now, d.veh_off, st->pos_off, d.o_r, d.o_v, d.o_px, d.o_py};
+}
+
+// the tracker's device arrays for the staging slots `slots`: empty tables, next_id 0, fresh statistics. Allocated into `al`; the caller
+// commits with sim_tracker_commit once everything else of its call succeeded
+struct SimTrackNew { SimAllocs al; SimTrack tk{}; std::vector<int> cap; };
+static int sim_tracker_alloc(ltpl_fleet* f, const std::vector<int>& slots, const std::vector<double>& par, SimTrackNew* t)
+{
+    const size_t N = (size_t)f->D.N;
+    std::vector<int> base(N);
+    t->cap.resize(N);
+    size_t total = 0;
+    for (size_t p = 0; p < N; ++p) {
+        base[p] = (int)total;
+        t->cap[p] = 2 * slots[p] < SIM_OBJ_CAP ? 2 * slots[p] : SIM_OBJ_CAP;
+        total += (size_t)t->cap[p];
+    }
+    int rc;
+    double* d_par = nullptr; int* d_base = nullptr; int* d_cap = nullptr; int* d_slots = nullptr;
+    if ((rc = sim_upload(f, t->al.p, par.data(), par.size(), &d_par))) return rc;
+    if ((rc = sim_upload(f, t->al.p, base.data(), N, &d_base))) return rc;
+    if ((rc = sim_upload(f, t->al.p, t->cap.data(), N, &d_cap))) return rc;
+    if ((rc = sim_upload(f, t->al.p, slots.data(), N, &d_slots))) return rc;
+    t->tk.par = d_par; t->tk.base = d_base; t->tk.cap = d_cap; t->tk.slots = d_slots;
+    if ((rc = sim_upload(f, t->al.p, (const double*)nullptr, total * LTPL_FLEET_SIM_TRACK_DOUBLES, &t->tk.rows))) return rc;
+    if ((rc = sim_upload(f, t->al.p, (const int*)nullptr, N, &t->tk.n))) return rc;
+    if ((rc = sim_upload(f, t->al.p, (const double*)nullptr, N, &t->tk.next_id))) return rc;
+    if ((rc = sim_upload(f, t->al.p, (const double*)nullptr, N * LTPL_FLEET_SIM_TRACKER_DOUBLES, &t->tk.rec))) return rc;
+    t->tk.adv = f->sim->sd.dt / 0.2;       // the one division of the rule (fleet_track.hpp)
+    return LTPL_OK;
+}
+static void sim_tracker_commit(FleetSim* s, SimTrackNew* t)
+{
+    sim_free_list(s->trk_allocs);
+    s->trk_allocs.swap(t->al.p);
+    s->tk = t->tk;
+    s->trk_cap.swap(t->cap);
+    s->has_trk = true;
 }
 
 static int sim_check_csr(ltpl_fleet* f, const int32_t* off, int N, const char* what, int* total)
@@ -1021,6 +1316,7 @@ try {
         SimStage st;
         if ((rc = sim_stage_alloc(f, s->own, &st))) return rc;
         sim_stage_commit(s.get(), &st);
+        s->slots = s->own;
     }
     s->zone_off = zo; s->zone_gid = zg;
     f->sim = s.release();
@@ -1110,6 +1406,12 @@ try {
             s.sn.tick = (uint32_t)s.sens_tick0 + (uint32_t)s.sens_tick++;
             hipLaunchKernelGGL(k_fleet_sim_sense, dim3(N), dim3(64), 0, st, s.sd, s.sn, s.has_noise ? s.nz.g_tx : (double*)nullptr,
                                s.has_noise ? s.nz.g_ty : (double*)nullptr, tr);
+            FLEET_TRY(f, hipGetLastError());
+        }
+        if (s.has_trk) {
+            // (the tick advances whether or not a planner is live, like the sensor's)
+            s.tk.tick = (uint32_t)s.trk_tick0 + (uint32_t)s.trk_tick++;
+            hipLaunchKernelGGL(k_fleet_sim_track, dim3(N), dim3(64), 0, st, s.sd, s.tk, tr);
             FLEET_TRY(f, hipGetLastError());
         }
         hipLaunchKernelGGL(k_fleet_sim_offsets, dim3(1), dim3(1024), 0, st, (const int*)s.sd.cnt, N, s.sd.veh_off);
@@ -1215,7 +1517,11 @@ try {
     if ((rc = sim_upload(f, ra.p, lo.data(), (size_t)N, &d_lo))) return rc;
     if ((rc = sim_upload(f, ra.p, hi.data(), (size_t)N, &d_hi))) return rc;
     if ((rc = sim_upload(f, ra.p, in->length, (size_t)N, &d_len))) return rc;
+    SimTrackNew tn;                         // a tracker keeps its configuration; its tables follow the new slot counts and start empty
+    if (s.has_trk && (rc = sim_tracker_alloc(f, slots, s.trk_par, &tn))) return rc;
     FLEET_TRY(f, hipMemcpy(s.sd.theta, in->heading0, sizeof(double) * (size_t)N, hipMemcpyHostToDevice));
+    if (s.has_trk) sim_tracker_commit(&s, &tn);
+    s.slots = slots;
     sim_stage_commit(&s, &st);
     sim_free_list(s.race_allocs);
     s.race_allocs.swap(ra.p);
@@ -1820,5 +2126,168 @@ try {
         FLEET_TRY(f, hipMemcpyAsync(u, d + o_u, 8 * no, hipMemcpyDeviceToHost, f->h->stream));
     }
     FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+// ---------------------------------------------------------------------------------------------------------------------
+// object tracker (ltpl_fleet_sim_tracker, include/ltpl_hip.h; the rule: fleet_track.hpp)
+// ---------------------------------------------------------------------------------------------------------------------
+// every argument is checked before the first HIP call
+static int sim_check_tracker(ltpl_fleet* f, const ltpl_fleet_sim_tracker_in* in)
+{
+    const int N = f->D.N;
+    auto bad = [&](const std::string& why) { f->err = "fleet sim tracker: " + why; return LTPL_ERR_INVALID_ARG; };
+    if (!f->sim) return bad("ltpl_fleet_sim_setup first");
+    if (!in) return LTPL_OK;
+    if (!in->gate) return bad("gate missing");
+    if (!in->w_pos) return bad("w_pos missing");
+    if (!in->w_vel) return bad("w_vel missing");
+    if (!in->n_confirm) return bad("n_confirm missing");
+    if (!in->n_coast) return bad("n_coast missing");
+    if (in->tick0 < 0) return bad("tick0 must not be negative");
+    for (int p = 0; p < N; ++p) {
+        const std::string who = "planner " + std::to_string(p) + ": ";
+        if (!std::isfinite(in->gate[p]) || !(in->gate[p] > 0.0)) return bad(who + "gate must be finite and positive");
+        if (!(in->w_pos[p] >= 0.0) || !(in->w_pos[p] < 1.0)) return bad(who + "w_pos must lie in [0, 1)");
+        if (!(in->w_vel[p] >= 0.0) || !(in->w_vel[p] < 1.0)) return bad(who + "w_vel must lie in [0, 1)");
+        if (in->n_confirm[p] < 1 || in->n_confirm[p] > 255) return bad(who + "n_confirm must lie in 1 .. 255");
+        if (in->n_coast[p] < 0 || in->n_coast[p] > 255) return bad(who + "n_coast must lie in 0 .. 255");
+    }
+    return LTPL_OK;
+}
+
+extern "C" int ltpl_fleet_sim_tracker(ltpl_fleet* f, const ltpl_fleet_sim_tracker_in* in)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    int rc = sim_check_tracker(f, in);
+    if (rc) return rc;
+    if ((rc = fleet_enter(f))) return rc;
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    FleetSim& s = *f->sim;
+    if (!in) {
+        sim_free_list(s.trk_allocs);
+        s.tk = SimTrack{}; s.has_trk = false; s.trk_tick0 = s.trk_tick = 0;
+        s.trk_par.clear(); s.trk_cap.clear();
+        return LTPL_OK;
+    }
+    const size_t N = (size_t)f->D.N;
+    std::vector<double> par(N * TRK_PARAMS);
+    for (size_t p = 0; p < N; ++p) {
+        double* q = &par[p * TRK_PARAMS];
+        q[0] = in->gate[p]; q[1] = in->w_pos[p]; q[2] = in->w_vel[p]; q[3] = (double)in->n_confirm[p]; q[4] = (double)in->n_coast[p];
+    }
+    // everything new is allocated first; the fleet keeps its previous tracker, its tables, its tick count and its statistics unless every step succeeds
+    SimTrackNew tn;
+    if ((rc = sim_tracker_alloc(f, s.slots, par, &tn))) return rc;
+    sim_tracker_commit(&s, &tn);
+    s.trk_par.swap(par);
+    s.trk_tick0 = in->tick0; s.trk_tick = 0;
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+extern "C" int ltpl_fleet_sim_tracker_read(ltpl_fleet* f, double* rec_out, int32_t doubles_per_planner, int32_t n_sel, const int32_t* sel_planners,
+                                           double* tracks_out, int32_t* n_tracks_out)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    auto bad = [&](const std::string& why) { f->err = "fleet sim tracker: " + why; return LTPL_ERR_INVALID_ARG; };
+    if (!f->sim) return bad("ltpl_fleet_sim_setup first");
+    if (!f->sim->has_trk) return bad("the tracker is off (ltpl_fleet_sim_tracker first)");
+    if (!rec_out) return bad("rec_out missing");
+    if (doubles_per_planner != LTPL_FLEET_SIM_TRACKER_DOUBLES) return bad("record size mismatch");
+    const int N = f->D.N;
+    if (n_sel < 0) return bad("n_sel must not be negative");
+    if (n_sel > 0 && (!sel_planners || !tracks_out || !n_tracks_out)) return bad("sel_planners / tracks_out / n_tracks_out missing");
+    for (int i = 0; i < n_sel; ++i) if (sel_planners[i] < 0 || sel_planners[i] >= N) return bad("planner index " + std::to_string(sel_planners[i]) + " out of range");
+    const FleetSim& s = *f->sim;
+    FLEET_TRY(f, hipSetDevice(f->h->device));
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    FLEET_TRY(f, hipMemcpy(rec_out, s.tk.rec, sizeof(double) * (size_t)N * LTPL_FLEET_SIM_TRACKER_DOUBLES, hipMemcpyDeviceToHost));
+    if (n_sel == 0) return LTPL_OK;
+    std::vector<int> n_trk((size_t)N);
+    FLEET_TRY(f, hipMemcpy(n_trk.data(), s.tk.n, sizeof(int) * (size_t)N, hipMemcpyDeviceToHost));
+    constexpr size_t RD = LTPL_FLEET_SIM_TRACK_DOUBLES, TAB = (size_t)SIM_OBJ_CAP * RD;
+    size_t base = 0;
+    std::vector<size_t> row0((size_t)N);
+    for (int p = 0; p < N; ++p) { row0[(size_t)p] = base; base += (size_t)s.trk_cap[(size_t)p]; }
+    for (int i = 0; i < n_sel; ++i) {
+        const size_t p = (size_t)sel_planners[i];
+        const int n = n_trk[p] < s.trk_cap[p] ? n_trk[p] : s.trk_cap[p];
+        double* o = tracks_out + (size_t)i * TAB;
+        for (size_t c = 0; c < TAB; ++c) o[c] = NAN;
+        if (n > 0) FLEET_TRY(f, hipMemcpy(o, s.tk.rows + row0[p] * RD, sizeof(double) * (size_t)n * RD, hipMemcpyDeviceToHost));
+        n_tracks_out[i] = n;
+    }
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+extern "C" int ltpl_fleet_sim_tracker_eval(ltpl_fleet* f, int32_t n_cases, const double* params, const double* adv, const uint32_t* tick,
+                                           const int32_t* cap_slots, const int32_t* trk_off, const double* tracks, const double* next_id,
+                                           const int32_t* det_off, const double* dets, double* tracks_out, int32_t* n_tracks_out, double* next_id_out,
+                                           double* out, int32_t* n_out, int32_t* assign, double* rec)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    auto bad = [&](const std::string& why) { f->err = "fleet sim tracker eval: " + why; return LTPL_ERR_INVALID_ARG; };
+    if (n_cases < 0) return bad("n_cases must not be negative");
+    if (n_cases == 0) return LTPL_OK;
+    if (!params || !adv || !tick || !cap_slots || !trk_off || !next_id || !det_off) return bad("params / adv / tick / cap_slots / trk_off / next_id / det_off missing");
+    if (!tracks_out || !n_tracks_out || !next_id_out || !out || !n_out || !rec) return bad("tracks_out / n_tracks_out / next_id_out / out / n_out / rec missing");
+    if (trk_off[0] != 0 || det_off[0] != 0) return bad("track and detection offsets must start at 0");
+    for (int q = 0; q < n_cases; ++q) {
+        const std::string who = "case " + std::to_string(q) + ": ";
+        const int T = trk_off[q + 1] - trk_off[q], K = det_off[q + 1] - det_off[q], cap = cap_slots[2 * q], slots = cap_slots[2 * q + 1];
+        if (cap < 0 || cap > SIM_OBJ_CAP || slots < 0 || slots > SIM_OBJ_CAP) return bad(who + "capacity and slots must lie in 0 .. 96");
+        if (T < 0 || T > cap) return bad(who + "0 .. capacity tracks");
+        if (K < 0 || K > slots) return bad(who + "0 .. slots detections");
+        const double* P = params + (size_t)q * TRK_PARAMS;
+        if (!std::isfinite(P[0]) || !(P[0] > 0.0) || !(P[1] >= 0.0) || !(P[1] < 1.0) || !(P[2] >= 0.0) || !(P[2] < 1.0) || !(P[3] >= 1.0) || !(P[3] <= 255.0) ||
+            !(P[4] >= 0.0) || !(P[4] <= 255.0))
+            return bad(who + "parameters out of range");
+    }
+    const size_t m = (size_t)n_cases, nt = (size_t)trk_off[n_cases], nd = (size_t)det_off[n_cases];
+    if (nt > 0 && !tracks) return bad("tracks missing");
+    if (nd > 0 && (!dets || !assign)) return bad("dets / assign missing");
+    constexpr size_t RD = LTPL_FLEET_SIM_TRACK_DOUBLES, TAB = (size_t)SIM_OBJ_CAP * RD, OUT = (size_t)SIM_OBJ_CAP * 6, SD = LTPL_FLEET_SIM_TRACKER_DOUBLES;
+    std::vector<double> tab(m * TAB, NAN), zero(m * (OUT > SD ? OUT : SD), 0.0);
+    std::vector<int> n0(m);
+    for (size_t q = 0; q < m; ++q) {
+        n0[q] = trk_off[q + 1] - trk_off[q];
+        if (n0[q]) std::memcpy(&tab[q * TAB], tracks + (size_t)trk_off[q] * RD, sizeof(double) * (size_t)n0[q] * RD);
+    }
+    int rc = fleet_enter(f);
+    if (rc) return rc;
+    Arena ar;     // one device block
+    const size_t o_par = ar.add(8 * TRK_PARAMS * m), o_adv = ar.add(8 * m), o_tab = ar.add(8 * TAB * m), o_id = ar.add(8 * m), o_dets = ar.add(48 * (nd ? nd : 1)),
+                 o_out = ar.add(8 * OUT * m), o_rec = ar.add(8 * SD * m), o_tick = ar.add(4 * m), o_cs = ar.add(8 * m), o_n = ar.add(4 * m),
+                 o_doff = ar.add(4 * (m + 1)), o_nout = ar.add(4 * m), o_asg = ar.add(4 * (nd ? nd : 1));
+    unsigned char* d = nullptr;
+    struct Guard { void* a = nullptr; ~Guard() { if (a) (void)hipFree(a); } } gd;
+    FLEET_TRY(f, hipMalloc(reinterpret_cast<void**>(&d), ar.size)); gd.a = d;
+    FLEET_TRY(f, hipMemcpy(d + o_par, params, 8 * TRK_PARAMS * m, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_adv, adv, 8 * m, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_tab, tab.data(), 8 * TAB * m, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_id, next_id, 8 * m, hipMemcpyHostToDevice));
+    if (nd) FLEET_TRY(f, hipMemcpy(d + o_dets, dets, 48 * nd, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_out, zero.data(), 8 * OUT * m, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_rec, zero.data(), 8 * SD * m, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_tick, tick, 4 * m, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_cs, cap_slots, 8 * m, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_n, n0.data(), 4 * m, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_doff, det_off, 4 * (m + 1), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_fleet_sim_tracker_eval, dim3((unsigned)m), dim3(64), 0, f->h->stream, (const double*)(d + o_par), (const double*)(d + o_adv),
+                       (const uint32_t*)(d + o_tick), (const int*)(d + o_cs), reinterpret_cast<double*>(d + o_tab), reinterpret_cast<int*>(d + o_n),
+                       reinterpret_cast<double*>(d + o_id), (const int*)(d + o_doff), (const double*)(d + o_dets), reinterpret_cast<double*>(d + o_out),
+                       reinterpret_cast<int*>(d + o_nout), reinterpret_cast<int*>(d + o_asg), reinterpret_cast<double*>(d + o_rec));
+    FLEET_TRY(f, hipGetLastError());
+    hipStream_t st = f->h->stream;
+    FLEET_TRY(f, hipMemcpyAsync(tracks_out, d + o_tab, 8 * TAB * m, hipMemcpyDeviceToHost, st));
+    FLEET_TRY(f, hipMemcpyAsync(n_tracks_out, d + o_n, 4 * m, hipMemcpyDeviceToHost, st));
+    FLEET_TRY(f, hipMemcpyAsync(next_id_out, d + o_id, 8 * m, hipMemcpyDeviceToHost, st));
+    FLEET_TRY(f, hipMemcpyAsync(out, d + o_out, 8 * OUT * m, hipMemcpyDeviceToHost, st));
+    FLEET_TRY(f, hipMemcpyAsync(n_out, d + o_nout, 4 * m, hipMemcpyDeviceToHost, st));
+    FLEET_TRY(f, hipMemcpyAsync(rec, d + o_rec, 8 * SD * m, hipMemcpyDeviceToHost, st));
+    if (nd) FLEET_TRY(f, hipMemcpyAsync(assign, d + o_asg, 4 * nd, hipMemcpyDeviceToHost, st));
+    FLEET_TRY(f, hipStreamSynchronize(st));
+    for (size_t q = 0; q < m; ++q)          // (rows behind the new count hold what the compaction left there)
+        for (size_t c = (size_t)(n_tracks_out[q] > 0 ? n_tracks_out[q] : 0) * RD; c < TAB; ++c) tracks_out[q * TAB + c] = NAN;
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))

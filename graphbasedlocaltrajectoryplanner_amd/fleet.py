@@ -17,6 +17,7 @@ from .planner import KEY_IDS, KEY_NAMES, PathsView, Planner, PlannerPathsIn, Pla
 from .sim import TELEMETRY_DOUBLES, TELEMETRY_FIELDS, telemetry_dict      # noqa: F401  (published here: fleet.TELEMETRY_FIELDS)
 from .sim import VEHICLE_DEFAULTS, VEHICLE_DOUBLES, VEHICLE_FIELDS, VEHICLE_PARAMS, vehicle_dict      # noqa: F401  (fleet.VEHICLE_FIELDS)
 from .sim import SENSOR_DOUBLES, SENSOR_FIELDS, SENSOR_PARAMS, sensor_dict, sensor_fov_cos      # noqa: F401  (fleet.SENSOR_FIELDS)
+from .sim import TRACK_CAP, TRACK_DOUBLES, TRACK_FIELDS, TRACKER_DEFAULTS, TRACKER_DOUBLES, TRACKER_FIELDS, TRACKER_PARAMS, tracker_dict      # noqa: F401
 from .sim import pack_events as sim_pack_events
 
 
@@ -61,6 +62,10 @@ class SimVehicleIn(C.Structure):           # ltpl_fleet_sim_vehicle_in
 
 class SimSensorIn(C.Structure):            # ltpl_fleet_sim_sensor_in
     _fields_ = [(k, C.c_void_p) for k in SENSOR_PARAMS] + [("seed", C.c_void_p), ("tick0", C.c_int32)]
+
+
+class SimTrackerIn(C.Structure):           # ltpl_fleet_sim_tracker_in
+    _fields_ = [(k, C.c_void_p) for k in TRACKER_PARAMS] + [("tick0", C.c_int32)]
 
 
 class SimRecordHead(C.Structure):         # ltpl_fleet_sim_record_head
@@ -125,6 +130,10 @@ class Fleet(Planner):
             f("sim_sensor").argtypes = [C.c_void_p, C.POINTER(SimSensorIn)]
             f("sim_sensor_read").argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
             f("sim_sensor_eval").argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 8
+        if hasattr(self.lib, "ltpl_fleet_sim_tracker"):
+            f("sim_tracker").argtypes = [C.c_void_p, C.POINTER(SimTrackerIn)]
+            f("sim_tracker_read").argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+            f("sim_tracker_eval").argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 16
         if hasattr(self.lib, "ltpl_fleet_friction"):
             f("friction").argtypes = [C.c_void_p, C.POINTER(FrictionIn)]
             f("friction_scale").argtypes = [C.c_void_p, C.c_void_p]
@@ -520,7 +529,8 @@ class Fleet(Planner):
         """Copies the simulation state of the ``planners`` (distinct indices; default: all) into snapshot slot ``slot`` (0 ..
         SIM_SNAPSHOTS - 1) on the device, replacing what the slot held (ltpl_fleet_sim_snapshot; after ``sim_setup``, before or after
         runs). State is what the tick kernels write: a planner's memory with its error word, its friction-row window, clock, action,
-        tracked pose, speed and heading, its opponents' positions and -- with telemetry on -- its record. What the caller set
+        tracked pose, speed and heading, its opponents' positions, with telemetry on its record and with ``sim_tracker`` set its track
+        table and next id (the tracker's parameters and statistics stay the destination's). What the caller set
         (preference lists, opponents' speeds, statics, zones, ``sim_vel`` arguments, friction maps, races, the recorder) is no part of it.
         ``sim_setup`` drops every snapshot; ``sim_telemetry`` invalidates their telemetry part."""
         if planners is None:
@@ -745,6 +755,75 @@ class Fleet(Planner):
         self._check(self._fn("sim_sensor_eval")(self.handle, m, pf.ctypes.data, params.ctypes.data, seeds.ctypes.data, ticks.ctypes.data,
                                                 off.ctypes.data, flat.ctypes.data, cause.ctypes.data, u.ctypes.data))
         return [cause[off[q]:off[q + 1]].copy() for q in range(m)], [u[off[q]:off[q + 1]].copy() for q in range(m)]
+
+    # ---- object tracker on the device -------------------------------------------------------------------------------------------------
+    def sim_tracker(self, gate=TRACKER_DEFAULTS["gate"], w_pos=TRACKER_DEFAULTS["w_pos"], w_vel=TRACKER_DEFAULTS["w_vel"],
+                    n_confirm=TRACKER_DEFAULTS["n_confirm"], n_coast=TRACKER_DEFAULTS["n_coast"], tick0=0):
+        """A multi-object tracker per planner between the staged object list (behind ``sim_sensor``) and the planner
+        (ltpl_fleet_sim_tracker; after ``sim_setup``, between runs at any time): detections are associated with predicted tracks inside
+        ``gate`` [m] (greedy nearest neighbour), a matched track is filtered with the prediction's weights ``w_pos`` / ``w_vel`` in
+        [0, 1), a new track is handed on from its ``n_confirm``-th detection, a confirmed track that is lost is coasted on for up to
+        ``n_coast`` ticks (scalars or one per planner). ``tick0``: the tracker tick of the next tick. ``gate=None`` switches the tracker
+        off. Tables and statistics start anew with every call. Host mirror: ``sim.TrackerModel``."""
+        if gate is None:
+            self._check(self._fn("sim_tracker")(self.handle, None))
+            return
+        n = self.n_scen
+        ti = SimTrackerIn()
+        val = dict(gate=gate, w_pos=w_pos, w_vel=w_vel, n_confirm=n_confirm, n_coast=n_coast)
+        keep = []
+        for name in TRACKER_PARAMS:
+            keep.append(np.ascontiguousarray(np.broadcast_to(np.asarray(val[name], np.int32 if name.startswith("n_") else np.float64), (n,))))
+            setattr(ti, name, keep[-1].ctypes.data)
+        ti.tick0 = int(tick0)
+        self._check(self._fn("sim_tracker")(self.handle, C.byref(ti)))
+
+    def sim_tracker_read(self, planners=None, raw=False):
+        """The tracker's statistics of every planner as a dict of named arrays (``sim.TRACKER_FIELDS``; ``raw=True``: the [n, 12] records)
+        (ltpl_fleet_sim_tracker_read). With ``planners`` (a list of indices): (records, tables, counts) -- their track tables
+        [len(planners), 96, 10] in the order of ``sim.TRACK_FIELDS``, unused rows NaN, and their track counts."""
+        out = np.zeros((self.n_scen, TRACKER_DOUBLES), np.float64)
+        if planners is None:
+            self._check(self._fn("sim_tracker_read")(self.handle, out.ctypes.data, TRACKER_DOUBLES, 0, None, None, None))
+            return out if raw else tracker_dict(out)
+        sel = np.ascontiguousarray(np.asarray(planners, np.int32).reshape(-1))
+        tabs = np.zeros((max(len(sel), 1), TRACK_CAP, TRACK_DOUBLES), np.float64)
+        cnt = np.zeros(max(len(sel), 1), np.int32)
+        self._check(self._fn("sim_tracker_read")(self.handle, out.ctypes.data, TRACKER_DOUBLES, len(sel), sel.ctypes.data, tabs.ctypes.data,
+                                                 cnt.ctypes.data))
+        return (out if raw else tracker_dict(out)), tabs[:len(sel)], cnt[:len(sel)]
+
+    def sim_tracker_eval(self, params, adv, tick, cap, slots, tracks, next_id, dets):
+        """The tracker's test hook (ltpl_fleet_sim_tracker_eval): independent cases on the device, one wave each, one tick each.
+        ``params`` [m, 5] in the order of ``sim.TRACKER_PARAMS``; ``adv``, ``tick``, ``cap``, ``slots``, ``next_id``: scalars or one per
+        case; ``tracks``: a list of m arrays [T_q, 10]; ``dets``: a list of m arrays [K_q, 6] = x, y, px, py, r, v. Returns a dict:
+        ``tables`` [m, 96, 10] (unused rows NaN), ``n_tracks`` [m], ``next_id`` [m], ``out`` (a list of [n_out_q, 6] arrays), ``assign`` (a
+        list of int32 arrays: matched id, -1 born, -2 overflow), ``rec`` [m, 12]; equals ``sim.TrackerModel.step`` bit for bit."""
+        tracks = [np.asarray(t, np.float64).reshape(-1, TRACK_DOUBLES) for t in tracks]
+        dets = [np.asarray(d, np.float64).reshape(-1, 6) for d in dets]
+        m = len(tracks)
+        if len(dets) != m:
+            raise ValueError("sim_tracker_eval: one table and one detection list per case expected")
+
+        def per(v, dt):
+            return np.ascontiguousarray(np.broadcast_to(np.asarray(v, dt), (m,)))
+        params = np.ascontiguousarray(np.broadcast_to(np.asarray(params, np.float64), (m, len(TRACKER_PARAMS))))
+        adv, tick, nid = per(adv, np.float64), per(tick, np.uint32), per(next_id, np.float64)
+        cs = np.ascontiguousarray(np.stack((per(cap, np.int32), per(slots, np.int32)), axis=1))
+        toff = np.ascontiguousarray(np.concatenate(([0], np.cumsum([t.shape[0] for t in tracks]))).astype(np.int32))
+        doff = np.ascontiguousarray(np.concatenate(([0], np.cumsum([d.shape[0] for d in dets]))).astype(np.int32))
+        tflat = np.ascontiguousarray(np.concatenate(tracks + [np.zeros((1, TRACK_DOUBLES))]))
+        dflat = np.ascontiguousarray(np.concatenate(dets + [np.zeros((1, 6))]))
+        mm = max(m, 1)
+        tabs, ntr, nid_out = np.zeros((mm, TRACK_CAP, TRACK_DOUBLES)), np.zeros(mm, np.int32), np.zeros(mm)
+        out, n_out, rec = np.zeros((mm, TRACK_CAP, 6)), np.zeros(mm, np.int32), np.zeros((mm, TRACKER_DOUBLES))
+        assign = np.zeros(int(doff[-1]) + 1, np.int32)
+        self._check(self._fn("sim_tracker_eval")(self.handle, m, params.ctypes.data, adv.ctypes.data, tick.ctypes.data, cs.ctypes.data, toff.ctypes.data,
+                                                 tflat.ctypes.data, nid.ctypes.data, doff.ctypes.data, dflat.ctypes.data, tabs.ctypes.data,
+                                                 ntr.ctypes.data, nid_out.ctypes.data, out.ctypes.data, n_out.ctypes.data, assign.ctypes.data,
+                                                 rec.ctypes.data))
+        return dict(tables=tabs[:m], n_tracks=ntr[:m], next_id=nid_out[:m], out=[out[q, :n_out[q]].copy() for q in range(m)],
+                    assign=[assign[doff[q]:doff[q + 1]].copy() for q in range(m)], rec=rec[:m])
 
     # ---- friction maps on the device ------------------------------------------------------------------------------------------------
     def friction(self, maps, map_idx=None, scale=1.0):

@@ -37,6 +37,12 @@ and of the sensor model of ``ltpl_fleet_sim_sensor`` (csrc/fleet_sensor.hpp) --
                      in the operation order of the header and of k_fleet_sim_sense, so the device's decisions;
   ``sensor_uniform`` / ``sensor_fov_cos`` / ``SENSOR_FIELDS`` / ``sensor_dict``   the dropout draw, the cone's cosine and the record.
 
+and of the object tracker of ``ltpl_fleet_sim_tracker`` (csrc/fleet_track.hpp) --
+
+  ``TrackerModel``   one planner's track table with memory from tick to tick: predict, greedy nearest-neighbour association, update,
+                     coasting, births and the list handed on, in the operation order of the header, so the device's bits;
+  ``TRACKER_FIELDS`` / ``TRACK_FIELDS`` / ``TRACKER_DEFAULTS`` / ``tracker_dict``   the statistics record, a table row and the defaults.
+
 Both simulators restate ``np.interp`` (numpy's ``arr_interp``) in the operation order of the device functions (``interp_at`` here,
 ``fleet::sim_interp`` there), so that host and device give the same bits as the reference.
 """
@@ -869,3 +875,168 @@ class SensorModel(object):
 
     def as_dict(self):
         return sensor_dict(self.rec)
+
+
+# ---- object tracker (ltpl_fleet_sim_tracker, include/ltpl_hip.h; csrc/fleet_track.hpp) ----------------------------------------------------
+# name, index, integer valued: the record of ltpl_fleet_sim_tracker_read (LTPL_FLEET_SIM_TRACKER_DOUBLES = 12 per planner)
+TRACKER_FIELDS = (("ticks", 0, True), ("n_det", 1, True), ("n_matched", 2, True), ("n_born", 3, True), ("n_confirmed", 4, True),
+                  ("n_del_tentative", 5, True), ("n_del_coast", 6, True), ("n_out", 7, True), ("n_out_coast", 8, True), ("n_withheld", 9, True),
+                  ("n_overflow", 10, True), ("tracks_max", 11, True))
+TRACKER_DOUBLES = 12
+# a row of a planner's track table (LTPL_FLEET_SIM_TRACK_DOUBLES = 10)
+TRACK_FIELDS = ("x", "y", "ex", "ey", "r", "v", "id", "hits", "miss", "born_tick")
+TRACK_DOUBLES = 10
+TRACK_CAP = 96
+TRACKER_PARAMS = ("gate", "w_pos", "w_vel", "n_confirm", "n_coast")
+TRACKER_DEFAULTS = dict(gate=5.0, w_pos=0.5, w_vel=0.5, n_confirm=2, n_coast=3)
+TRACKER_HORIZON = 0.2                     # s: the prediction horizon of the object ingestion (ObjectListInterface.py:121)
+TRACK_UNMATCHED, TRACK_OVERFLOW = -1, -2  # assignment of a detection that no track took: a track was born from it / the table was full
+
+
+def tracker_dict(rows):
+    """[n, 12] records as a dict of named int64 arrays."""
+    rows = np.asarray(rows, np.float64).reshape(-1, TRACKER_DOUBLES)
+    return {name: rows[:, i].astype(np.int64) for name, i, _ in TRACKER_FIELDS}
+
+
+def tracker_capacity(slots):
+    """C_p = min(96, 2 S_p)."""
+    return min(TRACK_CAP, 2 * int(slots))
+
+
+class TrackerModel(object):
+    """Scalar host mirror of ONE planner's tracker in the operation order of csrc/fleet_track.hpp: plain Python floats, + - * and
+    comparisons, so the device's bits. ``slots``: the planner's staging slots S_p (``cap`` = min(96, 2 S_p) unless given); ``adv`` = dt / 0.2
+    (or ``dt``). A detection is (x, y, px, py, r, v): a staged object. ``step(dets)`` -> the list handed on as [x, y, px, py, r, v] rows;
+    ``assign`` then holds per detection the id of the matched track, -1 (a track was born) or -2 (overflow), ``last`` the 12 counters of
+    the step; ``rec`` accumulates them."""
+
+    def __init__(self, slots, gate=TRACKER_DEFAULTS["gate"], w_pos=TRACKER_DEFAULTS["w_pos"], w_vel=TRACKER_DEFAULTS["w_vel"],
+                 n_confirm=TRACKER_DEFAULTS["n_confirm"], n_coast=TRACKER_DEFAULTS["n_coast"], tick0=0, adv=None, dt=None, cap=None):
+        self.slots = int(slots)
+        self.cap = tracker_capacity(slots) if cap is None else int(cap)
+        self.gate, self.w_pos, self.w_vel = float(gate), float(w_pos), float(w_vel)
+        self.n_confirm, self.n_coast = float(n_confirm), float(n_coast)
+        if adv is None:
+            adv = float(dt) / TRACKER_HORIZON
+        self.adv = float(adv)
+        self.tick = int(tick0)
+        self.tracks = []                  # rows of TRACK_FIELDS
+        self.next_id = 0.0
+        self.rec = np.zeros(TRACKER_DOUBLES)
+        self.assign, self.last, self.out_live = [], np.zeros(TRACKER_DOUBLES), 0
+
+    @property
+    def params(self):
+        return [self.gate, self.w_pos, self.w_vel, self.n_confirm, self.n_coast]
+
+    def table(self):
+        """[96, 10], unused rows NaN (the form of ``Fleet.sim_tracker_read``)."""
+        out = np.full((TRACK_CAP, TRACK_DOUBLES), np.nan)
+        if self.tracks:
+            out[:len(self.tracks)] = np.asarray(self.tracks, np.float64)
+        return out
+
+    def pairs(self, dets):
+        """[(d2, t, k)] of every track-detection pair, in (t, k) order."""
+        out = []
+        for t, r in enumerate(self.tracks):
+            sx, sy = self.adv * r[2], self.adv * r[3]
+            xp, yp = r[0] + sx, r[1] + sy
+            for k, d in enumerate(dets):
+                dx, dy = float(d[0]) - xp, float(d[1]) - yp
+                out.append((dx * dx + dy * dy, t, k))
+        return out
+
+    def candidates(self, dets):
+        """The pairs inside the gate in ascending (d2, t, k), and gate^2 (the margins of a scenario are read off both)."""
+        g2 = self.gate * self.gate
+        return sorted(c for c in self.pairs(dets) if c[0] <= g2), g2
+
+    @staticmethod
+    def _blend(det, w, pred):
+        diff = pred - det
+        part = w * diff
+        return det + part
+
+    def skip(self):
+        """A tick in which the planner is not live: the table is untouched, the tracker tick advances."""
+        self.tick += 1
+
+    def step(self, dets):
+        dets = [[float(v) for v in d] for d in dets]
+        K, T = len(dets), len(self.tracks)
+        if K > self.slots:
+            raise ValueError("TrackerModel: more detections than staging slots")
+        e = [(d[2] - d[0], d[3] - d[1]) for d in dets]
+        pred = []
+        for r in self.tracks:
+            sx, sy = self.adv * r[2], self.adv * r[3]
+            pred.append((r[0] + sx, r[1] + sy))
+        cand, _ = self.candidates(dets)
+        tm, dm = [-1] * T, [-1] * K
+        for _, t, k in cand:
+            if tm[t] < 0 and dm[k] < 0:
+                tm[t], dm[k] = k, t
+        c = np.zeros(TRACKER_DOUBLES)
+        self.assign = [TRACK_UNMATCHED] * K
+        new, live = [], []
+        for t, r in enumerate(self.tracks):
+            r = list(r)
+            xp, yp = pred[t]
+            if tm[t] >= 0:
+                k = tm[t]
+                d = dets[k]
+                r[0], r[1] = self._blend(d[0], self.w_pos, xp), self._blend(d[1], self.w_pos, yp)
+                r[2], r[3] = self._blend(e[k][0], self.w_vel, r[2]), self._blend(e[k][1], self.w_vel, r[3])
+                r[5] = self._blend(d[5], self.w_vel, r[5])
+                r[4] = d[4]
+                r[7] += 1.0
+                r[8] = 0.0
+                self.assign[k] = int(r[6])
+                c[2] += 1
+                c[4] += r[7] == self.n_confirm
+                new.append(r)
+                live.append(True)
+            elif r[7] < self.n_confirm:
+                c[5] += 1
+            else:
+                r[8] += 1.0
+                if r[8] > self.n_coast:
+                    c[6] += 1
+                else:
+                    r[0], r[1] = xp, yp
+                    new.append(r)
+                    live.append(False)
+        for k, d in enumerate(dets):
+            if dm[k] >= 0:
+                continue
+            if len(new) < self.cap:
+                new.append([d[0], d[1], e[k][0], e[k][1], d[4], d[5], self.next_id, 1.0, 0.0, float(self.tick)])
+                live.append(True)
+                self.next_id += 1.0
+                c[3] += 1
+                c[4] += 1.0 == self.n_confirm
+            else:
+                self.assign[k] = TRACK_OVERFLOW
+                c[10] += 1
+        self.tracks = new
+        out = [[r[0], r[1], r[0] + r[2], r[1] + r[3], r[4], r[5]] for r, lv in zip(new, live) if lv and r[7] >= self.n_confirm]
+        self.out_live = len(out)
+        for r, lv in zip(new, live):
+            if lv:
+                continue
+            if len(out) < self.slots:
+                out.append([r[0], r[1], r[0] + r[2], r[1] + r[3], r[4], r[5]])
+                c[8] += 1
+            else:
+                c[9] += 1
+        c[0], c[1], c[7], c[11] = 1, K, len(out), len(new)
+        self.last = c
+        self.rec[:11] += c[:11]
+        self.rec[11] = max(self.rec[11], c[11])
+        self.tick += 1
+        return out
+
+    def as_dict(self):
+        return tracker_dict(self.rec[None])

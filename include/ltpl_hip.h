@@ -63,7 +63,8 @@ extern "C" {
                                      ltpl_fleet_sim_snapshot / _snapshot_info / _snapshot_drop / _branch,
                                      ltpl_fleet_sim_noise / _estimate / _noise_draws,
                                      ltpl_fleet_sim_vehicle / _vehicle_read / _vehicle_step,
-                                     ltpl_fleet_sim_sensor / _sensor_read / _sensor_eval */
+                                     ltpl_fleet_sim_sensor / _sensor_read / _sensor_eval,
+                                     ltpl_fleet_sim_tracker / _tracker_read / _tracker_eval */
 
 /* status codes */
 #define LTPL_OK               0
@@ -1188,8 +1189,8 @@ int ltpl_fleet_sim_vehicle_step(ltpl_fleet* fleet, int32_t n_cases, const double
  * and the mates' view of one another keep acting on truth; offsets, compaction, the planner and the flight recorder see what the sensor
  * kept: the recorder's objects are the seen ones, and trace fields [5] .. [7] describe the list handed on. A planner that is not live is
  * skipped. SNAPSHOT / BRANCH copy neither the configuration nor the statistics: both stay the destination's own. No event kind sets it.
- * LIMITS: no memory between ticks -- no detection latency, no track persistence, no burst dropouts; an object the ingestion drops as off
- * the track neither is seen nor occludes.
+ * LIMITS: no memory between ticks -- detection latency and track persistence come from the tracker behind it (OBJECT TRACKER below); no
+ * burst dropouts; an object the ingestion drops as off the track neither is seen nor occludes.
  * THE CALL: after ltpl_fleet_sim_setup (which switches the sensor off) at any time between runs; in == NULL switches it off: the tick then
  * launches the kernels it launched before. Every argument is checked before the first HIP call, the message names the argument: every
  * array present; range not NaN and not negative (+inf allowed); r_near in [0, range]; fov_cos in [-1, 1]; occl finite and >= 0; p_drop
@@ -1215,6 +1216,88 @@ int ltpl_fleet_sim_sensor_read(ltpl_fleet* fleet, double* out, int32_t doubles_p
  * loss in the order of the table; u[i]: the dropout draw where one was made, NaN otherwise. Needs a fleet, no simulation. */
 int ltpl_fleet_sim_sensor_eval(ltpl_fleet* fleet, int32_t n_cases, const double* pose_f, const double* params, const uint64_t* seed,
                                const uint32_t* tick, const int32_t* obj_off, const double* objs, int32_t* cause, double* u);
+
+/* ------------------------------------------------------------------------------------------------------------------------------------------
+ * Additive to ABI v9 -- OBJECT TRACKER: a per-planner multi-object tracker with memory from tick to tick, run on the device inside
+ * ltpl_fleet_sim_run (csrc/fleet_sim.hpp: k_fleet_sim_track; the rule: csrc/fleet_track.hpp). It closes the perception chain
+ * truth -> noise -> sensor -> tracker -> planner: a new object is reported after n_confirm detections, a tracked object that is lost for
+ * up to n_coast ticks is coasted on, the reported position and speed are filtered. Off by default.
+ * ARITHMETIC: fp64, + - * and comparisons only, one fixed order (the library is built with -ffp-contract=off): the host mirror
+ * sim.TrackerModel and the device agree to the last bit. The one division, adv = dt / 0.2 (dt of ltpl_fleet_sim_setup over the prediction
+ * horizon of the object ingestion), is formed once per call.
+ * PER PLANNER p AND TICK: the detections k = 0 .. K - 1 are the staged on-track list as it stands behind the sensor model (or behind the
+ * ingestion and the mates): x, y (perceived), e = (px - x, py - y) the ingestion's displacement over 0.2 s, r, v. The planner's table holds
+ * T <= C_p = min(96, 2 S_p) tracks of LTPL_FLEET_SIM_TRACK_DOUBLES doubles, S_p the planner's staging slots (opponents + statics + mates):
+ *   [0] x  [1] y  [2] ex  [3] ey  [4] r  [5] v  [6] id  [7] hits  [8] miss  [9] born_tick
+ *   | # | step      | rule                                                                                                          |
+ *   | 1 | predict   | xp = x + adv ex, yp = y + adv ey (the product first, then the sum)                                            |
+ *   | 2 | associate | d2(t, k) = dx dx + dy dy, dx = x_k - xp_t, dy = y_k - yp_t; candidates d2 <= gate gate, taken in ascending     |
+ *   |   |           | (d2, t, k); accepted when neither its track nor its detection was accepted before (greedy nearest neighbour) |
+ *   | 3 | update    | matched: x = x_k + w_pos (xp - x_k), y likewise; ex = e_kx + w_vel (ex - e_kx), ey and v likewise; r = r_k;    |
+ *   |   |           | hits += 1; miss = 0. w = 0: the track is exactly the detection                                                 |
+ *   | 4 | miss      | unmatched: hits < n_confirm: deleted (a tentative track does not survive a miss); else miss += 1;             |
+ *   |   |           | miss > n_coast: deleted; else x = xp, y = yp, the rest kept (coasting)                                         |
+ *   | 5 | births    | unmatched detections in ascending k, while the table holds fewer than C_p tracks: the detection's values,      |
+ *   |   |           | id = next_id++ (per planner, from 0; never reused), hits = 1, miss = 0, born_tick = the tracker tick;          |
+ *   |   |           | otherwise counted as overflow                                                                                  |
+ *   | 6 | order     | the surviving old tracks in their previous order, then the births in detection order                          |
+ *   | 7 | hand on   | the confirmed tracks (hits >= n_confirm) matched or born this tick in table order, then the confirmed         |
+ *   |   |           | coasting tracks in table order until S_p objects are handed on (the rest: withheld). matched + born <= K      |
+ *   |   |           | <= S_p: a live detection is never withheld. Object: x, y, x + ex, y + ey, r, v                                 |
+ * The tracker tick = tick0 + the fleet ticks run since the call (it advances whether or not a planner is live). A planner that is not live
+ * is skipped: its table is untouched.
+ * STATISTICS per planner, LTPL_FLEET_SIM_TRACKER_DOUBLES doubles, updated in every tick in which the planner is live:
+ *   [0] ticks  [1] n_det  [2] n_matched  [3] n_born  [4] n_confirmed: tracks reaching n_confirm  [5] n_del_tentative  [6] n_del_coast
+ *   [7] n_out: objects handed on  [8] n_out_coast: coasting ones among them  [9] n_withheld  [10] n_overflow  [11] tracks_max
+ * IN THE TICK: behind k_fleet_sim_sense (or telemetry / the mates), in front of k_fleet_sim_offsets, only while a tracker is set. Telemetry,
+ * LTPL_SIM_WHEN_OPP_WITHIN and the mates keep acting on truth; offsets, compaction, the planner and the flight recorder see what the
+ * tracker hands on: the count of the tick and trace fields [5] .. [7] describe that list (NaN for an empty one).
+ *   | call                          | tracker                                                                                      |
+ *   | ltpl_fleet_sim_setup          | switched off                                                                                 |
+ *   | ltpl_fleet_sim_race           | (before the first run only) configuration kept, tables allocated for the new slot counts,    |
+ *   |                               | empty                                                                                        |
+ *   | ltpl_fleet_sim_snapshot       | table, track count and next_id are STATE: taken while a tracker is set; with the tracker off |
+ *   |                               | the snapshot is what it was before                                                           |
+ *   | ltpl_fleet_sim_branch         | a destination with a tracker takes table and next_id of a source that held tracker state (a  |
+ *   |                               | live planner while the tracker is set, a snapshot entry taken with one); a source without    |
+ *   |                               | empties the destination's table and sets next_id 0 (the start state); more tracks than the   |
+ *   |                               | destination's C_p: refused. Configuration and statistics stay the destination's own          |
+ *   | ltpl_fleet_sim_events         | no event kind sets it                                                                        |
+ *   | ltpl_fleet_sim_record / trace | the objects and fields [5] .. [7] are the list handed on                                     |
+ * LIMITS: coasting is straight-line along the last filtered displacement; a coasted position is not tested against the track bounds;
+ * velocity and displacement come from the object list, not from position differences; no track merging or splitting.
+ * THE CALL: after ltpl_fleet_sim_setup at any time between runs; in == NULL switches it off: the tick then launches the kernels it launched
+ * before. Every argument is checked before the first HIP call, the message names the argument: every array present; gate finite and
+ * > 0; w_pos, w_vel in [0, 1); n_confirm in 1 .. 255; n_coast in 0 .. 255; tick0 >= 0. Everything new is allocated before anything old
+ * is freed: a failing call keeps the previous tracker with its tables. A successful call starts with empty tables, next_id 0 and fresh
+ * statistics.
+ * ------------------------------------------------------------------------------------------------------------------------------------------ */
+#define LTPL_FLEET_SIM_TRACK_DOUBLES 10
+#define LTPL_FLEET_SIM_TRACKER_DOUBLES 12
+typedef struct {
+    const double* gate;              /* [n] m, finite, > 0 (every array is needed)                  */
+    const double* w_pos;             /* [n] weight of the prediction in the position update, [0, 1) */
+    const double* w_vel;             /* [n] the same for displacement and speed, [0, 1)             */
+    const int32_t* n_confirm;        /* [n] detections until a track is handed on, 1 .. 255          */
+    const int32_t* n_coast;          /* [n] ticks a confirmed track is coasted on, 0 .. 255          */
+    int32_t tick0;                   /* >= 0: the tracker tick of the next fleet tick               */
+} ltpl_fleet_sim_tracker_in;
+int ltpl_fleet_sim_tracker(ltpl_fleet* fleet, const ltpl_fleet_sim_tracker_in* in);
+/* rec_out: [n][LTPL_FLEET_SIM_TRACKER_DOUBLES], all planners. n_sel > 0: the tables of the planners sel_planners[n_sel] into
+ * tracks_out[n_sel][96][LTPL_FLEET_SIM_TRACK_DOUBLES] (unused rows NaN) and their track counts into n_tracks_out[n_sel]. No simulation, the
+ * tracker off, a wrong record size or a planner index out of range: LTPL_ERR_INVALID_ARG. */
+int ltpl_fleet_sim_tracker_read(ltpl_fleet* fleet, double* rec_out, int32_t doubles_per_planner, int32_t n_sel, const int32_t* sel_planners,
+                                double* tracks_out, int32_t* n_tracks_out);
+/* the test hook of the rule (k_fleet_sim_tracker_eval, one wave per case, the tick's own device functions): case q has params[q][5] = gate,
+ * w_pos, w_vel, n_confirm, n_coast (checked as above), adv[q], tick[q], cap_slots[q][2] = C, S (0 .. 96 each), the table
+ * tracks[trk_off[q] .. trk_off[q + 1])[10] (0 .. C rows), next_id[q] and the detections dets[det_off[q] .. det_off[q + 1])[6] = x, y, px, py,
+ * r, v (0 .. S of them). Out: tracks_out[q][96][10] (unused rows NaN), n_tracks_out[q], next_id_out[q], the list handed on out[q][96][6]
+ * (n_out[q] rows; the rest 0), assign[i] per detection: the id of the matched track, -1 unmatched (a track was born from it), -2 overflow;
+ * rec[q][12]: the counters of this one step. Needs a fleet, no simulation. */
+int ltpl_fleet_sim_tracker_eval(ltpl_fleet* fleet, int32_t n_cases, const double* params, const double* adv, const uint32_t* tick,
+                                const int32_t* cap_slots, const int32_t* trk_off, const double* tracks, const double* next_id,
+                                const int32_t* det_off, const double* dets, double* tracks_out, int32_t* n_tracks_out, double* next_id_out,
+                                double* out, int32_t* n_out, int32_t* assign, double* rec);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,7 @@
 """Closed-loop SIMULATION rate of a fleet (ltpl_fleet_sim_*): N planners, each with its own eight C2-style race-line opponents (SURVEY.md
 section 8d: s0_k = 250 + 280 k, vel_scale_k = 0.30 + 0.05 (k mod 4), here staggered by 10 m (p mod 16) per planner), run the example
 driver's loop on the device for T ticks without host work per tick.   tools/sim_rate.py [--planners 32768] [--ticks 200] [--no-tape]
-[--race-size K] [--friction-map] [--telemetry] [--record M [--record-depth D]] [--events] [--noise] [--vehicle] [--sensor [keep]] [--lib PATH]. Prints planner-ticks per second of sim_run (device time of the run) next to tape_run on the C2 tape (recorded inputs,
+[--race-size K] [--friction-map] [--telemetry] [--record M [--record-depth D]] [--events] [--noise] [--vehicle] [--sensor [keep]] [--tracker] [--lib PATH]. Prints planner-ticks per second of sim_run (device time of the run) next to tape_run on the C2 tape (recorded inputs,
 tools/fleet_rate.py). --race-size K > 1: races of K consecutive planners (ltpl_fleet_sim_race) that see one another, started 30 m apart
 along the race line with its heading; K = 1 (default) is the run without races. --friction-map: the same fleet on the friction grid of
 tests/golden/friction_grid.npz (ltpl_fleet_friction: rows evaluated on the device, grip factors 1.0 .. 0.7 over the planners) instead of
@@ -24,6 +24,10 @@ like --vehicle it puts the planners into races of one for the start heading; the
 sensor's kernel AND the changed planning work; the statistics are printed after the run. --sensor keep: every test evaluated and nothing
 lost (range 10^6 m, a cone of 359.999 degrees, occlusion with the radius times 10^-6, dropout 10^-12): the planning work of the run without
 a sensor plus the kernel.
+--tracker: every planner behind the object tracker (ltpl_fleet_sim_tracker, sim.TRACKER_DEFAULTS: gate 5 m, weights 0.5, confirmed by the
+second detection, coasted on for 3 ticks): k_fleet_sim_track in front of k_fleet_sim_offsets, behind k_fleet_sim_sense with --sensor (the
+tracker then bridges the sensor's dropouts: the planner sees more objects than behind the sensor alone); the statistics are printed after
+the run.
 --lib PATH: another build of
 the library (A/B against the parent's)."""
 import argparse
@@ -58,6 +62,7 @@ def main():
     ap.add_argument("--vehicle", action="store_true", help="every planner drives the vehicle model (sim.VEHICLE_DEFAULTS) instead of the ideal tracker")
     ap.add_argument("--sensor", nargs="?", const="lossy", default=None, choices=("lossy", "keep"),
                     help="every planner behind the sensor model: range, cone, near field, occlusion and dropout all active; 'keep': all evaluated, nothing lost")
+    ap.add_argument("--tracker", action="store_true", help="every planner behind the object tracker (sim.TRACKER_DEFAULTS)")
     ap.add_argument("--lib", default=None, help="path of the library to load (default: the in-tree build)")
     a = ap.parse_args()
     lat = Lattice.load(os.path.join(ROOT, "tests", "golden", "monteblanco_lattice.npz"))
@@ -119,6 +124,8 @@ def main():
             par = dict(range=300.0, fov_deg=240.0, r_near=5.0, occl=2.0, p_drop=0.1) if a.sensor == "lossy" else \
                 dict(range=1e6, fov_deg=359.999, r_near=0.0, occl=1e-6, p_drop=1e-12)
             fleet.sim_sensor(seed=np.arange(n, dtype=np.uint64) + np.uint64(1), **par)
+        if a.tracker:
+            fleet.sim_tracker()
         t0 = time.perf_counter()
         failed = 0
         try:
@@ -148,6 +155,12 @@ def main():
             print("  sensor: %d of %d objects seen; lost to range %d, cone %d, occlusion %d, dropout %d; %d planner-ticks with a lost object, smallest "
                   "blind clearance %.3f m" % (d["n_seen"].sum(), d["n_obj"].sum(), d["n_range"].sum(), d["n_fov"].sum(), d["n_occl"].sum(), d["n_drop"].sum(),
                                              d["blind_ticks"].sum(), np.min(d["blind_clear_min"])))
+        if a.tracker:
+            d = fleet.sim_tracker_read()
+            print("  tracker: %d detections, %d matched, %d tracks born, %d confirmed, %d tentative and %d coasted tracks deleted; %d objects handed on, "
+                  "%d of them coasting, %d withheld, %d overflows, up to %d tracks" % (
+                      d["n_det"].sum(), d["n_matched"].sum(), d["n_born"].sum(), d["n_confirmed"].sum(), d["n_del_tentative"].sum(), d["n_del_coast"].sum(),
+                      d["n_out"].sum(), d["n_out_coast"].sum(), d["n_withheld"].sum(), d["n_overflow"].sum(), d["tracks_max"].max()))
         if a.events:
             ft = fleet.sim_events_read()["fired_tick"].reshape(n, 3)
             print("  events: %d timed, %d opp_within and %d chained 'after' events fired of %d each (schedule tick %d)" % (
