@@ -33,6 +33,11 @@
 //                        sd.cnt and trace [5] .. [7] rewritten with the list handed on, lane 0 updates the planner's 12-double record
 //   k_fleet_sim_offsets  exclusive scan of the on-track counts -> veh_off (one workgroup)
 //   k_fleet_sim_compact  survivors into the fleet's object layout (one lane per planner)
+//   k_fleet_sim_predict  (prediction model set only: ltpl_fleet_sim_predictor; the rule: fleet_predict.hpp) in k_fleet_sim_compact's place,
+//                        one wave64 per planner: the staged survivors in LDS, per object the nearest race-line row (the wave strides
+//                        the rows, one wave minimum over (d2, row)), one lane per object for segment, offset and outcome, one lane per
+//                        (object, point) pair for the K points; own position + K points per object into the fleet's object layout
+//                        (pos_off[v] = (1 + K) v), lane 0 updates the planner's 11-double record
 //   k_fleet_sim_rec_paths / k_fleet_sim_rec_vel   (flight recorder on only: ltpl_fleet_sim_record) one wave64 per RECORDED planner: the
 //                        tick's paths behind paths_post, and its head, objects and trajectories behind the last velocity kernel, into
 //                        the planner's record of ring slot tick % depth. The tick then takes the unfused launch sequence
@@ -42,6 +47,7 @@
 #pragma once
 
 #include "fleet_noise.hpp"
+#include "fleet_predict.hpp"
 #include "fleet_sensor.hpp"
 #include "fleet_track.hpp"
 #include "fleet_vehicle.hpp"
@@ -977,7 +983,7 @@ __global__ __launch_bounds__(64) void k_fleet_sim_rec_paths(FleetArgs F, SimRec 
 
 // capture V, behind the last kernel of the velocity stage: the simulation's head of the tick, the objects the planner was handed (its slice
 // of the tick's object arrays) and what ltpl_fleet_get_trajectories would return now, rows trimmed to n_export, without vel_course
-__global__ __launch_bounds__(64) void k_fleet_sim_rec_vel(FleetArgs F, SimDev sd, SimRec rc, int slot, int tick)
+__global__ __launch_bounds__(64) void k_fleet_sim_rec_vel(FleetArgs F, SimDev sd, SimRec rc, int slot, int tick, int pos_stride /* positions per object */)
 {
     const int m = blockIdx.x, lane = threadIdx.x; const WaveX x{lane};
     const int p = rc.planners[m];
@@ -1011,8 +1017,9 @@ __global__ __launch_bounds__(64) void k_fleet_sim_rec_vel(FleetArgs F, SimDev sd
         for (int i = lane; i < cnt; i += 64) {
             const int v = v0 + i;
             ob[i] = sd.o_r[v]; ob[SIM_OBJ_CAP + i] = sd.o_v[v];
-            ob[2 * SIM_OBJ_CAP + i] = sd.o_px[2 * v]; ob[3 * SIM_OBJ_CAP + i] = sd.o_py[2 * v];
-            ob[4 * SIM_OBJ_CAP + i] = sd.o_px[2 * v + 1]; ob[5 * SIM_OBJ_CAP + i] = sd.o_py[2 * v + 1];
+            const size_t q = (size_t)pos_stride * v;          // own position and point 1 (the prediction model's further points are not recorded)
+            ob[2 * SIM_OBJ_CAP + i] = sd.o_px[q]; ob[3 * SIM_OBJ_CAP + i] = sd.o_py[q];
+            ob[4 * SIM_OBJ_CAP + i] = sd.o_px[q + 1]; ob[5 * SIM_OBJ_CAP + i] = sd.o_py[q + 1];
         }
     }
     for (int k = 0; k < nb; ++k) {
@@ -1056,6 +1063,135 @@ __global__ __launch_bounds__(64) void k_fleet_sim_compact(SimDev sd, int n)
         sd.o_r[v] = sd.g_r[g]; sd.o_v[v] = sd.g_v[g];
         sd.o_px[2 * v] = sd.g_x[g]; sd.o_py[2 * v] = sd.g_y[g]; sd.o_px[2 * v + 1] = sd.g_px[g]; sd.o_py[2 * v + 1] = sd.g_py[g];
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// prediction model (ltpl_fleet_sim_predictor, include/ltpl_hip.h; the rule: fleet_predict.hpp; host mirror: sim.PredictorModel).
+// Configuration and a statistics record, no state. While it is set the staging and the tick's object arrays hold 1 + K positions per
+// object (pos_off[v] = (1 + K) v) and k_fleet_sim_predict runs in k_fleet_sim_compact's place. The pointers live in a struct of their
+// own: no other kernel carries them.
+// ---------------------------------------------------------------------------------------------------------------------
+#define PRD_PARAMS 4                       // fleet::PredParams
+static_assert(fleet::PRS_DOUBLES == LTPL_FLEET_SIM_PREDICTOR_DOUBLES && sizeof(fleet::PredParams) == PRD_PARAMS * sizeof(double) &&
+              fleet::kPredMaxPoints == LTPL_FLEET_SIM_PREDICTOR_MAX_POINTS && SIM_OBJ_CAP * 2 <= MAX_POS, "predictor record layout");
+struct SimPred {
+    const double* par;                     // [N][PRD_PARAMS] in the order of fleet::PredParams
+    double* rec;                           // [N][LTPL_FLEET_SIM_PREDICTOR_DOUBLES]
+    int K;                                 // points per object
+};
+struct PredLds { double x[SIM_OBJ_CAP], y[SIM_OBJ_CAP], px[SIM_OBJ_CAP], py[SIM_OBJ_CAP], v[SIM_OBJ_CAP], s0[SIM_OBJ_CAP], d[SIM_OBJ_CAP]; int oc[SIM_OBJ_CAP]; };
+// objects in: five arrays (x, y, px, py, v), elements `stride` doubles apart
+struct PredIn { const double* c[5]; int stride; };
+
+__device__ __forceinline__ fleet::PredParams sim_pred_params(const double* q) { return fleet::PredParams{q[0], q[1], q[2], q[3]}; }
+
+// The prediction of one planner's `cnt` objects by one wave64 (every lane enters): own position and K points of object i into
+// ox / oy[(1 + K) i ..]; `outcome` (or null): per object its outcome; `rec` (or null): the planner's record, updated by lane 0.
+// Projection: the wave strides the table's rows per object (coalesced loads, one wave minimum over (d2, row): the exact first minimum),
+// then one lane per object decides; points: one lane per (object, point) pair in passes of 64.
+__device__ __forceinline__ void sim_predict_wave(int lane, const fleet::PredParams& P, const fleet::PredTable& R, int K, int cnt, const PredIn& in,
+                                                 double* ox, double* oy, int* outcome, double* rec, PredLds& L)
+{
+    for (int i = lane; i < cnt; i += 64) {
+        const size_t a = (size_t)i * in.stride;
+        L.x[i] = in.c[0][a]; L.y[i] = in.c[1][a]; L.px[i] = in.c[2][a]; L.py[i] = in.c[3][a]; L.v[i] = in.c[4][a];
+        L.oc[i] = 0;
+    }
+    __syncthreads();
+    if (P.mode == 2.0) {
+        for (int k = 0; k < cnt; ++k) {
+            if (!(L.v[k] > 0.0)) continue;             // (still: the row is not read; uniform)
+            const double xk = L.x[k], yk = L.y[k];
+            double bd = INFINITY; int bi = 0x7fffffff;
+            for (int i = lane; i < R.n; i += 64) {
+                const double d2 = fleet::pred_d2(xk, yk, R.x[i], R.y[i]);
+                if (d2 < bd) { bd = d2; bi = i; }
+            }
+            wave_min2(bd, bi);
+            if (lane == 0) L.oc[k] = bi == 0x7fffffff ? 0 : bi;
+        }
+        __syncthreads();
+    }
+    int n_oc[fleet::kPredOutcomes];
+#pragma unroll
+    for (int c = 0; c < fleet::kPredOutcomes; ++c) n_oc[c] = 0;
+    double d_big = 0.0;
+    const int stride = 1 + K;
+    for (int b0 = 0; b0 < cnt; b0 += 64) {
+        const int i = b0 + lane;
+        int oc = -1;
+        if (i < cnt) {
+            const fleet::PredProj o = fleet::pred_project(P, R, L.oc[i], L.x[i], L.y[i], L.px[i], L.py[i], L.v[i]);
+            oc = o.outcome;
+            L.oc[i] = oc; L.s0[i] = o.s0; L.d[i] = o.d;
+            if (oc == fleet::kPredTrack && fleet::pred_abs(o.d) > d_big) d_big = fleet::pred_abs(o.d);
+            ox[(size_t)stride * i] = L.x[i]; oy[(size_t)stride * i] = L.y[i];
+            if (outcome) outcome[i] = oc;
+        }
+#pragma unroll
+        for (int c = 0; c < fleet::kPredOutcomes; ++c) n_oc[c] += __popcll(__ballot(oc == c));
+    }
+    __syncthreads();
+    int wraps = 0;
+    const int pairs = cnt * K;
+    for (int b0 = 0; b0 < pairs; b0 += 64) {
+        const int q = b0 + lane;
+        bool w = false;
+        if (q < pairs) {
+            const int i = q / K, j = q - i * K + 1;
+            const fleet::PredProj o{L.oc[i], L.s0[i], L.d[i]};
+            const fleet::PredPoint pt = fleet::pred_point(P, R, K, j, o, L.x[i], L.y[i], L.px[i], L.py[i], L.v[i]);
+            ox[(size_t)stride * i + j] = pt.x; oy[(size_t)stride * i + j] = pt.y;
+            w = pt.wrapped;
+        }
+        wraps += __popcll(__ballot(w));
+    }
+    if (!rec) return;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) { const double o = __shfl_xor(d_big, m); if (o > d_big) d_big = o; }
+    if (lane == 0) {
+        rec[fleet::PRS_TICKS] += 1.0; rec[fleet::PRS_N_OBJ] += (double)cnt;
+#pragma unroll
+        for (int c = 0; c < fleet::kPredOutcomes; ++c) rec[fleet::PRS_OUTCOME0 + c] += (double)n_oc[c];
+        if (d_big > rec[fleet::PRS_D_MAX]) rec[fleet::PRS_D_MAX] = d_big;
+        rec[fleet::PRS_N_WRAP] += (double)wraps;
+    }
+}
+
+// behind k_fleet_sim_offsets, in k_fleet_sim_compact's place: the planner's staged survivors into the fleet's object layout at 1 + K
+// positions per object. A planner that is not live hands on what it staged (nothing) and leaves its record alone
+__global__ __launch_bounds__(64) void k_fleet_sim_predict(SimDev sd, SimPred pd)
+{
+    const int p = blockIdx.x, lane = threadIdx.x;
+    __shared__ PredLds L;
+    const int base = sd.obj_base[p], v0 = sd.veh_off[p];
+    int cnt = sd.cnt[p];
+    if (cnt > SIM_OBJ_CAP) cnt = SIM_OBJ_CAP;
+    const fleet::PredTable R{sd.race, sd.race + sd.n_rl, sd.race + (size_t)2 * sd.n_rl, sd.n_rl};
+    const PredIn in{{sd.g_x + base, sd.g_y + base, sd.g_px + base, sd.g_py + base, sd.g_v + base}, 1};
+    for (int i = lane; i < cnt; i += 64) { sd.o_r[v0 + i] = sd.g_r[base + i]; sd.o_v[v0 + i] = sd.g_v[base + i]; }
+    sim_predict_wave(lane, sim_pred_params(pd.par + (size_t)p * PRD_PARAMS), R, pd.K, cnt, in, sd.o_px + (size_t)(1 + pd.K) * v0,
+                     sd.o_py + (size_t)(1 + pd.K) * v0, nullptr, sd.live[p] ? pd.rec + (size_t)p * LTPL_FLEET_SIM_PREDICTOR_DOUBLES : nullptr, L);
+}
+
+// the test hook of the rule: one wave per case on the fleet's race table; objs[obj_off[q] ..][5] = x, y, px, py, v; out_x / out_y
+// [q][96][1 + kPredMaxPoints] (object i of the case from (1 + K) i on), outcome per object, rec[q][LTPL_FLEET_SIM_PREDICTOR_DOUBLES]
+__global__ __launch_bounds__(64) void k_fleet_sim_predictor_eval(SimDev sd, const double* par, int K, const int* obj_off, const double* objs, double* out_x,
+                                                                 double* out_y, int* outcome, double* rec)
+{
+    const int q = blockIdx.x, lane = threadIdx.x;
+    __shared__ PredLds L;
+    const int o0 = obj_off[q];
+    int cnt = obj_off[q + 1] - o0;
+    if (cnt > SIM_OBJ_CAP) cnt = SIM_OBJ_CAP;      // (refused by the host)
+    const fleet::PredTable R{sd.race, sd.race + sd.n_rl, sd.race + (size_t)2 * sd.n_rl, sd.n_rl};
+    PredIn in;
+#pragma unroll
+    for (int c = 0; c < 5; ++c) in.c[c] = objs + (size_t)o0 * 5 + c;
+    in.stride = 5;
+    constexpr size_t PER = (size_t)SIM_OBJ_CAP * (1 + fleet::kPredMaxPoints);
+    sim_predict_wave(lane, sim_pred_params(par + (size_t)q * PRD_PARAMS), R, K, cnt, in, out_x + (size_t)q * PER, out_y + (size_t)q * PER, outcome + o0,
+                     rec + (size_t)q * LTPL_FLEET_SIM_PREDICTOR_DOUBLES, L);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1116,6 +1252,10 @@ struct FleetSim {
     int trk_tick0 = 0, trk_tick = 0;        // tick0; ticks of ltpl_fleet_sim_run since the tracker was set
     std::vector<double> trk_par;            // [N][TRK_PARAMS] host copy (ltpl_fleet_sim_race allocates the tables again)
     std::vector<int> trk_cap;               // [N] host copy of tk.cap (ltpl_fleet_sim_branch compares track counts with it)
+    std::vector<void*> pred_allocs;         // parameters and records of ltpl_fleet_sim_predictor
+    SimPred pd{};
+    bool has_pred = false;                  // the tick launches k_fleet_sim_predict in k_fleet_sim_compact's place
+    int pos_stride = 2;                     // positions per object of the staging in use: 2, or 1 + K while a predictor is set
 };
 static void sim_free_list(std::vector<void*>& l)
 {
@@ -1134,6 +1274,7 @@ static void fleet_sim_free(FleetSim* s)
     sim_events_free(s->events);
     sim_free_list(s->stage_allocs); sim_free_list(s->race_allocs); sim_free_list(s->tele_allocs); sim_free_list(s->rec_allocs);
     sim_free_list(s->noise_allocs); sim_free_list(s->veh_allocs); sim_free_list(s->sens_allocs); sim_free_list(s->trk_allocs);
+    sim_free_list(s->pred_allocs);
     for (void* p : s->allocs) (void)hipFree(p);
     if (s->velt.d_buf) (void)hipFree(s->velt.d_buf);
     delete s;
@@ -1153,29 +1294,31 @@ static int sim_upload(ltpl_fleet* f, std::vector<void*>& allocs, const T* src, s
 template <class T>
 static int sim_upload(ltpl_fleet* f, FleetSim* s, const T* src, size_t n, T** out) { return sim_upload(f, s->allocs, src, n, out); }
 
-// staging slots of every planner from obj_base[p] on (slots[p] of them) and the tick's object arrays of the fleet (pos_off[v] = 2 v):
+// staging slots of every planner from obj_base[p] on (slots[p] of them) and the tick's object arrays of the fleet (pos_off[v] = stride v;
+// stride 2: own position and the ingestion's point; 1 + K with a prediction model):
 // allocated by sim_stage_alloc into a list of their own, which sim_stage_commit hands to the fleet (freeing the previous staging)
 struct SimStage {
     SimAllocs a;
-    int* obj_base = nullptr; int* pos_off = nullptr;
+    int* obj_base = nullptr; int* pos_off = nullptr; int stride = 2;
     double* g[8] = {};                      // g_x, g_y, g_px, g_py, g_r, g_v; g_tx, g_ty (written and read only while sensor noise is set)
     double* o[4] = {};                      // o_r, o_v, o_px, o_py
 };
-static int sim_stage_alloc(ltpl_fleet* f, const std::vector<int>& slots, SimStage* st)
+static int sim_stage_alloc(ltpl_fleet* f, const std::vector<int>& slots, int stride, SimStage* st)
 {
+    st->stride = stride;
     const int N = f->D.N;
     std::vector<int> base((size_t)N);
     int total = 0;
     for (int p = 0; p < N; ++p) { base[(size_t)p] = total; total += slots[(size_t)p]; }
     std::vector<int> pos_off((size_t)total + 1);
-    for (int v = 0; v <= total; ++v) pos_off[(size_t)v] = 2 * v;
+    for (int v = 0; v <= total; ++v) pos_off[(size_t)v] = stride * v;
     int rc;
     const double* z = nullptr;
 #define SIM_UP(dst, src, n) do { if ((rc = sim_upload(f, st->a.p, src, (size_t)(n), &dst))) return rc; } while (0)
     SIM_UP(st->obj_base, base.data(), N);
     for (double*& g : st->g) SIM_UP(g, z, total);
     SIM_UP(st->pos_off, pos_off.data(), total + 1);
-    SIM_UP(st->o[0], z, total); SIM_UP(st->o[1], z, total); SIM_UP(st->o[2], z, 2 * total); SIM_UP(st->o[3], z, 2 * total);
+    SIM_UP(st->o[0], z, total); SIM_UP(st->o[1], z, total); SIM_UP(st->o[2], z, (size_t)stride * total); SIM_UP(st->o[3], z, (size_t)stride * total);
 #undef SIM_UP
     return LTPL_OK;
 }
@@ -1188,6 +1331,7 @@ static void sim_stage_commit(FleetSim* s, SimStage* st)
     d.g_x = st->g[0]; d.g_y = st->g[1]; d.g_px = st->g[2]; d.g_py = st->g[3]; d.g_r = st->g[4]; d.g_v = st->g[5];
     d.o_r = st->o[0]; d.o_v = st->o[1]; d.o_px = st->o[2]; d.o_py = st->o[3];
     s->nz.g_tx = st->g[6]; s->nz.g_ty = st->g[7];
+    s->pos_stride = st->stride;
     s->ob = fleet::FObj{d.prev_action, d.t_now, d.veh_off, st->pos_off, d.o_r, d.o_v, d.o_px, d.o_py};
 }
 
@@ -1314,7 +1458,7 @@ try {
 #undef SIM_UP
     {
         SimStage st;
-        if ((rc = sim_stage_alloc(f, s->own, &st))) return rc;
+        if ((rc = sim_stage_alloc(f, s->own, 2, &st))) return rc;
         sim_stage_commit(s.get(), &st);
         s->slots = s->own;
     }
@@ -1416,7 +1560,8 @@ try {
         }
         hipLaunchKernelGGL(k_fleet_sim_offsets, dim3(1), dim3(1024), 0, st, (const int*)s.sd.cnt, N, s.sd.veh_off);
         FLEET_TRY(f, hipGetLastError());
-        hipLaunchKernelGGL(k_fleet_sim_compact, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, st, s.sd, N);
+        if (s.has_pred) hipLaunchKernelGGL(k_fleet_sim_predict, dim3(N), dim3(64), 0, st, s.sd, s.pd);
+        else hipLaunchKernelGGL(k_fleet_sim_compact, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, st, s.sd, N);
         FLEET_TRY(f, hipGetLastError());
         if (f->tape_fuse && !s.has_rec) {
             fleet::FPathsOut po{};
@@ -1433,7 +1578,8 @@ try {
         }
         if (s.has_rec) {
             // (the object arrays and veh_off through the simulation's pointers of this launch: ltpl_fleet_sim_race re-allocates the staging)
-            hipLaunchKernelGGL(k_fleet_sim_rec_vel, dim3(s.rec.M), dim3(64), 0, st, f->args, s.sd, s.rec, s.rec_tick % s.rec_depth, s.rec_tick);
+            hipLaunchKernelGGL(k_fleet_sim_rec_vel, dim3(s.rec.M), dim3(64), 0, st, f->args, s.sd, s.rec, s.rec_tick % s.rec_depth, s.rec_tick,
+                               s.pos_stride);
             FLEET_TRY(f, hipGetLastError());
             ++s.rec_tick;
         }
@@ -1489,6 +1635,11 @@ static int sim_check_race(ltpl_fleet* f, const ltpl_fleet_sim_race_in* in)
         for (int p = off[r]; p < off[r + 1]; ++p)
             if (f->sim->own[(size_t)p] + (off[r + 1] - off[r] - 1) > SIM_OBJ_CAP)
                 return bad("opponents + statics + mates above 96 for one planner", LTPL_ERR_CAPACITY);
+    if (f->sim->has_pred)                   // the path kernel's position arrays (ltpl_fleet_sim_predictor)
+        for (int r = 0; r < in->n_races; ++r)
+            for (int p = off[r]; p < off[r + 1]; ++p)
+                if ((f->sim->own[(size_t)p] + (off[r + 1] - off[r] - 1)) * f->sim->pos_stride > MAX_POS)
+                    return bad("(opponents + statics + mates) x (1 + n_points of the predictor) above 192 for one planner", LTPL_ERR_CAPACITY);
     return LTPL_OK;
 }
 
@@ -1513,7 +1664,7 @@ try {
     SimStage st;
     SimAllocs ra;
     int* d_lo = nullptr; int* d_hi = nullptr; double* d_len = nullptr;
-    if ((rc = sim_stage_alloc(f, slots, &st))) return rc;
+    if ((rc = sim_stage_alloc(f, slots, s.pos_stride, &st))) return rc;
     if ((rc = sim_upload(f, ra.p, lo.data(), (size_t)N, &d_lo))) return rc;
     if ((rc = sim_upload(f, ra.p, hi.data(), (size_t)N, &d_hi))) return rc;
     if ((rc = sim_upload(f, ra.p, in->length, (size_t)N, &d_len))) return rc;
@@ -2289,5 +2440,149 @@ try {
     FLEET_TRY(f, hipStreamSynchronize(st));
     for (size_t q = 0; q < m; ++q)          // (rows behind the new count hold what the compaction left there)
         for (size_t c = (size_t)(n_tracks_out[q] > 0 ? n_tracks_out[q] : 0) * RD; c < TAB; ++c) tracks_out[q * TAB + c] = NAN;
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+// ---------------------------------------------------------------------------------------------------------------------
+// prediction model (ltpl_fleet_sim_predictor, include/ltpl_hip.h; the rule: fleet_predict.hpp)
+// ---------------------------------------------------------------------------------------------------------------------
+static bool sim_pred_params_ok(double mode, double horizon, double relax, double d_max, std::string* why)
+{
+    if (!(mode == 0.0 || mode == 1.0 || mode == 2.0)) { *why = "mode must be 0, 1 or 2"; return false; }
+    if (!std::isfinite(horizon) || !(horizon > 0.0)) { *why = "horizon must be finite and positive"; return false; }
+    if (!(relax >= 0.0) || !(relax <= 1.0)) { *why = "relax must lie in [0, 1]"; return false; }
+    if (!(d_max >= 0.0)) { *why = "d_max must not be negative or NaN"; return false; }
+    return true;
+}
+
+// every argument is checked before the first HIP call
+static int sim_check_predictor(ltpl_fleet* f, const ltpl_fleet_sim_predictor_in* in)
+{
+    const int N = f->D.N;
+    auto bad = [&](const std::string& why, int code = LTPL_ERR_INVALID_ARG) { f->err = "fleet sim predictor: " + why; return code; };
+    if (!f->sim) return bad("ltpl_fleet_sim_setup first");
+    if (!in) return LTPL_OK;
+    if (in->n_points < 1 || in->n_points > LTPL_FLEET_SIM_PREDICTOR_MAX_POINTS) return bad("n_points must lie in 1 .. 8");
+    if (!in->mode) return bad("mode missing");
+    if (!in->horizon) return bad("horizon missing");
+    if (!in->relax) return bad("relax missing");
+    if (!in->d_max) return bad("d_max missing");
+    for (int p = 0; p < N; ++p) {
+        std::string why;
+        if (!sim_pred_params_ok((double)in->mode[p], in->horizon[p], in->relax[p], in->d_max[p], &why)) return bad("planner " + std::to_string(p) + ": " + why);
+    }
+    // the path kernel's per-position arrays hold MAX_POS entries and the simulation hands its objects on without the per-call check
+    for (int p = 0; p < N; ++p)
+        if (f->sim->slots[(size_t)p] * (1 + in->n_points) > MAX_POS)
+            return bad("planner " + std::to_string(p) + ": (opponents + statics + mates) x (1 + n_points) = " +
+                       std::to_string(f->sim->slots[(size_t)p] * (1 + in->n_points)) + " positions, above 192", LTPL_ERR_CAPACITY);
+    return LTPL_OK;
+}
+
+extern "C" int ltpl_fleet_sim_predictor(ltpl_fleet* f, const ltpl_fleet_sim_predictor_in* in)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    int rc = sim_check_predictor(f, in);
+    if (rc) return rc;
+    if ((rc = fleet_enter(f))) return rc;
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    FleetSim& s = *f->sim;
+    if (!in && !s.has_pred) return LTPL_OK;
+    // everything new is allocated first; the fleet keeps its previous predictor, its staging and its records unless every step succeeds
+    const int stride = in ? 1 + in->n_points : 2;
+    SimStage st;
+    if ((rc = sim_stage_alloc(f, s.slots, stride, &st))) return rc;
+    if (!in) {
+        sim_stage_commit(&s, &st);
+        sim_free_list(s.pred_allocs);
+        s.pd = SimPred{}; s.has_pred = false;
+        return LTPL_OK;
+    }
+    const size_t N = (size_t)f->D.N;
+    std::vector<double> par(N * PRD_PARAMS);
+    for (size_t p = 0; p < N; ++p) {
+        double* q = &par[p * PRD_PARAMS];
+        q[0] = (double)in->mode[p]; q[1] = in->horizon[p]; q[2] = in->relax[p]; q[3] = in->d_max[p];
+    }
+    SimAllocs al;
+    SimPred pd{};
+    double* d_par = nullptr;
+    if ((rc = sim_upload(f, al.p, par.data(), par.size(), &d_par))) return rc;
+    if ((rc = sim_upload(f, al.p, (const double*)nullptr, N * LTPL_FLEET_SIM_PREDICTOR_DOUBLES, &pd.rec))) return rc;
+    pd.par = d_par; pd.K = in->n_points;
+    sim_stage_commit(&s, &st);
+    sim_free_list(s.pred_allocs);
+    s.pred_allocs.swap(al.p);
+    s.pd = pd; s.has_pred = true;
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+extern "C" int ltpl_fleet_sim_predictor_read(ltpl_fleet* f, double* out, int32_t doubles_per_planner)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    auto bad = [&](const std::string& why) { f->err = "fleet sim predictor: " + why; return LTPL_ERR_INVALID_ARG; };
+    if (!f->sim) return bad("ltpl_fleet_sim_setup first");
+    if (!f->sim->has_pred) return bad("the predictor is off (ltpl_fleet_sim_predictor first)");
+    if (!out) return bad("out missing");
+    if (doubles_per_planner != LTPL_FLEET_SIM_PREDICTOR_DOUBLES) return bad("record size mismatch");
+    FLEET_TRY(f, hipSetDevice(f->h->device));
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    FLEET_TRY(f, hipMemcpy(out, f->sim->pd.rec, sizeof(double) * (size_t)f->D.N * LTPL_FLEET_SIM_PREDICTOR_DOUBLES, hipMemcpyDeviceToHost));
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+extern "C" int ltpl_fleet_sim_predictor_eval(ltpl_fleet* f, int32_t n_cases, int32_t n_points, const double* params, const int32_t* obj_off,
+                                             const double* objs, double* points, int32_t* outcome, double* rec)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    auto bad = [&](const std::string& why) { f->err = "fleet sim predictor eval: " + why; return LTPL_ERR_INVALID_ARG; };
+    if (!f->sim) return bad("ltpl_fleet_sim_setup first (the hook runs on the simulation's race-line table)");
+    if (n_cases < 0) return bad("n_cases must not be negative");
+    if (n_points < 1 || n_points > LTPL_FLEET_SIM_PREDICTOR_MAX_POINTS) return bad("n_points must lie in 1 .. 8");
+    if (n_cases == 0) return LTPL_OK;
+    if (!params || !obj_off || !rec) return bad("params / obj_off / rec missing");
+    if (obj_off[0] != 0) return bad("object offsets must start at 0");
+    for (int q = 0; q < n_cases; ++q) {
+        const std::string who = "case " + std::to_string(q) + ": ";
+        const int n = obj_off[q + 1] - obj_off[q];
+        if (n < 0 || n > SIM_OBJ_CAP) return bad(who + "0 .. 96 objects");
+        const double* P = params + (size_t)q * PRD_PARAMS;
+        std::string why;
+        if (!sim_pred_params_ok(P[0], P[1], P[2], P[3], &why)) return bad(who + why);
+    }
+    const size_t m = (size_t)n_cases, no = (size_t)obj_off[n_cases], K = (size_t)n_points;
+    if (no > 0 && (!objs || !points || !outcome)) return bad("objs / points / outcome missing");
+    constexpr size_t PER = (size_t)SIM_OBJ_CAP * (1 + LTPL_FLEET_SIM_PREDICTOR_MAX_POINTS), SD = LTPL_FLEET_SIM_PREDICTOR_DOUBLES;
+    int rc = fleet_enter(f);
+    if (rc) return rc;
+    Arena ar;     // one device block
+    const size_t o_par = ar.add(8 * PRD_PARAMS * m), o_objs = ar.add(40 * (no ? no : 1)), o_x = ar.add(8 * PER * m), o_y = ar.add(8 * PER * m),
+                 o_rec = ar.add(8 * SD * m), o_off = ar.add(4 * (m + 1)), o_oc = ar.add(4 * (no ? no : 1));
+    unsigned char* d = nullptr;
+    struct Guard { void* a = nullptr; ~Guard() { if (a) (void)hipFree(a); } } gd;
+    FLEET_TRY(f, hipMalloc(reinterpret_cast<void**>(&d), ar.size)); gd.a = d;
+    FLEET_TRY(f, hipMemset(d, 0, ar.size));
+    FLEET_TRY(f, hipMemcpy(d + o_par, params, 8 * PRD_PARAMS * m, hipMemcpyHostToDevice));
+    if (no) FLEET_TRY(f, hipMemcpy(d + o_objs, objs, 40 * no, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_off, obj_off, 4 * (m + 1), hipMemcpyHostToDevice));
+    hipStream_t st = f->h->stream;
+    FLEET_TRY(f, hipStreamSynchronize(st));
+    hipLaunchKernelGGL(k_fleet_sim_predictor_eval, dim3((unsigned)m), dim3(64), 0, st, f->sim->sd, (const double*)(d + o_par), n_points, (const int*)(d + o_off),
+                       (const double*)(d + o_objs), reinterpret_cast<double*>(d + o_x), reinterpret_cast<double*>(d + o_y), reinterpret_cast<int*>(d + o_oc),
+                       reinterpret_cast<double*>(d + o_rec));
+    FLEET_TRY(f, hipGetLastError());
+    std::vector<double> hx(PER * m), hy(PER * m);
+    FLEET_TRY(f, hipMemcpyAsync(hx.data(), d + o_x, 8 * PER * m, hipMemcpyDeviceToHost, st));
+    FLEET_TRY(f, hipMemcpyAsync(hy.data(), d + o_y, 8 * PER * m, hipMemcpyDeviceToHost, st));
+    FLEET_TRY(f, hipMemcpyAsync(rec, d + o_rec, 8 * SD * m, hipMemcpyDeviceToHost, st));
+    if (no) FLEET_TRY(f, hipMemcpyAsync(outcome, d + o_oc, 4 * no, hipMemcpyDeviceToHost, st));
+    FLEET_TRY(f, hipStreamSynchronize(st));
+    // points[object][1 + n_points][2]: the device's layout of the tick (own position, then the K points), objects in case order
+    for (size_t q = 0; q < m; ++q)
+        for (size_t i = 0, n = (size_t)(obj_off[q + 1] - obj_off[q]); i < n; ++i)
+            for (size_t j = 0; j <= K; ++j) {
+                double* o = points + (((size_t)obj_off[q] + i) * (1 + K) + j) * 2;
+                o[0] = hx[q * PER + (1 + K) * i + j]; o[1] = hy[q * PER + (1 + K) * i + j];
+            }
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))

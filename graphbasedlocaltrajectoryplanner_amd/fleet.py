@@ -18,6 +18,7 @@ from .sim import TELEMETRY_DOUBLES, TELEMETRY_FIELDS, telemetry_dict      # noqa
 from .sim import VEHICLE_DEFAULTS, VEHICLE_DOUBLES, VEHICLE_FIELDS, VEHICLE_PARAMS, vehicle_dict      # noqa: F401  (fleet.VEHICLE_FIELDS)
 from .sim import SENSOR_DOUBLES, SENSOR_FIELDS, SENSOR_PARAMS, sensor_dict, sensor_fov_cos      # noqa: F401  (fleet.SENSOR_FIELDS)
 from .sim import TRACK_CAP, TRACK_DOUBLES, TRACK_FIELDS, TRACKER_DEFAULTS, TRACKER_DOUBLES, TRACKER_FIELDS, TRACKER_PARAMS, tracker_dict      # noqa: F401
+from .sim import PREDICTOR_DEFAULTS, PREDICTOR_DOUBLES, PREDICTOR_FIELDS, PREDICTOR_MAX_POINTS, PREDICTOR_PARAMS, predictor_dict      # noqa: F401
 from .sim import pack_events as sim_pack_events
 
 
@@ -66,6 +67,10 @@ class SimSensorIn(C.Structure):            # ltpl_fleet_sim_sensor_in
 
 class SimTrackerIn(C.Structure):           # ltpl_fleet_sim_tracker_in
     _fields_ = [(k, C.c_void_p) for k in TRACKER_PARAMS] + [("tick0", C.c_int32)]
+
+
+class SimPredictorIn(C.Structure):         # ltpl_fleet_sim_predictor_in
+    _fields_ = [("n_points", C.c_int32)] + [(k, C.c_void_p) for k in PREDICTOR_PARAMS]
 
 
 class SimRecordHead(C.Structure):         # ltpl_fleet_sim_record_head
@@ -134,6 +139,10 @@ class Fleet(Planner):
             f("sim_tracker").argtypes = [C.c_void_p, C.POINTER(SimTrackerIn)]
             f("sim_tracker_read").argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
             f("sim_tracker_eval").argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 16
+        if hasattr(self.lib, "ltpl_fleet_sim_predictor"):
+            f("sim_predictor").argtypes = [C.c_void_p, C.POINTER(SimPredictorIn)]
+            f("sim_predictor_read").argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+            f("sim_predictor_eval").argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6
         if hasattr(self.lib, "ltpl_fleet_friction"):
             f("friction").argtypes = [C.c_void_p, C.POINTER(FrictionIn)]
             f("friction_scale").argtypes = [C.c_void_p, C.c_void_p]
@@ -824,6 +833,56 @@ class Fleet(Planner):
                                                  rec.ctypes.data))
         return dict(tables=tabs[:m], n_tracks=ntr[:m], next_id=nid_out[:m], out=[out[q, :n_out[q]].copy() for q in range(m)],
                     assign=[assign[doff[q]:doff[q + 1]].copy() for q in range(m)], rec=rec[:m])
+
+    # ---- prediction model on the device -----------------------------------------------------------------------------------------------
+    def sim_predictor(self, n_points=PREDICTOR_DEFAULTS["n_points"], mode=PREDICTOR_DEFAULTS["mode"], horizon=PREDICTOR_DEFAULTS["horizon"],
+                      relax=PREDICTOR_DEFAULTS["relax"], d_max=PREDICTOR_DEFAULTS["d_max"]):
+        """A multi-point prediction of every object a planner is handed, behind ``sim_sensor`` and ``sim_tracker`` and in front of the
+        path kernel (ltpl_fleet_sim_predictor; after ``sim_setup``, between runs at any time): every object reaches the planner with its
+        own position and ``n_points`` (1 .. 8, fleet-wide) predicted points over ``horizon`` [s] instead of the ingestion's single 0.2 s
+        point. ``mode`` 0: as ingested (the planner computes what it computes without a predictor), 1: straight line, 2: along the race
+        line at the object's lateral offset, of which the share ``relax`` in [0, 1] is given up by the last point; an object further than
+        ``d_max`` [m] from the race line, or moving against it, is predicted straight (scalars or one per planner). The planner takes its
+        closest object from a vehicle's LAST position, so with a long horizon a ``follow`` job may follow another car. Refused
+        (LTPL_ERR_CAPACITY) unless (opponents + statics + mates) (1 + n_points) <= 192 for every planner. ``n_points=None`` switches the
+        predictor off. The statistics start anew with every call. Host mirror: ``sim.PredictorModel``."""
+        if n_points is None:
+            self._check(self._fn("sim_predictor")(self.handle, None))
+            return
+        n = self.n_scen
+        pi = SimPredictorIn()
+        pi.n_points = int(n_points)
+        val = dict(mode=mode, horizon=horizon, relax=relax, d_max=d_max)
+        keep = []
+        for name in PREDICTOR_PARAMS:
+            keep.append(np.ascontiguousarray(np.broadcast_to(np.asarray(val[name], np.int32 if name == "mode" else np.float64), (n,))))
+            setattr(pi, name, keep[-1].ctypes.data)
+        self._check(self._fn("sim_predictor")(self.handle, C.byref(pi)))
+
+    def sim_predictor_read(self, raw=False):
+        """dict of named arrays (``sim.PREDICTOR_FIELDS``): live ticks, objects predicted, a count per outcome (as ingested, still,
+        straight by mode / ``d_max`` / direction / without a segment, along the track), the largest lateral offset used and the points
+        that wrapped (ltpl_fleet_sim_predictor_read). ``raw=True``: the [n, 11] records."""
+        out = np.zeros((self.n_scen, PREDICTOR_DOUBLES), np.float64)
+        self._check(self._fn("sim_predictor_read")(self.handle, out.ctypes.data, PREDICTOR_DOUBLES))
+        return out if raw else predictor_dict(out)
+
+    def sim_predictor_eval(self, n_points, params, objs):
+        """The predictor's test hook (ltpl_fleet_sim_predictor_eval): independent cases on the device, one wave each, on the race-line
+        table of ``sim_setup``. ``params`` [m, 4] in the order of ``sim.PREDICTOR_PARAMS``; ``objs``: a list of m arrays [n_q, 5] = x, y,
+        px, py, v (at most 96 rows). Returns (positions, outcomes, rec): per case the [n_q, 1 + n_points, 2] positions (own, then the
+        points) and the int32 outcomes, and the [m, 11] counters; equals ``sim.PredictorModel`` bit for bit."""
+        objs = [np.asarray(o, np.float64).reshape(-1, 5) for o in objs]
+        m, K = len(objs), int(n_points)
+        params = np.ascontiguousarray(np.broadcast_to(np.asarray(params, np.float64), (m, len(PREDICTOR_PARAMS))))
+        off = np.ascontiguousarray(np.concatenate(([0], np.cumsum([o.shape[0] for o in objs]))).astype(np.int32))
+        flat = np.ascontiguousarray(np.concatenate(objs + [np.zeros((1, 5))]))
+        total = int(off[-1])
+        pts = np.zeros((total + 1, 1 + max(K, 1), 2))
+        oc, rec = np.zeros(total + 1, np.int32), np.zeros((max(m, 1), PREDICTOR_DOUBLES))
+        self._check(self._fn("sim_predictor_eval")(self.handle, m, K, params.ctypes.data, off.ctypes.data, flat.ctypes.data, pts.ctypes.data,
+                                                   oc.ctypes.data, rec.ctypes.data))
+        return ([pts[off[q]:off[q + 1]].copy() for q in range(m)], [oc[off[q]:off[q + 1]].copy() for q in range(m)], rec[:m])
 
     # ---- friction maps on the device ------------------------------------------------------------------------------------------------
     def friction(self, maps, map_idx=None, scale=1.0):

@@ -43,6 +43,12 @@ and of the object tracker of ``ltpl_fleet_sim_tracker`` (csrc/fleet_track.hpp) -
                      coasting, births and the list handed on, in the operation order of the header, so the device's bits;
   ``TRACKER_FIELDS`` / ``TRACK_FIELDS`` / ``TRACKER_DEFAULTS`` / ``tracker_dict``   the statistics record, a table row and the defaults.
 
+and of the prediction model of ``ltpl_fleet_sim_predictor`` (csrc/fleet_predict.hpp) --
+
+  ``PredictorModel``   K predicted points per object in place of the ingestion's one: as ingested, straight line, or along the race line
+                       at the object's lateral offset, in the operation order of the header, so the device's bits;
+  ``PREDICTOR_FIELDS`` / ``PREDICTOR_DEFAULTS`` / ``predictor_dict``   the statistics record and the defaults.
+
 Both simulators restate ``np.interp`` (numpy's ``arr_interp``) in the operation order of the device functions (``interp_at`` here,
 ``fleet::sim_interp`` there), so that host and device give the same bits as the reference.
 """
@@ -1040,3 +1046,203 @@ class TrackerModel(object):
 
     def as_dict(self):
         return tracker_dict(self.rec[None])
+
+
+# ---- prediction model (ltpl_fleet_sim_predictor, include/ltpl_hip.h; csrc/fleet_predict.hpp) ----------------------------------------------
+# name, index, integer valued: the record of ltpl_fleet_sim_predictor_read (LTPL_FLEET_SIM_PREDICTOR_DOUBLES = 11 per planner)
+PREDICTOR_FIELDS = (("ticks", 0, True), ("n_obj", 1, True), ("n_ingested", 2, True), ("n_still", 3, True), ("n_straight_mode", 4, True),
+                    ("n_straight_dmax", 5, True), ("n_straight_dir", 6, True), ("n_straight_noseg", 7, True), ("n_track", 8, True),
+                    ("d_abs_max", 9, False), ("n_wrap", 10, True))
+PREDICTOR_DOUBLES = 11
+PREDICTOR_PARAMS = ("mode", "horizon", "relax", "d_max")
+PREDICTOR_DEFAULTS = dict(n_points=4, mode=2, horizon=2.0, relax=0.0, d_max=float("inf"))
+PREDICTOR_MAX_POINTS = 8
+PREDICTOR_MAX_POS = 192                   # positions per planner the path kernel holds: slots (1 + n_points) may not exceed it
+PREDICTOR_INGEST_T = 0.2                  # s: the horizon of the ingestion's point (ObjectListInterface.py:121)
+# outcome of an object, in the order of the record's counters [2] .. [8]
+PRED_INGESTED, PRED_STILL, PRED_STRAIGHT_MODE, PRED_STRAIGHT_DMAX, PRED_STRAIGHT_DIR, PRED_STRAIGHT_NOSEG, PRED_TRACK = range(7)
+
+
+def predictor_dict(rows):
+    """[n, 11] records as a dict of named arrays (counters as int64)."""
+    rows = np.asarray(rows, np.float64).reshape(-1, PREDICTOR_DOUBLES)
+    return {name: (rows[:, i].astype(np.int64) if is_int else rows[:, i].copy()) for name, i, is_int in PREDICTOR_FIELDS}
+
+
+def _fdiv(a, b):
+    """a / b of two floats by IEEE 754 (Python raises on a zero divisor)."""
+    try:
+        return a / b
+    except ZeroDivisionError:
+        with np.errstate(all="ignore"):
+            return float(np.float64(a) / np.float64(b))
+
+
+class PredictorModel(object):
+    """Scalar host mirror of the prediction model in the operation order of csrc/fleet_predict.hpp: plain Python floats, + - * / sqrt and
+    comparisons, so the device's bits. ``table``: a ``RaceLineTable`` (columns s_rl, x, y are read); ``n_points`` K in 1 .. 8, fleet-wide;
+    ``mode`` / ``horizon`` / ``relax`` / ``d_max``: scalars or one per planner. An object is (x, y, px, py, v): its staged position, the
+    ingestion's 0.2 s point and its speed. ``predict(p, objs)`` -> (points [len(objs), K, 2], outcomes); ``step`` does the same and
+    updates the planner's record ``rec[p]``; ``positions`` gives the [len(objs), 1 + K, 2] array the planner is handed."""
+
+    def __init__(self, n, table, n_points=PREDICTOR_DEFAULTS["n_points"], mode=PREDICTOR_DEFAULTS["mode"], horizon=PREDICTOR_DEFAULTS["horizon"],
+                 relax=PREDICTOR_DEFAULTS["relax"], d_max=PREDICTOR_DEFAULTS["d_max"]):
+        self.n, self.K = int(n), int(n_points)
+        if not 1 <= self.K <= PREDICTOR_MAX_POINTS:
+            raise ValueError("PredictorModel: n_points must lie in 1 .. 8")
+
+        def per(v):
+            return [float(x) for x in np.broadcast_to(np.asarray(v, np.float64), (self.n,))]
+        self.mode, self.horizon, self.relax, self.d_max = per(mode), per(horizon), per(relax), per(d_max)
+        self.S, self.X, self.Y = (np.ascontiguousarray(np.asarray(a, np.float64)) for a in (table.s_rl, table.x, table.y))
+        self.s, self.x, self.y = self.S.tolist(), self.X.tolist(), self.Y.tolist()
+        self.rows = len(self.s)
+        self.rec = np.zeros((self.n, PREDICTOR_DOUBLES))
+        self.last_wraps = 0
+
+    def params(self, p):
+        return [self.mode[p], self.horizon[p], self.relax[p], self.d_max[p]]
+
+    def nearest(self, x, y):
+        """Step 1: the first row with the smallest d2; a d2 that is NaN or +inf is never smaller (every one: row 0)."""
+        with np.errstate(all="ignore"):
+            dx, dy = self.X - x, self.Y - y
+            d2 = dx * dx + dy * dy
+        ok = d2 < np.inf
+        return int(np.argmin(np.where(ok, d2, np.inf))) if ok.any() else 0
+
+    def _candidate(self, a, x, y):
+        ex, ey = self.x[a + 1] - self.x[a], self.y[a + 1] - self.y[a]
+        l2 = ex * ex + ey * ey
+        if l2 == 0.0:
+            return None
+        t = ((x - self.x[a]) * ex + (y - self.y[a]) * ey) / l2
+        if t < 0.0:
+            t = 0.0
+        if t > 1.0:
+            t = 1.0
+        fx, fy = self.x[a] + t * ex, self.y[a] + t * ey
+        gx, gy = x - fx, y - fy
+        return t, gx * gx + gy * gy, ex, ey, l2
+
+    def project(self, p, x, y, px, py, v, istar=None):
+        """Steps 2 and 4 -> (outcome, s0, d, segment or -1)."""
+        mode = self.mode[p]
+        if mode == 0.0:
+            return PRED_INGESTED, 0.0, 0.0, -1
+        if not v > 0.0:
+            return PRED_STILL, 0.0, 0.0, -1
+        if mode == 1.0:
+            return PRED_STRAIGHT_MODE, 0.0, 0.0, -1
+        if istar is None:
+            istar = self.nearest(x, y)
+        a, c = -1, None
+        if istar >= 1:
+            c = self._candidate(istar - 1, x, y)
+            if c is not None:
+                a = istar - 1
+        if istar + 1 < self.rows:
+            hi = self._candidate(istar, x, y)
+            if hi is not None and (a < 0 or hi[1] < c[1]):
+                a, c = istar, hi
+        if a < 0:
+            return PRED_STRAIGHT_NOSEG, 0.0, 0.0, -1
+        t, _, ex, ey, l2 = c
+        s0 = self.s[a] + t * (self.s[a + 1] - self.s[a])
+        d = (ex * (y - self.y[a]) - ey * (x - self.x[a])) / math.sqrt(l2)
+        if d > self.d_max[p] or -d > self.d_max[p]:
+            return PRED_STRAIGHT_DMAX, s0, d, a
+        if (px - x) * ex + (py - y) * ey < 0.0:
+            return PRED_STRAIGHT_DIR, s0, d, a
+        return PRED_TRACK, s0, d, a
+
+    def _segment(self, x):
+        if not x >= self.s[0]:
+            return -1
+        return bisect.bisect_right(self.s, x) - 1
+
+    def _interp(self, x, fp, j):
+        xp, n = self.s, self.rows
+        if x != x:
+            return x
+        if j < 0:
+            return fp[0]
+        if j >= n - 1:
+            return fp[n - 1]
+        if xp[j] == x:
+            return fp[j]
+        slope = _fdiv(fp[j + 1] - fp[j], xp[j + 1] - xp[j])
+        r = slope * (x - xp[j]) + fp[j]
+        if r != r:
+            r = slope * (x - xp[j + 1]) + fp[j + 1]
+            if r != r and fp[j] == fp[j + 1]:
+                r = fp[j]
+        return r
+
+    def point(self, p, j, proj, x, y, px, py, v):
+        """Point j = 1 .. K -> (x, y, wrapped)."""
+        oc, s0, d = proj[0], proj[1], proj[2]
+        if oc in (PRED_INGESTED, PRED_STILL):
+            return px, py, False
+        K = self.K
+        tj = (self.horizon[p] * float(j)) / float(K)
+        if oc != PRED_TRACK:
+            cj = tj / PREDICTOR_INGEST_T
+            return x + (px - x) * cj, y + (py - y) * cj, False
+        sj = s0 + v * tj
+        wrapped = False
+        if sj >= self.s[-1]:
+            sj, wrapped = sj - self.s[-1], True
+        g = self._segment(sj)
+        X, Y = self._interp(sj, self.x, g), self._interp(sj, self.y, g)
+        q = 0 if g < 0 else min(g, self.rows - 2)
+        ex, ey = self.x[q + 1] - self.x[q], self.y[q + 1] - self.y[q]
+        l2 = ex * ex + ey * ey
+        if l2 == 0.0:
+            return X, Y, wrapped
+        ln = math.sqrt(l2)
+        ux, uy = ex / ln, ey / ln
+        dj = d * (1.0 - self.relax[p] * (float(j) / float(K)))
+        return X - dj * uy, Y + dj * ux, wrapped
+
+    def predict(self, p, objs):
+        pts, ocs, wraps, projs = np.zeros((len(objs), self.K, 2)), [], 0, []
+        for i, o in enumerate(objs):
+            x, y, px, py, v = (float(c) for c in o)
+            proj = self.project(p, x, y, px, py, v)
+            ocs.append(proj[0])
+            projs.append(proj)
+            for j in range(1, self.K + 1):
+                qx, qy, w = self.point(p, j, proj, x, y, px, py, v)
+                pts[i, j - 1] = (qx, qy)
+                wraps += w
+        self.last_wraps, self.last_proj = wraps, projs
+        return pts, ocs
+
+    def counters(self, objs, ocs):
+        """The record of ONE evaluation (the form of ``Fleet.sim_predictor_eval``'s ``rec``)."""
+        c = np.zeros(PREDICTOR_DOUBLES)
+        c[0], c[1] = 1.0, len(objs)
+        for oc in ocs:
+            c[2 + oc] += 1.0
+        c[9] = max([abs(pr[2]) for pr in self.last_proj if pr[0] == PRED_TRACK] + [0.0])
+        c[10] = self.last_wraps
+        return c
+
+    def step(self, p, objs):
+        """One live tick of planner ``p``: ``predict`` and the planner's record updated."""
+        pts, ocs = self.predict(p, objs)
+        c = self.counters(objs, ocs)
+        self.rec[p, :9] += c[:9]
+        self.rec[p, 9] = max(self.rec[p, 9], c[9])
+        self.rec[p, 10] += c[10]
+        return pts, ocs
+
+    def positions(self, p, objs, update=True):
+        """[len(objs), 1 + K, 2]: own position, then the K points -- what the planner is handed."""
+        pts, _ = self.step(p, objs) if update else self.predict(p, objs)
+        own = np.asarray([[float(o[0]), float(o[1])] for o in objs], np.float64).reshape(-1, 1, 2)
+        return np.concatenate((own, pts), axis=1)
+
+    def as_dict(self):
+        return predictor_dict(self.rec)

@@ -64,7 +64,8 @@ extern "C" {
                                      ltpl_fleet_sim_noise / _estimate / _noise_draws,
                                      ltpl_fleet_sim_vehicle / _vehicle_read / _vehicle_step,
                                      ltpl_fleet_sim_sensor / _sensor_read / _sensor_eval,
-                                     ltpl_fleet_sim_tracker / _tracker_read / _tracker_eval */
+                                     ltpl_fleet_sim_tracker / _tracker_read / _tracker_eval,
+                                     ltpl_fleet_sim_predictor / _predictor_read / _predictor_eval */
 
 /* status codes */
 #define LTPL_OK               0
@@ -1298,6 +1299,77 @@ int ltpl_fleet_sim_tracker_eval(ltpl_fleet* fleet, int32_t n_cases, const double
                                 const int32_t* cap_slots, const int32_t* trk_off, const double* tracks, const double* next_id,
                                 const int32_t* det_off, const double* dets, double* tracks_out, int32_t* n_tracks_out, double* next_id_out,
                                 double* out, int32_t* n_out, int32_t* assign, double* rec);
+
+/* ------------------------------------------------------------------------------------------------------------------------------------------
+ * Additive to ABI v9 -- PREDICTION MODEL: a per-planner multi-point prediction of the objects a planner is handed, run on the device inside
+ * ltpl_fleet_sim_run (csrc/fleet_sim.hpp: k_fleet_sim_predict; the rule: csrc/fleet_predict.hpp). The simulation's ingestion gives every
+ * object two positions, its own and one constant-velocity point 0.2 s ahead ("(at least) ... for delay comp.", ObjectListInterface.py:121-127);
+ * the reference expects a real prediction in object_el['prediction'], the path kernel blocks lattice edges against every position of a
+ * vehicle and takes the closest object from its LAST one. With the model set every object is handed on with 1 + K positions: its own and K
+ * predicted points over `horizon` seconds. It is the last link of truth -> noise -> sensor -> tracker -> prediction -> planner. Off by default.
+ * ARITHMETIC: fp64, + - * / sqrt and comparisons only, one fixed order (the library is built with -ffp-contract=off): the host mirror
+ * sim.PredictorModel and the device agree to the last bit.
+ * PER OBJECT: x, y, the ingestion's point px, py and the speed v as staged for the planner this tick (behind sensor and tracker). PER
+ * PLANNER: mode, horizon T [s], relax, d_max [m]. FLEET-WIDE: K = n_points and the simulation's race-line table S = s_rl, X, Y (n rows).
+ * Point j = 1 .. K belongs to the time t_j = (T j) / K.
+ *   | mode | points                                                                                                                  |
+ *   | 0    | as ingested: every point is (px, py). The planner computes what it computes without the model: the mask sees the same   |
+ *   |      | positions and the last position is the same point                                                                       |
+ *   | 1    | straight line: c_j = t_j / 0.2; (x + (px - x) c_j, y + (py - y) c_j)                                                    |
+ *   | 2    | along the track: (1) i* = the first table row with the smallest (X_i - x)^2 + (Y_i - y)^2; (2) of the segments           |
+ *   |      | (i* - 1, i*) and (i*, i* + 1) -- no wrap at the table's ends, a segment of length 0 is skipped -- the one whose foot point |
+ *   |      | (t clamped to [0, 1]) is nearer, ties to the lower: s0 = S_a + t (S_b - S_a), signed offset d = (ex (y - Y_a) - ey (x - X_a)) |
+ *   |      | / sqrt(ex ex + ey ey); (3) s_j = s0 + v t_j, minus S[n - 1] once if s_j >= S[n - 1] (a wrap, as the opponents wrap);     |
+ *   |      | X(s_j), Y(s_j) = np.interp on the segment of s_j, clamped at both ends as the opponents' evaluation is; (ux, uy) the     |
+ *   |      | unit direction of that segment (the first below S[0], the last at or above the end); d_j = d (1 - relax (j / K)); the    |
+ *   |      | point is (X(s_j) - d_j uy, Y(s_j) + d_j ux) (without the offset on a segment of length 0); (4) mode 1 instead when there |
+ *   |      | is no candidate segment, when |d| > d_max (equality stays), or when (px - x) ex + (py - y) ey < 0 on the chosen segment  |
+ *   |      | (the object moves against the track), tested in this order                                                              |
+ * In modes 1 and 2 an object with !(v > 0) gets K copies of (px, py). The full definition: the comment of csrc/fleet_predict.hpp.
+ * STATISTICS per planner, LTPL_FLEET_SIM_PREDICTOR_DOUBLES doubles, updated in every tick in which the planner is live:
+ *   [0] ticks  [1] n_obj: objects predicted  [2] n_ingested (mode 0)  [3] n_still  [4] n_straight_mode (mode 1)  [5] n_straight_dmax
+ *   [6] n_straight_dir  [7] n_straight_noseg  [8] n_track: along the track  [9] d_abs_max: the largest |d| used along the track
+ *   [10] n_wrap: points that wrapped
+ * IN THE TICK: k_fleet_sim_predict is launched INSTEAD of k_fleet_sim_compact, behind k_fleet_sim_offsets, only while a predictor is set:
+ * a fleet that never calls this entry point launches the kernels it launched before. The tick's object arrays then hold 1 + K positions
+ * per object (pos_off[v] = (1 + K) v).
+ *   | call                          | predictor                                                                                    |
+ *   | ltpl_fleet_sim_setup          | switched off                                                                                 |
+ *   | ltpl_fleet_sim_race           | configuration and records kept; the staging is allocated for the new slot counts at 1 + K     |
+ *   |                               | positions; refused with LTPL_ERR_CAPACITY, everything left as it was, when the new slot counts |
+ *   |                               | break the bound below                                                                        |
+ *   | snapshot / branch / events    | untouched: the predictor is configuration plus statistics, not state; no event kind sets it  |
+ *   | telemetry                     | keeps measuring on truth                                                                     |
+ *   | ltpl_fleet_sim_record         | the record's objects show own position and point 1; the record format is unchanged           |
+ * CAPACITY: the path kernel's per-position arrays hold 192 entries and the simulation hands its objects on without the per-call check, so
+ * the call is refused with LTPL_ERR_CAPACITY unless slots_p (1 + K) <= 192 for every planner, slots_p = opponents + statics + mates.
+ * KNOWN CONSEQUENCE: the planner's closest object is decided at the LAST position of every vehicle (the reference's rule for any supplied
+ * prediction), so with a long horizon it is decided at the far end of the prediction: which car a `follow` job follows may change.
+ * THE CALL: after ltpl_fleet_sim_setup at any time between runs; in == NULL switches it off and restores the two-position layout. Every
+ * argument is checked before the first HIP call, the message names the argument: n_points in 1 .. 8; every array present; mode 0, 1 or 2;
+ * horizon finite and > 0; relax in [0, 1]; d_max >= 0 (+inf allowed); the capacity bound. Everything new is allocated before anything old is
+ * freed: a refused or failing call keeps the previous predictor and its records. A successful call starts fresh records.
+ * ------------------------------------------------------------------------------------------------------------------------------------------ */
+#define LTPL_FLEET_SIM_PREDICTOR_DOUBLES 11
+#define LTPL_FLEET_SIM_PREDICTOR_MAX_POINTS 8
+typedef struct {
+    int32_t n_points;                /* K, 1 .. 8: predicted points per object, fleet-wide            */
+    const int32_t* mode;             /* [n] 0 as ingested, 1 straight line, 2 along the track         */
+    const double* horizon;           /* [n] s, finite, > 0                                            */
+    const double* relax;             /* [n] share of the lateral offset given up by the last point, [0, 1] */
+    const double* d_max;             /* [n] m, >= 0, +inf allowed: beyond it an object is predicted straight */
+} ltpl_fleet_sim_predictor_in;
+int ltpl_fleet_sim_predictor(ltpl_fleet* fleet, const ltpl_fleet_sim_predictor_in* in);
+/* out: [n][LTPL_FLEET_SIM_PREDICTOR_DOUBLES]. No simulation, the predictor off or a wrong record size: LTPL_ERR_INVALID_ARG. */
+int ltpl_fleet_sim_predictor_read(ltpl_fleet* fleet, double* out, int32_t doubles_per_planner);
+/* the test hook of the rule (k_fleet_sim_predictor_eval, one wave per case, the tick's own device functions, the fleet's race-line table: needs
+ * ltpl_fleet_sim_setup, no predictor): case q has params[q][4] = mode, horizon, relax, d_max (checked as above) and the objects
+ * objs[obj_off[q] .. obj_off[q + 1])[5] = x, y, px, py, v (0 .. 96 of them); n_points as above, the same for every case. Out:
+ * points[i][1 + n_points][2] per object in case order -- own position, then the K points, the tick's layout --, outcome[i] per object: 0 as
+ * ingested, 1 still, 2 straight by mode, 3 by d_max, 4 by direction, 5 without segment, 6 along the track; rec[q][11]: the counters of
+ * this one evaluation. */
+int ltpl_fleet_sim_predictor_eval(ltpl_fleet* fleet, int32_t n_cases, int32_t n_points, const double* params, const int32_t* obj_off,
+                                  const double* objs, double* points, int32_t* outcome, double* rec);
 
 #ifdef __cplusplus
 }

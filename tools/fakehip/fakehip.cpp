@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <set>
+#include <string>
 #include <vector>
 #include <map>
 #include <random>
@@ -22,6 +23,10 @@ std::mutex g_mu;
 std::map<void*, size_t> g_host; // page-locked allocations (hipPointerGetAttributes; zero-copy outputs live here)
 std::map<void*, size_t> g_dev;   // "device" allocations (FAKEHIP_GARBAGE: what a launch scribbles over)
 std::atomic<long> g_launches{0};
+// host stub -> (mangled) kernel name, from the module's registration, and launches per kernel name. Built on first use: the library's
+// registration runs from a static constructor that may come before this file's
+std::map<const void*, std::string>& kernel_names() { static auto* m = new std::map<const void*, std::string>(); return *m; }
+std::map<std::string, long>& launches_of() { static auto* m = new std::map<std::string, long>(); return *m; }
 struct CallCfg { dim3 grid, block; size_t shmem; hipStream_t stream; };
 thread_local CallCfg g_cfg[8];
 thread_local int g_ncfg = 0;
@@ -30,6 +35,14 @@ thread_local int g_ncfg = 0;
 extern "C" {
 
 long fakehip_launch_count() { return g_launches; }
+// launches so far of the kernels whose (mangled) name contains `part` (direct launches; graph nodes carry no name here)
+long fakehip_launches_of(const char* part)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    long n = 0;
+    for (const auto& k : launches_of()) if (k.first.find(part) != std::string::npos) n += k.second;
+    return n;
+}
 // failure injection: the n-th "device" allocation from now on fails (n <= 0: off). Error paths of ltpl_create and of the growing
 // staging buffers run under the sanitizers this way.
 static std::atomic<long> g_fail_malloc_in{0};
@@ -134,7 +147,7 @@ hipError_t __hipPopCallConfiguration(dim3* grid, dim3* block, size_t* shmem, hip
     if (g_ncfg >= 0 && g_ncfg < 8) { *grid = g_cfg[g_ncfg].grid; *block = g_cfg[g_ncfg].block; *shmem = g_cfg[g_ncfg].shmem; *stream = g_cfg[g_ncfg].stream; }
     return hipSuccess;
 }
-hipError_t hipLaunchKernel(const void*, dim3 grid, dim3 block, void**, size_t shmem, hipStream_t)
+hipError_t hipLaunchKernel(const void* fn, dim3 grid, dim3 block, void**, size_t shmem, hipStream_t)
 {
     // launch geometry sanity (what the real runtime would refuse)
     if (grid.x == 0 || grid.y == 0 || grid.z == 0 || block.x * block.y * block.z == 0 || block.x * block.y * block.z > 1024 || shmem > 160 * 1024) {
@@ -143,6 +156,11 @@ hipError_t hipLaunchKernel(const void*, dim3 grid, dim3 block, void**, size_t sh
         return hipErrorInvalidConfiguration;
     }
     ++g_launches;
+    {
+        std::lock_guard<std::mutex> lk(g_mu);
+        auto it = kernel_names().find(fn);
+        if (it != kernel_names().end()) ++launches_of()[it->second];
+    }
     // FAKEHIP_GARBAGE=<seed>: a launch overwrites every "device" allocation and every page-locked buffer with random words whose
     // magnitude is small often enough to pass for counts -- the host side must never turn a wrong device result into an out-of-bounds
     // access of its own (it may return nonsense or an error, not corrupt memory)
@@ -191,7 +209,11 @@ hipError_t hipGraphLaunch(hipGraphExec_t e, hipStream_t)
 }
 void** __hipRegisterFatBinary(const void*) { static void* dummy = nullptr; return &dummy; }
 void __hipUnregisterFatBinary(void**) {}
-void __hipRegisterFunction(void**, const void*, char*, const char*, unsigned, void*, void*, void*, void*, int*) {}
+void __hipRegisterFunction(void**, const void* host_fn, char*, const char* name, unsigned, void*, void*, void*, void*, int*)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (host_fn && name) kernel_names()[host_fn] = name;
+}
 void __hipRegisterVar(void**, void*, char*, const char*, int, size_t, int, int) {}
 
 }  // extern "C"

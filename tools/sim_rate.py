@@ -1,7 +1,7 @@
 """Closed-loop SIMULATION rate of a fleet (ltpl_fleet_sim_*): N planners, each with its own eight C2-style race-line opponents (SURVEY.md
 section 8d: s0_k = 250 + 280 k, vel_scale_k = 0.30 + 0.05 (k mod 4), here staggered by 10 m (p mod 16) per planner), run the example
 driver's loop on the device for T ticks without host work per tick.   tools/sim_rate.py [--planners 32768] [--ticks 200] [--no-tape]
-[--race-size K] [--friction-map] [--telemetry] [--record M [--record-depth D]] [--events] [--noise] [--vehicle] [--sensor [keep]] [--tracker] [--lib PATH]. Prints planner-ticks per second of sim_run (device time of the run) next to tape_run on the C2 tape (recorded inputs,
+[--race-size K] [--friction-map] [--telemetry] [--record M [--record-depth D]] [--events] [--noise] [--vehicle] [--sensor [keep]] [--tracker] [--predictor [K[:MODE]]] [--lib PATH]. Prints planner-ticks per second of sim_run (device time of the run) next to tape_run on the C2 tape (recorded inputs,
 tools/fleet_rate.py). --race-size K > 1: races of K consecutive planners (ltpl_fleet_sim_race) that see one another, started 30 m apart
 along the race line with its heading; K = 1 (default) is the run without races. --friction-map: the same fleet on the friction grid of
 tests/golden/friction_grid.npz (ltpl_fleet_friction: rows evaluated on the device, grip factors 1.0 .. 0.7 over the planners) instead of
@@ -28,6 +28,10 @@ a sensor plus the kernel.
 second detection, coasted on for 3 ticks): k_fleet_sim_track in front of k_fleet_sim_offsets, behind k_fleet_sim_sense with --sensor (the
 tracker then bridges the sensor's dropouts: the planner sees more objects than behind the sensor alone); the statistics are printed after
 the run.
+--predictor [K[:MODE]]: every planner behind the prediction model (ltpl_fleet_sim_predictor): K points per object (default 4) over 2 s in
+mode MODE (default 2, along the track, relax 0.5; 0: as ingested -- the planning work of the run without a predictor on 1 + K positions
+per object; 1: straight line): k_fleet_sim_predict in k_fleet_sim_compact's place, behind --sensor / --tracker when they are set; the
+statistics are printed after the run.
 --lib PATH: another build of
 the library (A/B against the parent's)."""
 import argparse
@@ -63,6 +67,8 @@ def main():
     ap.add_argument("--sensor", nargs="?", const="lossy", default=None, choices=("lossy", "keep"),
                     help="every planner behind the sensor model: range, cone, near field, occlusion and dropout all active; 'keep': all evaluated, nothing lost")
     ap.add_argument("--tracker", action="store_true", help="every planner behind the object tracker (sim.TRACKER_DEFAULTS)")
+    ap.add_argument("--predictor", nargs="?", const="4:2", default=None, metavar="K[:MODE]",
+                    help="every planner behind the prediction model: K points per object over 2 s, mode 0 / 1 / 2 (default 4:2)")
     ap.add_argument("--lib", default=None, help="path of the library to load (default: the in-tree build)")
     a = ap.parse_args()
     lat = Lattice.load(os.path.join(ROOT, "tests", "golden", "monteblanco_lattice.npz"))
@@ -126,6 +132,9 @@ def main():
             fleet.sim_sensor(seed=np.arange(n, dtype=np.uint64) + np.uint64(1), **par)
         if a.tracker:
             fleet.sim_tracker()
+        if a.predictor:
+            kp, _, mode = a.predictor.partition(":")
+            fleet.sim_predictor(n_points=int(kp), mode=int(mode or 2), horizon=2.0, relax=0.5)
         t0 = time.perf_counter()
         failed = 0
         try:
@@ -161,6 +170,12 @@ def main():
                   "%d of them coasting, %d withheld, %d overflows, up to %d tracks" % (
                       d["n_det"].sum(), d["n_matched"].sum(), d["n_born"].sum(), d["n_confirmed"].sum(), d["n_del_tentative"].sum(), d["n_del_coast"].sum(),
                       d["n_out"].sum(), d["n_out_coast"].sum(), d["n_withheld"].sum(), d["n_overflow"].sum(), d["tracks_max"].max()))
+        if a.predictor:
+            d = fleet.sim_predictor_read()
+            print("  predictor: %d objects predicted; as ingested %d, still %d, straight by mode %d / d_max %d / direction %d / no segment %d, along the "
+                  "track %d; largest offset %.3f m, %d points wrapped" % (
+                      d["n_obj"].sum(), d["n_ingested"].sum(), d["n_still"].sum(), d["n_straight_mode"].sum(), d["n_straight_dmax"].sum(),
+                      d["n_straight_dir"].sum(), d["n_straight_noseg"].sum(), d["n_track"].sum(), np.max(d["d_abs_max"]), d["n_wrap"].sum()))
         if a.events:
             ft = fleet.sim_events_read()["fired_tick"].reshape(n, 3)
             print("  events: %d timed, %d opp_within and %d chained 'after' events fired of %d each (schedule tick %d)" % (
