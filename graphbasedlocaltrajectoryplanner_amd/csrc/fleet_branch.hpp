@@ -5,18 +5,25 @@
 //            rows (Dims::gg_stride bytes of d_gg) when both sides have windows, now / sel / started / pos_x / pos_y / vel / theta / live,
 //            opp_s / opp_tic of its opponents, with telemetry on both sides its record, grid_s and prog, and the vehicle model's record
 //            (state and statistics, ltpl_fleet_sim_vehicle) where the DESTINATION has model 1, and the object tracker's table, track
-//            count and next_id (ltpl_fleet_sim_tracker) where the destination has a tracker;
+//            count and next_id (ltpl_fleet_sim_tracker) where the destination has a tracker, and the staged object list of the last tick
+//            (cnt and the first cnt entries of g_x, g_y, g_px, g_py, g_r) where the destination has a behaviour selector
+//            (ltpl_fleet_sim_selector), which reads that list at the head of the next tick;
 //   stays    the race line, the opponents' vel_scale / length, statics, zones, preference list, dt, n_export, the velocity arguments,
 //            friction map index and scale, race membership and length as a mate, contact radius, the recorder's ring and indices,
-//            the vehicle model's switch and parameters, the tracker's parameters and statistics.
+//            the vehicle model's switch and parameters, the tracker's parameters and statistics, the selector's parameters, ordered
+//            lists and statistics.
+// Behaviour selector, the mixed cases: a destination without a selector takes nothing; with one it takes the list of a source that held
+// one (a live planner while the selector is set, a snapshot entry taken with one), cut to the destination's staging slots where the
+// source staged more -- a source without leaves the destination an empty list (cnt 0): the first tick scores without objects.
 // Object tracker, the mixed cases: a destination without a tracker takes nothing; a destination with one takes the table of a source that
 // held tracker state (a live planner while the tracker is set, a snapshot entry taken with one) -- a source without empties the
 // destination's table and sets next_id 0, the tracker's start state; a source with more tracks than the destination's C_p is refused.
 // Vehicle model, the mixed cases: a destination on the ideal tracker (or a fleet without the model) takes no vehicle record and keeps its
 // NaN record, whatever the source drives; a destination with model 1 needs a source that had model 1 when it was copied (the live
 // planner now, the snapshot's planner when the snapshot was taken) -- otherwise the pair is refused with LTPL_ERR_INVALID_ARG.
-// Everything else the simulation holds per planner (cnt, prev_action, t_now, veh_off, the staging slots and object arrays, the job pools
-// of the velocity stage) is written by every tick before it is read.
+// Everything else the simulation holds per planner (prev_action, t_now, veh_off, g_v and the noise's true positions in the staging, the
+// tick's object arrays, the job pools of the velocity stage -- and cnt and the staging slots without a selector) is written by every tick
+// before it is read.
 // One kernel serves the three directions live -> snapshot, snapshot -> live and live -> live: it copies between two VIEWS, each a set of
 // base pointers indexed by an entry per pair. The live fleet is the view whose entries are planner indices; a snapshot is the same set of
 // arrays allocated per slot, with its planners packed (entry k = the k-th planner of the list) and an opponent offset table of its own.
@@ -30,6 +37,29 @@ struct BranchView {
     double* veh; const int* veh_model;                  // vehicle records (veh null: none); as a destination: the model of every entry
     double* trk; int* trk_n; double* trk_next; const int* trk_base;   // tracker: rows of entry e from row trk_base[e] on (trk_n null: none)
 };
+
+// the staged object list (behaviour selector only): cnt[e] entries of the five arrays from base[e] on; base[e + 1] - base[e] slots
+struct StagedView { int* cnt; double* g[5]; const int* base; };
+
+// behind k_fleet_sim_branch, only where the destination has a selector: one wave64 per pair. S.cnt null: the source holds no list
+__global__ __launch_bounds__(64) void k_fleet_sim_branch_staged(StagedView S, StagedView T, const int* __restrict__ src_entry,
+                                                                const int* __restrict__ dst_entry)
+{
+    const int k = blockIdx.x, t = threadIdx.x;
+    const int es = src_entry[k], ed = dst_entry[k];
+    const int cap = T.base[ed + 1] - T.base[ed];
+    int n = S.cnt ? S.cnt[es] : 0;
+    if (n > cap) n = cap;
+    if (n < 0) n = 0;
+    if (S.cnt) {
+        const int a = S.base[es], b = T.base[ed];
+        if (n > S.base[es + 1] - a) n = S.base[es + 1] - a;
+#pragma unroll
+        for (int c = 0; c < 5; ++c)
+            for (int q = t; q < n; q += 64) T.g[c][b + q] = S.g[c][a + q];
+    }
+    if (t == 0) T.cnt[ed] = n;
+}
 
 typedef unsigned int branch_u32x4 __attribute__((ext_vector_type(4)));
 #define BRANCH_THREADS 256
@@ -108,6 +138,7 @@ struct SimSnap {
     bool has_tele = false; int tele_gen = 0;     // a telemetry part, taken from the telemetry numbered tele_gen (FleetSim::tele_gen)
     std::vector<int> veh_model;             // [entries] the model of entry k when the snapshot was taken (empty: the model was off)
     bool has_trk = false;                   // a tracker part: tables of the planners' capacities, counts and next_id
+    StagedView stg{};                       // the staged lists (stg.cnt null: taken without a selector)
     uint64_t bytes = 0;
     bool held() const { return !planners.empty(); }
 };
@@ -130,6 +161,29 @@ static BranchView branch_live_view(const ltpl_fleet* f)
     if (s.has_veh) { v.veh = s.vh.rec; v.veh_model = s.vh.model; }
     if (s.has_trk) { v.trk = s.tk.rows; v.trk_n = s.tk.n; v.trk_next = s.tk.next_id; v.trk_base = s.tk.base; }
     return v;
+}
+
+static StagedView branch_live_staged(const ltpl_fleet* f)
+{
+    const SimDev& d = f->sim->sd;
+    return StagedView{d.cnt, {d.g_x, d.g_y, d.g_px, d.g_py, d.g_r}, d.obj_base};
+}
+// the staged lists of the pairs, behind branch_launch; T: a view with a selector's lists
+static int branch_launch_staged(ltpl_fleet* f, StagedView S, StagedView T, const std::vector<int>& src_entry, const std::vector<int>& dst_entry)
+{
+    const int n = (int)src_entry.size();
+    if (n == 0) return LTPL_OK;
+    SimAllocs a;
+    int* d_idx = nullptr;
+    std::vector<int> idx(src_entry);
+    idx.insert(idx.end(), dst_entry.begin(), dst_entry.end());
+    int rc = sim_upload(f, a.p, idx.data(), idx.size(), &d_idx);
+    if (rc) return rc;
+    hipStream_t st = f->h->stream;
+    hipLaunchKernelGGL(k_fleet_sim_branch_staged, dim3((unsigned)n), dim3(64), 0, st, S, T, (const int*)d_idx, (const int*)d_idx + n);
+    FLEET_TRY(f, hipGetLastError());
+    FLEET_TRY(f, hipStreamSynchronize(st));
+    return LTPL_OK;
 }
 
 // the pairs' entries go to the device in one allocation of the call ([src | dst]); the copy itself is one launch
@@ -242,10 +296,19 @@ try {
         { int* o = nullptr; SNAP_TAKE(&o, M + 1, tb.data()); v.trk_base = o; }
         q->has_trk = true;
     }
+    StagedView& sv = q->stg;
+    if (s.has_sel) {                                     // (a list is state only for a selector; slots as the planners have them now)
+        std::vector<int> sb(M + 1, 0);
+        for (size_t k = 0; k < M; ++k) sb[k + 1] = sb[k] + s.slots[(size_t)q->planners[k]];
+        SNAP_TAKE(&sv.cnt, M);
+        for (double*& g : sv.g) SNAP_TAKE(&g, (size_t)sb[M]);
+        { int* o = nullptr; SNAP_TAKE(&o, M + 1, sb.data()); sv.base = o; }
+    }
 #undef SNAP_TAKE
     std::vector<int> dst(M);
     for (size_t k = 0; k < M; ++k) dst[k] = (int)k;
     if ((rc = branch_launch(f, branch_live_view(f), v, q->planners, dst, nullptr))) return rc;
+    if (sv.cnt && (rc = branch_launch_staged(f, s.staged_valid ? branch_live_staged(f) : StagedView{}, sv, q->planners, dst))) return rc;
     q->allocs.swap(a.p);
     q->has_tele = s.has_tele; q->tele_gen = s.tele_gen; q->bytes = bytes;
     if (!s.snaps) s.snaps = new SimSnaps();
@@ -346,6 +409,13 @@ try {
     }
     if (q && !(q->has_tele && s.has_tele && q->tele_gen == s.tele_gen)) S.rec = nullptr;      // (a telemetry set since then started its records anew)
     if ((rc = branch_launch(f, S, branch_live_view(f), se, de, ms))) return rc;
+    if (s.has_sel) {                    // the staged lists: what the selector reads at the head of the next tick
+        if (!s.staged_valid) {          // (no list yet, or a fresh staging: the other planners keep the empty lists a run would start from)
+            FLEET_TRY(f, hipMemset(s.sd.cnt, 0, sizeof(int) * (size_t)N));
+            s.staged_valid = true;
+        }
+        if ((rc = branch_launch_staged(f, q ? q->stg : branch_live_staged(f), branch_live_staged(f), se, de))) return rc;
+    }
     f->cur.has_paths = false;           // (as after a run: a per-call calc_vel_profile needs its own calc_paths first)
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))

@@ -38,6 +38,11 @@
 //                        the rows, one wave minimum over (d2, row)), one lane per object for segment, offset and outcome, one lane per
 //                        (object, point) pair for the K points; own position + K points per object into the fleet's object layout
 //                        (pos_off[v] = (1 + K) v), lane 0 updates the planner's 11-double record
+//   k_fleet_sim_select   (behaviour selector set only: ltpl_fleet_sim_selector; the rule: fleet_select.hpp) at the HEAD of the tick, in front
+//                        of k_fleet_sim_step, one wave64 per planner: the previous exported set's rows (x, y, t) of up to four actions and
+//                        the previous tick's staged objects in LDS, time columns serially by one lane per action, row x object pairs over
+//                        the lanes, one wave minimum per action; the ORDERED preference list into a buffer of the selector's own, which
+//                        the step and mates kernels then get as SimDev::pref; lane 0 updates the planner's 12-double record
 //   k_fleet_sim_rec_paths / k_fleet_sim_rec_vel   (flight recorder on only: ltpl_fleet_sim_record) one wave64 per RECORDED planner: the
 //                        tick's paths behind paths_post, and its head, objects and trajectories behind the last velocity kernel, into
 //                        the planner's record of ring slot tick % depth. The tick then takes the unfused launch sequence
@@ -48,6 +53,7 @@
 
 #include "fleet_noise.hpp"
 #include "fleet_predict.hpp"
+#include "fleet_select.hpp"
 #include "fleet_sensor.hpp"
 #include "fleet_track.hpp"
 #include "fleet_vehicle.hpp"
@@ -1195,6 +1201,179 @@ __global__ __launch_bounds__(64) void k_fleet_sim_predictor_eval(SimDev sd, cons
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// behaviour selector (ltpl_fleet_sim_selector, include/ltpl_hip.h; the rule: fleet_select.hpp; host mirror: sim.SelectorModel).
+// Configuration and a statistics record, no state. While it is set k_fleet_sim_select runs in front of the step kernel and writes an
+// ordered copy of every planner's preference list into a buffer of its own (same pref_off); the step kernels get a SimDev whose `pref`
+// points there. The user's list is only read. The pointers live in a struct of their own: no other kernel carries them.
+// ---------------------------------------------------------------------------------------------------------------------
+#define SLC_PARAMS 6                       // fleet::SelParams
+static_assert(fleet::SLS_DOUBLES == LTPL_FLEET_SIM_SELECTOR_DOUBLES && sizeof(fleet::SelParams) == SLC_PARAMS * sizeof(double) &&
+              fleet::kSelMaxRows == LTPL_FLEET_SIM_MAX_EXPORT && fleet::kSelMaxPref == LTPL_FLEET_SIM_MAX_PREF && fleet::kSelMaxObj == SIM_OBJ_CAP &&
+              fleet::kSelEmergency == LTPL_ACT_EMERGENCY && LTPL_ACT_RIGHT == fleet::kSelActions - 1, "selector record layout");
+struct SimSel {
+    const double* par;                     // [N][SLC_PARAMS] in the order of fleet::SelParams
+    const int* on;                         // [N] 0: the planner's list is copied unchanged
+    int* ord;                              // the ordered lists, planner p's from pref_off[p] on
+    double* rec;                           // [N][LTPL_FLEET_SIM_SELECTOR_DOUBLES]
+};
+// an action's rows: columns s, x, y, vx of n rows (n < 0: not exported)
+struct SelRowsIn { const double* s; const double* x; const double* y; const double* v; int n; };
+// objects in: five arrays (x, y, px, py, r), elements `stride` doubles apart
+struct SelObjIn { const double* c[5]; int stride; };
+struct SelLds {
+    double x[fleet::kSelActions][LTPL_FLEET_SIM_MAX_EXPORT], y[fleet::kSelActions][LTPL_FLEET_SIM_MAX_EXPORT], t[fleet::kSelActions][LTPL_FLEET_SIM_MAX_EXPORT];
+    double ox[SIM_OBJ_CAP], oy[SIM_OBJ_CAP], opx[SIM_OBJ_CAP], opy[SIM_OBJ_CAP], orad[SIM_OBJ_CAP];
+    SelRowsIn rin[fleet::kSelActions];     // filled by the caller
+    fleet::SelAct act[fleet::kSelActions];
+    int user[8], ord[8], n_r[fleet::kSelActions], last[fleet::kSelActions];
+};
+
+__device__ __forceinline__ fleet::SelParams sim_sel_params(const double* q) { return fleet::SelParams{q[0], q[1], q[2], q[3], q[4], q[5]}; }
+
+// One evaluation of the rule by one wave64 (every lane enters; L.rin filled by the caller, no barrier needed behind it): the ordered list
+// into ord_out[0 .. n_pref), the four actions into act_out (or null), `rec` (or null) updated by lane 0.
+// Times: the time steps of a chunk of 64 rows by one lane each (the first standing row by ballot), then lane a adds up action a's column
+// serially -- the written order. Clearance: objects in turn, the window's rows over the lanes, one wave minimum per action on the key
+// (d, 256 o + i). Score, order and record: fleet_select.hpp's own functions on the LDS copy.
+__device__ __forceinline__ void sim_select_wave(int lane, const fleet::SelParams& P, const int* user, int n_pref, int sel_prev, bool emerg_exported,
+                                                int cnt, const SelObjIn& in, int* ord_out, fleet::SelAct* act_out, double* rec, SelLds& L)
+{
+    if (lane < n_pref) L.user[lane] = user[lane];
+    for (int i = lane; i < cnt; i += 64) {
+        const size_t a = (size_t)i * in.stride;
+        L.ox[i] = in.c[0][a]; L.oy[i] = in.c[1][a]; L.opx[i] = in.c[2][a]; L.opy[i] = in.c[3][a]; L.orad[i] = in.c[4][a];
+    }
+    __syncthreads();
+    unsigned exported = emerg_exported ? 1u << fleet::kSelEmergency : 0u;
+    for (int a = 0; a < fleet::kSelActions; ++a) {
+        const SelRowsIn r = L.rin[a];
+        if (r.n >= 0) exported |= 1u << a;
+        bool listed = false;
+        for (int e = 0; e < n_pref; ++e) listed = listed || L.user[e] == a;
+        const bool scored = listed && r.n >= 2;
+        int n_r = r.n;
+        if (scored) {
+            for (int b0 = 0; b0 < r.n; b0 += 64) {
+                const int i = b0 + lane;
+                bool stand = false;
+                if (i < r.n) {
+                    L.x[a][i] = r.x[i]; L.y[a][i] = r.y[i];
+                    if (i >= 1) L.t[a][i] = fleet::sel_dt(r.s[i - 1], r.s[i], r.v[i - 1], r.v[i], &stand);
+                }
+                const unsigned long long m = __ballot(stand);
+                if (m) { n_r = b0 + __ffsll((long long)m) - 1; break; }
+            }
+        }
+        if (lane == 0) {
+            L.act[a] = fleet::SelAct{(r.n >= 0 ? (int)fleet::kSelExported : 0) | (scored ? (int)fleet::kSelScored : 0), -1, 0.0, INFINITY, 0.0};
+            L.n_r[a] = n_r;
+        }
+    }
+    __syncthreads();
+    if (lane < fleet::kSelActions && (L.act[lane].flags & fleet::kSelScored)) {
+        const SelRowsIn r = L.rin[lane];
+        const int n_r = L.n_r[lane];
+        const int last = fleet::sel_prefix(L.t[lane], n_r, P.horizon);
+        L.last[lane] = last;
+        L.act[lane].vbar = fleet::sel_vbar(r.s, r.v[0], L.t[lane], r.n, n_r, last, P.horizon);
+    }
+    __syncthreads();
+    for (int a = 0; a < fleet::kSelActions; ++a) {
+        if (!(L.act[a].flags & fleet::kSelScored)) continue;       // (uniform)
+        const int last = L.last[a];
+        SimBest b{INFINITY, fleet::kSelNone};
+        for (int o = 0; o < cnt; ++o) {
+            const double ox = L.ox[o], oy = L.oy[o], opx = L.opx[o], opy = L.opy[o], orad = L.orad[o];
+            for (int i = lane; i <= last; i += 64) {
+                const double t = L.t[a][i];
+                if (t <= P.horizon) b = sim_better(b, SimBest{fleet::sel_gap(L.x[a][i], L.y[a][i], t, ox, oy, opx, opy, orad, P.r_ego), o * fleet::kSelMaxRows + i});
+            }
+        }
+        b = sim_wave_min(b);
+        if (lane == 0) {
+            L.act[a].clear = b.d; L.act[a].clear_obj = b.i == fleet::kSelNone ? -1 : b.i / fleet::kSelMaxRows;
+            fleet::sel_score(P, a, sel_prev, &L.act[a]);
+        }
+    }
+    __syncthreads();
+    if (lane < n_pref) {
+        const int r = fleet::sel_rank(lane, L.user, n_pref, L.act);
+        L.ord[r] = L.user[lane]; ord_out[r] = L.user[lane];
+    }
+    __syncthreads();
+    if (lane == 0 && rec) fleet::sel_record(rec, L.user, L.ord, n_pref, L.act, exported, sel_prev);
+    if (act_out && lane < fleet::kSelActions) act_out[lane] = L.act[lane];
+}
+
+// head of a tick, behind the events kernel and in front of the step kernel: planner p's ordered list from its user list `user`, the
+// exported set of the previous tick and the objects staged in it. Copied unchanged, the record left alone: a planner switched off in the
+// mask, one that has not started or has its error word set, a one-entry list
+__global__ __launch_bounds__(64) void k_fleet_sim_select(FleetArgs F, SimDev sd, SimSel sl)
+{
+    const int p = blockIdx.x, lane = threadIdx.x;
+    __shared__ SelLds L;
+    const int off = sd.pref_off[p];
+    int n_pref = sd.pref_off[p + 1] - off;
+    if (n_pref > LTPL_FLEET_SIM_MAX_PREF) n_pref = LTPL_FLEET_SIM_MAX_PREF;      // (refused by the host)
+    const fleet::Block B{F.state + F.D.stride * (size_t)p, F.D, nullptr};
+    const fleet::PlannerS* S = B.S();
+    if (!sl.on[p] || n_pref < 2 || !sd.started[p] || S->err) {
+        if (lane < n_pref) sl.ord[off + lane] = sd.pref[off + lane];
+        return;
+    }
+    int n_bp = S->n_bp;
+    if (n_bp > fleet::BPS) n_bp = fleet::BPS;
+    bool emerg = false;
+    if (lane < fleet::kSelActions) {
+        SelRowsIn r{nullptr, nullptr, nullptr, nullptr, -1};
+        for (int k = n_bp - 1; k >= 0; --k)             // (the first slot of an id, as the step kernel finds it)
+            if (S->bp_id[k] == lane) {
+                const fleet::Rows tr = B.bp(S->bp_slot[k]);
+                int n = S->bp_rows[k] < sd.n_export ? S->bp_rows[k] : sd.n_export;
+                if (n < 0) n = 0;
+                r = SelRowsIn{tr.col(0), tr.col(1), tr.col(2), tr.col(5), n};
+            }
+        L.rin[lane] = r;
+    }
+    for (int k = 0; k < n_bp; ++k) emerg = emerg || S->bp_id[k] == LTPL_ACT_EMERGENCY;
+    int cnt = sd.cnt[p];
+    if (cnt > SIM_OBJ_CAP) cnt = SIM_OBJ_CAP;
+    if (cnt < 0) cnt = 0;
+    const int base = sd.obj_base[p];
+    const SelObjIn in{{sd.g_x + base, sd.g_y + base, sd.g_px + base, sd.g_py + base, sd.g_r + base}, 1};
+    sim_select_wave(lane, sim_sel_params(sl.par + (size_t)p * SLC_PARAMS), sd.pref + off, n_pref, sd.sel[p], emerg, cnt, in, sl.ord + off, nullptr,
+                    sl.rec + (size_t)p * LTPL_FLEET_SIM_SELECTOR_DOUBLES, L);
+}
+
+// the test hook of the rule: one wave per case. lists[q][8] = n_pref, sel_prev, emergency exported (0 / 1), the user's entries;
+// n_rows[q][4] (-1: not exported); rows[q][4][4][256] = per action the columns s, x, y, vx; objs[obj_off[q] ..][5] = x, y, px, py, r.
+// Out: ord[q][5], act[q][4], rec[q][LTPL_FLEET_SIM_SELECTOR_DOUBLES] (in: the record before)
+__global__ __launch_bounds__(64) void k_fleet_sim_selector_eval(const double* par, const int* lists, const int* n_rows, const double* rows, const int* obj_off,
+                                                                 const double* objs, int* ord, fleet::SelAct* act, double* rec)
+{
+    const int q = blockIdx.x, lane = threadIdx.x;
+    __shared__ SelLds L;
+    const int* li = lists + (size_t)q * 8;
+    int n_pref = li[0];
+    if (n_pref > LTPL_FLEET_SIM_MAX_PREF) n_pref = LTPL_FLEET_SIM_MAX_PREF;      // (refused by the host)
+    if (lane < fleet::kSelActions) {
+        const double* c = rows + ((size_t)q * fleet::kSelActions + lane) * 4 * LTPL_FLEET_SIM_MAX_EXPORT;
+        int n = n_rows[(size_t)q * fleet::kSelActions + lane];
+        if (n > LTPL_FLEET_SIM_MAX_EXPORT) n = LTPL_FLEET_SIM_MAX_EXPORT;         // (refused by the host)
+        L.rin[lane] = SelRowsIn{c, c + LTPL_FLEET_SIM_MAX_EXPORT, c + 2 * LTPL_FLEET_SIM_MAX_EXPORT, c + 3 * LTPL_FLEET_SIM_MAX_EXPORT, n};
+    }
+    const int o0 = obj_off[q];
+    int cnt = obj_off[q + 1] - o0;
+    if (cnt > SIM_OBJ_CAP) cnt = SIM_OBJ_CAP;          // (refused by the host)
+    SelObjIn in;
+#pragma unroll
+    for (int c = 0; c < 5; ++c) in.c[c] = objs + (size_t)o0 * 5 + c;
+    in.stride = 5;
+    sim_select_wave(lane, sim_sel_params(par + (size_t)q * SLC_PARAMS), li + 3, n_pref, li[1], li[2] != 0, cnt, in, ord + (size_t)q * LTPL_FLEET_SIM_MAX_PREF,
+                    act + (size_t)q * fleet::kSelActions, rec + (size_t)q * LTPL_FLEET_SIM_SELECTOR_DOUBLES, L);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
 struct SimSnaps;                            // snapshot slots (fleet_branch.hpp, ltpl_fleet_sim_snapshot)
@@ -1256,6 +1435,11 @@ struct FleetSim {
     SimPred pd{};
     bool has_pred = false;                  // the tick launches k_fleet_sim_predict in k_fleet_sim_compact's place
     int pos_stride = 2;                     // positions per object of the staging in use: 2, or 1 + K while a predictor is set
+    std::vector<void*> sel_allocs;          // parameters, mask, ordered lists and records of ltpl_fleet_sim_selector
+    SimSel sl{};
+    bool has_sel = false;                   // the tick launches k_fleet_sim_select in front of the step kernel, which walks sl.ord
+    bool staged_valid = false;              // cnt and the staging slots hold the list of the last tick (false behind a re-allocation of the
+                                            // staging: a run with a selector then starts from empty lists)
 };
 static void sim_free_list(std::vector<void*>& l)
 {
@@ -1274,7 +1458,7 @@ static void fleet_sim_free(FleetSim* s)
     sim_events_free(s->events);
     sim_free_list(s->stage_allocs); sim_free_list(s->race_allocs); sim_free_list(s->tele_allocs); sim_free_list(s->rec_allocs);
     sim_free_list(s->noise_allocs); sim_free_list(s->veh_allocs); sim_free_list(s->sens_allocs); sim_free_list(s->trk_allocs);
-    sim_free_list(s->pred_allocs);
+    sim_free_list(s->pred_allocs); sim_free_list(s->sel_allocs);
     for (void* p : s->allocs) (void)hipFree(p);
     if (s->velt.d_buf) (void)hipFree(s->velt.d_buf);
     delete s;
@@ -1307,15 +1491,16 @@ static int sim_stage_alloc(ltpl_fleet* f, const std::vector<int>& slots, int str
 {
     st->stride = stride;
     const int N = f->D.N;
-    std::vector<int> base((size_t)N);
+    std::vector<int> base((size_t)N + 1);  // (entry N: the total; ltpl_fleet_sim_branch takes a planner's slot count from it)
     int total = 0;
     for (int p = 0; p < N; ++p) { base[(size_t)p] = total; total += slots[(size_t)p]; }
+    base[(size_t)N] = total;
     std::vector<int> pos_off((size_t)total + 1);
     for (int v = 0; v <= total; ++v) pos_off[(size_t)v] = stride * v;
     int rc;
     const double* z = nullptr;
 #define SIM_UP(dst, src, n) do { if ((rc = sim_upload(f, st->a.p, src, (size_t)(n), &dst))) return rc; } while (0)
-    SIM_UP(st->obj_base, base.data(), N);
+    SIM_UP(st->obj_base, base.data(), N + 1);
     for (double*& g : st->g) SIM_UP(g, z, total);
     SIM_UP(st->pos_off, pos_off.data(), total + 1);
     SIM_UP(st->o[0], z, total); SIM_UP(st->o[1], z, total); SIM_UP(st->o[2], z, (size_t)stride * total); SIM_UP(st->o[3], z, (size_t)stride * total);
@@ -1332,6 +1517,7 @@ static void sim_stage_commit(FleetSim* s, SimStage* st)
     d.o_r = st->o[0]; d.o_v = st->o[1]; d.o_px = st->o[2]; d.o_py = st->o[3];
     s->nz.g_tx = st->g[6]; s->nz.g_ty = st->g[7];
     s->pos_stride = st->stride;
+    s->staged_valid = false;                // (the new staging holds no list: see FleetSim::staged_valid)
     s->ob = fleet::FObj{d.prev_action, d.t_now, d.veh_off, st->pos_off, d.o_r, d.o_v, d.o_px, d.o_py};
 }
 
@@ -1517,23 +1703,32 @@ try {
     s.rec_host_valid = false;
     FLEET_TRY(f, hipStreamSynchronize(st));
     FLEET_TRY(f, hipEventRecord(e0, st));
+    // a selector reads the previous tick's staged list at the head of the tick: behind a re-allocation of the staging there is none
+    if (s.has_sel && !s.staged_valid) FLEET_TRY(f, hipMemsetAsync(s.sd.cnt, 0, sizeof(int) * (size_t)N, st));
+    s.staged_valid = true;
+    SimDev sds = s.sd;                      // what the step and mates kernels get: the selector's ordered lists in the user's place
+    if (s.has_sel) sds.pref = s.sl.ord;
     for (int k = 0; k < n_ticks; ++k) {
         double* tr = d_trace ? d_trace + rec * (size_t)k : nullptr;
         if (s.events && (rc = sim_events_tick(f, &t))) return rc;
+        if (s.has_sel) {
+            hipLaunchKernelGGL(k_fleet_sim_select, dim3(N), dim3(64), 0, st, f->args, s.sd, s.sl);
+            FLEET_TRY(f, hipGetLastError());
+        }
         if (s.has_noise) {
             // (the tick advances whether or not a planner is live: a draw depends on the fleet's tick, not on the planner's history)
             s.nz.tick = (uint32_t)s.noise_tick0 + (uint32_t)s.noise_tick++;
-            if (s.has_veh) hipLaunchKernelGGL(k_fleet_sim_step_noise_veh, dim3(N), dim3(64), 0, st, f->args, f->h->lat, s.sd, tr, s.nz, s.vh);
-            else hipLaunchKernelGGL(k_fleet_sim_step_noise, dim3(N), dim3(64), 0, st, f->args, f->h->lat, s.sd, tr, s.nz);
+            if (s.has_veh) hipLaunchKernelGGL(k_fleet_sim_step_noise_veh, dim3(N), dim3(64), 0, st, f->args, f->h->lat, sds, tr, s.nz, s.vh);
+            else hipLaunchKernelGGL(k_fleet_sim_step_noise, dim3(N), dim3(64), 0, st, f->args, f->h->lat, sds, tr, s.nz);
         } else if (s.has_veh) {
-            hipLaunchKernelGGL(k_fleet_sim_step_veh, dim3(N), dim3(64), 0, st, f->args, f->h->lat, s.sd, tr, s.vh);
+            hipLaunchKernelGGL(k_fleet_sim_step_veh, dim3(N), dim3(64), 0, st, f->args, f->h->lat, sds, tr, s.vh);
         } else {
-            hipLaunchKernelGGL(k_fleet_sim_step, dim3(N), dim3(64), 0, st, f->args, f->h->lat, s.sd, tr);
+            hipLaunchKernelGGL(k_fleet_sim_step, dim3(N), dim3(64), 0, st, f->args, f->h->lat, sds, tr);
         }
         FLEET_TRY(f, hipGetLastError());
         if (s.has_mates) {
-            if (s.has_noise) hipLaunchKernelGGL(k_fleet_sim_mates_noise, dim3(N), dim3(64), 0, st, f->h->lat, s.sd, tr, s.nz);
-            else hipLaunchKernelGGL(k_fleet_sim_mates, dim3(N), dim3(64), 0, st, f->h->lat, s.sd, tr);
+            if (s.has_noise) hipLaunchKernelGGL(k_fleet_sim_mates_noise, dim3(N), dim3(64), 0, st, f->h->lat, sds, tr, s.nz);
+            else hipLaunchKernelGGL(k_fleet_sim_mates, dim3(N), dim3(64), 0, st, f->h->lat, sds, tr);
             FLEET_TRY(f, hipGetLastError());
         }
         if (s.has_tele) {
@@ -2584,5 +2779,155 @@ try {
                 double* o = points + (((size_t)obj_off[q] + i) * (1 + K) + j) * 2;
                 o[0] = hx[q * PER + (1 + K) * i + j]; o[1] = hy[q * PER + (1 + K) * i + j];
             }
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+// ---------------------------------------------------------------------------------------------------------------------
+// behaviour selector (ltpl_fleet_sim_selector, include/ltpl_hip.h; the rule: fleet_select.hpp)
+// ---------------------------------------------------------------------------------------------------------------------
+static bool sim_sel_params_ok(const double* q, std::string* why)
+{
+    for (int c = 0; c < SLC_PARAMS; ++c) if (q[c] != q[c]) { *why = "a parameter is NaN"; return false; }
+    if (!(q[0] > 0.0)) { *why = "horizon must be positive"; return false; }
+    if (!(q[1] >= 0.0)) { *why = "r_ego must not be negative"; return false; }
+    if (!(q[4] >= 0.0)) { *why = "w_clear must not be negative"; return false; }
+    if (!(q[5] >= 0.0)) { *why = "w_switch must not be negative"; return false; }
+    return true;
+}
+
+// every argument is checked before the first HIP call
+static int sim_check_selector(ltpl_fleet* f, const ltpl_fleet_sim_selector_in* in, std::vector<double>* par)
+{
+    const int N = f->D.N;
+    auto bad = [&](const std::string& why) { f->err = "fleet sim selector: " + why; return LTPL_ERR_INVALID_ARG; };
+    if (!f->sim) return bad("ltpl_fleet_sim_setup first");
+    if (!in) return LTPL_OK;
+    if (!in->on) return bad("on missing");
+    if (!in->horizon) return bad("horizon missing");
+    if (!in->r_ego) return bad("r_ego missing");
+    if (!in->c_hard) return bad("c_hard missing");
+    if (!in->c_soft) return bad("c_soft missing");
+    if (!in->w_clear) return bad("w_clear missing");
+    if (!in->w_switch) return bad("w_switch missing");
+    par->resize((size_t)N * SLC_PARAMS);
+    for (int p = 0; p < N; ++p) {
+        double* q = &(*par)[(size_t)p * SLC_PARAMS];
+        q[0] = in->horizon[p]; q[1] = in->r_ego[p]; q[2] = in->c_hard[p]; q[3] = in->c_soft[p]; q[4] = in->w_clear[p]; q[5] = in->w_switch[p];
+        std::string why;
+        if (!sim_sel_params_ok(q, &why)) return bad("planner " + std::to_string(p) + ": " + why);
+    }
+    return LTPL_OK;
+}
+
+extern "C" int ltpl_fleet_sim_selector(ltpl_fleet* f, const ltpl_fleet_sim_selector_in* in)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    std::vector<double> par;
+    int rc = sim_check_selector(f, in, &par);
+    if (rc) return rc;
+    if ((rc = fleet_enter(f))) return rc;
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    FleetSim& s = *f->sim;
+    if (!in) {
+        sim_free_list(s.sel_allocs);
+        s.sl = SimSel{}; s.has_sel = false;
+        return LTPL_OK;
+    }
+    // everything new is allocated first; the fleet keeps its previous selector and its records unless every step succeeds
+    const size_t N = (size_t)f->D.N, n_pref = (size_t)s.pref_off[N];
+    std::vector<int> on(N);
+    for (size_t p = 0; p < N; ++p) on[p] = in->on[p] ? 1 : 0;
+    std::vector<double> rec(N * LTPL_FLEET_SIM_SELECTOR_DOUBLES, 0.0);
+    for (size_t p = 0; p < N; ++p) rec[p * LTPL_FLEET_SIM_SELECTOR_DOUBLES + fleet::SLS_CLEAR_MIN] = INFINITY;
+    SimAllocs al;
+    SimSel sl{};
+    double* d_par = nullptr; int* d_on = nullptr;
+    if ((rc = sim_upload(f, al.p, par.data(), par.size(), &d_par))) return rc;
+    if ((rc = sim_upload(f, al.p, on.data(), N, &d_on))) return rc;
+    if ((rc = sim_upload(f, al.p, (const int*)nullptr, n_pref, &sl.ord))) return rc;
+    if ((rc = sim_upload(f, al.p, rec.data(), rec.size(), &sl.rec))) return rc;
+    FLEET_TRY(f, hipMemcpy(sl.ord, s.sd.pref, sizeof(int) * n_pref, hipMemcpyDeviceToDevice));     // until the first tick: the user's lists
+    sl.par = d_par; sl.on = d_on;
+    sim_free_list(s.sel_allocs);
+    s.sel_allocs.swap(al.p);
+    s.sl = sl; s.has_sel = true;
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+extern "C" int ltpl_fleet_sim_selector_read(ltpl_fleet* f, double* out, int32_t doubles_per_planner, int32_t* ordered, int32_t n_ordered)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    auto bad = [&](const std::string& why) { f->err = "fleet sim selector: " + why; return LTPL_ERR_INVALID_ARG; };
+    if (!f->sim) return bad("ltpl_fleet_sim_setup first");
+    if (!f->sim->has_sel) return bad("the selector is off (ltpl_fleet_sim_selector first)");
+    if (!out) return bad("out missing");
+    if (doubles_per_planner != LTPL_FLEET_SIM_SELECTOR_DOUBLES) return bad("record size mismatch");
+    const size_t N = (size_t)f->D.N;
+    if (ordered && n_ordered != f->sim->pref_off[N])
+        return bad("n_ordered is " + std::to_string(n_ordered) + ", the preference lists hold " + std::to_string(f->sim->pref_off[N]) + " entries");
+    FLEET_TRY(f, hipSetDevice(f->h->device));
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    FLEET_TRY(f, hipMemcpy(out, f->sim->sl.rec, sizeof(double) * N * LTPL_FLEET_SIM_SELECTOR_DOUBLES, hipMemcpyDeviceToHost));
+    if (ordered) FLEET_TRY(f, hipMemcpy(ordered, f->sim->sl.ord, sizeof(int) * (size_t)f->sim->pref_off[N], hipMemcpyDeviceToHost));
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+extern "C" int ltpl_fleet_sim_selector_eval(ltpl_fleet* f, int32_t n_cases, const double* params, const int32_t* lists, const int32_t* n_rows,
+                                            const double* rows, const int32_t* obj_off, const double* objs, int32_t* ordered, double* act_d,
+                                            int32_t* act_i, double* rec)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    auto bad = [&](const std::string& why) { f->err = "fleet sim selector eval: " + why; return LTPL_ERR_INVALID_ARG; };
+    if (n_cases < 0) return bad("n_cases must not be negative");
+    if (n_cases == 0) return LTPL_OK;
+    if (!params || !lists || !n_rows || !rows || !obj_off || !ordered || !act_d || !act_i || !rec) return bad("an array is missing");
+    if (obj_off[0] != 0) return bad("object offsets must start at 0");
+    constexpr int A = fleet::kSelActions;
+    for (int q = 0; q < n_cases; ++q) {
+        const std::string who = "case " + std::to_string(q) + ": ";
+        const int n = obj_off[q + 1] - obj_off[q];
+        if (n < 0 || n > SIM_OBJ_CAP) return bad(who + "0 .. 96 objects");
+        std::string why;
+        if (!sim_sel_params_ok(params + (size_t)q * SLC_PARAMS, &why)) return bad(who + why);
+        const int32_t* li = lists + (size_t)q * 8;
+        if (li[0] < 1 || li[0] > LTPL_FLEET_SIM_MAX_PREF) return bad(who + "a preference list needs 1 .. 5 entries");
+        for (int e = 0; e < li[0]; ++e) if (li[3 + e] < LTPL_ACT_STRAIGHT || li[3 + e] > LTPL_ACT_EMERGENCY) return bad(who + "unknown action in the preference list");
+        for (int a = 0; a < A; ++a) if (n_rows[(size_t)q * A + a] < -1 || n_rows[(size_t)q * A + a] > LTPL_FLEET_SIM_MAX_EXPORT) return bad(who + "rows must lie in -1 .. 256");
+    }
+    const size_t m = (size_t)n_cases, no = (size_t)obj_off[n_cases];
+    if (no > 0 && !objs) return bad("objs missing");
+    constexpr size_t RW = (size_t)A * 4 * LTPL_FLEET_SIM_MAX_EXPORT, SD = LTPL_FLEET_SIM_SELECTOR_DOUBLES, MP = LTPL_FLEET_SIM_MAX_PREF;
+    int rc = fleet_enter(f);
+    if (rc) return rc;
+    Arena ar;     // one device block
+    const size_t o_par = ar.add(8 * SLC_PARAMS * m), o_rows = ar.add(8 * RW * m), o_objs = ar.add(40 * (no ? no : 1)), o_rec = ar.add(8 * SD * m),
+                 o_act = ar.add(sizeof(fleet::SelAct) * A * m), o_li = ar.add(32 * m), o_nr = ar.add(4 * A * m), o_off = ar.add(4 * (m + 1)),
+                 o_ord = ar.add(4 * MP * m);
+    unsigned char* d = nullptr;
+    struct Guard { void* a = nullptr; ~Guard() { if (a) (void)hipFree(a); } } gd;
+    FLEET_TRY(f, hipMalloc(reinterpret_cast<void**>(&d), ar.size)); gd.a = d;
+    FLEET_TRY(f, hipMemset(d, 0, ar.size));
+    FLEET_TRY(f, hipMemcpy(d + o_par, params, 8 * SLC_PARAMS * m, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_rows, rows, 8 * RW * m, hipMemcpyHostToDevice));
+    if (no) FLEET_TRY(f, hipMemcpy(d + o_objs, objs, 40 * no, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_rec, rec, 8 * SD * m, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_li, lists, 32 * m, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_nr, n_rows, 4 * A * m, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_off, obj_off, 4 * (m + 1), hipMemcpyHostToDevice));
+    hipStream_t st = f->h->stream;
+    FLEET_TRY(f, hipStreamSynchronize(st));
+    hipLaunchKernelGGL(k_fleet_sim_selector_eval, dim3((unsigned)m), dim3(64), 0, st, (const double*)(d + o_par), (const int*)(d + o_li), (const int*)(d + o_nr),
+                       (const double*)(d + o_rows), (const int*)(d + o_off), (const double*)(d + o_objs), reinterpret_cast<int*>(d + o_ord),
+                       reinterpret_cast<fleet::SelAct*>(d + o_act), reinterpret_cast<double*>(d + o_rec));
+    FLEET_TRY(f, hipGetLastError());
+    std::vector<fleet::SelAct> act(A * m);
+    FLEET_TRY(f, hipMemcpyAsync(act.data(), d + o_act, sizeof(fleet::SelAct) * A * m, hipMemcpyDeviceToHost, st));
+    FLEET_TRY(f, hipMemcpyAsync(rec, d + o_rec, 8 * SD * m, hipMemcpyDeviceToHost, st));
+    FLEET_TRY(f, hipMemcpyAsync(ordered, d + o_ord, 4 * MP * m, hipMemcpyDeviceToHost, st));
+    FLEET_TRY(f, hipStreamSynchronize(st));
+    for (size_t i = 0; i < A * m; ++i) {
+        act_d[3 * i] = act[i].vbar; act_d[3 * i + 1] = act[i].clear; act_d[3 * i + 2] = act[i].J;
+        act_i[2 * i] = act[i].clear_obj; act_i[2 * i + 1] = act[i].flags;
+    }
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))

@@ -19,6 +19,7 @@ from .sim import VEHICLE_DEFAULTS, VEHICLE_DOUBLES, VEHICLE_FIELDS, VEHICLE_PARA
 from .sim import SENSOR_DOUBLES, SENSOR_FIELDS, SENSOR_PARAMS, sensor_dict, sensor_fov_cos      # noqa: F401  (fleet.SENSOR_FIELDS)
 from .sim import TRACK_CAP, TRACK_DOUBLES, TRACK_FIELDS, TRACKER_DEFAULTS, TRACKER_DOUBLES, TRACKER_FIELDS, TRACKER_PARAMS, tracker_dict      # noqa: F401
 from .sim import PREDICTOR_DEFAULTS, PREDICTOR_DOUBLES, PREDICTOR_FIELDS, PREDICTOR_MAX_POINTS, PREDICTOR_PARAMS, predictor_dict      # noqa: F401
+from .sim import SELECTOR_DEFAULTS, SELECTOR_DOUBLES, SELECTOR_FIELDS, SELECTOR_MAX_ROWS, SELECTOR_PARAMS, selector_dict      # noqa: F401
 from .sim import pack_events as sim_pack_events
 
 
@@ -71,6 +72,10 @@ class SimTrackerIn(C.Structure):           # ltpl_fleet_sim_tracker_in
 
 class SimPredictorIn(C.Structure):         # ltpl_fleet_sim_predictor_in
     _fields_ = [("n_points", C.c_int32)] + [(k, C.c_void_p) for k in PREDICTOR_PARAMS]
+
+
+class SimSelectorIn(C.Structure):          # ltpl_fleet_sim_selector_in
+    _fields_ = [("on", C.c_void_p)] + [(k, C.c_void_p) for k in SELECTOR_PARAMS]
 
 
 class SimRecordHead(C.Structure):         # ltpl_fleet_sim_record_head
@@ -143,6 +148,10 @@ class Fleet(Planner):
             f("sim_predictor").argtypes = [C.c_void_p, C.POINTER(SimPredictorIn)]
             f("sim_predictor_read").argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
             f("sim_predictor_eval").argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6
+        if hasattr(self.lib, "ltpl_fleet_sim_selector"):
+            f("sim_selector").argtypes = [C.c_void_p, C.POINTER(SimSelectorIn)]
+            f("sim_selector_read").argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
+            f("sim_selector_eval").argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 10
         if hasattr(self.lib, "ltpl_fleet_friction"):
             f("friction").argtypes = [C.c_void_p, C.POINTER(FrictionIn)]
             f("friction_scale").argtypes = [C.c_void_p, C.c_void_p]
@@ -383,6 +392,7 @@ class Fleet(Planner):
         si.n_rl, si.t0, si.tic0, si.dt, si.n_export = rows.shape[0], float(t0), float(t0 if tic0 is None else tic0), float(dt), int(n_export)
         self._check(self._fn("sim_setup")(self.handle, C.byref(si)))
         self._sim_opp, self._sim_export = int(arrs["opp_off"][-1]), int(n_export)
+        self._sim_pref_off = arrs["pref_off"].astype(np.int64)      # (sim_selector_read sizes and splits the ordered lists with it)
         self._sim_event_order = np.zeros(0, np.int64)       # (sim_setup switches the events off)
 
     def sim_vel(self, ax_tables=None, ax_table_idx=None, **vel_kwargs):
@@ -883,6 +893,77 @@ class Fleet(Planner):
         self._check(self._fn("sim_predictor_eval")(self.handle, m, K, params.ctypes.data, off.ctypes.data, flat.ctypes.data, pts.ctypes.data,
                                                    oc.ctypes.data, rec.ctypes.data))
         return ([pts[off[q]:off[q + 1]].copy() for q in range(m)], [oc[off[q]:off[q + 1]].copy() for q in range(m)], rec[:m])
+
+    # ---- behaviour selector on the device ---------------------------------------------------------------------------------------------
+    def sim_selector(self, on=True, **params):
+        """A behaviour selector per planner (ltpl_fleet_sim_selector; after ``sim_setup``, between runs at any time): at the head of every
+        tick the trajectories of the previous exported set are scored against the objects the planner was handed -- pace over ``horizon``
+        [s], minus ``w_clear`` per metre of clearance (ego radius ``r_ego``) under ``c_soft``, minus ``w_switch`` for leaving the previous
+        action; an action whose clearance falls below ``c_hard`` is unsafe -- and the step walks the ORDERED list: safe actions by score,
+        emergency if listed, unsafe ones by clearance, the rest. The user's preference list stays the allowed set and the tie order and
+        is never written. Parameters (``sim.SELECTOR_PARAMS``, defaults ``sim.SELECTOR_DEFAULTS``) and ``on``: scalars or one per planner.
+        ``on=None`` switches the selector off. The statistics start anew with every call. Host mirror: ``sim.SelectorModel``."""
+        if on is None:
+            self._check(self._fn("sim_selector")(self.handle, None))
+            return
+        unknown = set(params) - set(SELECTOR_PARAMS)
+        if unknown:
+            raise ValueError("sim_selector: unknown parameter %s" % sorted(unknown))
+        n = self.n_scen
+        si = SimSelectorIn()
+        val = dict(SELECTOR_DEFAULTS, **params)
+        keep = [np.ascontiguousarray(np.broadcast_to(np.asarray(on), (n,)).astype(np.int32))]
+        si.on = keep[0].ctypes.data
+        for name in SELECTOR_PARAMS:
+            keep.append(np.ascontiguousarray(np.broadcast_to(np.asarray(val[name], np.float64), (n,))))
+            setattr(si, name, keep[-1].ctypes.data)
+        self._check(self._fn("sim_selector")(self.handle, C.byref(si)))
+
+    def sim_selector_read(self, raw=False):
+        """(records, ordered): the dict of named arrays (``sim.SELECTOR_FIELDS``; ``raw=True``: the [n, 12] records) and the current
+        ordered list of every planner, a list of int32 arrays in the order of the preference lists of ``sim_setup``
+        (ltpl_fleet_sim_selector_read)."""
+        off = getattr(self, "_sim_pref_off", np.zeros(self.n_scen + 1, np.int64))
+        out = np.zeros((self.n_scen, SELECTOR_DOUBLES), np.float64)
+        order = np.zeros(max(int(off[-1]), 1), np.int32)
+        self._check(self._fn("sim_selector_read")(self.handle, out.ctypes.data, SELECTOR_DOUBLES, order.ctypes.data, int(off[-1])))
+        return (out if raw else selector_dict(out)), [order[off[p]:off[p + 1]].copy() for p in range(self.n_scen)]
+
+    def sim_selector_eval(self, params, users, sel_prev, actions, objs, emergency=None, rec=None):
+        """The selector's test hook (ltpl_fleet_sim_selector_eval): independent cases on the device, one wave each. ``params`` [m, 6] in
+        the order of ``sim.SELECTOR_PARAMS``; per case: ``users`` the preference list, ``sel_prev``, ``actions`` four entries (None: not
+        exported, else rows [n, 4] = s, x, y, vx), ``objs`` [n_q, 5] = x, y, px, py, r, ``emergency`` exported or not; ``rec`` [m, 12]: the
+        records before (default: fresh ones). Returns (ordered lists, act_d [m, 4, 3] = vbar, clear, J, act_i [m, 4, 2] = clear_obj, flags,
+        records after); equals ``sim.SelectorModel.evaluate`` bit for bit."""
+        m = len(users)
+        R = SELECTOR_MAX_ROWS
+        params = np.ascontiguousarray(np.broadcast_to(np.asarray(params, np.float64), (m, len(SELECTOR_PARAMS))))
+        lists = np.zeros((max(m, 1), 8), np.int32)
+        n_rows = np.full((max(m, 1), 4), -1, np.int32)
+        rows = np.zeros((max(m, 1), 4, 4, R))
+        objs = [np.asarray(o, np.float64).reshape(-1, 5) for o in objs]
+        for q in range(m):
+            u = [int(a) for a in users[q]]
+            lists[q, 0], lists[q, 1], lists[q, 2] = len(u), int(sel_prev[q]), int(bool(emergency[q])) if emergency is not None else 0
+            lists[q, 3:3 + min(len(u), 5)] = u[:5]
+            for a in range(4):
+                if actions[q][a] is None:
+                    continue
+                t = np.asarray(actions[q][a], np.float64).reshape(-1, 4)
+                n_rows[q, a] = t.shape[0]
+                rows[q, a, :, :min(t.shape[0], R)] = t[:R].T
+        off = np.ascontiguousarray(np.concatenate(([0], np.cumsum([o.shape[0] for o in objs]))).astype(np.int32))
+        flat = np.ascontiguousarray(np.concatenate(objs + [np.zeros((1, 5))]))
+        order = np.zeros((max(m, 1), 5), np.int32)
+        act_d, act_i = np.zeros((max(m, 1), 4, 3)), np.zeros((max(m, 1), 4, 2), np.int32)
+        if rec is None:
+            rec = np.zeros((max(m, 1), SELECTOR_DOUBLES))
+            rec[:, 10] = np.inf
+        rec = np.ascontiguousarray(np.asarray(rec, np.float64).reshape(max(m, 1), SELECTOR_DOUBLES).copy())
+        self._check(self._fn("sim_selector_eval")(self.handle, m, params.ctypes.data, lists.ctypes.data, n_rows.ctypes.data, rows.ctypes.data,
+                                                  off.ctypes.data, flat.ctypes.data, order.ctypes.data, act_d.ctypes.data, act_i.ctypes.data,
+                                                  rec.ctypes.data))
+        return [order[q, :lists[q, 0]].copy() for q in range(m)], act_d[:m], act_i[:m], rec[:m]
 
     # ---- friction maps on the device ------------------------------------------------------------------------------------------------
     def friction(self, maps, map_idx=None, scale=1.0):

@@ -1246,3 +1246,192 @@ class PredictorModel(object):
 
     def as_dict(self):
         return predictor_dict(self.rec)
+
+
+# ---- behaviour selector (ltpl_fleet_sim_selector, include/ltpl_hip.h; csrc/fleet_select.hpp) ----------------------------------------------
+# name, index, integer valued: the record of ltpl_fleet_sim_selector_read (LTPL_FLEET_SIM_SELECTOR_DOUBLES = 12 per planner)
+SELECTOR_FIELDS = (("ticks", 0, True), ("n_scored", 1, True), ("n_switch", 2, True), ("n_override", 3, True), ("n_unsafe", 4, True),
+                   ("n_emergency", 5, True), ("chosen_straight", 6, True), ("chosen_follow", 7, True), ("chosen_left", 8, True),
+                   ("chosen_right", 9, True), ("clear_min", 10, False), ("j_last", 11, False))
+SELECTOR_DOUBLES = 12
+SELECTOR_PARAMS = ("horizon", "r_ego", "c_hard", "c_soft", "w_clear", "w_switch")
+SELECTOR_DEFAULTS = dict(horizon=2.0, r_ego=1.5, c_hard=0.0, c_soft=3.0, w_clear=2.0, w_switch=0.5)
+SELECTOR_INGEST_T = 0.2                   # s: the horizon of the ingestion's point (ObjectListInterface.py:121)
+SELECTOR_MAX_ROWS = 256                   # LTPL_FLEET_SIM_MAX_EXPORT
+SEL_SCORED, SEL_UNSAFE, SEL_NAN, SEL_EXPORTED = 1, 2, 4, 8      # flags of an action
+SEL_EMERGENCY = 4                         # LTPL_ACT_EMERGENCY
+
+
+def selector_dict(rows):
+    """[n, 12] records as a dict of named arrays (counters as int64)."""
+    rows = np.asarray(rows, np.float64).reshape(-1, SELECTOR_DOUBLES)
+    return {name: (rows[:, i].astype(np.int64) if is_int else rows[:, i].copy()) for name, i, is_int in SELECTOR_FIELDS}
+
+
+def selector_first(order, exported):
+    """The action taken from a list: its first entry in the exported set (a set of action ids), -1 without one."""
+    for a in order:
+        if a in exported:
+            return int(a)
+    return -1
+
+
+class SelectorModel(object):
+    """Scalar host mirror of the behaviour selector in the operation order of csrc/fleet_select.hpp: plain Python floats (the clearance as
+    elementwise numpy float64), + - * / sqrt and comparisons, so the device's bits. ``on`` and the parameters of ``SELECTOR_PARAMS``:
+    scalars or one per planner. ``evaluate`` is one evaluation of the rule (the test hook's case); ``select`` is the tick's use of it for
+    planner p: the list is copied unchanged for a planner that is off, has not started or has failed, and for a one-entry list; otherwise
+    the planner's record ``rec[p]`` is updated. Actions are ids 0 .. 4 (straight, follow, left, right, emergency); ``actions``: for each of
+    the four scored kinds None (not exported) or the rows [n, 4] = s, x, y, vx already trimmed to n_export; ``objs``: [cnt, 5] = x, y, px,
+    py, r, the previous tick's staged list."""
+
+    def __init__(self, n, on=True, **params):
+        self.n = int(n)
+        unknown = set(params) - set(SELECTOR_PARAMS)
+        if unknown:
+            raise ValueError("SelectorModel: unknown parameter %s" % sorted(unknown))
+        val = dict(SELECTOR_DEFAULTS, **params)
+        self.on = [bool(x) for x in np.broadcast_to(np.asarray(on), (self.n,))]
+        self.par = np.ascontiguousarray(np.stack([np.broadcast_to(np.asarray(val[k], np.float64), (self.n,)) for k in SELECTOR_PARAMS], axis=1))
+        self.rec = np.zeros((self.n, SELECTOR_DOUBLES))
+        self.rec[:, 10] = np.inf
+        self.last = None                  # the actions of the latest evaluation
+
+    def params(self, p):
+        return [float(x) for x in self.par[p]]
+
+    @staticmethod
+    def times(s, v, T):
+        """Steps 1 and 2: (t, n_r, last, vbar) of a trajectory with n >= 2 rows."""
+        n = len(s)
+        t = [0.0]
+        n_r = n
+        for i in range(1, n):
+            m = v[i] + v[i - 1]
+            if not m > 0.0:
+                n_r = i
+                break
+            t.append(t[i - 1] + _fdiv(2.0 * (s[i] - s[i - 1]), m))
+        last = 0
+        for i in range(1, n_r):
+            if t[i] <= T:
+                last = i
+        if last + 1 < n_r:
+            f = _fdiv(T - t[last], t[last + 1] - t[last])
+            s_t = s[last] + f * (s[last + 1] - s[last])
+            vbar = _fdiv(s_t - s[0], T)
+        elif n_r < n:
+            vbar = _fdiv(s[last] - s[0], T)
+        elif t[last] == 0.0:
+            vbar = v[0]
+        else:
+            vbar = _fdiv(s[last] - s[0], t[last])
+        return t, n_r, last, vbar
+
+    @staticmethod
+    def clearance(x, y, t, last, T, objs, r_ego):
+        """Step 3: (clear, clear_obj) over the window rows (t_i <= T, i <= last) and the objects."""
+        objs = np.asarray(objs, np.float64).reshape(-1, 5)
+        if objs.shape[0] == 0:
+            return float("inf"), -1
+        tt = np.asarray(t[:last + 1], np.float64)
+        xx, yy = np.asarray(x[:last + 1], np.float64), np.asarray(y[:last + 1], np.float64)
+        with np.errstate(all="ignore"):
+            c = tt / SELECTOR_INGEST_T
+            ox, oy, px, py, rr = (objs[:, k:k + 1] for k in range(5))
+            X = ox + (px - ox) * c[None, :]
+            Y = oy + (py - oy) * c[None, :]
+            dx, dy = xx[None, :] - X, yy[None, :] - Y
+            d = (np.sqrt(dx * dx + dy * dy) - rr) - r_ego
+            ok = (tt <= T)[None, :] & ~np.isnan(d)
+        if not ok.any():
+            return float("inf"), -1
+        k = int(np.argmin(np.where(ok, d, np.inf)))             # the first minimum in (object, row) order
+        if not ok.flat[k]:                                      # every candidate is +inf: the first of them
+            k = int(np.argmax(ok))
+        return float(d.flat[k]), k // d.shape[1]
+
+    @staticmethod
+    def _group(a, acts):
+        if a == SEL_EMERGENCY:
+            return 1, 0.0
+        if not 0 <= a < 4 or not acts[a]["flags"] & SEL_SCORED:
+            return 3, 0.0
+        if acts[a]["flags"] & SEL_UNSAFE:
+            return 2, (-float("inf") if acts[a]["flags"] & SEL_NAN else acts[a]["clear"])
+        return 0, acts[a]["J"]
+
+    def evaluate(self, params, user, sel_prev, actions, objs, emergency=False, rec=None):
+        """One evaluation: (ordered list, the four actions as dicts flags / clear_obj / vbar / clear / J); ``rec``: a record updated in place."""
+        T, r_ego, c_hard, c_soft, w_clear, w_switch = (float(q) for q in params)
+        user = [int(a) for a in user]
+        exported = set(a for a in range(4) if actions[a] is not None)
+        if emergency:
+            exported.add(SEL_EMERGENCY)
+        acts = []
+        for a in range(4):
+            A = dict(flags=SEL_EXPORTED if a in exported else 0, clear_obj=-1, vbar=0.0, clear=float("inf"), J=0.0)
+            acts.append(A)
+            if a not in user or a not in exported:
+                continue
+            rows = np.asarray(actions[a], np.float64).reshape(-1, 4)
+            if rows.shape[0] < 2:
+                continue
+            A["flags"] |= SEL_SCORED
+            s, x, y, v = (rows[:, k].tolist() for k in range(4))
+            t, n_r, last, A["vbar"] = self.times(s, v, T)
+            A["clear"], A["clear_obj"] = self.clearance(x, y, t, last, T, objs, r_ego)
+            pen = c_soft - A["clear"]
+            if not pen > 0.0:
+                pen = 0.0
+            with np.errstate(all="ignore"):
+                J = float((np.float64(A["vbar"]) - np.float64(w_clear) * np.float64(pen)) - np.float64(w_switch if a != sel_prev else 0.0))
+            A["J"] = J
+            if J != J:
+                A["flags"] |= SEL_NAN | SEL_UNSAFE
+            elif not A["clear"] >= c_hard:
+                A["flags"] |= SEL_UNSAFE
+        L = len(user)
+        keys = [self._group(a, acts) for a in user]
+        order = [0] * L
+        for e in range(L):
+            ge, ke = keys[e]
+            r = 0
+            for f in range(L):
+                if f == e:
+                    continue
+                gf, kf = keys[f]
+                if gf < ge or (gf == ge and (kf > ke or (not ke > kf and f < e))):
+                    r += 1
+            order[r] = user[e]
+        if rec is not None:
+            taken, alone = selector_first(order, exported), selector_first(user, exported)
+            scored = [A for A in acts if A["flags"] & SEL_SCORED]
+            rec[0] += 1.0
+            rec[1] += float(len(scored))
+            if taken >= 0 and taken != sel_prev:
+                rec[2] += 1.0
+            if taken != alone:
+                rec[3] += 1.0
+            if not any(not A["flags"] & SEL_UNSAFE for A in scored):
+                rec[4] += 1.0
+            if taken == SEL_EMERGENCY:
+                rec[5] += 1.0
+            elif taken >= 0:
+                rec[6 + taken] += 1.0
+            if 0 <= taken < 4 and acts[taken]["flags"] & SEL_SCORED:
+                if acts[taken]["clear"] < rec[10]:
+                    rec[10] = acts[taken]["clear"]
+                rec[11] = acts[taken]["J"]
+        self.last = acts
+        return order, acts
+
+    def select(self, p, user, sel_prev, actions, objs, emergency=False, started=True, failed=False):
+        """The tick's ordered list of planner p (see the class comment)."""
+        user = [int(a) for a in user]
+        if not self.on[p] or len(user) < 2 or not started or failed:
+            return user
+        return self.evaluate(self.params(p), user, sel_prev, actions, objs, emergency, self.rec[p])[0]
+
+    def as_dict(self):
+        return selector_dict(self.rec)

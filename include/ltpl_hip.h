@@ -65,7 +65,8 @@ extern "C" {
                                      ltpl_fleet_sim_vehicle / _vehicle_read / _vehicle_step,
                                      ltpl_fleet_sim_sensor / _sensor_read / _sensor_eval,
                                      ltpl_fleet_sim_tracker / _tracker_read / _tracker_eval,
-                                     ltpl_fleet_sim_predictor / _predictor_read / _predictor_eval */
+                                     ltpl_fleet_sim_predictor / _predictor_read / _predictor_eval,
+                                     ltpl_fleet_sim_selector / _selector_read / _selector_eval */
 
 /* status codes */
 #define LTPL_OK               0
@@ -1370,6 +1371,81 @@ int ltpl_fleet_sim_predictor_read(ltpl_fleet* fleet, double* out, int32_t double
  * this one evaluation. */
 int ltpl_fleet_sim_predictor_eval(ltpl_fleet* fleet, int32_t n_cases, int32_t n_points, const double* params, const int32_t* obj_off,
                                   const double* objs, double* points, int32_t* outcome, double* rec);
+
+/* ------------------------------------------------------------------------------------------------------------------------------------------
+ * Additive to ABI v9 -- BEHAVIOUR SELECTOR: a per-planner rule that scores the trajectories of the previous tick's exported set against the
+ * objects the planner was handed in that tick and writes an ORDERED preference list, which the step kernel walks exactly as it walks the
+ * user's list (csrc/fleet_sim.hpp: k_fleet_sim_select; the rule: csrc/fleet_select.hpp). Without it the simulation takes "the first
+ * preferred key of the previous exported set" (main_std_example.py), whatever the trajectories and the objects look like. Off by default.
+ * ARITHMETIC: fp64, + - * / sqrt and comparisons only, one fixed order (the library is built with -ffp-contract=off): the host mirror
+ * sim.SelectorModel and the device agree to the last bit.
+ * INPUTS, all of them the previous tick's: the user's preference list as the events last wrote it (the allowed set plus the tie order;
+ * the rule never adds an action and never writes the list), sel_action, the exported set (rows 0 .. n - 1, n = min(rows, n_export), columns
+ * s, x, y, vx), the staged object list (x, y, the ingestion's 0.2 s point, radius: what the planner perceived behind noise, sensor and
+ * tracker), and PER PLANNER horizon T [s], r_ego [m], c_hard [m], c_soft [m], w_clear [1/s], w_switch [m/s].
+ * An action is SCORED when it is straight, follow, left or right, stands in the user's list, is exported and has n >= 2 rows:
+ *   times      t_0 = 0, t_i = t_{i-1} + (2 (s_i - s_{i-1})) / (v_i + v_{i-1}); the first row with !(v_i + v_{i-1} > 0) and every later one
+ *              is unreachable (the car stands); the window: reachable rows with t_i <= T, `last` its highest
+ *   pace       vbar = (s_T - s_0) / T with s_T interpolated between rows last and last + 1; (s_last - s_0) / T where the car stands;
+ *              (s_last - s_0) / t_last where the trajectory ends inside the horizon (v_0 when t_last == 0)
+ *   clearance  over window rows i and objects o, the object moved at constant velocity through its 0.2 s point: c = t_i / 0.2,
+ *              d = sqrt((x_i - (x_o + (px_o - x_o) c))^2 + (y_i - (y_o + (py_o - y_o) c))^2) - r_o - r_ego; clear = min d (+inf
+ *              without objects), ties to the lower (object, row), a NaN never wins
+ *   score      J = vbar - w_clear max(0, c_soft - clear) - (action != sel_action ? w_switch : 0); UNSAFE when clear < c_hard (equality is
+ *              safe) or J is NaN (then ranked with clearance -inf)
+ *   order      safe actions by J descending; emergency, if listed; unsafe actions by clearance descending; every other entry (not
+ *              exported, n < 2) in the user's order. Ties keep the user's order; the output is a permutation of the user's list.
+ * A car with no safe option takes the emergency trajectory if its list holds it, the least bad action otherwise; c_hard = -inf switches
+ * that off. Copied unchanged, record untouched: a planner with on == 0, one that has not started or has its error word set (the step
+ * kernel's "straight before the first tick" rule and its E_SIM_ACTION stay), a one-entry list. The full definition: csrc/fleet_select.hpp.
+ * STATISTICS per planner, LTPL_FLEET_SIM_SELECTOR_DOUBLES doubles, updated in every evaluation ("taken": the first ordered entry that is in
+ * the exported set -- what the step kernel will choose):
+ *   [0] ticks  [1] n_scored: actions scored  [2] n_switch: taken != sel_action  [3] n_override: taken differs from what the user's list
+ *   alone gives  [4] n_unsafe: no safe action  [5] n_emergency: emergency taken  [6] .. [9] chosen_straight / _follow / _left / _right
+ *   [10] clear_min: the smallest clearance of a taken scored action (+inf at the start)  [11] j_last: J of the latest taken scored action
+ * IN THE TICK: k_fleet_sim_select (one wave64 per planner) runs at the head of the tick, behind the events kernels and in front of the step
+ * kernel, only while a selector is set; the step and mates kernels then get the ordered lists (a buffer of the selector's own, indexed by
+ * the same pref_off) in the user's place. A fleet that never calls this entry point launches the kernels it launched before.
+ *   | call                          | selector                                                                                     |
+ *   | ltpl_fleet_sim_setup          | switched off                                                                                 |
+ *   | ltpl_fleet_sim_events         | `pref` events keep writing the USER's list; the selector runs behind them, so from that tick on|
+ *   | noise / sensor / tracker      | the rule scores the staged list, i.e. what they handed on                                     |
+ *   | predictor                     | not read: the rule uses the staged 0.2 s point whether or not a predictor is set             |
+ *   | snapshot / branch             | parameters, ordered lists and records stay with the destination (configuration and statistics); |
+ *   |                               | sel_action travels as before, and so does the staged list (count and x, y, px, py, r of its    |
+ *   |                               | entries), which the selector made state: a snapshot taken and restored with the selector set   |
+ *   |                               | reproduces the run. A source without a list (taken without a selector) leaves an empty one; a  |
+ *   |                               | list longer than the destination's staging slots is cut to them                                |
+ *   | ltpl_fleet_sim_race / _predictor | kept; they allocate the staging again, which then holds no list: the next run starts from  |
+ *   |                               | empty lists (its first tick scores without objects)                                          |
+ * THE CALL: after ltpl_fleet_sim_setup at any time between runs; in == NULL switches it off. Every argument is checked before the first
+ * HIP call: every array present; horizon > 0; r_ego, w_clear, w_switch >= 0; no NaN anywhere (c_hard and c_soft may be infinite).
+ * Everything new is allocated before anything old is freed. A successful call starts fresh records.
+ * ------------------------------------------------------------------------------------------------------------------------------------------ */
+#define LTPL_FLEET_SIM_SELECTOR_DOUBLES 12
+typedef struct {
+    const int32_t* on;               /* [n] 0: the planner keeps its list as it is                     */
+    const double* horizon;           /* [n] s, > 0                                                     */
+    const double* r_ego;             /* [n] m, >= 0                                                    */
+    const double* c_hard;            /* [n] m: below it an action is unsafe (-inf: never)              */
+    const double* c_soft;            /* [n] m: below it clearance costs w_clear per metre              */
+    const double* w_clear;           /* [n] 1/s, >= 0                                                  */
+    const double* w_switch;          /* [n] m/s, >= 0: what leaving the previous action costs          */
+} ltpl_fleet_sim_selector_in;
+int ltpl_fleet_sim_selector(ltpl_fleet* fleet, const ltpl_fleet_sim_selector_in* in);
+/* out: [n][LTPL_FLEET_SIM_SELECTOR_DOUBLES]; ordered (or NULL): the current ordered lists, n_ordered = pref_off[n] entries laid out as the
+ * user's preference lists are. No simulation, the selector off, a wrong record size or a wrong n_ordered: LTPL_ERR_INVALID_ARG. */
+int ltpl_fleet_sim_selector_read(ltpl_fleet* fleet, double* out, int32_t doubles_per_planner, int32_t* ordered, int32_t n_ordered);
+/* the test hook of the rule (k_fleet_sim_selector_eval, one wave per case, the tick's own device functions; needs no simulation): case q
+ * has params[q][6] = horizon, r_ego, c_hard, c_soft, w_clear, w_switch (checked as above), lists[q][8] = n_pref (1 .. 5), sel_action,
+ * emergency exported (0 / 1) and the user's entries (LTPL_ACT_* 0 .. 4), n_rows[q][4] per action straight .. right (-1: not exported,
+ * else 0 .. 256), rows[q][4][4][256] = per action the columns s, x, y, vx, and the objects objs[obj_off[q] .. obj_off[q + 1])[5] = x, y,
+ * px, py, r (0 .. 96). Out: ordered[q][5] (the first n_pref entries), act_d[q][4][3] = vbar, clear, J, act_i[q][4][2] = clear_obj (-1:
+ * none), flags (1 scored, 2 unsafe, 4 NaN score, 8 exported); rec[q][12]: IN the record before, OUT the record after this evaluation
+ * (unlike the tick, the hook evaluates a one-entry list too). */
+int ltpl_fleet_sim_selector_eval(ltpl_fleet* fleet, int32_t n_cases, const double* params, const int32_t* lists, const int32_t* n_rows,
+                                 const double* rows, const int32_t* obj_off, const double* objs, int32_t* ordered, double* act_d, int32_t* act_i,
+                                 double* rec);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,7 @@
 """Closed-loop SIMULATION rate of a fleet (ltpl_fleet_sim_*): N planners, each with its own eight C2-style race-line opponents (SURVEY.md
 section 8d: s0_k = 250 + 280 k, vel_scale_k = 0.30 + 0.05 (k mod 4), here staggered by 10 m (p mod 16) per planner), run the example
 driver's loop on the device for T ticks without host work per tick.   tools/sim_rate.py [--planners 32768] [--ticks 200] [--no-tape]
-[--race-size K] [--friction-map] [--telemetry] [--record M [--record-depth D]] [--events] [--noise] [--vehicle] [--sensor [keep]] [--tracker] [--predictor [K[:MODE]]] [--lib PATH]. Prints planner-ticks per second of sim_run (device time of the run) next to tape_run on the C2 tape (recorded inputs,
+[--race-size K] [--friction-map] [--telemetry] [--record M [--record-depth D]] [--events] [--noise] [--vehicle] [--sensor [keep]] [--tracker] [--predictor [K[:MODE]]] [--selector] [--lib PATH]. Prints planner-ticks per second of sim_run (device time of the run) next to tape_run on the C2 tape (recorded inputs,
 tools/fleet_rate.py). --race-size K > 1: races of K consecutive planners (ltpl_fleet_sim_race) that see one another, started 30 m apart
 along the race line with its heading; K = 1 (default) is the run without races. --friction-map: the same fleet on the friction grid of
 tests/golden/friction_grid.npz (ltpl_fleet_friction: rows evaluated on the device, grip factors 1.0 .. 0.7 over the planners) instead of
@@ -32,6 +32,8 @@ the run.
 mode MODE (default 2, along the track, relax 0.5; 0: as ingested -- the planning work of the run without a predictor on 1 + K positions
 per object; 1: straight line): k_fleet_sim_predict in k_fleet_sim_compact's place, behind --sensor / --tracker when they are set; the
 statistics are printed after the run.
+--selector: every planner behind the behaviour selector (ltpl_fleet_sim_selector, sim.SELECTOR_DEFAULTS) on its four-entry list:
+k_fleet_sim_select at the head of every tick, in front of the step kernel; the statistics are printed after the run.
 --lib PATH: another build of
 the library (A/B against the parent's)."""
 import argparse
@@ -69,6 +71,7 @@ def main():
     ap.add_argument("--tracker", action="store_true", help="every planner behind the object tracker (sim.TRACKER_DEFAULTS)")
     ap.add_argument("--predictor", nargs="?", const="4:2", default=None, metavar="K[:MODE]",
                     help="every planner behind the prediction model: K points per object over 2 s, mode 0 / 1 / 2 (default 4:2)")
+    ap.add_argument("--selector", action="store_true", help="every planner behind the behaviour selector (sim.SELECTOR_DEFAULTS)")
     ap.add_argument("--lib", default=None, help="path of the library to load (default: the in-tree build)")
     a = ap.parse_args()
     lat = Lattice.load(os.path.join(ROOT, "tests", "golden", "monteblanco_lattice.npz"))
@@ -135,6 +138,8 @@ def main():
         if a.predictor:
             kp, _, mode = a.predictor.partition(":")
             fleet.sim_predictor(n_points=int(kp), mode=int(mode or 2), horizon=2.0, relax=0.5)
+        if a.selector:
+            fleet.sim_selector()
         t0 = time.perf_counter()
         failed = 0
         try:
@@ -170,6 +175,12 @@ def main():
                   "%d of them coasting, %d withheld, %d overflows, up to %d tracks" % (
                       d["n_det"].sum(), d["n_matched"].sum(), d["n_born"].sum(), d["n_confirmed"].sum(), d["n_del_tentative"].sum(), d["n_del_coast"].sum(),
                       d["n_out"].sum(), d["n_out_coast"].sum(), d["n_withheld"].sum(), d["n_overflow"].sum(), d["tracks_max"].max()))
+        if a.selector:
+            d = fleet.sim_selector_read()[0]
+            print("  selector: %d evaluations, %d actions scored; %d switches, %d overrides of the list, %d without a safe action, %d emergency; chosen "
+                  "straight %d, follow %d, left %d, right %d; smallest clearance taken %.3f m" % (
+                      d["ticks"].sum(), d["n_scored"].sum(), d["n_switch"].sum(), d["n_override"].sum(), d["n_unsafe"].sum(), d["n_emergency"].sum(),
+                      d["chosen_straight"].sum(), d["chosen_follow"].sum(), d["chosen_left"].sum(), d["chosen_right"].sum(), np.min(d["clear_min"])))
         if a.predictor:
             d = fleet.sim_predictor_read()
             print("  predictor: %d objects predicted; as ingested %d, still %d, straight by mode %d / d_max %d / direction %d / no segment %d, along the "
