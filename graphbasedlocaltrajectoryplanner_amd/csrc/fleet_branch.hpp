@@ -7,11 +7,15 @@
 //            (state and statistics, ltpl_fleet_sim_vehicle) where the DESTINATION has model 1, and the object tracker's table, track
 //            count and next_id (ltpl_fleet_sim_tracker) where the destination has a tracker, and the staged object list of the last tick
 //            (cnt and the first cnt entries of g_x, g_y, g_px, g_py, g_r) where the destination has a behaviour selector
-//            (ltpl_fleet_sim_selector), which reads that list at the head of the next tick;
+//            (ltpl_fleet_sim_selector), which reads that list at the head of the next tick, and the safety monitor's record and incident
+//            ring (ltpl_fleet_sim_safety) where the destination has a monitor: they are what the tick writes;
 //   stays    the race line, the opponents' vel_scale / length, statics, zones, preference list, dt, n_export, the velocity arguments,
 //            friction map index and scale, race membership and length as a mate, contact radius, the recorder's ring and indices,
 //            the vehicle model's switch and parameters, the tracker's parameters and statistics, the selector's parameters, ordered
-//            lists and statistics.
+//            lists and statistics, the safety monitor's parameters, mask and tick index.
+// Safety monitor, the mixed cases: a destination fleet without a monitor takes nothing; with one, a destination takes record and ring of a
+// source that held them (a live planner while the monitor is set, a snapshot entry taken with one) -- a source without leaves the
+// destination the start state (prev_valid 0: its next live tick is not evaluated).
 // Behaviour selector, the mixed cases: a destination without a selector takes nothing; with one it takes the list of a source that held
 // one (a live planner while the selector is set, a snapshot entry taken with one), cut to the destination's staging slots where the
 // source staged more -- a source without leaves the destination an empty list (cnt 0): the first tick scores without objects.
@@ -60,6 +64,27 @@ __global__ __launch_bounds__(64) void k_fleet_sim_branch_staged(StagedView S, St
     }
     if (t == 0) T.cnt[ed] = n;
 }
+
+// the safety monitor's record and ring of entry e (rec null: the source holds none)
+struct SafetyView { double* rec; double* inc; };
+
+// behind k_fleet_sim_branch, only where the live fleet has a monitor: one wave64 per pair
+__global__ __launch_bounds__(64) void k_fleet_sim_branch_safety(SafetyView S, SafetyView T, const int* __restrict__ src_entry,
+                                                                const int* __restrict__ dst_entry)
+{
+    const int k = blockIdx.x, t = threadIdx.x;
+    const size_t es = (size_t)src_entry[k], ed = (size_t)dst_entry[k];
+    double* r = T.rec + ed * LTPL_FLEET_SIM_SAFETY_DOUBLES; double* e = T.inc + ed * SAF_RING;
+    if (S.rec) {
+        if (t < LTPL_FLEET_SIM_SAFETY_DOUBLES) r[t] = S.rec[es * LTPL_FLEET_SIM_SAFETY_DOUBLES + t];
+        if (t < SAF_RING) e[t] = S.inc[es * SAF_RING + t];
+    } else {
+        if (t < LTPL_FLEET_SIM_SAFETY_DOUBLES)
+            r[t] = t == fleet::SAF_GAP_MIN || t == fleet::SAF_TTC_MIN || t == fleet::SAF_THW_MIN ? (double)INFINITY : 0.0;
+        if (t < SAF_RING) e[t] = NAN;
+    }
+}
+static_assert(LTPL_FLEET_SIM_SAFETY_DOUBLES <= 64 && SAF_RING <= 64, "k_fleet_sim_branch_safety: one lane per double");
 
 typedef unsigned int branch_u32x4 __attribute__((ext_vector_type(4)));
 #define BRANCH_THREADS 256
@@ -139,6 +164,7 @@ struct SimSnap {
     std::vector<int> veh_model;             // [entries] the model of entry k when the snapshot was taken (empty: the model was off)
     bool has_trk = false;                   // a tracker part: tables of the planners' capacities, counts and next_id
     StagedView stg{};                       // the staged lists (stg.cnt null: taken without a selector)
+    SafetyView saf{};                       // the safety monitor's records and rings (saf.rec null: taken without a monitor)
     uint64_t bytes = 0;
     bool held() const { return !planners.empty(); }
 };
@@ -181,6 +207,24 @@ static int branch_launch_staged(ltpl_fleet* f, StagedView S, StagedView T, const
     if (rc) return rc;
     hipStream_t st = f->h->stream;
     hipLaunchKernelGGL(k_fleet_sim_branch_staged, dim3((unsigned)n), dim3(64), 0, st, S, T, (const int*)d_idx, (const int*)d_idx + n);
+    FLEET_TRY(f, hipGetLastError());
+    FLEET_TRY(f, hipStreamSynchronize(st));
+    return LTPL_OK;
+}
+
+// the safety monitor's records and rings of the pairs, behind branch_launch; T: a view with a monitor's records
+static int branch_launch_safety(ltpl_fleet* f, SafetyView S, SafetyView T, const std::vector<int>& src_entry, const std::vector<int>& dst_entry)
+{
+    const int n = (int)src_entry.size();
+    if (n == 0) return LTPL_OK;
+    SimAllocs a;
+    int* d_idx = nullptr;
+    std::vector<int> idx(src_entry);
+    idx.insert(idx.end(), dst_entry.begin(), dst_entry.end());
+    int rc = sim_upload(f, a.p, idx.data(), idx.size(), &d_idx);
+    if (rc) return rc;
+    hipStream_t st = f->h->stream;
+    hipLaunchKernelGGL(k_fleet_sim_branch_safety, dim3((unsigned)n), dim3(64), 0, st, S, T, (const int*)d_idx, (const int*)d_idx + n);
     FLEET_TRY(f, hipGetLastError());
     FLEET_TRY(f, hipStreamSynchronize(st));
     return LTPL_OK;
@@ -304,11 +348,14 @@ try {
         for (double*& g : sv.g) SNAP_TAKE(&g, (size_t)sb[M]);
         { int* o = nullptr; SNAP_TAKE(&o, M + 1, sb.data()); sv.base = o; }
     }
+    SafetyView& fv = q->saf;
+    if (s.has_saf) { SNAP_TAKE(&fv.rec, M * LTPL_FLEET_SIM_SAFETY_DOUBLES); SNAP_TAKE(&fv.inc, M * SAF_RING); }
 #undef SNAP_TAKE
     std::vector<int> dst(M);
     for (size_t k = 0; k < M; ++k) dst[k] = (int)k;
     if ((rc = branch_launch(f, branch_live_view(f), v, q->planners, dst, nullptr))) return rc;
     if (sv.cnt && (rc = branch_launch_staged(f, s.staged_valid ? branch_live_staged(f) : StagedView{}, sv, q->planners, dst))) return rc;
+    if (fv.rec && (rc = branch_launch_safety(f, SafetyView{s.sf.rec, s.sf.inc}, fv, q->planners, dst))) return rc;
     q->allocs.swap(a.p);
     q->has_tele = s.has_tele; q->tele_gen = s.tele_gen; q->bytes = bytes;
     if (!s.snaps) s.snaps = new SimSnaps();
@@ -416,6 +463,8 @@ try {
         }
         if ((rc = branch_launch_staged(f, q ? q->stg : branch_live_staged(f), branch_live_staged(f), se, de))) return rc;
     }
+    // the safety monitor's records and rings: what the tick writes
+    if (s.has_saf && (rc = branch_launch_safety(f, q ? q->saf : SafetyView{s.sf.rec, s.sf.inc}, SafetyView{s.sf.rec, s.sf.inc}, se, de))) return rc;
     f->cur.has_paths = false;           // (as after a run: a per-call calc_vel_profile needs its own calc_paths first)
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))

@@ -43,6 +43,11 @@
 //                        the previous tick's staged objects in LDS, time columns serially by one lane per action, row x object pairs over
 //                        the lanes, one wave minimum per action; the ORDERED preference list into a buffer of the selector's own, which
 //                        the step and mates kernels then get as SimDev::pref; lane 0 updates the planner's 12-double record
+//   k_fleet_sim_safety   (safety monitor set only: ltpl_fleet_sim_safety; the rule: fleet_safety.hpp) behind k_fleet_sim_tele / k_fleet_sim_rank,
+//                        in front of k_fleet_sim_sense, one wave64 per planner: one lane per staged object (blocks of 64), time to
+//                        collision, required deceleration, headway, gap and closing speed against the TRUE pose and its displacement
+//                        since the previous live tick; wave reductions, lane 0 updates the planner's 31-double record and its incident
+//                        ring. Registers only; reads what the tick staged and writes nothing another kernel reads
 //   k_fleet_sim_rec_paths / k_fleet_sim_rec_vel   (flight recorder on only: ltpl_fleet_sim_record) one wave64 per RECORDED planner: the
 //                        tick's paths behind paths_post, and its head, objects and trajectories behind the last velocity kernel, into
 //                        the planner's record of ring slot tick % depth. The tick then takes the unfused launch sequence
@@ -53,6 +58,7 @@
 
 #include "fleet_noise.hpp"
 #include "fleet_predict.hpp"
+#include "fleet_safety.hpp"
 #include "fleet_select.hpp"
 #include "fleet_sensor.hpp"
 #include "fleet_track.hpp"
@@ -1374,6 +1380,106 @@ __global__ __launch_bounds__(64) void k_fleet_sim_selector_eval(const double* pa
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// safety monitor (ltpl_fleet_sim_safety, include/ltpl_hip.h; the rule: fleet_safety.hpp; host mirror: sim.SafetyModel). Measurement only:
+// parameters, a record and an incident ring per planner, which the tick writes (they travel with snapshot / branch, fleet_branch.hpp).
+// Nothing the planner reads is touched. The pointers live in a struct of their own: no other kernel carries them.
+// ---------------------------------------------------------------------------------------------------------------------
+#define SAF_PARAMS 5                       // fleet::SafetyParams
+#define SAF_RING (LTPL_FLEET_SIM_SAFETY_INCIDENTS * LTPL_FLEET_SIM_SAFETY_INCIDENT_DOUBLES)
+static_assert(fleet::SAF_DOUBLES == LTPL_FLEET_SIM_SAFETY_DOUBLES && sizeof(fleet::SafetyParams) == SAF_PARAMS * sizeof(double) &&
+              fleet::kSafIncidents == LTPL_FLEET_SIM_SAFETY_INCIDENTS && fleet::SAF_INC_DOUBLES == LTPL_FLEET_SIM_SAFETY_INCIDENT_DOUBLES,
+              "safety record layout");
+struct SimSafety {
+    const double* par;                     // [N][SAF_PARAMS] in the order of fleet::SafetyParams
+    const int* on;                         // [N] 0: the planner is not monitored
+    double* rec;                           // [N][LTPL_FLEET_SIM_SAFETY_DOUBLES]
+    double* inc;                           // [N][SAF_RING]
+    uint32_t tick;                         // tick0 + fleet ticks since the monitor was set
+};
+// objects in: five arrays (x, y, px, py, r), elements `stride` doubles apart. seen_x / seen_y (or null): the PERCEIVED positions next to
+// true x, y -- the staged 0.2 s point was built from them, so the rule is handed Q = X + (Q_staged - X_perceived): the true position and
+// the perceived displacement. (Q_staged - X_true would put the position error / 0.2 into the object's velocity.)
+struct SafObjIn { const double* c[5]; int stride; const double* seen_x; const double* seen_y; };
+
+__device__ __forceinline__ fleet::SafetyParams sim_safety_params(const double* q) { return fleet::SafetyParams{q[0], q[1], q[2], q[3], q[4]}; }
+
+// One live tick of one planner by one wave64 (every lane enters): one lane per object in blocks of 64, each lane folds its objects in slot
+// order (fleet::safety_fold), then the wave's reductions -- (value, slot) minima for gap and TTC, plain minima for the headway and, negated,
+// for the maxima, ballot / popcount for the counts -- and lane 0 applies the record and incident rules. Registers only: no LDS.
+// per_obj [cnt][6] and per_tick [8] (the hook's outputs) or null
+__device__ __forceinline__ void sim_safety_wave(int lane, const fleet::SafetyParams& P, double px, double py, double dt, double tick, int cnt,
+                                                const SafObjIn& in, double* rec, double* inc, double* per_obj, double* per_tick)
+{
+    double wx, wy;
+    const bool evaluated = fleet::safety_velocity(rec, px, py, dt, &wx, &wy);
+    fleet::SafetyTick T = fleet::safety_tick_start();
+    int overlaps = 0, skipped = 0;
+    for (int b0 = 0; b0 < cnt; b0 += 64) {
+        const int k = b0 + lane;
+        int fl = 0;
+        if (k < cnt) {
+            const size_t a = (size_t)k * in.stride;
+            const double ox = in.c[0][a], oy = in.c[1][a];
+            double qx = in.c[2][a], qy = in.c[3][a];
+            if (in.seen_x) { qx = ox + (qx - in.seen_x[a]); qy = oy + (qy - in.seen_y[a]); }      // (uniform)
+            const fleet::SafetyObj o = fleet::safety_obj(P, px, py, wx, wy, ox, oy, qx, qy, in.c[4][a]);
+            fleet::safety_fold(T, o, k);
+            fl = o.flags;
+            if (per_obj) {
+                double* q = per_obj + (size_t)6 * k;
+                q[0] = o.ttc; q[1] = o.drac; q[2] = o.thw; q[3] = o.gap; q[4] = o.closing; q[5] = (double)o.flags;
+            }
+        }
+        overlaps += __popcll(__ballot((fl & fleet::kSafOverlap) != 0));
+        skipped += __popcll(__ballot((fl & fleet::kSafSkipped) != 0));
+    }
+    wave_min2(T.gap, T.gap_slot);
+    wave_min2(T.ttc, T.ttc_slot);
+    T.thw = wave_min_f64(T.thw);
+    T.drac = -wave_min_f64(-T.drac); T.impact = -wave_min_f64(-T.impact); T.closing = -wave_min_f64(-T.closing);
+    T.overlaps = overlaps; T.skipped = skipped;
+    if (lane != 0) return;
+    if (per_tick) fleet::safety_tick_out(T, per_tick);
+    fleet::safety_apply(rec, inc, P, px, py, dt, tick, evaluated, T);
+}
+
+// behind k_fleet_sim_tele / k_fleet_sim_rank, in front of k_fleet_sim_sense: the staged list as the step and mates kernels left it, in
+// front of sensor and tracker. `g_tx`, `g_ty` (null while the noise is off): the true positions of the tick's objects; the displacement to
+// the 0.2 s point stays the perceived one (SafObjIn). A planner that is not live or not monitored returns at once
+__global__ __launch_bounds__(64) void k_fleet_sim_safety(SimDev sd, SimSafety sf, const double* g_tx, const double* g_ty)
+{
+    const int p = blockIdx.x, lane = threadIdx.x;
+    if (!sd.live[p] || !sf.on[p]) return;
+    const int base = sd.obj_base[p], slots = sd.obj_base[p + 1] - base;
+    int cnt = sd.cnt[p];
+    if (cnt > SIM_OBJ_CAP) cnt = SIM_OBJ_CAP;
+    if (cnt > slots) cnt = slots;
+    if (cnt < 0) cnt = 0;
+    const SafObjIn in{{(g_tx ? g_tx : sd.g_x) + base, (g_tx ? g_ty : sd.g_y) + base, sd.g_px + base, sd.g_py + base, sd.g_r + base}, 1,
+                      g_tx ? sd.g_x + base : nullptr, g_tx ? sd.g_y + base : nullptr};
+    sim_safety_wave(lane, sim_safety_params(sf.par + (size_t)p * SAF_PARAMS), sd.pos_x[p], sd.pos_y[p], sd.dt, (double)sf.tick, cnt, in,
+                    sf.rec + (size_t)p * LTPL_FLEET_SIM_SAFETY_DOUBLES, sf.inc + (size_t)p * SAF_RING, nullptr, nullptr);
+}
+
+// the test hook of the rule: one wave per case, the tick's own device function. pose[q][2], dt[q], tick[q], par[q][5],
+// objs[obj_off[q] ..][5] = x, y, px, py, r; rec[q][31] and inc[q][8][6] in and out; per_obj[..][6], per_tick[q][8] out
+__global__ __launch_bounds__(64) void k_fleet_sim_safety_eval(const double* pose, const double* dt, const int* tick, const double* par, const int* obj_off,
+                                                              const double* objs, double* rec, double* inc, double* per_obj, double* per_tick)
+{
+    const int q = blockIdx.x, lane = threadIdx.x;
+    const int o0 = obj_off[q];
+    int cnt = obj_off[q + 1] - o0;
+    if (cnt > SIM_OBJ_CAP) cnt = SIM_OBJ_CAP;          // (refused by the host)
+    if (cnt < 0) cnt = 0;
+    SafObjIn in;
+#pragma unroll
+    for (int c = 0; c < 5; ++c) in.c[c] = objs + (size_t)o0 * 5 + c;
+    in.stride = 5; in.seen_x = in.seen_y = nullptr;
+    sim_safety_wave(lane, sim_safety_params(par + (size_t)q * SAF_PARAMS), pose[2 * q], pose[2 * q + 1], dt[q], (double)tick[q], cnt, in,
+                    rec + (size_t)q * LTPL_FLEET_SIM_SAFETY_DOUBLES, inc + (size_t)q * SAF_RING, per_obj + (size_t)o0 * 6, per_tick + (size_t)q * 8);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
 struct SimSnaps;                            // snapshot slots (fleet_branch.hpp, ltpl_fleet_sim_snapshot)
@@ -1440,6 +1546,10 @@ struct FleetSim {
     bool has_sel = false;                   // the tick launches k_fleet_sim_select in front of the step kernel, which walks sl.ord
     bool staged_valid = false;              // cnt and the staging slots hold the list of the last tick (false behind a re-allocation of the
                                             // staging: a run with a selector then starts from empty lists)
+    std::vector<void*> saf_allocs;          // parameters, mask, records and incident rings of ltpl_fleet_sim_safety
+    SimSafety sf{};
+    bool has_saf = false;                   // the tick launches k_fleet_sim_safety behind telemetry, in front of the sensor
+    int saf_tick0 = 0, saf_tick = 0;        // tick0; ticks of ltpl_fleet_sim_run since the monitor was set
 };
 static void sim_free_list(std::vector<void*>& l)
 {
@@ -1458,7 +1568,7 @@ static void fleet_sim_free(FleetSim* s)
     sim_events_free(s->events);
     sim_free_list(s->stage_allocs); sim_free_list(s->race_allocs); sim_free_list(s->tele_allocs); sim_free_list(s->rec_allocs);
     sim_free_list(s->noise_allocs); sim_free_list(s->veh_allocs); sim_free_list(s->sens_allocs); sim_free_list(s->trk_allocs);
-    sim_free_list(s->pred_allocs); sim_free_list(s->sel_allocs);
+    sim_free_list(s->pred_allocs); sim_free_list(s->sel_allocs); sim_free_list(s->saf_allocs);
     for (void* p : s->allocs) (void)hipFree(p);
     if (s->velt.d_buf) (void)hipFree(s->velt.d_buf);
     delete s;
@@ -1739,6 +1849,13 @@ try {
                 hipLaunchKernelGGL(k_fleet_sim_rank, dim3(N), dim3(64), 0, st, s.sd, s.te);
                 FLEET_TRY(f, hipGetLastError());
             }
+        }
+        if (s.has_saf) {
+            // (the tick advances whether or not a planner is live, like the noise's)
+            s.sf.tick = (uint32_t)s.saf_tick0 + (uint32_t)s.saf_tick++;
+            hipLaunchKernelGGL(k_fleet_sim_safety, dim3(N), dim3(64), 0, st, s.sd, s.sf, (const double*)(s.has_noise ? s.nz.g_tx : nullptr),
+                               (const double*)(s.has_noise ? s.nz.g_ty : nullptr));
+            FLEET_TRY(f, hipGetLastError());
         }
         if (s.has_sens) {
             // (the tick advances whether or not a planner is live, like the noise's)
@@ -2929,5 +3046,152 @@ try {
         act_d[3 * i] = act[i].vbar; act_d[3 * i + 1] = act[i].clear; act_d[3 * i + 2] = act[i].J;
         act_i[2 * i] = act[i].clear_obj; act_i[2 * i + 1] = act[i].flags;
     }
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+// ---------------------------------------------------------------------------------------------------------------------
+// safety monitor (ltpl_fleet_sim_safety, include/ltpl_hip.h; the rule: fleet_safety.hpp)
+// ---------------------------------------------------------------------------------------------------------------------
+static bool sim_safety_params_ok(const double* q, std::string* why)
+{
+    static const char* const name[SAF_PARAMS] = {"r_ego", "ttc_thr", "drac_thr", "thw_thr", "margin"};
+    for (int c = 0; c < SAF_PARAMS; ++c) {
+        if (!std::isfinite(q[c])) { *why = std::string(name[c]) + " must be finite"; return false; }
+        if (c == 1 ? !(q[c] > 0.0) : !(q[c] >= 0.0)) { *why = std::string(name[c]) + (c == 1 ? " must be positive" : " must not be negative"); return false; }
+    }
+    return true;
+}
+
+// every argument is checked before the first HIP call
+static int sim_check_safety(ltpl_fleet* f, const ltpl_fleet_sim_safety_in* in, std::vector<double>* par)
+{
+    const int N = f->D.N;
+    auto bad = [&](const std::string& why) { f->err = "fleet sim safety: " + why; return LTPL_ERR_INVALID_ARG; };
+    if (!f->sim) return bad("ltpl_fleet_sim_setup first");
+    if (!in) return LTPL_OK;
+    const double* a[SAF_PARAMS] = {in->r_ego, in->ttc_thr, in->drac_thr, in->thw_thr, in->margin};
+    static const char* const name[SAF_PARAMS] = {"r_ego", "ttc_thr", "drac_thr", "thw_thr", "margin"};
+    if (!in->on) return bad("on missing");
+    for (int c = 0; c < SAF_PARAMS; ++c) if (!a[c]) return bad(std::string(name[c]) + " missing");
+    if (in->tick0 < 0) return bad("tick0 must not be negative");
+    if (in->flags & ~(uint32_t)LTPL_SIM_SAFETY_KEEP_STATE) return bad("unknown flag");
+    par->resize((size_t)N * SAF_PARAMS);
+    for (int p = 0; p < N; ++p) {
+        if (in->on[p] != 0 && in->on[p] != 1) return bad("planner " + std::to_string(p) + ": on must be 0 or 1");
+        double* q = &(*par)[(size_t)p * SAF_PARAMS];
+        for (int c = 0; c < SAF_PARAMS; ++c) q[c] = a[c][p];
+        std::string why;
+        if (!sim_safety_params_ok(q, &why)) return bad("planner " + std::to_string(p) + ": " + why);
+    }
+    return LTPL_OK;
+}
+
+extern "C" int ltpl_fleet_sim_safety(ltpl_fleet* f, const ltpl_fleet_sim_safety_in* in)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    std::vector<double> par;
+    int rc = sim_check_safety(f, in, &par);
+    if (rc) return rc;
+    if ((rc = fleet_enter(f))) return rc;
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    FleetSim& s = *f->sim;
+    if (!in) {
+        sim_free_list(s.saf_allocs);
+        s.sf = SimSafety{}; s.has_saf = false; s.saf_tick0 = s.saf_tick = 0;
+        return LTPL_OK;
+    }
+    const size_t N = (size_t)f->D.N;
+    constexpr size_t RD = LTPL_FLEET_SIM_SAFETY_DOUBLES, RI = SAF_RING;
+    const bool keep = (in->flags & LTPL_SIM_SAFETY_KEEP_STATE) && s.has_saf;
+    std::vector<double> rec(N * RD), inc(N * RI);
+    if (keep) {
+        FLEET_TRY(f, hipMemcpy(rec.data(), s.sf.rec, 8 * N * RD, hipMemcpyDeviceToHost));
+        FLEET_TRY(f, hipMemcpy(inc.data(), s.sf.inc, 8 * N * RI, hipMemcpyDeviceToHost));
+    } else {
+        for (size_t p = 0; p < N; ++p) fleet::safety_start(rec.data() + p * RD, inc.data() + p * RI);
+    }
+    // everything new is allocated first; the fleet keeps its previous monitor, its tick count, records and rings unless every step succeeds
+    SimAllocs al;
+    SimSafety sf{};
+    double* d_par = nullptr; int* d_on = nullptr;
+    if ((rc = sim_upload(f, al.p, par.data(), par.size(), &d_par))) return rc;
+    if ((rc = sim_upload(f, al.p, in->on, N, &d_on))) return rc;
+    if ((rc = sim_upload(f, al.p, rec.data(), rec.size(), &sf.rec))) return rc;
+    if ((rc = sim_upload(f, al.p, inc.data(), inc.size(), &sf.inc))) return rc;
+    sf.par = d_par; sf.on = d_on;
+    sim_free_list(s.saf_allocs);
+    s.saf_allocs.swap(al.p);
+    s.sf = sf; s.has_saf = true; s.saf_tick0 = in->tick0; s.saf_tick = 0;
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+extern "C" int ltpl_fleet_sim_safety_read(ltpl_fleet* f, double* out, int32_t doubles_per_planner, double* incidents, int32_t doubles_per_incident)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    auto bad = [&](const std::string& why) { f->err = "fleet sim safety: " + why; return LTPL_ERR_INVALID_ARG; };
+    if (!f->sim) return bad("ltpl_fleet_sim_setup first");
+    if (!f->sim->has_saf) return bad("the monitor is off (ltpl_fleet_sim_safety first)");
+    if (!out) return bad("out missing");
+    if (doubles_per_planner != LTPL_FLEET_SIM_SAFETY_DOUBLES) return bad("record size mismatch");
+    if (incidents && doubles_per_incident != LTPL_FLEET_SIM_SAFETY_INCIDENT_DOUBLES) return bad("incident size mismatch");
+    const size_t N = (size_t)f->D.N;
+    FLEET_TRY(f, hipSetDevice(f->h->device));
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    FLEET_TRY(f, hipMemcpy(out, f->sim->sf.rec, sizeof(double) * N * LTPL_FLEET_SIM_SAFETY_DOUBLES, hipMemcpyDeviceToHost));
+    if (incidents) FLEET_TRY(f, hipMemcpy(incidents, f->sim->sf.inc, sizeof(double) * N * SAF_RING, hipMemcpyDeviceToHost));
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+extern "C" int ltpl_fleet_sim_safety_eval(ltpl_fleet* f, int32_t n_cases, const double* pose, const double* dt, const int32_t* tick, const double* params,
+                                          const int32_t* obj_off, const double* objs, double* rec, double* inc, double* per_obj, double* per_tick)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    auto bad = [&](const std::string& why) { f->err = "fleet sim safety eval: " + why; return LTPL_ERR_INVALID_ARG; };
+    if (n_cases < 0) return bad("n_cases must not be negative");
+    if (n_cases == 0) return LTPL_OK;
+    if (!pose || !dt || !tick || !params || !obj_off || !rec || !inc || !per_tick) return bad("an array is missing");
+    if (obj_off[0] != 0) return bad("object offsets must start at 0");
+    for (int q = 0; q < n_cases; ++q) {
+        const std::string who = "case " + std::to_string(q) + ": ";
+        const int n = obj_off[q + 1] - obj_off[q];
+        if (n < 0 || n > SIM_OBJ_CAP) return bad(who + "0 .. 96 objects");
+        std::string why;
+        if (!sim_safety_params_ok(params + (size_t)q * SAF_PARAMS, &why)) return bad(who + why);
+        if (!std::isfinite(dt[q]) || !(dt[q] > 0.0)) return bad(who + "dt must be finite and positive");
+        if (tick[q] < 0) return bad(who + "tick must not be negative");
+    }
+    const size_t m = (size_t)n_cases, no = (size_t)obj_off[n_cases];
+    if (no > 0 && (!objs || !per_obj)) return bad("objs / per_obj missing");
+    constexpr size_t RD = LTPL_FLEET_SIM_SAFETY_DOUBLES, RI = SAF_RING;
+    int rc = fleet_enter(f);
+    if (rc) return rc;
+    Arena ar;     // one device block
+    const size_t o_pose = ar.add(16 * m), o_dt = ar.add(8 * m), o_par = ar.add(8 * SAF_PARAMS * m), o_objs = ar.add(40 * (no ? no : 1)),
+                 o_rec = ar.add(8 * RD * m), o_inc = ar.add(8 * RI * m), o_po = ar.add(48 * (no ? no : 1)), o_pt = ar.add(64 * m), o_tick = ar.add(4 * m),
+                 o_off = ar.add(4 * (m + 1));
+    unsigned char* d = nullptr;
+    struct Guard { void* a = nullptr; ~Guard() { if (a) (void)hipFree(a); } } gd;
+    FLEET_TRY(f, hipMalloc(reinterpret_cast<void**>(&d), ar.size)); gd.a = d;
+    FLEET_TRY(f, hipMemset(d, 0, ar.size));
+    FLEET_TRY(f, hipMemcpy(d + o_pose, pose, 16 * m, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_dt, dt, 8 * m, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_par, params, 8 * SAF_PARAMS * m, hipMemcpyHostToDevice));
+    if (no) FLEET_TRY(f, hipMemcpy(d + o_objs, objs, 40 * no, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_rec, rec, 8 * RD * m, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_inc, inc, 8 * RI * m, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_tick, tick, 4 * m, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_off, obj_off, 4 * (m + 1), hipMemcpyHostToDevice));
+    hipStream_t st = f->h->stream;
+    FLEET_TRY(f, hipStreamSynchronize(st));
+    hipLaunchKernelGGL(k_fleet_sim_safety_eval, dim3((unsigned)m), dim3(64), 0, st, (const double*)(d + o_pose), (const double*)(d + o_dt),
+                       (const int*)(d + o_tick), (const double*)(d + o_par), (const int*)(d + o_off), (const double*)(d + o_objs),
+                       reinterpret_cast<double*>(d + o_rec), reinterpret_cast<double*>(d + o_inc), reinterpret_cast<double*>(d + o_po),
+                       reinterpret_cast<double*>(d + o_pt));
+    FLEET_TRY(f, hipGetLastError());
+    FLEET_TRY(f, hipMemcpyAsync(rec, d + o_rec, 8 * RD * m, hipMemcpyDeviceToHost, st));
+    FLEET_TRY(f, hipMemcpyAsync(inc, d + o_inc, 8 * RI * m, hipMemcpyDeviceToHost, st));
+    FLEET_TRY(f, hipMemcpyAsync(per_tick, d + o_pt, 64 * m, hipMemcpyDeviceToHost, st));
+    if (no) FLEET_TRY(f, hipMemcpyAsync(per_obj, d + o_po, 48 * no, hipMemcpyDeviceToHost, st));
+    FLEET_TRY(f, hipStreamSynchronize(st));
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))

@@ -20,6 +20,8 @@ from .sim import SENSOR_DOUBLES, SENSOR_FIELDS, SENSOR_PARAMS, sensor_dict, sens
 from .sim import TRACK_CAP, TRACK_DOUBLES, TRACK_FIELDS, TRACKER_DEFAULTS, TRACKER_DOUBLES, TRACKER_FIELDS, TRACKER_PARAMS, tracker_dict      # noqa: F401
 from .sim import PREDICTOR_DEFAULTS, PREDICTOR_DOUBLES, PREDICTOR_FIELDS, PREDICTOR_MAX_POINTS, PREDICTOR_PARAMS, predictor_dict      # noqa: F401
 from .sim import SELECTOR_DEFAULTS, SELECTOR_DOUBLES, SELECTOR_FIELDS, SELECTOR_MAX_ROWS, SELECTOR_PARAMS, selector_dict      # noqa: F401
+from .sim import (INCIDENT_DOUBLES, INCIDENT_FIELDS, SAFETY_DEFAULTS, SAFETY_DOUBLES, SAFETY_FIELDS, SAFETY_INCIDENTS, SAFETY_KEEP_STATE,      # noqa: F401
+                  SAFETY_PARAMS, safety_dict, safety_start)
 from .sim import pack_events as sim_pack_events
 
 
@@ -76,6 +78,10 @@ class SimPredictorIn(C.Structure):         # ltpl_fleet_sim_predictor_in
 
 class SimSelectorIn(C.Structure):          # ltpl_fleet_sim_selector_in
     _fields_ = [("on", C.c_void_p)] + [(k, C.c_void_p) for k in SELECTOR_PARAMS]
+
+
+class SimSafetyIn(C.Structure):            # ltpl_fleet_sim_safety_in
+    _fields_ = [("on", C.c_void_p)] + [(k, C.c_void_p) for k in SAFETY_PARAMS] + [("tick0", C.c_int32), ("flags", C.c_uint32)]
 
 
 class SimRecordHead(C.Structure):         # ltpl_fleet_sim_record_head
@@ -152,6 +158,10 @@ class Fleet(Planner):
             f("sim_selector").argtypes = [C.c_void_p, C.POINTER(SimSelectorIn)]
             f("sim_selector_read").argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
             f("sim_selector_eval").argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 10
+        if hasattr(self.lib, "ltpl_fleet_sim_safety"):
+            f("sim_safety").argtypes = [C.c_void_p, C.POINTER(SimSafetyIn)]
+            f("sim_safety_read").argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
+            f("sim_safety_eval").argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 10
         if hasattr(self.lib, "ltpl_fleet_friction"):
             f("friction").argtypes = [C.c_void_p, C.POINTER(FrictionIn)]
             f("friction_scale").argtypes = [C.c_void_p, C.c_void_p]
@@ -964,6 +974,65 @@ class Fleet(Planner):
                                                   off.ctypes.data, flat.ctypes.data, order.ctypes.data, act_d.ctypes.data, act_i.ctypes.data,
                                                   rec.ctypes.data))
         return [order[q, :lists[q, 0]].copy() for q in range(m)], act_d[:m], act_i[:m], rec[:m]
+
+    # ---- safety monitor on the device -------------------------------------------------------------------------------------------------
+    def sim_safety(self, on=True, tick0=0, keep_state=False, **params):
+        """A safety monitor per planner (ltpl_fleet_sim_safety; after ``sim_setup``, between runs at any time): every live tick the staged
+        objects -- in front of sensor and tracker, at their true positions -- are measured against the true pose and its displacement since
+        the previous live tick: time to collision, required deceleration, time headway, gap and closing speed, accumulated into a 31-double
+        record (``sim.SAFETY_FIELDS``) and a ring of the last 8 incidents (``sim.INCIDENT_FIELDS``; an incident: consecutive evaluated ticks
+        with TTC under ``ttc_thr``). Measurement only: the run is bit-identical with and without it. Parameters (``sim.SAFETY_PARAMS``,
+        defaults ``sim.SAFETY_DEFAULTS``) and ``on``: scalars or one per planner; ``tick0``: the monitor's tick of the next fleet tick.
+        ``keep_state=True`` changes parameters, mask and tick0 and keeps records and rings. ``on=None`` clears the monitor. Host mirror:
+        ``sim.SafetyModel``."""
+        if on is None:
+            self._check(self._fn("sim_safety")(self.handle, None))
+            return
+        unknown = set(params) - set(SAFETY_PARAMS)
+        if unknown:
+            raise ValueError("sim_safety: unknown parameter %s" % sorted(unknown))
+        n = self.n_scen
+        si = SimSafetyIn()
+        val = dict(SAFETY_DEFAULTS, **params)
+        keep = [np.ascontiguousarray(np.broadcast_to(np.asarray(on), (n,)).astype(np.int32))]
+        si.on = keep[0].ctypes.data
+        for name in SAFETY_PARAMS:
+            keep.append(np.ascontiguousarray(np.broadcast_to(np.asarray(val[name], np.float64), (n,))))
+            setattr(si, name, keep[-1].ctypes.data)
+        si.tick0, si.flags = int(tick0), SAFETY_KEEP_STATE if keep_state else 0
+        self._check(self._fn("sim_safety")(self.handle, C.byref(si)))
+
+    def sim_safety_read(self, raw=False):
+        """(records, incidents): the dict of named arrays (``sim.SAFETY_FIELDS``; ``raw=True``: the [n, 31] records) and the incident rings
+        [n, 8, 6] (``sim.INCIDENT_FIELDS``; NaN: unwritten; ``sim.safety_incidents`` orders a ring) (ltpl_fleet_sim_safety_read)."""
+        out = np.zeros((self.n_scen, SAFETY_DOUBLES), np.float64)
+        inc = np.zeros((self.n_scen, SAFETY_INCIDENTS, INCIDENT_DOUBLES), np.float64)
+        self._check(self._fn("sim_safety_read")(self.handle, out.ctypes.data, SAFETY_DOUBLES, inc.ctypes.data, INCIDENT_DOUBLES))
+        return (out if raw else safety_dict(out)), inc
+
+    def sim_safety_eval(self, pose, dt, tick, params, objs, rec=None, inc=None):
+        """The monitor's test hook (ltpl_fleet_sim_safety_eval): independent cases on the device, one wave and one live tick each.
+        ``pose`` [m, 2], ``dt`` [m], ``tick`` [m], ``params`` [m, 5] in the order of ``sim.SAFETY_PARAMS``; per case ``objs`` [n_q, 5] = x,
+        y, px, py, r; ``rec`` [m, 31] and ``inc`` [m, 8, 6]: records and rings before (default: the start state). Returns (records after,
+        rings after, per_obj: a list of [n_q, 6] = ttc, drac, thw, gap, closing, flags, per_tick [m, 8]); equals ``sim.safety_tick`` bit
+        for bit."""
+        objs = [np.asarray(o, np.float64).reshape(-1, 5) for o in objs]
+        m = len(objs)
+        k = max(m, 1)
+        pose = np.ascontiguousarray(np.broadcast_to(np.asarray(pose, np.float64), (m, 2)).reshape(m, 2), np.float64)
+        dt = np.ascontiguousarray(np.broadcast_to(np.asarray(dt, np.float64), (m,)), np.float64)
+        tick = np.ascontiguousarray(np.broadcast_to(np.asarray(tick), (m,)).astype(np.int32))
+        params = np.ascontiguousarray(np.broadcast_to(np.asarray(params, np.float64), (m, len(SAFETY_PARAMS))), np.float64)
+        off = np.ascontiguousarray(np.concatenate(([0], np.cumsum([o.shape[0] for o in objs]))).astype(np.int32))
+        flat = np.ascontiguousarray(np.concatenate(objs + [np.zeros((1, 5))]))
+        r0, i0 = safety_start(k)
+        rec = r0 if rec is None else np.ascontiguousarray(np.asarray(rec, np.float64).reshape(k, SAFETY_DOUBLES).copy())
+        inc = i0 if inc is None else np.ascontiguousarray(np.asarray(inc, np.float64).reshape(k, SAFETY_INCIDENTS, INCIDENT_DOUBLES).copy())
+        per_obj, per_tick = np.zeros((flat.shape[0], 6)), np.zeros((k, 8))
+        self._check(self._fn("sim_safety_eval")(self.handle, m, pose.ctypes.data, dt.ctypes.data, tick.ctypes.data, params.ctypes.data,
+                                                off.ctypes.data, flat.ctypes.data, rec.ctypes.data, inc.ctypes.data, per_obj.ctypes.data,
+                                                per_tick.ctypes.data))
+        return rec[:m], inc[:m], [per_obj[off[q]:off[q + 1]].copy() for q in range(m)], per_tick[:m]
 
     # ---- friction maps on the device ------------------------------------------------------------------------------------------------
     def friction(self, maps, map_idx=None, scale=1.0):

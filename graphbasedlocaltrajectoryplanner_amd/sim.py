@@ -1435,3 +1435,234 @@ class SelectorModel(object):
 
     def as_dict(self):
         return selector_dict(self.rec)
+
+
+# ---- safety monitor (ltpl_fleet_sim_safety, include/ltpl_hip.h; csrc/fleet_safety.hpp) ------------------------------------------------------
+# name, index, integer valued: the record of ltpl_fleet_sim_safety_read (LTPL_FLEET_SIM_SAFETY_DOUBLES = 31 per planner; hist: 8 bins)
+SAFETY_FIELDS = (("ticks", 0, True), ("ticks_eval", 1, True), ("prev_x", 2, False), ("prev_y", 3, False), ("prev_valid", 4, True),
+                 ("gap_min", 5, False), ("gap_tick", 6, True), ("gap_slot", 7, True), ("ttc_min", 8, False), ("ttc_tick", 9, True),
+                 ("ttc_slot", 10, True), ("tet", 11, False), ("tit", 12, False), ("drac_max", 13, False), ("drac_tick", 14, True),
+                 ("drac_ticks", 15, True), ("thw_min", 16, False), ("thw_ticks", 17, True), ("overlap_ticks", 18, True), ("impact_max", 19, False),
+                 ("n_skipped", 20, True), ("n_incidents", 21, True), ("inc_open", 22, True), ("hist", 23, True))
+SAFETY_DOUBLES = 31
+SAFETY_HIST = 8
+# an entry of the incident ring (LTPL_FLEET_SIM_SAFETY_INCIDENTS = 8 entries of 6 doubles per planner; unwritten entries are NaN)
+INCIDENT_FIELDS = ("tick_first", "tick_last", "ttc_min", "slot", "gap_min", "closing_max")
+SAFETY_INCIDENTS = 8
+INCIDENT_DOUBLES = 6
+SAFETY_PARAMS = ("r_ego", "ttc_thr", "drac_thr", "thw_thr", "margin")
+SAFETY_DEFAULTS = dict(r_ego=1.5, ttc_thr=3.0, drac_thr=3.0, thw_thr=1.0, margin=0.5)
+SAFETY_INGEST_T = 0.2                     # s: the horizon of the ingestion's point (ObjectListInterface.py:121)
+SAFETY_KEEP_STATE = 1                     # LTPL_SIM_SAFETY_KEEP_STATE
+SAF_SKIPPED, SAF_OVERLAP, SAF_COURSE, SAF_CORRIDOR = 1, 2, 4, 8      # flags of an object
+_INF = float("inf")
+
+
+def safety_dict(rows):
+    """[n, 31] records as a dict of named arrays (counters as int64; ``hist``: [n, 8])."""
+    rows = np.asarray(rows, np.float64).reshape(-1, SAFETY_DOUBLES)
+    out = {name: (rows[:, i].astype(np.int64) if is_int else rows[:, i].copy()) for name, i, is_int in SAFETY_FIELDS if name != "hist"}
+    out["hist"] = rows[:, 23:31].astype(np.int64)
+    return out
+
+
+def safety_incidents(ring, n_incidents):
+    """The incidents a planner's ring [8, 6] still holds, oldest first, as dicts of ``INCIDENT_FIELDS``."""
+    ring = np.asarray(ring, np.float64).reshape(SAFETY_INCIDENTS, INCIDENT_DOUBLES)
+    n = int(n_incidents)
+    return [dict(zip(INCIDENT_FIELDS, (float(v) for v in ring[i % SAFETY_INCIDENTS]))) for i in range(max(0, n - SAFETY_INCIDENTS), n)]
+
+
+def safety_start(n=1):
+    """(records [n, 31], rings [n, 8, 6]) in the start state."""
+    rec = np.zeros((int(n), SAFETY_DOUBLES))
+    rec[:, [5, 8, 16]] = np.inf
+    return rec, np.full((int(n), SAFETY_INCIDENTS, INCIDENT_DOUBLES), np.nan)
+
+
+def _saf_finite(v):
+    return v - v == 0.0
+
+
+def _saf_div(a, b):
+    """a / b as IEEE fp64 does it where Python raises."""
+    if b != 0.0:
+        return a / b
+    if a != a or a == 0.0:
+        return float("nan")
+    return math.copysign(_INF, a) * math.copysign(1.0, b)
+
+
+def _saf_sqrt(v):
+    return math.sqrt(v) if v >= 0.0 else (v if v == 0.0 else float("nan"))
+
+
+def safety_object(par, px, py, wx, wy, obj):
+    """Steps 1 .. 11 of csrc/fleet_safety.hpp for one object (x, y, px, py, r): (ttc, drac, thw, gap, closing, flags)."""
+    r_ego, margin = par[0], par[4]
+    ox, oy, qx, qy, r_o = (float(v) for v in obj)
+    ux, uy = (qx - ox) / 0.2, (qy - oy) / 0.2
+    rx, ry, vx, vy = ox - px, oy - py, ux - wx, uy - wy
+    rr = rx * rx + ry * ry
+    dist = _saf_sqrt(rr)
+    gap = (dist - r_o) - r_ego
+    rho = r_o + r_ego
+    c, b, a = rr - rho * rho, rx * vx + ry * vy, vx * vx + vy * vy
+    if not (_saf_finite(rr) and _saf_finite(a) and _saf_finite(b) and _saf_finite(r_o)):
+        return (_INF, 0.0, _INF, gap, 0.0, SAF_SKIPPED)
+    overlap = not gap > 0.0
+    closing = 0.0
+    if dist == 0.0:
+        closing = _saf_sqrt(a)
+    elif b < 0.0:
+        closing = (-b) / dist
+    disc = b * b - a * c
+    course = b < 0.0 and disc >= 0.0
+    ttc = _INF
+    if overlap or not c > 0.0:
+        ttc = 0.0
+    elif course:
+        ttc = _saf_div(c, _saf_sqrt(disc) - b)
+    drac = _saf_div(closing * closing, 2.0 * gap) if (not overlap and course) else 0.0
+    w2 = wx * wx + wy * wy
+    wn = _saf_sqrt(w2)
+    thw, corridor = _INF, False
+    if wn > 0.0:
+        lon, lat = (rx * wx + ry * wy) / wn, (rx * wy - ry * wx) / wn
+        al = -lat if lat < 0.0 else lat
+        if lon > 0.0 and al <= rho + margin:
+            corridor = True
+            d = lon - rho
+            thw = d / wn if d > 0.0 else 0.0
+    return (ttc, drac, thw, gap, closing, (SAF_OVERLAP if overlap else 0) | (SAF_COURSE if course else 0) | (SAF_CORRIDOR if corridor else 0))
+
+
+def safety_objects(staged, true_xy=None):
+    """The rule's objects [n, 5] = x, y, px, py, r from a staged list ``staged`` [n, 5] (the positions the planner PERCEIVED, the 0.2 s
+    points built from them, radii) and, under sensor noise, the TRUE positions ``true_xy`` [n, 2] of the same objects: the true position
+    and the perceived displacement, Q = X_true + (Q_staged - X_perceived), as k_fleet_sim_safety forms it. ``true_xy`` None (noise off):
+    the staged list as it is."""
+    staged = np.asarray(staged, np.float64).reshape(-1, 5)
+    if true_xy is None:
+        return staged.copy()
+    t = np.asarray(true_xy, np.float64).reshape(-1, 2)
+    out = staged.copy()
+    out[:, 0:2] = t
+    out[:, 2:4] = t + (staged[:, 2:4] - staged[:, 0:2])
+    return out
+
+
+def safety_tick(par, px, py, dt, tick, objs, rec, inc):
+    """One live tick of the rule on a record ``rec`` [31] and a ring ``inc`` [8, 6], both updated in place (the test hook's case).
+    ``objs``: [n, 5] = x, y, px, py, r. Returns (per_obj [n, 6], per_tick [8] = gap_t, gap_slot, ttc_t, ttc_slot, drac_t, thw_t, impact_t,
+    closing_t)."""
+    par = [float(v) for v in par]
+    px, py, dt, tick = float(px), float(py), float(dt), float(tick)
+    objs = np.asarray(objs, np.float64).reshape(-1, 5)
+    evaluated = rec[4] != 0.0
+    wx, wy = ((px - float(rec[2])) / dt, (py - float(rec[3])) / dt) if evaluated else (0.0, 0.0)
+    gap_t, gap_slot, ttc_t, ttc_slot, drac_t, thw_t, impact_t, closing_t, overlaps, skipped = _INF, -1, _INF, -1, 0.0, _INF, 0.0, 0.0, 0, 0
+    per_obj = np.zeros((objs.shape[0], 6))
+    for k in range(objs.shape[0]):
+        o = safety_object(par, px, py, wx, wy, objs[k])
+        per_obj[k] = o
+        ttc, drac, thw, gap, closing, flags = o
+        if flags & SAF_SKIPPED:
+            skipped += 1
+            continue
+        if gap < gap_t or (gap == gap_t and gap_slot < 0):
+            gap_t, gap_slot = gap, k
+        if ttc < ttc_t or (ttc == ttc_t and ttc_slot < 0):
+            ttc_t, ttc_slot = ttc, k
+        drac_t = drac if drac > drac_t else drac_t
+        thw_t = thw if thw < thw_t else thw_t
+        closing_t = closing if closing > closing_t else closing_t
+        if flags & SAF_OVERLAP:
+            overlaps += 1
+            impact_t = closing if closing > impact_t else impact_t
+    per_tick = np.array([gap_t, gap_slot, ttc_t, ttc_slot, drac_t, thw_t, impact_t, closing_t], np.float64)
+    ttc_thr, drac_thr, thw_thr = par[1], par[2], par[3]
+    rec[0] += 1.0
+    if gap_t < rec[5]:
+        rec[5], rec[6], rec[7] = gap_t, tick, float(gap_slot)
+    if overlaps > 0:
+        rec[18] += 1.0
+    rec[2], rec[3], rec[4] = px, py, 1.0
+    if not evaluated:
+        return per_obj, per_tick
+    rec[1] += 1.0
+    if ttc_t < rec[8]:
+        rec[8], rec[9], rec[10] = ttc_t, tick, float(ttc_slot)
+    below = ttc_t < ttc_thr
+    if below:
+        rec[11] = float(rec[11]) + dt
+        rec[12] = float(rec[12]) + (ttc_thr - ttc_t) * dt
+    if drac_t > rec[13]:
+        rec[13], rec[14] = drac_t, tick
+    if drac_t > drac_thr:
+        rec[15] += 1.0
+    if thw_t < rec[16]:
+        rec[16] = thw_t
+    if thw_t < thw_thr:
+        rec[17] += 1.0
+    if impact_t > rec[19]:
+        rec[19] = impact_t
+    rec[20] += float(skipped)
+    b = 7
+    for j in range(6, -1, -1):
+        if ttc_t < (ttc_thr * float(j + 1)) / 7.0:
+            b = j
+    rec[23 + b] += 1.0
+    if not below:
+        rec[22] = 0.0
+        return per_obj, per_tick
+    if rec[22] == 0.0:
+        rec[21] += 1.0
+        rec[22] = 1.0
+        inc[(int(rec[21]) - 1) % SAFETY_INCIDENTS] = (tick, tick, ttc_t, float(ttc_slot), gap_t, closing_t)
+    else:
+        e = inc[(int(rec[21]) - 1) % SAFETY_INCIDENTS]
+        e[1] = tick
+        if ttc_t < e[2]:
+            e[2], e[3] = ttc_t, float(ttc_slot)
+        if gap_t < e[4]:
+            e[4] = gap_t
+        if closing_t > e[5]:
+            e[5] = closing_t
+    return per_obj, per_tick
+
+
+class SafetyModel(object):
+    """Scalar host mirror of the safety monitor in the operation order of csrc/fleet_safety.hpp: plain Python floats, + - * / sqrt and
+    comparisons, so the device's bits. ``on`` and the parameters of ``SAFETY_PARAMS``: scalars or one per planner. ``tick0``: the monitor's
+    tick of the next fleet tick. One fleet tick: ``step(p, pose, objs, dt)`` for every LIVE planner p (pose: the TRUE (x, y) of the tick,
+    objs: [cnt, 5] = x, y, px, py, r of the staged list; under sensor noise ``safety_objects(staged, true_xy)``: true positions, perceived
+    displacements), then ``advance()`` -- the tick index advances whether or not a planner was live. ``rec`` [n, 31] and ``inc`` [n, 8, 6] are the records and rings."""
+
+    def __init__(self, n, on=True, tick0=0, **params):
+        self.n = int(n)
+        unknown = set(params) - set(SAFETY_PARAMS)
+        if unknown:
+            raise ValueError("SafetyModel: unknown parameter %s" % sorted(unknown))
+        self.rec, self.inc = safety_start(self.n)
+        self.configure(on, tick0, **params)
+        self.last = [None] * self.n       # (per_obj, per_tick) of every planner's latest tick
+
+    def configure(self, on=True, tick0=0, **params):
+        """New mask, parameters and tick index; records and rings stay (LTPL_SIM_SAFETY_KEEP_STATE)."""
+        val = dict(SAFETY_DEFAULTS, **params)
+        self.on = [bool(x) for x in np.broadcast_to(np.asarray(on), (self.n,))]
+        self.par = np.ascontiguousarray(np.stack([np.broadcast_to(np.asarray(val[k], np.float64), (self.n,)) for k in SAFETY_PARAMS], axis=1))
+        self.tick = int(tick0)
+
+    def step(self, p, pose, objs, dt):
+        if not self.on[p]:
+            return None
+        self.last[p] = safety_tick(self.par[p], pose[0], pose[1], dt, self.tick, objs, self.rec[p], self.inc[p])
+        return self.last[p]
+
+    def advance(self):
+        self.tick += 1
+
+    def as_dict(self):
+        return safety_dict(self.rec)

@@ -66,7 +66,8 @@ extern "C" {
                                      ltpl_fleet_sim_sensor / _sensor_read / _sensor_eval,
                                      ltpl_fleet_sim_tracker / _tracker_read / _tracker_eval,
                                      ltpl_fleet_sim_predictor / _predictor_read / _predictor_eval,
-                                     ltpl_fleet_sim_selector / _selector_read / _selector_eval */
+                                     ltpl_fleet_sim_selector / _selector_read / _selector_eval,
+                                     ltpl_fleet_sim_safety / _safety_read / _safety_eval */
 
 /* status codes */
 #define LTPL_OK               0
@@ -1446,6 +1447,104 @@ int ltpl_fleet_sim_selector_read(ltpl_fleet* fleet, double* out, int32_t doubles
 int ltpl_fleet_sim_selector_eval(ltpl_fleet* fleet, int32_t n_cases, const double* params, const int32_t* lists, const int32_t* n_rows,
                                  const double* rows, const int32_t* obj_off, const double* objs, int32_t* ordered, double* act_d, int32_t* act_i,
                                  double* rec);
+
+/* ------------------------------------------------------------------------------------------------------------------------------------------
+ * Additive to ABI v9 -- SAFETY MONITOR: surrogate safety measures per planner and tick -- time to collision, time exposed below a TTC
+ * threshold, required deceleration, time headway, impact speed -- accumulated into a record, plus a log of the near misses (csrc/fleet_sim.hpp:
+ * k_fleet_sim_safety; the rule: csrc/fleet_safety.hpp). Telemetry's clear_min and contact_ticks are distances and blind to time; this says
+ * how fast the gap was closing and WHEN, so that the flight recorder and a snapshot can be pointed at the tick. MEASUREMENT ONLY: no kernel
+ * of the tick reads what it writes. Off by default.
+ * ARITHMETIC: fp64, + - * / sqrt and comparisons only, one fixed order (the library is built with -ffp-contract=off), no trigonometry: the
+ * host mirror sim.SafetyModel and the device agree to the last bit.
+ * INPUTS of planner p in a tick in which it is live: the TRUE pose P = (px, py) behind the step and mates kernels; dt; the monitor's tick
+ * index (tick0 + fleet ticks since the call: like the noise's it advances whether or not the planner is live); the staged on-track list --
+ * what telemetry reads, in FRONT of sensor and tracker: an object the sensor hides is still measured -- per object position X (the noise's
+ * TRUE position while noise is on), the ingestion's 0.2 s point Q, radius r_o; PER PLANNER on (0 / 1), r_ego >= 0 [m], ttc_thr > 0 [s],
+ * drac_thr >= 0 [m/s^2], thw_thr >= 0 [s], margin >= 0 [m], all finite.
+ *   | step        | rule                                                                                                              |
+ *   | ego velocity| W = ((px - prev_x) / dt, (py - prev_y) / dt) from the pose of the previous live tick (the record keeps it): the      |
+ *   |             | displacement the car really made, whatever drives it. A live tick WITHOUT a valid previous pose (the first after    |
+ *   |             | the call, the first after a branch from a source without a record) counts in ticks, moves the gap fields and        |
+ *   |             | overlap_ticks with W = (0, 0) and stores the pose; nothing else moves. Every other live tick is EVALUATED           |
+ *   | 1           | ux = (qx - ox) / 0.2, uy = (qy - oy) / 0.2                                                                          |
+ *   | 2           | rx = ox - px, ry = oy - py; vx = ux - wx, vy = uy - wy                                                              |
+ *   | 3           | rr = rx rx + ry ry; dist = sqrt(rr)                                                                                 |
+ *   | 4           | gap = (dist - r_o) - r_ego  (gap_min == telemetry's clear_min - r_ego bit for bit)                                  |
+ *   | 5           | rho = r_o + r_ego; c = rr - rho rho; b = rx vx + ry vy; a = vx vx + vy vy                                           |
+ *   | 6           | rr, a, b or r_o not finite: the object is SKIPPED -- counted, takes part in nothing                                 |
+ *   | 7           | overlap = !(gap > 0)                                                                                                |
+ *   | 8           | closing = b < 0 ? (-b) / dist : 0; with dist == 0: sqrt(a)                                                          |
+ *   | 9  TTC      | 0 when overlap or !(c > 0); else on a COLLISION COURSE (b < 0 and disc = b b - a c >= 0): c / (sqrt(disc) - b);      |
+ *   |             | else +inf  (two discs at constant velocity)                                                                         |
+ *   | 10 DRAC     | (closing closing) / (2 gap) when not overlapping and on a collision course, else 0                                  |
+ *   | 11 headway  | w2 = wx wx + wy wy, wn = sqrt(w2); with wn > 0: lon = (rx wx + ry wy) / wn, lat = (rx wy - ry wx) / wn; IN THE       |
+ *   |             | CORRIDOR when lon > 0 and |lat| <= rho + margin: thw = (lon - rho) / wn, 0 when !(lon - rho > 0); otherwise, and      |
+ *   |             | with wn == 0, +inf                                                                                                  |
+ *   | per tick    | gap_t, ttc_t: minima on the key (value, slot), ties to the lower slot, a NaN never wins, slot -1 without an object;  |
+ *   |             | drac_t a maximum (from 0); thw_t a minimum; overlap_t any overlap; impact_t the largest closing over the overlapping |
+ *   |             | objects, closing_t over all (from 0); skipped_t a count                                                             |
+ * THE RECORD, LTPL_FLEET_SIM_SAFETY_DOUBLES doubles: [0] ticks (live ticks seen) [1] ticks_eval [2] prev_x [3] prev_y [4] prev_valid
+ *   [5] gap_min [6] gap_tick [7] gap_slot (strictly smaller replaces) [8] ttc_min [9] ttc_tick [10] ttc_slot (strictly smaller replaces)
+ *   [11] tet += dt on a tick with ttc_t < ttc_thr [12] tit += (ttc_thr - ttc_t) dt on the same ticks [13] drac_max [14] drac_tick (strictly
+ *   larger replaces) [15] drac_ticks: ticks with drac_t > drac_thr [16] thw_min [17] thw_ticks: ticks with thw_t < thw_thr [18] overlap_ticks
+ *   [19] impact_max [20] n_skipped [21] n_incidents [22] inc_open [23] .. [30] hist: an evaluated tick goes into the first bin j in 0 .. 6
+ *   with ttc_t < (ttc_thr (j + 1)) / 7, else bin 7 (+inf: bin 7). The gap fields and overlap_ticks move on every live tick, everything else
+ *   on evaluated ticks only. Start state: zeros, gap_min = ttc_min = thw_min = +inf.
+ * THE INCIDENT LOG: a ring of LTPL_FLEET_SIM_SAFETY_INCIDENTS entries of LTPL_FLEET_SIM_SAFETY_INCIDENT_DOUBLES doubles per planner:
+ *   tick_first, tick_last, ttc_min, slot, gap_min, closing_max; unwritten entries are NaN. An incident OPENS on an evaluated tick with
+ *   ttc_t < ttc_thr while inc_open == 0: n_incidents += 1 and entry (n_incidents - 1) mod 8 is set from this tick. While it is open and
+ *   ttc_t < ttc_thr: tick_last moves, a strictly smaller ttc_t replaces ttc_min and slot, gap_min takes the minimum, closing_max the
+ *   maximum. The first evaluated tick with !(ttc_t < ttc_thr) closes it. An overlap has TTC 0: every contact is an incident.
+ * IN THE TICK: k_fleet_sim_safety (one wave64 per planner, registers only) runs behind k_fleet_sim_tele / k_fleet_sim_rank and in front of
+ * k_fleet_sim_sense, only while a monitor is set; a planner that is not live or has on == 0 returns at once. A fleet that never calls this
+ * entry point launches the kernels it launched before, with the same arguments.
+ *   | with                          | what happens                                                                                 |
+ *   | ltpl_fleet_sim_setup          | switched off                                                                                 |
+ *   | noise                         | positions are the TRUE ones; the 0.2 s displacement Q - (staged x, y) is the PERCEIVED one (the |
+ *   |                               | staging holds no true heading: a limit): the rule is handed Q = X_true + (Q_staged - X_staged), |
+ *   |                               | so the position error itself never enters the object's velocity                              |
+ *   | sensor / tracker / predictor / selector | not read: the monitor measures the staged list in front of them                    |
+ *   | races                         | mates are staged behind the own objects and measured like them                               |
+ *   | telemetry                     | independent: either can be on alone                                                          |
+ *   | snapshot / branch             | record and ring are what the tick writes: they TRAVEL (k_fleet_sim_branch_safety behind        |
+ *   |                               | k_fleet_sim_branch); parameters stay the destination's. A snapshot taken with the monitor on   |
+ *   |                               | holds them; a source without a record (a snapshot taken with the monitor off) leaves the       |
+ *   |                               | destination the start state with prev_valid = 0. Snapshot, run, restore,                       |
+ *   |                               | ltpl_fleet_sim_safety(KEEP_STATE, tick0 = the snapshot's tick), run reproduces record and ring |
+ *   | events                        | no new kind                                                                                  |
+ *   | ltpl_fleet_sim_race / _predictor | kept: the kernel reads the staging through the pointers of the launch                      |
+ *   | a failed planner              | skipped; its record stays                                                                    |
+ * THE CALL: after ltpl_fleet_sim_setup at any time between runs; in == NULL clears the monitor. Every argument is checked before the first
+ * HIP call: every array present, on 0 or 1, the parameters as above, tick0 >= 0, no unknown flag. Everything new is allocated before
+ * anything old is freed; a failed call keeps the previous monitor. A successful call starts fresh records and rings -- with
+ * LTPL_SIM_SAFETY_KEEP_STATE (and a monitor set) parameters, mask and tick0 change and records and rings stay.
+ * ------------------------------------------------------------------------------------------------------------------------------------------ */
+#define LTPL_FLEET_SIM_SAFETY_DOUBLES 31
+#define LTPL_FLEET_SIM_SAFETY_INCIDENTS 8
+#define LTPL_FLEET_SIM_SAFETY_INCIDENT_DOUBLES 6
+#define LTPL_SIM_SAFETY_KEEP_STATE 1u
+typedef struct {
+    const int32_t* on;               /* [n] 0: the planner is not monitored, 1: it is                  */
+    const double* r_ego;             /* [n] m, >= 0                                                    */
+    const double* ttc_thr;           /* [n] s, > 0                                                     */
+    const double* drac_thr;          /* [n] m/s^2, >= 0                                                */
+    const double* thw_thr;           /* [n] s, >= 0                                                    */
+    const double* margin;            /* [n] m, >= 0: widens the headway corridor                       */
+    int32_t tick0;                   /* >= 0: the monitor's tick of the next fleet tick                */
+    uint32_t flags;                  /* LTPL_SIM_SAFETY_KEEP_STATE                                     */
+} ltpl_fleet_sim_safety_in;
+int ltpl_fleet_sim_safety(ltpl_fleet* fleet, const ltpl_fleet_sim_safety_in* in);
+/* out: [n][LTPL_FLEET_SIM_SAFETY_DOUBLES]; incidents (or NULL): [n][LTPL_FLEET_SIM_SAFETY_INCIDENTS][LTPL_FLEET_SIM_SAFETY_INCIDENT_DOUBLES].
+ * No simulation, the monitor off, a wrong record or incident size: LTPL_ERR_INVALID_ARG. */
+int ltpl_fleet_sim_safety_read(ltpl_fleet* fleet, double* out, int32_t doubles_per_planner, double* incidents, int32_t doubles_per_incident);
+/* the test hook of the rule (k_fleet_sim_safety_eval, one wave per case, the tick's own device function; needs a fleet and no simulation):
+ * case q is one live tick at pose[q][2] with dt[q] > 0, tick[q] >= 0, params[q][5] = r_ego, ttc_thr, drac_thr, thw_thr, margin (checked as
+ * above) and the objects objs[obj_off[q] .. obj_off[q + 1])[5] = x, y, px, py, r (0 .. 96). rec[q][31] and inc[q][8][6]: IN the record and
+ * ring before (prev_x, prev_y, prev_valid decide whether the tick is evaluated), OUT after. per_obj[..][6] = ttc, drac, thw, gap, closing,
+ * flags (1 skipped, 2 overlap, 4 collision course, 8 in corridor); per_tick[q][8] = gap_t, gap_slot, ttc_t, ttc_slot, drac_t, thw_t,
+ * impact_t, closing_t. */
+int ltpl_fleet_sim_safety_eval(ltpl_fleet* fleet, int32_t n_cases, const double* pose, const double* dt, const int32_t* tick, const double* params,
+                               const int32_t* obj_off, const double* objs, double* rec, double* inc, double* per_obj, double* per_tick);
 
 #ifdef __cplusplus
 }

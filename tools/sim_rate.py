@@ -1,7 +1,7 @@
 """Closed-loop SIMULATION rate of a fleet (ltpl_fleet_sim_*): N planners, each with its own eight C2-style race-line opponents (SURVEY.md
 section 8d: s0_k = 250 + 280 k, vel_scale_k = 0.30 + 0.05 (k mod 4), here staggered by 10 m (p mod 16) per planner), run the example
 driver's loop on the device for T ticks without host work per tick.   tools/sim_rate.py [--planners 32768] [--ticks 200] [--no-tape]
-[--race-size K] [--friction-map] [--telemetry] [--record M [--record-depth D]] [--events] [--noise] [--vehicle] [--sensor [keep]] [--tracker] [--predictor [K[:MODE]]] [--selector] [--lib PATH]. Prints planner-ticks per second of sim_run (device time of the run) next to tape_run on the C2 tape (recorded inputs,
+[--race-size K] [--friction-map] [--telemetry] [--record M [--record-depth D]] [--events] [--noise] [--vehicle] [--sensor [keep]] [--tracker] [--predictor [K[:MODE]]] [--selector] [--safety] [--lib PATH]. Prints planner-ticks per second of sim_run (device time of the run) next to tape_run on the C2 tape (recorded inputs,
 tools/fleet_rate.py). --race-size K > 1: races of K consecutive planners (ltpl_fleet_sim_race) that see one another, started 30 m apart
 along the race line with its heading; K = 1 (default) is the run without races. --friction-map: the same fleet on the friction grid of
 tests/golden/friction_grid.npz (ltpl_fleet_friction: rows evaluated on the device, grip factors 1.0 .. 0.7 over the planners) instead of
@@ -34,6 +34,8 @@ per object; 1: straight line): k_fleet_sim_predict in k_fleet_sim_compact's plac
 statistics are printed after the run.
 --selector: every planner behind the behaviour selector (ltpl_fleet_sim_selector, sim.SELECTOR_DEFAULTS) on its four-entry list:
 k_fleet_sim_select at the head of every tick, in front of the step kernel; the statistics are printed after the run.
+--safety: every planner behind the safety monitor (ltpl_fleet_sim_safety, sim.SAFETY_DEFAULTS): k_fleet_sim_safety behind telemetry and
+in front of the sensor in every tick; the first planners' records and the fleet's totals are printed after the run.
 --lib PATH: another build of
 the library (A/B against the parent's)."""
 import argparse
@@ -49,6 +51,7 @@ import planner_replay as pr                                                   # 
 from graphbasedlocaltrajectoryplanner_amd import _capi                        # noqa: E402
 from graphbasedlocaltrajectoryplanner_amd.fleet import Fleet                  # noqa: E402
 from graphbasedlocaltrajectoryplanner_amd.lattice import Lattice              # noqa: E402
+from graphbasedlocaltrajectoryplanner_amd import sim                          # noqa: E402
 from graphbasedlocaltrajectoryplanner_amd.sim import Event, RaceLineTable     # noqa: E402
 
 
@@ -72,6 +75,7 @@ def main():
     ap.add_argument("--predictor", nargs="?", const="4:2", default=None, metavar="K[:MODE]",
                     help="every planner behind the prediction model: K points per object over 2 s, mode 0 / 1 / 2 (default 4:2)")
     ap.add_argument("--selector", action="store_true", help="every planner behind the behaviour selector (sim.SELECTOR_DEFAULTS)")
+    ap.add_argument("--safety", action="store_true", help="every planner behind the safety monitor (sim.SAFETY_DEFAULTS)")
     ap.add_argument("--lib", default=None, help="path of the library to load (default: the in-tree build)")
     a = ap.parse_args()
     lat = Lattice.load(os.path.join(ROOT, "tests", "golden", "monteblanco_lattice.npz"))
@@ -140,6 +144,8 @@ def main():
             fleet.sim_predictor(n_points=int(kp), mode=int(mode or 2), horizon=2.0, relax=0.5)
         if a.selector:
             fleet.sim_selector()
+        if a.safety:
+            fleet.sim_safety()
         t0 = time.perf_counter()
         failed = 0
         try:
@@ -175,6 +181,20 @@ def main():
                   "%d of them coasting, %d withheld, %d overflows, up to %d tracks" % (
                       d["n_det"].sum(), d["n_matched"].sum(), d["n_born"].sum(), d["n_confirmed"].sum(), d["n_del_tentative"].sum(), d["n_del_coast"].sum(),
                       d["n_out"].sum(), d["n_out_coast"].sum(), d["n_withheld"].sum(), d["n_overflow"].sum(), d["tracks_max"].max()))
+        if a.safety:
+            d, ring = fleet.sim_safety_read()
+            print("  safety: %d live ticks, %d evaluated; %d incidents in %d planners, %.1f s under the TTC threshold, %d ticks over the DRAC "
+                  "threshold, %d under the headway threshold, %d overlap ticks, %d objects skipped; smallest gap %.3f m, smallest TTC %.3f s, "
+                  "largest DRAC %.3f m/s^2, largest impact speed %.3f m/s" % (
+                      d["ticks"].sum(), d["ticks_eval"].sum(), d["n_incidents"].sum(), np.sum(d["n_incidents"] > 0), d["tet"].sum(),
+                      d["drac_ticks"].sum(), d["thw_ticks"].sum(), d["overlap_ticks"].sum(), d["n_skipped"].sum(), np.min(d["gap_min"]),
+                      np.min(d["ttc_min"]), np.max(d["drac_max"]), np.max(d["impact_max"])))
+            for p in range(min(3, fleet.n_scen)):
+                print("    planner %d: gap_min %.3f m (tick %d, slot %d), ttc_min %.3f s (tick %d, slot %d), tet %.2f s, tit %.3f s^2, drac_max "
+                      "%.3f, thw_min %.3f s, hist %s, incidents %s" % (
+                          p, d["gap_min"][p], d["gap_tick"][p], d["gap_slot"][p], d["ttc_min"][p], d["ttc_tick"][p], d["ttc_slot"][p], d["tet"][p],
+                          d["tit"][p], d["drac_max"][p], d["thw_min"][p], d["hist"][p].tolist(),
+                          [(int(i["tick_first"]), int(i["tick_last"]), round(i["ttc_min"], 3)) for i in sim.safety_incidents(ring[p], d["n_incidents"][p])]))
         if a.selector:
             d = fleet.sim_selector_read()[0]
             print("  selector: %d evaluations, %d actions scored; %d switches, %d overrides of the list, %d without a safe action, %d emergency; chosen "
