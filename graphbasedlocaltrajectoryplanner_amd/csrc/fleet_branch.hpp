@@ -8,11 +8,15 @@
 //            count and next_id (ltpl_fleet_sim_tracker) where the destination has a tracker, and the staged object list of the last tick
 //            (cnt and the first cnt entries of g_x, g_y, g_px, g_py, g_r) where the destination has a behaviour selector
 //            (ltpl_fleet_sim_selector), which reads that list at the head of the next tick, and the safety monitor's record and incident
-//            ring (ltpl_fleet_sim_safety) where the destination has a monitor: they are what the tick writes;
+//            ring (ltpl_fleet_sim_safety) where the destination has a monitor, and the reactive opponents' effective scales and record
+//            (ltpl_fleet_sim_react) where the destination has a model: they are what the tick writes;
 //   stays    the race line, the opponents' vel_scale / length, statics, zones, preference list, dt, n_export, the velocity arguments,
 //            friction map index and scale, race membership and length as a mate, contact radius, the recorder's ring and indices,
 //            the vehicle model's switch and parameters, the tracker's parameters and statistics, the selector's parameters, ordered
-//            lists and statistics, the safety monitor's parameters, mask and tick index.
+//            lists and statistics, the safety monitor's parameters, mask and tick index, the reactive opponents' parameters and tick index.
+// Reactive opponents, the mixed cases: a destination fleet without a model takes nothing; with one, a destination takes effective scales
+// and record of a source that held them (a live planner while the model is set, a snapshot entry taken with one) -- a source without
+// leaves the destination the start state: the start record and eff = its own configured scales.
 // Safety monitor, the mixed cases: a destination fleet without a monitor takes nothing; with one, a destination takes record and ring of a
 // source that held them (a live planner while the monitor is set, a snapshot entry taken with one) -- a source without leaves the
 // destination the start state (prev_valid 0: its next live tick is not evaluated).
@@ -85,6 +89,31 @@ __global__ __launch_bounds__(64) void k_fleet_sim_branch_safety(SafetyView S, Sa
     }
 }
 static_assert(LTPL_FLEET_SIM_SAFETY_DOUBLES <= 64 && SAF_RING <= 64, "k_fleet_sim_branch_safety: one lane per double");
+
+// the reactive opponents' effective scales and record of entry e (rec null: the source holds none); eff of entry e from opp_off[e] on
+struct ReactView { double* eff; double* rec; const int* opp_off; };
+
+// behind k_fleet_sim_branch, only where the live fleet has a model: one wave64 per pair. `own`: the destination view's configured scales
+// (same offsets as T.eff), what a destination starts from whose source holds no state
+__global__ __launch_bounds__(64) void k_fleet_sim_branch_react(ReactView S, ReactView T, const double* __restrict__ own,
+                                                               const int* __restrict__ src_entry, const int* __restrict__ dst_entry)
+{
+    const int k = blockIdx.x, t = threadIdx.x;
+    const int es = src_entry[k], ed = dst_entry[k];
+    const int to = T.opp_off[ed], no = T.opp_off[ed + 1] - to;       // (equal counts on both sides: the host's check)
+    double* r = T.rec + (size_t)ed * LTPL_FLEET_SIM_REACT_DOUBLES;
+    if (S.rec) {
+        const int so = S.opp_off[es];
+        if (t < LTPL_FLEET_SIM_REACT_DOUBLES) r[t] = S.rec[(size_t)es * LTPL_FLEET_SIM_REACT_DOUBLES + t];
+        for (int q = t; q < no; q += 64) T.eff[to + q] = S.eff[so + q];
+    } else {
+        if (t < LTPL_FLEET_SIM_REACT_DOUBLES)
+            r[t] = t == fleet::RCT_GAP_MIN || t == fleet::RCT_ACC_MIN || t == fleet::RCT_EGO_GAP_MIN ? (double)INFINITY
+                 : t == fleet::RCT_GAP_TICK || t == fleet::RCT_GAP_SLOT || t == fleet::RCT_ACC_TICK || t == fleet::RCT_ACC_SLOT || t == fleet::RCT_EGO_GAP_TICK ? -1.0 : 0.0;
+        for (int q = t; q < no; q += 64) T.eff[to + q] = own[to + q];
+    }
+}
+static_assert(LTPL_FLEET_SIM_REACT_DOUBLES <= 64, "k_fleet_sim_branch_react: one lane per double");
 
 typedef unsigned int branch_u32x4 __attribute__((ext_vector_type(4)));
 #define BRANCH_THREADS 256
@@ -165,6 +194,7 @@ struct SimSnap {
     bool has_trk = false;                   // a tracker part: tables of the planners' capacities, counts and next_id
     StagedView stg{};                       // the staged lists (stg.cnt null: taken without a selector)
     SafetyView saf{};                       // the safety monitor's records and rings (saf.rec null: taken without a monitor)
+    ReactView rct{};                        // the reactive opponents' effective scales and records (rct.rec null: taken without a model)
     uint64_t bytes = 0;
     bool held() const { return !planners.empty(); }
 };
@@ -225,6 +255,26 @@ static int branch_launch_safety(ltpl_fleet* f, SafetyView S, SafetyView T, const
     if (rc) return rc;
     hipStream_t st = f->h->stream;
     hipLaunchKernelGGL(k_fleet_sim_branch_safety, dim3((unsigned)n), dim3(64), 0, st, S, T, (const int*)d_idx, (const int*)d_idx + n);
+    FLEET_TRY(f, hipGetLastError());
+    FLEET_TRY(f, hipStreamSynchronize(st));
+    return LTPL_OK;
+}
+
+// the reactive opponents' effective scales and records of the pairs, behind branch_launch; T: a view with a model's state; `own`: the
+// configured scales on T's offsets (read only where S holds no state)
+static int branch_launch_react(ltpl_fleet* f, ReactView S, ReactView T, const double* own, const std::vector<int>& src_entry,
+                               const std::vector<int>& dst_entry)
+{
+    const int n = (int)src_entry.size();
+    if (n == 0) return LTPL_OK;
+    SimAllocs a;
+    int* d_idx = nullptr;
+    std::vector<int> idx(src_entry);
+    idx.insert(idx.end(), dst_entry.begin(), dst_entry.end());
+    int rc = sim_upload(f, a.p, idx.data(), idx.size(), &d_idx);
+    if (rc) return rc;
+    hipStream_t st = f->h->stream;
+    hipLaunchKernelGGL(k_fleet_sim_branch_react, dim3((unsigned)n), dim3(64), 0, st, S, T, own, (const int*)d_idx, (const int*)d_idx + n);
     FLEET_TRY(f, hipGetLastError());
     FLEET_TRY(f, hipStreamSynchronize(st));
     return LTPL_OK;
@@ -350,12 +400,15 @@ try {
     }
     SafetyView& fv = q->saf;
     if (s.has_saf) { SNAP_TAKE(&fv.rec, M * LTPL_FLEET_SIM_SAFETY_DOUBLES); SNAP_TAKE(&fv.inc, M * SAF_RING); }
+    ReactView& rv = q->rct;
+    if (s.has_react) { SNAP_TAKE(&rv.rec, M * LTPL_FLEET_SIM_REACT_DOUBLES); SNAP_TAKE(&rv.eff, n_opp); rv.opp_off = v.opp_off; }
 #undef SNAP_TAKE
     std::vector<int> dst(M);
     for (size_t k = 0; k < M; ++k) dst[k] = (int)k;
     if ((rc = branch_launch(f, branch_live_view(f), v, q->planners, dst, nullptr))) return rc;
     if (sv.cnt && (rc = branch_launch_staged(f, s.staged_valid ? branch_live_staged(f) : StagedView{}, sv, q->planners, dst))) return rc;
     if (fv.rec && (rc = branch_launch_safety(f, SafetyView{s.sf.rec, s.sf.inc}, fv, q->planners, dst))) return rc;
+    if (rv.rec && (rc = branch_launch_react(f, ReactView{s.rc.eff, s.rc.rec, s.sd.opp_off}, rv, nullptr, q->planners, dst))) return rc;
     q->allocs.swap(a.p);
     q->has_tele = s.has_tele; q->tele_gen = s.tele_gen; q->bytes = bytes;
     if (!s.snaps) s.snaps = new SimSnaps();
@@ -465,6 +518,11 @@ try {
     }
     // the safety monitor's records and rings: what the tick writes
     if (s.has_saf && (rc = branch_launch_safety(f, q ? q->saf : SafetyView{s.sf.rec, s.sf.inc}, SafetyView{s.sf.rec, s.sf.inc}, se, de))) return rc;
+    // the reactive opponents' effective scales and records: what the tick writes
+    if (s.has_react) {
+        const ReactView live{s.rc.eff, s.rc.rec, s.sd.opp_off};
+        if ((rc = branch_launch_react(f, q ? q->rct : live, live, s.sd.opp_scale, se, de))) return rc;
+    }
     f->cur.has_paths = false;           // (as after a run: a per-call calc_vel_profile needs its own calc_paths first)
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))

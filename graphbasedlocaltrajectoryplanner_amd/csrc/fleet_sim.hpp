@@ -48,6 +48,11 @@
 //                        collision, required deceleration, headway, gap and closing speed against the TRUE pose and its displacement
 //                        since the previous live tick; wave reductions, lane 0 updates the planner's 31-double record and its incident
 //                        ring. Registers only; reads what the tick staged and writes nothing another kernel reads
+//   k_fleet_sim_react    (reactive opponents set only: ltpl_fleet_sim_react; the rule: fleet_react.hpp) behind the events kernels and
+//                        k_fleet_sim_select, in front of the step kernel, one wave64 per planner: the ego projected onto the race line
+//                        (rows strided over the wave, sim_wave_min), s, leader speed and length of the opponents staged in LDS, one lane
+//                        per opponent (blocks of 64) with a serial leader scan; the EFFECTIVE vel_scale of every opponent into a buffer of
+//                        the model's own, which the step kernels then get as SimDev::opp_scale; lane 0 updates the 16-double record
 //   k_fleet_sim_rec_paths / k_fleet_sim_rec_vel   (flight recorder on only: ltpl_fleet_sim_record) one wave64 per RECORDED planner: the
 //                        tick's paths behind paths_post, and its head, objects and trajectories behind the last velocity kernel, into
 //                        the planner's record of ring slot tick % depth. The tick then takes the unfused launch sequence
@@ -58,6 +63,7 @@
 
 #include "fleet_noise.hpp"
 #include "fleet_predict.hpp"
+#include "fleet_react.hpp"
 #include "fleet_safety.hpp"
 #include "fleet_select.hpp"
 #include "fleet_sensor.hpp"
@@ -1480,6 +1486,124 @@ __global__ __launch_bounds__(64) void k_fleet_sim_safety_eval(const double* pose
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// reactive opponents (ltpl_fleet_sim_react, include/ltpl_hip.h; the rule: fleet_react.hpp; host mirror: sim.ReactModel): parameters, an
+// EFFECTIVE vel_scale per opponent and a record per planner, which the tick writes (they travel with snapshot / branch, fleet_branch.hpp).
+// While a model is set the step kernels get a SimDev whose opp_scale is `eff`; SimDev::opp_scale stays the configured scale, which the
+// events write. The pointers live in a struct of their own: no other kernel carries them.
+// ---------------------------------------------------------------------------------------------------------------------
+#define RCT_PARAMS LTPL_FLEET_SIM_REACT_PARAMS
+#define RCT_BLOCKS ((SIM_OBJ_CAP + 63) / 64)
+static_assert(fleet::RCT_DOUBLES == LTPL_FLEET_SIM_REACT_DOUBLES && sizeof(fleet::ReactParams) == RCT_PARAMS * sizeof(double) &&
+              fleet::kReactMaxOpp == SIM_OBJ_CAP, "reactive opponents: record layout");
+struct SimReact {
+    const double* par;                     // [N][RCT_PARAMS] in the order of fleet::ReactParams
+    double* eff;                           // the effective scales, in the order of SimDev::opp_s
+    double* rec;                           // [N][LTPL_FLEET_SIM_REACT_DOUBLES]
+    uint32_t tick;                         // tick0 + fleet ticks since the model was set
+};
+struct ReactLds { double s[SIM_OBJ_CAP], u[SIM_OBJ_CAP], len[SIM_OBJ_CAP]; };      // what a leader search reads of every opponent
+
+__device__ __forceinline__ fleet::ReactParams sim_react_params(const double* q)
+{
+    return fleet::ReactParams{q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8]};
+}
+
+// One tick of one planner's `no` opponents by one wave64 (every lane enters). Step 0: the wave strides the table's rows (coalesced loads)
+// and ends in the minimum over (d2, row) -- pred_nearest's first minimum; every lane then projects the ego. One lane per opponent in
+// blocks of 64: s, c, e, length (elements `stride` doubles apart) are read and s, leader speed and length staged in LDS BEFORE anything
+// is written, so e_out may be the array e_in points into; the leader scan of fleet::react_opp is serial in list order. The wave's
+// reductions fold the tick's values and lane 0 applies them to the record. per_opp [no][4] and ego_out [3] (the hook's outputs) or null
+__device__ __forceinline__ void sim_react_wave(int lane, const fleet::ReactParams& P, const fleet::ReactTable& R, double x, double y, double v, double dt,
+                                               double tick, int no, const double* in_s, const double* in_c, const double* in_e, const double* in_len,
+                                               int stride, double* e_out, double* rec, double* per_opp, double* ego_out, ReactLds& L)
+{
+    SimBest b{INFINITY, 0x7fffffff};
+    for (int i = lane; i < R.n; i += 64) {
+        const double d2 = fleet::pred_d2(x, y, R.x[i], R.y[i]);
+        if (d2 < b.d) { b.d = d2; b.i = i; }
+    }
+    b = sim_wave_min(b);
+    const fleet::ReactEgo E = fleet::react_ego(P, R, b.i == 0x7fffffff ? 0 : b.i, x, y, v);
+    double cq[RCT_BLOCKS], eq[RCT_BLOCKS], Vq[RCT_BLOCKS];
+#pragma unroll
+    for (int k = 0; k < RCT_BLOCKS; ++k) {
+        const int q = k * 64 + lane;
+        cq[k] = 0.0; eq[k] = 0.0; Vq[k] = 0.0;
+        if (q < no) {
+            const size_t a = (size_t)q * stride;
+            const double s = in_s[a];
+            cq[k] = in_c[a]; eq[k] = in_e[a]; Vq[k] = fleet::react_vrl(R, s);
+            L.s[q] = s; L.u[q] = fleet::react_speed(cq[k], eq[k], Vq[k]); L.len[q] = in_len[a];
+        }
+    }
+    __syncthreads();
+    fleet::ReactTick T = fleet::react_tick_start();
+#pragma unroll
+    for (int k = 0; k < RCT_BLOCKS; ++k) {
+        const int q = k * 64 + lane;
+        int fl = 0;
+        if (q < no) {
+            const fleet::ReactOpp o = fleet::react_opp(P, R, E, dt, q, no, L.s, L.u, L.len, cq[k], eq[k], Vq[k]);
+            fleet::react_fold(T, o, q);
+            fl = o.flags;
+            e_out[q] = o.e;
+            if (per_opp) { double* w = per_opp + (size_t)4 * q; w[0] = (double)o.leader; w[1] = o.delta; w[2] = o.gap; w[3] = o.acc; }
+        }
+        T.follow += __popcll(__ballot((fl & fleet::kReactFollow) != 0)); T.ego_lead += __popcll(__ballot((fl & fleet::kReactEgoLead) != 0));
+        T.clamped += __popcll(__ballot((fl & fleet::kReactClamped) != 0)); T.overlaps += __popcll(__ballot((fl & fleet::kReactOverlap) != 0));
+        T.passive += __popcll(__ballot((fl & fleet::kReactPassive) != 0));
+    }
+    wave_min2(T.gap, T.gap_slot);
+    wave_min2(T.acc, T.acc_slot);
+    T.ego_gap = wave_min_f64(T.ego_gap);
+    if (lane != 0) return;
+    if (ego_out) { ego_out[0] = E.s; ego_out[1] = E.d; ego_out[2] = E.has ? 1.0 : 0.0; }
+    fleet::react_apply(rec, E, no, tick, T);
+}
+
+// head of a tick, behind the events kernels and k_fleet_sim_select, in front of the step kernel: the effective scales the tick's opponents
+// drive with, from the TRUE pose and speed the previous tick left. A planner whose error word is set returns at once; one with on == 0
+// hands on its configured scales (an event's write still reaches the step) and leaves its record alone
+__global__ __launch_bounds__(64) void k_fleet_sim_react(FleetArgs F, SimDev sd, SimReact rc)
+{
+    const int p = blockIdx.x, lane = threadIdx.x;
+    __shared__ ReactLds L;
+    const fleet::Block B{F.state + F.D.stride * (size_t)p, F.D, nullptr};
+    if (B.S()->err) return;
+    const int o0 = sd.opp_off[p];
+    int no = sd.opp_off[p + 1] - o0;
+    if (no > SIM_OBJ_CAP) no = SIM_OBJ_CAP;            // (refused by the host)
+    const double* par = rc.par + (size_t)p * RCT_PARAMS;
+    if (par[0] == 0.0) {
+        for (int q = lane; q < no; q += 64) rc.eff[o0 + q] = sd.opp_scale[o0 + q];
+        return;
+    }
+    const size_t n = (size_t)sd.n_rl;
+    const fleet::ReactTable R{sd.race, sd.race + n, sd.race + 2 * n, sd.race + 4 * n, sd.n_rl};
+    sim_react_wave(lane, sim_react_params(par), R, sd.pos_x[p], sd.pos_y[p], sd.vel[p], sd.dt, (double)rc.tick, no, sd.opp_s + o0, sd.opp_scale + o0,
+                   rc.eff + o0, sd.opp_len + o0, 1, rc.eff + o0, rc.rec + (size_t)p * LTPL_FLEET_SIM_REACT_DOUBLES, nullptr, nullptr, L);
+}
+
+// the test hook of the rule: one wave per case on the fleet's race table, the tick's own device function. par[q][9], ego[q][3] = x, y, v,
+// dt[q], tick[q], opp[opp_off[q] ..][4] = s, c, e, length; rec[q][16] in and out; e_out[..], per_opp[..][4], ego_out[q][3] out
+__global__ __launch_bounds__(64) void k_fleet_sim_react_eval(SimDev sd, const double* par, const double* ego, const double* dt, const int* tick,
+                                                             const int* opp_off, const double* opp, double* rec, double* e_out, double* per_opp,
+                                                             double* ego_out)
+{
+    const int q = blockIdx.x, lane = threadIdx.x;
+    __shared__ ReactLds L;
+    const int o0 = opp_off[q];
+    int no = opp_off[q + 1] - o0;
+    if (no > SIM_OBJ_CAP) no = SIM_OBJ_CAP;            // (refused by the host)
+    if (no < 0) no = 0;
+    const size_t n = (size_t)sd.n_rl;
+    const fleet::ReactTable R{sd.race, sd.race + n, sd.race + 2 * n, sd.race + 4 * n, sd.n_rl};
+    const double* o = opp + (size_t)o0 * 4;
+    sim_react_wave(lane, sim_react_params(par + (size_t)q * RCT_PARAMS), R, ego[3 * q], ego[3 * q + 1], ego[3 * q + 2], dt[q], (double)tick[q], no, o,
+                   o + 1, o + 2, o + 3, 4, e_out + o0, rec + (size_t)q * LTPL_FLEET_SIM_REACT_DOUBLES, per_opp + (size_t)o0 * 4, ego_out + (size_t)3 * q, L);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
 struct SimSnaps;                            // snapshot slots (fleet_branch.hpp, ltpl_fleet_sim_snapshot)
@@ -1550,6 +1674,10 @@ struct FleetSim {
     SimSafety sf{};
     bool has_saf = false;                   // the tick launches k_fleet_sim_safety behind telemetry, in front of the sensor
     int saf_tick0 = 0, saf_tick = 0;        // tick0; ticks of ltpl_fleet_sim_run since the monitor was set
+    std::vector<void*> react_allocs;        // parameters, effective scales and records of ltpl_fleet_sim_react
+    SimReact rc{};
+    bool has_react = false;                 // the tick launches k_fleet_sim_react in front of the step kernel, which reads rc.eff as opp_scale
+    int react_tick0 = 0, react_tick = 0;    // tick0; ticks of ltpl_fleet_sim_run since the model was set
 };
 static void sim_free_list(std::vector<void*>& l)
 {
@@ -1568,7 +1696,7 @@ static void fleet_sim_free(FleetSim* s)
     sim_events_free(s->events);
     sim_free_list(s->stage_allocs); sim_free_list(s->race_allocs); sim_free_list(s->tele_allocs); sim_free_list(s->rec_allocs);
     sim_free_list(s->noise_allocs); sim_free_list(s->veh_allocs); sim_free_list(s->sens_allocs); sim_free_list(s->trk_allocs);
-    sim_free_list(s->pred_allocs); sim_free_list(s->sel_allocs); sim_free_list(s->saf_allocs);
+    sim_free_list(s->pred_allocs); sim_free_list(s->sel_allocs); sim_free_list(s->saf_allocs); sim_free_list(s->react_allocs);
     for (void* p : s->allocs) (void)hipFree(p);
     if (s->velt.d_buf) (void)hipFree(s->velt.d_buf);
     delete s;
@@ -1818,11 +1946,18 @@ try {
     s.staged_valid = true;
     SimDev sds = s.sd;                      // what the step and mates kernels get: the selector's ordered lists in the user's place
     if (s.has_sel) sds.pref = s.sl.ord;
+    if (s.has_react) sds.opp_scale = s.rc.eff;       // ... and the reactive opponents' effective scales in the configured ones' place
     for (int k = 0; k < n_ticks; ++k) {
         double* tr = d_trace ? d_trace + rec * (size_t)k : nullptr;
         if (s.events && (rc = sim_events_tick(f, &t))) return rc;
         if (s.has_sel) {
             hipLaunchKernelGGL(k_fleet_sim_select, dim3(N), dim3(64), 0, st, f->args, s.sd, s.sl);
+            FLEET_TRY(f, hipGetLastError());
+        }
+        if (s.has_react) {
+            // (the tick advances whether or not a planner is live, like the safety monitor's)
+            s.rc.tick = (uint32_t)s.react_tick0 + (uint32_t)s.react_tick++;
+            hipLaunchKernelGGL(k_fleet_sim_react, dim3(N), dim3(64), 0, st, f->args, s.sd, s.rc);
             FLEET_TRY(f, hipGetLastError());
         }
         if (s.has_noise) {
@@ -3192,6 +3327,161 @@ try {
     FLEET_TRY(f, hipMemcpyAsync(inc, d + o_inc, 8 * RI * m, hipMemcpyDeviceToHost, st));
     FLEET_TRY(f, hipMemcpyAsync(per_tick, d + o_pt, 64 * m, hipMemcpyDeviceToHost, st));
     if (no) FLEET_TRY(f, hipMemcpyAsync(per_obj, d + o_po, 48 * no, hipMemcpyDeviceToHost, st));
+    FLEET_TRY(f, hipStreamSynchronize(st));
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+// ---------------------------------------------------------------------------------------------------------------------
+// reactive opponents (ltpl_fleet_sim_react, include/ltpl_hip.h; the rule: fleet_react.hpp)
+// ---------------------------------------------------------------------------------------------------------------------
+static const char* const kReactParamName[RCT_PARAMS] = {"on", "a_max", "b_comf", "b_max", "headway", "gap0", "look", "lat_gate", "ego_len"};
+
+// q[RCT_PARAMS] in the order of fleet::ReactParams
+static bool sim_react_params_ok(const double* q, std::string* why)
+{
+    if (q[0] != 0.0 && q[0] != 1.0) { *why = "on must be 0 or 1"; return false; }
+    for (int c = 1; c < RCT_PARAMS; ++c) {
+        const bool positive = c <= 3 || c == 6;              // a_max, b_comf, b_max, look
+        if (std::isnan(q[c]) || (std::isinf(q[c]) && !(c == 6 && q[c] > 0.0))) { *why = std::string(kReactParamName[c]) + " must be finite"; return false; }
+        if (positive ? !(q[c] > 0.0) : !(q[c] >= 0.0)) { *why = std::string(kReactParamName[c]) + (positive ? " must be positive" : " must not be negative"); return false; }
+    }
+    return true;
+}
+
+// every argument is checked before the first HIP call; *any_on: some planner has on == 1
+static int sim_check_react(ltpl_fleet* f, const ltpl_fleet_sim_react_in* in, std::vector<double>* par, bool* any_on)
+{
+    const int N = f->D.N;
+    auto bad = [&](const std::string& why) { f->err = "fleet sim react: " + why; return LTPL_ERR_INVALID_ARG; };
+    *any_on = false;
+    if (!f->sim) return bad("ltpl_fleet_sim_setup first");
+    if (!in) return LTPL_OK;
+    const double* a[RCT_PARAMS] = {nullptr, in->a_max, in->b_comf, in->b_max, in->headway, in->gap0, in->look, in->lat_gate, in->ego_len};
+    if (!in->on) return bad("on missing");
+    for (int c = 1; c < RCT_PARAMS; ++c) if (!a[c]) return bad(std::string(kReactParamName[c]) + " missing");
+    if (in->tick0 < 0) return bad("tick0 must not be negative");
+    if (in->flags & ~(uint32_t)LTPL_SIM_REACT_KEEP_STATE) return bad("unknown flag");
+    par->resize((size_t)N * RCT_PARAMS);
+    for (int p = 0; p < N; ++p) {
+        double* q = &(*par)[(size_t)p * RCT_PARAMS];
+        q[0] = (double)in->on[p];
+        for (int c = 1; c < RCT_PARAMS; ++c) q[c] = a[c][p];
+        std::string why;
+        if (!sim_react_params_ok(q, &why)) return bad("planner " + std::to_string(p) + ": " + why);
+        *any_on = *any_on || in->on[p] == 1;
+    }
+    return LTPL_OK;
+}
+
+extern "C" int ltpl_fleet_sim_react(ltpl_fleet* f, const ltpl_fleet_sim_react_in* in)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    std::vector<double> par;
+    bool any_on = false;
+    int rc = sim_check_react(f, in, &par, &any_on);
+    if (rc) return rc;
+    if ((rc = fleet_enter(f))) return rc;
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    FleetSim& s = *f->sim;
+    if (!in || !any_on) {
+        sim_free_list(s.react_allocs);
+        s.rc = SimReact{}; s.has_react = false; s.react_tick0 = s.react_tick = 0;
+        return LTPL_OK;
+    }
+    const size_t N = (size_t)f->D.N, no = (size_t)s.n_opp;
+    constexpr size_t RD = LTPL_FLEET_SIM_REACT_DOUBLES;
+    const bool keep = (in->flags & LTPL_SIM_REACT_KEEP_STATE) && s.has_react;
+    std::vector<double> rec(N * RD), eff(no ? no : 1);
+    if (keep) {
+        FLEET_TRY(f, hipMemcpy(rec.data(), s.rc.rec, 8 * N * RD, hipMemcpyDeviceToHost));
+        if (no) FLEET_TRY(f, hipMemcpy(eff.data(), s.rc.eff, 8 * no, hipMemcpyDeviceToHost));
+    } else {
+        for (size_t p = 0; p < N; ++p) fleet::react_start(rec.data() + p * RD);
+        if (no) FLEET_TRY(f, hipMemcpy(eff.data(), s.sd.opp_scale, 8 * no, hipMemcpyDeviceToHost));      // the start state: e = the configured c
+    }
+    // everything new is allocated first; the fleet keeps its previous model, its tick count, scales and records unless every step succeeds
+    SimAllocs al;
+    SimReact r{};
+    double* d_par = nullptr;
+    if ((rc = sim_upload(f, al.p, par.data(), par.size(), &d_par))) return rc;
+    if ((rc = sim_upload(f, al.p, eff.data(), no, &r.eff))) return rc;
+    if ((rc = sim_upload(f, al.p, rec.data(), rec.size(), &r.rec))) return rc;
+    r.par = d_par;
+    sim_free_list(s.react_allocs);
+    s.react_allocs.swap(al.p);
+    s.rc = r; s.has_react = true; s.react_tick0 = in->tick0; s.react_tick = 0;
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+extern "C" int ltpl_fleet_sim_react_read(ltpl_fleet* f, double* out, int32_t doubles_per_planner, double* eff_scale)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    auto bad = [&](const std::string& why) { f->err = "fleet sim react: " + why; return LTPL_ERR_INVALID_ARG; };
+    if (!f->sim) return bad("ltpl_fleet_sim_setup first");
+    if (!f->sim->has_react) return bad("the model is off (ltpl_fleet_sim_react first)");
+    if (!out) return bad("out missing");
+    if (doubles_per_planner != LTPL_FLEET_SIM_REACT_DOUBLES) return bad("record size mismatch");
+    const size_t N = (size_t)f->D.N, no = (size_t)f->sim->n_opp;
+    FLEET_TRY(f, hipSetDevice(f->h->device));
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    FLEET_TRY(f, hipMemcpy(out, f->sim->rc.rec, sizeof(double) * N * LTPL_FLEET_SIM_REACT_DOUBLES, hipMemcpyDeviceToHost));
+    if (eff_scale && no) FLEET_TRY(f, hipMemcpy(eff_scale, f->sim->rc.eff, sizeof(double) * no, hipMemcpyDeviceToHost));
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+extern "C" int ltpl_fleet_sim_react_eval(ltpl_fleet* f, int32_t n_cases, const double* params, const double* ego, const double* dt, const int32_t* tick,
+                                         const int32_t* opp_off, const double* opp, double* rec, double* e_out, double* per_opp, double* ego_out)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    auto bad = [&](const std::string& why) { f->err = "fleet sim react eval: " + why; return LTPL_ERR_INVALID_ARG; };
+    if (!f->sim) return bad("ltpl_fleet_sim_setup first (the race table)");
+    if (n_cases < 0) return bad("n_cases must not be negative");
+    if (n_cases == 0) return LTPL_OK;
+    if (!params || !ego || !dt || !tick || !opp_off || !rec || !ego_out) return bad("an array is missing");
+    if (opp_off[0] != 0) return bad("opponent offsets must start at 0");
+    for (int q = 0; q < n_cases; ++q) {
+        const std::string who = "case " + std::to_string(q) + ": ";
+        const int n = opp_off[q + 1] - opp_off[q];
+        if (n < 0 || n > SIM_OBJ_CAP) return bad(who + "0 .. 96 opponents");
+        std::string why;
+        if (!sim_react_params_ok(params + (size_t)q * RCT_PARAMS, &why)) return bad(who + why);
+        if (!std::isfinite(dt[q]) || !(dt[q] > 0.0)) return bad(who + "dt must be finite and positive");
+        if (tick[q] < 0) return bad(who + "tick must not be negative");
+    }
+    const size_t m = (size_t)n_cases, no = (size_t)opp_off[n_cases];
+    if (no > 0 && (!opp || !e_out || !per_opp)) return bad("opp / e_out / per_opp missing");
+    for (size_t i = 0; i < 4 * no; ++i) if (!std::isfinite(opp[i])) return bad("opponent " + std::to_string(i / 4) + ": s, c, e and length must be finite");
+    constexpr size_t RD = LTPL_FLEET_SIM_REACT_DOUBLES;
+    int rc = fleet_enter(f);
+    if (rc) return rc;
+    Arena ar;     // one device block
+    const size_t n1 = no ? no : 1;
+    const size_t o_par = ar.add(8 * RCT_PARAMS * m), o_ego = ar.add(24 * m), o_dt = ar.add(8 * m), o_opp = ar.add(32 * n1), o_rec = ar.add(8 * RD * m),
+                 o_e = ar.add(8 * n1), o_po = ar.add(32 * n1), o_eo = ar.add(24 * m), o_tick = ar.add(4 * m), o_off = ar.add(4 * (m + 1));
+    unsigned char* d = nullptr;
+    struct Guard { void* a = nullptr; ~Guard() { if (a) (void)hipFree(a); } } gd;
+    FLEET_TRY(f, hipMalloc(reinterpret_cast<void**>(&d), ar.size)); gd.a = d;
+    FLEET_TRY(f, hipMemset(d, 0, ar.size));
+    FLEET_TRY(f, hipMemcpy(d + o_par, params, 8 * RCT_PARAMS * m, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_ego, ego, 24 * m, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_dt, dt, 8 * m, hipMemcpyHostToDevice));
+    if (no) FLEET_TRY(f, hipMemcpy(d + o_opp, opp, 32 * no, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_rec, rec, 8 * RD * m, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_tick, tick, 4 * m, hipMemcpyHostToDevice));
+    FLEET_TRY(f, hipMemcpy(d + o_off, opp_off, 4 * (m + 1), hipMemcpyHostToDevice));
+    hipStream_t st = f->h->stream;
+    FLEET_TRY(f, hipStreamSynchronize(st));
+    hipLaunchKernelGGL(k_fleet_sim_react_eval, dim3((unsigned)m), dim3(64), 0, st, f->sim->sd, (const double*)(d + o_par), (const double*)(d + o_ego),
+                       (const double*)(d + o_dt), (const int*)(d + o_tick), (const int*)(d + o_off), (const double*)(d + o_opp),
+                       reinterpret_cast<double*>(d + o_rec), reinterpret_cast<double*>(d + o_e), reinterpret_cast<double*>(d + o_po),
+                       reinterpret_cast<double*>(d + o_eo));
+    FLEET_TRY(f, hipGetLastError());
+    FLEET_TRY(f, hipMemcpyAsync(rec, d + o_rec, 8 * RD * m, hipMemcpyDeviceToHost, st));
+    FLEET_TRY(f, hipMemcpyAsync(ego_out, d + o_eo, 24 * m, hipMemcpyDeviceToHost, st));
+    if (no) {
+        FLEET_TRY(f, hipMemcpyAsync(e_out, d + o_e, 8 * no, hipMemcpyDeviceToHost, st));
+        FLEET_TRY(f, hipMemcpyAsync(per_opp, d + o_po, 32 * no, hipMemcpyDeviceToHost, st));
+    }
     FLEET_TRY(f, hipStreamSynchronize(st));
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))

@@ -22,6 +22,7 @@ from .sim import PREDICTOR_DEFAULTS, PREDICTOR_DOUBLES, PREDICTOR_FIELDS, PREDIC
 from .sim import SELECTOR_DEFAULTS, SELECTOR_DOUBLES, SELECTOR_FIELDS, SELECTOR_MAX_ROWS, SELECTOR_PARAMS, selector_dict      # noqa: F401
 from .sim import (INCIDENT_DOUBLES, INCIDENT_FIELDS, SAFETY_DEFAULTS, SAFETY_DOUBLES, SAFETY_FIELDS, SAFETY_INCIDENTS, SAFETY_KEEP_STATE,      # noqa: F401
                   SAFETY_PARAMS, safety_dict, safety_start)
+from .sim import REACT_DEFAULTS, REACT_DOUBLES, REACT_FIELDS, REACT_KEEP_STATE, REACT_MAX_OPP, REACT_PARAMS, react_dict, react_start      # noqa: F401
 from .sim import pack_events as sim_pack_events
 
 
@@ -82,6 +83,10 @@ class SimSelectorIn(C.Structure):          # ltpl_fleet_sim_selector_in
 
 class SimSafetyIn(C.Structure):            # ltpl_fleet_sim_safety_in
     _fields_ = [("on", C.c_void_p)] + [(k, C.c_void_p) for k in SAFETY_PARAMS] + [("tick0", C.c_int32), ("flags", C.c_uint32)]
+
+
+class SimReactIn(C.Structure):             # ltpl_fleet_sim_react_in
+    _fields_ = [("on", C.c_void_p)] + [(k, C.c_void_p) for k in REACT_PARAMS[1:]] + [("tick0", C.c_int32), ("flags", C.c_uint32)]
 
 
 class SimRecordHead(C.Structure):         # ltpl_fleet_sim_record_head
@@ -162,6 +167,10 @@ class Fleet(Planner):
             f("sim_safety").argtypes = [C.c_void_p, C.POINTER(SimSafetyIn)]
             f("sim_safety_read").argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
             f("sim_safety_eval").argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 10
+        if hasattr(self.lib, "ltpl_fleet_sim_react"):
+            f("sim_react").argtypes = [C.c_void_p, C.POINTER(SimReactIn)]
+            f("sim_react_read").argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+            f("sim_react_eval").argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 10
         if hasattr(self.lib, "ltpl_fleet_friction"):
             f("friction").argtypes = [C.c_void_p, C.POINTER(FrictionIn)]
             f("friction_scale").argtypes = [C.c_void_p, C.c_void_p]
@@ -1033,6 +1042,66 @@ class Fleet(Planner):
                                                 off.ctypes.data, flat.ctypes.data, rec.ctypes.data, inc.ctypes.data, per_obj.ctypes.data,
                                                 per_tick.ctypes.data))
         return rec[:m], inc[:m], [per_obj[off[q]:off[q + 1]].copy() for q in range(m)], per_tick[:m]
+
+    # ---- reactive opponents on the device ----------------------------------------------------------------------------------------------
+    def sim_react(self, on=True, tick0=0, keep_state=False, **params):
+        """Opponents that react to the car ahead (ltpl_fleet_sim_react; after ``sim_setup``, between runs at any time): at the head of
+        every tick each race-line opponent gets an EFFECTIVE vel_scale in [0, its configured one] from the car ahead of it on the race
+        line -- another opponent of the planner or the ego (its TRUE pose and speed, within ``lat_gate`` of the line) -- by the
+        car-following rule of csrc/fleet_react.hpp, and the tick integrates the race-line speed times that scale. Parameters
+        (``sim.REACT_PARAMS`` without ``on``, defaults ``sim.REACT_DEFAULTS``) and ``on``: scalars or one per planner; ``tick0``: the
+        model's tick of the next fleet tick. A call starts from the configured scales and fresh records; ``keep_state=True`` changes
+        parameters and tick0 and keeps scales and records. ``on=None`` (or 0 for every planner) switches the model off. A field whose
+        opponents never find a leader drives the run without the model bit for bit. Host mirror: ``sim.ReactModel``."""
+        if on is None:
+            self._check(self._fn("sim_react")(self.handle, None))
+            return
+        names = REACT_PARAMS[1:]
+        unknown = set(params) - set(names)
+        if unknown:
+            raise ValueError("sim_react: unknown parameter %s" % sorted(unknown))
+        n = self.n_scen
+        si = SimReactIn()
+        val = dict(REACT_DEFAULTS, **params)
+        keep = [np.ascontiguousarray(np.broadcast_to(np.asarray(on), (n,)).astype(np.int32))]
+        si.on = keep[0].ctypes.data
+        for name in names:
+            keep.append(np.ascontiguousarray(np.broadcast_to(np.asarray(val[name], np.float64), (n,))))
+            setattr(si, name, keep[-1].ctypes.data)
+        si.tick0, si.flags = int(tick0), REACT_KEEP_STATE if keep_state else 0
+        self._check(self._fn("sim_react")(self.handle, C.byref(si)))
+
+    def sim_react_read(self, raw=False):
+        """(records, eff_scale): the dict of named arrays (``sim.REACT_FIELDS``; ``raw=True``: the [n, 16] records) and the effective
+        scales of all opponents in the order of ``sim_state()['opp_s']`` (ltpl_fleet_sim_react_read)."""
+        no = getattr(self, "_sim_opp", 0)
+        out = np.zeros((self.n_scen, REACT_DOUBLES), np.float64)
+        eff = np.zeros(max(no, 1), np.float64)
+        self._check(self._fn("sim_react_read")(self.handle, out.ctypes.data, REACT_DOUBLES, eff.ctypes.data))
+        return (out if raw else react_dict(out)), eff[:no]
+
+    def sim_react_eval(self, params, ego, dt, tick, opp, rec=None):
+        """The rule's test hook (ltpl_fleet_sim_react_eval; needs ``sim_setup``, for the race table): independent cases on the device,
+        one wave and one tick each. ``params`` [m, 9] in the order of ``sim.REACT_PARAMS``, ``ego`` [m, 3] = x, y, v, ``dt`` [m],
+        ``tick`` [m]; per case ``opp`` [n_q, 4] = s, c, e, length (0 .. 96); ``rec`` [m, 16]: the records before (default: the start
+        state). Returns (records after, e_new: a list of [n_q], per_opp: a list of [n_q, 4] = leader, delta, gap, acc, ego_out [m, 3] =
+        s_e, d_e, has); equals ``sim.react_tick`` bit for bit."""
+        opp = [np.asarray(o, np.float64).reshape(-1, 4) for o in opp]
+        m = len(opp)
+        k = max(m, 1)
+        params = np.ascontiguousarray(np.broadcast_to(np.asarray(params, np.float64), (m, len(REACT_PARAMS))), np.float64)
+        ego = np.ascontiguousarray(np.broadcast_to(np.asarray(ego, np.float64), (m, 3)), np.float64)
+        dt = np.ascontiguousarray(np.broadcast_to(np.asarray(dt, np.float64), (m,)), np.float64)
+        tick = np.ascontiguousarray(np.broadcast_to(np.asarray(tick), (m,)).astype(np.int32))
+        off = np.ascontiguousarray(np.concatenate(([0], np.cumsum([o.shape[0] for o in opp]))).astype(np.int32))
+        flat = np.ascontiguousarray(np.concatenate(opp + [np.zeros((1, 4))]))
+        rec = react_start(k) if rec is None else np.ascontiguousarray(np.asarray(rec, np.float64).reshape(k, REACT_DOUBLES).copy())
+        e_out, per_opp, ego_out = np.zeros(flat.shape[0]), np.zeros((flat.shape[0], 4)), np.zeros((k, 3))
+        self._check(self._fn("sim_react_eval")(self.handle, m, params.ctypes.data, ego.ctypes.data, dt.ctypes.data, tick.ctypes.data,
+                                               off.ctypes.data, flat.ctypes.data, rec.ctypes.data, e_out.ctypes.data, per_opp.ctypes.data,
+                                               ego_out.ctypes.data))
+        return (rec[:m], [e_out[off[q]:off[q + 1]].copy() for q in range(m)], [per_opp[off[q]:off[q + 1]].copy() for q in range(m)],
+                ego_out[:m])
 
     # ---- friction maps on the device ------------------------------------------------------------------------------------------------
     def friction(self, maps, map_idx=None, scale=1.0):

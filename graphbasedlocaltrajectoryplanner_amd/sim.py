@@ -1666,3 +1666,201 @@ class SafetyModel(object):
 
     def as_dict(self):
         return safety_dict(self.rec)
+
+
+# ---- reactive opponents (ltpl_fleet_sim_react, include/ltpl_hip.h; csrc/fleet_react.hpp) -----------------------------------------------------
+# name, index, integer valued: the record of ltpl_fleet_sim_react_read (LTPL_FLEET_SIM_REACT_DOUBLES = 16 per planner)
+REACT_FIELDS = (("ticks", 0, True), ("opp_ticks", 1, True), ("follow_ticks", 2, True), ("ego_lead_ticks", 3, True), ("clamped", 4, True),
+                ("overlaps", 5, True), ("passive", 6, True), ("gap_min", 7, False), ("gap_tick", 8, True), ("gap_slot", 9, True),
+                ("acc_min", 10, False), ("acc_tick", 11, True), ("acc_slot", 12, True), ("ego_gap_min", 13, False), ("ego_gap_tick", 14, True),
+                ("ego_outside", 15, True))
+REACT_DOUBLES = 16
+REACT_PARAMS = ("on", "a_max", "b_comf", "b_max", "headway", "gap0", "look", "lat_gate", "ego_len")
+# a race car's order of magnitude (DESIGN section 4.5c, reactive opponents): 3 m/s^2 to get back to the configured speed, 4 m/s^2 of
+# comfortable and 9 m/s^2 of hardest braking, 1 s of headway on 2 m at standstill, 150 m of sight, the ego within 2 m of the race line, 5 m long
+REACT_DEFAULTS = dict(a_max=3.0, b_comf=4.0, b_max=9.0, headway=1.0, gap0=2.0, look=150.0, lat_gate=2.0, ego_len=5.0)
+REACT_KEEP_STATE = 1                      # LTPL_SIM_REACT_KEEP_STATE
+REACT_MAX_OPP = 96
+REACT_NONE, REACT_EGO = -2, -1            # `leader` of an opponent: none, the ego, else the opponent's index
+
+
+def react_dict(rows):
+    """[n, 16] records as a dict of named arrays (counters, ticks and slots as int64)."""
+    rows = np.asarray(rows, np.float64).reshape(-1, REACT_DOUBLES)
+    return {name: (rows[:, i].astype(np.int64) if is_int else rows[:, i].copy()) for name, i, is_int in REACT_FIELDS}
+
+
+def react_start(n=1):
+    """Records [n, 16] in the start state: zeros, +inf in the minima, -1 in their ticks and slots."""
+    rec = np.zeros((int(n), REACT_DOUBLES))
+    rec[:, [7, 10, 13]] = np.inf
+    rec[:, [8, 9, 11, 12, 14]] = -1.0
+    return rec
+
+
+def react_tick(par, proj, x, y, v, dt, tick, opp, rec):
+    """One tick of the rule of csrc/fleet_react.hpp for one planner (the test hook's case). ``par``: the nine values of ``REACT_PARAMS``
+    (``on`` is not read here); ``proj``: a ``PredictorModel`` on the race table (its nearest row, candidate segment and interpolation are
+    the rule's), with the table's speed column as ``proj.vrl``; ``x, y, v``: the ego's TRUE pose and speed; ``opp`` [n, 4] = s, c, e,
+    length; ``rec`` [16] is updated in place. Returns (e_new [n], per_opp [n, 4] = leader, delta, gap, acc, ego (s_e, d_e, has))."""
+    _, a_max, b_comf, b_max, headway, gap0, look, lat_gate, ego_len = (float(t) for t in par)
+    x, y, v, dt, tick = float(x), float(y), float(v), float(dt), float(tick)
+    opp = np.asarray(opp, np.float64).reshape(-1, 4)
+    n = opp.shape[0]
+    # step 0
+    istar = proj.nearest(x, y)
+    a, c = -1, None
+    if istar >= 1:
+        c = proj._candidate(istar - 1, x, y)
+        if c is not None:
+            a = istar - 1
+    if istar + 1 < proj.rows:
+        hi = proj._candidate(istar, x, y)
+        if hi is not None and (a < 0 or hi[1] < c[1]):
+            a, c = istar, hi
+    has, lead, s_e, d_e = a >= 0, False, 0.0, 0.0
+    if has:
+        t, _, ex, ey, l2 = c
+        s_e = proj.s[a] + t * (proj.s[a + 1] - proj.s[a])
+        d_e = (ex * (y - proj.y[a]) - ey * (x - proj.x[a])) / math.sqrt(l2)
+        lead = (-d_e if d_e < 0.0 else d_e) <= lat_gate
+    L = proj.s[-1]
+    s, cs, es, ln = ([float(t) for t in opp[:, k]] for k in range(4))
+    V = [proj._interp(s[q], proj.vrl, proj._segment(s[q])) for q in range(n)]
+    passive = [not cs[q] > 0.0 or not V[q] > 0.0 for q in range(n)]
+    u = [(cs[q] if passive[q] else es[q]) * V[q] for q in range(n)]
+    e_new, per_opp = np.zeros(n), np.zeros((n, 4))
+    gap_t, gap_slot, acc_t, acc_slot, ego_gap_t = _INF, -1, _INF, -1, _INF
+    follow = ego_lead = clamped = overlaps = n_passive = 0
+    for q in range(n):
+        if passive[q]:
+            n_passive += 1
+            e_new[q], per_opp[q] = cs[q], (REACT_NONE, _INF, _INF, 0.0)
+            continue
+        v_q = es[q] * V[q]
+        best, leader, ul, ll = _INF, REACT_NONE, 0.0, 0.0
+        if lead:
+            D = s_e - s[q]
+            if D < 0.0:
+                D = D + L
+            if D < best:
+                best, leader, ul, ll = D, REACT_EGO, v, ego_len
+        for r in range(n):
+            if r == q:
+                continue
+            D = s[r] - s[q]
+            if D < 0.0:
+                D = D + L
+            if D == 0.0 and r > q:
+                D = L
+            if D < best:
+                best, leader, ul, ll = D, r, u[r], ln[r]
+        if leader != REACT_NONE and not best <= look:
+            leader = REACT_NONE
+        r = es[q] / cs[q]
+        free = 1.0 - (r * r) * (r * r)
+        delta, gap = _INF, _INF
+        if leader == REACT_NONE:
+            acc = a_max * free
+        else:
+            delta = best
+            gap = (best - 0.5 * ll) - 0.5 * ln[q]
+            follow += 1
+            ego_lead += leader == REACT_EGO
+            if not gap > 0.0:
+                acc = -b_max
+                overlaps += 1
+            else:
+                dv = v_q - ul
+                z = v_q * headway + (v_q * dv) / (2.0 * math.sqrt(a_max * b_comf))
+                if not z > 0.0:
+                    z = 0.0
+                k = (gap0 + z) / gap
+                acc = a_max * (free - k * k)
+        if acc < -b_max:
+            acc = -b_max
+            clamped += 1
+        if acc > a_max:
+            acc = a_max
+        e = es[q] + (acc * dt) / V[q]
+        if not e > 0.0:
+            e = 0.0
+        if e > cs[q]:
+            e = cs[q]
+        e_new[q], per_opp[q] = e, (leader, delta, gap, acc)
+        if acc < acc_t:
+            acc_t, acc_slot = acc, q
+        if leader != REACT_NONE:
+            if gap < gap_t or (gap == gap_t and gap_slot < 0):
+                gap_t, gap_slot = gap, q
+            if leader == REACT_EGO and gap < ego_gap_t:
+                ego_gap_t = gap
+    rec[0] += 1.0
+    rec[1] += float(n)
+    rec[2] += float(follow)
+    rec[3] += float(ego_lead)
+    rec[4] += float(clamped)
+    rec[5] += float(overlaps)
+    rec[6] += float(n_passive)
+    if gap_t < rec[7]:
+        rec[7], rec[8], rec[9] = gap_t, tick, float(gap_slot)
+    if acc_t < rec[10]:
+        rec[10], rec[11], rec[12] = acc_t, tick, float(acc_slot)
+    if ego_gap_t < rec[13]:
+        rec[13], rec[14] = ego_gap_t, tick
+    if has and not lead:
+        rec[15] += 1.0
+    return e_new, per_opp, (s_e, d_e, 1.0 if has else 0.0)
+
+
+def react_projector(table):
+    """The race table in the form ``react_tick`` reads: a ``PredictorModel`` (nearest row, candidate segment, interpolation) with the
+    speed column ``vrl``."""
+    proj = PredictorModel(1, table)
+    proj.vrl = np.asarray(table.vel_rl, np.float64).tolist()
+    return proj
+
+
+class ReactModel(object):
+    """Scalar host mirror of the reactive opponents in the operation order of csrc/fleet_react.hpp: plain Python floats, + - * / sqrt and
+    comparisons, so the device's bits. ``table``: the ``RaceLineTable``; ``scales``: per planner the CONFIGURED vel_scale of its
+    opponents (the start value of the effective scale ``eff[p]``); ``on`` and the parameters of ``REACT_PARAMS``: scalars or one per
+    planner; ``tick0``: the model's tick of the next fleet tick. One fleet tick, at its head: ``step(p, pose, vel, opp_s, scales, lengths,
+    dt)`` for every planner without an error word (pose, vel: the TRUE ones of the previous tick; scales: the configured ones as the
+    events left them) returns and stores the effective scales the tick's opponents drive with, then ``advance()`` -- the tick index
+    advances whether or not a planner is live. A planner with ``on`` 0 gets its configured scales."""
+
+    def __init__(self, n, table, scales, on=True, tick0=0, **params):
+        self.n = int(n)
+        self.proj = react_projector(table)
+        self.eff = [np.array(c, np.float64).reshape(-1) for c in scales]
+        self.rec = react_start(self.n)
+        self.configure(on, tick0, **params)
+        self.last = [None] * self.n       # (per_opp, ego) of every planner's latest tick
+
+    def configure(self, on=True, tick0=0, **params):
+        """New mask, parameters and tick index; effective scales and records stay (LTPL_SIM_REACT_KEEP_STATE)."""
+        unknown = set(params) - set(REACT_PARAMS)
+        if unknown:
+            raise ValueError("ReactModel: unknown parameter %s" % sorted(unknown))
+        val = dict(REACT_DEFAULTS, **params)
+        self.on = [bool(x) for x in np.broadcast_to(np.asarray(on), (self.n,))]
+        val["on"] = [1.0 if x else 0.0 for x in self.on]
+        self.par = np.ascontiguousarray(np.stack([np.broadcast_to(np.asarray(val[k], np.float64), (self.n,)) for k in REACT_PARAMS], axis=1))
+        self.tick = int(tick0)
+
+    def step(self, p, pose, vel, opp_s, scales, lengths, dt):
+        scales = np.asarray(scales, np.float64).reshape(-1)
+        if not self.on[p]:
+            self.eff[p] = scales.copy()
+            return self.eff[p]
+        opp = np.column_stack((np.asarray(opp_s, np.float64).reshape(-1), scales, self.eff[p], np.asarray(lengths, np.float64).reshape(-1)))
+        e, per_opp, ego = react_tick(self.par[p], self.proj, pose[0], pose[1], vel, dt, self.tick, opp, self.rec[p])
+        self.eff[p], self.last[p] = e, (per_opp, ego)
+        return e
+
+    def advance(self):
+        self.tick += 1
+
+    def as_dict(self):
+        return react_dict(self.rec)

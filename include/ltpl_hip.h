@@ -67,7 +67,8 @@ extern "C" {
                                      ltpl_fleet_sim_tracker / _tracker_read / _tracker_eval,
                                      ltpl_fleet_sim_predictor / _predictor_read / _predictor_eval,
                                      ltpl_fleet_sim_selector / _selector_read / _selector_eval,
-                                     ltpl_fleet_sim_safety / _safety_read / _safety_eval */
+                                     ltpl_fleet_sim_safety / _safety_read / _safety_eval,
+                                     ltpl_fleet_sim_react / _react_read / _react_eval */
 
 /* status codes */
 #define LTPL_OK               0
@@ -1545,6 +1546,98 @@ int ltpl_fleet_sim_safety_read(ltpl_fleet* fleet, double* out, int32_t doubles_p
  * impact_t, closing_t. */
 int ltpl_fleet_sim_safety_eval(ltpl_fleet* fleet, int32_t n_cases, const double* pose, const double* dt, const int32_t* tick, const double* params,
                                const int32_t* obj_off, const double* objs, double* rec, double* inc, double* per_obj, double* per_tick);
+
+/* ------------------------------------------------------------------------------------------------------------------------------------------
+ * Additive to ABI v9 -- REACTIVE OPPONENTS: a car-following rule for the race-line opponents of the simulation (csrc/fleet_sim.hpp:
+ * k_fleet_sim_react; the rule: csrc/fleet_react.hpp). Without it every opponent integrates vel_rl(s) * vel_scale and sees nothing: a faster
+ * one drives through a slower one and through the ego from behind, contacts no planner could have avoided. With it every opponent keeps
+ * an EFFECTIVE scale e_q in [0, c_q] under its configured vel_scale c_q, decided at the head of every tick from the car ahead of it on the
+ * race line -- another opponent or the ego -- and the step kernels integrate vel_rl(s) * e_q. Off by default.
+ * ARITHMETIC: fp64, + - * / sqrt and comparisons only, one fixed order (the library is built with -ffp-contract=off), no pow, no
+ * trigonometry: the host mirror sim.ReactModel / sim.react_tick and the device agree to the last bit.
+ * INPUTS of planner p at the head of a tick: the TRUE pose pos_x / pos_y and speed vel the previous tick left (never the noise's estimate);
+ * dt; the model's tick index (tick0 + fleet ticks since the call: it advances whether or not the planner is live); the race table S, X, Y,
+ * V (columns 0, 1, 2, 4 of ltpl_fleet_sim_in::race), lap length L = S[n - 1]; per opponent s_q (opp_s), c_q (vel_scale as the events left
+ * it), e_q, l_q (length). PER PLANNER, all finite unless noted: on (0 / 1), a_max > 0, b_comf > 0, b_max > 0 [m/s^2], headway >= 0 [s],
+ * gap0 >= 0 [m], look > 0 [m] (+inf allowed), lat_gate >= 0 [m], ego_len >= 0 [m].
+ *   | step      | rule                                                                                                                |
+ *   | 0 ego     | the ego on the race line by steps 1 and 2 of the prediction model (nearest row, the better of its two segments):      |
+ *   |           | (s_e, d_e), or nothing without a candidate segment. A possible leader iff a projection exists and |d_e| <= lat_gate   |
+ *   |           | (equality inside, a NaN outside)                                                                                      |
+ *   | first     | Vq = np.interp of V at s_q. !(c_q > 0) or !(Vq > 0): PASSIVE -- e' = c_q, counted, steps 1 .. 5 skipped; as a leader  |
+ *   |           | of others its speed is c_q Vq                                                                                         |
+ *   | 1         | v_q = e_q Vq                                                                                                          |
+ *   | 2 leader  | candidates in the order ego, opponents r = 0 .. no - 1 (r != q): D = s_j - s_q, D < 0: D = D + L; against an opponent   |
+ *   |           | with D == 0: r < q is ahead at 0, r > q a lap ahead (D = L). Only a strictly smaller D replaces (the ego wins ties,   |
+ *   |           | then the lower index; a NaN never wins). No leader unless D <= look. Leader's speed u and length l_j: the ego's       |
+ *   |           | (vel, ego_len), opponent r's (e_r V(s_r), l_r) with e_r of the START of the tick                                      |
+ *   | 3         | gap = (D - 0.5 l_j) - 0.5 l_q                                                                                         |
+ *   | 4 acc     | r = e_q / c_q; free = 1 - (r r)(r r). No leader: a_max free. Leader and !(gap > 0): -b_max (an OVERLAP). Otherwise    |
+ *   |           | dv = v_q - u; z = v_q headway + (v_q dv) / (2 sqrt(a_max b_comf)), !(z > 0): 0; k = (gap0 + z) / gap;                 |
+ *   |           | acc = a_max (free - k k). Then acc < -b_max: -b_max (CLAMPED, counted); acc > a_max: a_max                            |
+ *   | 5         | e' = e_q + (acc dt) / Vq; !(e' > 0): 0; e' > c_q: c_q                                                                 |
+ * Every opponent reads the values of the start of the tick: the result does not depend on the order of evaluation. An opponent with no
+ * leader and e == c keeps e exactly (r = 1, free = 0, acc = 0, e + 0 / Vq = e): a fleet whose opponents never find a leader drives the run
+ * without a model bit for bit.
+ * THE RECORD, LTPL_FLEET_SIM_REACT_DOUBLES doubles: [0] ticks [1] opp_ticks (opponents x ticks) [2] follow_ticks: opponent-ticks with a
+ *   leader [3] ego_lead_ticks: those whose leader is the ego [4] clamped [5] overlaps [6] passive (opponent-ticks each) [7] gap_min
+ *   [8] gap_tick [9] gap_slot: the smallest gap of an opponent with a leader, its tick and the FOLLOWER's index [10] acc_min [11] acc_tick
+ *   [12] acc_slot: the smallest acc of an opponent that is not passive [13] ego_gap_min [14] ego_gap_tick: the smallest gap behind the ego
+ *   [15] ego_outside: ticks with a projection outside the gate. Minima replace when strictly smaller, ties go to the lower slot, a NaN
+ *   never wins. Start state: zeros, +inf in the minima, -1 in their ticks and slots.
+ * IN THE TICK: k_fleet_sim_react (one wave64 per planner, 2.3 KB of LDS) runs behind the events kernels and k_fleet_sim_select and in
+ * front of the step kernel, only while a model is set; the step kernels then read the effective scales where they read vel_scale. A
+ * planner whose error word is set returns at once (scales and record stay); one with on == 0 hands on its configured scales and does
+ * nothing else. A fleet that never calls this entry point launches the kernels it launched before, with the same arguments.
+ *   | with                          | what happens                                                                                 |
+ *   | ltpl_fleet_sim_setup          | switched off                                                                                 |
+ *   | events                        | LTPL_SIM_SET_OPP_VEL_SCALE writes c; e follows by the rule from that tick on (down at once by  |
+ *   |                               | the clamp e <= c, up at a_max). No new event kind                                             |
+ *   | noise / vehicle model         | the opponents react to the TRUE pose and speed                                               |
+ *   | sensor / tracker / predictor / selector / telemetry / safety / recorder | untouched: they read the staging              |
+ *   | snapshot / branch             | effective scales and record are what the tick writes: they TRAVEL (k_fleet_sim_branch_react    |
+ *   |                               | behind k_fleet_sim_branch); parameters and tick0 stay the destination's. A destination fleet   |
+ *   |                               | without a model takes nothing; a source without state (a snapshot taken with the model off)    |
+ *   |                               | leaves the destination the start state, e = its own c. Snapshot, run, restore,                 |
+ *   |                               | ltpl_fleet_sim_react(KEEP_STATE, tick0 = the snapshot's tick), run reproduces scales, records, |
+ *   |                               | trace and state bit for bit                                                                  |
+ *   | ltpl_fleet_sim_race / _predictor | kept                                                                                      |
+ *   | a failed planner              | skipped; scales and record stay                                                              |
+ * LIMITS: statics and race mates are no leaders; no lateral moves, no blue flags; parameters per planner, not per opponent; no event
+ * writes the model's parameters; the opponents see the truth, never a noisy view.
+ * THE CALL: after ltpl_fleet_sim_setup at any time between runs; in == NULL or on == 0 for every planner switches the model off. Every
+ * argument is checked before the first HIP call: every array present, on 0 or 1, the parameters as above, tick0 >= 0, no unknown flag.
+ * Everything new is allocated before anything old is freed; a failed call keeps the previous model. A successful call starts from e = c
+ * and fresh records -- with LTPL_SIM_REACT_KEEP_STATE (and a model set) parameters and tick0 change and scales and records stay.
+ * ------------------------------------------------------------------------------------------------------------------------------------------ */
+#define LTPL_FLEET_SIM_REACT_PARAMS 9
+#define LTPL_FLEET_SIM_REACT_DOUBLES 16
+#define LTPL_SIM_REACT_KEEP_STATE 1u
+typedef struct {
+    const int32_t* on;               /* [n] 0: the planner's opponents drive their configured scale, 1: they react */
+    const double* a_max;             /* [n] m/s^2, > 0: acceleration back to the configured speed      */
+    const double* b_comf;            /* [n] m/s^2, > 0: comfortable deceleration                       */
+    const double* b_max;             /* [n] m/s^2, > 0: hardest deceleration                           */
+    const double* headway;           /* [n] s, >= 0                                                    */
+    const double* gap0;              /* [n] m, >= 0: gap at standstill                                 */
+    const double* look;              /* [n] m, > 0, +inf allowed: how far ahead a leader is looked for */
+    const double* lat_gate;          /* [n] m, >= 0: the ego leads only within this distance of the race line */
+    const double* ego_len;           /* [n] m, >= 0                                                    */
+    int32_t tick0;                   /* >= 0: the model's tick of the next fleet tick                  */
+    uint32_t flags;                  /* LTPL_SIM_REACT_KEEP_STATE                                      */
+} ltpl_fleet_sim_react_in;
+int ltpl_fleet_sim_react(ltpl_fleet* fleet, const ltpl_fleet_sim_react_in* in);
+/* out: [n][LTPL_FLEET_SIM_REACT_DOUBLES]; eff_scale (or NULL): the effective scales in the order of ltpl_fleet_sim_state's opp_s.
+ * No simulation, the model off, a wrong record size: LTPL_ERR_INVALID_ARG. */
+int ltpl_fleet_sim_react_read(ltpl_fleet* fleet, double* out, int32_t doubles_per_planner, double* eff_scale);
+/* the test hook of the rule (k_fleet_sim_react_eval, one wave per case, the tick's own device function; needs a simulation, for the race
+ * table): case q is one tick with params[q][9] = on, a_max, b_comf, b_max, headway, gap0, look, lat_gate, ego_len (checked as above; on is
+ * not read), the ego ego[q][3] = x, y, v (any value, NaN included), dt[q] > 0, tick[q] >= 0 and the opponents
+ * opp[opp_off[q] .. opp_off[q + 1])[4] = s, c, e, length (0 .. 96, finite). rec[q][16]: IN the record before, OUT after. e_out[..]: the new
+ * scales; per_opp[..][4] = leader (-2 none, -1 the ego, else the index), D, gap, acc (D and gap +inf without a leader, acc 0 for a
+ * passive opponent); ego_out[q][3] = s_e, d_e, has. */
+int ltpl_fleet_sim_react_eval(ltpl_fleet* fleet, int32_t n_cases, const double* params, const double* ego, const double* dt, const int32_t* tick,
+                              const int32_t* opp_off, const double* opp, double* rec, double* e_out, double* per_opp, double* ego_out);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,7 @@
 """Closed-loop SIMULATION rate of a fleet (ltpl_fleet_sim_*): N planners, each with its own eight C2-style race-line opponents (SURVEY.md
 section 8d: s0_k = 250 + 280 k, vel_scale_k = 0.30 + 0.05 (k mod 4), here staggered by 10 m (p mod 16) per planner), run the example
 driver's loop on the device for T ticks without host work per tick.   tools/sim_rate.py [--planners 32768] [--ticks 200] [--no-tape]
-[--race-size K] [--friction-map] [--telemetry] [--record M [--record-depth D]] [--events] [--noise] [--vehicle] [--sensor [keep]] [--tracker] [--predictor [K[:MODE]]] [--selector] [--safety] [--lib PATH]. Prints planner-ticks per second of sim_run (device time of the run) next to tape_run on the C2 tape (recorded inputs,
+[--race-size K] [--friction-map] [--telemetry] [--record M [--record-depth D]] [--events] [--noise] [--vehicle] [--sensor [keep]] [--tracker] [--predictor [K[:MODE]]] [--selector] [--safety] [--react] [--lib PATH]. Prints planner-ticks per second of sim_run (device time of the run) next to tape_run on the C2 tape (recorded inputs,
 tools/fleet_rate.py). --race-size K > 1: races of K consecutive planners (ltpl_fleet_sim_race) that see one another, started 30 m apart
 along the race line with its heading; K = 1 (default) is the run without races. --friction-map: the same fleet on the friction grid of
 tests/golden/friction_grid.npz (ltpl_fleet_friction: rows evaluated on the device, grip factors 1.0 .. 0.7 over the planners) instead of
@@ -36,6 +36,8 @@ statistics are printed after the run.
 k_fleet_sim_select at the head of every tick, in front of the step kernel; the statistics are printed after the run.
 --safety: every planner behind the safety monitor (ltpl_fleet_sim_safety, sim.SAFETY_DEFAULTS): k_fleet_sim_safety behind telemetry and
 in front of the sensor in every tick; the first planners' records and the fleet's totals are printed after the run.
+--react: the opponents of every planner react to the car ahead (ltpl_fleet_sim_react, sim.REACT_DEFAULTS): k_fleet_sim_react at the head of
+every tick, in front of the step kernel; the fleet's totals and the first planners' records and scales are printed after the run.
 --lib PATH: another build of
 the library (A/B against the parent's)."""
 import argparse
@@ -76,6 +78,7 @@ def main():
                     help="every planner behind the prediction model: K points per object over 2 s, mode 0 / 1 / 2 (default 4:2)")
     ap.add_argument("--selector", action="store_true", help="every planner behind the behaviour selector (sim.SELECTOR_DEFAULTS)")
     ap.add_argument("--safety", action="store_true", help="every planner behind the safety monitor (sim.SAFETY_DEFAULTS)")
+    ap.add_argument("--react", action="store_true", help="the opponents of every planner react to the car ahead (sim.REACT_DEFAULTS)")
     ap.add_argument("--lib", default=None, help="path of the library to load (default: the in-tree build)")
     a = ap.parse_args()
     lat = Lattice.load(os.path.join(ROOT, "tests", "golden", "monteblanco_lattice.npz"))
@@ -146,6 +149,8 @@ def main():
             fleet.sim_selector()
         if a.safety:
             fleet.sim_safety()
+        if a.react:
+            fleet.sim_react()
         t0 = time.perf_counter()
         failed = 0
         try:
@@ -195,6 +200,18 @@ def main():
                           p, d["gap_min"][p], d["gap_tick"][p], d["gap_slot"][p], d["ttc_min"][p], d["ttc_tick"][p], d["ttc_slot"][p], d["tet"][p],
                           d["tit"][p], d["drac_max"][p], d["thw_min"][p], d["hist"][p].tolist(),
                           [(int(i["tick_first"]), int(i["tick_last"]), round(i["ttc_min"], 3)) for i in sim.safety_incidents(ring[p], d["n_incidents"][p])]))
+        if a.react:
+            d, eff = fleet.sim_react_read()
+            print("  react: %d ticks, %d opponent-ticks: %d with a leader (%d behind the ego), %d clamped at -b_max, %d overlapping, %d passive; "
+                  "smallest gap %.3f m, smallest acc %.3f m/s^2, smallest gap behind an ego %.3f m; %d ticks with the ego outside the gate" % (
+                      d["ticks"].sum(), d["opp_ticks"].sum(), d["follow_ticks"].sum(), d["ego_lead_ticks"].sum(), d["clamped"].sum(),
+                      d["overlaps"].sum(), d["passive"].sum(), np.min(d["gap_min"]), np.min(d["acc_min"]), np.min(d["ego_gap_min"]),
+                      d["ego_outside"].sum()))
+            no = eff.size // max(fleet.n_scen, 1)
+            for p in range(min(3, fleet.n_scen)):
+                print("    planner %d: follow_ticks %d, ego_lead_ticks %d, gap_min %.3f m (tick %d, opponent %d), acc_min %.3f (tick %d, opponent %d), "
+                      "effective scales %s" % (p, d["follow_ticks"][p], d["ego_lead_ticks"][p], d["gap_min"][p], d["gap_tick"][p], d["gap_slot"][p],
+                                               d["acc_min"][p], d["acc_tick"][p], d["acc_slot"][p], np.round(eff[p * no:(p + 1) * no], 4).tolist()))
         if a.selector:
             d = fleet.sim_selector_read()[0]
             print("  selector: %d evaluations, %d actions scored; %d switches, %d overrides of the list, %d without a safe action, %d emergency; chosen "
