@@ -472,6 +472,10 @@ typedef struct {
     const double*  given_coeff;     /* [n_edges * 8] x a0..a3, y a0..a3 (only read where raceline_edge != 0)      */
 } ltpl_offline_edges_in;
 
+/* n_samples is reported for every edge. An edge that does not fit (n_samples > cap_samples) and an edge whose nodes coincide
+ * (n_samples < 2: its 15-point length is 0) get valid = 0 and length = kappa_avg = kappa_range = 0; their coefficients are written.
+ * Of `samples`, rows [0, n_samples) of an edge that fits are written, the element length of row n_samples - 1 being 0. Rows at and
+ * beyond n_samples, and ALL rows of an edge that did not fit or has n_samples < 2, are unspecified (not cleared). */
 typedef struct {
     int32_t* n_samples;             /* [n_edges]  (> cap_samples: the edge did not fit, samples not written)      */
     int32_t* valid;                 /* [n_edges]  1 = kept by the curvature filter                                */

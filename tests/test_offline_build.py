@@ -116,6 +116,9 @@ def test_device_edges_match_the_restatement(hip_backend):
         assert_close_rel(d[k], r[k], what=k)
     assert_close_rel(d["samples"][..., 0:2], r["samples"][..., 0:2], what="xy")
     assert_close_rel(d["samples"][..., 3:5], r["samples"][..., 3:5], what="kappa, el")
+    rows = np.arange(d["samples"].shape[1])[None, :] < r["n_samples"][:, None]      # rows at and beyond n_samples are unspecified
+    dpsi = np.abs(np.mod(d["samples"][..., 2] - r["samples"][..., 2] + np.pi, 2 * np.pi) - np.pi)
+    assert float(dpsi[rows].max()) <= 1e-5 * np.pi                                  # psi modulo 2 pi, as check_against_reference_export
 
 
 @pytest.mark.gpu
