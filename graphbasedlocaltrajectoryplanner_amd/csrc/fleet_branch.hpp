@@ -213,9 +213,9 @@ static BranchView branch_live_view(const ltpl_fleet* f)
     v.state = f->d_state; v.gg = f->d_gg;
     v.now = d.now; v.sel = d.sel; v.started = d.started; v.pos_x = d.pos_x; v.pos_y = d.pos_y; v.vel = d.vel; v.theta = d.theta; v.live = d.live;
     v.opp_off = d.opp_off; v.opp_s = d.opp_s; v.opp_tic = d.opp_tic;
-    if (s.has_tele) { v.rec = s.te.rec; v.grid_s = s.te.grid_s; v.prog = s.te.prog; }
-    if (s.has_veh) { v.veh = s.vh.rec; v.veh_model = s.vh.model; }
-    if (s.has_trk) { v.trk = s.tk.rows; v.trk_n = s.tk.n; v.trk_next = s.tk.next_id; v.trk_base = s.tk.base; }
+    if (s.tele.on) { v.rec = s.tele.dev.rec; v.grid_s = s.tele.dev.grid_s; v.prog = s.tele.dev.prog; }
+    if (s.veh.on) { v.veh = s.veh.dev.rec; v.veh_model = s.veh.dev.model; }
+    if (s.trk.on) { v.trk = s.trk.dev.rows; v.trk_n = s.trk.dev.n; v.trk_next = s.trk.dev.next_id; v.trk_base = s.trk.dev.base; }
     return v;
 }
 
@@ -376,14 +376,14 @@ try {
     SNAP_TAKE(&v.theta, M); SNAP_TAKE(&v.live, M);
     { int* o = nullptr; SNAP_TAKE(&o, M + 1, q->opp_off.data()); v.opp_off = o; }
     SNAP_TAKE(&v.opp_s, n_opp); SNAP_TAKE(&v.opp_tic, n_opp);
-    if (s.has_tele) { SNAP_TAKE(&v.rec, M * LTPL_FLEET_SIM_TELE_DOUBLES); SNAP_TAKE(&v.grid_s, M); SNAP_TAKE(&v.prog, M); }
-    if (s.has_veh) {                                     // (the snapshot's entries carry the source's model: its records are copied as they are)
+    if (s.tele.on) { SNAP_TAKE(&v.rec, M * LTPL_FLEET_SIM_TELE_DOUBLES); SNAP_TAKE(&v.grid_s, M); SNAP_TAKE(&v.prog, M); }
+    if (s.veh.on) {                                     // (the snapshot's entries carry the source's model: its records are copied as they are)
         q->veh_model.resize(M);
         for (size_t k = 0; k < M; ++k) q->veh_model[k] = s.veh_model[(size_t)q->planners[k]];
         SNAP_TAKE(&v.veh, M * LTPL_FLEET_SIM_VEH_DOUBLES);
         { int* o = nullptr; SNAP_TAKE(&o, M, q->veh_model.data()); v.veh_model = o; }
     }
-    if (s.has_trk) {                                     // (with the tracker off the snapshot holds what it held before)
+    if (s.trk.on) {                                     // (with the tracker off the snapshot holds what it held before)
         std::vector<int> tb(M + 1, 0);
         for (size_t k = 0; k < M; ++k) tb[k + 1] = tb[k] + s.trk_cap[(size_t)q->planners[k]];
         SNAP_TAKE(&v.trk, (size_t)tb[M] * LTPL_FLEET_SIM_TRACK_DOUBLES); SNAP_TAKE(&v.trk_n, M); SNAP_TAKE(&v.trk_next, M);
@@ -391,7 +391,7 @@ try {
         q->has_trk = true;
     }
     StagedView& sv = q->stg;
-    if (s.has_sel) {                                     // (a list is state only for a selector; slots as the planners have them now)
+    if (s.sel.on) {                                     // (a list is state only for a selector; slots as the planners have them now)
         std::vector<int> sb(M + 1, 0);
         for (size_t k = 0; k < M; ++k) sb[k + 1] = sb[k] + s.slots[(size_t)q->planners[k]];
         SNAP_TAKE(&sv.cnt, M);
@@ -399,18 +399,18 @@ try {
         { int* o = nullptr; SNAP_TAKE(&o, M + 1, sb.data()); sv.base = o; }
     }
     SafetyView& fv = q->saf;
-    if (s.has_saf) { SNAP_TAKE(&fv.rec, M * LTPL_FLEET_SIM_SAFETY_DOUBLES); SNAP_TAKE(&fv.inc, M * SAF_RING); }
+    if (s.saf.on) { SNAP_TAKE(&fv.rec, M * LTPL_FLEET_SIM_SAFETY_DOUBLES); SNAP_TAKE(&fv.inc, M * SAF_RING); }
     ReactView& rv = q->rct;
-    if (s.has_react) { SNAP_TAKE(&rv.rec, M * LTPL_FLEET_SIM_REACT_DOUBLES); SNAP_TAKE(&rv.eff, n_opp); rv.opp_off = v.opp_off; }
+    if (s.react.on) { SNAP_TAKE(&rv.rec, M * LTPL_FLEET_SIM_REACT_DOUBLES); SNAP_TAKE(&rv.eff, n_opp); rv.opp_off = v.opp_off; }
 #undef SNAP_TAKE
     std::vector<int> dst(M);
     for (size_t k = 0; k < M; ++k) dst[k] = (int)k;
     if ((rc = branch_launch(f, branch_live_view(f), v, q->planners, dst, nullptr))) return rc;
     if (sv.cnt && (rc = branch_launch_staged(f, s.staged_valid ? branch_live_staged(f) : StagedView{}, sv, q->planners, dst))) return rc;
-    if (fv.rec && (rc = branch_launch_safety(f, SafetyView{s.sf.rec, s.sf.inc}, fv, q->planners, dst))) return rc;
-    if (rv.rec && (rc = branch_launch_react(f, ReactView{s.rc.eff, s.rc.rec, s.sd.opp_off}, rv, nullptr, q->planners, dst))) return rc;
+    if (fv.rec && (rc = branch_launch_safety(f, SafetyView{s.saf.dev.rec, s.saf.dev.inc}, fv, q->planners, dst))) return rc;
+    if (rv.rec && (rc = branch_launch_react(f, ReactView{s.react.dev.eff, s.react.dev.rec, s.sd.opp_off}, rv, nullptr, q->planners, dst))) return rc;
     q->allocs.swap(a.p);
-    q->has_tele = s.has_tele; q->tele_gen = s.tele_gen; q->bytes = bytes;
+    q->has_tele = s.tele.on; q->tele_gen = s.tele_gen; q->bytes = bytes;
     if (!s.snaps) s.snaps = new SimSnaps();
     SimSnap& old = s.snaps->slot[slot];
     sim_free_list(old.allocs);
@@ -489,7 +489,7 @@ try {
         }
         const int no_dst = s.opp_off[(size_t)b + 1] - s.opp_off[(size_t)b];
         if (no_src != no_dst) return bad(pair(k) + "the source has " + std::to_string(no_src) + " opponents, the destination " + std::to_string(no_dst));
-        if (s.has_veh && s.veh_model[(size_t)b] != 0) {      // (a destination on the ideal tracker takes no vehicle record)
+        if (s.veh.on && s.veh_model[(size_t)b] != 0) {      // (a destination on the ideal tracker takes no vehicle record)
             const bool src_has = q ? !q->veh_model.empty() && q->veh_model[(size_t)se.back()] != 0 : s.veh_model[(size_t)a] != 0;
             if (!src_has) return bad(pair(k) + "the destination drives the vehicle model, the source has no vehicle state (model 0 when it was copied)");
         }
@@ -498,7 +498,7 @@ try {
     if ((rc = fleet_enter(f))) return rc;
     FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
     BranchView S = q ? q->v : branch_live_view(f);
-    if (s.has_trk && S.trk_n && !se.empty()) {              // the sources' track counts against the destinations' capacities
+    if (s.trk.on && S.trk_n && !se.empty()) {              // the sources' track counts against the destinations' capacities
         const size_t ns = q ? q->planners.size() : (size_t)N;
         std::vector<int> nt(ns);
         FLEET_TRY(f, hipMemcpy(nt.data(), S.trk_n, sizeof(int) * ns, hipMemcpyDeviceToHost));
@@ -507,9 +507,9 @@ try {
                 return bad("the source of destination " + std::to_string(de[k]) + " holds " + std::to_string(nt[(size_t)se[k]]) + " tracks, the destination's table " +
                            std::to_string(s.trk_cap[(size_t)de[k]]));
     }
-    if (q && !(q->has_tele && s.has_tele && q->tele_gen == s.tele_gen)) S.rec = nullptr;      // (a telemetry set since then started its records anew)
+    if (q && !(q->has_tele && s.tele.on && q->tele_gen == s.tele_gen)) S.rec = nullptr;      // (a telemetry set since then started its records anew)
     if ((rc = branch_launch(f, S, branch_live_view(f), se, de, ms))) return rc;
-    if (s.has_sel) {                    // the staged lists: what the selector reads at the head of the next tick
+    if (s.sel.on) {                    // the staged lists: what the selector reads at the head of the next tick
         if (!s.staged_valid) {          // (no list yet, or a fresh staging: the other planners keep the empty lists a run would start from)
             FLEET_TRY(f, hipMemset(s.sd.cnt, 0, sizeof(int) * (size_t)N));
             s.staged_valid = true;
@@ -517,10 +517,10 @@ try {
         if ((rc = branch_launch_staged(f, q ? q->stg : branch_live_staged(f), branch_live_staged(f), se, de))) return rc;
     }
     // the safety monitor's records and rings: what the tick writes
-    if (s.has_saf && (rc = branch_launch_safety(f, q ? q->saf : SafetyView{s.sf.rec, s.sf.inc}, SafetyView{s.sf.rec, s.sf.inc}, se, de))) return rc;
+    if (s.saf.on && (rc = branch_launch_safety(f, q ? q->saf : SafetyView{s.saf.dev.rec, s.saf.dev.inc}, SafetyView{s.saf.dev.rec, s.saf.dev.inc}, se, de))) return rc;
     // the reactive opponents' effective scales and records: what the tick writes
-    if (s.has_react) {
-        const ReactView live{s.rc.eff, s.rc.rec, s.sd.opp_off};
+    if (s.react.on) {
+        const ReactView live{s.react.dev.eff, s.react.dev.rec, s.sd.opp_off};
         if ((rc = branch_launch_react(f, q ? q->rct : live, live, s.sd.opp_scale, se, de))) return rc;
     }
     f->cur.has_paths = false;           // (as after a run: a per-call calc_vel_profile needs its own calc_paths first)

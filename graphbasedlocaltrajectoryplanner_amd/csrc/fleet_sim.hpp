@@ -1613,6 +1613,34 @@ static void sim_events_free(SimEvents* e);
 static int sim_events_check_run(ltpl_fleet* f);                 // before the first launch of a run
 static int sim_events_tick(ltpl_fleet* f, FleetTickIn* t);      // head of a tick: the event kernels, t->any_emerg
 
+static void sim_free_list(std::vector<void*>& l)
+{
+    for (void* p : l) (void)hipFree(p);
+    l.clear();
+}
+// device buffers of a call that become the fleet's only when the whole call succeeded: freed on every early return
+struct SimAllocs {
+    std::vector<void*> p;
+    ~SimAllocs() { sim_free_list(p); }
+};
+
+// What the fleet holds of one model: the device buffers of the model's entry point, the argument struct its kernels get, whether the tick
+// launches them, and the model's tick count. An entry point allocates everything new into a SimAllocs and calls commit() last, so the
+// previous state stays unless every step succeeded; clear() switches the model off. A model without a tick leaves stamp() alone
+namespace {                                 // (host helpers of this file: nothing of them is exported)
+template <class Dev>
+struct SimModule {
+    std::vector<void*> allocs;
+    Dev dev{};
+    bool on = false;
+    int tick0 = 0, tick = 0;                // the caller's tick0; ticks of ltpl_fleet_sim_run since the model was set
+    void clear(const Dev& off = Dev{}) { sim_free_list(allocs); dev = off; on = false; tick0 = tick = 0; }
+    void commit(SimAllocs& a, const Dev& d, int t0 = 0) { sim_free_list(allocs); allocs.swap(a.p); dev = d; on = true; tick0 = t0; tick = 0; }
+    // the tick a launch of ltpl_fleet_sim_run stamps into dev.tick: counts on whether or not a planner is live, wraps like a uint32_t
+    uint32_t stamp() { return (uint32_t)tick0 + (uint32_t)tick++; }
+};
+}  // namespace
+
 struct FleetSim {
     std::vector<void*> allocs;
     std::vector<void*> stage_allocs;        // staging slots, the tick's object arrays and obj_base: sized again by ltpl_fleet_sim_race
@@ -1625,14 +1653,11 @@ struct FleetSim {
     bool ran = false;                       // ltpl_fleet_sim_run was called (ltpl_fleet_sim_race comes before it)
     int n_opp = 0, n_obj = 0;
     std::vector<int> own;                   // [N] opponents + statics of planner p
-    std::vector<void*> tele_allocs;         // race-line copies, radius, grid_s, records and progress of ltpl_fleet_sim_telemetry
-    SimTele te{};
-    bool has_tele = false;                  // k_fleet_sim_tele (and k_fleet_sim_rank with has_mates) run every tick
-    int tele_tick = 0;                      // ticks of ltpl_fleet_sim_run since the telemetry was set
-    std::vector<void*> rec_allocs;          // planner indices and ring of ltpl_fleet_sim_record
-    SimRec rec{};
-    bool has_rec = false;                   // k_fleet_sim_rec_paths / k_fleet_sim_rec_vel run every tick, on the unfused launch sequence
-    int rec_depth = 0, rec_tick = 0;        // ring depth; ticks of ltpl_fleet_sim_run since the recorder was set
+    SimModule<SimTele> tele;                // race-line copies, radius, grid_s, records and progress of ltpl_fleet_sim_telemetry:
+                                            // k_fleet_sim_tele (and k_fleet_sim_rank with has_mates) run every tick
+    SimModule<SimRec> rec;                  // planner indices and ring of ltpl_fleet_sim_record: k_fleet_sim_rec_paths / k_fleet_sim_rec_vel
+                                            // run every tick, on the unfused launch sequence; rec.tick picks the ring's row
+    int rec_depth = 0;                      // ring depth
     std::vector<int> rec_planners;          // host copy of the indices
     std::vector<double> rec_host;           // host copy of the ring (ltpl_fleet_sim_record_get), valid until the next run or recorder
     bool rec_host_valid = false;
@@ -1642,61 +1667,37 @@ struct FleetSim {
     std::vector<int> st_off, pref_off;      // [N + 1] host copies of sd.st_off / sd.pref_off (ltpl_fleet_sim_events checks local indices)
     std::vector<int> emerg; int n_emerg = 0;     // [N] host shadow of incl_emerg_traj (stored by ltpl_fleet_sim_vel, followed by the timed events) and its sum
     SimEvents* events = nullptr;            // the event list of ltpl_fleet_sim_events (null: events are off)
-    std::vector<void*> noise_allocs;        // seeds and sigmas of ltpl_fleet_sim_noise
-    SimNoise nz{};                          // est_x / est_y / est_v live in `allocs` (ltpl_fleet_sim_setup), g_tx / g_ty in the staging
-    bool has_noise = false;                 // the tick launches k_fleet_sim_step_noise / k_fleet_sim_mates_noise and reads pos_est / vel_est from nz.est_*
-    int noise_tick0 = 0, noise_tick = 0;    // tick0; ticks of ltpl_fleet_sim_run since the noise was set
-    std::vector<void*> veh_allocs;          // model, parameters and records of ltpl_fleet_sim_vehicle
-    SimVeh vh{};
-    bool has_veh = false;                   // the tick launches k_fleet_sim_step_veh / k_fleet_sim_step_noise_veh
-    std::vector<int> veh_model;             // [N] host copy of vh.model (KEEP_STATE; ltpl_fleet_sim_branch compares models)
-    std::vector<void*> sens_allocs;         // parameters, seeds and records of ltpl_fleet_sim_sensor
-    SimSense sn{};
-    bool has_sens = false;                  // the tick launches k_fleet_sim_sense in front of k_fleet_sim_offsets
-    int sens_tick0 = 0, sens_tick = 0;      // tick0; ticks of ltpl_fleet_sim_run since the sensor was set
+    SimModule<SimNoise> noise;              // seeds and sigmas of ltpl_fleet_sim_noise; est_x / est_y / est_v live in `allocs`
+                                            // (ltpl_fleet_sim_setup), g_tx / g_ty in the staging. On: the tick launches k_fleet_sim_step_noise /
+                                            // k_fleet_sim_mates_noise and reads pos_est / vel_est from noise.dev.est_*
+    SimModule<SimVeh> veh;                  // model, parameters and records of ltpl_fleet_sim_vehicle: the tick launches k_fleet_sim_step_veh /
+                                            // k_fleet_sim_step_noise_veh
+    std::vector<int> veh_model;             // [N] host copy of veh.dev.model (KEEP_STATE; ltpl_fleet_sim_branch compares models)
+    SimModule<SimSense> sens;               // parameters, seeds and records of ltpl_fleet_sim_sensor: k_fleet_sim_sense in front of k_fleet_sim_offsets
     std::vector<int> slots;                 // [N] staging slots of planner p (own + mates): the tracker's S_p
-    std::vector<void*> trk_allocs;          // parameters, tables, counts and records of ltpl_fleet_sim_tracker
-    SimTrack tk{};
-    bool has_trk = false;                   // the tick launches k_fleet_sim_track in front of k_fleet_sim_offsets
-    int trk_tick0 = 0, trk_tick = 0;        // tick0; ticks of ltpl_fleet_sim_run since the tracker was set
+    SimModule<SimTrack> trk;                // parameters, tables, counts and records of ltpl_fleet_sim_tracker: k_fleet_sim_track in front of
+                                            // k_fleet_sim_offsets
     std::vector<double> trk_par;            // [N][TRK_PARAMS] host copy (ltpl_fleet_sim_race allocates the tables again)
-    std::vector<int> trk_cap;               // [N] host copy of tk.cap (ltpl_fleet_sim_branch compares track counts with it)
-    std::vector<void*> pred_allocs;         // parameters and records of ltpl_fleet_sim_predictor
-    SimPred pd{};
-    bool has_pred = false;                  // the tick launches k_fleet_sim_predict in k_fleet_sim_compact's place
+    std::vector<int> trk_cap;               // [N] host copy of trk.dev.cap (ltpl_fleet_sim_branch compares track counts with it)
+    SimModule<SimPred> pred;                // parameters and records of ltpl_fleet_sim_predictor: k_fleet_sim_predict in k_fleet_sim_compact's place
     int pos_stride = 2;                     // positions per object of the staging in use: 2, or 1 + K while a predictor is set
-    std::vector<void*> sel_allocs;          // parameters, mask, ordered lists and records of ltpl_fleet_sim_selector
-    SimSel sl{};
-    bool has_sel = false;                   // the tick launches k_fleet_sim_select in front of the step kernel, which walks sl.ord
+    SimModule<SimSel> sel;                  // parameters, mask, ordered lists and records of ltpl_fleet_sim_selector: k_fleet_sim_select in front
+                                            // of the step kernel, which walks sel.dev.ord
     bool staged_valid = false;              // cnt and the staging slots hold the list of the last tick (false behind a re-allocation of the
                                             // staging: a run with a selector then starts from empty lists)
-    std::vector<void*> saf_allocs;          // parameters, mask, records and incident rings of ltpl_fleet_sim_safety
-    SimSafety sf{};
-    bool has_saf = false;                   // the tick launches k_fleet_sim_safety behind telemetry, in front of the sensor
-    int saf_tick0 = 0, saf_tick = 0;        // tick0; ticks of ltpl_fleet_sim_run since the monitor was set
-    std::vector<void*> react_allocs;        // parameters, effective scales and records of ltpl_fleet_sim_react
-    SimReact rc{};
-    bool has_react = false;                 // the tick launches k_fleet_sim_react in front of the step kernel, which reads rc.eff as opp_scale
-    int react_tick0 = 0, react_tick = 0;    // tick0; ticks of ltpl_fleet_sim_run since the model was set
-};
-static void sim_free_list(std::vector<void*>& l)
-{
-    for (void* p : l) (void)hipFree(p);
-    l.clear();
-}
-// device buffers of a call that become the fleet's only when the whole call succeeded: freed on every early return
-struct SimAllocs {
-    std::vector<void*> p;
-    ~SimAllocs() { sim_free_list(p); }
+    SimModule<SimSafety> saf;               // parameters, mask, records and incident rings of ltpl_fleet_sim_safety: k_fleet_sim_safety behind
+                                            // telemetry, in front of the sensor
+    SimModule<SimReact> react;              // parameters, effective scales and records of ltpl_fleet_sim_react: k_fleet_sim_react in front of the
+                                            // step kernel, which reads react.dev.eff as opp_scale
 };
 static void fleet_sim_free(FleetSim* s)
 {
     if (!s) return;
     sim_snaps_free(s->snaps);
     sim_events_free(s->events);
-    sim_free_list(s->stage_allocs); sim_free_list(s->race_allocs); sim_free_list(s->tele_allocs); sim_free_list(s->rec_allocs);
-    sim_free_list(s->noise_allocs); sim_free_list(s->veh_allocs); sim_free_list(s->sens_allocs); sim_free_list(s->trk_allocs);
-    sim_free_list(s->pred_allocs); sim_free_list(s->sel_allocs); sim_free_list(s->saf_allocs); sim_free_list(s->react_allocs);
+    sim_free_list(s->stage_allocs); sim_free_list(s->race_allocs);
+    s->tele.clear(); s->rec.clear(); s->noise.clear(); s->veh.clear(); s->sens.clear(); s->trk.clear(); s->pred.clear(); s->sel.clear();
+    s->saf.clear(); s->react.clear();
     for (void* p : s->allocs) (void)hipFree(p);
     if (s->velt.d_buf) (void)hipFree(s->velt.d_buf);
     delete s;
@@ -1715,6 +1716,119 @@ static int sim_upload(ltpl_fleet* f, std::vector<void*>& allocs, const T* src, s
 }
 template <class T>
 static int sim_upload(ltpl_fleet* f, FleetSim* s, const T* src, size_t n, T** out) { return sim_upload(f, s->allocs, src, n, out); }
+
+// one per-planner column of a model's ltpl_fleet_sim_*_in: its name in the messages and its values, doubles or integers
+struct SimCol {
+    const char* name; const double* d = nullptr; const int32_t* i = nullptr;
+    SimCol(const char* n, const double* p) : name(n), d(p) {}
+    SimCol(const char* n, const int32_t* p) : name(n), i(p) {}
+    double at(int p) const { return d ? d[p] : (double)i[p]; }
+};
+// Gathers the columns into the model's [N][P] parameter table *par, the one the entry point uploads, and checks it on the way:
+// "fleet sim <what>: <name> missing" for a column that is not there, then head() (the entry point's checks that come between the two:
+// null, or what is wrong), then row_ok(p, row, &why) for every planner, reported as "... planner <p>: <why>". The rules stay the model's
+template <size_t P, class Head, class RowOk>
+static int sim_param_table(ltpl_fleet* f, const char* what, const SimCol (&col)[P], Head head, RowOk row_ok, std::vector<double>* par)
+{
+    auto bad = [&](const std::string& why) { f->err = std::string("fleet sim ") + what + ": " + why; return LTPL_ERR_INVALID_ARG; };
+    for (const SimCol& c : col) if (!c.d && !c.i) return bad(std::string(c.name) + " missing");
+    if (const char* why = head()) return bad(why);
+    const int N = f->D.N;
+    par->resize((size_t)N * P);
+    for (int p = 0; p < N; ++p) {
+        double* q = par->data() + (size_t)p * P;
+        for (size_t c = 0; c < P; ++c) q[c] = col[c].at(p);
+        std::string why;
+        if (!row_ok(p, q, &why)) return bad("planner " + std::to_string(p) + ": " + why);
+    }
+    return LTPL_OK;
+}
+static const char* sim_no_head() { return nullptr; }
+
+// The shape the _read entry points share. Before the first HIP call, in this order: simulation present, model on (`off`: what the refusal
+// says), `out` present, record size, then extra(), the entry point's checks of its further outputs (0: fine). Then the device, the
+// stream and the N records of the model
+template <class Dev, class Extra>
+static int sim_read_records(ltpl_fleet* f, const char* what, SimModule<Dev> FleetSim::* mod, const char* off, double* out, const char* out_name,
+                            int32_t doubles_per_planner, int32_t record_doubles, Extra extra)
+{
+    auto bad = [&](const std::string& why) { f->err = std::string("fleet sim ") + what + ": " + why; return LTPL_ERR_INVALID_ARG; };
+    if (!f->sim) return bad("ltpl_fleet_sim_setup first");
+    const SimModule<Dev>& m = f->sim->*mod;
+    if (!m.on) return bad(off);
+    if (!out) return bad(std::string(out_name) + " missing");
+    if (doubles_per_planner != record_doubles) return bad("record size mismatch");
+    if (int rc = extra()) return rc;
+    FLEET_TRY(f, hipSetDevice(f->h->device));
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    FLEET_TRY(f, hipMemcpy(out, m.dev.rec, sizeof(double) * (size_t)f->D.N * (size_t)record_doubles, hipMemcpyDeviceToHost));
+    return LTPL_OK;
+}
+template <class Dev>
+static int sim_read_records(ltpl_fleet* f, const char* what, SimModule<Dev> FleetSim::* mod, const char* off, double* out, int32_t doubles_per_planner,
+                            int32_t record_doubles)
+{
+    return sim_read_records(f, what, mod, off, out, "out", doubles_per_planner, record_doubles, [] { return 0; });
+}
+
+// The device block of a test hook (ltpl_fleet_sim_*_eval and their kin): one hipMalloc, freed on every return. in / out / inout declare
+// the arrays by element count and return references that turn into device pointers once upload() has run; an array of 0 elements still
+// gets an address of its own, and is neither copied in nor fetched.
+// Order, the same for every hook: upload() zeroes the whole block, copies the inputs in and synchronises the stream; the hook launches;
+// fetch() queues the copies back behind the kernel and finish() waits for them. All of it runs on the fleet's stream, so the stream's
+// order is the only one needed; the synchronisation in front of the launch keeps the kernel from starting while the runtime may still
+// read a caller's pageable array. (Blocking hipMemset / hipMemcpy on the null stream, as the hooks once did, are correct as well: the
+// fleet's stream does not wait for the null stream, but a blocking copy returns with its bytes, and what was queued before it, in place.)
+namespace {
+class SimHookBlock {
+public:
+    template <class T> struct Ref {
+        const SimHookBlock* b; size_t off;
+        T* get() const { return reinterpret_cast<T*>(b->d_ + off); }
+        operator T*() const { return get(); }
+    };
+    explicit SimHookBlock(ltpl_fleet* f) : f_(f) {}
+    SimHookBlock(const SimHookBlock&) = delete;
+    SimHookBlock& operator=(const SimHookBlock&) = delete;
+    ~SimHookBlock() { if (d_) (void)hipFree(d_); }
+    template <class T> Ref<const T> in(const T* host, size_t count) { return {this, add(host, count * sizeof(T))}; }
+    template <class T> Ref<T> out(size_t count) { return {this, add(nullptr, count * sizeof(T))}; }
+    template <class T> Ref<T> inout(const T* host, size_t count) { return {this, add(host, count * sizeof(T))}; }
+    int upload()
+    {
+        hipStream_t st = f_->h->stream;
+        FLEET_TRY(f_, hipMalloc(reinterpret_cast<void**>(&d_), ar_.size));
+        FLEET_TRY(f_, hipMemsetAsync(d_, 0, ar_.size, st));
+        for (const Copy& c : copies_) FLEET_TRY(f_, hipMemcpyAsync(d_ + c.off, c.host, c.bytes, hipMemcpyHostToDevice, st));
+        FLEET_TRY(f_, hipStreamSynchronize(st));
+        return LTPL_OK;
+    }
+    template <class T, class U>
+    int fetch(T* host, Ref<U> dev, size_t count)
+    {
+        static_assert(std::is_same<T, typename std::remove_const<U>::type>::value, "the host array has the device array's element type");
+        if (count) FLEET_TRY(f_, hipMemcpyAsync(host, dev.get(), count * sizeof(T), hipMemcpyDeviceToHost, f_->h->stream));
+        return LTPL_OK;
+    }
+    int finish()
+    {
+        FLEET_TRY(f_, hipStreamSynchronize(f_->h->stream));
+        return LTPL_OK;
+    }
+private:
+    struct Copy { size_t off; const void* host; size_t bytes; };
+    size_t add(const void* host, size_t bytes)
+    {
+        const size_t off = ar_.add(bytes ? bytes : 1);
+        if (host && bytes) copies_.push_back(Copy{off, host, bytes});
+        return off;
+    }
+    ltpl_fleet* f_;
+    Arena ar_;                              // (arrays start on cache-line multiples)
+    std::vector<Copy> copies_;
+    unsigned char* d_ = nullptr;
+};
+}  // namespace
 
 // staging slots of every planner from obj_base[p] on (slots[p] of them) and the tick's object arrays of the fleet (pos_off[v] = stride v;
 // stride 2: own position and the ingestion's point; 1 + K with a prediction model):
@@ -1753,14 +1867,14 @@ static void sim_stage_commit(FleetSim* s, SimStage* st)
     d.obj_base = st->obj_base;
     d.g_x = st->g[0]; d.g_y = st->g[1]; d.g_px = st->g[2]; d.g_py = st->g[3]; d.g_r = st->g[4]; d.g_v = st->g[5];
     d.o_r = st->o[0]; d.o_v = st->o[1]; d.o_px = st->o[2]; d.o_py = st->o[3];
-    s->nz.g_tx = st->g[6]; s->nz.g_ty = st->g[7];
+    s->noise.dev.g_tx = st->g[6]; s->noise.dev.g_ty = st->g[7];
     s->pos_stride = st->stride;
     s->staged_valid = false;                // (the new staging holds no list: see FleetSim::staged_valid)
     s->ob = fleet::FObj{d.prev_action, d.t_now, d.veh_off, st->pos_off, d.o_r, d.o_v, d.o_px, d.o_py};
 }
 
 // the tracker's device arrays for the staging slots `slots`: empty tables, next_id 0, fresh statistics. Allocated into `al`; the caller
-// commits with sim_tracker_commit once everything else of its call succeeded
+// commits with sim_tracker_commit (which starts the tick count at tick0) once everything else of its call succeeded
 struct SimTrackNew { SimAllocs al; SimTrack tk{}; std::vector<int> cap; };
 static int sim_tracker_alloc(ltpl_fleet* f, const std::vector<int>& slots, const std::vector<double>& par, SimTrackNew* t)
 {
@@ -1787,13 +1901,10 @@ static int sim_tracker_alloc(ltpl_fleet* f, const std::vector<int>& slots, const
     t->tk.adv = f->sim->sd.dt / 0.2;       // the one division of the rule (fleet_track.hpp)
     return LTPL_OK;
 }
-static void sim_tracker_commit(FleetSim* s, SimTrackNew* t)
+static void sim_tracker_commit(FleetSim* s, SimTrackNew* t, int tick0)
 {
-    sim_free_list(s->trk_allocs);
-    s->trk_allocs.swap(t->al.p);
-    s->tk = t->tk;
+    s->trk.commit(t->al, t->tk, tick0);
     s->trk_cap.swap(t->cap);
-    s->has_trk = true;
 }
 
 static int sim_check_csr(ltpl_fleet* f, const int32_t* off, int N, const char* what, int* total)
@@ -1875,7 +1986,7 @@ try {
     SIM_UP(d.pos_x, in->pos_est_x, N); SIM_UP(d.pos_y, in->pos_est_y, N); SIM_UP(d.vel, in->vel_est, N);
     SIM_UP(d.theta, (const double*)nullptr, N); SIM_UP(d.live, (const int*)nullptr, N);
     SIM_UP(d.cnt, (const int*)nullptr, N);
-    SIM_UP(s->nz.est_x, in->pos_est_x, N); SIM_UP(s->nz.est_y, in->pos_est_y, N); SIM_UP(s->nz.est_v, in->vel_est, N);
+    SIM_UP(s->noise.dev.est_x, in->pos_est_x, N); SIM_UP(s->noise.dev.est_y, in->pos_est_y, N); SIM_UP(s->noise.dev.est_v, in->vel_est, N);
     SIM_UP(d.prev_action, sel.data(), N); SIM_UP(d.t_now, now.data(), N); SIM_UP(d.veh_off, (const int*)nullptr, N + 1);
     int* zo = nullptr; int* zg = nullptr;
     SIM_UP(zo, in->zone_off, N + 1); SIM_UP(zg, in->zone_gid, n_zone);
@@ -1934,7 +2045,10 @@ try {
     t.any_emerg = s.n_emerg > 0 ? 1 : 0;
     t.ob = s.ob; t.zone_off = s.zone_off; t.zone_gid = s.zone_gid;
     t.vin.pos_x = s.sd.pos_x; t.vin.pos_y = s.sd.pos_y; t.vin.vel_est = s.sd.vel;
-    if (s.has_noise) { t.vin.pos_x = s.nz.est_x; t.vin.pos_y = s.nz.est_y; t.vin.vel_est = s.nz.est_v; }   // get_ref_idx and the velocity stage see the estimate
+    SimNoise& nz = s.noise.dev;
+    if (s.noise.on) { t.vin.pos_x = nz.est_x; t.vin.pos_y = nz.est_y; t.vin.vel_est = nz.est_v; }   // get_ref_idx and the velocity stage see the estimate
+    // g_tx / g_ty of the staging for telemetry, the safety monitor and the sensor (written and read only while sensor noise is set)
+    double* const g_tx = s.noise.on ? nz.g_tx : nullptr; double* const g_ty = s.noise.on ? nz.g_ty : nullptr;
     t.has_paths = true;
     hipStream_t st = f->h->stream;
     s.ran = true;
@@ -1942,93 +2056,86 @@ try {
     FLEET_TRY(f, hipStreamSynchronize(st));
     FLEET_TRY(f, hipEventRecord(e0, st));
     // a selector reads the previous tick's staged list at the head of the tick: behind a re-allocation of the staging there is none
-    if (s.has_sel && !s.staged_valid) FLEET_TRY(f, hipMemsetAsync(s.sd.cnt, 0, sizeof(int) * (size_t)N, st));
+    if (s.sel.on && !s.staged_valid) FLEET_TRY(f, hipMemsetAsync(s.sd.cnt, 0, sizeof(int) * (size_t)N, st));
     s.staged_valid = true;
     SimDev sds = s.sd;                      // what the step and mates kernels get: the selector's ordered lists in the user's place
-    if (s.has_sel) sds.pref = s.sl.ord;
-    if (s.has_react) sds.opp_scale = s.rc.eff;       // ... and the reactive opponents' effective scales in the configured ones' place
+    if (s.sel.on) sds.pref = s.sel.dev.ord;
+    if (s.react.on) sds.opp_scale = s.react.dev.eff; // ... and the reactive opponents' effective scales in the configured ones' place
+    // (every model's tick advances whether or not a planner is live: a draw depends on the fleet's tick, not on the planner's history)
     for (int k = 0; k < n_ticks; ++k) {
         double* tr = d_trace ? d_trace + rec * (size_t)k : nullptr;
         if (s.events && (rc = sim_events_tick(f, &t))) return rc;
-        if (s.has_sel) {
-            hipLaunchKernelGGL(k_fleet_sim_select, dim3(N), dim3(64), 0, st, f->args, s.sd, s.sl);
+        if (s.sel.on) {
+            hipLaunchKernelGGL(k_fleet_sim_select, dim3(N), dim3(64), 0, st, f->args, s.sd, s.sel.dev);
             FLEET_TRY(f, hipGetLastError());
         }
-        if (s.has_react) {
-            // (the tick advances whether or not a planner is live, like the safety monitor's)
-            s.rc.tick = (uint32_t)s.react_tick0 + (uint32_t)s.react_tick++;
-            hipLaunchKernelGGL(k_fleet_sim_react, dim3(N), dim3(64), 0, st, f->args, s.sd, s.rc);
+        if (s.react.on) {
+            s.react.dev.tick = s.react.stamp();
+            hipLaunchKernelGGL(k_fleet_sim_react, dim3(N), dim3(64), 0, st, f->args, s.sd, s.react.dev);
             FLEET_TRY(f, hipGetLastError());
         }
-        if (s.has_noise) {
-            // (the tick advances whether or not a planner is live: a draw depends on the fleet's tick, not on the planner's history)
-            s.nz.tick = (uint32_t)s.noise_tick0 + (uint32_t)s.noise_tick++;
-            if (s.has_veh) hipLaunchKernelGGL(k_fleet_sim_step_noise_veh, dim3(N), dim3(64), 0, st, f->args, f->h->lat, sds, tr, s.nz, s.vh);
-            else hipLaunchKernelGGL(k_fleet_sim_step_noise, dim3(N), dim3(64), 0, st, f->args, f->h->lat, sds, tr, s.nz);
-        } else if (s.has_veh) {
-            hipLaunchKernelGGL(k_fleet_sim_step_veh, dim3(N), dim3(64), 0, st, f->args, f->h->lat, sds, tr, s.vh);
+        if (s.noise.on) {
+            nz.tick = s.noise.stamp();
+            if (s.veh.on) hipLaunchKernelGGL(k_fleet_sim_step_noise_veh, dim3(N), dim3(64), 0, st, f->args, f->h->lat, sds, tr, nz, s.veh.dev);
+            else hipLaunchKernelGGL(k_fleet_sim_step_noise, dim3(N), dim3(64), 0, st, f->args, f->h->lat, sds, tr, nz);
+        } else if (s.veh.on) {
+            hipLaunchKernelGGL(k_fleet_sim_step_veh, dim3(N), dim3(64), 0, st, f->args, f->h->lat, sds, tr, s.veh.dev);
         } else {
             hipLaunchKernelGGL(k_fleet_sim_step, dim3(N), dim3(64), 0, st, f->args, f->h->lat, sds, tr);
         }
         FLEET_TRY(f, hipGetLastError());
         if (s.has_mates) {
-            if (s.has_noise) hipLaunchKernelGGL(k_fleet_sim_mates_noise, dim3(N), dim3(64), 0, st, f->h->lat, sds, tr, s.nz);
+            if (s.noise.on) hipLaunchKernelGGL(k_fleet_sim_mates_noise, dim3(N), dim3(64), 0, st, f->h->lat, sds, tr, nz);
             else hipLaunchKernelGGL(k_fleet_sim_mates, dim3(N), dim3(64), 0, st, f->h->lat, sds, tr);
             FLEET_TRY(f, hipGetLastError());
         }
-        if (s.has_tele) {
-            hipLaunchKernelGGL(k_fleet_sim_tele, dim3(N), dim3(64), 0, st, s.sd, s.te, s.tele_tick++,
-                               (const double*)(s.has_noise ? s.nz.g_tx : nullptr), (const double*)(s.has_noise ? s.nz.g_ty : nullptr));
+        if (s.tele.on) {
+            hipLaunchKernelGGL(k_fleet_sim_tele, dim3(N), dim3(64), 0, st, s.sd, s.tele.dev, s.tele.tick++, (const double*)g_tx, (const double*)g_ty);
             FLEET_TRY(f, hipGetLastError());
             if (s.has_mates) {
-                hipLaunchKernelGGL(k_fleet_sim_rank, dim3(N), dim3(64), 0, st, s.sd, s.te);
+                hipLaunchKernelGGL(k_fleet_sim_rank, dim3(N), dim3(64), 0, st, s.sd, s.tele.dev);
                 FLEET_TRY(f, hipGetLastError());
             }
         }
-        if (s.has_saf) {
-            // (the tick advances whether or not a planner is live, like the noise's)
-            s.sf.tick = (uint32_t)s.saf_tick0 + (uint32_t)s.saf_tick++;
-            hipLaunchKernelGGL(k_fleet_sim_safety, dim3(N), dim3(64), 0, st, s.sd, s.sf, (const double*)(s.has_noise ? s.nz.g_tx : nullptr),
-                               (const double*)(s.has_noise ? s.nz.g_ty : nullptr));
+        if (s.saf.on) {
+            s.saf.dev.tick = s.saf.stamp();
+            hipLaunchKernelGGL(k_fleet_sim_safety, dim3(N), dim3(64), 0, st, s.sd, s.saf.dev, (const double*)g_tx, (const double*)g_ty);
             FLEET_TRY(f, hipGetLastError());
         }
-        if (s.has_sens) {
-            // (the tick advances whether or not a planner is live, like the noise's)
-            s.sn.tick = (uint32_t)s.sens_tick0 + (uint32_t)s.sens_tick++;
-            hipLaunchKernelGGL(k_fleet_sim_sense, dim3(N), dim3(64), 0, st, s.sd, s.sn, s.has_noise ? s.nz.g_tx : (double*)nullptr,
-                               s.has_noise ? s.nz.g_ty : (double*)nullptr, tr);
+        if (s.sens.on) {
+            s.sens.dev.tick = s.sens.stamp();
+            hipLaunchKernelGGL(k_fleet_sim_sense, dim3(N), dim3(64), 0, st, s.sd, s.sens.dev, g_tx, g_ty, tr);
             FLEET_TRY(f, hipGetLastError());
         }
-        if (s.has_trk) {
-            // (the tick advances whether or not a planner is live, like the sensor's)
-            s.tk.tick = (uint32_t)s.trk_tick0 + (uint32_t)s.trk_tick++;
-            hipLaunchKernelGGL(k_fleet_sim_track, dim3(N), dim3(64), 0, st, s.sd, s.tk, tr);
+        if (s.trk.on) {
+            s.trk.dev.tick = s.trk.stamp();
+            hipLaunchKernelGGL(k_fleet_sim_track, dim3(N), dim3(64), 0, st, s.sd, s.trk.dev, tr);
             FLEET_TRY(f, hipGetLastError());
         }
         hipLaunchKernelGGL(k_fleet_sim_offsets, dim3(1), dim3(1024), 0, st, (const int*)s.sd.cnt, N, s.sd.veh_off);
         FLEET_TRY(f, hipGetLastError());
-        if (s.has_pred) hipLaunchKernelGGL(k_fleet_sim_predict, dim3(N), dim3(64), 0, st, s.sd, s.pd);
+        if (s.pred.on) hipLaunchKernelGGL(k_fleet_sim_predict, dim3(N), dim3(64), 0, st, s.sd, s.pred.dev);
         else hipLaunchKernelGGL(k_fleet_sim_compact, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, st, s.sd, N);
         FLEET_TRY(f, hipGetLastError());
-        if (f->tape_fuse && !s.has_rec) {
+        const SimRec& rd = s.rec.dev;
+        if (f->tape_fuse && !s.rec.on) {
             fleet::FPathsOut po{};
             if ((rc = fleet_launch_paths(f, t, true, true, false, &po))) return rc;
             if ((rc = fleet_launch_vel(f, t, &po))) return rc;
         } else {
             // (the recorder looks at the state between paths_post and stage A: the launch sequence of LTPL_FLEET_NO_FUSE)
             if ((rc = fleet_launch_paths(f, t, true, true))) return rc;
-            if (s.has_rec) {
-                hipLaunchKernelGGL(k_fleet_sim_rec_paths, dim3(s.rec.M), dim3(64), 0, st, f->args, s.rec, s.rec_tick % s.rec_depth);
+            if (s.rec.on) {
+                hipLaunchKernelGGL(k_fleet_sim_rec_paths, dim3(rd.M), dim3(64), 0, st, f->args, rd, s.rec.tick % s.rec_depth);
                 FLEET_TRY(f, hipGetLastError());
             }
             if ((rc = fleet_launch_vel(f, t))) return rc;
         }
-        if (s.has_rec) {
+        if (s.rec.on) {
             // (the object arrays and veh_off through the simulation's pointers of this launch: ltpl_fleet_sim_race re-allocates the staging)
-            hipLaunchKernelGGL(k_fleet_sim_rec_vel, dim3(s.rec.M), dim3(64), 0, st, f->args, s.sd, s.rec, s.rec_tick % s.rec_depth, s.rec_tick,
-                               s.pos_stride);
+            hipLaunchKernelGGL(k_fleet_sim_rec_vel, dim3(rd.M), dim3(64), 0, st, f->args, s.sd, rd, s.rec.tick % s.rec_depth, s.rec.tick, s.pos_stride);
             FLEET_TRY(f, hipGetLastError());
-            ++s.rec_tick;
+            ++s.rec.tick;
         }
         if (tr) {
             hipLaunchKernelGGL(k_fleet_digest, dim3(N), dim3(64), 0, st, f->args, tr + 8, (int)LTPL_FLEET_SIM_TRACE_DOUBLES);
@@ -2082,7 +2189,7 @@ static int sim_check_race(ltpl_fleet* f, const ltpl_fleet_sim_race_in* in)
         for (int p = off[r]; p < off[r + 1]; ++p)
             if (f->sim->own[(size_t)p] + (off[r + 1] - off[r] - 1) > SIM_OBJ_CAP)
                 return bad("opponents + statics + mates above 96 for one planner", LTPL_ERR_CAPACITY);
-    if (f->sim->has_pred)                   // the path kernel's position arrays (ltpl_fleet_sim_predictor)
+    if (f->sim->pred.on)                    // the path kernel's position arrays (ltpl_fleet_sim_predictor)
         for (int r = 0; r < in->n_races; ++r)
             for (int p = off[r]; p < off[r + 1]; ++p)
                 if ((f->sim->own[(size_t)p] + (off[r + 1] - off[r] - 1)) * f->sim->pos_stride > MAX_POS)
@@ -2116,9 +2223,9 @@ try {
     if ((rc = sim_upload(f, ra.p, hi.data(), (size_t)N, &d_hi))) return rc;
     if ((rc = sim_upload(f, ra.p, in->length, (size_t)N, &d_len))) return rc;
     SimTrackNew tn;                         // a tracker keeps its configuration; its tables follow the new slot counts and start empty
-    if (s.has_trk && (rc = sim_tracker_alloc(f, slots, s.trk_par, &tn))) return rc;
+    if (s.trk.on && (rc = sim_tracker_alloc(f, slots, s.trk_par, &tn))) return rc;
     FLEET_TRY(f, hipMemcpy(s.sd.theta, in->heading0, sizeof(double) * (size_t)N, hipMemcpyHostToDevice));
-    if (s.has_trk) sim_tracker_commit(&s, &tn);
+    if (s.trk.on) sim_tracker_commit(&s, &tn, s.trk.tick0);    // (no run yet, see sim_check_race: its tick count is still 0)
     s.slots = slots;
     sim_stage_commit(&s, &st);
     sim_free_list(s.race_allocs);
@@ -2164,8 +2271,7 @@ try {
     FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
     FleetSim& s = *f->sim;
     if (!in) {
-        sim_free_list(s.tele_allocs);
-        s.te = SimTele{}; s.has_tele = false; s.tele_tick = 0; ++s.tele_gen;
+        s.tele.clear(); ++s.tele_gen;
         return LTPL_OK;
     }
     const int N = f->D.N;
@@ -2193,23 +2299,17 @@ try {
     SIM_UP(te.grid_s, in->grid_s ? in->grid_s : grid_nan.data(), N);
     SIM_UP(te.rec, rec.data(), rec.size()); SIM_UP(te.prog, prog.data(), N);
 #undef SIM_UP
-    sim_free_list(s.tele_allocs);
-    s.tele_allocs.swap(a.p);
-    s.te = te; s.has_tele = true; s.tele_tick = 0; ++s.tele_gen;
+    s.tele.commit(a, te); ++s.tele_gen;
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))
 
 extern "C" int ltpl_fleet_sim_telemetry_read(ltpl_fleet* f, double* out, int32_t doubles_per_planner, double* track_length)
 try {
     if (!f || !out) return LTPL_ERR_INVALID_ARG;
-    if (!f->sim) { f->err = "fleet sim telemetry: ltpl_fleet_sim_setup first"; return LTPL_ERR_INVALID_ARG; }
-    if (!f->sim->has_tele) { f->err = "fleet sim telemetry: telemetry is off (ltpl_fleet_sim_telemetry first)"; return LTPL_ERR_INVALID_ARG; }
-    if (doubles_per_planner != LTPL_FLEET_SIM_TELE_DOUBLES) { f->err = "fleet sim telemetry: record size mismatch"; return LTPL_ERR_INVALID_ARG; }
-    FLEET_TRY(f, hipSetDevice(f->h->device));
-    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
-    FLEET_TRY(f, hipMemcpy(out, f->sim->te.rec, sizeof(double) * (size_t)f->D.N * LTPL_FLEET_SIM_TELE_DOUBLES, hipMemcpyDeviceToHost));
-    if (track_length) *track_length = f->sim->te.length;
-    return LTPL_OK;
+    const int rc = sim_read_records(f, "telemetry", &FleetSim::tele, "telemetry is off (ltpl_fleet_sim_telemetry first)", out, doubles_per_planner,
+                                    LTPL_FLEET_SIM_TELE_DOUBLES);
+    if (rc == LTPL_OK && track_length) *track_length = f->sim->tele.dev.length;
+    return rc;
 } LTPL_ABI_CATCH(abi_err_of(f))
 
 // every argument is checked before the first HIP call
@@ -2239,11 +2339,10 @@ try {
     if ((rc = fleet_enter(f))) return rc;
     FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
     FleetSim& s = *f->sim;
-    auto reset = [&]() { s.rec_tick = 0; s.rec_host_valid = false; s.rec_host.clear(); s.rec_host.shrink_to_fit(); };
+    auto drop_host = [&]() { s.rec_host_valid = false; s.rec_host.clear(); s.rec_host.shrink_to_fit(); };
     if (!planners || n_planners == 0) {
-        sim_free_list(s.rec_allocs);
-        s.rec = SimRec{}; s.has_rec = false; s.rec_depth = 0; s.rec_planners.clear();
-        reset();
+        s.rec.clear(); s.rec_depth = 0; s.rec_planners.clear();
+        drop_host();
         return LTPL_OK;
     }
     SimRec r = sim_rec_layout(f->D, s.sd.n_export);
@@ -2254,10 +2353,8 @@ try {
     if ((rc = sim_upload(f, a.p, planners, (size_t)n_planners, &d_idx))) return rc;
     if ((rc = sim_upload(f, a.p, (const double*)nullptr, (size_t)depth * (size_t)n_planners * r.stride, &r.ring))) return rc;
     r.planners = d_idx;
-    sim_free_list(s.rec_allocs);
-    s.rec_allocs.swap(a.p);
-    s.rec = r; s.has_rec = true; s.rec_depth = depth; s.rec_planners.assign(planners, planners + n_planners);
-    reset();
+    s.rec.commit(a, r); s.rec_depth = depth; s.rec_planners.assign(planners, planners + n_planners);
+    drop_host();
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))
 
@@ -2266,10 +2363,10 @@ try {
     if (!f) return LTPL_ERR_INVALID_ARG;
     if (!f->sim) { f->err = "fleet sim record: ltpl_fleet_sim_setup first"; return LTPL_ERR_INVALID_ARG; }
     const FleetSim& s = *f->sim;
-    const int held = s.has_rec ? (s.rec_tick < s.rec_depth ? s.rec_tick : s.rec_depth) : 0;
-    if (n_planners) *n_planners = s.has_rec ? s.rec.M : 0;
+    const int held = s.rec.on ? (s.rec.tick < s.rec_depth ? s.rec.tick : s.rec_depth) : 0;
+    if (n_planners) *n_planners = s.rec.on ? s.rec.dev.M : 0;
     if (depth) *depth = s.rec_depth;
-    if (first_tick) *first_tick = s.rec_tick - held;
+    if (first_tick) *first_tick = s.rec.tick - held;
     if (n_ticks) *n_ticks = held;
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))
@@ -2281,13 +2378,13 @@ try {
     auto bad = [&](const char* why) { f->err = std::string("fleet sim record: ") + why; return LTPL_ERR_INVALID_ARG; };
     if (!f->sim) return bad("ltpl_fleet_sim_setup first");
     FleetSim& s = *f->sim;
-    if (!s.has_rec) return bad("the recorder is off (ltpl_fleet_sim_record first)");
-    const int held = s.rec_tick < s.rec_depth ? s.rec_tick : s.rec_depth;
-    if (tick < s.rec_tick - held || tick >= s.rec_tick) return bad("the ring does not hold this tick (ltpl_fleet_sim_record_info)");
-    if (slot < 0 || slot >= s.rec.M) return bad("slot outside the recorded planners");
+    if (!s.rec.on) return bad("the recorder is off (ltpl_fleet_sim_record first)");
+    const int held = s.rec.tick < s.rec_depth ? s.rec.tick : s.rec_depth;
+    if (tick < s.rec.tick - held || tick >= s.rec.tick) return bad("the ring does not hold this tick (ltpl_fleet_sim_record_info)");
+    if (slot < 0 || slot >= s.rec.dev.M) return bad("slot outside the recorded planners");
     FLEET_TRY(f, hipSetDevice(f->h->device));
     FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
-    const SimRec& r = s.rec;
+    const SimRec& r = s.rec.dev;
     if (!s.rec_host_valid) {                                    // once per run: later calls are served from the host copy
         const size_t n = (size_t)s.rec_depth * (size_t)r.M * r.stride;
         s.rec_host.resize(n);
@@ -2371,8 +2468,9 @@ try {
     FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
     FleetSim& s = *f->sim;
     if (!in) {
-        sim_free_list(s.noise_allocs);
-        s.nz.seed = nullptr; s.nz.sigma = nullptr; s.has_noise = false; s.noise_tick0 = s.noise_tick = 0;
+        SimNoise nz = s.noise.dev;         // (est_* and g_* belong to the setup and the staging: they stay)
+        nz.seed = nullptr; nz.sigma = nullptr;
+        s.noise.clear(nz);
         return LTPL_OK;
     }
     const size_t N = (size_t)f->D.N;
@@ -2384,14 +2482,14 @@ try {
     uint64_t* d_seed = nullptr; double* d_sigma = nullptr;
     if ((rc = sim_upload(f, a.p, in->seed, N, &d_seed))) return rc;
     if ((rc = sim_upload(f, a.p, sigma.data(), sigma.size(), &d_sigma))) return rc;
-    if (!s.has_noise) {                     // until the first noisy tick the estimate is the true state
-        FLEET_TRY(f, hipMemcpy(s.nz.est_x, s.sd.pos_x, 8 * N, hipMemcpyDeviceToDevice));
-        FLEET_TRY(f, hipMemcpy(s.nz.est_y, s.sd.pos_y, 8 * N, hipMemcpyDeviceToDevice));
-        FLEET_TRY(f, hipMemcpy(s.nz.est_v, s.sd.vel, 8 * N, hipMemcpyDeviceToDevice));
+    SimNoise nz = s.noise.dev;             // (est_* and g_* belong to the setup and the staging: they stay)
+    if (!s.noise.on) {                      // until the first noisy tick the estimate is the true state
+        FLEET_TRY(f, hipMemcpy(nz.est_x, s.sd.pos_x, 8 * N, hipMemcpyDeviceToDevice));
+        FLEET_TRY(f, hipMemcpy(nz.est_y, s.sd.pos_y, 8 * N, hipMemcpyDeviceToDevice));
+        FLEET_TRY(f, hipMemcpy(nz.est_v, s.sd.vel, 8 * N, hipMemcpyDeviceToDevice));
     }
-    sim_free_list(s.noise_allocs);
-    s.noise_allocs.swap(a.p);
-    s.nz.seed = d_seed; s.nz.sigma = d_sigma; s.has_noise = true; s.noise_tick0 = in->tick0; s.noise_tick = 0;
+    nz.seed = d_seed; nz.sigma = d_sigma;
+    s.noise.commit(a, nz, in->tick0);
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))
 
@@ -2403,9 +2501,10 @@ try {
     FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
     const FleetSim& s = *f->sim;
     const size_t n = (size_t)f->D.N;
-    if (x) FLEET_TRY(f, hipMemcpy(x, s.has_noise ? s.nz.est_x : s.sd.pos_x, 8 * n, hipMemcpyDeviceToHost));
-    if (y) FLEET_TRY(f, hipMemcpy(y, s.has_noise ? s.nz.est_y : s.sd.pos_y, 8 * n, hipMemcpyDeviceToHost));
-    if (v) FLEET_TRY(f, hipMemcpy(v, s.has_noise ? s.nz.est_v : s.sd.vel, 8 * n, hipMemcpyDeviceToHost));
+    const SimNoise& nz = s.noise.dev;
+    if (x) FLEET_TRY(f, hipMemcpy(x, s.noise.on ? nz.est_x : s.sd.pos_x, 8 * n, hipMemcpyDeviceToHost));
+    if (y) FLEET_TRY(f, hipMemcpy(y, s.noise.on ? nz.est_y : s.sd.pos_y, 8 * n, hipMemcpyDeviceToHost));
+    if (v) FLEET_TRY(f, hipMemcpy(v, s.noise.on ? nz.est_v : s.sd.vel, 8 * n, hipMemcpyDeviceToHost));
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))
 
@@ -2431,81 +2530,67 @@ try {
     int rc = fleet_enter(f);
     if (rc) return rc;
     const size_t m = (size_t)n;
-    Arena ar;     // one device block
-    const size_t o_seed = ar.add(8 * m), o_g = ar.add(8 * m), o_tick = ar.add(4 * m), o_obj = ar.add(4 * m), o_comp = ar.add(4 * m), o_words = ar.add(48 * m);
-    unsigned char* d = nullptr;
-    struct Guard { void* a = nullptr; ~Guard() { if (a) (void)hipFree(a); } } gd;
-    FLEET_TRY(f, hipMalloc(reinterpret_cast<void**>(&d), ar.size)); gd.a = d;
-    uint64_t* d_seed = reinterpret_cast<uint64_t*>(d + o_seed); double* d_g = reinterpret_cast<double*>(d + o_g);
-    uint32_t* d_tick = reinterpret_cast<uint32_t*>(d + o_tick); uint32_t* d_obj = reinterpret_cast<uint32_t*>(d + o_obj);
-    uint32_t* d_comp = reinterpret_cast<uint32_t*>(d + o_comp); uint32_t* d_words = reinterpret_cast<uint32_t*>(d + o_words);
-    FLEET_TRY(f, hipMemcpy(d_seed, seed, 8 * m, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d_tick, tick, 4 * m, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d_obj, obj, 4 * m, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d_comp, comp, 4 * m, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_fleet_noise_draws, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, f->h->stream, (const uint64_t*)d_seed, (const uint32_t*)d_tick,
-                       (const uint32_t*)d_obj, (const uint32_t*)d_comp, (int)n, d_g, words ? d_words : (uint32_t*)nullptr);
+    SimHookBlock b(f);
+    const auto d_seed = b.in(seed, m); const auto d_tick = b.in(tick, m); const auto d_obj = b.in(obj, m); const auto d_comp = b.in(comp, m);
+    const auto d_g = b.out<double>(m); const auto d_words = b.out<uint32_t>(12 * m);
+    if ((rc = b.upload())) return rc;
+    hipLaunchKernelGGL(k_fleet_noise_draws, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, f->h->stream, d_seed, d_tick, d_obj, d_comp, (int)n, d_g,
+                       words ? d_words.get() : nullptr);
     FLEET_TRY(f, hipGetLastError());
-    FLEET_TRY(f, hipMemcpyAsync(g, d_g, 8 * m, hipMemcpyDeviceToHost, f->h->stream));
-    if (words) FLEET_TRY(f, hipMemcpyAsync(words, d_words, 48 * m, hipMemcpyDeviceToHost, f->h->stream));
-    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
-    return LTPL_OK;
+    if ((rc = b.fetch(g, d_g, m))) return rc;
+    if (words && (rc = b.fetch(words, d_words, 12 * m))) return rc;
+    return b.finish();
 } LTPL_ABI_CATCH(abi_err_of(f))
 
 // ---------------------------------------------------------------------------------------------------------------------
 // vehicle model (ltpl_fleet_sim_vehicle, include/ltpl_hip.h; the model: fleet_vehicle.hpp)
 // ---------------------------------------------------------------------------------------------------------------------
 // every argument is checked before the first HIP call
-static int sim_check_vehicle(ltpl_fleet* f, const ltpl_fleet_sim_vehicle_in* in)
+static int sim_check_vehicle(ltpl_fleet* f, const ltpl_fleet_sim_vehicle_in* in, std::vector<double>* par)
 {
-    const int N = f->D.N;
     auto bad = [&](const std::string& why) { f->err = "fleet sim vehicle: " + why; return LTPL_ERR_INVALID_ARG; };
     if (!f->sim) return bad("ltpl_fleet_sim_setup first");
     if (!in) return LTPL_OK;
     if (in->flags & ~(uint32_t)LTPL_SIM_VEH_KEEP_STATE) return bad("unknown flag");
     if (in->ctl_steps < 1) return bad("ctl_steps must be at least 1");
     if (!in->model) return bad("model missing");
-    const double* a[VEH_PARAMS] = {in->ax_max, in->ay_max, in->grip, in->kappa_max, in->tau_a, in->tau_kappa, in->k_v, in->t_look, in->ld_min};
-    static const char* const name[VEH_PARAMS] = {"ax_max", "ay_max", "grip", "kappa_max", "tau_a", "tau_kappa", "k_v", "t_look", "ld_min"};
-    for (int c = 0; c < VEH_PARAMS; ++c) if (!a[c]) return bad(std::string(name[c]) + " missing");
-    for (int p = 0; p < N; ++p) {
-        if (in->model[p] != 0 && in->model[p] != 1) return bad("planner " + std::to_string(p) + ": model must be 0 or 1");
-        if (in->model[p] == 0) continue;            // (the parameters of a planner on the ideal tracker are not read)
+    const SimCol col[VEH_PARAMS] = {{"ax_max", in->ax_max}, {"ay_max", in->ay_max}, {"grip", in->grip}, {"kappa_max", in->kappa_max}, {"tau_a", in->tau_a},
+                                    {"tau_kappa", in->tau_kappa}, {"k_v", in->k_v}, {"t_look", in->t_look}, {"ld_min", in->ld_min}};
+    return sim_param_table(f, "vehicle", col, sim_no_head, [&](int p, const double* q, std::string* why) {
+        if (in->model[p] != 0 && in->model[p] != 1) { *why = "model must be 0 or 1"; return false; }
+        if (in->model[p] == 0) return true;         // (the parameters of a planner on the ideal tracker are not read)
         for (int c = 0; c < VEH_PARAMS; ++c) {
-            const double v = a[c][p];
-            if (!std::isfinite(v) || !(v > 0.0)) return bad("planner " + std::to_string(p) + ": " + name[c] + " must be finite and positive");
-            if ((c == 4 || c == 5) && v < 0.001) return bad("planner " + std::to_string(p) + ": " + name[c] + " must be at least 0.001 s");
+            if (!std::isfinite(q[c]) || !(q[c] > 0.0)) { *why = std::string(col[c].name) + " must be finite and positive"; return false; }
+            if ((c == 4 || c == 5) && q[c] < 0.001) { *why = std::string(col[c].name) + " must be at least 0.001 s"; return false; }
         }
-    }
-    return LTPL_OK;
+        return true;
+    }, par);
 }
 
 extern "C" int ltpl_fleet_sim_vehicle(ltpl_fleet* f, const ltpl_fleet_sim_vehicle_in* in)
 try {
     if (!f) return LTPL_ERR_INVALID_ARG;
-    int rc = sim_check_vehicle(f, in);
+    std::vector<double> par;
+    int rc = sim_check_vehicle(f, in, &par);
     if (rc) return rc;
     if ((rc = fleet_enter(f))) return rc;
     FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
     FleetSim& s = *f->sim;
     if (!in) {
-        sim_free_list(s.veh_allocs);
-        s.vh = SimVeh{}; s.has_veh = false; s.veh_model.clear();
+        s.veh.clear(); s.veh_model.clear();
         return LTPL_OK;
     }
     const size_t N = (size_t)f->D.N;
     constexpr size_t RD = LTPL_FLEET_SIM_VEH_DOUBLES;
-    const bool keep = (in->flags & LTPL_SIM_VEH_KEEP_STATE) && s.has_veh;
-    const double* a[VEH_PARAMS] = {in->ax_max, in->ay_max, in->grip, in->kappa_max, in->tau_a, in->tau_kappa, in->k_v, in->t_look, in->ld_min};
-    std::vector<double> par(N * VEH_PARAMS), rec(N * RD, NAN), old, px(N), py(N), pv(N), pt(N);
-    for (size_t p = 0; p < N; ++p) for (int c = 0; c < VEH_PARAMS; ++c) par[p * VEH_PARAMS + c] = a[c][p];
+    const bool keep = (in->flags & LTPL_SIM_VEH_KEEP_STATE) && s.veh.on;
+    std::vector<double> rec(N * RD, NAN), old, px(N), py(N), pv(N), pt(N);
     FLEET_TRY(f, hipMemcpy(px.data(), s.sd.pos_x, 8 * N, hipMemcpyDeviceToHost));
     FLEET_TRY(f, hipMemcpy(py.data(), s.sd.pos_y, 8 * N, hipMemcpyDeviceToHost));
     FLEET_TRY(f, hipMemcpy(pv.data(), s.sd.vel, 8 * N, hipMemcpyDeviceToHost));
     FLEET_TRY(f, hipMemcpy(pt.data(), s.sd.theta, 8 * N, hipMemcpyDeviceToHost));
     if (keep) {
         old.resize(N * RD);
-        FLEET_TRY(f, hipMemcpy(old.data(), s.vh.rec, 8 * N * RD, hipMemcpyDeviceToHost));
+        FLEET_TRY(f, hipMemcpy(old.data(), s.veh.dev.rec, 8 * N * RD, hipMemcpyDeviceToHost));
     }
     for (size_t p = 0; p < N; ++p) {
         if (in->model[p] == 0) continue;            // NaN: no state, no statistics
@@ -2520,24 +2605,16 @@ try {
     if ((rc = sim_upload(f, al.p, in->model, N, &d_model))) return rc;
     if ((rc = sim_upload(f, al.p, par.data(), par.size(), &d_par))) return rc;
     if ((rc = sim_upload(f, al.p, rec.data(), rec.size(), &d_rec))) return rc;
-    sim_free_list(s.veh_allocs);
-    s.veh_allocs.swap(al.p);
-    s.vh = SimVeh{d_model, d_par, d_rec, in->ctl_steps};
-    s.has_veh = true;
+    s.veh.commit(al, SimVeh{d_model, d_par, d_rec, in->ctl_steps});
     s.veh_model.assign(in->model, in->model + N);
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))
 
 extern "C" int ltpl_fleet_sim_vehicle_read(ltpl_fleet* f, double* out, int32_t doubles_per_planner)
 try {
-    if (!f || !out) return LTPL_ERR_INVALID_ARG;
-    if (!f->sim) { f->err = "fleet sim vehicle: ltpl_fleet_sim_setup first"; return LTPL_ERR_INVALID_ARG; }
-    if (!f->sim->has_veh) { f->err = "fleet sim vehicle: the model is off (ltpl_fleet_sim_vehicle first)"; return LTPL_ERR_INVALID_ARG; }
-    if (doubles_per_planner != LTPL_FLEET_SIM_VEH_DOUBLES) { f->err = "fleet sim vehicle: record size mismatch"; return LTPL_ERR_INVALID_ARG; }
-    FLEET_TRY(f, hipSetDevice(f->h->device));
-    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
-    FLEET_TRY(f, hipMemcpy(out, f->sim->vh.rec, sizeof(double) * (size_t)f->D.N * LTPL_FLEET_SIM_VEH_DOUBLES, hipMemcpyDeviceToHost));
-    return LTPL_OK;
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    return sim_read_records(f, "vehicle", &FleetSim::veh, "the model is off (ltpl_fleet_sim_vehicle first)", out, doubles_per_planner,
+                            LTPL_FLEET_SIM_VEH_DOUBLES);
 } LTPL_ABI_CATCH(abi_err_of(f))
 
 // the test hook of the model: one wave per case, the device function of the tick (sim_vehicle_tick) on the case's own rows, staged in LDS
@@ -2591,99 +2668,73 @@ try {
     if (nr > 0 && !rows) return bad("rows missing");
     int rc = fleet_enter(f);
     if (rc) return rc;
-    Arena ar;     // one device block
-    const size_t o_state = ar.add(56 * m), o_par = ar.add(8 * VEH_PARAMS * m), o_rows = ar.add(40 * (nr ? nr : 1)), o_dt = ar.add(8 * m),
-                 o_out = ar.add(8 * LTPL_FLEET_SIM_VEH_DOUBLES * m), o_theta = ar.add(8 * m), o_off = ar.add(4 * (m + 1)), o_ctl = ar.add(4 * m);
-    unsigned char* d = nullptr;
-    struct Guard { void* a = nullptr; ~Guard() { if (a) (void)hipFree(a); } } gd;
-    FLEET_TRY(f, hipMalloc(reinterpret_cast<void**>(&d), ar.size)); gd.a = d;
-    FLEET_TRY(f, hipMemcpy(d + o_state, state, 56 * m, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_par, params, 8 * VEH_PARAMS * m, hipMemcpyHostToDevice));
-    if (nr) FLEET_TRY(f, hipMemcpy(d + o_rows, rows, 40 * nr, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_dt, dt, 8 * m, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_off, row_off, 4 * (m + 1), hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_ctl, ctl_steps, 4 * m, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_fleet_sim_vehicle_step, dim3((unsigned)m), dim3(64), 0, f->h->stream, f->h->lat, (const double*)(d + o_state),
-                       (const double*)(d + o_par), (const int*)(d + o_off), (const double*)(d + o_rows), (const double*)(d + o_dt),
-                       (const int*)(d + o_ctl), reinterpret_cast<double*>(d + o_out), reinterpret_cast<double*>(d + o_theta));
+    SimHookBlock b(f);
+    const auto d_state = b.in(state, 7 * m); const auto d_par = b.in(params, VEH_PARAMS * m); const auto d_off = b.in(row_off, m + 1);
+    const auto d_rows = b.in(rows, 5 * nr); const auto d_dt = b.in(dt, m); const auto d_ctl = b.in(ctl_steps, m);
+    const auto d_out = b.out<double>(LTPL_FLEET_SIM_VEH_DOUBLES * m); const auto d_theta = b.out<double>(m);
+    if ((rc = b.upload())) return rc;
+    hipLaunchKernelGGL(k_fleet_sim_vehicle_step, dim3((unsigned)m), dim3(64), 0, f->h->stream, f->h->lat, d_state, d_par, d_off, d_rows, d_dt, d_ctl, d_out,
+                       d_theta);
     FLEET_TRY(f, hipGetLastError());
-    FLEET_TRY(f, hipMemcpyAsync(out, d + o_out, 8 * LTPL_FLEET_SIM_VEH_DOUBLES * m, hipMemcpyDeviceToHost, f->h->stream));
-    FLEET_TRY(f, hipMemcpyAsync(theta, d + o_theta, 8 * m, hipMemcpyDeviceToHost, f->h->stream));
-    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
-    return LTPL_OK;
+    if ((rc = b.fetch(out, d_out, LTPL_FLEET_SIM_VEH_DOUBLES * m))) return rc;
+    if ((rc = b.fetch(theta, d_theta, m))) return rc;
+    return b.finish();
 } LTPL_ABI_CATCH(abi_err_of(f))
 
 // ---------------------------------------------------------------------------------------------------------------------
 // sensor model (ltpl_fleet_sim_sensor, include/ltpl_hip.h; the rule: fleet_sensor.hpp)
 // ---------------------------------------------------------------------------------------------------------------------
 // every argument is checked before the first HIP call
-static int sim_check_sensor(ltpl_fleet* f, const ltpl_fleet_sim_sensor_in* in)
+static int sim_check_sensor(ltpl_fleet* f, const ltpl_fleet_sim_sensor_in* in, std::vector<double>* par)
 {
-    const int N = f->D.N;
     auto bad = [&](const std::string& why) { f->err = "fleet sim sensor: " + why; return LTPL_ERR_INVALID_ARG; };
     if (!f->sim) return bad("ltpl_fleet_sim_setup first");
     if (!in) return LTPL_OK;
-    const double* a[SENS_PARAMS] = {in->range, in->r_near, in->fov_cos, in->occl, in->p_drop};
-    static const char* const name[SENS_PARAMS] = {"range", "r_near", "fov_cos", "occl", "p_drop"};
-    for (int c = 0; c < SENS_PARAMS; ++c) if (!a[c]) return bad(std::string(name[c]) + " missing");
-    if (!in->seed) return bad("seed missing");
-    if (in->tick0 < 0) return bad("tick0 must not be negative");
-    for (int p = 0; p < N; ++p) {
-        const std::string who = "planner " + std::to_string(p) + ": ";
-        const double range = in->range[p], r_near = in->r_near[p], fov_cos = in->fov_cos[p], occl = in->occl[p], p_drop = in->p_drop[p];
-        if (!(range >= 0.0)) return bad(who + "range must not be negative or NaN (+inf: no limit)");
-        if (!(r_near >= 0.0) || !(r_near <= range)) return bad(who + "r_near must lie in [0, range]");
-        if (!(fov_cos >= -1.0) || !(fov_cos <= 1.0)) return bad(who + "fov_cos must lie in [-1, 1]");
-        if (!std::isfinite(occl) || !(occl >= 0.0)) return bad(who + "occl must be finite and not negative");
-        if (!(p_drop >= 0.0) || !(p_drop < 1.0)) return bad(who + "p_drop must lie in [0, 1)");
-    }
-    return LTPL_OK;
+    const SimCol col[SENS_PARAMS] = {{"range", in->range}, {"r_near", in->r_near}, {"fov_cos", in->fov_cos}, {"occl", in->occl}, {"p_drop", in->p_drop}};
+    auto head = [&]() -> const char* { return !in->seed ? "seed missing" : in->tick0 < 0 ? "tick0 must not be negative" : nullptr; };
+    return sim_param_table(f, "sensor", col, head, [](int, const double* q, std::string* why) {
+        const double range = q[0], r_near = q[1], fov_cos = q[2], occl = q[3], p_drop = q[4];
+        if (!(range >= 0.0)) { *why = "range must not be negative or NaN (+inf: no limit)"; return false; }
+        if (!(r_near >= 0.0) || !(r_near <= range)) { *why = "r_near must lie in [0, range]"; return false; }
+        if (!(fov_cos >= -1.0) || !(fov_cos <= 1.0)) { *why = "fov_cos must lie in [-1, 1]"; return false; }
+        if (!std::isfinite(occl) || !(occl >= 0.0)) { *why = "occl must be finite and not negative"; return false; }
+        if (!(p_drop >= 0.0) || !(p_drop < 1.0)) { *why = "p_drop must lie in [0, 1)"; return false; }
+        return true;
+    }, par);
 }
 
 extern "C" int ltpl_fleet_sim_sensor(ltpl_fleet* f, const ltpl_fleet_sim_sensor_in* in)
 try {
     if (!f) return LTPL_ERR_INVALID_ARG;
-    int rc = sim_check_sensor(f, in);
+    std::vector<double> par;
+    int rc = sim_check_sensor(f, in, &par);
     if (rc) return rc;
     if ((rc = fleet_enter(f))) return rc;
     FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
     FleetSim& s = *f->sim;
     if (!in) {
-        sim_free_list(s.sens_allocs);
-        s.sn = SimSense{}; s.has_sens = false; s.sens_tick0 = s.sens_tick = 0;
+        s.sens.clear();
         return LTPL_OK;
     }
     const size_t N = (size_t)f->D.N;
     constexpr size_t RD = LTPL_FLEET_SIM_SENSOR_DOUBLES;
-    const double* a[SENS_PARAMS] = {in->range, in->r_near, in->fov_cos, in->occl, in->p_drop};
-    std::vector<double> par(N * SENS_PARAMS), rec(N * RD, 0.0);
-    for (size_t p = 0; p < N; ++p) {
-        for (int c = 0; c < SENS_PARAMS; ++c) par[p * SENS_PARAMS + c] = a[c][p];
-        rec[p * RD + SENS_CLEAR_MIN] = INFINITY; rec[p * RD + SENS_CLEAR_TICK] = -1.0;
-    }
+    std::vector<double> rec(N * RD, 0.0);
+    for (size_t p = 0; p < N; ++p) { rec[p * RD + SENS_CLEAR_MIN] = INFINITY; rec[p * RD + SENS_CLEAR_TICK] = -1.0; }
     // everything new is allocated first; the fleet keeps its previous sensor, its tick count and its statistics unless every step succeeds
     SimAllocs al;
     double* d_par = nullptr; uint64_t* d_seed = nullptr; double* d_rec = nullptr;
     if ((rc = sim_upload(f, al.p, par.data(), par.size(), &d_par))) return rc;
     if ((rc = sim_upload(f, al.p, in->seed, N, &d_seed))) return rc;
     if ((rc = sim_upload(f, al.p, rec.data(), rec.size(), &d_rec))) return rc;
-    sim_free_list(s.sens_allocs);
-    s.sens_allocs.swap(al.p);
-    s.sn = SimSense{d_par, d_seed, d_rec, 0u};
-    s.has_sens = true; s.sens_tick0 = in->tick0; s.sens_tick = 0;
+    s.sens.commit(al, SimSense{d_par, d_seed, d_rec, 0u}, in->tick0);
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))
 
 extern "C" int ltpl_fleet_sim_sensor_read(ltpl_fleet* f, double* out, int32_t doubles_per_planner)
 try {
-    if (!f || !out) return LTPL_ERR_INVALID_ARG;
-    if (!f->sim) { f->err = "fleet sim sensor: ltpl_fleet_sim_setup first"; return LTPL_ERR_INVALID_ARG; }
-    if (!f->sim->has_sens) { f->err = "fleet sim sensor: the sensor is off (ltpl_fleet_sim_sensor first)"; return LTPL_ERR_INVALID_ARG; }
-    if (doubles_per_planner != LTPL_FLEET_SIM_SENSOR_DOUBLES) { f->err = "fleet sim sensor: record size mismatch"; return LTPL_ERR_INVALID_ARG; }
-    FLEET_TRY(f, hipSetDevice(f->h->device));
-    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
-    FLEET_TRY(f, hipMemcpy(out, f->sim->sn.rec, sizeof(double) * (size_t)f->D.N * LTPL_FLEET_SIM_SENSOR_DOUBLES, hipMemcpyDeviceToHost));
-    return LTPL_OK;
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    return sim_read_records(f, "sensor", &FleetSim::sens, "the sensor is off (ltpl_fleet_sim_sensor first)", out, doubles_per_planner,
+                            LTPL_FLEET_SIM_SENSOR_DOUBLES);
 } LTPL_ABI_CATCH(abi_err_of(f))
 
 extern "C" int ltpl_fleet_sim_sensor_eval(ltpl_fleet* f, int32_t n_cases, const double* pose_f, const double* params, const uint64_t* seed,
@@ -2703,83 +2754,58 @@ try {
     if (no > 0 && (!objs || !cause || !u)) return bad("objs / cause / u missing");
     int rc = fleet_enter(f);
     if (rc) return rc;
-    Arena ar;     // one device block
-    const size_t o_pf = ar.add(32 * m), o_par = ar.add(8 * SENS_PARAMS * m), o_seed = ar.add(8 * m), o_objs = ar.add(24 * (no ? no : 1)),
-                 o_u = ar.add(8 * (no ? no : 1)), o_tick = ar.add(4 * m), o_off = ar.add(4 * (m + 1)), o_cause = ar.add(4 * (no ? no : 1));
-    unsigned char* d = nullptr;
-    struct Guard { void* a = nullptr; ~Guard() { if (a) (void)hipFree(a); } } gd;
-    FLEET_TRY(f, hipMalloc(reinterpret_cast<void**>(&d), ar.size)); gd.a = d;
-    FLEET_TRY(f, hipMemcpy(d + o_pf, pose_f, 32 * m, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_par, params, 8 * SENS_PARAMS * m, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_seed, seed, 8 * m, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_tick, tick, 4 * m, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_off, obj_off, 4 * (m + 1), hipMemcpyHostToDevice));
-    if (no) FLEET_TRY(f, hipMemcpy(d + o_objs, objs, 24 * no, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_fleet_sim_sensor_eval, dim3((unsigned)m), dim3(64), 0, f->h->stream, (const double*)(d + o_pf), (const double*)(d + o_par),
-                       (const uint64_t*)(d + o_seed), (const uint32_t*)(d + o_tick), (const int*)(d + o_off), (const double*)(d + o_objs),
-                       reinterpret_cast<int*>(d + o_cause), reinterpret_cast<double*>(d + o_u));
+    SimHookBlock b(f);
+    const auto d_pf = b.in(pose_f, 4 * m); const auto d_par = b.in(params, SENS_PARAMS * m); const auto d_seed = b.in(seed, m);
+    const auto d_tick = b.in(tick, m); const auto d_off = b.in(obj_off, m + 1); const auto d_objs = b.in(objs, 3 * no);
+    const auto d_cause = b.out<int32_t>(no); const auto d_u = b.out<double>(no);
+    if ((rc = b.upload())) return rc;
+    hipLaunchKernelGGL(k_fleet_sim_sensor_eval, dim3((unsigned)m), dim3(64), 0, f->h->stream, d_pf, d_par, d_seed, d_tick, d_off, d_objs, d_cause, d_u);
     FLEET_TRY(f, hipGetLastError());
-    if (no) {
-        FLEET_TRY(f, hipMemcpyAsync(cause, d + o_cause, 4 * no, hipMemcpyDeviceToHost, f->h->stream));
-        FLEET_TRY(f, hipMemcpyAsync(u, d + o_u, 8 * no, hipMemcpyDeviceToHost, f->h->stream));
-    }
-    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
-    return LTPL_OK;
+    if ((rc = b.fetch(cause, d_cause, no))) return rc;
+    if ((rc = b.fetch(u, d_u, no))) return rc;
+    return b.finish();
 } LTPL_ABI_CATCH(abi_err_of(f))
 
 // ---------------------------------------------------------------------------------------------------------------------
 // object tracker (ltpl_fleet_sim_tracker, include/ltpl_hip.h; the rule: fleet_track.hpp)
 // ---------------------------------------------------------------------------------------------------------------------
 // every argument is checked before the first HIP call
-static int sim_check_tracker(ltpl_fleet* f, const ltpl_fleet_sim_tracker_in* in)
+static int sim_check_tracker(ltpl_fleet* f, const ltpl_fleet_sim_tracker_in* in, std::vector<double>* par)
 {
-    const int N = f->D.N;
     auto bad = [&](const std::string& why) { f->err = "fleet sim tracker: " + why; return LTPL_ERR_INVALID_ARG; };
     if (!f->sim) return bad("ltpl_fleet_sim_setup first");
     if (!in) return LTPL_OK;
-    if (!in->gate) return bad("gate missing");
-    if (!in->w_pos) return bad("w_pos missing");
-    if (!in->w_vel) return bad("w_vel missing");
-    if (!in->n_confirm) return bad("n_confirm missing");
-    if (!in->n_coast) return bad("n_coast missing");
-    if (in->tick0 < 0) return bad("tick0 must not be negative");
-    for (int p = 0; p < N; ++p) {
-        const std::string who = "planner " + std::to_string(p) + ": ";
-        if (!std::isfinite(in->gate[p]) || !(in->gate[p] > 0.0)) return bad(who + "gate must be finite and positive");
-        if (!(in->w_pos[p] >= 0.0) || !(in->w_pos[p] < 1.0)) return bad(who + "w_pos must lie in [0, 1)");
-        if (!(in->w_vel[p] >= 0.0) || !(in->w_vel[p] < 1.0)) return bad(who + "w_vel must lie in [0, 1)");
-        if (in->n_confirm[p] < 1 || in->n_confirm[p] > 255) return bad(who + "n_confirm must lie in 1 .. 255");
-        if (in->n_coast[p] < 0 || in->n_coast[p] > 255) return bad(who + "n_coast must lie in 0 .. 255");
-    }
-    return LTPL_OK;
+    const SimCol col[TRK_PARAMS] = {{"gate", in->gate}, {"w_pos", in->w_pos}, {"w_vel", in->w_vel}, {"n_confirm", in->n_confirm}, {"n_coast", in->n_coast}};
+    auto head = [&]() -> const char* { return in->tick0 < 0 ? "tick0 must not be negative" : nullptr; };
+    return sim_param_table(f, "tracker", col, head, [](int, const double* q, std::string* why) {
+        if (!std::isfinite(q[0]) || !(q[0] > 0.0)) { *why = "gate must be finite and positive"; return false; }
+        if (!(q[1] >= 0.0) || !(q[1] < 1.0)) { *why = "w_pos must lie in [0, 1)"; return false; }
+        if (!(q[2] >= 0.0) || !(q[2] < 1.0)) { *why = "w_vel must lie in [0, 1)"; return false; }
+        if (q[3] < 1.0 || q[3] > 255.0) { *why = "n_confirm must lie in 1 .. 255"; return false; }
+        if (q[4] < 0.0 || q[4] > 255.0) { *why = "n_coast must lie in 0 .. 255"; return false; }
+        return true;
+    }, par);
 }
 
 extern "C" int ltpl_fleet_sim_tracker(ltpl_fleet* f, const ltpl_fleet_sim_tracker_in* in)
 try {
     if (!f) return LTPL_ERR_INVALID_ARG;
-    int rc = sim_check_tracker(f, in);
+    std::vector<double> par;
+    int rc = sim_check_tracker(f, in, &par);
     if (rc) return rc;
     if ((rc = fleet_enter(f))) return rc;
     FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
     FleetSim& s = *f->sim;
     if (!in) {
-        sim_free_list(s.trk_allocs);
-        s.tk = SimTrack{}; s.has_trk = false; s.trk_tick0 = s.trk_tick = 0;
+        s.trk.clear();
         s.trk_par.clear(); s.trk_cap.clear();
         return LTPL_OK;
-    }
-    const size_t N = (size_t)f->D.N;
-    std::vector<double> par(N * TRK_PARAMS);
-    for (size_t p = 0; p < N; ++p) {
-        double* q = &par[p * TRK_PARAMS];
-        q[0] = in->gate[p]; q[1] = in->w_pos[p]; q[2] = in->w_vel[p]; q[3] = (double)in->n_confirm[p]; q[4] = (double)in->n_coast[p];
     }
     // everything new is allocated first; the fleet keeps its previous tracker, its tables, its tick count and its statistics unless every step succeeds
     SimTrackNew tn;
     if ((rc = sim_tracker_alloc(f, s.slots, par, &tn))) return rc;
-    sim_tracker_commit(&s, &tn);
+    sim_tracker_commit(&s, &tn, in->tick0);
     s.trk_par.swap(par);
-    s.trk_tick0 = in->tick0; s.trk_tick = 0;
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))
 
@@ -2788,21 +2814,20 @@ extern "C" int ltpl_fleet_sim_tracker_read(ltpl_fleet* f, double* rec_out, int32
 try {
     if (!f) return LTPL_ERR_INVALID_ARG;
     auto bad = [&](const std::string& why) { f->err = "fleet sim tracker: " + why; return LTPL_ERR_INVALID_ARG; };
-    if (!f->sim) return bad("ltpl_fleet_sim_setup first");
-    if (!f->sim->has_trk) return bad("the tracker is off (ltpl_fleet_sim_tracker first)");
-    if (!rec_out) return bad("rec_out missing");
-    if (doubles_per_planner != LTPL_FLEET_SIM_TRACKER_DOUBLES) return bad("record size mismatch");
     const int N = f->D.N;
-    if (n_sel < 0) return bad("n_sel must not be negative");
-    if (n_sel > 0 && (!sel_planners || !tracks_out || !n_tracks_out)) return bad("sel_planners / tracks_out / n_tracks_out missing");
-    for (int i = 0; i < n_sel; ++i) if (sel_planners[i] < 0 || sel_planners[i] >= N) return bad("planner index " + std::to_string(sel_planners[i]) + " out of range");
+    int rc = sim_read_records(f, "tracker", &FleetSim::trk, "the tracker is off (ltpl_fleet_sim_tracker first)", rec_out, "rec_out", doubles_per_planner,
+                              LTPL_FLEET_SIM_TRACKER_DOUBLES, [&] {
+        if (n_sel < 0) return bad("n_sel must not be negative");
+        if (n_sel > 0 && (!sel_planners || !tracks_out || !n_tracks_out)) return bad("sel_planners / tracks_out / n_tracks_out missing");
+        for (int i = 0; i < n_sel; ++i) if (sel_planners[i] < 0 || sel_planners[i] >= N) return bad("planner index " + std::to_string(sel_planners[i]) + " out of range");
+        return LTPL_OK;
+    });
+    if (rc) return rc;
     const FleetSim& s = *f->sim;
-    FLEET_TRY(f, hipSetDevice(f->h->device));
-    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
-    FLEET_TRY(f, hipMemcpy(rec_out, s.tk.rec, sizeof(double) * (size_t)N * LTPL_FLEET_SIM_TRACKER_DOUBLES, hipMemcpyDeviceToHost));
+    const SimTrack& tk = s.trk.dev;
     if (n_sel == 0) return LTPL_OK;
     std::vector<int> n_trk((size_t)N);
-    FLEET_TRY(f, hipMemcpy(n_trk.data(), s.tk.n, sizeof(int) * (size_t)N, hipMemcpyDeviceToHost));
+    FLEET_TRY(f, hipMemcpy(n_trk.data(), tk.n, sizeof(int) * (size_t)N, hipMemcpyDeviceToHost));
     constexpr size_t RD = LTPL_FLEET_SIM_TRACK_DOUBLES, TAB = (size_t)SIM_OBJ_CAP * RD;
     size_t base = 0;
     std::vector<size_t> row0((size_t)N);
@@ -2812,7 +2837,7 @@ try {
         const int n = n_trk[p] < s.trk_cap[p] ? n_trk[p] : s.trk_cap[p];
         double* o = tracks_out + (size_t)i * TAB;
         for (size_t c = 0; c < TAB; ++c) o[c] = NAN;
-        if (n > 0) FLEET_TRY(f, hipMemcpy(o, s.tk.rows + row0[p] * RD, sizeof(double) * (size_t)n * RD, hipMemcpyDeviceToHost));
+        if (n > 0) FLEET_TRY(f, hipMemcpy(o, tk.rows + row0[p] * RD, sizeof(double) * (size_t)n * RD, hipMemcpyDeviceToHost));
         n_tracks_out[i] = n;
     }
     return LTPL_OK;
@@ -2845,7 +2870,7 @@ try {
     if (nt > 0 && !tracks) return bad("tracks missing");
     if (nd > 0 && (!dets || !assign)) return bad("dets / assign missing");
     constexpr size_t RD = LTPL_FLEET_SIM_TRACK_DOUBLES, TAB = (size_t)SIM_OBJ_CAP * RD, OUT = (size_t)SIM_OBJ_CAP * 6, SD = LTPL_FLEET_SIM_TRACKER_DOUBLES;
-    std::vector<double> tab(m * TAB, NAN), zero(m * (OUT > SD ? OUT : SD), 0.0);
+    std::vector<double> tab(m * TAB, NAN);
     std::vector<int> n0(m);
     for (size_t q = 0; q < m; ++q) {
         n0[q] = trk_off[q + 1] - trk_off[q];
@@ -2853,38 +2878,24 @@ try {
     }
     int rc = fleet_enter(f);
     if (rc) return rc;
-    Arena ar;     // one device block
-    const size_t o_par = ar.add(8 * TRK_PARAMS * m), o_adv = ar.add(8 * m), o_tab = ar.add(8 * TAB * m), o_id = ar.add(8 * m), o_dets = ar.add(48 * (nd ? nd : 1)),
-                 o_out = ar.add(8 * OUT * m), o_rec = ar.add(8 * SD * m), o_tick = ar.add(4 * m), o_cs = ar.add(8 * m), o_n = ar.add(4 * m),
-                 o_doff = ar.add(4 * (m + 1)), o_nout = ar.add(4 * m), o_asg = ar.add(4 * (nd ? nd : 1));
-    unsigned char* d = nullptr;
-    struct Guard { void* a = nullptr; ~Guard() { if (a) (void)hipFree(a); } } gd;
-    FLEET_TRY(f, hipMalloc(reinterpret_cast<void**>(&d), ar.size)); gd.a = d;
-    FLEET_TRY(f, hipMemcpy(d + o_par, params, 8 * TRK_PARAMS * m, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_adv, adv, 8 * m, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_tab, tab.data(), 8 * TAB * m, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_id, next_id, 8 * m, hipMemcpyHostToDevice));
-    if (nd) FLEET_TRY(f, hipMemcpy(d + o_dets, dets, 48 * nd, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_out, zero.data(), 8 * OUT * m, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_rec, zero.data(), 8 * SD * m, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_tick, tick, 4 * m, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_cs, cap_slots, 8 * m, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_n, n0.data(), 4 * m, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_doff, det_off, 4 * (m + 1), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_fleet_sim_tracker_eval, dim3((unsigned)m), dim3(64), 0, f->h->stream, (const double*)(d + o_par), (const double*)(d + o_adv),
-                       (const uint32_t*)(d + o_tick), (const int*)(d + o_cs), reinterpret_cast<double*>(d + o_tab), reinterpret_cast<int*>(d + o_n),
-                       reinterpret_cast<double*>(d + o_id), (const int*)(d + o_doff), (const double*)(d + o_dets), reinterpret_cast<double*>(d + o_out),
-                       reinterpret_cast<int*>(d + o_nout), reinterpret_cast<int*>(d + o_asg), reinterpret_cast<double*>(d + o_rec));
+    SimHookBlock b(f);
+    const auto d_par = b.in(params, TRK_PARAMS * m); const auto d_adv = b.in(adv, m); const auto d_tick = b.in(tick, m);
+    const auto d_cs = b.in(cap_slots, 2 * m); const auto d_doff = b.in(det_off, m + 1); const auto d_dets = b.in(dets, 6 * nd);
+    const auto d_tab = b.inout(tab.data(), TAB * m); const auto d_n = b.inout(n0.data(), m); const auto d_id = b.inout(next_id, m);
+    const auto d_out = b.out<double>(OUT * m); const auto d_nout = b.out<int32_t>(m); const auto d_asg = b.out<int32_t>(nd);
+    const auto d_rec = b.out<double>(SD * m);
+    if ((rc = b.upload())) return rc;
+    hipLaunchKernelGGL(k_fleet_sim_tracker_eval, dim3((unsigned)m), dim3(64), 0, f->h->stream, d_par, d_adv, d_tick, d_cs, d_tab, d_n, d_id, d_doff, d_dets,
+                       d_out, d_nout, d_asg, d_rec);
     FLEET_TRY(f, hipGetLastError());
-    hipStream_t st = f->h->stream;
-    FLEET_TRY(f, hipMemcpyAsync(tracks_out, d + o_tab, 8 * TAB * m, hipMemcpyDeviceToHost, st));
-    FLEET_TRY(f, hipMemcpyAsync(n_tracks_out, d + o_n, 4 * m, hipMemcpyDeviceToHost, st));
-    FLEET_TRY(f, hipMemcpyAsync(next_id_out, d + o_id, 8 * m, hipMemcpyDeviceToHost, st));
-    FLEET_TRY(f, hipMemcpyAsync(out, d + o_out, 8 * OUT * m, hipMemcpyDeviceToHost, st));
-    FLEET_TRY(f, hipMemcpyAsync(n_out, d + o_nout, 4 * m, hipMemcpyDeviceToHost, st));
-    FLEET_TRY(f, hipMemcpyAsync(rec, d + o_rec, 8 * SD * m, hipMemcpyDeviceToHost, st));
-    if (nd) FLEET_TRY(f, hipMemcpyAsync(assign, d + o_asg, 4 * nd, hipMemcpyDeviceToHost, st));
-    FLEET_TRY(f, hipStreamSynchronize(st));
+    if ((rc = b.fetch(tracks_out, d_tab, TAB * m))) return rc;
+    if ((rc = b.fetch(n_tracks_out, d_n, m))) return rc;
+    if ((rc = b.fetch(next_id_out, d_id, m))) return rc;
+    if ((rc = b.fetch(out, d_out, OUT * m))) return rc;
+    if ((rc = b.fetch(n_out, d_nout, m))) return rc;
+    if ((rc = b.fetch(rec, d_rec, SD * m))) return rc;
+    if ((rc = b.fetch(assign, d_asg, nd))) return rc;
+    if ((rc = b.finish())) return rc;
     for (size_t q = 0; q < m; ++q)          // (rows behind the new count hold what the compaction left there)
         for (size_t c = (size_t)(n_tracks_out[q] > 0 ? n_tracks_out[q] : 0) * RD; c < TAB; ++c) tracks_out[q * TAB + c] = NAN;
     return LTPL_OK;
@@ -2893,8 +2904,10 @@ try {
 // ---------------------------------------------------------------------------------------------------------------------
 // prediction model (ltpl_fleet_sim_predictor, include/ltpl_hip.h; the rule: fleet_predict.hpp)
 // ---------------------------------------------------------------------------------------------------------------------
-static bool sim_pred_params_ok(double mode, double horizon, double relax, double d_max, std::string* why)
+// q[PRD_PARAMS] = mode, horizon, relax, d_max
+static bool sim_pred_params_ok(const double* q, std::string* why)
 {
+    const double mode = q[0], horizon = q[1], relax = q[2], d_max = q[3];
     if (!(mode == 0.0 || mode == 1.0 || mode == 2.0)) { *why = "mode must be 0, 1 or 2"; return false; }
     if (!std::isfinite(horizon) || !(horizon > 0.0)) { *why = "horizon must be finite and positive"; return false; }
     if (!(relax >= 0.0) || !(relax <= 1.0)) { *why = "relax must lie in [0, 1]"; return false; }
@@ -2903,21 +2916,16 @@ static bool sim_pred_params_ok(double mode, double horizon, double relax, double
 }
 
 // every argument is checked before the first HIP call
-static int sim_check_predictor(ltpl_fleet* f, const ltpl_fleet_sim_predictor_in* in)
+static int sim_check_predictor(ltpl_fleet* f, const ltpl_fleet_sim_predictor_in* in, std::vector<double>* par)
 {
     const int N = f->D.N;
     auto bad = [&](const std::string& why, int code = LTPL_ERR_INVALID_ARG) { f->err = "fleet sim predictor: " + why; return code; };
     if (!f->sim) return bad("ltpl_fleet_sim_setup first");
     if (!in) return LTPL_OK;
     if (in->n_points < 1 || in->n_points > LTPL_FLEET_SIM_PREDICTOR_MAX_POINTS) return bad("n_points must lie in 1 .. 8");
-    if (!in->mode) return bad("mode missing");
-    if (!in->horizon) return bad("horizon missing");
-    if (!in->relax) return bad("relax missing");
-    if (!in->d_max) return bad("d_max missing");
-    for (int p = 0; p < N; ++p) {
-        std::string why;
-        if (!sim_pred_params_ok((double)in->mode[p], in->horizon[p], in->relax[p], in->d_max[p], &why)) return bad("planner " + std::to_string(p) + ": " + why);
-    }
+    const SimCol col[PRD_PARAMS] = {{"mode", in->mode}, {"horizon", in->horizon}, {"relax", in->relax}, {"d_max", in->d_max}};
+    if (int rc = sim_param_table(f, "predictor", col, sim_no_head, [](int, const double* q, std::string* why) { return sim_pred_params_ok(q, why); }, par))
+        return rc;
     // the path kernel's per-position arrays hold MAX_POS entries and the simulation hands its objects on without the per-call check
     for (int p = 0; p < N; ++p)
         if (f->sim->slots[(size_t)p] * (1 + in->n_points) > MAX_POS)
@@ -2929,28 +2937,23 @@ static int sim_check_predictor(ltpl_fleet* f, const ltpl_fleet_sim_predictor_in*
 extern "C" int ltpl_fleet_sim_predictor(ltpl_fleet* f, const ltpl_fleet_sim_predictor_in* in)
 try {
     if (!f) return LTPL_ERR_INVALID_ARG;
-    int rc = sim_check_predictor(f, in);
+    std::vector<double> par;
+    int rc = sim_check_predictor(f, in, &par);
     if (rc) return rc;
     if ((rc = fleet_enter(f))) return rc;
     FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
     FleetSim& s = *f->sim;
-    if (!in && !s.has_pred) return LTPL_OK;
+    if (!in && !s.pred.on) return LTPL_OK;
     // everything new is allocated first; the fleet keeps its previous predictor, its staging and its records unless every step succeeds
     const int stride = in ? 1 + in->n_points : 2;
     SimStage st;
     if ((rc = sim_stage_alloc(f, s.slots, stride, &st))) return rc;
     if (!in) {
         sim_stage_commit(&s, &st);
-        sim_free_list(s.pred_allocs);
-        s.pd = SimPred{}; s.has_pred = false;
+        s.pred.clear();
         return LTPL_OK;
     }
     const size_t N = (size_t)f->D.N;
-    std::vector<double> par(N * PRD_PARAMS);
-    for (size_t p = 0; p < N; ++p) {
-        double* q = &par[p * PRD_PARAMS];
-        q[0] = (double)in->mode[p]; q[1] = in->horizon[p]; q[2] = in->relax[p]; q[3] = in->d_max[p];
-    }
     SimAllocs al;
     SimPred pd{};
     double* d_par = nullptr;
@@ -2958,24 +2961,15 @@ try {
     if ((rc = sim_upload(f, al.p, (const double*)nullptr, N * LTPL_FLEET_SIM_PREDICTOR_DOUBLES, &pd.rec))) return rc;
     pd.par = d_par; pd.K = in->n_points;
     sim_stage_commit(&s, &st);
-    sim_free_list(s.pred_allocs);
-    s.pred_allocs.swap(al.p);
-    s.pd = pd; s.has_pred = true;
+    s.pred.commit(al, pd);
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))
 
 extern "C" int ltpl_fleet_sim_predictor_read(ltpl_fleet* f, double* out, int32_t doubles_per_planner)
 try {
     if (!f) return LTPL_ERR_INVALID_ARG;
-    auto bad = [&](const std::string& why) { f->err = "fleet sim predictor: " + why; return LTPL_ERR_INVALID_ARG; };
-    if (!f->sim) return bad("ltpl_fleet_sim_setup first");
-    if (!f->sim->has_pred) return bad("the predictor is off (ltpl_fleet_sim_predictor first)");
-    if (!out) return bad("out missing");
-    if (doubles_per_planner != LTPL_FLEET_SIM_PREDICTOR_DOUBLES) return bad("record size mismatch");
-    FLEET_TRY(f, hipSetDevice(f->h->device));
-    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
-    FLEET_TRY(f, hipMemcpy(out, f->sim->pd.rec, sizeof(double) * (size_t)f->D.N * LTPL_FLEET_SIM_PREDICTOR_DOUBLES, hipMemcpyDeviceToHost));
-    return LTPL_OK;
+    return sim_read_records(f, "predictor", &FleetSim::pred, "the predictor is off (ltpl_fleet_sim_predictor first)", out, doubles_per_planner,
+                            LTPL_FLEET_SIM_PREDICTOR_DOUBLES);
 } LTPL_ABI_CATCH(abi_err_of(f))
 
 extern "C" int ltpl_fleet_sim_predictor_eval(ltpl_fleet* f, int32_t n_cases, int32_t n_points, const double* params, const int32_t* obj_off,
@@ -2993,37 +2987,28 @@ try {
         const std::string who = "case " + std::to_string(q) + ": ";
         const int n = obj_off[q + 1] - obj_off[q];
         if (n < 0 || n > SIM_OBJ_CAP) return bad(who + "0 .. 96 objects");
-        const double* P = params + (size_t)q * PRD_PARAMS;
         std::string why;
-        if (!sim_pred_params_ok(P[0], P[1], P[2], P[3], &why)) return bad(who + why);
+        if (!sim_pred_params_ok(params + (size_t)q * PRD_PARAMS, &why)) return bad(who + why);
     }
     const size_t m = (size_t)n_cases, no = (size_t)obj_off[n_cases], K = (size_t)n_points;
     if (no > 0 && (!objs || !points || !outcome)) return bad("objs / points / outcome missing");
     constexpr size_t PER = (size_t)SIM_OBJ_CAP * (1 + LTPL_FLEET_SIM_PREDICTOR_MAX_POINTS), SD = LTPL_FLEET_SIM_PREDICTOR_DOUBLES;
     int rc = fleet_enter(f);
     if (rc) return rc;
-    Arena ar;     // one device block
-    const size_t o_par = ar.add(8 * PRD_PARAMS * m), o_objs = ar.add(40 * (no ? no : 1)), o_x = ar.add(8 * PER * m), o_y = ar.add(8 * PER * m),
-                 o_rec = ar.add(8 * SD * m), o_off = ar.add(4 * (m + 1)), o_oc = ar.add(4 * (no ? no : 1));
-    unsigned char* d = nullptr;
-    struct Guard { void* a = nullptr; ~Guard() { if (a) (void)hipFree(a); } } gd;
-    FLEET_TRY(f, hipMalloc(reinterpret_cast<void**>(&d), ar.size)); gd.a = d;
-    FLEET_TRY(f, hipMemset(d, 0, ar.size));
-    FLEET_TRY(f, hipMemcpy(d + o_par, params, 8 * PRD_PARAMS * m, hipMemcpyHostToDevice));
-    if (no) FLEET_TRY(f, hipMemcpy(d + o_objs, objs, 40 * no, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_off, obj_off, 4 * (m + 1), hipMemcpyHostToDevice));
-    hipStream_t st = f->h->stream;
-    FLEET_TRY(f, hipStreamSynchronize(st));
-    hipLaunchKernelGGL(k_fleet_sim_predictor_eval, dim3((unsigned)m), dim3(64), 0, st, f->sim->sd, (const double*)(d + o_par), n_points, (const int*)(d + o_off),
-                       (const double*)(d + o_objs), reinterpret_cast<double*>(d + o_x), reinterpret_cast<double*>(d + o_y), reinterpret_cast<int*>(d + o_oc),
-                       reinterpret_cast<double*>(d + o_rec));
+    SimHookBlock b(f);
+    const auto d_par = b.in(params, PRD_PARAMS * m); const auto d_off = b.in(obj_off, m + 1); const auto d_objs = b.in(objs, 5 * no);
+    const auto d_x = b.out<double>(PER * m); const auto d_y = b.out<double>(PER * m); const auto d_oc = b.out<int32_t>(no);
+    const auto d_rec = b.out<double>(SD * m);
+    if ((rc = b.upload())) return rc;
+    hipLaunchKernelGGL(k_fleet_sim_predictor_eval, dim3((unsigned)m), dim3(64), 0, f->h->stream, f->sim->sd, d_par, n_points, d_off, d_objs, d_x, d_y, d_oc,
+                       d_rec);
     FLEET_TRY(f, hipGetLastError());
     std::vector<double> hx(PER * m), hy(PER * m);
-    FLEET_TRY(f, hipMemcpyAsync(hx.data(), d + o_x, 8 * PER * m, hipMemcpyDeviceToHost, st));
-    FLEET_TRY(f, hipMemcpyAsync(hy.data(), d + o_y, 8 * PER * m, hipMemcpyDeviceToHost, st));
-    FLEET_TRY(f, hipMemcpyAsync(rec, d + o_rec, 8 * SD * m, hipMemcpyDeviceToHost, st));
-    if (no) FLEET_TRY(f, hipMemcpyAsync(outcome, d + o_oc, 4 * no, hipMemcpyDeviceToHost, st));
-    FLEET_TRY(f, hipStreamSynchronize(st));
+    if ((rc = b.fetch(hx.data(), d_x, PER * m))) return rc;
+    if ((rc = b.fetch(hy.data(), d_y, PER * m))) return rc;
+    if ((rc = b.fetch(rec, d_rec, SD * m))) return rc;
+    if ((rc = b.fetch(outcome, d_oc, no))) return rc;
+    if ((rc = b.finish())) return rc;
     // points[object][1 + n_points][2]: the device's layout of the tick (own position, then the K points), objects in case order
     for (size_t q = 0; q < m; ++q)
         for (size_t i = 0, n = (size_t)(obj_off[q + 1] - obj_off[q]); i < n; ++i)
@@ -3050,25 +3035,13 @@ static bool sim_sel_params_ok(const double* q, std::string* why)
 // every argument is checked before the first HIP call
 static int sim_check_selector(ltpl_fleet* f, const ltpl_fleet_sim_selector_in* in, std::vector<double>* par)
 {
-    const int N = f->D.N;
     auto bad = [&](const std::string& why) { f->err = "fleet sim selector: " + why; return LTPL_ERR_INVALID_ARG; };
     if (!f->sim) return bad("ltpl_fleet_sim_setup first");
     if (!in) return LTPL_OK;
     if (!in->on) return bad("on missing");
-    if (!in->horizon) return bad("horizon missing");
-    if (!in->r_ego) return bad("r_ego missing");
-    if (!in->c_hard) return bad("c_hard missing");
-    if (!in->c_soft) return bad("c_soft missing");
-    if (!in->w_clear) return bad("w_clear missing");
-    if (!in->w_switch) return bad("w_switch missing");
-    par->resize((size_t)N * SLC_PARAMS);
-    for (int p = 0; p < N; ++p) {
-        double* q = &(*par)[(size_t)p * SLC_PARAMS];
-        q[0] = in->horizon[p]; q[1] = in->r_ego[p]; q[2] = in->c_hard[p]; q[3] = in->c_soft[p]; q[4] = in->w_clear[p]; q[5] = in->w_switch[p];
-        std::string why;
-        if (!sim_sel_params_ok(q, &why)) return bad("planner " + std::to_string(p) + ": " + why);
-    }
-    return LTPL_OK;
+    const SimCol col[SLC_PARAMS] = {{"horizon", in->horizon}, {"r_ego", in->r_ego}, {"c_hard", in->c_hard}, {"c_soft", in->c_soft}, {"w_clear", in->w_clear},
+                                    {"w_switch", in->w_switch}};
+    return sim_param_table(f, "selector", col, sim_no_head, [](int, const double* q, std::string* why) { return sim_sel_params_ok(q, why); }, par);
 }
 
 extern "C" int ltpl_fleet_sim_selector(ltpl_fleet* f, const ltpl_fleet_sim_selector_in* in)
@@ -3081,8 +3054,7 @@ try {
     FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
     FleetSim& s = *f->sim;
     if (!in) {
-        sim_free_list(s.sel_allocs);
-        s.sl = SimSel{}; s.has_sel = false;
+        s.sel.clear();
         return LTPL_OK;
     }
     // everything new is allocated first; the fleet keeps its previous selector and its records unless every step succeeds
@@ -3100,9 +3072,7 @@ try {
     if ((rc = sim_upload(f, al.p, rec.data(), rec.size(), &sl.rec))) return rc;
     FLEET_TRY(f, hipMemcpy(sl.ord, s.sd.pref, sizeof(int) * n_pref, hipMemcpyDeviceToDevice));     // until the first tick: the user's lists
     sl.par = d_par; sl.on = d_on;
-    sim_free_list(s.sel_allocs);
-    s.sel_allocs.swap(al.p);
-    s.sl = sl; s.has_sel = true;
+    s.sel.commit(al, sl);
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))
 
@@ -3110,17 +3080,15 @@ extern "C" int ltpl_fleet_sim_selector_read(ltpl_fleet* f, double* out, int32_t 
 try {
     if (!f) return LTPL_ERR_INVALID_ARG;
     auto bad = [&](const std::string& why) { f->err = "fleet sim selector: " + why; return LTPL_ERR_INVALID_ARG; };
-    if (!f->sim) return bad("ltpl_fleet_sim_setup first");
-    if (!f->sim->has_sel) return bad("the selector is off (ltpl_fleet_sim_selector first)");
-    if (!out) return bad("out missing");
-    if (doubles_per_planner != LTPL_FLEET_SIM_SELECTOR_DOUBLES) return bad("record size mismatch");
-    const size_t N = (size_t)f->D.N;
-    if (ordered && n_ordered != f->sim->pref_off[N])
-        return bad("n_ordered is " + std::to_string(n_ordered) + ", the preference lists hold " + std::to_string(f->sim->pref_off[N]) + " entries");
-    FLEET_TRY(f, hipSetDevice(f->h->device));
-    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
-    FLEET_TRY(f, hipMemcpy(out, f->sim->sl.rec, sizeof(double) * N * LTPL_FLEET_SIM_SELECTOR_DOUBLES, hipMemcpyDeviceToHost));
-    if (ordered) FLEET_TRY(f, hipMemcpy(ordered, f->sim->sl.ord, sizeof(int) * (size_t)f->sim->pref_off[N], hipMemcpyDeviceToHost));
+    int rc = sim_read_records(f, "selector", &FleetSim::sel, "the selector is off (ltpl_fleet_sim_selector first)", out, "out", doubles_per_planner,
+                              LTPL_FLEET_SIM_SELECTOR_DOUBLES, [&] {
+        const int n_pref = f->sim->pref_off[(size_t)f->D.N];
+        if (ordered && n_ordered != n_pref)
+            return bad("n_ordered is " + std::to_string(n_ordered) + ", the preference lists hold " + std::to_string(n_pref) + " entries");
+        return LTPL_OK;
+    });
+    if (rc) return rc;
+    if (ordered) FLEET_TRY(f, hipMemcpy(ordered, f->sim->sel.dev.ord, sizeof(int) * (size_t)n_ordered, hipMemcpyDeviceToHost));
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))
 
@@ -3151,32 +3119,18 @@ try {
     constexpr size_t RW = (size_t)A * 4 * LTPL_FLEET_SIM_MAX_EXPORT, SD = LTPL_FLEET_SIM_SELECTOR_DOUBLES, MP = LTPL_FLEET_SIM_MAX_PREF;
     int rc = fleet_enter(f);
     if (rc) return rc;
-    Arena ar;     // one device block
-    const size_t o_par = ar.add(8 * SLC_PARAMS * m), o_rows = ar.add(8 * RW * m), o_objs = ar.add(40 * (no ? no : 1)), o_rec = ar.add(8 * SD * m),
-                 o_act = ar.add(sizeof(fleet::SelAct) * A * m), o_li = ar.add(32 * m), o_nr = ar.add(4 * A * m), o_off = ar.add(4 * (m + 1)),
-                 o_ord = ar.add(4 * MP * m);
-    unsigned char* d = nullptr;
-    struct Guard { void* a = nullptr; ~Guard() { if (a) (void)hipFree(a); } } gd;
-    FLEET_TRY(f, hipMalloc(reinterpret_cast<void**>(&d), ar.size)); gd.a = d;
-    FLEET_TRY(f, hipMemset(d, 0, ar.size));
-    FLEET_TRY(f, hipMemcpy(d + o_par, params, 8 * SLC_PARAMS * m, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_rows, rows, 8 * RW * m, hipMemcpyHostToDevice));
-    if (no) FLEET_TRY(f, hipMemcpy(d + o_objs, objs, 40 * no, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_rec, rec, 8 * SD * m, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_li, lists, 32 * m, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_nr, n_rows, 4 * A * m, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_off, obj_off, 4 * (m + 1), hipMemcpyHostToDevice));
-    hipStream_t st = f->h->stream;
-    FLEET_TRY(f, hipStreamSynchronize(st));
-    hipLaunchKernelGGL(k_fleet_sim_selector_eval, dim3((unsigned)m), dim3(64), 0, st, (const double*)(d + o_par), (const int*)(d + o_li), (const int*)(d + o_nr),
-                       (const double*)(d + o_rows), (const int*)(d + o_off), (const double*)(d + o_objs), reinterpret_cast<int*>(d + o_ord),
-                       reinterpret_cast<fleet::SelAct*>(d + o_act), reinterpret_cast<double*>(d + o_rec));
+    SimHookBlock b(f);
+    const auto d_par = b.in(params, SLC_PARAMS * m); const auto d_li = b.in(lists, 8 * m); const auto d_nr = b.in(n_rows, A * m);
+    const auto d_rows = b.in(rows, RW * m); const auto d_off = b.in(obj_off, m + 1); const auto d_objs = b.in(objs, 5 * no);
+    const auto d_ord = b.out<int32_t>(MP * m); const auto d_act = b.out<fleet::SelAct>(A * m); const auto d_rec = b.inout(rec, SD * m);
+    if ((rc = b.upload())) return rc;
+    hipLaunchKernelGGL(k_fleet_sim_selector_eval, dim3((unsigned)m), dim3(64), 0, f->h->stream, d_par, d_li, d_nr, d_rows, d_off, d_objs, d_ord, d_act, d_rec);
     FLEET_TRY(f, hipGetLastError());
     std::vector<fleet::SelAct> act(A * m);
-    FLEET_TRY(f, hipMemcpyAsync(act.data(), d + o_act, sizeof(fleet::SelAct) * A * m, hipMemcpyDeviceToHost, st));
-    FLEET_TRY(f, hipMemcpyAsync(rec, d + o_rec, 8 * SD * m, hipMemcpyDeviceToHost, st));
-    FLEET_TRY(f, hipMemcpyAsync(ordered, d + o_ord, 4 * MP * m, hipMemcpyDeviceToHost, st));
-    FLEET_TRY(f, hipStreamSynchronize(st));
+    if ((rc = b.fetch(act.data(), d_act, A * m))) return rc;
+    if ((rc = b.fetch(rec, d_rec, SD * m))) return rc;
+    if ((rc = b.fetch(ordered, d_ord, MP * m))) return rc;
+    if ((rc = b.finish())) return rc;
     for (size_t i = 0; i < A * m; ++i) {
         act_d[3 * i] = act[i].vbar; act_d[3 * i + 1] = act[i].clear; act_d[3 * i + 2] = act[i].J;
         act_i[2 * i] = act[i].clear_obj; act_i[2 * i + 1] = act[i].flags;
@@ -3200,25 +3154,18 @@ static bool sim_safety_params_ok(const double* q, std::string* why)
 // every argument is checked before the first HIP call
 static int sim_check_safety(ltpl_fleet* f, const ltpl_fleet_sim_safety_in* in, std::vector<double>* par)
 {
-    const int N = f->D.N;
     auto bad = [&](const std::string& why) { f->err = "fleet sim safety: " + why; return LTPL_ERR_INVALID_ARG; };
     if (!f->sim) return bad("ltpl_fleet_sim_setup first");
     if (!in) return LTPL_OK;
-    const double* a[SAF_PARAMS] = {in->r_ego, in->ttc_thr, in->drac_thr, in->thw_thr, in->margin};
-    static const char* const name[SAF_PARAMS] = {"r_ego", "ttc_thr", "drac_thr", "thw_thr", "margin"};
     if (!in->on) return bad("on missing");
-    for (int c = 0; c < SAF_PARAMS; ++c) if (!a[c]) return bad(std::string(name[c]) + " missing");
-    if (in->tick0 < 0) return bad("tick0 must not be negative");
-    if (in->flags & ~(uint32_t)LTPL_SIM_SAFETY_KEEP_STATE) return bad("unknown flag");
-    par->resize((size_t)N * SAF_PARAMS);
-    for (int p = 0; p < N; ++p) {
-        if (in->on[p] != 0 && in->on[p] != 1) return bad("planner " + std::to_string(p) + ": on must be 0 or 1");
-        double* q = &(*par)[(size_t)p * SAF_PARAMS];
-        for (int c = 0; c < SAF_PARAMS; ++c) q[c] = a[c][p];
-        std::string why;
-        if (!sim_safety_params_ok(q, &why)) return bad("planner " + std::to_string(p) + ": " + why);
-    }
-    return LTPL_OK;
+    const SimCol col[SAF_PARAMS] = {{"r_ego", in->r_ego}, {"ttc_thr", in->ttc_thr}, {"drac_thr", in->drac_thr}, {"thw_thr", in->thw_thr}, {"margin", in->margin}};
+    auto head = [&]() -> const char* {
+        return in->tick0 < 0 ? "tick0 must not be negative" : (in->flags & ~(uint32_t)LTPL_SIM_SAFETY_KEEP_STATE) ? "unknown flag" : nullptr;
+    };
+    return sim_param_table(f, "safety", col, head, [&](int p, const double* q, std::string* why) {
+        if (in->on[p] != 0 && in->on[p] != 1) { *why = "on must be 0 or 1"; return false; }
+        return sim_safety_params_ok(q, why);
+    }, par);
 }
 
 extern "C" int ltpl_fleet_sim_safety(ltpl_fleet* f, const ltpl_fleet_sim_safety_in* in)
@@ -3231,17 +3178,16 @@ try {
     FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
     FleetSim& s = *f->sim;
     if (!in) {
-        sim_free_list(s.saf_allocs);
-        s.sf = SimSafety{}; s.has_saf = false; s.saf_tick0 = s.saf_tick = 0;
+        s.saf.clear();
         return LTPL_OK;
     }
     const size_t N = (size_t)f->D.N;
     constexpr size_t RD = LTPL_FLEET_SIM_SAFETY_DOUBLES, RI = SAF_RING;
-    const bool keep = (in->flags & LTPL_SIM_SAFETY_KEEP_STATE) && s.has_saf;
+    const bool keep = (in->flags & LTPL_SIM_SAFETY_KEEP_STATE) && s.saf.on;
     std::vector<double> rec(N * RD), inc(N * RI);
     if (keep) {
-        FLEET_TRY(f, hipMemcpy(rec.data(), s.sf.rec, 8 * N * RD, hipMemcpyDeviceToHost));
-        FLEET_TRY(f, hipMemcpy(inc.data(), s.sf.inc, 8 * N * RI, hipMemcpyDeviceToHost));
+        FLEET_TRY(f, hipMemcpy(rec.data(), s.saf.dev.rec, 8 * N * RD, hipMemcpyDeviceToHost));
+        FLEET_TRY(f, hipMemcpy(inc.data(), s.saf.dev.inc, 8 * N * RI, hipMemcpyDeviceToHost));
     } else {
         for (size_t p = 0; p < N; ++p) fleet::safety_start(rec.data() + p * RD, inc.data() + p * RI);
     }
@@ -3254,9 +3200,7 @@ try {
     if ((rc = sim_upload(f, al.p, rec.data(), rec.size(), &sf.rec))) return rc;
     if ((rc = sim_upload(f, al.p, inc.data(), inc.size(), &sf.inc))) return rc;
     sf.par = d_par; sf.on = d_on;
-    sim_free_list(s.saf_allocs);
-    s.saf_allocs.swap(al.p);
-    s.sf = sf; s.has_saf = true; s.saf_tick0 = in->tick0; s.saf_tick = 0;
+    s.saf.commit(al, sf, in->tick0);
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))
 
@@ -3264,16 +3208,13 @@ extern "C" int ltpl_fleet_sim_safety_read(ltpl_fleet* f, double* out, int32_t do
 try {
     if (!f) return LTPL_ERR_INVALID_ARG;
     auto bad = [&](const std::string& why) { f->err = "fleet sim safety: " + why; return LTPL_ERR_INVALID_ARG; };
-    if (!f->sim) return bad("ltpl_fleet_sim_setup first");
-    if (!f->sim->has_saf) return bad("the monitor is off (ltpl_fleet_sim_safety first)");
-    if (!out) return bad("out missing");
-    if (doubles_per_planner != LTPL_FLEET_SIM_SAFETY_DOUBLES) return bad("record size mismatch");
-    if (incidents && doubles_per_incident != LTPL_FLEET_SIM_SAFETY_INCIDENT_DOUBLES) return bad("incident size mismatch");
-    const size_t N = (size_t)f->D.N;
-    FLEET_TRY(f, hipSetDevice(f->h->device));
-    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
-    FLEET_TRY(f, hipMemcpy(out, f->sim->sf.rec, sizeof(double) * N * LTPL_FLEET_SIM_SAFETY_DOUBLES, hipMemcpyDeviceToHost));
-    if (incidents) FLEET_TRY(f, hipMemcpy(incidents, f->sim->sf.inc, sizeof(double) * N * SAF_RING, hipMemcpyDeviceToHost));
+    int rc = sim_read_records(f, "safety", &FleetSim::saf, "the monitor is off (ltpl_fleet_sim_safety first)", out, "out", doubles_per_planner,
+                              LTPL_FLEET_SIM_SAFETY_DOUBLES, [&] {
+        if (incidents && doubles_per_incident != LTPL_FLEET_SIM_SAFETY_INCIDENT_DOUBLES) return bad("incident size mismatch");
+        return LTPL_OK;
+    });
+    if (rc) return rc;
+    if (incidents) FLEET_TRY(f, hipMemcpy(incidents, f->sim->saf.dev.inc, sizeof(double) * (size_t)f->D.N * SAF_RING, hipMemcpyDeviceToHost));
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))
 
@@ -3300,35 +3241,20 @@ try {
     constexpr size_t RD = LTPL_FLEET_SIM_SAFETY_DOUBLES, RI = SAF_RING;
     int rc = fleet_enter(f);
     if (rc) return rc;
-    Arena ar;     // one device block
-    const size_t o_pose = ar.add(16 * m), o_dt = ar.add(8 * m), o_par = ar.add(8 * SAF_PARAMS * m), o_objs = ar.add(40 * (no ? no : 1)),
-                 o_rec = ar.add(8 * RD * m), o_inc = ar.add(8 * RI * m), o_po = ar.add(48 * (no ? no : 1)), o_pt = ar.add(64 * m), o_tick = ar.add(4 * m),
-                 o_off = ar.add(4 * (m + 1));
-    unsigned char* d = nullptr;
-    struct Guard { void* a = nullptr; ~Guard() { if (a) (void)hipFree(a); } } gd;
-    FLEET_TRY(f, hipMalloc(reinterpret_cast<void**>(&d), ar.size)); gd.a = d;
-    FLEET_TRY(f, hipMemset(d, 0, ar.size));
-    FLEET_TRY(f, hipMemcpy(d + o_pose, pose, 16 * m, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_dt, dt, 8 * m, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_par, params, 8 * SAF_PARAMS * m, hipMemcpyHostToDevice));
-    if (no) FLEET_TRY(f, hipMemcpy(d + o_objs, objs, 40 * no, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_rec, rec, 8 * RD * m, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_inc, inc, 8 * RI * m, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_tick, tick, 4 * m, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_off, obj_off, 4 * (m + 1), hipMemcpyHostToDevice));
-    hipStream_t st = f->h->stream;
-    FLEET_TRY(f, hipStreamSynchronize(st));
-    hipLaunchKernelGGL(k_fleet_sim_safety_eval, dim3((unsigned)m), dim3(64), 0, st, (const double*)(d + o_pose), (const double*)(d + o_dt),
-                       (const int*)(d + o_tick), (const double*)(d + o_par), (const int*)(d + o_off), (const double*)(d + o_objs),
-                       reinterpret_cast<double*>(d + o_rec), reinterpret_cast<double*>(d + o_inc), reinterpret_cast<double*>(d + o_po),
-                       reinterpret_cast<double*>(d + o_pt));
+    SimHookBlock b(f);
+    const auto d_pose = b.in(pose, 2 * m); const auto d_dt = b.in(dt, m); const auto d_tick = b.in(tick, m); const auto d_par = b.in(params, SAF_PARAMS * m);
+    const auto d_off = b.in(obj_off, m + 1); const auto d_objs = b.in(objs, 5 * no);
+    const auto d_rec = b.inout(rec, RD * m); const auto d_inc = b.inout(inc, RI * m);
+    const auto d_po = b.out<double>(6 * no); const auto d_pt = b.out<double>(8 * m);
+    if ((rc = b.upload())) return rc;
+    hipLaunchKernelGGL(k_fleet_sim_safety_eval, dim3((unsigned)m), dim3(64), 0, f->h->stream, d_pose, d_dt, d_tick, d_par, d_off, d_objs, d_rec, d_inc, d_po,
+                       d_pt);
     FLEET_TRY(f, hipGetLastError());
-    FLEET_TRY(f, hipMemcpyAsync(rec, d + o_rec, 8 * RD * m, hipMemcpyDeviceToHost, st));
-    FLEET_TRY(f, hipMemcpyAsync(inc, d + o_inc, 8 * RI * m, hipMemcpyDeviceToHost, st));
-    FLEET_TRY(f, hipMemcpyAsync(per_tick, d + o_pt, 64 * m, hipMemcpyDeviceToHost, st));
-    if (no) FLEET_TRY(f, hipMemcpyAsync(per_obj, d + o_po, 48 * no, hipMemcpyDeviceToHost, st));
-    FLEET_TRY(f, hipStreamSynchronize(st));
-    return LTPL_OK;
+    if ((rc = b.fetch(rec, d_rec, RD * m))) return rc;
+    if ((rc = b.fetch(inc, d_inc, RI * m))) return rc;
+    if ((rc = b.fetch(per_tick, d_pt, 8 * m))) return rc;
+    if ((rc = b.fetch(per_obj, d_po, 6 * no))) return rc;
+    return b.finish();
 } LTPL_ABI_CATCH(abi_err_of(f))
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -3351,26 +3277,21 @@ static bool sim_react_params_ok(const double* q, std::string* why)
 // every argument is checked before the first HIP call; *any_on: some planner has on == 1
 static int sim_check_react(ltpl_fleet* f, const ltpl_fleet_sim_react_in* in, std::vector<double>* par, bool* any_on)
 {
-    const int N = f->D.N;
     auto bad = [&](const std::string& why) { f->err = "fleet sim react: " + why; return LTPL_ERR_INVALID_ARG; };
     *any_on = false;
     if (!f->sim) return bad("ltpl_fleet_sim_setup first");
     if (!in) return LTPL_OK;
-    const double* a[RCT_PARAMS] = {nullptr, in->a_max, in->b_comf, in->b_max, in->headway, in->gap0, in->look, in->lat_gate, in->ego_len};
-    if (!in->on) return bad("on missing");
-    for (int c = 1; c < RCT_PARAMS; ++c) if (!a[c]) return bad(std::string(kReactParamName[c]) + " missing");
-    if (in->tick0 < 0) return bad("tick0 must not be negative");
-    if (in->flags & ~(uint32_t)LTPL_SIM_REACT_KEEP_STATE) return bad("unknown flag");
-    par->resize((size_t)N * RCT_PARAMS);
-    for (int p = 0; p < N; ++p) {
-        double* q = &(*par)[(size_t)p * RCT_PARAMS];
-        q[0] = (double)in->on[p];
-        for (int c = 1; c < RCT_PARAMS; ++c) q[c] = a[c][p];
-        std::string why;
-        if (!sim_react_params_ok(q, &why)) return bad("planner " + std::to_string(p) + ": " + why);
-        *any_on = *any_on || in->on[p] == 1;
-    }
-    return LTPL_OK;
+    const char* const* nm = kReactParamName;
+    const SimCol col[RCT_PARAMS] = {{nm[0], in->on}, {nm[1], in->a_max}, {nm[2], in->b_comf}, {nm[3], in->b_max}, {nm[4], in->headway}, {nm[5], in->gap0},
+                                    {nm[6], in->look}, {nm[7], in->lat_gate}, {nm[8], in->ego_len}};
+    auto head = [&]() -> const char* {
+        return in->tick0 < 0 ? "tick0 must not be negative" : (in->flags & ~(uint32_t)LTPL_SIM_REACT_KEEP_STATE) ? "unknown flag" : nullptr;
+    };
+    return sim_param_table(f, "react", col, head, [&](int, const double* q, std::string* why) {
+        if (!sim_react_params_ok(q, why)) return false;
+        *any_on = *any_on || q[0] == 1.0;
+        return true;
+    }, par);
 }
 
 extern "C" int ltpl_fleet_sim_react(ltpl_fleet* f, const ltpl_fleet_sim_react_in* in)
@@ -3384,17 +3305,16 @@ try {
     FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
     FleetSim& s = *f->sim;
     if (!in || !any_on) {
-        sim_free_list(s.react_allocs);
-        s.rc = SimReact{}; s.has_react = false; s.react_tick0 = s.react_tick = 0;
+        s.react.clear();
         return LTPL_OK;
     }
     const size_t N = (size_t)f->D.N, no = (size_t)s.n_opp;
     constexpr size_t RD = LTPL_FLEET_SIM_REACT_DOUBLES;
-    const bool keep = (in->flags & LTPL_SIM_REACT_KEEP_STATE) && s.has_react;
+    const bool keep = (in->flags & LTPL_SIM_REACT_KEEP_STATE) && s.react.on;
     std::vector<double> rec(N * RD), eff(no ? no : 1);
     if (keep) {
-        FLEET_TRY(f, hipMemcpy(rec.data(), s.rc.rec, 8 * N * RD, hipMemcpyDeviceToHost));
-        if (no) FLEET_TRY(f, hipMemcpy(eff.data(), s.rc.eff, 8 * no, hipMemcpyDeviceToHost));
+        FLEET_TRY(f, hipMemcpy(rec.data(), s.react.dev.rec, 8 * N * RD, hipMemcpyDeviceToHost));
+        if (no) FLEET_TRY(f, hipMemcpy(eff.data(), s.react.dev.eff, 8 * no, hipMemcpyDeviceToHost));
     } else {
         for (size_t p = 0; p < N; ++p) fleet::react_start(rec.data() + p * RD);
         if (no) FLEET_TRY(f, hipMemcpy(eff.data(), s.sd.opp_scale, 8 * no, hipMemcpyDeviceToHost));      // the start state: e = the configured c
@@ -3407,25 +3327,18 @@ try {
     if ((rc = sim_upload(f, al.p, eff.data(), no, &r.eff))) return rc;
     if ((rc = sim_upload(f, al.p, rec.data(), rec.size(), &r.rec))) return rc;
     r.par = d_par;
-    sim_free_list(s.react_allocs);
-    s.react_allocs.swap(al.p);
-    s.rc = r; s.has_react = true; s.react_tick0 = in->tick0; s.react_tick = 0;
+    s.react.commit(al, r, in->tick0);
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))
 
 extern "C" int ltpl_fleet_sim_react_read(ltpl_fleet* f, double* out, int32_t doubles_per_planner, double* eff_scale)
 try {
     if (!f) return LTPL_ERR_INVALID_ARG;
-    auto bad = [&](const std::string& why) { f->err = "fleet sim react: " + why; return LTPL_ERR_INVALID_ARG; };
-    if (!f->sim) return bad("ltpl_fleet_sim_setup first");
-    if (!f->sim->has_react) return bad("the model is off (ltpl_fleet_sim_react first)");
-    if (!out) return bad("out missing");
-    if (doubles_per_planner != LTPL_FLEET_SIM_REACT_DOUBLES) return bad("record size mismatch");
-    const size_t N = (size_t)f->D.N, no = (size_t)f->sim->n_opp;
-    FLEET_TRY(f, hipSetDevice(f->h->device));
-    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
-    FLEET_TRY(f, hipMemcpy(out, f->sim->rc.rec, sizeof(double) * N * LTPL_FLEET_SIM_REACT_DOUBLES, hipMemcpyDeviceToHost));
-    if (eff_scale && no) FLEET_TRY(f, hipMemcpy(eff_scale, f->sim->rc.eff, sizeof(double) * no, hipMemcpyDeviceToHost));
+    int rc = sim_read_records(f, "react", &FleetSim::react, "the model is off (ltpl_fleet_sim_react first)", out, doubles_per_planner,
+                              LTPL_FLEET_SIM_REACT_DOUBLES);
+    if (rc) return rc;
+    const size_t no = (size_t)f->sim->n_opp;
+    if (eff_scale && no) FLEET_TRY(f, hipMemcpy(eff_scale, f->sim->react.dev.eff, sizeof(double) * no, hipMemcpyDeviceToHost));
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))
 
@@ -3454,34 +3367,18 @@ try {
     constexpr size_t RD = LTPL_FLEET_SIM_REACT_DOUBLES;
     int rc = fleet_enter(f);
     if (rc) return rc;
-    Arena ar;     // one device block
-    const size_t n1 = no ? no : 1;
-    const size_t o_par = ar.add(8 * RCT_PARAMS * m), o_ego = ar.add(24 * m), o_dt = ar.add(8 * m), o_opp = ar.add(32 * n1), o_rec = ar.add(8 * RD * m),
-                 o_e = ar.add(8 * n1), o_po = ar.add(32 * n1), o_eo = ar.add(24 * m), o_tick = ar.add(4 * m), o_off = ar.add(4 * (m + 1));
-    unsigned char* d = nullptr;
-    struct Guard { void* a = nullptr; ~Guard() { if (a) (void)hipFree(a); } } gd;
-    FLEET_TRY(f, hipMalloc(reinterpret_cast<void**>(&d), ar.size)); gd.a = d;
-    FLEET_TRY(f, hipMemset(d, 0, ar.size));
-    FLEET_TRY(f, hipMemcpy(d + o_par, params, 8 * RCT_PARAMS * m, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_ego, ego, 24 * m, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_dt, dt, 8 * m, hipMemcpyHostToDevice));
-    if (no) FLEET_TRY(f, hipMemcpy(d + o_opp, opp, 32 * no, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_rec, rec, 8 * RD * m, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_tick, tick, 4 * m, hipMemcpyHostToDevice));
-    FLEET_TRY(f, hipMemcpy(d + o_off, opp_off, 4 * (m + 1), hipMemcpyHostToDevice));
-    hipStream_t st = f->h->stream;
-    FLEET_TRY(f, hipStreamSynchronize(st));
-    hipLaunchKernelGGL(k_fleet_sim_react_eval, dim3((unsigned)m), dim3(64), 0, st, f->sim->sd, (const double*)(d + o_par), (const double*)(d + o_ego),
-                       (const double*)(d + o_dt), (const int*)(d + o_tick), (const int*)(d + o_off), (const double*)(d + o_opp),
-                       reinterpret_cast<double*>(d + o_rec), reinterpret_cast<double*>(d + o_e), reinterpret_cast<double*>(d + o_po),
-                       reinterpret_cast<double*>(d + o_eo));
+    SimHookBlock b(f);
+    const auto d_par = b.in(params, RCT_PARAMS * m); const auto d_ego = b.in(ego, 3 * m); const auto d_dt = b.in(dt, m); const auto d_tick = b.in(tick, m);
+    const auto d_off = b.in(opp_off, m + 1); const auto d_opp = b.in(opp, 4 * no);
+    const auto d_rec = b.inout(rec, RD * m);
+    const auto d_e = b.out<double>(no); const auto d_po = b.out<double>(4 * no); const auto d_eo = b.out<double>(3 * m);
+    if ((rc = b.upload())) return rc;
+    hipLaunchKernelGGL(k_fleet_sim_react_eval, dim3((unsigned)m), dim3(64), 0, f->h->stream, f->sim->sd, d_par, d_ego, d_dt, d_tick, d_off, d_opp, d_rec, d_e,
+                       d_po, d_eo);
     FLEET_TRY(f, hipGetLastError());
-    FLEET_TRY(f, hipMemcpyAsync(rec, d + o_rec, 8 * RD * m, hipMemcpyDeviceToHost, st));
-    FLEET_TRY(f, hipMemcpyAsync(ego_out, d + o_eo, 24 * m, hipMemcpyDeviceToHost, st));
-    if (no) {
-        FLEET_TRY(f, hipMemcpyAsync(e_out, d + o_e, 8 * no, hipMemcpyDeviceToHost, st));
-        FLEET_TRY(f, hipMemcpyAsync(per_opp, d + o_po, 32 * no, hipMemcpyDeviceToHost, st));
-    }
-    FLEET_TRY(f, hipStreamSynchronize(st));
-    return LTPL_OK;
+    if ((rc = b.fetch(rec, d_rec, RD * m))) return rc;
+    if ((rc = b.fetch(ego_out, d_eo, 3 * m))) return rc;
+    if ((rc = b.fetch(e_out, d_e, no))) return rc;
+    if ((rc = b.fetch(per_opp, d_po, 4 * no))) return rc;
+    return b.finish();
 } LTPL_ABI_CATCH(abi_err_of(f))

@@ -9,56 +9,21 @@ results are not looked at -- only the return codes, the messages and the kernels
   - an allocation failing at any point of ltpl_fleet_friction leaves the fleet with its previous maps: LTPL_ERR_HIP, and the lookup on the
     old map still works."""
 import ctypes
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-from graphbasedlocaltrajectoryplanner_amd import _capi, sim                # noqa: E402
-from graphbasedlocaltrajectoryplanner_amd.fleet import Fleet, FrictionIn   # noqa: E402
-from graphbasedlocaltrajectoryplanner_amd.friction import FrictionGrid     # noqa: E402
-from graphbasedlocaltrajectoryplanner_amd.lattice import Lattice           # noqa: E402
+import sim_args_common as common
+from sim_args_common import launches_per_tick, msg, no_allocation
+from graphbasedlocaltrajectoryplanner_amd.fleet import FrictionIn
+from graphbasedlocaltrajectoryplanner_amd.friction import FrictionGrid
 
-FAKE = os.path.join(ROOT, "tools", "fakehip", "build" if "--san" in sys.argv else "build_plain", "libltpl_hip_fake.so")
 N = 4
-lat = Lattice.load(os.path.join(ROOT, "tests", "golden", "monteblanco_lattice.npz"))
-table = sim.RaceLineTable.from_track(np.load(os.path.join(ROOT, "tests", "golden", "monteblanco_track.npz")))
-hip = _capi.HipBackend(lat, lib_path=FAKE)
-lib = hip.lib
-lib.fakehip_launch_count.restype = ctypes.c_long
-lib.fakehip_fail_malloc_after.argtypes = [ctypes.c_long]
-lib.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
-lib.hipFree.argtypes = [ctypes.c_void_p]
-lib.ltpl_fleet_last_error.restype = ctypes.c_char_p
-lib.ltpl_fleet_last_error.argtypes = [ctypes.c_void_p]
+lib, fleet, table = common.start(N, "build" if "--san" in sys.argv else "build_plain")
 lib.ltpl_fleet_friction.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
 lib.ltpl_fleet_friction_scale.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
 lib.ltpl_fleet_friction_rows.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_void_p]
-fleet = Fleet(hip, N)
 h = fleet.handle
-
-
-def no_allocation(fn):
-    """Runs ``fn`` with an allocation failure armed for the next hipMalloc; asserts that ``fn`` did not allocate."""
-    lib.fakehip_fail_malloc_after(1)
-    try:
-        out = fn()
-    finally:
-        p = ctypes.c_void_p()
-        pending = lib.hipMalloc(ctypes.byref(p), 8) != 0
-        if not pending:
-            lib.hipFree(p)
-        lib.fakehip_fail_malloc_after(0)
-    assert pending, "a refused call allocated device memory"
-    return out
-
-
-def msg():
-    return (lib.ltpl_fleet_last_error(h) or b"").decode()
-
-
 GRIDS = [FrictionGrid(0.0, 0.0, 10.0, 10.0, np.full((3, 4), 4.0), np.full((3, 4), 3.0)),
          FrictionGrid(-5.0, 2.0, 1.0, 2.0, np.full((2, 2), 5.0), np.full((2, 2), 6.0))]
 
@@ -129,12 +94,6 @@ refused(1, "map_idx out of range", map_idx=[0, 1, -2, 0])
 good = dict(opponents=[(250.0, 0.3, 5.0)], pref=("right", "straight"), pos_est=(0.0, 0.0), zone_gids=[3])
 
 
-def launches_per_tick():
-    before = lib.fakehip_launch_count()
-    fleet.sim_run(1, trace=False)
-    return lib.fakehip_launch_count() - before
-
-
 fleet.sim_setup(table, [good] * N)
 fleet.sim_vel()
 plain = launches_per_tick()
@@ -166,22 +125,18 @@ fleet.friction(GRIDS, map_idx=[0, 1, -1, 1], scale=[1.0, 0.8, 1.0, 0.6])     # (
 assert launches_per_tick() == plain + 1
 
 # ---- an allocation failing at every point of ltpl_fleet_friction: the previous maps stay -------------------------------------------------
-fresh = Fleet(hip, N)                                       # (a fleet whose rows array does not exist yet: one allocation more)
+fresh = common.Fleet(common.hip, N)                         # (a fleet whose rows array does not exist yet: one allocation more)
 h_old, h = h, fresh.handle
+common.use_handle(h)
 one_map = [GRIDS[0]]
-failures = 0
-for k in range(1, 32):
-    lib.fakehip_fail_malloc_after(k)
-    rc = call()
-    lib.fakehip_fail_malloc_after(0)
-    if rc == 0:
-        break
-    assert rc == 3 and "hipMalloc" in msg(), (k, rc, msg())           # LTPL_ERR_HIP
-    failures += 1
-    # the cleared state is still in place: no map 0
+
+
+def no_map_0(k, _):
+    """The cleared state is still in place."""
     assert lib.ltpl_fleet_friction_rows(h, 0, x.ctypes.data, y.ctypes.data, 3, 1.0, out.ctypes.data) == 1
-else:
-    raise AssertionError("ltpl_fleet_friction never succeeded")
+
+
+failures = common.alloc_sweep("ltpl_fleet_friction", lambda: (call(), msg()), 32, no_map_0)
 assert failures == 5, failures                             # maps, nodes, map_idx, scale, the planners' rows
 fresh.friction(one_map)
 for k in range(1, 5):                                       # (the rows array exists by now)
@@ -194,7 +149,6 @@ for k in range(1, 5):                                       # (the rows array ex
 print("allocation failure at each of the %d allocations of ltpl_fleet_friction: previous maps kept" % failures)
 print("launches per tick: %d without a map, %d with" % (plain, plain + 1))
 h = h_old
+common.use_handle(h)
 fresh.close()
-fleet.close()
-hip.close()
-print("friction args OK")
+common.finish("friction args OK")

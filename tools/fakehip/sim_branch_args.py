@@ -10,58 +10,21 @@ messages, what ``info`` reports and the number of kernel launches:
   - an allocation failing at each allocation of ltpl_fleet_sim_snapshot leaves the slot's previous content and ``info`` unchanged;
   - a tick of ltpl_fleet_sim_run launches the same kernels with and without snapshots held; a snapshot and a branch are one launch each."""
 import ctypes
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-from graphbasedlocaltrajectoryplanner_amd import _capi, sim               # noqa: E402
-from graphbasedlocaltrajectoryplanner_amd.fleet import SIM_SNAPSHOTS, Fleet   # noqa: E402
-from graphbasedlocaltrajectoryplanner_amd.lattice import Lattice          # noqa: E402
+import sim_args_common as common
+from sim_args_common import _capi, expect, launches_out as launches, msg, quiet
+from graphbasedlocaltrajectoryplanner_amd.fleet import SIM_SNAPSHOTS
 
-FAKE = os.path.join(ROOT, "tools", "fakehip", "build_plain", "libltpl_hip_fake.so")
 N = 6
+lib, fleet, table = common.start(N)
 OPPONENTS = (1, 1, 0, 2, 1, 1)                                            # per planner: the offsets of planners 4 and 5 differ from 0 and 1
-lat = Lattice.load(os.path.join(ROOT, "tests", "golden", "monteblanco_lattice.npz"))
-table = sim.RaceLineTable.from_track(np.load(os.path.join(ROOT, "tests", "golden", "monteblanco_track.npz")))
-hip = _capi.HipBackend(lat, lib_path=FAKE)
-lib = hip.lib
-lib.fakehip_launch_count.restype = ctypes.c_long
-lib.fakehip_fail_malloc_after.argtypes = [ctypes.c_long]
-lib.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
-lib.hipFree.argtypes = [ctypes.c_void_p]
-lib.ltpl_fleet_last_error.restype = ctypes.c_char_p
-lib.ltpl_fleet_last_error.argtypes = [ctypes.c_void_p]
 lib.ltpl_fleet_sim_snapshot.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32]
 lib.ltpl_fleet_sim_snapshot_info.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
 lib.ltpl_fleet_sim_snapshot_drop.argtypes = [ctypes.c_void_p, ctypes.c_int32]
 lib.ltpl_fleet_sim_branch.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
-fleet = Fleet(hip, N)
 h = fleet.handle
-
-
-def quiet(fn):
-    """Runs ``fn`` with an allocation failure armed for the next hipMalloc; asserts that ``fn`` neither allocated (the failure is still
-    pending afterwards) nor launched. Returns ``fn``'s result."""
-    before = lib.fakehip_launch_count()
-    lib.fakehip_fail_malloc_after(1)
-    try:
-        out = fn()
-    finally:
-        p = ctypes.c_void_p()
-        pending = lib.hipMalloc(ctypes.byref(p), 8) != 0
-        if not pending:
-            lib.hipFree(p)
-        lib.fakehip_fail_malloc_after(0)
-    assert pending, "a refused call allocated device memory"
-    assert lib.fakehip_launch_count() == before, "a refused call launched a kernel"
-    return out
-
-
-def msg():
-    return (lib.ltpl_fleet_last_error(h) or b"").decode()
 
 
 def snapshot(slot, planners=None):
@@ -85,22 +48,8 @@ def branch(slot, src, dst):
     return rc, msg()
 
 
-def expect(rc_msg, text):
-    rc, m = rc_msg[0], rc_msg[-1]
-    assert rc == 1 and text in m, (rc, m, text)                           # LTPL_ERR_INVALID_ARG
-    print("refused (%d): %s" % (rc, m))
-
-
-def launches(fn):
-    before = lib.fakehip_launch_count()
-    out = fn()
-    return lib.fakehip_launch_count() - before, out
-
-
 def fresh():
-    fleet.sim_setup(table, [dict(opponents=[(250.0 + 100.0 * k, 0.3, 5.0) for k in range(no)], pref=("right", "straight"), pos_est=(0.0, 0.0),
-                                 zone_gids=[3]) for no in OPPONENTS])
-    fleet.sim_vel()
+    common.fresh([dict(common.GOOD_ENTRY, opponents=[(250.0 + 100.0 * k, 0.3, 5.0) for k in range(no)]) for no in OPPONENTS])
 
 
 # null fleet, no simulation
@@ -189,24 +138,19 @@ assert launches(lambda: fleet.sim_run(1, trace=False))[0] == plain
 
 # an allocation failing at each allocation of ltpl_fleet_sim_snapshot: the slot keeps what it held
 for tele in (False, True):
-    failures = 0
-    for k in range(1, 40):
+    def slot_1_taken():
         fresh()
         if tele:
             fleet.sim_telemetry()
         assert snapshot(1, [5, 0])[0] == 0
-        held = info(1)[:3]
-        lib.fakehip_fail_malloc_after(k)
-        rc, m = snapshot(1, [1, 2, 3])
-        lib.fakehip_fail_malloc_after(0)
-        if rc == 0:
-            assert info(1)[1] == [1, 2, 3]
-            break
-        assert rc == 3 and "hipMalloc" in m, (k, rc, m)                                   # LTPL_ERR_HIP
-        failures += 1
+        return info(1)[:3]
+
+    def slot_1_kept(k, held):
         assert info(1)[:3] == held and branch(1, [5], [4])[0] == 0, (k, info(1))
-    else:
-        raise AssertionError("ltpl_fleet_sim_snapshot never succeeded")
+
+    def slot_1_new():
+        assert info(1)[1] == [1, 2, 3]
+    failures = common.alloc_sweep("ltpl_fleet_sim_snapshot", lambda: snapshot(1, [1, 2, 3]), 40, slot_1_kept, before=slot_1_taken, after_success=slot_1_new)
     assert failures >= (16 if tele else 13), failures
     print("allocation failure at each of the %d allocations of ltpl_fleet_sim_snapshot (telemetry %s): previous snapshot kept" % (
         failures, "on" if tele else "off"))
@@ -217,6 +161,4 @@ n_launch, rc = launches(lambda: branch(-1, [0], [1]))
 lib.fakehip_fail_malloc_after(0)
 assert rc[0] == 3 and "hipMalloc" in rc[1] and n_launch == 0, (rc, n_launch)
 print("launches per tick: %d with and without snapshots; a snapshot and a branch: 1 launch each" % plain)
-fleet.close()
-hip.close()
-print("sim branch args OK")
+common.finish("sim branch args OK")

@@ -12,59 +12,21 @@ simulation, csrc/fleet_events.hpp) without a device. The library's host code bui
   - timed emergency-flag events: tick k launches what a run split at k (ltpl_fleet_sim_vel in between) launches; a flag an event set keeps
     these launches after the list is switched off or replaced, until ltpl_fleet_sim_vel sets the flags anew."""
 import ctypes
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-from graphbasedlocaltrajectoryplanner_amd import _capi, sim               # noqa: E402
-from graphbasedlocaltrajectoryplanner_amd.fleet import Fleet, SimEventsIn   # noqa: E402
-from graphbasedlocaltrajectoryplanner_amd.lattice import Lattice          # noqa: E402
-from graphbasedlocaltrajectoryplanner_amd.sim import Event                # noqa: E402
+import sim_args_common as common
+from sim_args_common import CAPACITY, INVALID, UNSUPPORTED, _capi, expect, launches_out as launches, msg, quiet, sim
+from graphbasedlocaltrajectoryplanner_amd.fleet import SimEventsIn
+from graphbasedlocaltrajectoryplanner_amd.sim import Event
 
-FAKE = os.path.join(ROOT, "tools", "fakehip", "build_plain", "libltpl_hip_fake.so")
 N = 6
+lib, fleet, table = common.start(N)
 OPPONENTS = (1, 1, 0, 2, 1, 1)
 STATICS = (0, 2, 0, 0, 1, 0)
-INVALID, HIP, CAPACITY, UNSUPPORTED = 1, 3, 4, 5
-lat = Lattice.load(os.path.join(ROOT, "tests", "golden", "monteblanco_lattice.npz"))
-table = sim.RaceLineTable.from_track(np.load(os.path.join(ROOT, "tests", "golden", "monteblanco_track.npz")))
-hip = _capi.HipBackend(lat, lib_path=FAKE)
-lib = hip.lib
-lib.fakehip_launch_count.restype = ctypes.c_long
-lib.fakehip_fail_malloc_after.argtypes = [ctypes.c_long]
-lib.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
-lib.hipFree.argtypes = [ctypes.c_void_p]
-lib.ltpl_fleet_last_error.restype = ctypes.c_char_p
-lib.ltpl_fleet_last_error.argtypes = [ctypes.c_void_p]
 lib.ltpl_fleet_sim_events.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
 lib.ltpl_fleet_sim_events_read.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-fleet = Fleet(hip, N)
 h = fleet.handle
-
-
-def quiet(fn):
-    """Runs ``fn`` with an allocation failure armed for the next hipMalloc; asserts that ``fn`` neither allocated (the failure is still
-    pending afterwards) nor launched. Returns ``fn``'s result."""
-    before = lib.fakehip_launch_count()
-    lib.fakehip_fail_malloc_after(1)
-    try:
-        out = fn()
-    finally:
-        p = ctypes.c_void_p()
-        pending = lib.hipMalloc(ctypes.byref(p), 8) != 0
-        if not pending:
-            lib.hipFree(p)
-        lib.fakehip_fail_malloc_after(0)
-    assert pending, "a refused call allocated device memory"
-    assert lib.fakehip_launch_count() == before, "a refused call launched a kernel"
-    return out
-
-
-def msg():
-    return (lib.ltpl_fleet_last_error(h) or b"").decode()
 
 
 def set_events(events):
@@ -84,23 +46,9 @@ def read():
     return rc, n.value, tick.value, fired[:max(n.value, 0)].tolist()
 
 
-def expect(rc_msg, code, *texts):
-    rc, m = rc_msg
-    assert rc == code and all(t in m for t in texts), (rc, m, code, texts)
-    print("refused (%d): %s" % (rc, m))
-
-
-def launches(fn):
-    before = lib.fakehip_launch_count()
-    out = fn()
-    return lib.fakehip_launch_count() - before, out
-
-
 def fresh(**vel):
-    fleet.sim_setup(table, [dict(opponents=[(250.0 + 100.0 * k, 0.3, 5.0) for k in range(no)],
-                                 static=[(10.0 * k, 5.0, 0.0, 0.0, 4.0) for k in range(ns)], pref=("right", "straight"), pos_est=(0.0, 0.0),
-                                 zone_gids=[3]) for no, ns in zip(OPPONENTS, STATICS)])
-    fleet.sim_vel(**vel)
+    common.fresh([dict(common.GOOD_ENTRY, opponents=[(250.0 + 100.0 * k, 0.3, 5.0) for k in range(no)],
+                       static=[(10.0 * k, 5.0, 0.0, 0.0, 4.0) for k in range(ns)]) for no, ns in zip(OPPONENTS, STATICS)], **vel)
 
 
 def per_tick(n):
@@ -269,27 +217,25 @@ assert per_tick(1) == [plain]
 print("emergency launches: a flag set by an event keeps them after the list is switched off (%d per tick), sim_vel takes them back (%d)" % (emerg, plain))
 
 # an allocation failing at each allocation of ltpl_fleet_sim_events: the previous list, its tick and its size stay
-failures = 0
-for k in range(1, 40):
+def list_at_tick_3():
     fresh()
     assert set_events(good)[0] == 0
     fleet.sim_run(3, trace=False)
     held = read()
     assert held[1:3] == (5, 3)
-    lib.fakehip_fail_malloc_after(k)
-    rc, m = set_events(ok)
-    lib.fakehip_fail_malloc_after(0)
-    if rc == 0:
-        assert read()[1:3] == (len(ok), 0)
-        break
-    assert rc == HIP and "hipMalloc" in m, (k, rc, m)
-    failures += 1
+    return held
+
+
+def list_kept(k, held):
     assert read() == held, (k, read(), held)
     assert per_tick(1) == [plain + 1] and read()[2] == 4                                  # (the kept list still runs: its triggers)
-else:
-    raise AssertionError("ltpl_fleet_sim_events never succeeded")
+
+
+def new_list():
+    assert read()[1:3] == (len(ok), 0)
+
+
+failures = common.alloc_sweep("ltpl_fleet_sim_events", lambda: set_events(ok), 40, list_kept, before=list_at_tick_3, after_success=new_list)
 assert failures >= 11, failures
 print("allocation failure at each of the %d allocations of ltpl_fleet_sim_events: previous list kept" % failures)
-fleet.close()
-hip.close()
-print("sim events args OK")
+common.finish("sim events args OK")

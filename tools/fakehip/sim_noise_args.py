@@ -9,55 +9,19 @@ number of kernel launches:
   - the estimate is the true state while the noise is off and until the first noisy tick;
   - an allocation failing at each allocation of ltpl_fleet_sim_noise is LTPL_ERR_HIP, and the fleet runs on."""
 import ctypes
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-from graphbasedlocaltrajectoryplanner_amd import _capi, sim               # noqa: E402
-from graphbasedlocaltrajectoryplanner_amd.fleet import Fleet, SimNoiseIn  # noqa: E402
-from graphbasedlocaltrajectoryplanner_amd.lattice import Lattice          # noqa: E402
+import sim_args_common as common
+from sim_args_common import expect, launches, msg, quiet
+from graphbasedlocaltrajectoryplanner_amd.fleet import SimNoiseIn
 
-FAKE = os.path.join(ROOT, "tools", "fakehip", "build_plain", "libltpl_hip_fake.so")
 N = 4
-lat = Lattice.load(os.path.join(ROOT, "tests", "golden", "monteblanco_lattice.npz"))
-table = sim.RaceLineTable.from_track(np.load(os.path.join(ROOT, "tests", "golden", "monteblanco_track.npz")))
-hip = _capi.HipBackend(lat, lib_path=FAKE)
-lib = hip.lib
-lib.fakehip_launch_count.restype = ctypes.c_long
-lib.fakehip_fail_malloc_after.argtypes = [ctypes.c_long]
-lib.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
-lib.hipFree.argtypes = [ctypes.c_void_p]
-lib.ltpl_fleet_last_error.restype = ctypes.c_char_p
-lib.ltpl_fleet_last_error.argtypes = [ctypes.c_void_p]
+lib, fleet, table = common.start(N)
 lib.ltpl_fleet_sim_noise.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
 lib.ltpl_fleet_sim_estimate.argtypes = [ctypes.c_void_p] * 4
 lib.ltpl_fleet_sim_noise_draws.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
-fleet = Fleet(hip, N)
 h = fleet.handle
-
-
-def quiet(fn):
-    """Runs ``fn`` with an allocation failure armed for the next hipMalloc; asserts that ``fn`` neither allocated nor launched."""
-    before = lib.fakehip_launch_count()
-    lib.fakehip_fail_malloc_after(1)
-    try:
-        out = fn()
-    finally:
-        p = ctypes.c_void_p()
-        pending = lib.hipMalloc(ctypes.byref(p), 8) != 0
-        if not pending:
-            lib.hipFree(p)
-        lib.fakehip_fail_malloc_after(0)
-    assert pending, "a refused call allocated device memory"
-    assert lib.fakehip_launch_count() == before, "a refused call launched a kernel"
-    return out
-
-
-def msg():
-    return (lib.ltpl_fleet_last_error(h) or b"").decode()
 
 
 def noise(seed=True, tick0=0, **sig):
@@ -70,24 +34,11 @@ def noise(seed=True, tick0=0, **sig):
     return lib.ltpl_fleet_sim_noise(h, ctypes.byref(ni)), msg()
 
 
-def expect(rc_msg, text):
-    assert rc_msg[0] == 1 and text in rc_msg[1], (rc_msg, text)             # LTPL_ERR_INVALID_ARG
-    print("refused (%d): %s" % rc_msg)
-
-
-def launches(fn):
-    before = lib.fakehip_launch_count()
-    fn()
-    return lib.fakehip_launch_count() - before
-
-
 POS = [(10.0 + p, -3.0 * p) for p in range(N)]
 
 
 def fresh():
-    fleet.sim_setup(table, [dict(opponents=[(250.0, 0.3, 5.0)], static=[(1.0, 2.0, 0.0, 0.0, 4.0)], pref=("right", "straight"), pos_est=POS[p],
-                                 vel_est=1.5 * p, zone_gids=[]) for p in range(N)])
-    fleet.sim_vel()
+    common.fresh(common.moving_entries(N, static=[(1.0, 2.0, 0.0, 0.0, 4.0)]))
 
 
 def estimate_is_truth():
@@ -136,18 +87,11 @@ assert launches(lambda: fleet.sim_run(1, trace=False)) == plain
 # an allocation failing at each allocation of ltpl_fleet_sim_noise
 fresh()
 assert noise(pos=0.1)[0] == 0
-failures = 0
-for k in range(1, 10):
-    lib.fakehip_fail_malloc_after(k)
-    rc, m = noise(pos=0.2, tick0=7)
-    lib.fakehip_fail_malloc_after(0)
-    if rc == 0:
-        break
-    assert rc == 3 and "hipMalloc" in m, (k, rc, m)                          # LTPL_ERR_HIP
-    failures += 1
+def runs_on(k, _):
     assert launches(lambda: fleet.sim_run(1, trace=False)) == plain
-else:
-    raise AssertionError("ltpl_fleet_sim_noise never succeeded")
+
+
+failures = common.alloc_sweep("ltpl_fleet_sim_noise", lambda: noise(pos=0.2, tick0=7), 10, runs_on)
 assert failures == 2, failures
 print("allocation failure at each of the %d allocations of ltpl_fleet_sim_noise: the fleet runs on" % failures)
 
@@ -163,6 +107,4 @@ for hole in range(5):
 assert quiet(lambda: lib.ltpl_fleet_sim_noise_draws(h, None, None, None, None, 0, None, None)) == 0
 assert launches(lambda: fleet.sim_noise_draws(z, 0, 0, 0)) == 1 and launches(lambda: fleet.sim_noise_draws(z, 0, 0, 0, words=True)) == 1
 print("launches per tick: %d with the noise on, off and never set (%d with races and telemetry)" % (plain, with_mates))
-fleet.close()
-hip.close()
-print("sim noise args OK")
+common.finish("sim noise args OK")

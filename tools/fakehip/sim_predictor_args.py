@@ -12,61 +12,19 @@ messages and the kernel launches (by number and, through fakehip_launches_of, by
   - per tick a fleet with the predictor set launches k_fleet_sim_predict and not k_fleet_sim_compact, the same number of kernels as
     before; a fleet that had one and cleared it, and one after ltpl_fleet_sim_setup, launch what a fleet that never had one launches."""
 import ctypes
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-from graphbasedlocaltrajectoryplanner_amd import _capi, sim               # noqa: E402
-from graphbasedlocaltrajectoryplanner_amd.fleet import Fleet, SimPredictorIn  # noqa: E402
-from graphbasedlocaltrajectoryplanner_amd.lattice import Lattice          # noqa: E402
+import sim_args_common as common
+from sim_args_common import CAPACITY as CAP, _capi, I32, INVALID, P, expect, launches, msg, quiet, run1, sim
+from graphbasedlocaltrajectoryplanner_amd.fleet import SimPredictorIn
 
-FAKE = os.path.join(ROOT, "tools", "fakehip", "build_plain", "libltpl_hip_fake.so")
 N = 4
-lat = Lattice.load(os.path.join(ROOT, "tests", "golden", "monteblanco_lattice.npz"))
-table = sim.RaceLineTable.from_track(np.load(os.path.join(ROOT, "tests", "golden", "monteblanco_track.npz")))
-hip = _capi.HipBackend(lat, lib_path=FAKE)
-lib = hip.lib
-P, I32 = ctypes.c_void_p, ctypes.c_int32
-lib.fakehip_launch_count.restype = ctypes.c_long
-lib.fakehip_launches_of.restype = ctypes.c_long
-lib.fakehip_launches_of.argtypes = [ctypes.c_char_p]
-lib.fakehip_fail_malloc_after.argtypes = [ctypes.c_long]
-lib.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
-lib.hipFree.argtypes = [ctypes.c_void_p]
-lib.ltpl_fleet_last_error.restype = ctypes.c_char_p
-lib.ltpl_fleet_last_error.argtypes = [P]
+lib, fleet, table = common.start(N)
 lib.ltpl_fleet_sim_predictor.argtypes = [P, P]
 lib.ltpl_fleet_sim_predictor_read.argtypes = [P, P, I32]
 lib.ltpl_fleet_sim_predictor_eval.argtypes = [P, I32, I32] + [P] * 6
-fleet = Fleet(hip, N)
 h = fleet.handle
-INVALID, HIP_ERR, CAP = 1, 3, 4          # LTPL_ERR_INVALID_ARG, LTPL_ERR_HIP, LTPL_ERR_CAPACITY
-
-
-def quiet(fn):
-    """Runs ``fn`` with an allocation failure armed for the next hipMalloc; asserts that ``fn`` neither allocated nor launched."""
-    before = lib.fakehip_launch_count()
-    lib.fakehip_fail_malloc_after(1)
-    try:
-        out = fn()
-    finally:
-        p = ctypes.c_void_p()
-        pending = lib.hipMalloc(ctypes.byref(p), 8) != 0
-        if not pending:
-            lib.hipFree(p)
-        lib.fakehip_fail_malloc_after(0)
-    assert pending, "a refused call allocated device memory"
-    assert lib.fakehip_launch_count() == before, "a refused call launched a kernel"
-    return out
-
-
-def msg():
-    return (lib.ltpl_fleet_last_error(h) or b"").decode()
-
-
 GOOD = dict(mode=2, horizon=2.0, relax=0.25, d_max=6.0)
 
 
@@ -80,17 +38,6 @@ def predictor(n_points=4, missing=None, **par):
     return lib.ltpl_fleet_sim_predictor(h, ctypes.byref(pi)), msg()
 
 
-def expect(rc_msg, text, code=INVALID):
-    assert rc_msg[0] == code and text in rc_msg[1], (rc_msg, text, code)
-    print("refused (%d): %s" % rc_msg)
-
-
-def launches(fn):
-    before = lib.fakehip_launch_count()
-    fn()
-    return lib.fakehip_launch_count() - before
-
-
 def named(fn):
     """(launches of k_fleet_sim_predict, of k_fleet_sim_compact) during ``fn``."""
     a = [lib.fakehip_launches_of(b"k_fleet_sim_predict"), lib.fakehip_launches_of(b"k_fleet_sim_compact")]
@@ -100,13 +47,10 @@ def named(fn):
 
 def fresh(opponents=(1, 1, 1, 1)):
     """``opponents``: opponents per planner (their staging slots before a race)."""
-    fleet.sim_setup(table, [dict(opponents=[(250.0 + 5.0 * k, 0.3, 5.0) for k in range(opponents[p])], static=[], pref=("right", "straight"),
-                                 pos_est=(10.0 + p, -3.0 * p), vel_est=1.5 * p, zone_gids=[]) for p in range(N)])
-    fleet.sim_vel()
-
-
-def run1():
-    fleet.sim_run(1, trace=False)
+    entries = common.moving_entries(N)
+    for p in range(N):
+        entries[p]["opponents"] = [(250.0 + 5.0 * k, 0.3, 5.0) for k in range(opponents[p])]
+    common.fresh(entries)
 
 
 out = np.zeros((N, sim.PREDICTOR_DOUBLES))
@@ -216,19 +160,10 @@ expect(quiet(read), "the predictor is off")
 # an allocation failing at each allocation of ltpl_fleet_sim_predictor: setting, replacing and clearing
 for what, call, ok_after in (("setting", lambda: predictor(n_points=2), (0, 1)), ("replacing", lambda: predictor(n_points=5, horizon=9.0), (1, 0)),
                              ("clearing", lambda: (lib.ltpl_fleet_sim_predictor(h, None), msg()), (1, 0))):
-    failures = 0
-    for k in range(1, 40):
-        lib.fakehip_fail_malloc_after(k)
-        rc, m = call()
-        lib.fakehip_fail_malloc_after(0)
-        if rc == 0:
-            break
-        assert rc == HIP_ERR and "hipMalloc" in m, (what, k, rc, m)
-        failures += 1
+    def still(k, _):
         assert launches(run1) == plain and named(run1) == ok_after, (what, k)        # the previous state: still off / still the old predictor
         assert (read()[0] == 0) == (ok_after == (1, 0)), (what, k)
-    else:
-        raise AssertionError("ltpl_fleet_sim_predictor never succeeded")
+    failures = common.alloc_sweep("ltpl_fleet_sim_predictor", call, 40, still)
     assert failures == (14 if what == "clearing" else 16), (what, failures)
     print("%s: allocation failure at each of the %d allocations of ltpl_fleet_sim_predictor: the fleet runs on" % (what, failures))
 assert named(run1) == (0, 1)
@@ -263,6 +198,4 @@ assert quiet(lambda: lib.ltpl_fleet_sim_predictor_eval(h, 0, 1, *([None] * 6))) 
 assert launches(lambda: hook(off=(0, 96, 192))) == 1 and launches(lambda: hook(off=(0, 0, 0), hole=2)) == 1
 print("launches per tick: %d without the predictor, %d with it (k_fleet_sim_predict in k_fleet_sim_compact's place); %d with races, telemetry, "
       "noise, sensor and tracker, with and without it" % (plain, with_pred, busy))
-fleet.close()
-hip.close()
-print("sim predictor args OK")
+common.finish("sim predictor args OK")

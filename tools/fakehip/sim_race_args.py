@@ -8,49 +8,18 @@ so results are not looked at -- only the return codes, the messages and the numb
   - an allocation failing at any point of ltpl_fleet_sim_race leaves the fleet with its previous races and staging: the call returns
     LTPL_ERR_HIP and the next run launches what the previous state launches."""
 import ctypes
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-from graphbasedlocaltrajectoryplanner_amd import _capi, sim               # noqa: E402
-from graphbasedlocaltrajectoryplanner_amd.fleet import Fleet, SimRaceIn   # noqa: E402
-from graphbasedlocaltrajectoryplanner_amd.lattice import Lattice          # noqa: E402
+import sim_args_common as common
+from sim_args_common import expect, launches_per_tick, no_allocation
+from graphbasedlocaltrajectoryplanner_amd.fleet import SimRaceIn
 
-FAKE = os.path.join(ROOT, "tools", "fakehip", "build_plain", "libltpl_hip_fake.so")
 N = 4
-lat = Lattice.load(os.path.join(ROOT, "tests", "golden", "monteblanco_lattice.npz"))
-table = sim.RaceLineTable.from_track(np.load(os.path.join(ROOT, "tests", "golden", "monteblanco_track.npz")))
-hip = _capi.HipBackend(lat, lib_path=FAKE)
-lib = hip.lib
-lib.fakehip_launch_count.restype = ctypes.c_long
-lib.fakehip_fail_malloc_after.argtypes = [ctypes.c_long]
-lib.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
-lib.hipFree.argtypes = [ctypes.c_void_p]
-lib.ltpl_fleet_last_error.restype = ctypes.c_char_p
-lib.ltpl_fleet_last_error.argtypes = [ctypes.c_void_p]
+lib, fleet, table = common.start(N)
 lib.ltpl_fleet_sim_race.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
 lib.ltpl_fleet_sim_heading.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-fleet = Fleet(hip, N)
 h = fleet.handle
-
-
-def no_allocation(fn):
-    """Runs ``fn`` with an allocation failure armed for the next hipMalloc; asserts that ``fn`` did not allocate (the failure is still
-    pending afterwards). Returns ``fn``'s result."""
-    lib.fakehip_fail_malloc_after(1)
-    try:
-        out = fn()
-    finally:
-        p = ctypes.c_void_p()
-        pending = lib.hipMalloc(ctypes.byref(p), 8) != 0
-        if not pending:
-            lib.hipFree(p)
-        lib.fakehip_fail_malloc_after(0)
-    assert pending, "a refused call allocated device memory"
-    return out
 
 
 def call(off, length=5.0, heading0=0.0, n_races=None):
@@ -65,17 +34,11 @@ def call(off, length=5.0, heading0=0.0, n_races=None):
     return rc, lib.fakehip_launch_count() - before, (lib.ltpl_fleet_last_error(h) or b"").decode()
 
 
-def expect(rc_msg, code, text):
-    rc, launches, msg = rc_msg
-    assert rc == code and text in msg, (rc, msg, code, text)
-    print("refused (%d): %s" % (rc, msg))
-
-
 assert lib.ltpl_fleet_sim_race(None, None) == 1 and lib.ltpl_fleet_sim_heading(None, None) == 1
 expect(no_allocation(lambda: call([0, N])), 1, "ltpl_fleet_sim_setup first")
 assert lib.ltpl_fleet_sim_heading(h, np.zeros(N).ctypes.data) == 1
 
-good = dict(opponents=[(250.0, 0.3, 5.0)], pref=("right", "straight"), pos_est=(0.0, 0.0), zone_gids=[3])
+good = common.GOOD_ENTRY
 crowded = dict(good, opponents=[(10.0 * k, 0.3, 5.0) for k in range(95)])
 fleet.sim_setup(table, [crowded, good, good, good])
 fleet.sim_vel()
@@ -97,15 +60,8 @@ ri.n_races, ri.race_off = 1, off.ctypes.data
 assert no_allocation(lambda: lib.ltpl_fleet_sim_race(h, ctypes.byref(ri))) == 1 and b"missing" in lib.ltpl_fleet_last_error(h)
 
 
-def launches_per_tick():
-    before = lib.fakehip_launch_count()
-    fleet.sim_run(1, trace=False)
-    return lib.fakehip_launch_count() - before
-
-
 def fresh():
-    fleet.sim_setup(table, [crowded, good, good, good])      # (clears the races)
-    fleet.sim_vel()
+    common.fresh([crowded, good, good, good])               # (clears the races)
 
 
 fresh()
@@ -129,23 +85,21 @@ fresh()                                                      # sim_setup clears 
 assert launches_per_tick() == plain
 assert lib.ltpl_fleet_sim_heading(h, np.zeros(N).ctypes.data) == 0
 # an allocation failing at every point of ltpl_fleet_sim_race: the previous state (here: races of 1, 1, 2) stays in place and works
-failures = 0
-for k in range(1, 64):
+def races_1_1_2():
     fresh()
     assert call([0, 1, 2, 4])[0] == 0
-    lib.fakehip_fail_malloc_after(k)
-    rc, _, msg = call([0, 2, 4])
-    lib.fakehip_fail_malloc_after(0)
-    if rc == 0:
-        assert launches_per_tick() == plain + 1
-        break
-    assert rc == 3 and "hipMalloc" in msg, (k, rc, msg)      # LTPL_ERR_HIP
-    failures += 1
+
+
+def still_runs(k, _):
     assert launches_per_tick() == plain + 1                  # the previous races still run (their buffers were not freed)
-    st = fleet.sim_state()
-    assert st["pos_est"].shape == (N, 2)
-else:
-    raise AssertionError("ltpl_fleet_sim_race never succeeded")
+    assert fleet.sim_state()["pos_est"].shape == (N, 2)
+
+
+def mates_run():
+    assert launches_per_tick() == plain + 1
+
+
+failures = common.alloc_sweep("ltpl_fleet_sim_race", lambda: call([0, 2, 4]), 64, still_runs, before=races_1_1_2, after_success=mates_run)
 assert failures >= 10, failures
 print("allocation failure at each of the %d allocations of ltpl_fleet_sim_race: previous state kept" % failures)
 print("launches per tick: %d without mates, %d with" % (plain, plain + 1))
@@ -158,6 +112,4 @@ fleet.sim_setup(table, [at_cap] * (N - 1) + [dict(at_cap, static=[(0.0, 0.0, 0.0
 fleet.sim_vel()
 expect(no_allocation(lambda: call([0, N])), 4, "above 96")                       # LTPL_ERR_CAPACITY
 print("own objects + mates: 96 accepted, 97 refused")
-fleet.close()
-hip.close()
-print("sim race args OK")
+common.finish("sim race args OK")

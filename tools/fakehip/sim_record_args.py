@@ -7,77 +7,27 @@ launches per simulated tick are looked at:
   - a recorder adds two launches per tick to the unfused sequence (k_fleet_sim_rec_paths, k_fleet_sim_rec_vel); off, and after
     ltpl_fleet_sim_setup, a tick launches what it launched before;
   - an allocation failing at any point of ltpl_fleet_sim_record leaves the previous recorder, its depth and its tick count in place."""
-import ctypes
 import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-from graphbasedlocaltrajectoryplanner_amd import _capi, sim               # noqa: E402
-from graphbasedlocaltrajectoryplanner_amd.fleet import Fleet              # noqa: E402
-from graphbasedlocaltrajectoryplanner_amd.lattice import Lattice          # noqa: E402
+import sim_args_common as common
+from sim_args_common import expect, fresh, launches_per_tick, msg, no_allocation
 
-FAKE = os.path.join(ROOT, "tools", "fakehip", "build_plain", "libltpl_hip_fake.so")
 N = 6
-lat = Lattice.load(os.path.join(ROOT, "tests", "golden", "monteblanco_lattice.npz"))
-table = sim.RaceLineTable.from_track(np.load(os.path.join(ROOT, "tests", "golden", "monteblanco_track.npz")))
-hip = _capi.HipBackend(lat, lib_path=FAKE)
-lib = hip.lib
-lib.fakehip_launch_count.restype = ctypes.c_long
-lib.fakehip_fail_malloc_after.argtypes = [ctypes.c_long]
-lib.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
-lib.hipFree.argtypes = [ctypes.c_void_p]
-lib.ltpl_fleet_last_error.restype = ctypes.c_char_p
-lib.ltpl_fleet_last_error.argtypes = [ctypes.c_void_p]
-fleet = Fleet(hip, N)
+lib, fleet, table = common.start(N)
 h = fleet.handle
-
-
-def no_allocation(fn):
-    lib.fakehip_fail_malloc_after(1)
-    try:
-        out = fn()
-    finally:
-        p = ctypes.c_void_p()
-        pending = lib.hipMalloc(ctypes.byref(p), 8) != 0
-        if not pending:
-            lib.hipFree(p)
-        lib.fakehip_fail_malloc_after(0)
-    assert pending, "a refused call allocated device memory"
-    return out
 
 
 def record(planners, depth):
     idx = np.ascontiguousarray(np.asarray(planners, np.int32))
     rc = lib.ltpl_fleet_sim_record(h, idx.ctypes.data if idx.size else None, int(idx.size), depth)
-    return rc, (lib.ltpl_fleet_last_error(h) or b"").decode()
+    return rc, msg()
 
 
 def get(tick, slot):
-    rc = lib.ltpl_fleet_sim_record_get(h, tick, slot, None, None, None, None, None)
-    return rc, (lib.ltpl_fleet_last_error(h) or b"").decode()
+    return lib.ltpl_fleet_sim_record_get(h, tick, slot, None, None, None, None, None), msg()
 
-
-def expect(rc_msg, code, text):
-    rc, msg = rc_msg
-    assert rc == code and text in msg, (rc, msg, code, text)
-    print("refused (%d): %s" % (rc, msg))
-
-
-def launches_per_tick(n=1):
-    before = lib.fakehip_launch_count()
-    fleet.sim_run(n, trace=False)
-    return (lib.fakehip_launch_count() - before) // n
-
-
-good = dict(opponents=[(250.0, 0.3, 5.0)], pref=("right", "straight"), pos_est=(0.0, 0.0), zone_gids=[3])
-
-
-def fresh():
-    fleet.sim_setup(table, [good] * N)
-    fleet.sim_vel()
 
 
 assert lib.ltpl_fleet_sim_record(None, None, 0, 1) == 1 and lib.ltpl_fleet_sim_record_info(None, None, None, None, None) == 1
@@ -86,8 +36,8 @@ expect(no_allocation(lambda: get(0, 0)), 1, "ltpl_fleet_sim_setup first")
 fresh()
 fused = launches_per_tick()
 os.environ["LTPL_FLEET_NO_FUSE"] = "1"
-unfused_fleet = Fleet(hip, N)
-unfused_fleet.sim_setup(table, [good] * N)
+unfused_fleet = common.Fleet(common.hip, N)
+unfused_fleet.sim_setup(table, [common.GOOD_ENTRY] * N)
 unfused_fleet.sim_vel()
 before = lib.fakehip_launch_count()
 unfused_fleet.sim_run(1, trace=False)
@@ -129,25 +79,19 @@ assert launches_per_tick() == unfused + 2 + 3
 assert fleet.sim_record_info() == dict(n_planners=2, depth=3, first_tick=0, n_ticks=1)
 
 # an allocation failing at every point of ltpl_fleet_sim_record: the previous recorder stays in place and works
-failures = 0
-for k in range(1, 16):
+def three_ticks_recorded():
     fresh()
     assert record([4, 2], 5)[0] == 0
     fleet.sim_run(3, trace=False)
-    lib.fakehip_fail_malloc_after(k)
-    rc, msg = record([0], 9)
-    lib.fakehip_fail_malloc_after(0)
-    if rc == 0:
-        break
-    assert rc == 3 and "hipMalloc" in msg, (k, rc, msg)                         # LTPL_ERR_HIP
-    failures += 1
+
+
+def recorder_kept(k, _):
     assert fleet.sim_record_info() == dict(n_planners=2, depth=5, first_tick=0, n_ticks=3)
     assert launches_per_tick() == unfused + 2 and get(3, 1)[0] == 0
-else:
-    raise AssertionError("ltpl_fleet_sim_record never succeeded")
+
+
+failures = common.alloc_sweep("ltpl_fleet_sim_record", lambda: record([0], 9), 16, recorder_kept, before=three_ticks_recorded)
 assert failures >= 2, failures
 print("allocation failure at each of the %d allocations of ltpl_fleet_sim_record: previous recorder kept" % failures)
 print("launches per tick: %d fused, %d unfused, %d with a recorder" % (fused, unfused, unfused + 2))
-fleet.close()
-hip.close()
-print("sim record args OK")
+common.finish("sim record args OK")

@@ -12,62 +12,20 @@ kernel launches (by number and, through fakehip_launches_of, by name):
     had one and cleared it, and one after ltpl_fleet_sim_setup, launch what a fleet that never had one launches, k_fleet_sim_safety never;
   - snapshot and branch launch k_fleet_sim_branch_safety only while the monitor is set."""
 import ctypes
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-from graphbasedlocaltrajectoryplanner_amd import _capi, sim               # noqa: E402
-from graphbasedlocaltrajectoryplanner_amd.fleet import Fleet, SimSafetyIn  # noqa: E402
-from graphbasedlocaltrajectoryplanner_amd.lattice import Lattice          # noqa: E402
+import sim_args_common as common
+from sim_args_common import I32, INVALID, P, expect, launches, msg, quiet, run1, sim
+from graphbasedlocaltrajectoryplanner_amd.fleet import SimSafetyIn
 
-FAKE = os.path.join(ROOT, "tools", "fakehip", "build_plain", "libltpl_hip_fake.so")
 N = 4
-lat = Lattice.load(os.path.join(ROOT, "tests", "golden", "monteblanco_lattice.npz"))
-table = sim.RaceLineTable.from_track(np.load(os.path.join(ROOT, "tests", "golden", "monteblanco_track.npz")))
-hip = _capi.HipBackend(lat, lib_path=FAKE)
-lib = hip.lib
-P, I32 = ctypes.c_void_p, ctypes.c_int32
-lib.fakehip_launch_count.restype = ctypes.c_long
-lib.fakehip_launches_of.restype = ctypes.c_long
-lib.fakehip_launches_of.argtypes = [ctypes.c_char_p]
-lib.fakehip_fail_malloc_after.argtypes = [ctypes.c_long]
-lib.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
-lib.hipFree.argtypes = [ctypes.c_void_p]
-lib.ltpl_fleet_last_error.restype = ctypes.c_char_p
-lib.ltpl_fleet_last_error.argtypes = [P]
+lib, fleet, table = common.start(N)
 lib.ltpl_fleet_sim_safety.argtypes = [P, P]
 lib.ltpl_fleet_sim_safety_read.argtypes = [P, P, I32, P, I32]
 lib.ltpl_fleet_sim_safety_eval.argtypes = [P, I32] + [P] * 10
-fleet = Fleet(hip, N)
 h = fleet.handle
-INVALID, HIP_ERR = 1, 3                  # LTPL_ERR_INVALID_ARG, LTPL_ERR_HIP
 RD, ID = sim.SAFETY_DOUBLES, sim.INCIDENT_DOUBLES
-
-
-def quiet(fn):
-    """Runs ``fn`` with an allocation failure armed for the next hipMalloc; asserts that ``fn`` neither allocated nor launched."""
-    before = lib.fakehip_launch_count()
-    lib.fakehip_fail_malloc_after(1)
-    try:
-        out = fn()
-    finally:
-        p = ctypes.c_void_p()
-        pending = lib.hipMalloc(ctypes.byref(p), 8) != 0
-        if not pending:
-            lib.hipFree(p)
-        lib.fakehip_fail_malloc_after(0)
-    assert pending, "a refused call allocated device memory"
-    assert lib.fakehip_launch_count() == before, "a refused call launched a kernel"
-    return out
-
-
-def msg():
-    return (lib.ltpl_fleet_last_error(h) or b"").decode()
-
-
 GOOD = dict(sim.SAFETY_DEFAULTS)
 
 
@@ -82,37 +40,17 @@ def safety(missing=None, on=1, tick0=0, flags=0, **par):
     return lib.ltpl_fleet_sim_safety(h, ctypes.byref(si)), msg()
 
 
-def expect(rc_msg, text, code=INVALID):
-    assert rc_msg[0] == code and text in rc_msg[1], (rc_msg, text, code)
-    print("refused (%d): %s" % rc_msg)
-
-
-def launches(fn):
-    before = lib.fakehip_launch_count()
-    fn()
-    return lib.fakehip_launch_count() - before
-
-
 SAFETY = b"_Z18k_fleet_sim_safety"       # the whole mangled name up to the arguments: 18 = len("k_fleet_sim_safety"), so the hook
                                         # k_fleet_sim_safety_eval (_Z23...) does not match
 BRANCH = b"_Z25k_fleet_sim_branch_safety"
 
 
 def named(fn, name=SAFETY):
-    """Launches of the kernel ``name`` during ``fn``."""
-    a = lib.fakehip_launches_of(name)
-    fn()
-    return lib.fakehip_launches_of(name) - a
+    return common.named(fn, name)
 
 
 def fresh():
-    fleet.sim_setup(table, [dict(opponents=[(250.0, 0.3, 5.0)], static=[], pref=("right", "straight"), pos_est=(10.0 + p, -3.0 * p), vel_est=1.5 * p,
-                                 zone_gids=[]) for p in range(N)])
-    fleet.sim_vel()
-
-
-def run1():
-    fleet.sim_run(1, trace=False)
+    common.fresh(common.moving_entries(N))
 
 
 out, inc = np.zeros((N, RD)), np.zeros((N, sim.SAFETY_INCIDENTS, ID))
@@ -196,19 +134,10 @@ expect(quiet(read), "the monitor is off")
 # an allocation failing at each allocation of ltpl_fleet_sim_safety: setting, replacing, and replacing with KEEP_STATE
 for what, call, ok_after in (("setting", lambda: safety(), 0), ("replacing", lambda: safety(ttc_thr=9.0), 1),
                              ("keeping the state", lambda: safety(ttc_thr=2.0, flags=1), 1)):
-    failures = 0
-    for k in range(1, 40):
-        lib.fakehip_fail_malloc_after(k)
-        rc, m = call()
-        lib.fakehip_fail_malloc_after(0)
-        if rc == 0:
-            break
-        assert rc == HIP_ERR and "hipMalloc" in m, (what, k, rc, m)
-        failures += 1
+    def still(k, _):
         assert launches(run1) == plain + ok_after and named(run1) == ok_after, (what, k)      # the previous state: still off / still the old monitor
         assert (read()[0] == 0) == (ok_after == 1), (what, k)
-    else:
-        raise AssertionError("ltpl_fleet_sim_safety never succeeded")
+    failures = common.alloc_sweep("ltpl_fleet_sim_safety", call, 40, still)
     assert failures == 4, (what, failures)
     print("%s: allocation failure at each of the %d allocations of ltpl_fleet_sim_safety: the fleet runs on" % (what, failures))
 assert named(run1) == 1
@@ -249,6 +178,4 @@ assert launches(lambda: hook(off=(0, 96, 192))) == 1
 assert launches(lambda: (hook(off=(0, 0, 0), hole=5), hook(off=(0, 0, 0), hole=8))) == 2       # (no objects: objs and per_obj may be null)
 print("launches per tick: %d without the monitor, %d with it (k_fleet_sim_safety behind telemetry, in front of the sensor); %d and %d with "
       "races, telemetry, noise, sensor, tracker, predictor and selector" % (plain, with_saf, busy, busy + 1))
-fleet.close()
-hip.close()
-print("sim safety args OK")
+common.finish("sim safety args OK")

@@ -10,62 +10,20 @@ messages and the kernel launches (by number and, through fakehip_launches_of, by
   - per tick a fleet with the selector set launches k_fleet_sim_select once, one kernel more than before; a fleet that had one and cleared
     it, and one after ltpl_fleet_sim_setup, launch what a fleet that never had one launches, k_fleet_sim_select never."""
 import ctypes
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-from graphbasedlocaltrajectoryplanner_amd import _capi, sim               # noqa: E402
-from graphbasedlocaltrajectoryplanner_amd.fleet import Fleet, SimSelectorIn  # noqa: E402
-from graphbasedlocaltrajectoryplanner_amd.lattice import Lattice          # noqa: E402
+import sim_args_common as common
+from sim_args_common import I32, INVALID, P, expect, launches, msg, quiet, run1, sim
+from graphbasedlocaltrajectoryplanner_amd.fleet import SimSelectorIn
 
-FAKE = os.path.join(ROOT, "tools", "fakehip", "build_plain", "libltpl_hip_fake.so")
 N = 4
+lib, fleet, table = common.start(N)
 N_PREF = 2 * N
-lat = Lattice.load(os.path.join(ROOT, "tests", "golden", "monteblanco_lattice.npz"))
-table = sim.RaceLineTable.from_track(np.load(os.path.join(ROOT, "tests", "golden", "monteblanco_track.npz")))
-hip = _capi.HipBackend(lat, lib_path=FAKE)
-lib = hip.lib
-P, I32 = ctypes.c_void_p, ctypes.c_int32
-lib.fakehip_launch_count.restype = ctypes.c_long
-lib.fakehip_launches_of.restype = ctypes.c_long
-lib.fakehip_launches_of.argtypes = [ctypes.c_char_p]
-lib.fakehip_fail_malloc_after.argtypes = [ctypes.c_long]
-lib.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
-lib.hipFree.argtypes = [ctypes.c_void_p]
-lib.ltpl_fleet_last_error.restype = ctypes.c_char_p
-lib.ltpl_fleet_last_error.argtypes = [P]
 lib.ltpl_fleet_sim_selector.argtypes = [P, P]
 lib.ltpl_fleet_sim_selector_read.argtypes = [P, P, I32, P, I32]
 lib.ltpl_fleet_sim_selector_eval.argtypes = [P, I32] + [P] * 10
-fleet = Fleet(hip, N)
 h = fleet.handle
-INVALID, HIP_ERR = 1, 3                  # LTPL_ERR_INVALID_ARG, LTPL_ERR_HIP
-
-
-def quiet(fn):
-    """Runs ``fn`` with an allocation failure armed for the next hipMalloc; asserts that ``fn`` neither allocated nor launched."""
-    before = lib.fakehip_launch_count()
-    lib.fakehip_fail_malloc_after(1)
-    try:
-        out = fn()
-    finally:
-        p = ctypes.c_void_p()
-        pending = lib.hipMalloc(ctypes.byref(p), 8) != 0
-        if not pending:
-            lib.hipFree(p)
-        lib.fakehip_fail_malloc_after(0)
-    assert pending, "a refused call allocated device memory"
-    assert lib.fakehip_launch_count() == before, "a refused call launched a kernel"
-    return out
-
-
-def msg():
-    return (lib.ltpl_fleet_last_error(h) or b"").decode()
-
-
 GOOD = dict(sim.SELECTOR_DEFAULTS)
 
 
@@ -79,36 +37,16 @@ def selector(missing=None, on=1, **par):
     return lib.ltpl_fleet_sim_selector(h, ctypes.byref(si)), msg()
 
 
-def expect(rc_msg, text, code=INVALID):
-    assert rc_msg[0] == code and text in rc_msg[1], (rc_msg, text, code)
-    print("refused (%d): %s" % rc_msg)
-
-
-def launches(fn):
-    before = lib.fakehip_launch_count()
-    fn()
-    return lib.fakehip_launch_count() - before
-
-
 SELECT = b"_Z18k_fleet_sim_select"       # the whole mangled name up to the arguments: 18 = len("k_fleet_sim_select"), so the hook
                                         # k_fleet_sim_selector_eval (_Z25...) does not match
 
 
 def named(fn):
-    """Launches of k_fleet_sim_select during ``fn``."""
-    a = lib.fakehip_launches_of(SELECT)
-    fn()
-    return lib.fakehip_launches_of(SELECT) - a
+    return common.named(fn, SELECT)
 
 
 def fresh():
-    fleet.sim_setup(table, [dict(opponents=[(250.0, 0.3, 5.0)], static=[], pref=("right", "straight"), pos_est=(10.0 + p, -3.0 * p), vel_est=1.5 * p,
-                                 zone_gids=[]) for p in range(N)])
-    fleet.sim_vel()
-
-
-def run1():
-    fleet.sim_run(1, trace=False)
+    common.fresh(common.moving_entries(N))
 
 
 out, order = np.zeros((N, sim.SELECTOR_DOUBLES)), np.zeros(N_PREF, np.int32)
@@ -181,19 +119,10 @@ expect(quiet(read), "the selector is off")
 
 # an allocation failing at each allocation of ltpl_fleet_sim_selector: setting and replacing
 for what, call, ok_after in (("setting", lambda: selector(), 0), ("replacing", lambda: selector(horizon=9.0), 1)):
-    failures = 0
-    for k in range(1, 40):
-        lib.fakehip_fail_malloc_after(k)
-        rc, m = call()
-        lib.fakehip_fail_malloc_after(0)
-        if rc == 0:
-            break
-        assert rc == HIP_ERR and "hipMalloc" in m, (what, k, rc, m)
-        failures += 1
+    def still(k, _):
         assert launches(run1) == plain + ok_after and named(run1) == ok_after, (what, k)      # the previous state: still off / still the old selector
         assert (read()[0] == 0) == (ok_after == 1), (what, k)
-    else:
-        raise AssertionError("ltpl_fleet_sim_selector never succeeded")
+    failures = common.alloc_sweep("ltpl_fleet_sim_selector", call, 40, still)
     assert failures == 4, (what, failures)
     print("%s: allocation failure at each of the %d allocations of ltpl_fleet_sim_selector: the fleet runs on" % (what, failures))
 assert named(run1) == 1
@@ -239,6 +168,4 @@ assert quiet(lambda: lib.ltpl_fleet_sim_selector_eval(h, 0, *([None] * 10))) == 
 assert launches(lambda: hook(off=(0, 96, 192))) == 1 and launches(lambda: hook(off=(0, 0, 0), hole=5)) == 1
 print("launches per tick: %d without the selector, %d with it (k_fleet_sim_select at the head of the tick); %d and %d with races, telemetry, "
       "noise, sensor, tracker and predictor" % (plain, with_sel, busy, busy + 1))
-fleet.close()
-hip.close()
-print("sim selector args OK")
+common.finish("sim selector args OK")

@@ -8,50 +8,19 @@ codes, the messages and the number of kernel launches per simulated tick are loo
     (k_fleet_sim_rank); off, and after ltpl_fleet_sim_setup, a tick launches what it launched before;
   - an allocation failing at any point of ltpl_fleet_sim_telemetry leaves the previous telemetry in place."""
 import ctypes
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-from graphbasedlocaltrajectoryplanner_amd import _capi, sim               # noqa: E402
-from graphbasedlocaltrajectoryplanner_amd.fleet import Fleet, SimTeleIn   # noqa: E402
-from graphbasedlocaltrajectoryplanner_amd.lattice import Lattice          # noqa: E402
+import sim_args_common as common
+from sim_args_common import _capi, expect, launches_per_tick, msg, no_allocation, sim
+from graphbasedlocaltrajectoryplanner_amd.fleet import SimTeleIn
 
-FAKE = os.path.join(ROOT, "tools", "fakehip", "build_plain", "libltpl_hip_fake.so")
 N = 4
+lib, fleet, table = common.start(N)
 D = sim.TELEMETRY_DOUBLES
-lat = Lattice.load(os.path.join(ROOT, "tests", "golden", "monteblanco_lattice.npz"))
-table = sim.RaceLineTable.from_track(np.load(os.path.join(ROOT, "tests", "golden", "monteblanco_track.npz")))
-hip = _capi.HipBackend(lat, lib_path=FAKE)
-lib = hip.lib
-lib.fakehip_launch_count.restype = ctypes.c_long
-lib.fakehip_fail_malloc_after.argtypes = [ctypes.c_long]
-lib.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
-lib.hipFree.argtypes = [ctypes.c_void_p]
-lib.ltpl_fleet_last_error.restype = ctypes.c_char_p
-lib.ltpl_fleet_last_error.argtypes = [ctypes.c_void_p]
 lib.ltpl_fleet_sim_telemetry.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
 lib.ltpl_fleet_sim_telemetry_read.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
-fleet = Fleet(hip, N)
 h = fleet.handle
-
-
-def no_allocation(fn):
-    """Runs ``fn`` with an allocation failure armed for the next hipMalloc; asserts that ``fn`` did not allocate (the failure is still
-    pending afterwards). Returns ``fn``'s result."""
-    lib.fakehip_fail_malloc_after(1)
-    try:
-        out = fn()
-    finally:
-        p = ctypes.c_void_p()
-        pending = lib.hipMalloc(ctypes.byref(p), 8) != 0
-        if not pending:
-            lib.hipFree(p)
-        lib.fakehip_fail_malloc_after(0)
-    assert pending, "a refused call allocated device memory"
-    return out
 
 
 def call(radius=2.5, grid_s=None):
@@ -61,27 +30,14 @@ def call(radius=2.5, grid_s=None):
     if grid_s is not None:
         gs = np.ascontiguousarray(np.broadcast_to(np.asarray(grid_s, np.float64), (N,)))
         ti.grid_s = gs.ctypes.data
-    rc = lib.ltpl_fleet_sim_telemetry(h, ctypes.byref(ti))
-    return rc, (lib.ltpl_fleet_last_error(h) or b"").decode()
+    return lib.ltpl_fleet_sim_telemetry(h, ctypes.byref(ti)), msg()
 
 
 def read(doubles=D):
     out = np.full((N, D), 7.0)
     L = ctypes.c_double(0.0)
     rc = lib.ltpl_fleet_sim_telemetry_read(h, out.ctypes.data, doubles, ctypes.byref(L))
-    return rc, out, L.value, (lib.ltpl_fleet_last_error(h) or b"").decode()
-
-
-def expect(rc_msg, code, text):
-    rc, msg = rc_msg[0], rc_msg[-1]
-    assert rc == code and text in msg, (rc, msg, code, text)
-    print("refused (%d): %s" % (rc, msg))
-
-
-def launches_per_tick():
-    before = lib.fakehip_launch_count()
-    fleet.sim_run(1, trace=False)
-    return lib.fakehip_launch_count() - before
+    return rc, out, L.value, msg()
 
 
 BEFORE = np.zeros(D)
@@ -95,12 +51,8 @@ def intact():
     assert rc == 0 and abs(L - 2382.2979975) < 1e-6 and all(np.array_equal(row, BEFORE, equal_nan=True) for row in out), (rc, L, out)
 
 
-good = dict(opponents=[(250.0, 0.3, 5.0)], pref=("right", "straight"), pos_est=(0.0, 0.0), zone_gids=[3])
-
-
 def fresh(races=None):
-    fleet.sim_setup(table, [good] * N)
-    fleet.sim_vel()
+    common.fresh()
     if races:
         fleet.sim_race(races)
 
@@ -163,24 +115,18 @@ fleet.sim_race([2, 2])
 assert launches_per_tick() == plain + 3
 
 # an allocation failing at every point of ltpl_fleet_sim_telemetry: the previous telemetry stays in place and works
-failures = 0
-for k in range(1, 32):
+def telemetry_set():
     fresh()
     assert call()[0] == 0
-    lib.fakehip_fail_malloc_after(k)
-    rc, msg = call(radius=1.0)
-    lib.fakehip_fail_malloc_after(0)
-    if rc == 0:
-        break
-    assert rc == 3 and "hipMalloc" in msg, (k, rc, msg)                         # LTPL_ERR_HIP
-    failures += 1
+
+
+def telemetry_kept(k, _):
     intact()
     assert launches_per_tick() == plain + 1
-else:
-    raise AssertionError("ltpl_fleet_sim_telemetry never succeeded")
+
+
+failures = common.alloc_sweep("ltpl_fleet_sim_telemetry", lambda: call(radius=1.0), 32, telemetry_kept, before=telemetry_set)
 assert failures >= 7, failures
 print("allocation failure at each of the %d allocations of ltpl_fleet_sim_telemetry: previous telemetry kept" % failures)
 print("launches per tick: %d without telemetry, %d with, %d with a race" % (plain, plain + 1, plain + 3))
-fleet.close()
-hip.close()
-print("sim telemetry args OK")
+common.finish("sim telemetry args OK")

@@ -11,58 +11,19 @@ number of kernel launches:
   - a refused or failing call keeps the previous tracker (the tick still launches the extra kernel, the records stay readable);
   - an allocation failing at each allocation of ltpl_fleet_sim_tracker is LTPL_ERR_HIP, and the fleet runs on."""
 import ctypes
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-from graphbasedlocaltrajectoryplanner_amd import _capi, sim               # noqa: E402
-from graphbasedlocaltrajectoryplanner_amd.fleet import Fleet, SimTrackerIn  # noqa: E402
-from graphbasedlocaltrajectoryplanner_amd.lattice import Lattice          # noqa: E402
+import sim_args_common as common
+from sim_args_common import I32, P, expect, launches, msg, quiet, sim
+from graphbasedlocaltrajectoryplanner_amd.fleet import SimTrackerIn
 
-FAKE = os.path.join(ROOT, "tools", "fakehip", "build_plain", "libltpl_hip_fake.so")
 N = 4
-lat = Lattice.load(os.path.join(ROOT, "tests", "golden", "monteblanco_lattice.npz"))
-table = sim.RaceLineTable.from_track(np.load(os.path.join(ROOT, "tests", "golden", "monteblanco_track.npz")))
-hip = _capi.HipBackend(lat, lib_path=FAKE)
-lib = hip.lib
-P, I32 = ctypes.c_void_p, ctypes.c_int32
-lib.fakehip_launch_count.restype = ctypes.c_long
-lib.fakehip_fail_malloc_after.argtypes = [ctypes.c_long]
-lib.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
-lib.hipFree.argtypes = [ctypes.c_void_p]
-lib.ltpl_fleet_last_error.restype = ctypes.c_char_p
-lib.ltpl_fleet_last_error.argtypes = [P]
+lib, fleet, table = common.start(N)
 lib.ltpl_fleet_sim_tracker.argtypes = [P, P]
 lib.ltpl_fleet_sim_tracker_read.argtypes = [P, P, I32, I32, P, P, P]
 lib.ltpl_fleet_sim_tracker_eval.argtypes = [P, I32] + [P] * 16
-fleet = Fleet(hip, N)
 h = fleet.handle
-
-
-def quiet(fn):
-    """Runs ``fn`` with an allocation failure armed for the next hipMalloc; asserts that ``fn`` neither allocated nor launched."""
-    before = lib.fakehip_launch_count()
-    lib.fakehip_fail_malloc_after(1)
-    try:
-        out = fn()
-    finally:
-        p = ctypes.c_void_p()
-        pending = lib.hipMalloc(ctypes.byref(p), 8) != 0
-        if not pending:
-            lib.hipFree(p)
-        lib.fakehip_fail_malloc_after(0)
-    assert pending, "a refused call allocated device memory"
-    assert lib.fakehip_launch_count() == before, "a refused call launched a kernel"
-    return out
-
-
-def msg():
-    return (lib.ltpl_fleet_last_error(h) or b"").decode()
-
-
 GOOD = dict(gate=5.0, w_pos=0.5, w_vel=0.25, n_confirm=2, n_coast=3)
 
 
@@ -76,21 +37,8 @@ def tracker(tick0=0, missing=None, **par):
     return lib.ltpl_fleet_sim_tracker(h, ctypes.byref(ti)), msg()
 
 
-def expect(rc_msg, text):
-    assert rc_msg[0] == 1 and text in rc_msg[1], (rc_msg, text)             # LTPL_ERR_INVALID_ARG
-    print("refused (%d): %s" % rc_msg)
-
-
-def launches(fn):
-    before = lib.fakehip_launch_count()
-    fn()
-    return lib.fakehip_launch_count() - before
-
-
 def fresh():
-    fleet.sim_setup(table, [dict(opponents=[(250.0, 0.3, 5.0)], static=[(1.0, 2.0, 0.0, 0.0, 4.0)], pref=("right", "straight"),
-                                 pos_est=(10.0 + p, -3.0 * p), vel_est=1.5 * p, zone_gids=[]) for p in range(N)])
-    fleet.sim_vel()
+    common.fresh(common.moving_entries(N, static=[(1.0, 2.0, 0.0, 0.0, 4.0)]))
 
 
 out = np.zeros((N, 12))
@@ -171,18 +119,11 @@ expect(quiet(read), "the tracker is off")
 
 # an allocation failing at each allocation of ltpl_fleet_sim_tracker
 assert tracker()[0] == 0
-failures = 0
-for k in range(1, 20):
-    lib.fakehip_fail_malloc_after(k)
-    rc, m = tracker(gate=9.0, tick0=7)
-    lib.fakehip_fail_malloc_after(0)
-    if rc == 0:
-        break
-    assert rc == 3 and "hipMalloc" in m, (k, rc, m)                          # LTPL_ERR_HIP
-    failures += 1
+def runs_on(k, _):
     assert launches(lambda: fleet.sim_run(1, trace=False)) == with_tracker and read(n_sel=N)[0] == 0
-else:
-    raise AssertionError("ltpl_fleet_sim_tracker never succeeded")
+
+
+failures = common.alloc_sweep("ltpl_fleet_sim_tracker", lambda: tracker(gate=9.0, tick0=7), 20, runs_on)
 assert failures == 8, failures
 print("allocation failure at each of the %d allocations of ltpl_fleet_sim_tracker: the fleet runs on" % failures)
 
@@ -224,6 +165,4 @@ assert quiet(lambda: lib.ltpl_fleet_sim_tracker_eval(h, 0, *([None] * 16))) == 0
 assert launches(lambda: hook(toff=(0, 96, 192), doff=(0, 96, 192))) == 1 and launches(lambda: hook(toff=(0, 0, 0), doff=(0, 0, 0), hole=5)) == 1
 print("launches per tick: %d without the tracker, %d with it (%d and %d with races, telemetry and noise, %d with the sensor as well)" % (
     plain, with_tracker, busy, busy + 1, busy + 2))
-fleet.close()
-hip.close()
-print("sim tracker args OK")
+common.finish("sim tracker args OK")
