@@ -1007,9 +1007,12 @@ struct SweepK {
 #endif
 #define CW_SHIFT 24
 #define CW_ONE (1u << CW_SHIFT)
+// flag on top of the filter bits of a layer body's ACT: the F_DEF slot serves the filter LayerArgs::side, a run-time value
+constexpr unsigned ACT_SIDE = 1u << NFILT;
 struct LayerArgs {
     int j, b, v0, Kb, ne, eb, kpad, hm, cur, prv, H;
     int fs, fd, cl_hit, cn;                      // cl_hit: this layer is the closest object's layer
+    int side;                                    // ACT_SIDE body: the filter (F_DEF, F_LEFT or F_RIGHT) that the body's F_DEF slot stands for
     bool from_def;
     double fac;
 };
@@ -1043,11 +1046,16 @@ __device__ __forceinline__ void team_layer(const SweepK& K, const Scen& sc, cons
         else return ci >= LTPL_CH_ALWAYS && ci >= pin_sgpr(nch);
     };
     const bool any_blk = __ballot(blk != 0u) != 0ull;
+    // ACT_SIDE ("planning_range plus ONE more filter": `default`, or the overtaking side that is left once the other side's frontier has died
+    // out): the body's F_DEF slot stands for the filter A.side. Frontier, parent table and reachability row are addressed with it (run-time
+    // offsets anyway); the election scratch (cnt / widx / dumin) lives for one layer only and stays in the slot's own rows.
+    constexpr bool SIDE = (ACT & ACT_SIDE) != 0u;
+    auto filt_of = [&](int f) { return SIDE && f == F_DEF ? A.side : f; };
     int poff[NFILT], coff[NFILT];
 #pragma unroll
     for (int f = 0; f < NFILT; ++f) {
-        const int fprev = (A.from_def && (f == F_LEFT || f == F_RIGHT)) ? F_DEF : f;
-        poff[f] = (fprev * 2 + A.prv) * kpad; coff[f] = (f * 2 + A.cur) * kpad;
+        const int fc = filt_of(f), fprev = (A.from_def && (fc == F_LEFT || fc == F_RIGHT)) ? F_DEF : fc;
+        poff[f] = (fprev * 2 + A.prv) * kpad; coff[f] = (fc * 2 + A.cur) * kpad;
     }
     // reset the targets of this layer
     for (int n = tid; n < kpad; n += NT) {
@@ -1243,14 +1251,15 @@ __device__ __forceinline__ void team_layer(const SweepK& K, const Scen& sc, cons
             bool rem = zone_rem;
             if (f == F_LEFT) rem = rem || (A.cl_hit && n >= A.cn);
             if (f == F_RIGHT) rem = rem || (A.cl_hit && n < A.cn);
+            if (SIDE && f == F_DEF && A.side != F_DEF) rem = rem || (A.cl_hit && (A.side == F_LEFT ? n >= A.cn : n < A.cn));
             const bool fin = c >= 1u && !rem;
             const int bsrc = fin ? (int)((w >> 8) & 255u) : 0, bk = fin ? (int)(w & 255u) : 0, tie = (fin && c >= 2u) ? 1 : 0;   // elect_key layout
             if (rem) dist[coff[f] + n] = INFINITY;
-            par_store<P>(par, ((size_t)par_tab(f) * A.hm + A.j) * kpad + n, bsrc, bk, tie);
+            par_store<P>(par, ((size_t)par_tab(filt_of(f)) * A.hm + A.j) * kpad + n, bsrc, bk, tie);
             any = fin;
         }
         any = __ballot(any) != 0ull;
-        if (lane == 0) best[f * A.hm + A.j] = any ? -2 : -1;           // the goal node of the last layer is evaluated after the sweep
+        if (lane == 0) best[filt_of(f) * A.hm + A.j] = any ? -2 : -1;          // the goal node of the last layer is evaluated after the sweep
     }
 }
 #undef has_tail
@@ -1857,12 +1866,28 @@ __device__ __forceinline__ WavePath team_paths_body(const DevLat& lat_, const De
             if (lane == 0) ts.start_ok[F_PR] = ts.start_ok[F_DEF];
             team_sync<SWN>();
         };
+        // The filters whose frontier can still hold a finite entry (uniform bit set; `default` is in it while it carries the shared prefix).
+        // A filter leaves it for the rest of the sweep when its start node is removed, or BETWEEN RUNS once the reachability entry of the last
+        // layer it advanced through reads -1 (prune, below): an empty frontier stays empty, its layers would only produce +inf candidates,
+        // zero counters and parents nobody reads. The rows of `best` behind a dropped filter are filled with -1 (drop), which is what
+        // the skipped layers would have written and what phase 5 reads when it backs a slot off.
+        unsigned alive = need | (share_prefix ? 1u << F_DEF : 0u);
+        auto drop = [&](unsigned dead, int jn) {              // `dead` stop in front of layer jn: layers jn .. H read "unreachable"
+            // what hangs on `default`: a riding `planning_range` (it takes over the complete layers first), left / right in front of their own layers
+            if (pr_shared && ((dead >> F_DEF) & 1u)) { copy_def_to_pr(jn, (jn - 1) & 1); pr_shared = false; dead |= 1u << F_PR; }
+            if (share_prefix && jn <= jcl && ((dead >> F_DEF) & 1u)) dead |= need & ((1u << F_LEFT) | (1u << F_RIGHT));
+            alive &= ~dead;
+            for (int f = 0; f < NFILT; ++f)
+                if ((dead >> f) & 1u)
+                    for (int r = jn + (SWN == 1 ? lane : tid); r <= H; r += SNT) best[f * hm + r] = -1;
+            team_sync<SWN>();
+        };
         // The layer loop is split into RUNS of layers that share one configuration (set of advancing filters, `planning_range` still
         // riding on `default` or not): the per-layer decisions (which filters advance, first own layer of left / right, ...) are taken
         // once per run by the driver below, the loop of a run is specialised for its filter set at compile time and carries no template
         // logic. (As one loop with the decisions inside, the uniform booleans lived in scalar register PAIRS across the whole sweep and
         // were spilled: ~20 v_readlane reloads per layer.)
-        auto layer_args = [&](int j, const int4& ly, bool from_def, EdgeRegs (&er)[CH]) {
+        auto layer_args = [&](int j, const int4& ly, bool from_def, int side, EdgeRegs (&er)[CH]) {
             LayerArgs A;
             int b = sc.sl + j; if (b >= L) b -= L;
             A.j = j; A.b = b; A.v0 = ly.x; A.Kb = ly.y & 0xffff; A.ne = ly.w - ly.z; A.eb = ly.z; A.kpad = kpad; A.hm = hm; A.cur = j & 1; A.prv = (j - 1) & 1;
@@ -1876,6 +1901,7 @@ __device__ __forceinline__ WavePath team_paths_body(const DevLat& lat_, const De
                     }
             }
             A.from_def = from_def;
+            A.side = side;                                        // (read by the ACT_SIDE body only)
             if (A.fs >= 0) {
                 // previous-solution discount (first layers only): patch the one edge in the register image
 #pragma unroll
@@ -1893,7 +1919,7 @@ __device__ __forceinline__ WavePath team_paths_body(const DevLat& lat_, const De
         // layers j0 .. j1 for the compile-time filter set of `act_tag`; stops in front of the first layer that needs something else:
         // why = 1: `planning_range` has to part from `default` here (a blocked edge, or edges beyond the register image),
         // why = 2: more than 64 nodes in the layer (serial form; runtime LDS plans only). Returns the first layer NOT done.
-        auto run = [&](auto act_tag, int j0, int j1, bool riding, bool from_def, int& why) -> int {
+        auto run = [&](auto act_tag, int j0, int j1, bool riding, bool from_def, int& why, int side = F_DEF) -> int {
             constexpr unsigned ACT = decltype(act_tag)::value;
             why = 0;
             int j = j0;
@@ -1902,7 +1928,7 @@ __device__ __forceinline__ WavePath team_paths_body(const DevLat& lat_, const De
                 const int4 ly = lyc;                               // = lay[j], read with the prefetch of this transition one layer ago
                 if (riding) { if (__ballot(bm != 0u) != 0ull || ly.w - ly.z > CH * SNT) { why = 1; break; } }
                 if constexpr (!P::fixed) { if ((ly.y & 0xffff) > 64) { why = 2; break; } }
-                const LayerArgs A = layer_args(j, ly, from_def && j == j0, er);
+                const LayerArgs A = layer_args(j, ly, from_def && j == j0, side, er);
                 if (j < H) prefetch(j + 1, en, bn);                // global loads in flight during this layer's LDS work
                 if constexpr (SWN == 1 && CH == 3) {               // one-wave batch form: the layer body specialised for 1 / 2 / 3 chunks of edges
                     if (A.ne <= 64) team_layer<P, SWN, CH, ACT, 1>(swk, sc, lp, smem, A, er, bm, swave, lane);
@@ -1915,7 +1941,7 @@ __device__ __forceinline__ WavePath team_paths_body(const DevLat& lat_, const De
         };
         // one layer in the serial form (lane = node): more than 64 nodes in the layer, or a filter set without a specialisation
         auto serial_layer = [&](int j, unsigned actm, bool from_def) {
-            const LayerArgs A = layer_args(j, lay[j], from_def, er);
+            const LayerArgs A = layer_args(j, lay[j], from_def, F_DEF, er);
             if (j < H) prefetch(j + 1, en, bn);
             const SerialK srk = serial_k(lat, lp, smem);          // (rare path: read here, not held across the edge-parallel runs)
             for (int f = swave; f < NFILT; f += SWN) {
@@ -1929,24 +1955,41 @@ __device__ __forceinline__ WavePath team_paths_body(const DevLat& lat_, const De
             }
             rotate();
         };
-        for (int j = 1; j <= H && !LTPL_ABLATED(lp, 2);) {
+        if (!LTPL_ABLATED(lp, 2)) {
+            // a removed start node (an object on the start layer closes a side there): the filter never starts. (A riding `planning_range`
+            // and the sides of a shared prefix have `default`'s start node.)
+            unsigned dead = 0u;
+            for (int f = 0; f < NFILT; ++f) {
+                if (!((alive >> f) & 1u) || (f == F_PR && pr_shared) || (share_prefix && (f == F_LEFT || f == F_RIGHT))) continue;
+                if (!__builtin_amdgcn_readfirstlane(ts.start_ok[f])) dead |= 1u << f;
+            }
+            if (dead) drop(dead, 1);
+        }
+        // (with no filter left, the remaining layers are not swept at all)
+        for (int j = 1; j <= H && alive != 0u && !LTPL_ABLATED(lp, 2);) {
             // filters that advance through layer j; left / right read `default`'s frontier in their first own layer (j == jcl)
             const bool from_def = share_prefix && j == jcl;
             if (pr_shared && from_def) { copy_def_to_pr(j, (j - 1) & 1); pr_shared = false; }
-            unsigned actm = 0;
-            if (((need >> F_PR) & 1u) && !pr_shared) actm |= 1u << F_PR;
-            if (((need >> F_DEF) & 1u) || (share_prefix && j < jcl)) actm |= 1u << F_DEF;
-            if (((need >> F_LEFT) & 1u) && (!share_prefix || j >= jcl)) actm |= 1u << F_LEFT;
-            if (((need >> F_RIGHT) & 1u) && (!share_prefix || j >= jcl)) actm |= 1u << F_RIGHT;
-            const int j1 = (share_prefix && j < jcl) ? jcl - 1 : (from_def ? j : H);       // last layer of this configuration
+            if (from_def && !((need >> F_DEF) & 1u)) alive &= ~(1u << F_DEF);             // the prefix is handed over
+            const bool own_lr = !share_prefix || j >= jcl;
+            unsigned actm = alive;
+            if (pr_shared) actm &= ~(1u << F_PR);
+            if (!own_lr) actm &= ~((1u << F_LEFT) | (1u << F_RIGHT));
+            // last layer of this configuration. The first two layers on which left / right advance on their own are runs of ONE layer: nearly
+            // every side that dies out does so there (census: DESIGN.md section 4.1), and the prune behind the run takes it out of the rest
+            const bool lr_now = (actm & ((1u << F_LEFT) | (1u << F_RIGHT))) != 0u;
+            const int j1 = (share_prefix && j < jcl) ? jcl - 1 : ((from_def || (lr_now && j == jcl + 1)) ? j : H);
             int why = 0, jn;
-            switch (actm) {          // the action templates only produce these filter sets (phase 3); anything else takes the serial form
+            switch (actm) {          // the action templates and the prune only produce these filter sets; anything else takes the serial form
                 case (1u << F_DEF):
                     jn = run(std::integral_constant<unsigned, (1u << F_DEF)>(), j, j1, pr_shared, from_def, why); break;
                 case (1u << F_PR):
                     jn = run(std::integral_constant<unsigned, (1u << F_PR)>(), j, j1, false, from_def, why); break;
-                case (1u << F_PR) | (1u << F_DEF):
-                    jn = run(std::integral_constant<unsigned, (1u << F_PR) | (1u << F_DEF)>(), j, j1, false, from_def, why); break;
+                case (1u << F_PR) | (1u << F_DEF):          // `planning_range` plus ONE more filter -- `default`, or the side that is left once the other
+                case (1u << F_PR) | (1u << F_LEFT):         // one has died out: one body for the three, the filter is a run-time value (LayerArgs::side)
+                case (1u << F_PR) | (1u << F_RIGHT):
+                    jn = run(std::integral_constant<unsigned, (1u << F_PR) | (1u << F_DEF) | ACT_SIDE>(), j, j1, false, from_def, why,
+                             __ffs((int)(actm & ~(1u << F_PR))) - 1); break;
                 case (1u << F_PR) | (1u << F_LEFT) | (1u << F_RIGHT):
                     jn = run(std::integral_constant<unsigned, (1u << F_PR) | (1u << F_LEFT) | (1u << F_RIGHT)>(), j, j1, false, from_def, why); break;
                 default:
@@ -1957,9 +2000,22 @@ __device__ __forceinline__ WavePath team_paths_body(const DevLat& lat_, const De
                     }
                     serial_layer(j, actm, from_def); jn = j + 1; break;
             }
-            if (why == 1) { copy_def_to_pr(jn, (jn - 1) & 1); pr_shared = false; }
-            else if (why == 2) { serial_layer(jn, actm, from_def && jn == j); jn = jn + 1; }   // (the run has already checked that a riding
-                                                                                               //  `planning_range` need not part here)
+            // prune: a filter that advanced and whose last layer has no reachable node is done. (Uniform read: the layer step wrote the entry,
+            // the rotation behind it has synchronised the team.) In front of the parting below, so that a riding `planning_range` dies with
+            // `default`.
+            auto prune = [&](int jdone) {
+                unsigned dead = 0u;
+                for (int f = 0; f < NFILT; ++f)
+                    if (((actm & alive) >> f) & 1u)
+                        if (__builtin_amdgcn_readfirstlane(best[f * hm + jdone]) == -1) dead |= 1u << f;
+                if (dead) drop(dead, jdone + 1);
+            };
+            if (jn > j) prune(jn - 1);
+            if (why == 1) { if (pr_shared) { copy_def_to_pr(jn, (jn - 1) & 1); pr_shared = false; } }
+            else if (why == 2) {                                          // (the run has already checked that a riding `planning_range` need not part here)
+                if ((actm & alive) == 0u) break;                          // the whole run died out, and what hangs on it with it: `alive` is empty
+                serial_layer(jn, actm & alive, from_def && jn == j); prune(jn); jn = jn + 1;
+            }
             j = jn;
         }
         if (pr_shared && !LTPL_ABLATED(lp, 2)) copy_def_to_pr(H + 1, H & 1);        // no blocked edge in the whole range: identical sweeps
