@@ -58,6 +58,10 @@
 //                        the planner's record of ring slot tick % depth. The tick then takes the unfused launch sequence
 //   then paths_pre | path kernel | paths_post (+ vel_a) | velocity stages as in ltpl_fleet_tape_run. Tick k + 1's inputs depend on tick k's
 //   trajectories, so the tape's "next paths_pre inside the last kernel" fusion does not apply: paths_pre is launched on its own.
+//   k_fleet_sim_stats_chunk / k_fleet_sim_stats_merge   (a statistics plan with a period only: ltpl_fleet_sim_stats; the rule: fleet_stats.hpp)
+//                        at the TAIL of every period-th tick, behind every kernel above: one wave64 per (group, chunk of 1024 members)
+//                        walks the plan's measures over the planners' records, one wave64 per (group, measure) folds the chunks'
+//                        partials into a row of the plan's ring. They read records and write buffers of the plan's own
 // The host mirrors of the same arithmetic are graphbasedlocaltrajectoryplanner_amd/sim.py.
 #pragma once
 
@@ -67,6 +71,7 @@
 #include "fleet_safety.hpp"
 #include "fleet_select.hpp"
 #include "fleet_sensor.hpp"
+#include "fleet_stats.hpp"
 #include "fleet_track.hpp"
 #include "fleet_vehicle.hpp"
 
@@ -1604,9 +1609,209 @@ __global__ __launch_bounds__(64) void k_fleet_sim_react_eval(SimDev sd, const do
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// campaign statistics (ltpl_fleet_sim_stats, include/ltpl_hip.h; the rule: fleet_stats.hpp; host mirror: sim.stats_reduce / sim.StatsModel).
+// Measurement only: the kernels read the planners' records and write the plan's own buffers, which no kernel of the tick reads
+// ---------------------------------------------------------------------------------------------------------------------
+static_assert(fleet::STA_DOUBLES == LTPL_FLEET_SIM_STATS_DOUBLES && fleet::kStatsTop == LTPL_FLEET_SIM_STATS_MAX_TOP &&
+              fleet::kStatsBins == LTPL_FLEET_SIM_STATS_MAX_BINS && fleet::STA_FAM_STATE == LTPL_SIM_STATS_STATE, "statistics row layout");
+#define STA_TOP (2 * LTPL_FLEET_SIM_STATS_MAX_TOP)      // doubles of a top-K list: (value, planner) pairs
+struct SimStats {
+    int G, M;                              // groups, measures per group
+    int spec_stride;                       // the spec of (group g, measure m) is g * spec_stride + m: 0 for a plan (every group the same
+                                           // measures), 1 for the hook (M = 1, a spec per case)
+    const int* ch_group; const int* ch_first; const int* ch_cnt;    // [chunks] group, first member (an index into `members`) and members
+    const int* g_choff;                    // [G + 1] the chunks of group g: g_choff[g] .. g_choff[g + 1] - 1, in ascending member order
+    const int* members;                    // the groups' planners, group after group
+    const int* ms_fam; const int* ms_col; const int* ms_bins; const int* ms_dir; const int* ms_topk;      // [specs]
+    const double* ms_edges;                // [specs][17] fleet::stats_edges
+    double* part_row; double* part_top;    // [chunks][M][27], [chunks][M][8][2]
+    const double* rec[fleet::STA_FAM_RECORDS];      // the records of the eight families AT THE LAUNCH (null: not referenced)
+    const unsigned char* state; size_t state_stride;      // the planners' blocks (fleet::PlannerS in front): STATE / failed
+};
+struct StatsLds { double v[fleet::kStatsChunk]; int p[fleet::kStatsChunk]; double e[fleet::kStatsBins + 1]; };   // (e: the measure's edges)
+struct StatsSpec { const double* e; int bins, top_dir, top_k; };
+
+// the fixed tree of the sum order over the 64 lanes: t[l] + t[l + s] for s = 32 .. 1, as a butterfly -- the add commutes bit for bit, so
+// every lane ends with the value the tree leaves in t[0]
+__device__ __forceinline__ double sim_stats_tree(double t)
+{
+    double a, b;
+    swap_pair_f64<32>(t, a, b); t = a + b;
+    swap_pair_f64<16>(t, a, b); t = a + b;
+    t = t + xor_f64<8>(t); t = t + xor_f64<4>(t); t = t + xor_f64<2>(t); t = t + xor_f64<1>(t);
+    return t;
+}
+
+// One measure of one chunk by one wave64 (every lane enters): the cnt <= 1024 members staged in L (member i by lane i & 63: a lane reads
+// what it wrote itself) -> the partial row and top-K list. Counts by ballot / popcount (cell c, under and over are kept by lane c, 16 and
+// 17), extrema by wave_min2 on (value, planner) and (-value, planner), sums lane-serial and then the tree, top-K by rounds of wave_min2
+// over the keys strictly above the last winner
+__device__ __forceinline__ void sim_stats_chunk_wave(int lane, int cnt, const StatsLds& L, const StatsSpec& sp, double* row, double* top)
+{
+    double s = 0.0, q = 0.0, mn = INFINITY, xk = INFINITY;
+    int mp = fleet::kStatsNoPlanner, xp = fleet::kStatsNoPlanner, n = 0, n_nan = 0, n_inf = 0, mine = 0;
+    const int rounds = (cnt + 63) >> 6;
+    for (int j = 0; j < rounds; ++j) {
+        const int i = j * 64 + lane;
+        const bool in = i < cnt;
+        const double v = in ? L.v[i] : NAN;
+        const int p = in ? L.p[i] : fleet::kStatsNoPlanner;
+        const bool nan = fleet::stats_nan(v), fin = fleet::stats_finite(v);
+        const int cls = in ? fleet::stats_class(v, sp.e, sp.bins) : (int)fleet::kStatsNoClass;
+        n_nan += __popcll(__ballot(in && nan)); n_inf += __popcll(__ballot(!nan && !fin)); n += __popcll(__ballot(fin));
+        if (fin) { s = s + v; q = q + v * v; }
+        if (!nan) {
+            if (fleet::stats_before(v, p, mn, mp)) { mn = v; mp = p; }
+            if (fleet::stats_before(-v, p, xk, xp)) { xk = -v; xp = p; }
+        }
+        for (int c = 0; c < fleet::kStatsClasses; ++c) {
+            if (c >= sp.bins && c < fleet::kStatsBins) continue;
+            const int k = __popcll(__ballot(cls == c));
+            if (lane == c) mine += k;
+        }
+    }
+    s = sim_stats_tree(s); q = sim_stats_tree(q);
+    wave_min2(mn, mp); wave_min2(xk, xp);
+    if (lane == 0) {
+        const bool any = mp != fleet::kStatsNoPlanner;
+        row[fleet::STA_N] = (double)n; row[fleet::STA_N_NAN] = (double)n_nan; row[fleet::STA_N_INF] = (double)n_inf;
+        row[fleet::STA_MIN] = mn; row[fleet::STA_ARGMIN] = any ? (double)mp : -1.0;
+        row[fleet::STA_MAX] = -xk; row[fleet::STA_ARGMAX] = any ? (double)xp : -1.0;
+        row[fleet::STA_SUM] = s; row[fleet::STA_SUMSQ] = q;
+    }
+    if (lane < fleet::kStatsBins) row[fleet::STA_HIST + lane] = lane < sp.bins ? (double)mine : 0.0;
+    if (lane == fleet::kStatsUnder) row[fleet::STA_UNDER] = (double)mine;
+    if (lane == fleet::kStatsOver) row[fleet::STA_OVER] = (double)mine;
+    double lk = -INFINITY; int lp = -1;
+    bool open = sp.top_dir != 0;
+    for (int r = 0; r < fleet::kStatsTop; ++r) {
+        double bk = INFINITY; int bp = fleet::kStatsNoPlanner;
+        if (open && r < sp.top_k) {
+            for (int j = 0; j < rounds; ++j) {
+                const int i = j * 64 + lane;
+                if (i < cnt) {
+                    const double v = L.v[i]; const int p = L.p[i];
+                    const double k = fleet::stats_top_key(v, sp.top_dir);
+                    if (!fleet::stats_nan(v) && fleet::stats_before(lk, lp, k, p) && fleet::stats_before(k, p, bk, bp)) { bk = k; bp = p; }
+                }
+            }
+            wave_min2(bk, bp);
+        }
+        open = open && bp != fleet::kStatsNoPlanner;
+        if (lane == 0) { top[2 * r] = open ? fleet::stats_top_key(bk, sp.top_dir) : NAN; top[2 * r + 1] = open ? (double)bp : -1.0; }
+        lk = bk; lp = bp;
+    }
+}
+
+__device__ __forceinline__ StatsSpec sim_stats_spec(const SimStats& st, int spec)
+{
+    return StatsSpec{st.ms_edges + (size_t)spec * (fleet::kStatsBins + 1), st.ms_bins[spec], st.ms_dir[spec], st.ms_topk[spec]};
+}
+
+// the records' base and doubles per planner of a family (a chain of uniform selects: the kernel's argument block is never indexed)
+__device__ __forceinline__ const double* sim_stats_family(const SimStats& st, int fam, int* stride)
+{
+    constexpr int D[fleet::STA_FAM_RECORDS] = {LTPL_FLEET_SIM_TELE_DOUBLES, LTPL_FLEET_SIM_VEH_DOUBLES, LTPL_FLEET_SIM_SENSOR_DOUBLES, LTPL_FLEET_SIM_TRACKER_DOUBLES,
+                                               LTPL_FLEET_SIM_PREDICTOR_DOUBLES, LTPL_FLEET_SIM_SELECTOR_DOUBLES, LTPL_FLEET_SIM_SAFETY_DOUBLES,
+                                               LTPL_FLEET_SIM_REACT_DOUBLES};
+    const double* b = nullptr; int d = 0;
+#pragma unroll
+    for (int k = 0; k < fleet::STA_FAM_RECORDS; ++k) if (fam == k) { b = st.rec[k]; d = D[k]; }
+    *stride = d;
+    return b;
+}
+
+// One workgroup of one wave64 per (group, chunk): the chunk's planners into LDS once, then measure after measure -- the column of the
+// family's [N][D] records (a strided read; the lines of a family fetched for one measure serve its later measures from the cache), the
+// partial row and list of (chunk, measure). RAW (the hook): the values come from an array in member order
+template <bool RAW>
+__device__ __forceinline__ void sim_stats_chunk_body(const SimStats& st, const double* raw)
+{
+    __shared__ StatsLds L;
+    const int ch = blockIdx.x, lane = threadIdx.x;
+    const int g = st.ch_group[ch], first = st.ch_first[ch], cnt = st.ch_cnt[ch];
+    for (int i = lane; i < cnt; i += 64) L.p[i] = st.members[first + i];
+    for (int m = 0; m < st.M; ++m) {
+        const int spec = g * st.spec_stride + m;
+        if constexpr (RAW) {
+            for (int i = lane; i < cnt; i += 64) L.v[i] = raw[first + i];
+        } else {
+            const int fam = st.ms_fam[spec], col = st.ms_col[spec];
+            int stride = 0;
+            const double* base = sim_stats_family(st, fam, &stride);
+            for (int i = lane; i < cnt; i += 64) {
+                const size_t p = (size_t)L.p[i];
+                if (fam == fleet::STA_FAM_STATE)
+                    L.v[i] = reinterpret_cast<const fleet::PlannerS*>(st.state + st.state_stride * p)->err != 0 ? 1.0 : 0.0;
+                else L.v[i] = base[p * (size_t)stride + (size_t)col];
+            }
+        }
+        StatsSpec sp = sim_stats_spec(st, spec);
+        wave_sync_lds();                   // (the previous measure's compares are done with L.e)
+        if (lane <= sp.bins) L.e[lane] = sp.e[lane];
+        wave_sync_lds();
+        sp.e = L.e;                        // every lane compares against the same 17 doubles: LDS broadcasts, not 34 scalar registers
+        const size_t o = (size_t)ch * st.M + m;
+        sim_stats_chunk_wave(lane, cnt, L, sp, st.part_row + o * LTPL_FLEET_SIM_STATS_DOUBLES, st.part_top + o * STA_TOP);
+    }
+}
+__global__ __launch_bounds__(64) void k_fleet_sim_stats_chunk(SimStats st) { sim_stats_chunk_body<false>(st, nullptr); }
+// the test hook (ltpl_fleet_sim_stats_eval): the same body on raw values; k_fleet_sim_stats_merge follows it as it follows the plan's
+__global__ __launch_bounds__(64) void k_fleet_sim_stats_eval(SimStats st, const double* values) { sim_stats_chunk_body<true>(st, values); }
+
+// One wave64 per (group, measure): the partials of the group's chunks folded in ascending chunk order -- lane j < 27 holds column j (counts
+// and sums added serially from +0.0, the lanes of min and max fold (value, planner) and write their planner too), then the top-K list by
+// rounds of wave_min2 over the chunks' lists
+__global__ __launch_bounds__(64) void k_fleet_sim_stats_merge(SimStats st, double* rows, double* tops)
+{
+    const int g = blockIdx.x / st.M, m = blockIdx.x % st.M, lane = threadIdx.x;
+    const int c0 = st.g_choff[g], c1 = st.g_choff[g + 1];
+    const StatsSpec sp = sim_stats_spec(st, g * st.spec_stride + m);
+    double* row = rows + (size_t)blockIdx.x * LTPL_FLEET_SIM_STATS_DOUBLES;
+    double* top = tops + (size_t)blockIdx.x * STA_TOP;
+    const double* part = st.part_row + ((size_t)c0 * st.M + m) * LTPL_FLEET_SIM_STATS_DOUBLES;
+    const size_t step = (size_t)st.M * LTPL_FLEET_SIM_STATS_DOUBLES;
+    if (lane == fleet::STA_MIN || lane == fleet::STA_MAX) {
+        const double sign = lane == fleet::STA_MIN ? 1.0 : -1.0;      // the key of the maximum: (-value, planner)
+        double bk = INFINITY, bv = sign * INFINITY; int bp = -1;
+        for (int c = c0; c < c1; ++c) {
+            const double* pr = part + (size_t)(c - c0) * step;
+            const double v = pr[lane]; const int p = (int)pr[lane + 1];
+            if (p >= 0 && (bp < 0 || fleet::stats_before(sign * v, p, bk, bp))) { bk = sign * v; bv = v; bp = p; }
+        }
+        row[lane] = bv; row[lane + 1] = (double)bp;
+    } else if (lane < LTPL_FLEET_SIM_STATS_DOUBLES && lane != fleet::STA_ARGMIN && lane != fleet::STA_ARGMAX) {
+        double a = 0.0;
+        for (int c = c0; c < c1; ++c) a = a + part[(size_t)(c - c0) * step + lane];
+        row[lane] = a;
+    }
+    const double* ptop = st.part_top;
+    const int entries = (c1 - c0) * fleet::kStatsTop;
+    double lk = -INFINITY; int lp = -1;
+    bool open = sp.top_dir != 0;
+    for (int r = 0; r < fleet::kStatsTop; ++r) {
+        double bk = INFINITY; int bp = fleet::kStatsNoPlanner;
+        if (open && r < sp.top_k) {
+            for (int t = lane; t < entries; t += 64) {
+                const double* e = ptop + (((size_t)(c0 + t / fleet::kStatsTop) * st.M + m) * fleet::kStatsTop + (size_t)(t % fleet::kStatsTop)) * 2;
+                const int p = (int)e[1];
+                if (p >= 0) {
+                    const double k = fleet::stats_top_key(e[0], sp.top_dir);
+                    if (fleet::stats_before(lk, lp, k, p) && fleet::stats_before(k, p, bk, bp)) { bk = k; bp = p; }
+                }
+            }
+            wave_min2(bk, bp);
+        }
+        open = open && bp != fleet::kStatsNoPlanner;
+        if (lane == 0) { top[2 * r] = open ? fleet::stats_top_key(bk, sp.top_dir) : NAN; top[2 * r + 1] = open ? (double)bp : -1.0; }
+        lk = bk; lp = bp;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
-struct SimSnaps;                            // snapshot slots (fleet_branch.hpp, ltpl_fleet_sim_snapshot)
+struct SimSnaps;                           // snapshot slots (fleet_branch.hpp, ltpl_fleet_sim_snapshot)
 static void sim_snaps_free(SimSnaps* s);
 struct SimEvents;                           // scripted events (fleet_events.hpp, ltpl_fleet_sim_events)
 static void sim_events_free(SimEvents* e);
@@ -1689,6 +1894,18 @@ struct FleetSim {
                                             // telemetry, in front of the sensor
     SimModule<SimReact> react;              // parameters, effective scales and records of ltpl_fleet_sim_react: k_fleet_sim_react in front of the
                                             // step kernel, which reads react.dev.eff as opp_scale
+    SimModule<SimStats> stats;              // the plan of ltpl_fleet_sim_stats (groups, chunks, specs, partials, rows and lists); stats.tick
+                                            // counts the fleet's ticks since the plan was set. The records' pointers are filled in at
+                                            // every launch (sim_stats_sources): a module that is set again re-allocates its records
+    struct StatsPlan {                      // its host part
+        int n_chunks = 0, top_k = 0, period = 0, depth = 0;
+        std::vector<int> fam;               // [M] the family of every measure
+        double* rows = nullptr; double* tops = nullptr;      // [G][M][27], [G][M][8][2] of ltpl_fleet_sim_stats_reduce (in stats.allocs)
+        std::vector<void*> ring_allocs;     // the series: [depth][G][M][27], a list of its own (LTPL_SIM_STATS_KEEP_SERIES hands it on)
+        double* ring = nullptr;
+        std::vector<int32_t> ring_tick;     // [depth] the tick of the row in ring slot i (the host knows it at the launch)
+        long long n_rows = 0;               // rows ever written
+    } sp;
 };
 static void fleet_sim_free(FleetSim* s)
 {
@@ -1697,7 +1914,7 @@ static void fleet_sim_free(FleetSim* s)
     sim_events_free(s->events);
     sim_free_list(s->stage_allocs); sim_free_list(s->race_allocs);
     s->tele.clear(); s->rec.clear(); s->noise.clear(); s->veh.clear(); s->sens.clear(); s->trk.clear(); s->pred.clear(); s->sel.clear();
-    s->saf.clear(); s->react.clear();
+    s->saf.clear(); s->react.clear(); s->stats.clear(); sim_free_list(s->sp.ring_allocs);
     for (void* p : s->allocs) (void)hipFree(p);
     if (s->velt.d_buf) (void)hipFree(s->velt.d_buf);
     delete s;
@@ -2022,6 +2239,9 @@ try {
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))
 
+static int sim_stats_sources(ltpl_fleet* f, SimStats* st);        // the records' pointers of this moment; refuses a family that is off
+static int sim_stats_series_row(ltpl_fleet* f, uint32_t tick);    // the two statistics kernels into the next row of the ring
+
 extern "C" int ltpl_fleet_sim_run(ltpl_fleet* f, int32_t n_ticks, double* trace, int32_t doubles_per_tick_planner, float* ms_total)
 try {
     if (!f) return LTPL_ERR_INVALID_ARG;
@@ -2030,6 +2250,10 @@ try {
     if (!f->sim || !f->sim->has_vel) { f->err = "fleet sim: ltpl_fleet_sim_setup and ltpl_fleet_sim_vel first"; return LTPL_ERR_INVALID_ARG; }
     int rc = sim_events_check_run(f);
     if (rc) return rc;
+    if (f->sim->stats.on && f->sim->sp.period > 0) {             // a series over a family that is off: refused before the first tick
+        SimStats probe = f->sim->stats.dev;
+        if ((rc = sim_stats_sources(f, &probe))) return rc;
+    }
     if ((rc = fleet_enter(f))) return rc;
     FleetSim& s = *f->sim;
     const int N = f->D.N;
@@ -2140,6 +2364,10 @@ try {
         if (tr) {
             hipLaunchKernelGGL(k_fleet_digest, dim3(N), dim3(64), 0, st, f->args, tr + 8, (int)LTPL_FLEET_SIM_TRACE_DOUBLES);
             FLEET_TRY(f, hipGetLastError());
+        }
+        if (s.stats.on && s.sp.period > 0) {                     // the tail of the tick: every record of the tick is written
+            const uint32_t index = s.stats.stamp();
+            if ((index + 1u) % (uint32_t)s.sp.period == 0u && (rc = sim_stats_series_row(f, index))) return rc;
         }
     }
     FLEET_TRY(f, hipEventRecord(e1, st));
@@ -3380,5 +3608,304 @@ try {
     if ((rc = b.fetch(ego_out, d_eo, 3 * m))) return rc;
     if ((rc = b.fetch(e_out, d_e, no))) return rc;
     if ((rc = b.fetch(per_opp, d_po, 4 * no))) return rc;
+    return b.finish();
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+// ---------------------------------------------------------------------------------------------------------------------
+// campaign statistics (ltpl_fleet_sim_stats, include/ltpl_hip.h; the rule: fleet_stats.hpp)
+// ---------------------------------------------------------------------------------------------------------------------
+static const char* const kStatsFamily[fleet::STA_FAMILIES] = {"telemetry", "vehicle", "sensor", "tracker", "predictor", "selector", "safety", "react", "state"};
+static const int kStatsColumns[fleet::STA_FAMILIES] = {LTPL_FLEET_SIM_TELE_DOUBLES, LTPL_FLEET_SIM_VEH_DOUBLES, LTPL_FLEET_SIM_SENSOR_DOUBLES,
+                                                       LTPL_FLEET_SIM_TRACKER_DOUBLES, LTPL_FLEET_SIM_PREDICTOR_DOUBLES, LTPL_FLEET_SIM_SELECTOR_DOUBLES,
+                                                       LTPL_FLEET_SIM_SAFETY_DOUBLES, LTPL_FLEET_SIM_REACT_DOUBLES, 1};
+#define STA_MAX_GROUPS 4096
+#define STA_MAX_MEASURES 64
+#define STA_MAX_SERIES_BYTES ((size_t)256 << 20)
+
+// the records of family `fam` as they are now (null: the module is off)
+static const double* sim_stats_records(const FleetSim& s, int fam)
+{
+    switch (fam) {
+    case fleet::STA_FAM_TELEMETRY: return s.tele.on ? s.tele.dev.rec : nullptr;
+    case fleet::STA_FAM_VEHICLE: return s.veh.on ? s.veh.dev.rec : nullptr;
+    case fleet::STA_FAM_SENSOR: return s.sens.on ? s.sens.dev.rec : nullptr;
+    case fleet::STA_FAM_TRACKER: return s.trk.on ? s.trk.dev.rec : nullptr;
+    case fleet::STA_FAM_PREDICTOR: return s.pred.on ? s.pred.dev.rec : nullptr;
+    case fleet::STA_FAM_SELECTOR: return s.sel.on ? s.sel.dev.rec : nullptr;
+    case fleet::STA_FAM_SAFETY: return s.saf.on ? s.saf.dev.rec : nullptr;
+    case fleet::STA_FAM_REACT: return s.react.on ? s.react.dev.rec : nullptr;
+    }
+    return nullptr;
+}
+static int sim_stats_sources(ltpl_fleet* f, SimStats* st)
+{
+    const FleetSim& s = *f->sim;
+    for (double const*& r : st->rec) r = nullptr;
+    for (int fam : s.sp.fam) {
+        if (fam == fleet::STA_FAM_STATE) continue;
+        if (!(st->rec[fam] = sim_stats_records(s, fam))) {
+            f->err = std::string("fleet sim stats: family ") + kStatsFamily[fam] + " is off (a measure of the plan reads its records)";
+            return LTPL_ERR_INVALID_ARG;
+        }
+    }
+    st->state = f->d_state; st->state_stride = f->D.stride;
+    return LTPL_OK;
+}
+// k_fleet_sim_stats_chunk (or, with `raw`, the hook's kernel) and k_fleet_sim_stats_merge on the fleet's stream
+static int sim_stats_launch(ltpl_fleet* f, const SimStats& st, int n_chunks, const double* raw, double* rows, double* tops)
+{
+    hipStream_t sm = f->h->stream;
+    if (n_chunks > 0) {
+        if (raw) hipLaunchKernelGGL(k_fleet_sim_stats_eval, dim3((unsigned)n_chunks), dim3(64), 0, sm, st, raw);
+        else hipLaunchKernelGGL(k_fleet_sim_stats_chunk, dim3((unsigned)n_chunks), dim3(64), 0, sm, st);
+        FLEET_TRY(f, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_fleet_sim_stats_merge, dim3((unsigned)(st.G * st.M)), dim3(64), 0, sm, st, rows, tops);
+    FLEET_TRY(f, hipGetLastError());
+    return LTPL_OK;
+}
+static int sim_stats_series_row(ltpl_fleet* f, uint32_t tick)
+{
+    FleetSim& s = *f->sim;
+    SimStats st = s.stats.dev;
+    int rc = sim_stats_sources(f, &st);
+    if (rc) return rc;
+    const size_t slot = (size_t)(s.sp.n_rows % s.sp.depth), row = (size_t)st.G * st.M * LTPL_FLEET_SIM_STATS_DOUBLES;
+    if ((rc = sim_stats_launch(f, st, s.sp.n_chunks, nullptr, s.sp.ring + slot * row, s.sp.tops))) return rc;
+    s.sp.ring_tick[slot] = (int32_t)tick;
+    ++s.sp.n_rows;
+    return LTPL_OK;
+}
+
+// the chunks of groups with the member offsets off[0 .. G]: group, first member and count per chunk, and the groups' chunk offsets
+struct StatsChunks { std::vector<int> group, first, cnt, g_choff; };
+template <class Off>
+static StatsChunks sim_stats_chunks(const Off* off, int G)
+{
+    StatsChunks c;
+    c.g_choff.assign((size_t)G + 1, 0);
+    for (int g = 0; g < G; ++g) {
+        for (int i = (int)off[g]; i < (int)off[g + 1]; i += fleet::kStatsChunk) {
+            c.group.push_back(g); c.first.push_back(i);
+            c.cnt.push_back((int)off[g + 1] - i < fleet::kStatsChunk ? (int)off[g + 1] - i : (int)fleet::kStatsChunk);
+        }
+        c.g_choff[(size_t)g + 1] = (int)c.group.size();
+    }
+    return c;
+}
+// lo / hi / bins / top_dir of one measure or case; null: fine
+static const char* sim_stats_spec_bad(double lo, double hi, double bins, double top_dir)
+{
+    if (!(bins >= 1.0 && bins <= (double)fleet::kStatsBins) || bins != std::floor(bins)) return "bins must be 1 .. 16";
+    if (!std::isfinite(lo) || !std::isfinite(hi)) return "lo and hi must be finite";
+    if (!(lo < hi)) return "lo must be below hi";
+    if (top_dir != -1.0 && top_dir != 0.0 && top_dir != 1.0) return "top_dir must be -1, 0 or +1";
+    return nullptr;
+}
+
+// every argument is checked before the first HIP call
+static int sim_check_stats(ltpl_fleet* f, const ltpl_fleet_sim_stats_in* in, bool* keep)
+{
+    auto bad = [&](const std::string& why, int code = LTPL_ERR_INVALID_ARG) { f->err = "fleet sim stats: " + why; return code; };
+    *keep = false;
+    if (!f->sim) return bad("ltpl_fleet_sim_setup first");
+    if (!in) return LTPL_OK;
+    const FleetSim& s = *f->sim;
+    const int N = f->D.N;
+    if (in->n_groups < 1 || in->n_groups > STA_MAX_GROUPS) return bad("n_groups must be 1 .. 4096");
+    if (!in->group) return bad("group missing");
+    for (int p = 0; p < N; ++p)
+        if (in->group[p] < -1 || in->group[p] >= in->n_groups) return bad("planner " + std::to_string(p) + ": group must be -1 .. n_groups - 1");
+    if (in->n_measures < 1 || in->n_measures > STA_MAX_MEASURES) return bad("n_measures must be 1 .. 64");
+    if (!in->family || !in->column || !in->lo || !in->hi || !in->bins || !in->top_dir) return bad("a measure array is missing");
+    for (int m = 0; m < in->n_measures; ++m) {
+        const std::string who = "measure " + std::to_string(m) + ": ";
+        const int fam = in->family[m];
+        if (fam < 0 || fam >= fleet::STA_FAMILIES) return bad(who + "unknown family");
+        if (in->column[m] < 0 || in->column[m] >= kStatsColumns[fam])
+            return bad(who + "column outside the " + std::to_string(kStatsColumns[fam]) + " doubles of family " + kStatsFamily[fam]);
+        if (fam != fleet::STA_FAM_STATE && !sim_stats_records(s, fam)) return bad(who + "family " + kStatsFamily[fam] + " is off");
+        if (const char* why = sim_stats_spec_bad(in->lo[m], in->hi[m], (double)in->bins[m], (double)in->top_dir[m])) return bad(who + why);
+    }
+    if (in->top_k < 0 || in->top_k > fleet::kStatsTop) return bad("top_k must be 0 .. 8");
+    if (in->period < 0) return bad("period must not be negative");
+    if (in->period > 0 && in->depth < 1) return bad("depth must be positive with a period");
+    if (in->tick0 < 0) return bad("tick0 must not be negative");
+    if (in->flags & ~(uint32_t)LTPL_SIM_STATS_KEEP_SERIES) return bad("unknown flag");
+    if (in->period > 0) {
+        const size_t row = sizeof(double) * (size_t)in->n_groups * (size_t)in->n_measures * LTPL_FLEET_SIM_STATS_DOUBLES;
+        if ((size_t)in->depth > STA_MAX_SERIES_BYTES / row) return bad("the series would take more than 256 MiB", LTPL_ERR_CAPACITY);
+    }
+    if ((in->flags & LTPL_SIM_STATS_KEEP_SERIES) && s.stats.on && s.sp.period > 0) {
+        if (in->period < 1 || in->n_groups != s.stats.dev.G || in->n_measures != s.stats.dev.M || in->depth != s.sp.depth)
+            return bad("LTPL_SIM_STATS_KEEP_SERIES: n_groups, n_measures and depth must be the plan's, with a period");
+        *keep = true;
+    }
+    return LTPL_OK;
+}
+
+extern "C" int ltpl_fleet_sim_stats(ltpl_fleet* f, const ltpl_fleet_sim_stats_in* in)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    bool keep = false;
+    int rc = sim_check_stats(f, in, &keep);
+    if (rc) return rc;
+    if ((rc = fleet_enter(f))) return rc;
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    FleetSim& s = *f->sim;
+    if (!in) {
+        s.stats.clear(); sim_free_list(s.sp.ring_allocs);
+        s.sp = FleetSim::StatsPlan{};
+        return LTPL_OK;
+    }
+    const int N = f->D.N, G = in->n_groups, M = in->n_measures;
+    std::vector<int> off((size_t)G + 1, 0), members;
+    for (int p = 0; p < N; ++p) if (in->group[p] >= 0) ++off[(size_t)in->group[p] + 1];
+    for (int g = 0; g < G; ++g) off[(size_t)g + 1] += off[(size_t)g];
+    members.resize((size_t)off[(size_t)G]);
+    {
+        std::vector<int> at(off.begin(), off.end() - 1);
+        for (int p = 0; p < N; ++p) if (in->group[p] >= 0) members[(size_t)at[(size_t)in->group[p]]++] = p;     // planners ascending inside a group
+    }
+    const StatsChunks ch = sim_stats_chunks(off.data(), G);
+    const size_t nc = ch.group.size();
+    std::vector<int> topk((size_t)M, in->top_k);
+    std::vector<double> edges((size_t)M * (fleet::kStatsBins + 1), 0.0);
+    for (int m = 0; m < M; ++m) fleet::stats_edges(in->lo[m], in->hi[m], in->bins[m], edges.data() + (size_t)m * (fleet::kStatsBins + 1));
+    // everything new is allocated first; the fleet keeps its previous plan and series unless every step succeeds
+    SimAllocs al, ring;
+    SimStats st{};
+    st.G = G; st.M = M; st.spec_stride = 0;
+    int* pi = nullptr; double* pd = nullptr;
+#define STA_UP(dst, src, n) do { if ((rc = sim_upload(f, al.p, src, (size_t)(n), &pi))) return rc; dst = pi; } while (0)
+    STA_UP(st.members, members.data(), members.size());
+    STA_UP(st.ch_group, ch.group.data(), nc); STA_UP(st.ch_first, ch.first.data(), nc); STA_UP(st.ch_cnt, ch.cnt.data(), nc);
+    STA_UP(st.g_choff, ch.g_choff.data(), G + 1);
+    STA_UP(st.ms_fam, in->family, M); STA_UP(st.ms_col, in->column, M); STA_UP(st.ms_bins, in->bins, M); STA_UP(st.ms_dir, in->top_dir, M);
+    STA_UP(st.ms_topk, topk.data(), M);
+#undef STA_UP
+    if ((rc = sim_upload(f, al.p, edges.data(), edges.size(), &pd))) return rc;
+    st.ms_edges = pd;
+    double* d_rows = nullptr; double* d_tops = nullptr; double* d_ring = nullptr;
+    if ((rc = sim_upload(f, al.p, (const double*)nullptr, nc * M * LTPL_FLEET_SIM_STATS_DOUBLES, &st.part_row))) return rc;
+    if ((rc = sim_upload(f, al.p, (const double*)nullptr, nc * M * STA_TOP, &st.part_top))) return rc;
+    if ((rc = sim_upload(f, al.p, (const double*)nullptr, (size_t)G * M * LTPL_FLEET_SIM_STATS_DOUBLES, &d_rows))) return rc;
+    if ((rc = sim_upload(f, al.p, (const double*)nullptr, (size_t)G * M * STA_TOP, &d_tops))) return rc;
+    if (in->period > 0 && !keep &&
+        (rc = sim_upload(f, ring.p, (const double*)nullptr, (size_t)in->depth * G * M * LTPL_FLEET_SIM_STATS_DOUBLES, &d_ring))) return rc;
+    s.stats.commit(al, st, in->tick0);
+    FleetSim::StatsPlan& sp = s.sp;
+    sp.n_chunks = (int)nc; sp.top_k = in->top_k; sp.period = in->period; sp.depth = in->period > 0 ? in->depth : 0;
+    sp.fam.assign(in->family, in->family + M);
+    sp.rows = d_rows; sp.tops = d_tops;
+    if (!keep) {
+        sim_free_list(sp.ring_allocs);
+        sp.ring_allocs.swap(ring.p);
+        sp.ring = d_ring; sp.n_rows = 0;
+        sp.ring_tick.assign((size_t)sp.depth, 0);
+    }
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+extern "C" int ltpl_fleet_sim_stats_reduce(ltpl_fleet* f, double* rows_out, int32_t doubles_per_row, double* top_out, int32_t top_k)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    auto bad = [&](const std::string& why) { f->err = "fleet sim stats: " + why; return LTPL_ERR_INVALID_ARG; };
+    if (!f->sim) return bad("ltpl_fleet_sim_setup first");
+    FleetSim& s = *f->sim;
+    if (!s.stats.on) return bad("no plan (ltpl_fleet_sim_stats first)");
+    if (!rows_out) return bad("rows_out missing");
+    if (doubles_per_row != LTPL_FLEET_SIM_STATS_DOUBLES) return bad("row size mismatch");
+    if (top_out && top_k != s.sp.top_k) return bad("top_k is not the plan's");
+    SimStats st = s.stats.dev;
+    int rc = sim_stats_sources(f, &st);
+    if (rc) return rc;
+    if ((rc = fleet_enter(f))) return rc;
+    if ((rc = sim_stats_launch(f, st, s.sp.n_chunks, nullptr, s.sp.rows, s.sp.tops))) return rc;
+    const size_t GM = (size_t)st.G * st.M;
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    FLEET_TRY(f, hipMemcpy(rows_out, s.sp.rows, sizeof(double) * GM * LTPL_FLEET_SIM_STATS_DOUBLES, hipMemcpyDeviceToHost));
+    if (top_out && top_k > 0) {
+        std::vector<double> tops(GM * STA_TOP);
+        FLEET_TRY(f, hipMemcpy(tops.data(), s.sp.tops, sizeof(double) * tops.size(), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < GM; ++i) for (size_t k = 0; k < 2 * (size_t)top_k; ++k) top_out[i * 2 * (size_t)top_k + k] = tops[i * STA_TOP + k];
+    }
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+extern "C" int ltpl_fleet_sim_stats_series(ltpl_fleet* f, int32_t* ticks_out, double* rows_out, int32_t doubles_per_row, int32_t* n_rows_out,
+                                           int64_t* n_total_out)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    auto bad = [&](const std::string& why) { f->err = "fleet sim stats: " + why; return LTPL_ERR_INVALID_ARG; };
+    if (!f->sim) return bad("ltpl_fleet_sim_setup first");
+    FleetSim& s = *f->sim;
+    if (!s.stats.on || s.sp.period < 1) return bad("no series (ltpl_fleet_sim_stats with a period first)");
+    if (rows_out && doubles_per_row != LTPL_FLEET_SIM_STATS_DOUBLES) return bad("row size mismatch");
+    const size_t depth = (size_t)s.sp.depth, held = s.sp.n_rows < (long long)depth ? (size_t)s.sp.n_rows : depth;
+    const size_t row = (size_t)s.stats.dev.G * s.stats.dev.M * LTPL_FLEET_SIM_STATS_DOUBLES;
+    if (n_rows_out) *n_rows_out = (int32_t)held;
+    if (n_total_out) *n_total_out = (int64_t)s.sp.n_rows;
+    if (!rows_out && !ticks_out) return LTPL_OK;
+    FLEET_TRY(f, hipSetDevice(f->h->device));
+    FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
+    for (size_t k = 0; k < held; ++k) {                          // oldest first
+        const size_t slot = (size_t)((s.sp.n_rows - (long long)held + (long long)k) % (long long)depth);
+        if (ticks_out) ticks_out[k] = s.sp.ring_tick[slot];
+        if (rows_out) FLEET_TRY(f, hipMemcpy(rows_out + k * row, s.sp.ring + slot * row, sizeof(double) * row, hipMemcpyDeviceToHost));
+    }
+    return LTPL_OK;
+} LTPL_ABI_CATCH(abi_err_of(f))
+
+extern "C" int ltpl_fleet_sim_stats_eval(ltpl_fleet* f, int32_t n_cases, const int32_t* val_off, const double* values, const int32_t* planner_idx,
+                                         const double* spec, double* rows_out, double* top_out)
+try {
+    if (!f) return LTPL_ERR_INVALID_ARG;
+    auto bad = [&](const std::string& why) { f->err = "fleet sim stats eval: " + why; return LTPL_ERR_INVALID_ARG; };
+    if (n_cases < 0) return bad("n_cases must not be negative");
+    if (n_cases == 0) return LTPL_OK;
+    if (n_cases > STA_MAX_GROUPS) return bad("at most 4096 cases");
+    if (!val_off || !spec || !rows_out || !top_out) return bad("an array is missing");
+    if (val_off[0] != 0) return bad("value offsets must start at 0");
+    const size_t m = (size_t)n_cases;
+    for (size_t q = 0; q < m; ++q) {
+        const std::string who = "case " + std::to_string(q) + ": ";
+        if (val_off[q + 1] < val_off[q]) return bad(who + "value offsets must not decrease");
+        const double* sq = spec + 5 * q;
+        if (const char* why = sim_stats_spec_bad(sq[0], sq[1], sq[2], sq[3])) return bad(who + why);
+        if (!(sq[4] >= 0.0 && sq[4] <= (double)fleet::kStatsTop) || sq[4] != std::floor(sq[4])) return bad(who + "top_k must be 0 .. 8");
+    }
+    const size_t nv = (size_t)val_off[m];
+    if (nv > 0 && !values) return bad("values missing");
+    if (planner_idx) for (size_t i = 0; i < nv; ++i) if (planner_idx[i] < 0 || planner_idx[i] == fleet::kStatsNoPlanner) return bad("a planner index must be 0 .. 2^31 - 2");
+    const StatsChunks ch = sim_stats_chunks(val_off, n_cases);
+    const size_t nc = ch.group.size();
+    std::vector<int> members(nv), zero(m, 0), bins(m), dir(m), topk(m);
+    std::vector<double> edges(m * (fleet::kStatsBins + 1), 0.0);
+    for (size_t q = 0; q < m; ++q) {
+        for (int i = val_off[q]; i < val_off[q + 1]; ++i) members[(size_t)i] = planner_idx ? planner_idx[i] : i - val_off[q];
+        const double* sq = spec + 5 * q;
+        bins[q] = (int)sq[2]; dir[q] = (int)sq[3]; topk[q] = (int)sq[4];
+        fleet::stats_edges(sq[0], sq[1], bins[q], edges.data() + q * (fleet::kStatsBins + 1));
+    }
+    int rc = fleet_enter(f);
+    if (rc) return rc;
+    SimHookBlock b(f);
+    const auto d_val = b.in(values, nv); const auto d_mem = b.in(members.data(), nv);
+    const auto d_cg = b.in(ch.group.data(), nc); const auto d_cf = b.in(ch.first.data(), nc); const auto d_cc = b.in(ch.cnt.data(), nc);
+    const auto d_go = b.in(ch.g_choff.data(), m + 1);
+    const auto d_fam = b.in(zero.data(), m); const auto d_bins = b.in(bins.data(), m); const auto d_dir = b.in(dir.data(), m); const auto d_topk = b.in(topk.data(), m);
+    const auto d_edges = b.in(edges.data(), edges.size());
+    const auto d_pr = b.out<double>(nc * LTPL_FLEET_SIM_STATS_DOUBLES); const auto d_pt = b.out<double>(nc * STA_TOP);
+    const auto d_rows = b.out<double>(m * LTPL_FLEET_SIM_STATS_DOUBLES); const auto d_tops = b.out<double>(m * STA_TOP);
+    if ((rc = b.upload())) return rc;
+    SimStats st{};
+    st.G = n_cases; st.M = 1; st.spec_stride = 1;
+    st.ch_group = d_cg; st.ch_first = d_cf; st.ch_cnt = d_cc; st.g_choff = d_go; st.members = d_mem;
+    st.ms_fam = d_fam; st.ms_col = d_fam; st.ms_bins = d_bins; st.ms_dir = d_dir; st.ms_topk = d_topk; st.ms_edges = d_edges;
+    st.part_row = d_pr; st.part_top = d_pt;
+    if ((rc = sim_stats_launch(f, st, (int)nc, d_val, d_rows, d_tops))) return rc;
+    if ((rc = b.fetch(rows_out, d_rows, m * LTPL_FLEET_SIM_STATS_DOUBLES))) return rc;
+    if ((rc = b.fetch(top_out, d_tops, m * STA_TOP))) return rc;
     return b.finish();
 } LTPL_ABI_CATCH(abi_err_of(f))

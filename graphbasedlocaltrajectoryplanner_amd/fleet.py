@@ -23,6 +23,8 @@ from .sim import SELECTOR_DEFAULTS, SELECTOR_DOUBLES, SELECTOR_FIELDS, SELECTOR_
 from .sim import (INCIDENT_DOUBLES, INCIDENT_FIELDS, SAFETY_DEFAULTS, SAFETY_DOUBLES, SAFETY_FIELDS, SAFETY_INCIDENTS, SAFETY_KEEP_STATE,      # noqa: F401
                   SAFETY_PARAMS, safety_dict, safety_start)
 from .sim import REACT_DEFAULTS, REACT_DOUBLES, REACT_FIELDS, REACT_KEEP_STATE, REACT_MAX_OPP, REACT_PARAMS, react_dict, react_start      # noqa: F401
+from .sim import (STATE_FIELDS, STATS_BINS, STATS_DOUBLES, STATS_FAMILIES, STATS_FIELDS, STATS_KEEP_SERIES, STATS_MAX_TOP, stats_column,      # noqa: F401
+                  stats_dict)
 from .sim import pack_events as sim_pack_events
 
 
@@ -87,6 +89,12 @@ class SimSafetyIn(C.Structure):            # ltpl_fleet_sim_safety_in
 
 class SimReactIn(C.Structure):             # ltpl_fleet_sim_react_in
     _fields_ = [("on", C.c_void_p)] + [(k, C.c_void_p) for k in REACT_PARAMS[1:]] + [("tick0", C.c_int32), ("flags", C.c_uint32)]
+
+
+class SimStatsIn(C.Structure):             # ltpl_fleet_sim_stats_in
+    _fields_ = [("n_groups", C.c_int32), ("group", C.c_void_p), ("n_measures", C.c_int32), ("family", C.c_void_p), ("column", C.c_void_p),
+                ("lo", C.c_void_p), ("hi", C.c_void_p), ("bins", C.c_void_p), ("top_dir", C.c_void_p), ("top_k", C.c_int32),
+                ("period", C.c_int32), ("depth", C.c_int32), ("tick0", C.c_int32), ("flags", C.c_uint32)]
 
 
 class SimRecordHead(C.Structure):         # ltpl_fleet_sim_record_head
@@ -171,6 +179,11 @@ class Fleet(Planner):
             f("sim_react").argtypes = [C.c_void_p, C.POINTER(SimReactIn)]
             f("sim_react_read").argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
             f("sim_react_eval").argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 10
+        if hasattr(self.lib, "ltpl_fleet_sim_stats"):
+            f("sim_stats").argtypes = [C.c_void_p, C.POINTER(SimStatsIn)]
+            f("sim_stats_reduce").argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
+            f("sim_stats_series").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+            f("sim_stats_eval").argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6
         if hasattr(self.lib, "ltpl_fleet_friction"):
             f("friction").argtypes = [C.c_void_p, C.POINTER(FrictionIn)]
             f("friction_scale").argtypes = [C.c_void_p, C.c_void_p]
@@ -1102,6 +1115,76 @@ class Fleet(Planner):
                                                ego_out.ctypes.data))
         return (rec[:m], [e_out[off[q]:off[q + 1]].copy() for q in range(m)], [per_opp[off[q]:off[q + 1]].copy() for q in range(m)],
                 ego_out[:m])
+
+    # ---- campaign statistics on the device ---------------------------------------------------------------------------------------------
+    def sim_stats(self, groups, measures=None, top_k=0, period=0, depth=0, tick0=0, keep_series=False, n_groups=None):
+        """A statistics plan (ltpl_fleet_sim_stats; after ``sim_setup``, between runs at any time): ``groups`` [n] gives every planner its
+        group, -1 .. G - 1 (-1: none; G = ``n_groups`` or the largest index + 1); ``measures``: a list of (family, field, lo, hi, bins,
+        top_dir) -- a family of ``sim.STATS_FAMILIES`` whose module is on (or ``"state"`` with its field ``"failed"``), a field of the
+        family's ``*_FIELDS`` table (``"act[2]"`` for an element; or the column), the histogram's range and 1 .. 16 cells, and -1 / 0 / +1
+        for a list of the ``top_k`` (0 .. 8) smallest / no / largest planners. ``sim_stats_reduce`` reduces on demand; with ``period`` > 0
+        ``sim_run`` reduces at the tail of every tick with (tick0 + ticks since this call + 1) % period == 0 into a ring of ``depth``
+        rows (``sim_stats_series``). ``keep_series=True`` keeps the ring of a plan with the same G, number of measures and depth.
+        ``groups=None`` clears the plan. Measurement only: the run is bit-identical with and without it. Host mirror: ``sim.StatsModel``."""
+        if groups is None:
+            self._check(self._fn("sim_stats")(self.handle, None))
+            self._sim_stats = None
+            return
+        i32, f64 = np.int32, np.float64
+        group = np.ascontiguousarray(np.broadcast_to(np.asarray(groups), (self.n_scen,)).astype(i32))
+        G = (int(group.max()) + 1 if group.size else 0) if n_groups is None else int(n_groups)
+        cols = [stats_column(m[0], m[1]) for m in measures]
+        fam = np.ascontiguousarray([c[0] for c in cols], i32)
+        col = np.ascontiguousarray([c[1] for c in cols], i32)
+        lo, hi = np.ascontiguousarray([m[2] for m in measures], f64), np.ascontiguousarray([m[3] for m in measures], f64)
+        bins, top_dir = np.ascontiguousarray([m[4] for m in measures], i32), np.ascontiguousarray([m[5] for m in measures], i32)
+        si = SimStatsIn()
+        si.n_groups, si.group, si.n_measures = G, group.ctypes.data, len(cols)
+        si.family, si.column, si.lo, si.hi, si.bins, si.top_dir = (a.ctypes.data for a in (fam, col, lo, hi, bins, top_dir))
+        si.top_k, si.period, si.depth, si.tick0 = int(top_k), int(period), int(depth), int(tick0)
+        si.flags = STATS_KEEP_SERIES if keep_series else 0
+        self._check(self._fn("sim_stats")(self.handle, C.byref(si)))
+        self._sim_stats = (G, len(cols), int(top_k), int(depth) if int(period) > 0 else 0)
+
+    def _stats_shape(self):
+        shape = getattr(self, "_sim_stats", None)
+        return shape if shape is not None else (1, 1, 0, 0)      # (no plan: the call below refuses)
+
+    def sim_stats_reduce(self, raw=True):
+        """(rows [G, M, 27], tops [G, M, top_k, 2] = value, planner) of the plan, reduced now on the device from the planners' records
+        (ltpl_fleet_sim_stats_reduce; ``sim.STATS_FIELDS``; ``raw=False``: the rows as ``sim.stats_dict``). Unused list entries are
+        (NaN, -1)."""
+        G, M, K, _ = self._stats_shape()
+        rows, tops = np.zeros((G, M, STATS_DOUBLES), np.float64), np.zeros((G, M, max(K, 1), 2), np.float64)
+        self._check(self._fn("sim_stats_reduce")(self.handle, rows.ctypes.data, STATS_DOUBLES, tops.ctypes.data if K else None, K))
+        return (rows if raw else stats_dict(rows)), tops[:, :, :K]
+
+    def sim_stats_series(self):
+        """(ticks [held], rows [held, G, M, 27], rows ever written): the ring of the plan's series, oldest first
+        (ltpl_fleet_sim_stats_series)."""
+        G, M, _, depth = self._stats_shape()
+        ticks, rows = np.zeros(max(depth, 1), np.int32), np.zeros((max(depth, 1), G, M, STATS_DOUBLES), np.float64)
+        held, total = C.c_int32(0), C.c_int64(0)
+        self._check(self._fn("sim_stats_series")(self.handle, ticks.ctypes.data, rows.ctypes.data, STATS_DOUBLES, C.byref(held), C.byref(total)))
+        return ticks[:held.value].copy(), rows[:held.value].copy(), int(total.value)
+
+    def sim_stats_eval(self, values, spec, planners=None):
+        """The rule's test hook (ltpl_fleet_sim_stats_eval): independent cases on the device, each one group and one measure on raw values.
+        Per case ``values`` [n_q] and ``spec`` = (lo, hi, bins, top_dir, top_k); ``planners`` (or None: the positions): per case the
+        planner index of every value. Returns (rows [m, 27], tops [m, 8, 2]); equals ``sim.stats_reduce`` bit for bit."""
+        values = [np.asarray(v, np.float64).reshape(-1) for v in values]
+        m = len(values)
+        k = max(m, 1)
+        off = np.ascontiguousarray(np.concatenate(([0], np.cumsum([v.size for v in values]))).astype(np.int32))
+        flat = np.ascontiguousarray(np.concatenate(values + [np.zeros(1)]))
+        spec = np.ascontiguousarray(np.asarray(spec, np.float64).reshape(m, 5))
+        idx = None
+        if planners is not None:
+            idx = np.ascontiguousarray(np.concatenate([np.asarray(p).reshape(-1) for p in planners] + [np.zeros(1)]).astype(np.int32))
+        rows, tops = np.zeros((k, STATS_DOUBLES), np.float64), np.zeros((k, STATS_MAX_TOP, 2), np.float64)
+        self._check(self._fn("sim_stats_eval")(self.handle, m, off.ctypes.data, flat.ctypes.data, None if idx is None else idx.ctypes.data,
+                                               spec.ctypes.data, rows.ctypes.data, tops.ctypes.data))
+        return rows[:m], tops[:m]
 
     # ---- friction maps on the device ------------------------------------------------------------------------------------------------
     def friction(self, maps, map_idx=None, scale=1.0):

@@ -1864,3 +1864,181 @@ class ReactModel(object):
 
     def as_dict(self):
         return react_dict(self.rec)
+
+
+# ---- campaign statistics (ltpl_fleet_sim_stats, include/ltpl_hip.h; csrc/fleet_stats.hpp) ---------------------------------------------------
+# name, index, integer valued: the row of ltpl_fleet_sim_stats_reduce (LTPL_FLEET_SIM_STATS_DOUBLES = 27 per group and measure; hist: 16 cells)
+STATS_FIELDS = (("n", 0, True), ("n_nan", 1, True), ("n_inf", 2, True), ("min", 3, False), ("argmin", 4, True), ("max", 5, False),
+                ("argmax", 6, True), ("sum", 7, False), ("sumsq", 8, False), ("under", 9, True), ("over", 10, True), ("hist", 11, True))
+STATS_DOUBLES = 27
+STATS_BINS = 16                           # LTPL_FLEET_SIM_STATS_MAX_BINS
+STATS_MAX_TOP = 8                         # LTPL_FLEET_SIM_STATS_MAX_TOP
+STATS_CHUNK, STATS_LANES = 1024, 64       # the sum order: chunks of 1024 members, 64 lane sums per chunk
+STATS_KEEP_SERIES = 1                     # LTPL_SIM_STATS_KEEP_SERIES
+STATS_FAMILIES = ("telemetry", "vehicle", "sensor", "tracker", "predictor", "selector", "safety", "react", "state")      # LTPL_SIM_STATS_*
+STATE_FIELDS = (("failed", 0, True),)     # the pseudo-family: 1.0 for a planner whose error word is set
+
+
+def _stats_family_columns():
+    cols = {}
+    for fam, fields in (("telemetry", TELEMETRY_FIELDS), ("vehicle", VEHICLE_FIELDS), ("sensor", SENSOR_FIELDS), ("tracker", TRACKER_FIELDS),
+                        ("predictor", PREDICTOR_FIELDS), ("selector", SELECTOR_FIELDS), ("safety", SAFETY_FIELDS), ("react", REACT_FIELDS),
+                        ("state", STATE_FIELDS)):
+        cols[fam] = {f[0]: int(f[1]) for f in fields}
+    return cols
+
+
+STATS_FAMILY_DOUBLES = dict(telemetry=TELEMETRY_DOUBLES, vehicle=VEHICLE_DOUBLES, sensor=SENSOR_DOUBLES, tracker=TRACKER_DOUBLES,
+                            predictor=PREDICTOR_DOUBLES, selector=SELECTOR_DOUBLES, safety=SAFETY_DOUBLES, react=REACT_DOUBLES, state=1)
+
+
+def stats_column(family, field):
+    """(family id, column) of a measure: ``family`` a name of ``STATS_FAMILIES`` (or its id), ``field`` a name of the family's ``*_FIELDS``
+    table, ``"name[k]"`` for element k of a field with several doubles (``"act[2]"``, ``"hist[3]"``), or the column itself."""
+    fam = STATS_FAMILIES[family] if isinstance(family, (int, np.integer)) else str(family)
+    if fam not in STATS_FAMILIES:
+        raise ValueError("stats: unknown family %r" % (family,))
+    if isinstance(field, (int, np.integer)):
+        return STATS_FAMILIES.index(fam), int(field)
+    name, k = str(field), 0
+    if name.endswith("]") and "[" in name:
+        name, k = name[:-1].split("[")
+        k = int(k)
+    cols = _stats_family_columns()[fam]
+    if name not in cols:
+        raise ValueError("stats: family %s has no field %r" % (fam, field))
+    return STATS_FAMILIES.index(fam), cols[name] + k
+
+
+def stats_edges(lo, hi, bins):
+    """The bins + 1 edges e_j = lo + ((hi - lo) * j) / bins, in exactly this order."""
+    lo, hi = float(lo), float(hi)
+    return [lo + ((hi - lo) * float(j)) / float(int(bins)) for j in range(int(bins) + 1)]
+
+
+def stats_sum(x):
+    """The sum of the doubles ``x`` (member order; a skipped member as +0.0) in THE order of csrc/fleet_stats.hpp: chunks of 1024, inside
+    a chunk 64 lane sums (lane i mod 64, serially in ascending i from +0.0), folded by t[l] += t[l + s] for s = 32 .. 1, the chunk sums
+    added serially from +0.0. Adding +0.0 for a skipped member leaves every bit: a sum that starts at +0.0 is never -0.0."""
+    x = np.asarray(x, np.float64).reshape(-1)
+    nch = (x.size + STATS_CHUNK - 1) // STATS_CHUNK
+    a = np.zeros(nch * STATS_CHUNK)
+    a[:x.size] = x
+    a = a.reshape(nch, STATS_CHUNK // STATS_LANES, STATS_LANES)
+    with np.errstate(over="ignore", invalid="ignore"):
+        t = np.zeros((nch, STATS_LANES))
+        for j in range(a.shape[1]):
+            t = t + a[:, j, :]
+        s = STATS_LANES // 2
+        while s >= 1:
+            t = t[:, :s] + t[:, s:2 * s]
+            s //= 2
+        total = 0.0
+        for c in range(nch):
+            total = total + float(t[c, 0])
+    return total
+
+
+def stats_reduce(values, planners, lo, hi, bins, top_dir, top_k):
+    """One group and one measure on the host, bit for bit what k_fleet_sim_stats_chunk / _merge leave: (row [27], top [8, 2]).
+    ``values`` in member order, ``planners`` their planner indices (None: the positions), distinct."""
+    v = np.asarray(values, np.float64).reshape(-1)
+    p = np.arange(v.size, dtype=np.int64) if planners is None else np.asarray(planners, np.int64).reshape(-1)
+    bins, top_dir, top_k = int(bins), int(top_dir), int(top_k)
+    row = np.zeros(STATS_DOUBLES)
+    top = np.full((STATS_MAX_TOP, 2), np.nan)
+    top[:, 1] = -1.0
+    nan = np.isnan(v)
+    fin = np.isfinite(v)
+    row[0], row[1], row[2] = fin.sum(), nan.sum(), (~nan & ~fin).sum()
+    row[3], row[4], row[5], row[6] = np.inf, -1.0, -np.inf, -1.0
+    ok = np.flatnonzero(~nan)
+    if ok.size:
+        for at, val in ((3, v[ok].min()), (5, v[ok].max())):
+            tie = ok[v[ok] == val]                               # (== : a -0.0 ties with a +0.0)
+            i = tie[np.argmin(p[tie])]
+            row[at], row[at + 1] = v[i], p[i]
+    with np.errstate(over="ignore"):
+        good = np.where(fin, v, 0.0)
+        row[7] = stats_sum(good)
+        row[8] = stats_sum(good * good)
+    e = stats_edges(lo, hi, bins)
+    with np.errstate(invalid="ignore"):
+        under, over = ~nan & (v < e[0]), ~nan & (v >= e[bins])
+        cell = np.zeros(v.size, np.int64)
+        for j in range(1, bins):
+            cell += (e[j] <= v)
+    row[9], row[10] = under.sum(), over.sum()
+    inside = fin & ~under & ~over
+    row[11:11 + STATS_BINS] = np.bincount(cell[inside], minlength=STATS_BINS)[:STATS_BINS]
+    if top_dir != 0 and top_k > 0 and ok.size:
+        key = -v[ok] if top_dir > 0 else v[ok]
+        order = ok[np.lexsort((p[ok], key))][:top_k]
+        top[:order.size, 0], top[:order.size, 1] = v[order], p[order]
+    return row, top
+
+
+def stats_dict(rows):
+    """[..., 27] rows as a dict of named arrays (counts as int64; ``hist``: [..., 16]) plus ``mean`` = sum / n and ``var`` = sumsq / n -
+    mean^2, computed here on the host (NaN where n == 0)."""
+    rows = np.asarray(rows, np.float64)
+    out = {name: (rows[..., i].astype(np.int64) if is_int else rows[..., i].copy()) for name, i, is_int in STATS_FIELDS if name != "hist"}
+    out["hist"] = rows[..., 11:11 + STATS_BINS].astype(np.int64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        n = rows[..., 0]
+        out["mean"] = np.where(n > 0, rows[..., 7] / n, np.nan)
+        out["var"] = np.where(n > 0, rows[..., 8] / n - out["mean"] * out["mean"], np.nan)
+    return out
+
+
+class StatsModel(object):
+    """Host mirror of a statistics plan (ltpl_fleet_sim_stats): ``groups`` [n] in -1 .. G - 1, ``measures`` a list of (family, field, lo,
+    hi, bins, top_dir) as ``Fleet.sim_stats`` takes them, ``top_k``, ``period``, ``depth``, ``tick0``. ``reduce(records, failed)`` takes
+    the record arrays a test has from the ``_read`` calls or the other mirrors -- a dict family name -> [n, D] -- and ``failed`` [n] (the
+    STATE family; default: nobody) and returns (rows [G, M, 27], tops [G, M, top_k, 2]). ``tick(records, failed)`` is one fleet tick: the
+    index advances, and on the ticks of the rule ((index + 1) % period == 0) a row enters the ring; ``series()`` returns (ticks, rows
+    [held, G, M, 27], rows ever written), oldest first."""
+
+    def __init__(self, groups, measures, top_k=0, period=0, depth=0, tick0=0, n_groups=None):
+        self.group = np.asarray(groups, np.int64).reshape(-1)
+        self.G = int(self.group.max()) + 1 if n_groups is None else int(n_groups)
+        self.members = [np.flatnonzero(self.group == g) for g in range(self.G)]      # planners ascending inside a group
+        self.measures = [stats_column(m[0], m[1]) + (float(m[2]), float(m[3]), int(m[4]), int(m[5])) for m in measures]
+        self.top_k, self.period, self.depth, self.index = int(top_k), int(period), int(depth), int(tick0)
+        self.ring, self.ring_tick, self.n_rows = [], [], 0
+
+    def values(self, records, failed, fam, col):
+        if STATS_FAMILIES[fam] == "state":
+            f = np.zeros(self.group.size) if failed is None else np.asarray(failed).reshape(-1)
+            return np.where(f != 0, 1.0, 0.0)
+        return np.asarray(records[STATS_FAMILIES[fam]], np.float64).reshape(self.group.size, -1)[:, col]
+
+    def reduce(self, records, failed=None):
+        rows = np.zeros((self.G, len(self.measures), STATS_DOUBLES))
+        tops = np.zeros((self.G, len(self.measures), self.top_k, 2))
+        for m, (fam, col, lo, hi, bins, top_dir) in enumerate(self.measures):
+            col_v = self.values(records, failed, fam, col)
+            for g, mem in enumerate(self.members):
+                rows[g, m], top = stats_reduce(col_v[mem], mem, lo, hi, bins, top_dir, self.top_k)
+                tops[g, m] = top[:self.top_k]
+        return rows, tops
+
+    def tick(self, records, failed=None):
+        index = self.index
+        self.index += 1
+        if self.period > 0 and (index + 1) % self.period == 0:
+            row = self.reduce(records, failed)[0]
+            if len(self.ring) < self.depth:
+                self.ring.append(row)
+                self.ring_tick.append(index)
+            else:
+                self.ring[self.n_rows % self.depth], self.ring_tick[self.n_rows % self.depth] = row, index
+            self.n_rows += 1
+            return True
+        return False
+
+    def series(self):
+        held = len(self.ring)
+        order = [(self.n_rows - held + k) % self.depth for k in range(held)] if held else []
+        return (np.asarray([self.ring_tick[i] for i in order], np.int32), np.asarray([self.ring[i] for i in order]).reshape(held, self.G, -1, STATS_DOUBLES),
+                self.n_rows)

@@ -68,7 +68,8 @@ extern "C" {
                                      ltpl_fleet_sim_predictor / _predictor_read / _predictor_eval,
                                      ltpl_fleet_sim_selector / _selector_read / _selector_eval,
                                      ltpl_fleet_sim_safety / _safety_read / _safety_eval,
-                                     ltpl_fleet_sim_react / _react_read / _react_eval */
+                                     ltpl_fleet_sim_react / _react_read / _react_eval,
+                                     ltpl_fleet_sim_stats / _stats_reduce / _stats_series / _stats_eval */
 
 /* status codes */
 #define LTPL_OK               0
@@ -1642,6 +1643,103 @@ int ltpl_fleet_sim_react_read(ltpl_fleet* fleet, double* out, int32_t doubles_pe
  * passive opponent); ego_out[q][3] = s_e, d_e, has. */
 int ltpl_fleet_sim_react_eval(ltpl_fleet* fleet, int32_t n_cases, const double* params, const double* ego, const double* dt, const int32_t* tick,
                               const int32_t* opp_off, const double* opp, double* rec, double* e_out, double* per_opp, double* ego_out);
+
+/* ------------------------------------------------------------------------------------------------------------------------------------------
+ * Additive to ABI v9 -- CAMPAIGN STATISTICS: chosen fields of the planners' records reduced on the device per group of planners
+ * (csrc/fleet_sim.hpp: k_fleet_sim_stats_chunk / k_fleet_sim_stats_merge; the rule: csrc/fleet_stats.hpp). A fleet is one situation fanned
+ * out into thousands of planners; judging it took eight _read calls (129 doubles per planner, eight stream synchronisations) and a host
+ * pass. A PLAN names groups of planners and measures; ltpl_fleet_sim_stats_reduce reduces now, and with a period ltpl_fleet_sim_run reduces
+ * at the tail of every period-th tick into a ring, with no host round trip. Measurement only: no kernel of the tick reads what the
+ * statistics write, and the run is bit-identical with and without a plan. Off by default.
+ * ARITHMETIC: fp64, + - * / and comparisons only, one fixed order (the library is built with -ffp-contract=off), no floating-point
+ * atomics: the host mirror sim.stats_reduce / sim.StatsModel and the device agree to the last bit, for every launch geometry.
+ * THE PLAN: n_groups G (1 .. 4096); group[p] in -1 .. G - 1 per planner (-1: in no group); the host turns it into group offsets and a
+ * member list, planners ascending inside a group, uploaded once. n_measures M (1 .. 64), each a family (LTPL_SIM_STATS_*: the eight record
+ * families, whose module must be on, and LTPL_SIM_STATS_STATE with its one column 0, `failed`: 1.0 when the planner's error word is set --
+ * the word that makes the planner skip its ticks -- else 0.0), a column of the family's record, lo < hi (finite), bins (1 .. 16) and
+ * top_dir (-1: the smallest, +1: the largest, 0: no list). top_k (0 .. 8) entries per list. period (0: no series), depth (rows of the
+ * ring), tick0 (the plan's tick of the next fleet tick).
+ * ONE VALUE v of member i (its position in the group) and planner p:
+ *   | NaN (v != v) | counted in n_nan; takes part in nothing else                                                                   |
+ *   | +-inf        | counted in n_inf; takes part in min / max / top-K and in under / over; not in n, sum, sumsq or the cells         |
+ *   | finite       | n += 1, sum, sumsq (v * v), min / max, one histogram cell                                                       |
+ * MINIMUM on the key (value, planner), MAXIMUM on (-value, planner): a strict compare of the values decides, ties go to the lower planner;
+ * a -0.0 that ties with a +0.0 keeps the bits of the lower planner's value. An empty group: min = +inf, argmin = -1, max = -inf, argmax = -1.
+ * HISTOGRAM: edges e_j = lo + ((hi - lo) * j) / bins for j = 0 .. bins, in exactly this order; under counts v < e_0, cell j counts
+ * e_j <= v < e_(j+1), over counts v >= e_bins.
+ * TOP-K: the K smallest (top_dir -1) or largest (+1) keys of the group, in order; a NaN never enters, an infinity may; unused entries are
+ * (NaN, -1).
+ * SUM ORDER of sum and sumsq: members are cut into chunks of 1024 consecutive positions; inside a chunk lane l = i mod 64 adds its
+ * values serially in ascending i from +0.0 (a skipped value adds nothing); the 64 lane sums are folded by the tree t[l] = t[l] + t[l + s]
+ * for l < s, s = 32, 16, 8, 4, 2, 1; the chunk sums are added serially in ascending chunk order from +0.0.
+ * THE ROW, LTPL_FLEET_SIM_STATS_DOUBLES doubles: [0] n [1] n_nan [2] n_inf [3] min [4] argmin [5] max [6] argmax [7] sum [8] sumsq [9] under
+ * [10] over [11 .. 26] hist (unused cells 0).
+ * THE SERIES: with period > 0 ltpl_fleet_sim_run launches the two kernels at the tail of every tick whose index satisfies
+ * (index + 1) % period == 0, behind every other kernel of the tick; index = tick0 + the fleet's ticks since the plan was set (it advances
+ * in every tick). The rows [G][M][27] go into slot (rows written) mod depth of a ring, with the tick; no lists. A run that would reduce a
+ * family that is off is refused before its first tick.
+ *   | with                          | what happens                                                                                 |
+ *   | ltpl_fleet_sim_setup          | the plan is cleared                                                                          |
+ *   | a module set again            | the records' addresses are taken at every launch: the plan follows                           |
+ *   | a module switched off         | ltpl_fleet_sim_stats_reduce and a run with a period refuse, naming the family, until the plan |
+ *   |                               | is cleared or replaced or the module is back                                                 |
+ *   | snapshot / branch / restore   | the plan holds no per-planner state: nothing travels, plan and series stay                   |
+ *   | ltpl_fleet_sim_race / _predictor | kept                                                                                      |
+ *   | events                        | no new kind                                                                                  |
+ *   | a failed planner              | its records stay and are reduced like any other; STATE / failed counts or excludes them      |
+ *   | a planner whose module has on == 0 | contributes its start-state record; groups are the caller's tool to leave it out       |
+ * LIMITS: no quantiles beyond the histogram; one device (the rows of disjoint groups of several fleets concatenate); no event is
+ * triggered by a statistic; the incident rings and the tracker's tables are not reduced.
+ * THE CALL: after ltpl_fleet_sim_setup at any time between runs; in == NULL clears the plan. Every argument is checked before the first
+ * HIP call, each with a message that names it; a series above 256 MiB is LTPL_ERR_CAPACITY. Everything new is allocated before anything
+ * old is freed; a failed call keeps the previous plan and series. With LTPL_SIM_STATS_KEEP_SERIES (and a plan with a series set) the ring,
+ * its ticks and its count stay; n_groups, n_measures and depth must then be the plan's and period > 0 (else LTPL_ERR_INVALID_ARG).
+ * ------------------------------------------------------------------------------------------------------------------------------------------ */
+#define LTPL_FLEET_SIM_STATS_DOUBLES 27
+#define LTPL_FLEET_SIM_STATS_MAX_BINS 16
+#define LTPL_FLEET_SIM_STATS_MAX_TOP 8
+#define LTPL_SIM_STATS_TELEMETRY 0
+#define LTPL_SIM_STATS_VEHICLE   1
+#define LTPL_SIM_STATS_SENSOR    2
+#define LTPL_SIM_STATS_TRACKER   3
+#define LTPL_SIM_STATS_PREDICTOR 4
+#define LTPL_SIM_STATS_SELECTOR  5
+#define LTPL_SIM_STATS_SAFETY    6
+#define LTPL_SIM_STATS_REACT     7
+#define LTPL_SIM_STATS_STATE     8
+#define LTPL_SIM_STATS_KEEP_SERIES 1u
+typedef struct {
+    int32_t n_groups;                /* G: 1 .. 4096                                                   */
+    const int32_t* group;            /* [n] -1 .. G - 1                                                */
+    int32_t n_measures;              /* M: 1 .. 64                                                     */
+    const int32_t* family;           /* [M] LTPL_SIM_STATS_*                                           */
+    const int32_t* column;           /* [M] a column of the family's record                            */
+    const double* lo;                /* [M] finite, lo < hi                                            */
+    const double* hi;                /* [M]                                                            */
+    const int32_t* bins;             /* [M] 1 .. 16                                                    */
+    const int32_t* top_dir;          /* [M] -1 / 0 / +1                                                */
+    int32_t top_k;                   /* 0 .. 8                                                         */
+    int32_t period;                  /* >= 0; 0: no series                                             */
+    int32_t depth;                   /* >= 1 with a period                                             */
+    int32_t tick0;                   /* >= 0: the plan's tick of the next fleet tick                   */
+    uint32_t flags;                  /* LTPL_SIM_STATS_KEEP_SERIES                                     */
+} ltpl_fleet_sim_stats_in;
+int ltpl_fleet_sim_stats(ltpl_fleet* fleet, const ltpl_fleet_sim_stats_in* in);
+/* reduces now: rows_out [G][M][LTPL_FLEET_SIM_STATS_DOUBLES]; top_out (or NULL) [G][M][top_k][2] = value, planner, top_k the plan's.
+ * Synchronises the handle's stream. No simulation, no plan, a wrong row size or top_k, a referenced family that is off (the message
+ * names it): LTPL_ERR_INVALID_ARG. */
+int ltpl_fleet_sim_stats_reduce(ltpl_fleet* fleet, double* rows_out, int32_t doubles_per_row, double* top_out, int32_t top_k);
+/* the ring, oldest first: ticks_out [depth], rows_out [depth][G][M][27] (both may be NULL: the counts only); *n_rows_out: the rows held,
+ * *n_total_out: the rows ever written. No simulation, no plan with a period, a wrong row size: LTPL_ERR_INVALID_ARG. */
+int ltpl_fleet_sim_stats_series(ltpl_fleet* fleet, int32_t* ticks_out, double* rows_out, int32_t doubles_per_row, int32_t* n_rows_out,
+                                int64_t* n_total_out);
+/* the test hook of the rule (k_fleet_sim_stats_eval in k_fleet_sim_stats_chunk's place: the same device functions on raw values, then
+ * k_fleet_sim_stats_merge; needs a fleet and no simulation): case q (at most 4096) reduces values[val_off[q] .. val_off[q + 1]) as one
+ * group and one measure with spec[q][5] = lo, hi, bins, top_dir, top_k (checked as above); planner_idx (or NULL: the position in the case)
+ * gives every value its planner, 0 .. 2^31 - 2, distinct inside a case. rows_out [n_cases][27]; top_out [n_cases][8][2], entries from
+ * top_k on (NaN, -1). */
+int ltpl_fleet_sim_stats_eval(ltpl_fleet* fleet, int32_t n_cases, const int32_t* val_off, const double* values, const int32_t* planner_idx,
+                              const double* spec, double* rows_out, double* top_out);
 
 #ifdef __cplusplus
 }
