@@ -143,7 +143,9 @@ typedef double ke_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ ke_t make_ke(double k, double e) { ke_t v; v.x = k; v.y = e; return v; }
 // 1 / |kappa|: hardware reciprocal + ONE Newton step. Measured on gfx950 over 4 M values of |kappa| between 1e-12 and 4e3 1/m
 // (tools/ubench/rcp/rcp_f64.hip, profiles/r06c_rcp_f64.txt): v_rcp_f64 alone 4.6e-8 relative, one step 2.2e-15 (20 ulp), two steps correctly
-// rounded. The limit speed ay / |kappa| enters results that are compared at 1e-5 (element-wise error of vx against the oracle ~1e-13 with either);
+// rounded. The limit speed ay / |kappa| is a row of the result wherever no sweep lowers it: tests/test_gpu_vel_ref.py holds those rows to the
+// long-double reference at 5e-10 (exponent 1; vel_cases.BOUNDS, class "regular"), which one step meets (20 ulp = 2e-15 in v^2) and the bare
+// v_rcp_f64 does not (4.6e-8 in v^2 = 2.3e-8 in v: passes the oracle comparisons at 1e-5, fails there);
 // the second step was two dependent fma on the lane kernels' serial chain: +1.7 % ticks/s without it (same-box A/B, profiles/r06b_ab_bench.txt).
 __device__ __forceinline__ double ke_rcp(const ke_t& r)        // (0 -> NaN: treated as +inf by the callers' fmin)
 {

@@ -41,7 +41,8 @@ struct LaneProf {
     const ke_t* KE;                       // tile-strided: element i at [i * 64]
 };
 
-// a / b with the hardware reciprocal and two Newton steps (~1 ulp; the velocity stage is checked to 1e-5 relative). b = 0
+// a / b with the hardware reciprocal and two Newton steps (~1 ulp; the rows it produces are limit speeds, checked against the long-double
+// reference at 3e-10 .. 5e-10 relative -- tests/vel_cases.py BOUNDS, class "regular" -- where one step fewer leaves 1e-15, none 2e-8). b = 0
 // yields NaN, which the callers' `!(w < vmax2)` clamp treats like +inf.
 __device__ __forceinline__ double fast_div(double a, double b)
 {
@@ -464,7 +465,7 @@ __device__ __forceinline__ LaneFollowOut lane_follow_controlled(const DevLat& la
     const double vel0 = grl[(size_t)idx_s_opp * 5 + 4];
     double wopp = fmin(v_obj, vel0); wopp *= wopp;
     double opp_stop = 0.0;
-    for (int base = 0; base < G && wopp > 0.01; base += LCH) {
+    for (int base = 0; base < G && wopp > W_STANDSTILL; base += LCH) {
         double kr[LCH], lr[LCH];
 #pragma unroll
         for (int c = 0; c < LCH; ++c) {
@@ -474,7 +475,7 @@ __device__ __forceinline__ LaneFollowOut lane_follow_controlled(const DevLat& la
 #pragma unroll
         for (int c = 0; c < LCH; ++c) {
             const int k = base + c;
-            if (k < G && wopp > 0.01) {
+            if (k < G && wopp > W_STANDSTILL) {
                 opp_stop += lr[c];
                 if (k + 1 >= G) wopp = 0.0;
                 else {
@@ -510,7 +511,7 @@ __device__ __forceinline__ LaneFollowOut lane_follow_controlled(const DevLat& la
                     const double wv = braking ? w : 0.0;
                     P2[(size_t)i * 64] = wv;
                     if (first_le < 0 && wv <= wctl) first_le = i;
-                    if (counting) { if (wv > 0.01) ego_stop += er[c]; else counting = false; }
+                    if (counting) { if (wv > W_STANDSTILL) ego_stop += er[c]; else counting = false; }
                     if (searching) { if (i < n - 1 && s_run < s_stop) stop_idx = i + 1; else searching = false; }
                     if (i == n - 1) s_last = s_run; // s[n - 1]
                     s_run += er[c];                 // s[i + 1]

@@ -3,6 +3,11 @@
 // velocity stage of the fused tick (tick_vel_stage). Included by ltpl_hip.hip behind the path kernel (needs DevLat, DevPathsIn / Out,
 // WavePath, wave_ops.hpp).
 #pragma once
+// Standstill in the w = v^2 state. The reference compares v > 0.1; the kernels compare w > fl(0.1 * 0.1) = 0.010000000000000002, NOT the
+// literal 0.01: for v = 0.1 exactly (a v_start or v_obj of 0.1 m/s) fl(v * v) exceeds 0.01 and the car would count as moving where the
+// reference has it stopped (ego stop distance one element longer, another branch, vel_bound flipped: tests/vel_cases.py "v_start == 0.1").
+// With this constant the two agree for every double: squaring separates neighbouring doubles around 0.1, and sqrt(w) > 0.1 <=> w > fl(0.1^2).
+constexpr double W_STANDSTILL = 0.1 * 0.1;
 // ---------------------------------------------------------------------------------------------------------------------
 // velocity stage (seam 2): tph.calc_vel_profile / calc_vel_profile_brake / calc_vel_profile_follow on the device
 // ---------------------------------------------------------------------------------------------------------------------
@@ -397,7 +402,7 @@ __device__ __forceinline__ void follow_profile(const DevLat& lat, int n, int n_e
     // arc length s = [0, cumsum(el[:-1])] (:203) next to the ego stop distance (:162-166)
     wave_cumsum_seq(vs.el, vs.s, n_el, lane);                  // s[i] = sum of el[0 .. i-1], sequential order
     // first point at or below 0.1 m/s on the brake profile; the ego stop distance is the arc length up to it (:162-166)
-    int idb = wave_find_first(n, lane, [&](int i) { return !(vs.wb[i] > 0.01); });
+    int idb = wave_find_first(n, lane, [&](int i) { return !(vs.wb[i] > W_STANDSTILL); });
     if (idb > n_el) idb = n_el;
     double ego_stop = 0.0;
     if (idb > 0) ego_stop = (idb < n_el) ? vs.s[idb] : vs.s[n_el - 1] + vs.el[n_el - 1];
@@ -411,7 +416,7 @@ __device__ __forceinline__ void follow_profile(const DevLat& lat, int n, int n_e
     const double vel0 = grl[(size_t)idx_s_opp * 5 + 4];
     const double vel_start = fi.v_obj < vel0 ? fi.v_obj : vel0;                          // :182
     double opp_stop = 0.0, wopp = vel_start * vel_start;
-    int stopped = (wopp > 0.01) ? 0 : 1;                                                 // id_brake counts v > 0.1
+    int stopped = (wopp > W_STANDSTILL) ? 0 : 1;                                                 // id_brake counts v > 0.1
     for (int c0 = 0; c0 < G && !stopped; c0 += 64) {
         const int i = c0 + lane;
         if (i < G) {
@@ -429,7 +434,7 @@ __device__ __forceinline__ void follow_profile(const DevLat& lat, int n, int n_e
                 const double a = ax_poss_w<EM, true, VMODE_DECEL_FORW>(wopp, vs.chunk[k] * (1.0 / 14.0), 14.0, p, vs.axm, 0.0);
                 const double r = wopp + 2.0 * a * vs.chunk[64 + k];
                 wopp = r < 0.0 ? 0.0 : r;                                                // standstill: profile stays 0
-                if (!(wopp > 0.01)) { stopped = 1; break; }
+                if (!(wopp > W_STANDSTILL)) { stopped = 1; break; }
             }
         }
         stopped = __shfl(stopped, 0);
