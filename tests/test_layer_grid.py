@@ -105,3 +105,27 @@ def test_synthetic_ovals_are_served():
             if c is not None:
                 d2 = (rx - p[0]) * (rx - p[0]) + (ry - p[1]) * (ry - p[1])
                 assert int(c[int(np.argmin(d2[c]))]) == int(np.argmin(d2))
+
+
+@pytest.mark.parametrize("name", ("monteblanco", "open", "C", "V", "c3"))
+def test_exact_fp64_ties_take_the_lower_layer(name):
+    """The points above lie NEAR a bisector; these lie on it in fp64: the exact ties of tests/template_cases.py (d2 equal on two layers and
+    equal to the minimum -- adjacent layers, the seam pair (L - 1, 0), layers more than 10 apart). The candidates' first minimum must be the
+    lower tied layer, as np.argmin's is."""
+    import template_cases as tc
+    lat = tc.lattice(name)
+    rx, ry, oc, dims, cells = grid_of(lat)
+    ties = [p for p in tc.case_set(name, "layer").probes if p["kind"] == "tie" and p["partner"] is None]
+    assert len(ties) >= 30
+    pts = np.array([[p["x"], p["y"]] for p in ties])
+    n_grid = 0
+    for p, q, c in zip(ties, pts, lookup(oc, dims, cells, pts)):
+        d2 = (rx - q[0]) * (rx - q[0]) + (ry - q[1]) * (ry - q[1])
+        a, b = p["pair"]
+        assert d2[a] == d2[b] == d2.min() and int(np.argmin(d2)) == min(a, b)
+        if c is None:
+            continue
+        assert len(c) >= 1 and np.all(np.diff(c) > 0)
+        assert int(c[int(np.argmin(d2[c]))]) == min(a, b), (name, p["family"], p["pair"], q)
+        n_grid += 1
+    assert n_grid >= 30, (name, n_grid, len(ties))
