@@ -109,85 +109,123 @@ SIM_SNAPSHOTS = 8                                          # LTPL_FLEET_SIM_SNAP
 SIM_MAX_TRIGGERS = 16                                      # LTPL_FLEET_SIM_MAX_TRIGGERS
 
 
+def _per(v, dtype, n):
+    """A scalar, or one value per planner / per case, as a contiguous array of ``dtype`` with ``n`` entries (``n`` may be a shape)."""
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype), n if isinstance(n, tuple) else (n,)))
+
+
+def _zeros(m, *tail, dtype=np.float64):
+    """An output buffer for ``m`` cases that holds at least one, so that no pointer is empty; the caller cuts the result back to [:m]."""
+    return np.zeros((max(int(m), 1),) + tail, dtype)
+
+
+def _offsets(counts):
+    """int32 offsets [len(counts) + 1] of lists laid back to back, starting at 0."""
+    return np.ascontiguousarray(np.concatenate(([0], np.cumsum(counts))).astype(np.int32))
+
+
+def _ragged(lists, width=None, dtype=np.float64):
+    """Per-case lists of rows [n_q, width] (``width=None``: values [n_q]) for a test hook: (int32 offsets [m + 1] starting at 0, the rows
+    back to back with one zero row appended, so that no pointer is empty)."""
+    tail = () if width is None else (width,)
+    rows = [np.asarray(x, dtype).reshape((-1,) + tail) for x in lists]
+    return _offsets([r.shape[0] for r in rows]), np.ascontiguousarray(np.concatenate(rows + [np.zeros((1,) + tail)]))
+
+
+def _split(buf, off):
+    """What a test hook wrote per row of ``_ragged``'s flat array, cut back into one copy per case."""
+    return [buf[off[q]:off[q + 1]].copy() for q in range(len(off) - 1)]
+
+
+_h = _p = C.c_void_p                      # the handle; an array handed over as its address
+_i, _d, _pi = C.c_int32, C.c_double, C.POINTER(C.c_int32)
+# (probe symbol, ((entry point, argtypes), ...)): a group is declared when the library exports its probe (None: always) -- a build without
+# the simulation binds too
+_ENTRY_POINTS = (
+    (None, (("set_start_range", (_h, _i, _i, _d, _d, _d, _d, _d, _pi, _pi)),
+            ("tape_clear", (_h,)),
+            ("tape_append", (_h, C.POINTER(PlannerPathsIn), C.POINTER(PlannerVelIn))),
+            ("tape_run", (_h, _i, _i, C.POINTER(C.c_float))))),
+    ("digest", (("digest", (_h, C.POINTER(_d), _i)),)),
+    ("sim_run", (("sim_setup", (_h, C.POINTER(SimIn))),
+                 ("sim_vel", (_h, C.POINTER(PlannerVelIn))),
+                 ("sim_run", (_h, _i, _p, _i, C.POINTER(C.c_float))),
+                 ("sim_state", (_h,) + (_p,) * 7))),
+    ("sim_race", (("sim_race", (_h, C.POINTER(SimRaceIn))),
+                  ("sim_heading", (_h, _p)))),
+    ("sim_telemetry", (("sim_telemetry", (_h, C.POINTER(SimTeleIn))),
+                       ("sim_telemetry_read", (_h, _p, _i, C.POINTER(_d))))),
+    ("sim_record", (("sim_record", (_h, _p, _i, _i)),
+                    ("sim_record_info", (_h,) + (_pi,) * 4),
+                    ("sim_record_get", (_h, _i, _i, C.POINTER(SimRecordHead), _p, C.POINTER(PathsView), _p, C.POINTER(TrajView))))),
+    ("sim_branch", (("sim_snapshot", (_h, _i, _p, _i)),
+                    ("sim_snapshot_info", (_h, _i, _pi, _p, _i, C.POINTER(C.c_uint64))),
+                    ("sim_snapshot_drop", (_h, _i)),
+                    ("sim_branch", (_h, _i, _p, _p, _i, C.POINTER(C.c_float))))),
+    ("sim_events", (("sim_events", (_h, C.POINTER(SimEventsIn))),
+                    ("sim_events_read", (_h, _p, _pi, _pi)))),
+    ("sim_noise", (("sim_noise", (_h, C.POINTER(SimNoiseIn))),
+                   ("sim_estimate", (_h, _p, _p, _p)),
+                   ("sim_noise_draws", (_h, _p, _p, _p, _p, _i, _p, _p)))),
+    ("sim_vehicle", (("sim_vehicle", (_h, C.POINTER(SimVehicleIn))),
+                     ("sim_vehicle_read", (_h, _p, _i)),
+                     ("sim_vehicle_step", (_h, _i) + (_p,) * 7 + (_i, _p)))),
+    ("sim_sensor", (("sim_sensor", (_h, C.POINTER(SimSensorIn))),
+                    ("sim_sensor_read", (_h, _p, _i)),
+                    ("sim_sensor_eval", (_h, _i) + (_p,) * 8))),
+    ("sim_tracker", (("sim_tracker", (_h, C.POINTER(SimTrackerIn))),
+                     ("sim_tracker_read", (_h, _p, _i, _i, _p, _p, _p)),
+                     ("sim_tracker_eval", (_h, _i) + (_p,) * 16))),
+    ("sim_predictor", (("sim_predictor", (_h, C.POINTER(SimPredictorIn))),
+                       ("sim_predictor_read", (_h, _p, _i)),
+                       ("sim_predictor_eval", (_h, _i, _i) + (_p,) * 6))),
+    ("sim_selector", (("sim_selector", (_h, C.POINTER(SimSelectorIn))),
+                      ("sim_selector_read", (_h, _p, _i, _p, _i)),
+                      ("sim_selector_eval", (_h, _i) + (_p,) * 10))),
+    ("sim_safety", (("sim_safety", (_h, C.POINTER(SimSafetyIn))),
+                    ("sim_safety_read", (_h, _p, _i, _p, _i)),
+                    ("sim_safety_eval", (_h, _i) + (_p,) * 10))),
+    ("sim_react", (("sim_react", (_h, C.POINTER(SimReactIn))),
+                   ("sim_react_read", (_h, _p, _i, _p)),
+                   ("sim_react_eval", (_h, _i) + (_p,) * 10))),
+    ("sim_stats", (("sim_stats", (_h, C.POINTER(SimStatsIn))),
+                   ("sim_stats_reduce", (_h, _p, _i, _p, _i)),
+                   ("sim_stats_series", (_h, _p, _p, _i, _pi, C.POINTER(C.c_int64))),
+                   ("sim_stats_eval", (_h, _i) + (_p,) * 6))),
+    ("friction", (("friction", (_h, C.POINTER(FrictionIn))),
+                  ("friction_scale", (_h, _p)),
+                  ("friction_rows", (_h, _i, _p, _p, _i, _d, _p)))))
+
+
 class Fleet(Planner):
     def __init__(self, backend, n_planners, **config):
         Planner.__init__(self, backend, n_scen=n_planners, prefix="ltpl_fleet_", **config)
 
     def _declare(self):
         Planner._declare(self)
-        f = self._fn
-        f("set_start_range").argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
-                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-        f("tape_clear").argtypes = [C.c_void_p]
-        f("tape_append").argtypes = [C.c_void_p, C.POINTER(PlannerPathsIn), C.POINTER(PlannerVelIn)]
-        f("tape_run").argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_float)]
-        if hasattr(self.lib, "ltpl_fleet_digest"):
-            f("digest").argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32]
-        if hasattr(self.lib, "ltpl_fleet_sim_run"):
-            f("sim_setup").argtypes = [C.c_void_p, C.POINTER(SimIn)]
-            f("sim_vel").argtypes = [C.c_void_p, C.POINTER(PlannerVelIn)]
-            f("sim_run").argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_float)]
-            f("sim_state").argtypes = [C.c_void_p] + [C.c_void_p] * 7
-        if hasattr(self.lib, "ltpl_fleet_sim_race"):
-            f("sim_race").argtypes = [C.c_void_p, C.POINTER(SimRaceIn)]
-            f("sim_heading").argtypes = [C.c_void_p, C.c_void_p]
-        if hasattr(self.lib, "ltpl_fleet_sim_telemetry"):
-            f("sim_telemetry").argtypes = [C.c_void_p, C.POINTER(SimTeleIn)]
-            f("sim_telemetry_read").argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_double)]
-        if hasattr(self.lib, "ltpl_fleet_sim_record"):
-            f("sim_record").argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
-            f("sim_record_info").argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 4
-            f("sim_record_get").argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(SimRecordHead), C.c_void_p, C.POINTER(PathsView),
-                                            C.c_void_p, C.POINTER(TrajView)]
-        if hasattr(self.lib, "ltpl_fleet_sim_branch"):
-            f("sim_snapshot").argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
-            f("sim_snapshot_info").argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_int32, C.POINTER(C.c_uint64)]
-            f("sim_snapshot_drop").argtypes = [C.c_void_p, C.c_int32]
-            f("sim_branch").argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_float)]
-        if hasattr(self.lib, "ltpl_fleet_sim_events"):
-            f("sim_events").argtypes = [C.c_void_p, C.POINTER(SimEventsIn)]
-            f("sim_events_read").argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-        if hasattr(self.lib, "ltpl_fleet_sim_noise"):
-            f("sim_noise").argtypes = [C.c_void_p, C.POINTER(SimNoiseIn)]
-            f("sim_estimate").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-            f("sim_noise_draws").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-        if hasattr(self.lib, "ltpl_fleet_sim_vehicle"):
-            f("sim_vehicle").argtypes = [C.c_void_p, C.POINTER(SimVehicleIn)]
-            f("sim_vehicle_read").argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
-            f("sim_vehicle_step").argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 7 + [C.c_int32, C.c_void_p]
-        if hasattr(self.lib, "ltpl_fleet_sim_sensor"):
-            f("sim_sensor").argtypes = [C.c_void_p, C.POINTER(SimSensorIn)]
-            f("sim_sensor_read").argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
-            f("sim_sensor_eval").argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 8
-        if hasattr(self.lib, "ltpl_fleet_sim_tracker"):
-            f("sim_tracker").argtypes = [C.c_void_p, C.POINTER(SimTrackerIn)]
-            f("sim_tracker_read").argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-            f("sim_tracker_eval").argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 16
-        if hasattr(self.lib, "ltpl_fleet_sim_predictor"):
-            f("sim_predictor").argtypes = [C.c_void_p, C.POINTER(SimPredictorIn)]
-            f("sim_predictor_read").argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
-            f("sim_predictor_eval").argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6
-        if hasattr(self.lib, "ltpl_fleet_sim_selector"):
-            f("sim_selector").argtypes = [C.c_void_p, C.POINTER(SimSelectorIn)]
-            f("sim_selector_read").argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
-            f("sim_selector_eval").argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 10
-        if hasattr(self.lib, "ltpl_fleet_sim_safety"):
-            f("sim_safety").argtypes = [C.c_void_p, C.POINTER(SimSafetyIn)]
-            f("sim_safety_read").argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
-            f("sim_safety_eval").argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 10
-        if hasattr(self.lib, "ltpl_fleet_sim_react"):
-            f("sim_react").argtypes = [C.c_void_p, C.POINTER(SimReactIn)]
-            f("sim_react_read").argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-            f("sim_react_eval").argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 10
-        if hasattr(self.lib, "ltpl_fleet_sim_stats"):
-            f("sim_stats").argtypes = [C.c_void_p, C.POINTER(SimStatsIn)]
-            f("sim_stats_reduce").argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
-            f("sim_stats_series").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
-            f("sim_stats_eval").argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6
-        if hasattr(self.lib, "ltpl_fleet_friction"):
-            f("friction").argtypes = [C.c_void_p, C.POINTER(FrictionIn)]
-            f("friction_scale").argtypes = [C.c_void_p, C.c_void_p]
-            f("friction_rows").argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p]
+        for probe, group in _ENTRY_POINTS:
+            if probe is None or hasattr(self.lib, "ltpl_fleet_" + probe):
+                for name, argtypes in group:
+                    self._fn(name).argtypes = list(argtypes)
+
+    # ---- one path each for the setters, the reads and (with _ragged / _split) the test hooks of the simulation's models ----------------------
+    def _set(self, name, struct=None, columns=(), **scalars):
+        """A setter's call: ``struct`` with its plain members ``scalars`` and an array per entry of ``columns`` = (member, value, dtype[,
+        entries]) -- a scalar or one value per planner (or per ``entries``); a member without an entry stays NULL. ``struct=None`` hands
+        NULL, the off switch. The arrays live until the call is back."""
+        if struct is None:
+            return self._check(self._fn(name)(self.handle, None))
+        si = struct(**scalars)
+        keep = [_per(c[1], c[2], c[3] if len(c) > 3 else self.n_scen) for c in columns]
+        for c, a in zip(columns, keep):
+            setattr(si, c[0], a.ctypes.data)
+        self._check(self._fn(name)(self.handle, C.byref(si)))
+
+    def _read(self, name, doubles, *extra, rows=None):
+        """A read's call: the records [n_planners (or the shape ``rows``), doubles], filled by ``name`` (out, doubles, *extra)."""
+        out = np.zeros((rows if rows is not None else (self.n_scen,)) + (doubles,), np.float64)
+        self._check(self._fn(name)(self.handle, out.ctypes.data, doubles, *extra))
+        return out
 
     def set_start(self, scen, pos, heading, vel=0.0, max_heading_offset=math.pi / 4):
         out = Planner.set_start(self, scen, pos, heading, vel, max_heading_offset)
@@ -462,13 +500,8 @@ class Fleet(Planner):
             sizes = [len(r) for r in races]
         else:
             sizes = [int(r) for r in races]
-        off = np.ascontiguousarray(np.concatenate(([0], np.cumsum(sizes))).astype(np.int32))
-        lens = np.ascontiguousarray(np.broadcast_to(np.asarray(length, np.float64), (n,)))
-        h0 = self._start_heading() if heading0 is None else np.broadcast_to(np.asarray(heading0, np.float64), (n,))
-        h0 = np.ascontiguousarray(h0, np.float64)
-        ri = SimRaceIn()
-        ri.n_races, ri.race_off, ri.length, ri.heading0 = len(sizes), off.ctypes.data, lens.ctypes.data, h0.ctypes.data
-        self._check(self._fn("sim_race")(self.handle, C.byref(ri)))
+        self._set("sim_race", SimRaceIn, (("race_off", _offsets(sizes), np.int32, len(sizes) + 1), ("length", length, np.float64),
+                                          ("heading0", self._start_heading() if heading0 is None else heading0, np.float64)), n_races=len(sizes))
 
     def sim_heading(self):
         """[n] heading of every planner's tracked pose (``sim_race``'s heading0 until its first trajectory)."""
@@ -483,25 +516,15 @@ class Fleet(Planner):
         (scalar or one per planner; None switches the telemetry off); ``grid_s``: progress offset of every planner (default: s of its
         first live tick; hand it in for grids that straddle the start line)."""
         if radius is None:
-            self._check(self._fn("sim_telemetry")(self.handle, None))
-            return
-        n = self.n_scen
-        rad = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float64), (n,)))
-        ti = SimTeleIn()
-        ti.radius, ti.grid_s = rad.ctypes.data, None
-        if grid_s is not None:
-            gs = np.ascontiguousarray(np.broadcast_to(np.asarray(grid_s, np.float64), (n,)))
-            ti.grid_s = gs.ctypes.data
-        self._check(self._fn("sim_telemetry")(self.handle, C.byref(ti)))
+            return self._set("sim_telemetry")
+        self._set("sim_telemetry", SimTeleIn, (("radius", radius, np.float64), ("grid_s", grid_s, np.float64))[:1 if grid_s is None else 2])
 
     def sim_telemetry_read(self):
         """The records as they stand (ltpl_fleet_sim_telemetry_read; accumulation goes on): dict of named arrays, one entry per planner
         (``TELEMETRY_FIELDS``: counts as int64, ``act`` [n, 5] in the order straight, follow, left, right, emergency), plus
         ``track_length``, the closed length of the race line. BackendError while the telemetry is off."""
-        out = np.zeros((self.n_scen, TELEMETRY_DOUBLES), np.float64)
         length = C.c_double(0.0)
-        self._check(self._fn("sim_telemetry_read")(self.handle, out.ctypes.data, TELEMETRY_DOUBLES, C.byref(length)))
-        return telemetry_dict(out, float(length.value))
+        return telemetry_dict(self._read("sim_telemetry_read", TELEMETRY_DOUBLES, C.byref(length)), float(length.value))
 
     # ---- flight recorder on the device ----------------------------------------------------------------------------------------------
     def sim_record(self, planners, depth=1):
@@ -673,17 +696,9 @@ class Fleet(Planner):
         of every opponent, static object and mate it perceives. A sigma of 0 draws nothing. ``tick0``: the noise tick of the next tick
         to run (draws depend on seed, tick, object and component only: ``sim.noise_gauss``, ``sim.NoiseModel``)."""
         if seed is None:
-            self._check(self._fn("sim_noise")(self.handle, None))
-            return
-        n = self.n_scen
-        ni = SimNoiseIn()
-        keep = [np.ascontiguousarray(np.broadcast_to(np.asarray(seed, np.uint64), (n,)))]
-        ni.seed, ni.tick0 = keep[0].ctypes.data, int(tick0)
-        for name, v in (("sigma_pos", pos), ("sigma_vel", vel), ("sigma_obj_pos", obj_pos), ("sigma_obj_theta", obj_theta),
-                        ("sigma_obj_vel", obj_vel)):
-            keep.append(np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float64), (n,))))
-            setattr(ni, name, keep[-1].ctypes.data)
-        self._check(self._fn("sim_noise")(self.handle, C.byref(ni)))
+            return self._set("sim_noise")
+        sigmas = (("sigma_pos", pos), ("sigma_vel", vel), ("sigma_obj_pos", obj_pos), ("sigma_obj_theta", obj_theta), ("sigma_obj_vel", obj_vel))
+        self._set("sim_noise", SimNoiseIn, (("seed", seed, np.uint64),) + tuple((k, v, np.float64) for k, v in sigmas), tick0=int(tick0))
 
     def sim_estimate(self):
         """dict(pos_est [n, 2], vel_est [n]): what every planner was handed as its pose and speed in the last tick
@@ -699,7 +714,7 @@ class Fleet(Planner):
         sd, tk, ob, cp = (np.ascontiguousarray(v.reshape(-1)) for v in a)
         n = int(sd.size)
         g = np.zeros(n, np.float64)
-        w = np.zeros((max(n, 1), 12), np.uint32) if words else None
+        w = _zeros(n, 12, dtype=np.uint32) if words else None
         self._check(self._fn("sim_noise_draws")(self.handle, sd.ctypes.data, tk.ctypes.data, ob.ctypes.data, cp.ctypes.data, n, g.ctypes.data,
                                                 None if w is None else w.ctypes.data))
         return (g, w[:n]) if words else g
@@ -713,27 +728,19 @@ class Fleet(Planner):
         a = kappa = 0 and cleared statistics; ``keep_state=True``: planners that already drove the model keep state and statistics and
         only the parameters change (a grip that drops between two runs). Host mirror: ``sim.VehicleModel``."""
         if model is None:
-            self._check(self._fn("sim_vehicle")(self.handle, None))
-            return
+            return self._set("sim_vehicle")
         unknown = set(params) - set(VEHICLE_DEFAULTS)
         if unknown:
             raise TypeError("sim_vehicle: unknown parameter(s) %s" % sorted(unknown))
         par = dict(VEHICLE_DEFAULTS, **params)
-        n = self.n_scen
-        vi = SimVehicleIn()
-        keep = [np.ascontiguousarray(np.broadcast_to(np.asarray(model, np.int32), (n,)))]
-        vi.model, vi.ctl_steps, vi.flags = keep[0].ctypes.data, int(par["ctl_steps"]), 1 if keep_state else 0
-        for name in VEHICLE_PARAMS:
-            keep.append(np.ascontiguousarray(np.broadcast_to(np.asarray(par[name], np.float64), (n,))))
-            setattr(vi, name, keep[-1].ctypes.data)
-        self._check(self._fn("sim_vehicle")(self.handle, C.byref(vi)))
+        self._set("sim_vehicle", SimVehicleIn, (("model", model, np.int32),) + tuple((k, par[k], np.float64) for k in VEHICLE_PARAMS),
+                  ctl_steps=int(par["ctl_steps"]), flags=1 if keep_state else 0)
 
     def sim_vehicle_read(self, raw=False):
         """dict of named arrays (``sim.VEHICLE_FIELDS``): state x, y, c, s, v, a, kappa and statistics e, e_max, e2_sum, dv_max, ctl_steps,
         sat_lat, sat_lon, off_track_ticks of every planner (ltpl_fleet_sim_vehicle_read). A planner on the ideal tracker holds NaN (its
         counters read -1). ``raw=True``: the [n, 15] records."""
-        out = np.zeros((self.n_scen, VEHICLE_DOUBLES), np.float64)
-        self._check(self._fn("sim_vehicle_read")(self.handle, out.ctypes.data, VEHICLE_DOUBLES))
+        out = self._read("sim_vehicle_read", VEHICLE_DOUBLES)
         return out if raw else vehicle_dict(out)
 
     def sim_vehicle_step(self, state, params, rows, dt, ctl_steps):
@@ -743,15 +750,12 @@ class Fleet(Planner):
         tick's statistics, theta [m]); equals ``sim.VehicleModel.tick`` bit for bit."""
         state = np.ascontiguousarray(np.asarray(state, np.float64).reshape(-1, 7))
         m = state.shape[0]
-        params = np.ascontiguousarray(np.broadcast_to(np.asarray(params, np.float64), (m, len(VEHICLE_PARAMS))))
-        rows = [np.asarray(r, np.float64).reshape(-1, 5) for r in rows]
-        if len(rows) != m:
+        params = _per(params, np.float64, (m, len(VEHICLE_PARAMS)))
+        off, flat = _ragged(rows, 5)
+        if len(off) - 1 != m:
             raise ValueError("sim_vehicle_step: one row table per case expected")
-        off = np.ascontiguousarray(np.concatenate(([0], np.cumsum([r.shape[0] for r in rows]))).astype(np.int32))
-        flat = np.ascontiguousarray(np.concatenate(rows + [np.zeros((1, 5))]))
-        dts = np.ascontiguousarray(np.broadcast_to(np.asarray(dt, np.float64), (m,)))
-        ctl = np.ascontiguousarray(np.broadcast_to(np.asarray(ctl_steps, np.int32), (m,)))
-        out, theta = np.zeros((max(m, 1), VEHICLE_DOUBLES), np.float64), np.zeros(max(m, 1), np.float64)
+        dts, ctl = _per(dt, np.float64, m), _per(ctl_steps, np.int32, m)
+        out, theta = _zeros(m, VEHICLE_DOUBLES), _zeros(m)
         self._check(self._fn("sim_vehicle_step")(self.handle, m, state.ctypes.data, params.ctypes.data, off.ctypes.data, flat.ctypes.data,
                                                  dts.ctypes.data, ctl.ctypes.data, out.ctypes.data, VEHICLE_DOUBLES, theta.ctypes.data))
         return out[:m], theta[:m]
@@ -765,25 +769,16 @@ class Fleet(Planner):
         ``tick0``: the sensor tick of the next tick. ``range=None`` switches the sensor off. The statistics start anew with every
         call. Host mirror: ``sim.SensorModel``."""
         if range is None:
-            self._check(self._fn("sim_sensor")(self.handle, None))
-            return
-        n = self.n_scen
-        si = SimSensorIn()
+            return self._set("sim_sensor")
         val = dict(range=range, r_near=r_near, fov_cos=sensor_fov_cos(fov_deg), occl=occl, p_drop=p_drop)
-        keep = []
-        for name in SENSOR_PARAMS:
-            keep.append(np.ascontiguousarray(np.broadcast_to(np.asarray(val[name], np.float64), (n,))))
-            setattr(si, name, keep[-1].ctypes.data)
-        keep.append(np.ascontiguousarray(np.broadcast_to(np.asarray(0 if seed is None else seed, np.uint64), (n,))))
-        si.seed, si.tick0 = keep[-1].ctypes.data, int(tick0)
-        self._check(self._fn("sim_sensor")(self.handle, C.byref(si)))
+        self._set("sim_sensor", SimSensorIn, tuple((k, val[k], np.float64) for k in SENSOR_PARAMS) + (("seed", 0 if seed is None else seed, np.uint64),),
+                  tick0=int(tick0))
 
     def sim_sensor_read(self, raw=False):
         """dict of named arrays (``sim.SENSOR_FIELDS``): live ticks, objects on the track, seen, lost to range / cone / occlusion / dropout,
         ticks with a lost object, the smallest true clearance to a lost object and its sensor tick, of every planner
         (ltpl_fleet_sim_sensor_read). ``raw=True``: the [n, 10] records."""
-        out = np.zeros((self.n_scen, SENSOR_DOUBLES), np.float64)
-        self._check(self._fn("sim_sensor_read")(self.handle, out.ctypes.data, SENSOR_DOUBLES))
+        out = self._read("sim_sensor_read", SENSOR_DOUBLES)
         return out if raw else sensor_dict(out)
 
     def sim_sensor_eval(self, pose, f, params, seed, tick, objs):
@@ -793,19 +788,16 @@ class Fleet(Planner):
         1 .. 4 the cause of loss) and the dropout draws (NaN where none was made); equals ``sim.SensorModel.evaluate`` bit for bit."""
         pose = np.asarray(pose, np.float64).reshape(-1, 2)
         m = pose.shape[0]
-        pf = np.ascontiguousarray(np.concatenate((pose, np.broadcast_to(np.asarray(f, np.float64), (m, 2))), axis=1))
-        params = np.ascontiguousarray(np.broadcast_to(np.asarray(params, np.float64), (m, len(SENSOR_PARAMS))))
-        seeds = np.ascontiguousarray(np.broadcast_to(np.asarray(seed, np.uint64), (m,)))
-        ticks = np.ascontiguousarray(np.broadcast_to(np.asarray(tick, np.uint32), (m,)))
-        objs = [np.asarray(o, np.float64).reshape(-1, 3) for o in objs]
-        if len(objs) != m:
+        pf = np.ascontiguousarray(np.concatenate((pose, _per(f, np.float64, (m, 2))), axis=1))
+        params = _per(params, np.float64, (m, len(SENSOR_PARAMS)))
+        seeds, ticks = _per(seed, np.uint64, m), _per(tick, np.uint32, m)
+        off, flat = _ragged(objs, 3)
+        if len(off) - 1 != m:
             raise ValueError("sim_sensor_eval: one object list per case expected")
-        off = np.ascontiguousarray(np.concatenate(([0], np.cumsum([o.shape[0] for o in objs]))).astype(np.int32))
-        flat = np.ascontiguousarray(np.concatenate(objs + [np.zeros((1, 3))]))
-        cause, u = np.zeros(int(off[-1]) + 1, np.int32), np.zeros(int(off[-1]) + 1, np.float64)
+        cause, u = np.zeros(flat.shape[0], np.int32), np.zeros(flat.shape[0], np.float64)
         self._check(self._fn("sim_sensor_eval")(self.handle, m, pf.ctypes.data, params.ctypes.data, seeds.ctypes.data, ticks.ctypes.data,
                                                 off.ctypes.data, flat.ctypes.data, cause.ctypes.data, u.ctypes.data))
-        return [cause[off[q]:off[q + 1]].copy() for q in range(m)], [u[off[q]:off[q + 1]].copy() for q in range(m)]
+        return _split(cause, off), _split(u, off)
 
     # ---- object tracker on the device -------------------------------------------------------------------------------------------------
     def sim_tracker(self, gate=TRACKER_DEFAULTS["gate"], w_pos=TRACKER_DEFAULTS["w_pos"], w_vel=TRACKER_DEFAULTS["w_vel"],
@@ -817,31 +809,21 @@ class Fleet(Planner):
         ``n_coast`` ticks (scalars or one per planner). ``tick0``: the tracker tick of the next tick. ``gate=None`` switches the tracker
         off. Tables and statistics start anew with every call. Host mirror: ``sim.TrackerModel``."""
         if gate is None:
-            self._check(self._fn("sim_tracker")(self.handle, None))
-            return
-        n = self.n_scen
-        ti = SimTrackerIn()
+            return self._set("sim_tracker")
         val = dict(gate=gate, w_pos=w_pos, w_vel=w_vel, n_confirm=n_confirm, n_coast=n_coast)
-        keep = []
-        for name in TRACKER_PARAMS:
-            keep.append(np.ascontiguousarray(np.broadcast_to(np.asarray(val[name], np.int32 if name.startswith("n_") else np.float64), (n,))))
-            setattr(ti, name, keep[-1].ctypes.data)
-        ti.tick0 = int(tick0)
-        self._check(self._fn("sim_tracker")(self.handle, C.byref(ti)))
+        self._set("sim_tracker", SimTrackerIn, tuple((k, val[k], np.int32 if k.startswith("n_") else np.float64) for k in TRACKER_PARAMS),
+                  tick0=int(tick0))
 
     def sim_tracker_read(self, planners=None, raw=False):
         """The tracker's statistics of every planner as a dict of named arrays (``sim.TRACKER_FIELDS``; ``raw=True``: the [n, 12] records)
         (ltpl_fleet_sim_tracker_read). With ``planners`` (a list of indices): (records, tables, counts) -- their track tables
         [len(planners), 96, 10] in the order of ``sim.TRACK_FIELDS``, unused rows NaN, and their track counts."""
-        out = np.zeros((self.n_scen, TRACKER_DOUBLES), np.float64)
         if planners is None:
-            self._check(self._fn("sim_tracker_read")(self.handle, out.ctypes.data, TRACKER_DOUBLES, 0, None, None, None))
+            out = self._read("sim_tracker_read", TRACKER_DOUBLES, 0, None, None, None)
             return out if raw else tracker_dict(out)
         sel = np.ascontiguousarray(np.asarray(planners, np.int32).reshape(-1))
-        tabs = np.zeros((max(len(sel), 1), TRACK_CAP, TRACK_DOUBLES), np.float64)
-        cnt = np.zeros(max(len(sel), 1), np.int32)
-        self._check(self._fn("sim_tracker_read")(self.handle, out.ctypes.data, TRACKER_DOUBLES, len(sel), sel.ctypes.data, tabs.ctypes.data,
-                                                 cnt.ctypes.data))
+        tabs, cnt = _zeros(len(sel), TRACK_CAP, TRACK_DOUBLES), _zeros(len(sel), dtype=np.int32)
+        out = self._read("sim_tracker_read", TRACKER_DOUBLES, len(sel), sel.ctypes.data, tabs.ctypes.data, cnt.ctypes.data)
         return (out if raw else tracker_dict(out)), tabs[:len(sel)], cnt[:len(sel)]
 
     def sim_tracker_eval(self, params, adv, tick, cap, slots, tracks, next_id, dets):
@@ -850,31 +832,22 @@ class Fleet(Planner):
         case; ``tracks``: a list of m arrays [T_q, 10]; ``dets``: a list of m arrays [K_q, 6] = x, y, px, py, r, v. Returns a dict:
         ``tables`` [m, 96, 10] (unused rows NaN), ``n_tracks`` [m], ``next_id`` [m], ``out`` (a list of [n_out_q, 6] arrays), ``assign`` (a
         list of int32 arrays: matched id, -1 born, -2 overflow), ``rec`` [m, 12]; equals ``sim.TrackerModel.step`` bit for bit."""
-        tracks = [np.asarray(t, np.float64).reshape(-1, TRACK_DOUBLES) for t in tracks]
-        dets = [np.asarray(d, np.float64).reshape(-1, 6) for d in dets]
-        m = len(tracks)
-        if len(dets) != m:
+        (toff, tflat), (doff, dflat) = _ragged(tracks, TRACK_DOUBLES), _ragged(dets, 6)
+        m = len(toff) - 1
+        if len(doff) - 1 != m:
             raise ValueError("sim_tracker_eval: one table and one detection list per case expected")
-
-        def per(v, dt):
-            return np.ascontiguousarray(np.broadcast_to(np.asarray(v, dt), (m,)))
-        params = np.ascontiguousarray(np.broadcast_to(np.asarray(params, np.float64), (m, len(TRACKER_PARAMS))))
-        adv, tick, nid = per(adv, np.float64), per(tick, np.uint32), per(next_id, np.float64)
-        cs = np.ascontiguousarray(np.stack((per(cap, np.int32), per(slots, np.int32)), axis=1))
-        toff = np.ascontiguousarray(np.concatenate(([0], np.cumsum([t.shape[0] for t in tracks]))).astype(np.int32))
-        doff = np.ascontiguousarray(np.concatenate(([0], np.cumsum([d.shape[0] for d in dets]))).astype(np.int32))
-        tflat = np.ascontiguousarray(np.concatenate(tracks + [np.zeros((1, TRACK_DOUBLES))]))
-        dflat = np.ascontiguousarray(np.concatenate(dets + [np.zeros((1, 6))]))
-        mm = max(m, 1)
-        tabs, ntr, nid_out = np.zeros((mm, TRACK_CAP, TRACK_DOUBLES)), np.zeros(mm, np.int32), np.zeros(mm)
-        out, n_out, rec = np.zeros((mm, TRACK_CAP, 6)), np.zeros(mm, np.int32), np.zeros((mm, TRACKER_DOUBLES))
-        assign = np.zeros(int(doff[-1]) + 1, np.int32)
+        params = _per(params, np.float64, (m, len(TRACKER_PARAMS)))
+        adv, tick, nid = _per(adv, np.float64, m), _per(tick, np.uint32, m), _per(next_id, np.float64, m)
+        cs = np.ascontiguousarray(np.stack((_per(cap, np.int32, m), _per(slots, np.int32, m)), axis=1))
+        tabs, ntr, nid_out = _zeros(m, TRACK_CAP, TRACK_DOUBLES), _zeros(m, dtype=np.int32), _zeros(m)
+        out, n_out, rec = _zeros(m, TRACK_CAP, 6), _zeros(m, dtype=np.int32), _zeros(m, TRACKER_DOUBLES)
+        assign = np.zeros(dflat.shape[0], np.int32)
         self._check(self._fn("sim_tracker_eval")(self.handle, m, params.ctypes.data, adv.ctypes.data, tick.ctypes.data, cs.ctypes.data, toff.ctypes.data,
                                                  tflat.ctypes.data, nid.ctypes.data, doff.ctypes.data, dflat.ctypes.data, tabs.ctypes.data,
                                                  ntr.ctypes.data, nid_out.ctypes.data, out.ctypes.data, n_out.ctypes.data, assign.ctypes.data,
                                                  rec.ctypes.data))
         return dict(tables=tabs[:m], n_tracks=ntr[:m], next_id=nid_out[:m], out=[out[q, :n_out[q]].copy() for q in range(m)],
-                    assign=[assign[doff[q]:doff[q + 1]].copy() for q in range(m)], rec=rec[:m])
+                    assign=_split(assign, doff), rec=rec[:m])
 
     # ---- prediction model on the device -----------------------------------------------------------------------------------------------
     def sim_predictor(self, n_points=PREDICTOR_DEFAULTS["n_points"], mode=PREDICTOR_DEFAULTS["mode"], horizon=PREDICTOR_DEFAULTS["horizon"],
@@ -889,24 +862,16 @@ class Fleet(Planner):
         (LTPL_ERR_CAPACITY) unless (opponents + statics + mates) (1 + n_points) <= 192 for every planner. ``n_points=None`` switches the
         predictor off. The statistics start anew with every call. Host mirror: ``sim.PredictorModel``."""
         if n_points is None:
-            self._check(self._fn("sim_predictor")(self.handle, None))
-            return
-        n = self.n_scen
-        pi = SimPredictorIn()
-        pi.n_points = int(n_points)
+            return self._set("sim_predictor")
         val = dict(mode=mode, horizon=horizon, relax=relax, d_max=d_max)
-        keep = []
-        for name in PREDICTOR_PARAMS:
-            keep.append(np.ascontiguousarray(np.broadcast_to(np.asarray(val[name], np.int32 if name == "mode" else np.float64), (n,))))
-            setattr(pi, name, keep[-1].ctypes.data)
-        self._check(self._fn("sim_predictor")(self.handle, C.byref(pi)))
+        self._set("sim_predictor", SimPredictorIn, tuple((k, val[k], np.int32 if k == "mode" else np.float64) for k in PREDICTOR_PARAMS),
+                  n_points=int(n_points))
 
     def sim_predictor_read(self, raw=False):
         """dict of named arrays (``sim.PREDICTOR_FIELDS``): live ticks, objects predicted, a count per outcome (as ingested, still,
         straight by mode / ``d_max`` / direction / without a segment, along the track), the largest lateral offset used and the points
         that wrapped (ltpl_fleet_sim_predictor_read). ``raw=True``: the [n, 11] records."""
-        out = np.zeros((self.n_scen, PREDICTOR_DOUBLES), np.float64)
-        self._check(self._fn("sim_predictor_read")(self.handle, out.ctypes.data, PREDICTOR_DOUBLES))
+        out = self._read("sim_predictor_read", PREDICTOR_DOUBLES)
         return out if raw else predictor_dict(out)
 
     def sim_predictor_eval(self, n_points, params, objs):
@@ -914,17 +879,14 @@ class Fleet(Planner):
         table of ``sim_setup``. ``params`` [m, 4] in the order of ``sim.PREDICTOR_PARAMS``; ``objs``: a list of m arrays [n_q, 5] = x, y,
         px, py, v (at most 96 rows). Returns (positions, outcomes, rec): per case the [n_q, 1 + n_points, 2] positions (own, then the
         points) and the int32 outcomes, and the [m, 11] counters; equals ``sim.PredictorModel`` bit for bit."""
-        objs = [np.asarray(o, np.float64).reshape(-1, 5) for o in objs]
-        m, K = len(objs), int(n_points)
-        params = np.ascontiguousarray(np.broadcast_to(np.asarray(params, np.float64), (m, len(PREDICTOR_PARAMS))))
-        off = np.ascontiguousarray(np.concatenate(([0], np.cumsum([o.shape[0] for o in objs]))).astype(np.int32))
-        flat = np.ascontiguousarray(np.concatenate(objs + [np.zeros((1, 5))]))
-        total = int(off[-1])
-        pts = np.zeros((total + 1, 1 + max(K, 1), 2))
-        oc, rec = np.zeros(total + 1, np.int32), np.zeros((max(m, 1), PREDICTOR_DOUBLES))
+        off, flat = _ragged(objs, 5)
+        m, K = len(off) - 1, int(n_points)
+        params = _per(params, np.float64, (m, len(PREDICTOR_PARAMS)))
+        pts = np.zeros((flat.shape[0], 1 + max(K, 1), 2))
+        oc, rec = np.zeros(flat.shape[0], np.int32), _zeros(m, PREDICTOR_DOUBLES)
         self._check(self._fn("sim_predictor_eval")(self.handle, m, K, params.ctypes.data, off.ctypes.data, flat.ctypes.data, pts.ctypes.data,
                                                    oc.ctypes.data, rec.ctypes.data))
-        return ([pts[off[q]:off[q + 1]].copy() for q in range(m)], [oc[off[q]:off[q + 1]].copy() for q in range(m)], rec[:m])
+        return _split(pts, off), _split(oc, off), rec[:m]
 
     # ---- behaviour selector on the device ---------------------------------------------------------------------------------------------
     def sim_selector(self, on=True, **params):
@@ -936,30 +898,21 @@ class Fleet(Planner):
         is never written. Parameters (``sim.SELECTOR_PARAMS``, defaults ``sim.SELECTOR_DEFAULTS``) and ``on``: scalars or one per planner.
         ``on=None`` switches the selector off. The statistics start anew with every call. Host mirror: ``sim.SelectorModel``."""
         if on is None:
-            self._check(self._fn("sim_selector")(self.handle, None))
-            return
+            return self._set("sim_selector")
         unknown = set(params) - set(SELECTOR_PARAMS)
         if unknown:
             raise ValueError("sim_selector: unknown parameter %s" % sorted(unknown))
-        n = self.n_scen
-        si = SimSelectorIn()
         val = dict(SELECTOR_DEFAULTS, **params)
-        keep = [np.ascontiguousarray(np.broadcast_to(np.asarray(on), (n,)).astype(np.int32))]
-        si.on = keep[0].ctypes.data
-        for name in SELECTOR_PARAMS:
-            keep.append(np.ascontiguousarray(np.broadcast_to(np.asarray(val[name], np.float64), (n,))))
-            setattr(si, name, keep[-1].ctypes.data)
-        self._check(self._fn("sim_selector")(self.handle, C.byref(si)))
+        self._set("sim_selector", SimSelectorIn, (("on", on, np.int32),) + tuple((k, val[k], np.float64) for k in SELECTOR_PARAMS))
 
     def sim_selector_read(self, raw=False):
         """(records, ordered): the dict of named arrays (``sim.SELECTOR_FIELDS``; ``raw=True``: the [n, 12] records) and the current
         ordered list of every planner, a list of int32 arrays in the order of the preference lists of ``sim_setup``
         (ltpl_fleet_sim_selector_read)."""
         off = getattr(self, "_sim_pref_off", np.zeros(self.n_scen + 1, np.int64))
-        out = np.zeros((self.n_scen, SELECTOR_DOUBLES), np.float64)
-        order = np.zeros(max(int(off[-1]), 1), np.int32)
-        self._check(self._fn("sim_selector_read")(self.handle, out.ctypes.data, SELECTOR_DOUBLES, order.ctypes.data, int(off[-1])))
-        return (out if raw else selector_dict(out)), [order[off[p]:off[p + 1]].copy() for p in range(self.n_scen)]
+        order = _zeros(off[-1], dtype=np.int32)
+        out = self._read("sim_selector_read", SELECTOR_DOUBLES, order.ctypes.data, int(off[-1]))
+        return (out if raw else selector_dict(out)), _split(order, off)
 
     def sim_selector_eval(self, params, users, sel_prev, actions, objs, emergency=None, rec=None):
         """The selector's test hook (ltpl_fleet_sim_selector_eval): independent cases on the device, one wave each. ``params`` [m, 6] in
@@ -969,11 +922,11 @@ class Fleet(Planner):
         records after); equals ``sim.SelectorModel.evaluate`` bit for bit."""
         m = len(users)
         R = SELECTOR_MAX_ROWS
-        params = np.ascontiguousarray(np.broadcast_to(np.asarray(params, np.float64), (m, len(SELECTOR_PARAMS))))
-        lists = np.zeros((max(m, 1), 8), np.int32)
+        params = _per(params, np.float64, (m, len(SELECTOR_PARAMS)))
+        lists = _zeros(m, 8, dtype=np.int32)
         n_rows = np.full((max(m, 1), 4), -1, np.int32)
-        rows = np.zeros((max(m, 1), 4, 4, R))
-        objs = [np.asarray(o, np.float64).reshape(-1, 5) for o in objs]
+        rows = _zeros(m, 4, 4, R)
+        off, flat = _ragged(objs, 5)
         for q in range(m):
             u = [int(a) for a in users[q]]
             lists[q, 0], lists[q, 1], lists[q, 2] = len(u), int(sel_prev[q]), int(bool(emergency[q])) if emergency is not None else 0
@@ -984,12 +937,9 @@ class Fleet(Planner):
                 t = np.asarray(actions[q][a], np.float64).reshape(-1, 4)
                 n_rows[q, a] = t.shape[0]
                 rows[q, a, :, :min(t.shape[0], R)] = t[:R].T
-        off = np.ascontiguousarray(np.concatenate(([0], np.cumsum([o.shape[0] for o in objs]))).astype(np.int32))
-        flat = np.ascontiguousarray(np.concatenate(objs + [np.zeros((1, 5))]))
-        order = np.zeros((max(m, 1), 5), np.int32)
-        act_d, act_i = np.zeros((max(m, 1), 4, 3)), np.zeros((max(m, 1), 4, 2), np.int32)
+        order, act_d, act_i = _zeros(m, 5, dtype=np.int32), _zeros(m, 4, 3), _zeros(m, 4, 2, dtype=np.int32)
         if rec is None:
-            rec = np.zeros((max(m, 1), SELECTOR_DOUBLES))
+            rec = _zeros(m, SELECTOR_DOUBLES)
             rec[:, 10] = np.inf
         rec = np.ascontiguousarray(np.asarray(rec, np.float64).reshape(max(m, 1), SELECTOR_DOUBLES).copy())
         self._check(self._fn("sim_selector_eval")(self.handle, m, params.ctypes.data, lists.ctypes.data, n_rows.ctypes.data, rows.ctypes.data,
@@ -1008,28 +958,19 @@ class Fleet(Planner):
         ``keep_state=True`` changes parameters, mask and tick0 and keeps records and rings. ``on=None`` clears the monitor. Host mirror:
         ``sim.SafetyModel``."""
         if on is None:
-            self._check(self._fn("sim_safety")(self.handle, None))
-            return
+            return self._set("sim_safety")
         unknown = set(params) - set(SAFETY_PARAMS)
         if unknown:
             raise ValueError("sim_safety: unknown parameter %s" % sorted(unknown))
-        n = self.n_scen
-        si = SimSafetyIn()
         val = dict(SAFETY_DEFAULTS, **params)
-        keep = [np.ascontiguousarray(np.broadcast_to(np.asarray(on), (n,)).astype(np.int32))]
-        si.on = keep[0].ctypes.data
-        for name in SAFETY_PARAMS:
-            keep.append(np.ascontiguousarray(np.broadcast_to(np.asarray(val[name], np.float64), (n,))))
-            setattr(si, name, keep[-1].ctypes.data)
-        si.tick0, si.flags = int(tick0), SAFETY_KEEP_STATE if keep_state else 0
-        self._check(self._fn("sim_safety")(self.handle, C.byref(si)))
+        self._set("sim_safety", SimSafetyIn, (("on", on, np.int32),) + tuple((k, val[k], np.float64) for k in SAFETY_PARAMS),
+                  tick0=int(tick0), flags=SAFETY_KEEP_STATE if keep_state else 0)
 
     def sim_safety_read(self, raw=False):
         """(records, incidents): the dict of named arrays (``sim.SAFETY_FIELDS``; ``raw=True``: the [n, 31] records) and the incident rings
         [n, 8, 6] (``sim.INCIDENT_FIELDS``; NaN: unwritten; ``sim.safety_incidents`` orders a ring) (ltpl_fleet_sim_safety_read)."""
-        out = np.zeros((self.n_scen, SAFETY_DOUBLES), np.float64)
         inc = np.zeros((self.n_scen, SAFETY_INCIDENTS, INCIDENT_DOUBLES), np.float64)
-        self._check(self._fn("sim_safety_read")(self.handle, out.ctypes.data, SAFETY_DOUBLES, inc.ctypes.data, INCIDENT_DOUBLES))
+        out = self._read("sim_safety_read", SAFETY_DOUBLES, inc.ctypes.data, INCIDENT_DOUBLES)
         return (out if raw else safety_dict(out)), inc
 
     def sim_safety_eval(self, pose, dt, tick, params, objs, rec=None, inc=None):
@@ -1038,15 +979,11 @@ class Fleet(Planner):
         y, px, py, r; ``rec`` [m, 31] and ``inc`` [m, 8, 6]: records and rings before (default: the start state). Returns (records after,
         rings after, per_obj: a list of [n_q, 6] = ttc, drac, thw, gap, closing, flags, per_tick [m, 8]); equals ``sim.safety_tick`` bit
         for bit."""
-        objs = [np.asarray(o, np.float64).reshape(-1, 5) for o in objs]
-        m = len(objs)
+        off, flat = _ragged(objs, 5)
+        m = len(off) - 1
         k = max(m, 1)
-        pose = np.ascontiguousarray(np.broadcast_to(np.asarray(pose, np.float64), (m, 2)).reshape(m, 2), np.float64)
-        dt = np.ascontiguousarray(np.broadcast_to(np.asarray(dt, np.float64), (m,)), np.float64)
-        tick = np.ascontiguousarray(np.broadcast_to(np.asarray(tick), (m,)).astype(np.int32))
-        params = np.ascontiguousarray(np.broadcast_to(np.asarray(params, np.float64), (m, len(SAFETY_PARAMS))), np.float64)
-        off = np.ascontiguousarray(np.concatenate(([0], np.cumsum([o.shape[0] for o in objs]))).astype(np.int32))
-        flat = np.ascontiguousarray(np.concatenate(objs + [np.zeros((1, 5))]))
+        pose, dt, tick = _per(pose, np.float64, (m, 2)), _per(dt, np.float64, m), _per(tick, np.int32, m)
+        params = _per(params, np.float64, (m, len(SAFETY_PARAMS)))
         r0, i0 = safety_start(k)
         rec = r0 if rec is None else np.ascontiguousarray(np.asarray(rec, np.float64).reshape(k, SAFETY_DOUBLES).copy())
         inc = i0 if inc is None else np.ascontiguousarray(np.asarray(inc, np.float64).reshape(k, SAFETY_INCIDENTS, INCIDENT_DOUBLES).copy())
@@ -1054,7 +991,7 @@ class Fleet(Planner):
         self._check(self._fn("sim_safety_eval")(self.handle, m, pose.ctypes.data, dt.ctypes.data, tick.ctypes.data, params.ctypes.data,
                                                 off.ctypes.data, flat.ctypes.data, rec.ctypes.data, inc.ctypes.data, per_obj.ctypes.data,
                                                 per_tick.ctypes.data))
-        return rec[:m], inc[:m], [per_obj[off[q]:off[q + 1]].copy() for q in range(m)], per_tick[:m]
+        return rec[:m], inc[:m], _split(per_obj, off), per_tick[:m]
 
     # ---- reactive opponents on the device ----------------------------------------------------------------------------------------------
     def sim_react(self, on=True, tick0=0, keep_state=False, **params):
@@ -1067,30 +1004,21 @@ class Fleet(Planner):
         parameters and tick0 and keeps scales and records. ``on=None`` (or 0 for every planner) switches the model off. A field whose
         opponents never find a leader drives the run without the model bit for bit. Host mirror: ``sim.ReactModel``."""
         if on is None:
-            self._check(self._fn("sim_react")(self.handle, None))
-            return
-        names = REACT_PARAMS[1:]
+            return self._set("sim_react")
+        names = REACT_PARAMS[1:]                           # (``on`` travels apart, as int32)
         unknown = set(params) - set(names)
         if unknown:
             raise ValueError("sim_react: unknown parameter %s" % sorted(unknown))
-        n = self.n_scen
-        si = SimReactIn()
         val = dict(REACT_DEFAULTS, **params)
-        keep = [np.ascontiguousarray(np.broadcast_to(np.asarray(on), (n,)).astype(np.int32))]
-        si.on = keep[0].ctypes.data
-        for name in names:
-            keep.append(np.ascontiguousarray(np.broadcast_to(np.asarray(val[name], np.float64), (n,))))
-            setattr(si, name, keep[-1].ctypes.data)
-        si.tick0, si.flags = int(tick0), REACT_KEEP_STATE if keep_state else 0
-        self._check(self._fn("sim_react")(self.handle, C.byref(si)))
+        self._set("sim_react", SimReactIn, (("on", on, np.int32),) + tuple((k, val[k], np.float64) for k in names),
+                  tick0=int(tick0), flags=REACT_KEEP_STATE if keep_state else 0)
 
     def sim_react_read(self, raw=False):
         """(records, eff_scale): the dict of named arrays (``sim.REACT_FIELDS``; ``raw=True``: the [n, 16] records) and the effective
         scales of all opponents in the order of ``sim_state()['opp_s']`` (ltpl_fleet_sim_react_read)."""
         no = getattr(self, "_sim_opp", 0)
-        out = np.zeros((self.n_scen, REACT_DOUBLES), np.float64)
-        eff = np.zeros(max(no, 1), np.float64)
-        self._check(self._fn("sim_react_read")(self.handle, out.ctypes.data, REACT_DOUBLES, eff.ctypes.data))
+        eff = _zeros(no)
+        out = self._read("sim_react_read", REACT_DOUBLES, eff.ctypes.data)
         return (out if raw else react_dict(out)), eff[:no]
 
     def sim_react_eval(self, params, ego, dt, tick, opp, rec=None):
@@ -1099,22 +1027,17 @@ class Fleet(Planner):
         ``tick`` [m]; per case ``opp`` [n_q, 4] = s, c, e, length (0 .. 96); ``rec`` [m, 16]: the records before (default: the start
         state). Returns (records after, e_new: a list of [n_q], per_opp: a list of [n_q, 4] = leader, delta, gap, acc, ego_out [m, 3] =
         s_e, d_e, has); equals ``sim.react_tick`` bit for bit."""
-        opp = [np.asarray(o, np.float64).reshape(-1, 4) for o in opp]
-        m = len(opp)
+        off, flat = _ragged(opp, 4)
+        m = len(off) - 1
         k = max(m, 1)
-        params = np.ascontiguousarray(np.broadcast_to(np.asarray(params, np.float64), (m, len(REACT_PARAMS))), np.float64)
-        ego = np.ascontiguousarray(np.broadcast_to(np.asarray(ego, np.float64), (m, 3)), np.float64)
-        dt = np.ascontiguousarray(np.broadcast_to(np.asarray(dt, np.float64), (m,)), np.float64)
-        tick = np.ascontiguousarray(np.broadcast_to(np.asarray(tick), (m,)).astype(np.int32))
-        off = np.ascontiguousarray(np.concatenate(([0], np.cumsum([o.shape[0] for o in opp]))).astype(np.int32))
-        flat = np.ascontiguousarray(np.concatenate(opp + [np.zeros((1, 4))]))
+        params, ego = _per(params, np.float64, (m, len(REACT_PARAMS))), _per(ego, np.float64, (m, 3))
+        dt, tick = _per(dt, np.float64, m), _per(tick, np.int32, m)
         rec = react_start(k) if rec is None else np.ascontiguousarray(np.asarray(rec, np.float64).reshape(k, REACT_DOUBLES).copy())
         e_out, per_opp, ego_out = np.zeros(flat.shape[0]), np.zeros((flat.shape[0], 4)), np.zeros((k, 3))
         self._check(self._fn("sim_react_eval")(self.handle, m, params.ctypes.data, ego.ctypes.data, dt.ctypes.data, tick.ctypes.data,
                                                off.ctypes.data, flat.ctypes.data, rec.ctypes.data, e_out.ctypes.data, per_opp.ctypes.data,
                                                ego_out.ctypes.data))
-        return (rec[:m], [e_out[off[q]:off[q + 1]].copy() for q in range(m)], [per_opp[off[q]:off[q + 1]].copy() for q in range(m)],
-                ego_out[:m])
+        return rec[:m], _split(e_out, off), _split(per_opp, off), ego_out[:m]
 
     # ---- campaign statistics on the device ---------------------------------------------------------------------------------------------
     def sim_stats(self, groups, measures=None, top_k=0, period=0, depth=0, tick0=0, keep_series=False, n_groups=None):
@@ -1127,24 +1050,19 @@ class Fleet(Planner):
         rows (``sim_stats_series``). ``keep_series=True`` keeps the ring of a plan with the same G, number of measures and depth.
         ``groups=None`` clears the plan. Measurement only: the run is bit-identical with and without it. Host mirror: ``sim.StatsModel``."""
         if groups is None:
-            self._check(self._fn("sim_stats")(self.handle, None))
+            self._set("sim_stats")
             self._sim_stats = None
             return
         i32, f64 = np.int32, np.float64
-        group = np.ascontiguousarray(np.broadcast_to(np.asarray(groups), (self.n_scen,)).astype(i32))
+        group = _per(groups, i32, self.n_scen)
         G = (int(group.max()) + 1 if group.size else 0) if n_groups is None else int(n_groups)
         cols = [stats_column(m[0], m[1]) for m in measures]
-        fam = np.ascontiguousarray([c[0] for c in cols], i32)
-        col = np.ascontiguousarray([c[1] for c in cols], i32)
-        lo, hi = np.ascontiguousarray([m[2] for m in measures], f64), np.ascontiguousarray([m[3] for m in measures], f64)
-        bins, top_dir = np.ascontiguousarray([m[4] for m in measures], i32), np.ascontiguousarray([m[5] for m in measures], i32)
-        si = SimStatsIn()
-        si.n_groups, si.group, si.n_measures = G, group.ctypes.data, len(cols)
-        si.family, si.column, si.lo, si.hi, si.bins, si.top_dir = (a.ctypes.data for a in (fam, col, lo, hi, bins, top_dir))
-        si.top_k, si.period, si.depth, si.tick0 = int(top_k), int(period), int(depth), int(tick0)
-        si.flags = STATS_KEEP_SERIES if keep_series else 0
-        self._check(self._fn("sim_stats")(self.handle, C.byref(si)))
-        self._sim_stats = (G, len(cols), int(top_k), int(depth) if int(period) > 0 else 0)
+        M = len(cols)
+        per_measure = (("family", [c[0] for c in cols], i32), ("column", [c[1] for c in cols], i32), ("lo", [m[2] for m in measures], f64),
+                       ("hi", [m[3] for m in measures], f64), ("bins", [m[4] for m in measures], i32), ("top_dir", [m[5] for m in measures], i32))
+        self._set("sim_stats", SimStatsIn, (("group", group, i32),) + tuple(c + (M,) for c in per_measure), n_groups=G, n_measures=M,
+                  top_k=int(top_k), period=int(period), depth=int(depth), tick0=int(tick0), flags=STATS_KEEP_SERIES if keep_series else 0)
+        self._sim_stats = (G, M, int(top_k), int(depth) if int(period) > 0 else 0)
 
     def _stats_shape(self):
         shape = getattr(self, "_sim_stats", None)
@@ -1155,15 +1073,15 @@ class Fleet(Planner):
         (ltpl_fleet_sim_stats_reduce; ``sim.STATS_FIELDS``; ``raw=False``: the rows as ``sim.stats_dict``). Unused list entries are
         (NaN, -1)."""
         G, M, K, _ = self._stats_shape()
-        rows, tops = np.zeros((G, M, STATS_DOUBLES), np.float64), np.zeros((G, M, max(K, 1), 2), np.float64)
-        self._check(self._fn("sim_stats_reduce")(self.handle, rows.ctypes.data, STATS_DOUBLES, tops.ctypes.data if K else None, K))
+        tops = np.zeros((G, M, max(K, 1), 2), np.float64)
+        rows = self._read("sim_stats_reduce", STATS_DOUBLES, tops.ctypes.data if K else None, K, rows=(G, M))
         return (rows if raw else stats_dict(rows)), tops[:, :, :K]
 
     def sim_stats_series(self):
         """(ticks [held], rows [held, G, M, 27], rows ever written): the ring of the plan's series, oldest first
         (ltpl_fleet_sim_stats_series)."""
         G, M, _, depth = self._stats_shape()
-        ticks, rows = np.zeros(max(depth, 1), np.int32), np.zeros((max(depth, 1), G, M, STATS_DOUBLES), np.float64)
+        ticks, rows = _zeros(depth, dtype=np.int32), _zeros(depth, G, M, STATS_DOUBLES)
         held, total = C.c_int32(0), C.c_int64(0)
         self._check(self._fn("sim_stats_series")(self.handle, ticks.ctypes.data, rows.ctypes.data, STATS_DOUBLES, C.byref(held), C.byref(total)))
         return ticks[:held.value].copy(), rows[:held.value].copy(), int(total.value)
@@ -1172,16 +1090,11 @@ class Fleet(Planner):
         """The rule's test hook (ltpl_fleet_sim_stats_eval): independent cases on the device, each one group and one measure on raw values.
         Per case ``values`` [n_q] and ``spec`` = (lo, hi, bins, top_dir, top_k); ``planners`` (or None: the positions): per case the
         planner index of every value. Returns (rows [m, 27], tops [m, 8, 2]); equals ``sim.stats_reduce`` bit for bit."""
-        values = [np.asarray(v, np.float64).reshape(-1) for v in values]
-        m = len(values)
-        k = max(m, 1)
-        off = np.ascontiguousarray(np.concatenate(([0], np.cumsum([v.size for v in values]))).astype(np.int32))
-        flat = np.ascontiguousarray(np.concatenate(values + [np.zeros(1)]))
+        off, flat = _ragged(values)
+        m = len(off) - 1
         spec = np.ascontiguousarray(np.asarray(spec, np.float64).reshape(m, 5))
-        idx = None
-        if planners is not None:
-            idx = np.ascontiguousarray(np.concatenate([np.asarray(p).reshape(-1) for p in planners] + [np.zeros(1)]).astype(np.int32))
-        rows, tops = np.zeros((k, STATS_DOUBLES), np.float64), np.zeros((k, STATS_MAX_TOP, 2), np.float64)
+        idx = None if planners is None else _ragged(planners)[1].astype(np.int32)
+        rows, tops = _zeros(m, STATS_DOUBLES), _zeros(m, STATS_MAX_TOP, 2)
         self._check(self._fn("sim_stats_eval")(self.handle, m, off.ctypes.data, flat.ctypes.data, None if idx is None else idx.ctypes.data,
                                                spec.ctypes.data, rows.ctypes.data, tops.ctypes.data))
         return rows[:m], tops[:m]
@@ -1193,34 +1106,25 @@ class Fleet(Planner):
         per planner, -1: the planner keeps its constant ``local_gg`` tuple; default: map 0 for all); ``scale``: grip factor per planner.
         A planner with a map takes the rows of every offered key from the map on every route of the velocity stage
         (``calc_vel_profile``, ``tape_run``, ``sim_run`` with or without races); between ticks or runs at any time."""
-        n, f64, i32 = self.n_scen, np.float64, np.int32
+        f64, i32 = np.float64, np.int32
         if maps is None:
             maps = []
         elif hasattr(maps, "rows"):
             maps = [maps]
         maps = list(maps)
-        fi = FrictionIn()
-        fi.n_maps = len(maps)
-        keep = []
+        cols = ()
         if maps:
-            def col(vals, dt):
-                a = np.ascontiguousarray(np.array(vals, dt))
-                keep.append(a)
-                return a.ctypes.data
-            fi.x0, fi.y0 = col([m.x0 for m in maps], f64), col([m.y0 for m in maps], f64)
-            fi.dx, fi.dy = col([m.dx for m in maps], f64), col([m.dy for m in maps], f64)
-            fi.nx, fi.ny = col([m.nx for m in maps], i32), col([m.ny for m in maps], i32)
-            fi.node_off = col(np.concatenate(([0], np.cumsum([m.nx * m.ny for m in maps]))), i32)
-            nodes = np.ascontiguousarray(np.concatenate([m.nodes() for m in maps]), f64)
-            idx = np.ascontiguousarray(np.broadcast_to(np.asarray(0 if map_idx is None else map_idx, i32), (n,)))
-            sc = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, f64), (n,)))
-            keep += [nodes, idx, sc]
-            fi.nodes, fi.map_idx, fi.scale = nodes.ctypes.data, idx.ctypes.data, sc.ctypes.data
-        self._check(self._fn("friction")(self.handle, C.byref(fi)))
+            k = len(maps)
+            nodes = np.concatenate([m.nodes() for m in maps])
+            cols = tuple((a, [getattr(m, a) for m in maps], f64, k) for a in ("x0", "y0", "dx", "dy"))
+            cols += tuple((a, [getattr(m, a) for m in maps], i32, k) for a in ("nx", "ny"))
+            cols += (("node_off", _offsets([m.nx * m.ny for m in maps]), i32, k + 1), ("nodes", nodes, f64, nodes.shape),
+                     ("map_idx", 0 if map_idx is None else map_idx, i32), ("scale", scale, f64))
+        self._set("friction", FrictionIn, cols, n_maps=len(maps))
 
     def friction_scale(self, scale):
         """New grip factors (scalar or one per planner) on the maps set by ``friction`` (ltpl_fleet_friction_scale)."""
-        sc = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, np.float64), (self.n_scen,)))
+        sc = _per(scale, np.float64, self.n_scen)
         self._check(self._fn("friction_scale")(self.handle, sc.ctypes.data))
 
     def friction_rows(self, map, xy, scale=1.0):
@@ -1238,7 +1142,7 @@ class Fleet(Planner):
         n, no = self.n_scen, getattr(self, "_sim_opp", 0)
         px, py, v, now = (np.zeros(n, np.float64) for _ in range(4))
         sel = np.zeros(n, np.int32)
-        os_, ot = np.zeros(max(no, 1), np.float64), np.zeros(max(no, 1), np.float64)
+        os_, ot = _zeros(no), _zeros(no)
         self._check(self._fn("sim_state")(self.handle, px.ctypes.data, py.ctypes.data, v.ctypes.data, sel.ctypes.data, now.ctypes.data,
                                           os_.ctypes.data, ot.ctypes.data))
         return dict(pos_est=np.column_stack((px, py)), vel_est=v, sel_action=sel, now=now, opp_s=os_[:no], opp_tic=ot[:no])

@@ -226,13 +226,22 @@ def closed_length(raceline, s_raceline):
     return float(s_raceline[-1]) + math.sqrt(dx * dx + dy * dy)
 
 
+def fields_dict(rows, fields, doubles=None, wide=(), nan_int=None):
+    """Records [..., doubles] as a dict of named arrays in the order of a ``*_FIELDS`` table -- (name, first index, integer valued), or
+    (name, first index, doubles, integer valued): integer valued fields as int64 (a NaN reads ``nan_int`` there, if given), the others
+    as copies. ``doubles``: the records are reshaped to [-1, doubles]; ``wide`` = ((name, doubles), ...): array-valued fields of a
+    three-column table."""
+    rows = np.asarray(rows, np.float64) if doubles is None else np.asarray(rows, np.float64).reshape(-1, doubles)
+    out = {}
+    for name, i, cnt, is_int in ((f[0], f[1], f[2] if len(f) == 4 else dict(wide).get(f[0], 1), f[-1]) for f in fields):
+        a = rows[..., i] if cnt == 1 else rows[..., i:i + cnt]
+        out[name] = (a if nan_int is None else np.where(np.isnan(a), nan_int, a)).astype(np.int64) if is_int else a.copy()
+    return out
+
+
 def telemetry_dict(rows, track_length=None):
     """[n, 22] records as a dict of named arrays (integer valued fields as int64, ``act`` as [n, 5])."""
-    rows = np.asarray(rows, np.float64).reshape(-1, TELEMETRY_DOUBLES)
-    out = {}
-    for name, i, cnt, is_int in TELEMETRY_FIELDS:
-        a = rows[:, i] if cnt == 1 else rows[:, i:i + cnt]
-        out[name] = a.astype(np.int64) if is_int else a.copy()
+    out = fields_dict(rows, TELEMETRY_FIELDS, TELEMETRY_DOUBLES)
     if track_length is not None:
         out["track_length"] = float(track_length)
     return out
@@ -600,9 +609,7 @@ VEH_STEP = 0.001
 
 def vehicle_dict(rows):
     """[n, 15] records as a dict of named arrays (counters as int64; planners on the ideal tracker hold NaN and read -1 there)."""
-    rows = np.asarray(rows, np.float64).reshape(-1, VEHICLE_DOUBLES)
-    return {name: (np.where(np.isnan(rows[:, i]), -1.0, rows[:, i]).astype(np.int64) if is_int else rows[:, i].copy())
-            for name, i, is_int in VEHICLE_FIELDS}
+    return fields_dict(rows, VEHICLE_FIELDS, VEHICLE_DOUBLES, nan_int=-1.0)
 
 
 def _veh_interp(x, xp, fp, n):
@@ -778,8 +785,7 @@ SENSOR_SEEN, SENSOR_RANGE, SENSOR_FOV, SENSOR_OCCL, SENSOR_DROP = 0, 1, 2, 3, 4 
 
 def sensor_dict(rows):
     """[n, 10] records as a dict of named arrays (counters as int64; blind_clear_tick reads -1 until an object was lost)."""
-    rows = np.asarray(rows, np.float64).reshape(-1, SENSOR_DOUBLES)
-    return {name: (rows[:, i].astype(np.int64) if is_int else rows[:, i].copy()) for name, i, is_int in SENSOR_FIELDS}
+    return fields_dict(rows, SENSOR_FIELDS, SENSOR_DOUBLES)
 
 
 def sensor_fov_cos(fov_deg):
@@ -901,8 +907,7 @@ TRACK_UNMATCHED, TRACK_OVERFLOW = -1, -2  # assignment of a detection that no tr
 
 def tracker_dict(rows):
     """[n, 12] records as a dict of named int64 arrays."""
-    rows = np.asarray(rows, np.float64).reshape(-1, TRACKER_DOUBLES)
-    return {name: rows[:, i].astype(np.int64) for name, i, _ in TRACKER_FIELDS}
+    return fields_dict(rows, TRACKER_FIELDS, TRACKER_DOUBLES)      # (every field of the table is integer valued)
 
 
 def tracker_capacity(slots):
@@ -1065,8 +1070,7 @@ PRED_INGESTED, PRED_STILL, PRED_STRAIGHT_MODE, PRED_STRAIGHT_DMAX, PRED_STRAIGHT
 
 def predictor_dict(rows):
     """[n, 11] records as a dict of named arrays (counters as int64)."""
-    rows = np.asarray(rows, np.float64).reshape(-1, PREDICTOR_DOUBLES)
-    return {name: (rows[:, i].astype(np.int64) if is_int else rows[:, i].copy()) for name, i, is_int in PREDICTOR_FIELDS}
+    return fields_dict(rows, PREDICTOR_FIELDS, PREDICTOR_DOUBLES)
 
 
 def _fdiv(a, b):
@@ -1264,8 +1268,7 @@ SEL_EMERGENCY = 4                         # LTPL_ACT_EMERGENCY
 
 def selector_dict(rows):
     """[n, 12] records as a dict of named arrays (counters as int64)."""
-    rows = np.asarray(rows, np.float64).reshape(-1, SELECTOR_DOUBLES)
-    return {name: (rows[:, i].astype(np.int64) if is_int else rows[:, i].copy()) for name, i, is_int in SELECTOR_FIELDS}
+    return fields_dict(rows, SELECTOR_FIELDS, SELECTOR_DOUBLES)
 
 
 def selector_first(order, exported):
@@ -1460,10 +1463,7 @@ _INF = float("inf")
 
 def safety_dict(rows):
     """[n, 31] records as a dict of named arrays (counters as int64; ``hist``: [n, 8])."""
-    rows = np.asarray(rows, np.float64).reshape(-1, SAFETY_DOUBLES)
-    out = {name: (rows[:, i].astype(np.int64) if is_int else rows[:, i].copy()) for name, i, is_int in SAFETY_FIELDS if name != "hist"}
-    out["hist"] = rows[:, 23:31].astype(np.int64)
-    return out
+    return fields_dict(rows, SAFETY_FIELDS, SAFETY_DOUBLES, wide=(("hist", SAFETY_HIST),))
 
 
 def safety_incidents(ring, n_incidents):
@@ -1686,8 +1686,7 @@ REACT_NONE, REACT_EGO = -2, -1            # `leader` of an opponent: none, the e
 
 def react_dict(rows):
     """[n, 16] records as a dict of named arrays (counters, ticks and slots as int64)."""
-    rows = np.asarray(rows, np.float64).reshape(-1, REACT_DOUBLES)
-    return {name: (rows[:, i].astype(np.int64) if is_int else rows[:, i].copy()) for name, i, is_int in REACT_FIELDS}
+    return fields_dict(rows, REACT_FIELDS, REACT_DOUBLES)
 
 
 def react_start(n=1):
@@ -1982,8 +1981,7 @@ def stats_dict(rows):
     """[..., 27] rows as a dict of named arrays (counts as int64; ``hist``: [..., 16]) plus ``mean`` = sum / n and ``var`` = sumsq / n -
     mean^2, computed here on the host (NaN where n == 0)."""
     rows = np.asarray(rows, np.float64)
-    out = {name: (rows[..., i].astype(np.int64) if is_int else rows[..., i].copy()) for name, i, is_int in STATS_FIELDS if name != "hist"}
-    out["hist"] = rows[..., 11:11 + STATS_BINS].astype(np.int64)
+    out = fields_dict(rows, STATS_FIELDS, wide=(("hist", STATS_BINS),))
     with np.errstate(divide="ignore", invalid="ignore"):
         n = rows[..., 0]
         out["mean"] = np.where(n > 0, rows[..., 7] / n, np.nan)
