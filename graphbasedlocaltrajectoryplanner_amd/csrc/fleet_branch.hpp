@@ -3,32 +3,28 @@
 // The rule: what the tick kernels WRITE travels with a planner's state, what the caller SET stays with the destination --
 //   copied   the planner block (Dims::stride bytes of d_state; the planner's error word PlannerS::err lies in it), its window of friction
 //            rows (Dims::gg_stride bytes of d_gg) when both sides have windows, now / sel / started / pos_x / pos_y / vel / theta / live,
-//            opp_s / opp_tic of its opponents, with telemetry on both sides its record, grid_s and prog, and the vehicle model's record
-//            (state and statistics, ltpl_fleet_sim_vehicle) where the DESTINATION has model 1, and the object tracker's table, track
-//            count and next_id (ltpl_fleet_sim_tracker) where the destination has a tracker, and the staged object list of the last tick
-//            (cnt and the first cnt entries of g_x, g_y, g_px, g_py, g_r) where the destination has a behaviour selector
-//            (ltpl_fleet_sim_selector), which reads that list at the head of the next tick, and the safety monitor's record and incident
-//            ring (ltpl_fleet_sim_safety) where the destination has a monitor, and the reactive opponents' effective scales and record
-//            (ltpl_fleet_sim_react) where the destination has a model: they are what the tick writes;
+//            opp_s / opp_tic of its opponents, and the six parts of the table below: what the models' tick kernels write;
 //   stays    the race line, the opponents' vel_scale / length, statics, zones, preference list, dt, n_export, the velocity arguments,
 //            friction map index and scale, race membership and length as a mate, contact radius, the recorder's ring and indices,
 //            the vehicle model's switch and parameters, the tracker's parameters and statistics, the selector's parameters, ordered
 //            lists and statistics, the safety monitor's parameters, mask and tick index, the reactive opponents' parameters and tick index.
-// Reactive opponents, the mixed cases: a destination fleet without a model takes nothing; with one, a destination takes effective scales
-// and record of a source that held them (a live planner while the model is set, a snapshot entry taken with one) -- a source without
-// leaves the destination the start state: the start record and eff = its own configured scales.
-// Safety monitor, the mixed cases: a destination fleet without a monitor takes nothing; with one, a destination takes record and ring of a
-// source that held them (a live planner while the monitor is set, a snapshot entry taken with one) -- a source without leaves the
-// destination the start state (prev_valid 0: its next live tick is not evaluated).
-// Behaviour selector, the mixed cases: a destination without a selector takes nothing; with one it takes the list of a source that held
-// one (a live planner while the selector is set, a snapshot entry taken with one), cut to the destination's staging slots where the
-// source staged more -- a source without leaves the destination an empty list (cnt 0): the first tick scores without objects.
-// Object tracker, the mixed cases: a destination without a tracker takes nothing; a destination with one takes the table of a source that
-// held tracker state (a live planner while the tracker is set, a snapshot entry taken with one) -- a source without empties the
-// destination's table and sets next_id 0, the tracker's start state; a source with more tracks than the destination's C_p is refused.
-// Vehicle model, the mixed cases: a destination on the ideal tracker (or a fleet without the model) takes no vehicle record and keeps its
-// NaN record, whatever the source drives; a destination with model 1 needs a source that had model 1 when it was copied (the live
-// planner now, the snapshot's planner when the snapshot was taken) -- otherwise the pair is refused with LTPL_ERR_INVALID_ARG.
+// The parts. A source HOLDS a part as a live planner while the model is set, and as a snapshot entry taken while it was set:
+//   part         copied by                   the destination takes it where        a source without it leaves             the pair is refused where
+//   telemetry    bulk kernel, wave 0         telemetry is on and the source's      the destination's record, grid_s and   never
+//   (record, grid_s, prog)                   is of the same ltpl_fleet_sim_        prog as they are
+//                                            telemetry call (FleetSim::tele_gen)
+//   vehicle      bulk kernel, wave 0         the destination drives model 1 (one   -- (refused)                           the destination drives model 1 and the
+//   (record: state and statistics)           on the ideal tracker keeps its NaN                                           source drove model 0, or none, when
+//                                            record, whatever the source drives)                                          it was copied
+//   tracker      bulk kernel, wave 0         the fleet has a tracker               an empty table and next_id 0, the      the source holds more tracks than
+//   (table, track count, next_id)                                                  tracker's start state                  the destination's table (C_p)
+//   staged list  k_fleet_sim_branch_staged   the fleet has a selector, which       an empty list (cnt 0): the next tick   never (a longer list is cut to the
+//   (cnt, cnt entries of g_x .. g_r)         reads the list at the next tick's     scores without objects                 destination's staging slots)
+//                                            head
+//   safety       k_fleet_sim_branch_safety   the fleet has a monitor               fleet::safety_start (prev_valid 0:     never
+//   (record, incident ring)                                                        its next live tick is not evaluated)
+//   react        k_fleet_sim_branch_react    the fleet has a model                 fleet::react_start and eff = its own   never
+//   (record, effective scales)                                                     configured scales
 // Everything else the simulation holds per planner (prev_action, t_now, veh_off, g_v and the noise's true positions in the staging, the
 // tick's object arrays, the job pools of the velocity stage -- and cnt and the staging slots without a selector) is written by every tick
 // before it is read.
@@ -82,11 +78,7 @@ __global__ __launch_bounds__(64) void k_fleet_sim_branch_safety(SafetyView S, Sa
     if (S.rec) {
         if (t < LTPL_FLEET_SIM_SAFETY_DOUBLES) r[t] = S.rec[es * LTPL_FLEET_SIM_SAFETY_DOUBLES + t];
         if (t < SAF_RING) e[t] = S.inc[es * SAF_RING + t];
-    } else {
-        if (t < LTPL_FLEET_SIM_SAFETY_DOUBLES)
-            r[t] = t == fleet::SAF_GAP_MIN || t == fleet::SAF_TTC_MIN || t == fleet::SAF_THW_MIN ? (double)INFINITY : 0.0;
-        if (t < SAF_RING) e[t] = NAN;
-    }
+    } else if (t == 0) fleet::safety_start(r, e);
 }
 static_assert(LTPL_FLEET_SIM_SAFETY_DOUBLES <= 64 && SAF_RING <= 64, "k_fleet_sim_branch_safety: one lane per double");
 
@@ -107,9 +99,7 @@ __global__ __launch_bounds__(64) void k_fleet_sim_branch_react(ReactView S, Reac
         if (t < LTPL_FLEET_SIM_REACT_DOUBLES) r[t] = S.rec[(size_t)es * LTPL_FLEET_SIM_REACT_DOUBLES + t];
         for (int q = t; q < no; q += 64) T.eff[to + q] = S.eff[so + q];
     } else {
-        if (t < LTPL_FLEET_SIM_REACT_DOUBLES)
-            r[t] = t == fleet::RCT_GAP_MIN || t == fleet::RCT_ACC_MIN || t == fleet::RCT_EGO_GAP_MIN ? (double)INFINITY
-                 : t == fleet::RCT_GAP_TICK || t == fleet::RCT_GAP_SLOT || t == fleet::RCT_ACC_TICK || t == fleet::RCT_ACC_SLOT || t == fleet::RCT_EGO_GAP_TICK ? -1.0 : 0.0;
+        if (t == 0) fleet::react_start(r);
         for (int q = t; q < no; q += 64) T.eff[to + q] = own[to + q];
     }
 }
@@ -183,18 +173,23 @@ static_assert(LTPL_FLEET_SIM_TELE_DOUBLES + 2 <= 64, "k_fleet_sim_branch: one la
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
+// one side of a copy: the live fleet, or a snapshot's slot. A part the side does not hold is a null view (the table at the top)
+struct BranchSide {
+    BranchView v;
+    StagedView stg;                         // stg.cnt null: no selector
+    SafetyView saf;                         // saf.rec null: no monitor
+    ReactView rct;                          // rct.rec null: no reactive model
+    const double* own;                      // the live fleet's configured scales on rct's offsets: k_fleet_sim_branch_react's `own`
+};
+
 struct SimSnap {
     std::vector<void*> allocs;
-    BranchView v{};
+    BranchSide side{};
     std::vector<int> planners;              // entry k holds planner planners[k]
     std::vector<int> entry_of;              // [N] entry of planner p, -1: not in the snapshot
-    std::vector<int> opp_off;               // [entries + 1] host copy of v.opp_off
-    bool has_tele = false; int tele_gen = 0;     // a telemetry part, taken from the telemetry numbered tele_gen (FleetSim::tele_gen)
+    std::vector<int> opp_off;               // [entries + 1] host copy of side.v.opp_off
+    int tele_gen = 0;                       // a telemetry part was taken from the telemetry numbered tele_gen (FleetSim::tele_gen)
     std::vector<int> veh_model;             // [entries] the model of entry k when the snapshot was taken (empty: the model was off)
-    bool has_trk = false;                   // a tracker part: tables of the planners' capacities, counts and next_id
-    StagedView stg{};                       // the staged lists (stg.cnt null: taken without a selector)
-    SafetyView saf{};                       // the safety monitor's records and rings (saf.rec null: taken without a monitor)
-    ReactView rct{};                        // the reactive opponents' effective scales and records (rct.rec null: taken without a model)
     uint64_t bytes = 0;
     bool held() const { return !planners.empty(); }
 };
@@ -206,88 +201,35 @@ static void sim_snaps_free(SimSnaps* s)
     delete s;
 }
 
-static BranchView branch_live_view(const ltpl_fleet* f)
+// the live fleet as a side: its entries are planner indices, its parts those of the models that are set
+static BranchSide branch_live_side(const ltpl_fleet* f)
 {
     const FleetSim& s = *f->sim; const SimDev& d = s.sd;
-    BranchView v{};
+    BranchSide L{};
+    BranchView& v = L.v;
     v.state = f->d_state; v.gg = f->d_gg;
     v.now = d.now; v.sel = d.sel; v.started = d.started; v.pos_x = d.pos_x; v.pos_y = d.pos_y; v.vel = d.vel; v.theta = d.theta; v.live = d.live;
     v.opp_off = d.opp_off; v.opp_s = d.opp_s; v.opp_tic = d.opp_tic;
     if (s.tele.on) { v.rec = s.tele.dev.rec; v.grid_s = s.tele.dev.grid_s; v.prog = s.tele.dev.prog; }
     if (s.veh.on) { v.veh = s.veh.dev.rec; v.veh_model = s.veh.dev.model; }
     if (s.trk.on) { v.trk = s.trk.dev.rows; v.trk_n = s.trk.dev.n; v.trk_next = s.trk.dev.next_id; v.trk_base = s.trk.dev.base; }
-    return v;
+    if (s.sel.on) L.stg = StagedView{d.cnt, {d.g_x, d.g_y, d.g_px, d.g_py, d.g_r}, d.obj_base};
+    if (s.saf.on) L.saf = SafetyView{s.saf.dev.rec, s.saf.dev.inc};
+    if (s.react.on) { L.rct = ReactView{s.react.dev.eff, s.react.dev.rec, d.opp_off}; L.own = d.opp_scale; }
+    return L;
 }
 
-static StagedView branch_live_staged(const ltpl_fleet* f)
-{
-    const SimDev& d = f->sim->sd;
-    return StagedView{d.cnt, {d.g_x, d.g_y, d.g_px, d.g_py, d.g_r}, d.obj_base};
-}
-// the staged lists of the pairs, behind branch_launch; T: a view with a selector's lists
-static int branch_launch_staged(ltpl_fleet* f, StagedView S, StagedView T, const std::vector<int>& src_entry, const std::vector<int>& dst_entry)
-{
-    const int n = (int)src_entry.size();
-    if (n == 0) return LTPL_OK;
-    SimAllocs a;
-    int* d_idx = nullptr;
-    std::vector<int> idx(src_entry);
-    idx.insert(idx.end(), dst_entry.begin(), dst_entry.end());
-    int rc = sim_upload(f, a.p, idx.data(), idx.size(), &d_idx);
-    if (rc) return rc;
-    hipStream_t st = f->h->stream;
-    hipLaunchKernelGGL(k_fleet_sim_branch_staged, dim3((unsigned)n), dim3(64), 0, st, S, T, (const int*)d_idx, (const int*)d_idx + n);
-    FLEET_TRY(f, hipGetLastError());
-    FLEET_TRY(f, hipStreamSynchronize(st));
-    return LTPL_OK;
-}
-
-// the safety monitor's records and rings of the pairs, behind branch_launch; T: a view with a monitor's records
-static int branch_launch_safety(ltpl_fleet* f, SafetyView S, SafetyView T, const std::vector<int>& src_entry, const std::vector<int>& dst_entry)
-{
-    const int n = (int)src_entry.size();
-    if (n == 0) return LTPL_OK;
-    SimAllocs a;
-    int* d_idx = nullptr;
-    std::vector<int> idx(src_entry);
-    idx.insert(idx.end(), dst_entry.begin(), dst_entry.end());
-    int rc = sim_upload(f, a.p, idx.data(), idx.size(), &d_idx);
-    if (rc) return rc;
-    hipStream_t st = f->h->stream;
-    hipLaunchKernelGGL(k_fleet_sim_branch_safety, dim3((unsigned)n), dim3(64), 0, st, S, T, (const int*)d_idx, (const int*)d_idx + n);
-    FLEET_TRY(f, hipGetLastError());
-    FLEET_TRY(f, hipStreamSynchronize(st));
-    return LTPL_OK;
-}
-
-// the reactive opponents' effective scales and records of the pairs, behind branch_launch; T: a view with a model's state; `own`: the
-// configured scales on T's offsets (read only where S holds no state)
-static int branch_launch_react(ltpl_fleet* f, ReactView S, ReactView T, const double* own, const std::vector<int>& src_entry,
-                               const std::vector<int>& dst_entry)
-{
-    const int n = (int)src_entry.size();
-    if (n == 0) return LTPL_OK;
-    SimAllocs a;
-    int* d_idx = nullptr;
-    std::vector<int> idx(src_entry);
-    idx.insert(idx.end(), dst_entry.begin(), dst_entry.end());
-    int rc = sim_upload(f, a.p, idx.data(), idx.size(), &d_idx);
-    if (rc) return rc;
-    hipStream_t st = f->h->stream;
-    hipLaunchKernelGGL(k_fleet_sim_branch_react, dim3((unsigned)n), dim3(64), 0, st, S, T, own, (const int*)d_idx, (const int*)d_idx + n);
-    FLEET_TRY(f, hipGetLastError());
-    FLEET_TRY(f, hipStreamSynchronize(st));
-    return LTPL_OK;
-}
-
-// the pairs' entries go to the device in one allocation of the call ([src | dst]); the copy itself is one launch
-static int branch_launch(ltpl_fleet* f, BranchView S, BranchView T, const std::vector<int>& src_entry, const std::vector<int>& dst_entry, float* ms)
+// The device work of a snapshot and of a branch. The pairs' entries go to the device in the call's one allocation ([src | dst]), in front
+// of the first launch: a failing allocation changes nothing. Then the launches back to back on the handle's stream and one
+// synchronisation. A part kernel is launched only where the destination side T holds the part; a source side without it is the null
+// view its kernel knows. `ms`: device time of the bulk kernel alone
+static int branch_copy(ltpl_fleet* f, BranchSide S, BranchSide T, const std::vector<int>& src_entry, const std::vector<int>& dst_entry, float* ms)
 {
     const int n = (int)src_entry.size();
     if (ms) *ms = 0.0f;
     if (n == 0) return LTPL_OK;
-    if (!S.rec || !T.rec) S.rec = T.rec = nullptr;
-    const bool rows = S.gg && T.gg;
+    if (!S.v.rec || !T.v.rec) S.v.rec = T.v.rec = nullptr;
+    const bool rows = S.v.gg && T.v.gg;
     const size_t stride = f->D.stride, gg_stride = f->D.gg_stride;
     const int state_chunks = (int)((stride + BRANCH_CHUNK - 1) / BRANCH_CHUNK), gg_chunks = rows ? (int)((gg_stride + BRANCH_CHUNK - 1) / BRANCH_CHUNK) : 0;
     SimAllocs a;
@@ -296,6 +238,7 @@ static int branch_launch(ltpl_fleet* f, BranchView S, BranchView T, const std::v
     idx.insert(idx.end(), dst_entry.begin(), dst_entry.end());
     int rc = sim_upload(f, a.p, idx.data(), idx.size(), &d_idx);
     if (rc) return rc;
+    const int* d_src = d_idx; const int* d_dst = d_idx + n;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     struct Guard { hipEvent_t* a; hipEvent_t* b; ~Guard() { if (*a) (void)hipEventDestroy(*a); if (*b) (void)hipEventDestroy(*b); } } g{&e0, &e1};
     FLEET_TRY(f, hipEventCreate(&e0)); FLEET_TRY(f, hipEventCreate(&e1));
@@ -304,13 +247,16 @@ static int branch_launch(ltpl_fleet* f, BranchView S, BranchView T, const std::v
     FLEET_TRY(f, hipEventRecord(e0, st));
 #ifdef LTPL_EXPERIMENT
     if (getenv("LTPL_SIM_BRANCH_NT") && atoi(getenv("LTPL_SIM_BRANCH_NT")) != 0)        // (the store form: DESIGN 4.5c, measured with tools/sim_branch_rate.py)
-        hipLaunchKernelGGL(k_fleet_sim_branch<true>, grid, dim3(BRANCH_THREADS), 0, st, S, T, (const int*)d_idx, (const int*)d_idx + n, n, stride, gg_stride, state_chunks);
+        hipLaunchKernelGGL(k_fleet_sim_branch<true>, grid, dim3(BRANCH_THREADS), 0, st, S.v, T.v, d_src, d_dst, n, stride, gg_stride, state_chunks);
     else
 #endif
-    hipLaunchKernelGGL(k_fleet_sim_branch<false>, grid, dim3(BRANCH_THREADS), 0, st, S, T, (const int*)d_idx, (const int*)d_idx + n, n, stride, gg_stride, state_chunks);
+    hipLaunchKernelGGL(k_fleet_sim_branch<false>, grid, dim3(BRANCH_THREADS), 0, st, S.v, T.v, d_src, d_dst, n, stride, gg_stride, state_chunks);
     FLEET_TRY(f, hipGetLastError());
     FLEET_TRY(f, hipEventRecord(e1, st));
-    FLEET_TRY(f, hipEventSynchronize(e1));
+    auto part = [&](auto kernel, auto... views) { hipLaunchKernelGGL(kernel, dim3((unsigned)n), dim3(64), 0, st, views..., d_src, d_dst); };     // one wave64 per pair
+    if (T.stg.cnt) { part(k_fleet_sim_branch_staged, S.stg, T.stg); FLEET_TRY(f, hipGetLastError()); }
+    if (T.saf.rec) { part(k_fleet_sim_branch_safety, S.saf, T.saf); FLEET_TRY(f, hipGetLastError()); }
+    if (T.rct.rec) { part(k_fleet_sim_branch_react, S.rct, T.rct, T.own); FLEET_TRY(f, hipGetLastError()); }
     FLEET_TRY(f, hipStreamSynchronize(st));
     if (ms) FLEET_TRY(f, hipEventElapsedTime(ms, e0, e1));
     return LTPL_OK;
@@ -357,60 +303,58 @@ try {
     FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
     // everything new is allocated first; the slot keeps its previous snapshot unless every step succeeds
     SimAllocs a;
-    BranchView& v = q->v;
+    BranchView& v = q->side.v;
     uint64_t bytes = 0;
-    auto take = [&](auto** out, size_t n, const int* init = nullptr) {
-        using T = std::remove_pointer_t<std::remove_pointer_t<decltype(out)>>;
+    auto take = [&](auto*& out, size_t n, const int* init = nullptr) {
+        using T = std::remove_const_t<std::remove_pointer_t<std::remove_reference_t<decltype(out)>>>;
         void* p = nullptr;
         const size_t b = (n ? n : 1) * sizeof(T);
         if (hipMalloc(&p, b) != hipSuccess) { f->err = "fleet sim snapshot: hipMalloc of " + std::to_string(b) + " bytes failed"; return (int)LTPL_ERR_HIP; }
         a.p.push_back(p); bytes += b;
         if (init && hipMemcpy(p, init, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) { f->err = "fleet sim snapshot: upload failed"; return (int)LTPL_ERR_HIP; }
-        *out = static_cast<T*>(p);
+        out = static_cast<T*>(p);
         return (int)LTPL_OK;
     };
 #define SNAP_TAKE(...) do { if ((rc = take(__VA_ARGS__))) return rc; } while (0)
-    SNAP_TAKE(&v.state, f->D.stride * M);
-    if (f->d_gg) SNAP_TAKE(&v.gg, f->D.gg_stride * M);
-    SNAP_TAKE(&v.now, M); SNAP_TAKE(&v.sel, M); SNAP_TAKE(&v.started, M); SNAP_TAKE(&v.pos_x, M); SNAP_TAKE(&v.pos_y, M); SNAP_TAKE(&v.vel, M);
-    SNAP_TAKE(&v.theta, M); SNAP_TAKE(&v.live, M);
-    { int* o = nullptr; SNAP_TAKE(&o, M + 1, q->opp_off.data()); v.opp_off = o; }
-    SNAP_TAKE(&v.opp_s, n_opp); SNAP_TAKE(&v.opp_tic, n_opp);
-    if (s.tele.on) { SNAP_TAKE(&v.rec, M * LTPL_FLEET_SIM_TELE_DOUBLES); SNAP_TAKE(&v.grid_s, M); SNAP_TAKE(&v.prog, M); }
+    SNAP_TAKE(v.state, f->D.stride * M);
+    if (f->d_gg) SNAP_TAKE(v.gg, f->D.gg_stride * M);
+    SNAP_TAKE(v.now, M); SNAP_TAKE(v.sel, M); SNAP_TAKE(v.started, M); SNAP_TAKE(v.pos_x, M); SNAP_TAKE(v.pos_y, M); SNAP_TAKE(v.vel, M);
+    SNAP_TAKE(v.theta, M); SNAP_TAKE(v.live, M);
+    SNAP_TAKE(v.opp_off, M + 1, q->opp_off.data());
+    SNAP_TAKE(v.opp_s, n_opp); SNAP_TAKE(v.opp_tic, n_opp);
+    if (s.tele.on) { SNAP_TAKE(v.rec, M * LTPL_FLEET_SIM_TELE_DOUBLES); SNAP_TAKE(v.grid_s, M); SNAP_TAKE(v.prog, M); }
     if (s.veh.on) {                                     // (the snapshot's entries carry the source's model: its records are copied as they are)
         q->veh_model.resize(M);
         for (size_t k = 0; k < M; ++k) q->veh_model[k] = s.veh_model[(size_t)q->planners[k]];
-        SNAP_TAKE(&v.veh, M * LTPL_FLEET_SIM_VEH_DOUBLES);
-        { int* o = nullptr; SNAP_TAKE(&o, M, q->veh_model.data()); v.veh_model = o; }
+        SNAP_TAKE(v.veh, M * LTPL_FLEET_SIM_VEH_DOUBLES);
+        SNAP_TAKE(v.veh_model, M, q->veh_model.data());
     }
     if (s.trk.on) {                                     // (with the tracker off the snapshot holds what it held before)
         std::vector<int> tb(M + 1, 0);
         for (size_t k = 0; k < M; ++k) tb[k + 1] = tb[k] + s.trk_cap[(size_t)q->planners[k]];
-        SNAP_TAKE(&v.trk, (size_t)tb[M] * LTPL_FLEET_SIM_TRACK_DOUBLES); SNAP_TAKE(&v.trk_n, M); SNAP_TAKE(&v.trk_next, M);
-        { int* o = nullptr; SNAP_TAKE(&o, M + 1, tb.data()); v.trk_base = o; }
-        q->has_trk = true;
+        SNAP_TAKE(v.trk, (size_t)tb[M] * LTPL_FLEET_SIM_TRACK_DOUBLES); SNAP_TAKE(v.trk_n, M); SNAP_TAKE(v.trk_next, M);
+        SNAP_TAKE(v.trk_base, M + 1, tb.data());
     }
-    StagedView& sv = q->stg;
+    StagedView& sv = q->side.stg;
     if (s.sel.on) {                                     // (a list is state only for a selector; slots as the planners have them now)
         std::vector<int> sb(M + 1, 0);
         for (size_t k = 0; k < M; ++k) sb[k + 1] = sb[k] + s.slots[(size_t)q->planners[k]];
-        SNAP_TAKE(&sv.cnt, M);
-        for (double*& g : sv.g) SNAP_TAKE(&g, (size_t)sb[M]);
-        { int* o = nullptr; SNAP_TAKE(&o, M + 1, sb.data()); sv.base = o; }
+        SNAP_TAKE(sv.cnt, M);
+        for (double*& g : sv.g) SNAP_TAKE(g, (size_t)sb[M]);
+        SNAP_TAKE(sv.base, M + 1, sb.data());
     }
-    SafetyView& fv = q->saf;
-    if (s.saf.on) { SNAP_TAKE(&fv.rec, M * LTPL_FLEET_SIM_SAFETY_DOUBLES); SNAP_TAKE(&fv.inc, M * SAF_RING); }
-    ReactView& rv = q->rct;
-    if (s.react.on) { SNAP_TAKE(&rv.rec, M * LTPL_FLEET_SIM_REACT_DOUBLES); SNAP_TAKE(&rv.eff, n_opp); rv.opp_off = v.opp_off; }
+    SafetyView& fv = q->side.saf;
+    if (s.saf.on) { SNAP_TAKE(fv.rec, M * LTPL_FLEET_SIM_SAFETY_DOUBLES); SNAP_TAKE(fv.inc, M * SAF_RING); }
+    ReactView& rv = q->side.rct;
+    if (s.react.on) { SNAP_TAKE(rv.rec, M * LTPL_FLEET_SIM_REACT_DOUBLES); SNAP_TAKE(rv.eff, n_opp); rv.opp_off = v.opp_off; }
 #undef SNAP_TAKE
     std::vector<int> dst(M);
     for (size_t k = 0; k < M; ++k) dst[k] = (int)k;
-    if ((rc = branch_launch(f, branch_live_view(f), v, q->planners, dst, nullptr))) return rc;
-    if (sv.cnt && (rc = branch_launch_staged(f, s.staged_valid ? branch_live_staged(f) : StagedView{}, sv, q->planners, dst))) return rc;
-    if (fv.rec && (rc = branch_launch_safety(f, SafetyView{s.saf.dev.rec, s.saf.dev.inc}, fv, q->planners, dst))) return rc;
-    if (rv.rec && (rc = branch_launch_react(f, ReactView{s.react.dev.eff, s.react.dev.rec, s.sd.opp_off}, rv, nullptr, q->planners, dst))) return rc;
+    BranchSide live = branch_live_side(f);
+    if (!s.staged_valid) live.stg = StagedView{};       // (a staging that holds no list is a source without one)
+    if ((rc = branch_copy(f, live, q->side, q->planners, dst, nullptr))) return rc;
     q->allocs.swap(a.p);
-    q->has_tele = s.tele.on; q->tele_gen = s.tele_gen; q->bytes = bytes;
+    q->tele_gen = s.tele_gen; q->bytes = bytes;
     if (!s.snaps) s.snaps = new SimSnaps();
     SimSnap& old = s.snaps->slot[slot];
     sim_free_list(old.allocs);
@@ -497,32 +441,24 @@ try {
     }
     if ((rc = fleet_enter(f))) return rc;
     FLEET_TRY(f, hipStreamSynchronize(f->h->stream));
-    BranchView S = q ? q->v : branch_live_view(f);
-    if (s.trk.on && S.trk_n && !se.empty()) {              // the sources' track counts against the destinations' capacities
+    BranchSide S = q ? q->side : branch_live_side(f);
+    if (s.trk.on && S.v.trk_n && !se.empty()) {              // the sources' track counts against the destinations' capacities
         const size_t ns = q ? q->planners.size() : (size_t)N;
         std::vector<int> nt(ns);
-        FLEET_TRY(f, hipMemcpy(nt.data(), S.trk_n, sizeof(int) * ns, hipMemcpyDeviceToHost));
+        FLEET_TRY(f, hipMemcpy(nt.data(), S.v.trk_n, sizeof(int) * ns, hipMemcpyDeviceToHost));
         for (size_t k = 0; k < se.size(); ++k)
             if (nt[(size_t)se[k]] > s.trk_cap[(size_t)de[k]])
                 return bad("the source of destination " + std::to_string(de[k]) + " holds " + std::to_string(nt[(size_t)se[k]]) + " tracks, the destination's table " +
                            std::to_string(s.trk_cap[(size_t)de[k]]));
     }
-    if (q && !(q->has_tele && s.tele.on && q->tele_gen == s.tele_gen)) S.rec = nullptr;      // (a telemetry set since then started its records anew)
-    if ((rc = branch_launch(f, S, branch_live_view(f), se, de, ms))) return rc;
-    if (s.sel.on) {                    // the staged lists: what the selector reads at the head of the next tick
-        if (!s.staged_valid) {          // (no list yet, or a fresh staging: the other planners keep the empty lists a run would start from)
-            FLEET_TRY(f, hipMemset(s.sd.cnt, 0, sizeof(int) * (size_t)N));
-            s.staged_valid = true;
-        }
-        if ((rc = branch_launch_staged(f, q ? q->stg : branch_live_staged(f), branch_live_staged(f), se, de))) return rc;
+    if (q && q->tele_gen != s.tele_gen) S.v.rec = nullptr;      // (a telemetry set since then started its records anew)
+    // no list yet, or a fresh staging: every planner gets the empty list a run would start from, the destinations' are then written over
+    // it. (No change a caller can see, should the copy fail: nothing reads cnt while the flag is down, and a run sets both the same way.)
+    if (s.sel.on && !s.staged_valid) {
+        FLEET_TRY(f, hipMemset(s.sd.cnt, 0, sizeof(int) * (size_t)N));
+        s.staged_valid = true;
     }
-    // the safety monitor's records and rings: what the tick writes
-    if (s.saf.on && (rc = branch_launch_safety(f, q ? q->saf : SafetyView{s.saf.dev.rec, s.saf.dev.inc}, SafetyView{s.saf.dev.rec, s.saf.dev.inc}, se, de))) return rc;
-    // the reactive opponents' effective scales and records: what the tick writes
-    if (s.react.on) {
-        const ReactView live{s.react.dev.eff, s.react.dev.rec, s.sd.opp_off};
-        if ((rc = branch_launch_react(f, q ? q->rct : live, live, s.sd.opp_scale, se, de))) return rc;
-    }
+    if ((rc = branch_copy(f, S, branch_live_side(f), se, de, ms))) return rc;
     f->cur.has_paths = false;           // (as after a run: a per-call calc_vel_profile needs its own calc_paths first)
     return LTPL_OK;
 } LTPL_ABI_CATCH(abi_err_of(f))

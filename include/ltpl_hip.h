@@ -938,7 +938,8 @@ int ltpl_fleet_sim_record_get(ltpl_fleet* fleet, int32_t tick, int32_t slot, ltp
  *   ltpl_fleet_friction* do not.
  * - All four calls need ltpl_fleet_sim_setup first, may come before or after runs, check every argument before the first HIP call,
  *   synchronise the handle's stream on entry and return after the copy has finished. A failing allocation returns LTPL_ERR_HIP and
- *   changes nothing. After a branch a per-call ltpl_fleet_calc_vel_profile needs its own ltpl_fleet_calc_paths first, as after a run;
+ *   changes nothing. With models set (a selector, a safety monitor, reactive opponents) a branch is still one allocation, in front of
+ *   up to four launches. After a branch a per-call ltpl_fleet_calc_vel_profile needs its own ltpl_fleet_calc_paths first, as after a run;
  *   ltpl_fleet_get_paths / _get_trajectories read the device at every call and so return the branched state.
  * ------------------------------------------------------------------------------------------------------------------ */
 #define LTPL_FLEET_SIM_SNAPSHOTS 8   /* snapshot slots of a fleet */

@@ -523,3 +523,86 @@ def test_snapshots_belong_to_their_fleet(hip, table, classes, c2):
     a.close()
     assert b.sim_snapshot_info(0) is None
     b.close()
+
+
+# ---- 10. every part in one call -------------------------------------------------------------------------------------------------------------
+def parts_of(fleet, off, p):
+    """What the models hold of planner ``p`` and a branch carries: telemetry, vehicle, safety and react records, the incident ring, the
+    effective scales and the tracker's rows -- and the selector's ordered list, which the next tick computes from the carried list."""
+    tele = fleet.sim_telemetry_read()
+    _, tabs, cnt = fleet.sim_tracker_read(planners=[p], raw=True)
+    (saf, ring), (rct, eff) = fleet.sim_safety_read(raw=True), fleet.sim_react_read(raw=True)
+    return dict(tele={k: np.array(v[p]) for k, v in tele.items() if k != "track_length"}, veh=fleet.sim_vehicle_read(raw=True)[p].copy(),
+                n_tracks=int(cnt[0]), tracks=tabs[0, :cnt[0]].copy(), order=fleet.sim_selector_read()[1][p].copy(), safety=saf[p].copy(),
+                ring=ring[p].copy(), react=rct[p].copy(), eff=eff[off[p]:off[p + 1]].copy())
+
+
+def test_every_part_in_one_call(hip, table, classes):
+    """Telemetry, vehicle model, tracker, selector, safety monitor and reactive opponents set together: one ``sim_branch`` moves all of it.
+    Planners (0, 1) and (2, 3) are twins by configuration -- one and three opponents, so offsets and bases of source and destination differ
+    -- and not by state: the second of a pair starts elsewhere, its opponents further ahead. Leg 1: behind the branch a twin IS its source,
+    in the trace, in ``sim_state`` and in every model's records, tick by tick. Leg 2: a snapshot taken with selector, monitor and reactive
+    model off leaves their start states behind a restore, whatever the three had written since."""
+    from graphbasedlocaltrajectoryplanner_amd import sim
+    poses, further = [300.0, 700.0, 1100.0, 1500.0], [0.0, 9.0, 0.0, 7.0]
+    # (opponents that have someone to react to, so that scales and reactive records are state: the lone one comes up behind the ego, within
+    #  the model's sight; of the three the faster one closes in on the slower)
+    ahead = [[(-120.0, 0.35, 5.0)]] * 2 + [[(45.0, 0.40, 5.0), (60.0, 0.30, 5.0), (110.0, 0.35, 5.0)]] * 2
+    starts = [elsewhere(table, s) for s in poses]
+    entries = [dict(classes["one"]["entry"], pos_est=starts[p][0], opponents=[(poses[p] + d + further[p], scale, length) for d, scale, length in ahead[p]])
+               for p in range(4)]
+    scales = np.array([q[1] for e in entries for q in e["opponents"]])
+    off = opp_offsets(entries)
+    fleet = build(hip, table, entries, starts, [sl.C2_VEL] * 4)
+
+    def set_three():
+        fleet.sim_selector()
+        fleet.sim_safety()
+        fleet.sim_react()
+    fleet.sim_telemetry()
+    fleet.sim_vehicle()
+    fleet.sim_tracker()
+    set_three()
+    gd.run_one(fleet, 20)
+    assert healthy(fleet)
+    pairs = [(0, 1), (2, 3)]
+    for s, d in pairs:
+        a, b = parts_of(fleet, off, s), parts_of(fleet, off, d)
+        assert a["n_tracks"] > 0 and not same(state_of(fleet, off, s), state_of(fleet, off, d))
+        for key in ("tele", "veh", "tracks", "safety", "react"):
+            assert not same(a[key], b[key]), (s, d, key)
+    assert np.any(fleet.sim_react_read()[1][off[2]:off[3]] != scales[off[2]:off[3]])              # (effective scales that are state)
+    assert fleet.sim_branch([0, 2], [1, 3]) >= 0.0
+    for k in range(11):                                                                           # behind the branch, then behind each of 10 ticks
+        for s, d in pairs:
+            a, b = parts_of(fleet, off, s), parts_of(fleet, off, d)
+            for key in a:
+                assert key == "order" and k == 0 or same(a[key], b[key]), "%d ticks behind the branch: %s of planner %d is not planner %d's" % (k, key, d, s)
+            assert same(state_of(fleet, off, d), state_of(fleet, off, s)), (k, s, d)
+        if k < 10:
+            tr = gd.run_one(fleet, 1)
+            for s, d in pairs:
+                same_rows(tr, d, tr, s, "tick %d behind the branch" % k)
+    assert healthy(fleet)
+
+    # leg 2: a source without state
+    fleet.sim_selector(None)
+    fleet.sim_safety(None)
+    fleet.sim_react(None)
+    fleet.sim_snapshot(0)
+    set_three()
+    gd.run_one(fleet, 2)
+    fleet.sim_selector()                                                                          # (fresh statistics: the list stays)
+    gd.run_one(fleet, 1)
+    assert np.all(fleet.sim_selector_read()[0]["clear_min"] < np.inf)                             # objects were scored behind a fresh selector
+    assert not same(fleet.sim_safety_read(raw=True)[0], sim.safety_start(4)[0]) and not same(fleet.sim_react_read(raw=True)[0], sim.react_start(4))
+    fleet.sim_restore(0)
+    (saf, ring), (rct, eff) = fleet.sim_safety_read(raw=True), fleet.sim_react_read(raw=True)
+    assert same(saf, sim.safety_start(4)[0]) and same(ring, sim.safety_start(4)[1]) and same(rct, sim.react_start(4))
+    assert same(eff, scales)
+    fleet.sim_selector()
+    gd.run_one(fleet, 1)
+    d = fleet.sim_selector_read()[0]
+    assert np.all(d["ticks"] == 1) and np.all(d["clear_min"] == np.inf)                           # the restored lists are empty
+    assert healthy(fleet)
+    fleet.close()

@@ -18,6 +18,7 @@ def test_snapshot_and_branch_entry_points_check_their_arguments_without_a_device
                        stderr=subprocess.STDOUT, universal_newlines=True, timeout=600)
     assert p.returncode == 0 and "sim branch args OK" in p.stdout, p.stdout[-3000:]
     assert "launches per tick" in p.stdout and p.stdout.count("previous snapshot kept") == 2, p.stdout[-3000:]
+    assert p.stdout.count("each part kernel once, 1 allocation in front of them") == 2 and "nothing launched, the slot as it was" in p.stdout, p.stdout[-3000:]
 
 
 def test_python_binding_declares_the_four_entry_points():

@@ -8,7 +8,10 @@ messages, what ``info`` reports and the number of kernel launches:
     n_pairs == 0, which returns LTPL_OK;
   - a pair src == dst with the live fleet as source is accepted (and skipped); ltpl_fleet_sim_setup empties every slot;
   - an allocation failing at each allocation of ltpl_fleet_sim_snapshot leaves the slot's previous content and ``info`` unchanged;
-  - a tick of ltpl_fleet_sim_run launches the same kernels with and without snapshots held; a snapshot and a branch are one launch each."""
+  - a tick of ltpl_fleet_sim_run launches the same kernels with and without snapshots held; a snapshot and a branch are one launch each;
+  - with telemetry, the vehicle model, a tracker, a selector, a safety monitor and reactive opponents set together a branch (from the live
+    fleet and from a snapshot) is four launches, each part kernel once, behind ONE allocation: failing, that allocation leaves nothing
+    launched; a snapshot that fails at any of its allocations launches nothing and leaves the slot as it was."""
 import ctypes
 
 import numpy as np
@@ -160,5 +163,78 @@ lib.fakehip_fail_malloc_after(1)
 n_launch, rc = launches(lambda: branch(-1, [0], [1]))
 lib.fakehip_fail_malloc_after(0)
 assert rc[0] == 3 and "hipMalloc" in rc[1] and n_launch == 0, (rc, n_launch)
+
+# telemetry, the vehicle model, a tracker, a selector, a safety monitor and reactive opponents set together: a branch is ONE allocation
+# (the pairs' entries, in front of the first launch) and four launches, each part kernel once; a failing call launches nothing
+BULK = b"_Z18k_fleet_sim_branchILb"                                                       # (either store form; 18: not the part kernels)
+PARTS = (b"_Z25k_fleet_sim_branch_staged", b"_Z25k_fleet_sim_branch_safety", b"_Z24k_fleet_sim_branch_react")
+
+
+def all_models():
+    fresh()
+    fleet.sim_telemetry()
+    fleet.sim_vehicle()
+    fleet.sim_tracker()
+    fleet.sim_selector()
+    fleet.sim_safety()
+    fleet.sim_react()
+    fleet.sim_run(1, trace=False)                                                         # (the staging holds a list)
+
+
+def by_kernel(fn):
+    """(launches during ``fn``, those of the bulk kernel, those of each part kernel, what ``fn`` returned)"""
+    before = [lib.fakehip_launches_of(k) for k in (BULK,) + PARTS]
+    n, out = launches(fn)
+    return n, [lib.fakehip_launches_of(k) - b for k, b in zip((BULK,) + PARTS, before)], out
+
+
+def armed(k, fn):
+    """``fn`` with the k-th allocation from now on failing: (launches, what ``fn`` returned, the failure is still pending afterwards)"""
+    lib.fakehip_fail_malloc_after(k)
+    try:
+        n, out = launches(fn)
+    finally:
+        p = ctypes.c_void_p()
+        pending = lib.hipMalloc(ctypes.byref(p), 8) != 0
+        if not pending:
+            lib.hipFree(p)
+        lib.fakehip_fail_malloc_after(0)
+    return n, out, pending
+
+
+all_models()
+assert snapshot(3)[0] == 0
+for slot, src, dst, what in ((-1, [0, 4], [1, 5], "the live fleet"), (3, [0, 4, 3], [1, 5, 3], "a snapshot")):
+    n_launch, per_kernel, rc = by_kernel(lambda: branch(slot, src, dst))
+    assert rc[0] == 0 and n_launch == 4 and per_kernel == [1, 1, 1, 1], (what, rc, n_launch, per_kernel)
+    n_launch, rc, _ = armed(1, lambda: branch(slot, src, dst))
+    assert rc[0] == 3 and "hipMalloc" in rc[1] and n_launch == 0, (what, rc, n_launch)
+    n_launch, rc, pending = armed(2, lambda: branch(slot, src, dst))
+    assert rc[0] == 0 and n_launch == 4 and pending, (what, rc, n_launch, pending)      # the call allocates once
+    print("every model set, a branch from %s: 4 launches, each part kernel once, 1 allocation in front of them" % what)
+
+
+def slot_1_taken_all():
+    all_models()
+    assert snapshot(1, [5, 0])[0] == 0
+    return info(1)[:3], lib.fakehip_launch_count()
+
+
+def slot_1_kept_all(k, ctx):
+    held, count = ctx
+    assert lib.fakehip_launch_count() == count, (k, "a failing snapshot launched")
+    assert info(1)[:3] == held and branch(1, [5], [4])[0] == 0, (k, info(1))
+
+
+def slot_1_new_all():
+    assert info(1)[1] == [1, 2, 3]
+
+
+failures = common.alloc_sweep("ltpl_fleet_sim_snapshot", lambda: snapshot(1, [1, 2, 3]), 40, slot_1_kept_all, before=slot_1_taken_all,
+                              after_success=slot_1_new_all)
+assert failures >= 16, failures
+n_launch, per_kernel, rc = by_kernel(lambda: snapshot(1, [1, 2, 3]))
+assert rc[0] == 0 and n_launch == 4 and per_kernel == [1, 1, 1, 1], (rc, n_launch, per_kernel)
+print("every model set: allocation failure at each of the %d allocations of ltpl_fleet_sim_snapshot: nothing launched, the slot as it was" % failures)
 print("launches per tick: %d with and without snapshots; a snapshot and a branch: 1 launch each" % plain)
 common.finish("sim branch args OK")
